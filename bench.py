@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- SG-MCMC transitions/s of the HIP path on synthetic volumes (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 256] [--loss gmm|ssd] [--decomp slab|chains]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 256] [--loss gmm|ssd] [--decomp slab|chains] [--dump-outputs DIR]
 
 A "step" is one full `_SGLD_transition` (noise + Sobolev, 12-step scaling and squaring, warp, LCC/GMM data term with
 virtual decimation, regulariser, backward, SGLD update) over one synthetic fixed/moving pair resident in HBM, with
@@ -189,6 +189,40 @@ def side_run(N, loss, init, amp, steps, warmup, dev, timed_reps=0, chains=1, sig
     return out
 
 
+DUMP_FULL_MAX = 1 << 23     # values of a field written whole (32 MB in float32)
+DUMP_SAMPLE = 1 << 21       # values of a larger field written as a seeded sample (+ their flat indices: 24 MB together)
+
+
+def dump_outputs(out_dir, eng, v, rank):
+    """`--dump-outputs`: what the timed path hands its caller after its last transition -- the velocity field it updated in place,
+    the per-chain scalars and the mixture / regulariser state -- as float32 / float64 .npy files, so that two builds run with the
+    same arguments can be compared output for output.  Collective in slab mode (the field is gathered); rank 0 writes."""
+    import numpy as np
+    import torch
+    full = eng.gather(v) if hasattr(eng, 'gather') else v.detach().cpu()   # flushes / syncs; the slab engine's owned planes, assembled
+    sc, st = eng.scalars(), eng.state()
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(x, dtype=np.float64) for k, x in sc.items()}
+    if eng.cfg.data_loss == 'GMM':
+        K = eng.cfg.gmm_components
+        arrays['gmm_log_std'] = np.asarray(st.gmm_log_std[:K], dtype=np.float32)
+        arrays['gmm_logits'] = np.asarray(st.gmm_logits[:K], dtype=np.float32)
+    arrays['reg_param'] = np.asarray(st.reg_param[:], dtype=np.float64)
+    flat = full.reshape(-1).float()
+    if flat.numel() <= DUMP_FULL_MAX:
+        arrays['velocity'] = full.float().numpy()
+    else:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.unique(torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g))   # sorted, fixed for a given field size
+        arrays['velocity_sample'] = flat[idx].numpy()
+        arrays['velocity_sample_index'] = idx.numpy().astype(np.float64)   # (exact: indices < 2^53)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+    print(f'[bench] outputs of the last timed transition -> {out_dir}: {", ".join(sorted(arrays))}', file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -221,6 +255,9 @@ def main():
     ap.add_argument('--cpu-size', type=int, default=256, help='edge of the CPU-baseline volume (capped at --size); 256: one transition takes ~25 s on 16 cores')
     ap.add_argument('--cpu-reps', type=int, default=1)
     ap.add_argument('--cpu-reps-128', type=int, default=5, help='timed 128^3 transitions of the CPU oracle (after 3 warm-up) reported next to the bench-size one; 0 = skip')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed transition left for its caller (velocity field, scalars, '
+                         'mixture state) as DIR/<name>.npy, float32 / float64, at most 64 MB; fields above 8 M values as a fixed, seeded sample')
     args = ap.parse_args()
 
     # no launcher (or a stale single-process WORLD_SIZE = 1 in the environment): start the ranks ourselves
@@ -418,6 +455,8 @@ def main():
     elapsed_here = time.perf_counter() - t0
     elapsed = par.max_over_ranks(elapsed_here)
     assert bool(torch.isfinite(v).all()), 'chain diverged'
+    if args.dump_outputs:   # before anything below moves the chain on
+        dump_outputs(args.dump_outputs, eng, v, rank)
     slab_diag = None
     if slab:
         slab_status = eng.status()   # mispredictions are reported in the output line (`slab`), not fatal: the chain was repaired
