@@ -31,6 +31,7 @@ extern "C" {
 #define IRS_MAX_COMPONENTS 8
 #define IRS_MAX_CHAINS 8
 #define IRS_MAX_HALF_WIDTH 4 /* Sobolev / LCC half widths up to 4 */
+#define IRS_MAX_LABELS 64    /* labels of one surface-distance call */
 
 enum { IRS_DATA_GMM_LCC = 0, IRS_DATA_SSD = 1 };
 enum { IRS_REG_L2 = 0, IRS_REG_LOGNORMAL = 1, IRS_REG_STUDENT = 2, IRS_REG_LOGNORMAL_L2 = 3 };
@@ -109,6 +110,26 @@ int irs_gradient_operator(const float* v, float* nabla, int transformation, int 
  * log_det: (C,1,D,H,W) or NULL; nan_count: C int64 on the device (zeroed by the call). */
 int irs_log_det_jacobian(const float* transformation, float* log_det, long long* nan_count, int C, int D, int H, int W,
                          void* stream);
+
+/* Average surface distance of label contours, the ASD half of calc_metrics (utils/util.py:152-206: sitk.LabelContour +
+ * HausdorffDistanceImageFilter.GetAverageHausdorffDistance per chain and label), with an exact Euclidean distance transform.
+ * seg_fixed: (Cf,1,D,H,W) int16, Cf in {1, C}; seg_moving: (C,1,D,H,W) int16; labels: n_labels (<= IRS_MAX_LABELS) HOST ints.
+ * Pair p = c * n_labels + l.  Two steps with one read-back in between:
+ *  1. irs_label_boxes: boxes (device, n_pairs x 6 int32) = {zmin, ymin, xmin, zmax, ymax, xmax} (inclusive) of the voxels
+ *     labelled labels[l] in seg_fixed[c] or seg_moving[c]; zmin > zmax when there are none.
+ *  2. the caller copies the boxes to the host; irs_surface_distance_workspace sizes the workspace from that copy;
+ *     irs_label_surface_distance takes it (HOST pointer, validated) and writes, per pair, counts[2p] = |A|, counts[2p+1] = |B|
+ *     (A, B: contours of the label in seg_fixed / seg_moving) and sums[2p] = sum over A of the distance to B, sums[2p+1] = sum
+ *     over B of the distance to A, in spacing units (spacing[0] scales W, [1] H, [2] D).  ASD = (sums[2p] / |A| +
+ *     sums[2p+1] / |B|) / 2, infinite when |A| or |B| is 0.  counts / sums: device.  Deterministic (no float atomics).
+ *     Blocking only for the upload of a small per-pair table into the head of the workspace; the kernels run asynchronously. */
+int irs_label_boxes(const int16_t* seg_fixed, int Cf, const int16_t* seg_moving, const int32_t* labels, int n_labels,
+                    int32_t* boxes, int C, int D, int H, int W, void* stream);
+int irs_surface_distance_workspace(const int32_t* boxes, int n_pairs, int D, int H, int W, size_t* bytes);
+int irs_label_surface_distance(const int16_t* seg_fixed, int Cf, const int16_t* seg_moving, const int32_t* labels,
+                               int n_labels, const float* spacing, const int32_t* boxes, void* workspace,
+                               size_t workspace_bytes, long long* counts, double* sums, int C, int D, int H, int W,
+                               void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * fused transition (Trainer._SGLD_transition, trainer/trainer.py:291-356)

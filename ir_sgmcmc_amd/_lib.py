@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get('IRS_LIB') or os.path.join(_HERE, 'csrc', 'libirsgmcmc
 IRS_MAX_COMPONENTS = 8
 IRS_MAX_CHAINS = 8
 IRS_MAX_HALF_WIDTH = 4
+IRS_MAX_LABELS = 64
 IRS_DATA_GMM_LCC, IRS_DATA_SSD = 0, 1
 IRS_REG_L2, IRS_REG_LOGNORMAL, IRS_REG_STUDENT, IRS_REG_LOGNORMAL_L2 = 0, 1, 2, 3
 
@@ -127,6 +128,10 @@ SIGNATURES = {
     'irs_reduce_scratch_doubles': [],
     'irs_gradient_operator': [_P, _P, _I, _I, _I, _I, _I, _P],
     'irs_log_det_jacobian': [_P, _P, _P, _I, _I, _I, _I, _P],
+    'irs_label_boxes': [_P, _I, _P, _I32P, _I, _P, _I, _I, _I, _I, _P],
+    'irs_surface_distance_workspace': [_I32P, _I, _I, _I, _I, C.POINTER(C.c_size_t)],
+    'irs_label_surface_distance': [_P, _I, _P, _I32P, _I, C.POINTER(C.c_float), _I32P, _P, C.c_size_t, _P, _P, _I, _I, _I, _I,
+                                   _P],
     'irs_create': [C.POINTER(IrsConfig), C.POINTER(_P)],
     'irs_destroy': [_P],
     'irs_workspace_bytes': [_P],

@@ -6,8 +6,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <mutex>
 #include <new>
+#include <vector>
 
 #include "comm.h"
 #include "ctx.h"
@@ -469,6 +471,155 @@ int irs_log_det_jacobian(const float* transformation, float* log_det, long long*
                          void* stream) {
     if (!transformation || !nan_count || !dims_ok(C, D, H, W)) return fail("irs_log_det_jacobian: bad arguments");
     launch_log_det_jacobian(transformation, log_det, nan_count, C, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"
+
+// ================================================================================================
+// average surface distance (metric_kernels.hip)
+// ================================================================================================
+namespace {
+
+constexpr size_t kSurfScratchBudget = (size_t)256 << 20;  // envelope slots of lines longer than kSurfLdsLine
+constexpr int kSurfMaxSlots = 4096;
+
+size_t surf_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// the per-pair table, the workspace layout and the launch shapes, from the host copy of the boxes
+struct SurfLayout {
+    std::vector<SurfPair> plan;
+    int64_t tasks[3] = {0, 0, 0};
+    int line[3] = {0, 0, 0};
+    int lanes = 1;
+    int slots[3] = {0, 0, 0};
+    size_t plan_off = 0, partials_off = 0, memb_off = 0, ga_off = 0, gb_off = 0, env_off[3] = {0, 0, 0}, bytes = 0;
+};
+
+int surface_layout(const int32_t* boxes, int P, int D, int H, int W, SurfLayout* out) {
+    if (!boxes || P < 1 || !dims_ok(1, D, H, W)) return fail("irs_surface_distance: bad boxes / dims");
+    SurfLayout& s = *out;
+    s.plan.assign((size_t)P + 1, SurfPair{});
+    const int dims[3] = {D, H, W};
+    int64_t vox = 0;
+    int nx_max = 1;
+    for (int p = 0; p < P; ++p) {
+        const int32_t* b = boxes + 6 * (int64_t)p;
+        SurfPair& q = s.plan[p];
+        q.vox = vox;
+        q.tw = s.tasks[0];
+        q.th = s.tasks[1];
+        q.td = s.tasks[2];
+        if (b[0] > b[3]) continue;  // label in neither map
+        for (int a = 0; a < 3; ++a)
+            if (b[a] < 0 || b[a] > b[3 + a] || b[3 + a] >= dims[a]) return fail("irs_surface_distance: box %d out of the volume", p);
+        q.z0 = b[0], q.y0 = b[1], q.x0 = b[2];
+        q.nz = b[3] - b[0] + 1, q.ny = b[4] - b[1] + 1, q.nx = b[5] - b[2] + 1;
+        const int chunks = (q.nx + kWave - 1) / kWave;
+        vox += (int64_t)q.nz * q.ny * q.nx;
+        s.tasks[0] += (int64_t)q.nz * q.ny;
+        s.tasks[1] += (int64_t)q.nz * chunks;
+        s.tasks[2] += (int64_t)q.ny * chunks;
+        s.line[1] = std::max(s.line[1], q.ny);
+        s.line[2] = std::max(s.line[2], q.nz);
+        nx_max = std::max(nx_max, q.nx);
+    }
+    SurfPair& end = s.plan[P];
+    end.vox = vox;
+    end.tw = s.tasks[0];
+    end.th = s.tasks[1];
+    end.td = s.tasks[2];
+    s.lanes = std::min(nx_max, kWave);  // a lane at or above nx_max never holds an envelope
+    size_t off = surf_align(sizeof(SurfPair) * s.plan.size());
+    s.partials_off = off;
+    off = surf_align(off + sizeof(double) * 4 * (size_t)s.tasks[2]);
+    s.memb_off = off;
+    off = surf_align(off + (size_t)vox);
+    s.ga_off = off;
+    off = surf_align(off + sizeof(float) * (size_t)vox);
+    s.gb_off = off;
+    off = surf_align(off + sizeof(float) * (size_t)vox);
+    for (int pass = 1; pass <= 2; ++pass) {
+        if (s.line[pass] <= kSurfLdsLine || s.tasks[pass] == 0) continue;
+        const size_t slot = sizeof(float) * 3 * (size_t)s.line[pass] * s.lanes;
+        s.slots[pass] = (int)std::max<int64_t>(1, std::min<int64_t>({s.tasks[pass], (int64_t)(kSurfScratchBudget / slot), kSurfMaxSlots}));
+        s.env_off[pass] = off;
+        off = surf_align(off + slot * s.slots[pass]);
+    }
+    s.bytes = off;
+    return 0;
+}
+
+bool labels_ok(const int32_t* labels, int n) {
+    if (!labels || n < 1 || n > IRS_MAX_LABELS) return false;
+    for (int i = 0; i < n; ++i)
+        if (labels[i] < INT16_MIN || labels[i] > INT16_MAX) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int irs_label_boxes(const int16_t* seg_fixed, int Cf, const int16_t* seg_moving, const int32_t* labels, int n_labels,
+                    int32_t* boxes, int C, int D, int H, int W, void* stream) {
+    if (!seg_fixed || !seg_moving || !boxes || !dims_ok(C, D, H, W) || C > IRS_MAX_CHAINS || (Cf != 1 && Cf != C))
+        return fail("irs_label_boxes: bad arguments");
+    if (!labels_ok(labels, n_labels)) return fail("irs_label_boxes: 1..%d labels in the int16 range", IRS_MAX_LABELS);
+    SurfLabels lab = {};
+    memcpy(lab.v, labels, sizeof(int32_t) * n_labels);
+    const Vol vol = make_vol(D, H, W);
+    launch_surface_boxes(seg_fixed, Cf == 1 ? 0 : vol.V, seg_moving, lab, n_labels, boxes, C, vol, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_surface_distance_workspace(const int32_t* boxes, int n_pairs, int D, int H, int W, size_t* bytes) {
+    if (!bytes) return fail("irs_surface_distance_workspace: null argument");
+    SurfLayout s;
+    if (surface_layout(boxes, n_pairs, D, H, W, &s)) return 1;
+    *bytes = s.bytes;
+    return 0;
+}
+
+int irs_label_surface_distance(const int16_t* seg_fixed, int Cf, const int16_t* seg_moving, const int32_t* labels,
+                               int n_labels, const float* spacing, const int32_t* boxes, void* workspace,
+                               size_t workspace_bytes, long long* counts, double* sums, int C, int D, int H, int W,
+                               void* stream) {
+    if (!seg_fixed || !seg_moving || !spacing || !workspace || !counts || !sums || !dims_ok(C, D, H, W) || C > IRS_MAX_CHAINS ||
+        (Cf != 1 && Cf != C))
+        return fail("irs_label_surface_distance: bad arguments");
+    if (!labels_ok(labels, n_labels)) return fail("irs_label_surface_distance: 1..%d labels in the int16 range", IRS_MAX_LABELS);
+    for (int a = 0; a < 3; ++a)
+        if (!(spacing[a] > 0.0f) || !isfinite(spacing[a])) return fail("irs_label_surface_distance: spacing must be positive");
+    SurfLayout s;
+    if (surface_layout(boxes, C * n_labels, D, H, W, &s)) return 1;
+    if (workspace_bytes < s.bytes)
+        return fail("irs_label_surface_distance: workspace of %zu bytes, %zu needed (irs_surface_distance_workspace)", workspace_bytes, s.bytes);
+    const hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = (uint8_t*)workspace;
+    // the table is small; the copy is waited for so that the host vector may go (its source is pageable memory)
+    HIP_TRY(hipMemcpyAsync(ws, s.plan.data(), sizeof(SurfPair) * s.plan.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    SurfPassArgs a = {};
+    a.plan = (const SurfPair*)ws;
+    a.P = C * n_labels;
+    for (int pass = 0; pass < 3; ++pass) {
+        a.tasks[pass] = s.tasks[pass];
+        a.line[pass] = s.line[pass];
+        a.env_scratch[pass] = s.slots[pass] ? (float*)(ws + s.env_off[pass]) : nullptr;
+        a.env_slots[pass] = s.slots[pass];
+    }
+    a.lanes = s.lanes;
+    a.memb = ws + s.memb_off;
+    a.gA = (float*)(ws + s.ga_off);
+    a.gB = (float*)(ws + s.gb_off);
+    a.partials = (double*)(ws + s.partials_off);
+    SurfLabels lab = {};
+    memcpy(lab.v, labels, sizeof(int32_t) * n_labels);
+    const Vol vol = make_vol(D, H, W);
+    launch_surface_distance(seg_fixed, Cf == 1 ? 0 : vol.V, seg_moving, lab, n_labels, spacing, a, counts, sums, vol, st);
     LAUNCH_CHECK();
     return 0;
 }

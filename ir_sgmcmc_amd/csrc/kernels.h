@@ -115,6 +115,40 @@ void launch_sgld_update_march(float* v, const float* sigma, const float* g_d0, c
 int stats_blocks(Vol vol);
 int energy_blocks(Vol vol);
 
+// ---- metric_kernels.hip: average surface distance of label contours (utils/util.py:152-206)
+struct SurfLabels {
+    int32_t v[IRS_MAX_LABELS];
+};
+// one (chain, label) pair: its box [z0, z0 + nz) x [y0, y0 + ny) x [x0, x0 + nx), where its voxels start in the box arrays,
+// and its first task in each pass.  The table has n_pairs + 1 entries; the last one holds the totals.
+struct SurfPair {
+    int32_t z0, y0, x0, nz, ny, nx;
+    int64_t vox;
+    int64_t tw, th, td;
+};
+constexpr int kSurfLdsLine = 64;  // longest line whose lower envelope stays in LDS (64 entries x 64 lanes x 12 B = 48 KB)
+void launch_surface_boxes(const int16_t* fixed, int64_t f_stride, const int16_t* moving, const SurfLabels& lab, int L,
+                          int32_t* boxes, int C, Vol vol, hipStream_t st);
+// pass W (contours + 1-D distances), passes H and D (lower envelopes; D ends in the reduction) and the per-pair reduction.
+// env_scratch: NULL -> the envelopes of a pass live in LDS (its longest line <= kSurfLdsLine); else env_slots slots of
+// 3 * line * lanes floats each.
+struct SurfPassArgs {
+    const SurfPair* plan;
+    int P;
+    int64_t tasks[3];     // W, H, D
+    int line[3];          // longest line of passes H and D (index 1, 2)
+    int lanes;            // lanes of an envelope slot in global memory (<= 64)
+    float* env_scratch[3];
+    int env_slots[3];
+    uint8_t* memb;
+    float* gA;
+    float* gB;
+    double* partials;     // 4 per task of pass D: nA, nB, sum A->B, sum B->A
+};
+void launch_surface_distance(const int16_t* fixed, int64_t f_stride, const int16_t* moving, const SurfLabels& lab, int L,
+                             const float spacing[3], const SurfPassArgs& a, long long* counts, double* sums, Vol vol,
+                             hipStream_t st);
+
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h
 }  // namespace irs

@@ -203,3 +203,38 @@ def log_det_jacobian(transformation):
     L.check(lib.irs_log_det_jacobian(L.dev_ptr(transformation, torch.float32), L.dev_ptr(ld), L.dev_ptr(cnt), Cn, D, H, W,
                                      L.stream_ptr()))
     return cnt, ld
+
+
+def label_surface_distance(seg_fixed, seg_moving, labels, spacing):
+    """Average surface distance per chain and label, the ASD half of calc_metrics (utils/util.py:152-206): contours as
+    sitk.LabelContour draws them (face neighbours inside the volume), GetAverageHausdorffDistance of the two contours with an
+    exact Euclidean distance transform.  seg_fixed (Cf,1,D,H,W) int16 with Cf in {1, C}, seg_moving (C,1,D,H,W) int16,
+    spacing (sx, sy, sz) as SetSpacing takes it (sx scales the last axis).  -> (C, L) float64 tensor; inf where a contour
+    is empty (the reference's `except` branch).  One device-to-host read: the boxes that size the workspace."""
+    lib = L.load()
+    Cn, D, H, W = _dims5(seg_moving, 1)
+    if seg_fixed.dim() != 5 or seg_fixed.shape[1] != 1 or seg_fixed.shape[0] not in (1, Cn) or tuple(seg_fixed.shape[2:]) != (D, H, W):
+        raise L.IrsError(f'fixed segmentation {tuple(seg_fixed.shape)} does not match the moving one {tuple(seg_moving.shape)}')
+    f, m = L.dev_ptr(seg_fixed, torch.int16), L.dev_ptr(seg_moving, torch.int16)
+    labels = [int(x) for x in labels]
+    sp = [float(x) for x in (spacing.tolist() if hasattr(spacing, 'tolist') else spacing)]
+    if len(sp) != 3:
+        raise L.IrsError(f'spacing must have 3 entries, got {len(sp)}')
+    n = len(labels)
+    lab = (C.c_int32 * max(n, 1))(*labels)
+    P = Cn * n
+    dev = seg_moving.device
+    boxes = torch.empty((max(P, 1), 6), device=dev, dtype=torch.int32)
+    L.check(lib.irs_label_boxes(f, seg_fixed.shape[0], m, lab, n, L.dev_ptr(boxes), Cn, D, H, W, L.stream_ptr()))
+    boxes_h = boxes.cpu()
+    bp = C.cast(C.c_void_p(boxes_h.data_ptr()), C.POINTER(C.c_int32))
+    nbytes = C.c_size_t()
+    L.check(lib.irs_surface_distance_workspace(bp, P, D, H, W, C.byref(nbytes)))
+    ws = torch.empty(nbytes.value, device=dev, dtype=torch.uint8)
+    counts = torch.empty((P, 2), device=dev, dtype=torch.int64)
+    sums = torch.empty((P, 2), device=dev, dtype=torch.float64)
+    L.check(lib.irs_label_surface_distance(f, seg_fixed.shape[0], m, lab, n, (C.c_float * 3)(*sp), bp, L.dev_ptr(ws), nbytes.value,
+                                           L.dev_ptr(counts), L.dev_ptr(sums), Cn, D, H, W, L.stream_ptr()))
+    empty = (counts == 0).any(dim=1)
+    asd = 0.5 * (sums[:, 0] / counts[:, 0].clamp(min=1) + sums[:, 1] / counts[:, 1].clamp(min=1))
+    return torch.where(empty, torch.full_like(asd, math.inf), asd).view(Cn, n)

@@ -88,6 +88,7 @@ class ConfigParser:
         m = [f'MCMC/GMM/scale_{i}' for i in range(K)] + [f'MCMC/GMM/proportion_{i}' for i in range(K)] + ['MCMC/avg_loss']
         for i in range(C):
             m += [f'MCMC/chain_{i}/{t}' for t in ('data_term', 'reg_term', 'VD/alpha', 'reg/energy', 'no_non_diffeomorphic_voxels')]
+            m += [f'MCMC/chain_{i}/ASD/{s}' for s in self.structures_dict]
             m += [f'MCMC/chain_{i}/DSC/{s}' for s in self.structures_dict]
         return m
 

@@ -19,7 +19,7 @@ import torch
 from ..base import BaseTrainer
 from ..engine import EngineConfig, TransitionEngine
 from ..logger import save_displacement_mean_and_std_dev, save_sample
-from ..utils import calc_norm, calc_no_non_diffeomorphic_voxels, calc_DSC_GPU, sample_q_v
+from ..utils import calc_norm, calc_no_non_diffeomorphic_voxels, calc_metrics, sample_q_v
 from .vi import VIMixin
 
 
@@ -313,9 +313,10 @@ class Trainer(VIMixin, BaseTrainer):
                 no_folds, log_det_J = calc_no_non_diffeomorphic_voxels(transformation, self.diff_op)
                 if 'seg' in moving and 'seg' in fixed and self.structures_dict:
                     seg_warped = self.registration_module(moving['seg'], transformation)
-                    DSC = calc_DSC_GPU(self.no_chains, fixed['seg'].expand_as(seg_warped), seg_warped, self.structures_dict)
+                    ASD, DSC = calc_metrics(fixed['seg'], seg_warped, self.structures_dict, spacing, no_samples=self.no_chains)
                     for idx in range(self.no_chains):
                         for j, name in enumerate(self.structures_dict):
+                            self.metrics.update(f'MCMC/chain_{idx}/ASD/{name}', float(ASD[idx][j]))
                             self.metrics.update(f'MCMC/chain_{idx}/DSC/{name}', float(DSC[idx][j]))
                 no_voxels = int(np.prod(displacement.shape[2:]))
                 if save_samples:
@@ -363,6 +364,7 @@ class Trainer(VIMixin, BaseTrainer):
             moving = {k: v.to(self.device) for k, v in moving.items()}
             self._engine_init(fixed, moving)
             self._GMM_init(fixed, moving, var_params_q_v)
+            self._metrics_init(fixed, moving)
             var_params_q_v = {k: v.to(self.device) for k, v in var_params_q_v.items()}
             self._sobolev_init()
             self._init_optimizers()

@@ -14,7 +14,7 @@ import torch
 
 from ..logger import (save_displacement_mean_and_std_dev, save_field, save_fixed_im, save_fixed_mask, save_im, save_moving_im,
                       save_moving_mask, save_sample)
-from ..utils import (SobolevGrad, add_noise_uniform_field, calc_DSC_GPU, calc_no_non_diffeomorphic_voxels, calc_posterior_statistics,
+from ..utils import (SobolevGrad, add_noise_uniform_field, calc_metrics, calc_no_non_diffeomorphic_voxels, calc_posterior_statistics,
                      calc_VD_factor, max_field_update, rescale_residuals, sample_q_v)
 from ..utils.functions import Sobolev_kernel_1D
 
@@ -204,8 +204,9 @@ class VIMixin:
                     self.metrics.update(f'VI/train/max_updates/{key}', max_field_update(prev[key], var_params_q_v[key])[0].item())
                 if (iter_no % self.log_period_VI == 0 or iter_no == self.no_iters_VI) and 'seg' in moving and self.structures_dict:
                     seg_warped = self.registration_module(moving['seg'], output['transformation'].detach())
-                    DSC = calc_DSC_GPU(1, fixed['seg'], seg_warped, self.structures_dict)
+                    ASD, DSC = calc_metrics(fixed['seg'], seg_warped, self.structures_dict, spacing)
                     for j, structure in enumerate(self.structures_dict):
+                        self.metrics.update(f'VI/train/ASD/{structure}', float(ASD[0][j]))
                         self.metrics.update(f'VI/train/DSC/{structure}', float(DSC[0][j]))
 
     @torch.no_grad()
@@ -224,8 +225,9 @@ class VIMixin:
             self.metrics.update('VI/test/no_non_diffeomorphic_voxels', int(no_folds.sum()))
             warped = self.registration_module(moving['im'], transformation)
             if 'seg' in moving and self.structures_dict:
-                DSC = calc_DSC_GPU(1, fixed['seg'], self.registration_module(moving['seg'], transformation), self.structures_dict)
+                ASD, DSC = calc_metrics(fixed['seg'], self.registration_module(moving['seg'], transformation), self.structures_dict, spacing)
                 for j, structure in enumerate(self.structures_dict):
+                    self.metrics.update(f'VI/test/ASD/{structure}', float(ASD[0][j]))
                     self.metrics.update(f'VI/test/DSC/{structure}', float(DSC[0][j]))
             if save:
                 save_sample(self.config.save_dirs, spacing, n, warped, displacement, log_det_J, 'VI')
@@ -251,6 +253,17 @@ class VIMixin:
         torch.cuda.synchronize()
         self.VI_sampling_speed = n_speed / (time.perf_counter() - start)
         self.logger.info(f'\nVI sampling speed: {self.VI_sampling_speed:.2f} samples/sec')
+
+    @torch.no_grad()
+    def _metrics_init(self, fixed, moving):
+        """trainer.py:550-567, the metrics only: ASD and Dice of the unregistered pair at step 0"""
+        if 'seg' not in fixed or 'seg' not in moving or not self.structures_dict:
+            return
+        self.writer.set_step(0)
+        ASD, DSC = calc_metrics(fixed['seg'], moving['seg'], self.structures_dict, self._spacing())
+        for j, structure in enumerate(self.structures_dict):
+            self.metrics.update(f'VI/train/ASD/{structure}', float(ASD[0][j]))
+            self.metrics.update(f'VI/train/DSC/{structure}', float(DSC[0][j]))
 
     def _spacing(self):
         sp = getattr(self.data_loader, 'im_spacing', None)

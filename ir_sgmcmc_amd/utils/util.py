@@ -137,6 +137,19 @@ def calc_DSC_GPU(no_samples, seg_fixed, seg_moving, structures_dict):
     return DSC.numpy()
 
 
+@torch.no_grad()
+def calc_metrics(seg_fixed, seg_moving, structures_dict, spacing, GPU=True, no_samples=1):
+    """average surface distances and Dice scores (utils/util.py:152-206) -> (ASD, DSC), numpy arrays [no_samples, L].
+    The ASD runs on the device (ops.label_surface_distance) instead of SimpleITK on the host; `GPU` only chose where the
+    reference computed Dice, which is the same number either way."""
+    seg_moving = seg_moving[:no_samples].contiguous()
+    shared = seg_fixed.shape[0] == 1 or seg_fixed.stride(0) == 0  # one volume, or .expand()-ed chains sharing it
+    seg_fixed = seg_fixed[:1].contiguous() if shared else seg_fixed[:no_samples].contiguous()
+    ASD = _ops.label_surface_distance(seg_fixed, seg_moving, list(structures_dict.values()), spacing).cpu().numpy()
+    DSC = calc_DSC_GPU(no_samples, seg_fixed.expand_as(seg_moving), seg_moving, structures_dict)
+    return ASD, DSC
+
+
 def rescale_residuals(res, mask, data_loss):
     """VD-rescaled residual x = sum_k r_k (z / sigma_k)^2 (utils/util.py:330-347).  The reference obtains it as
     sum_k s_k * d(-log p)/d(s_k) with a nested backward; the closed form with the responsibilities r_k is the same number."""
