@@ -131,6 +131,20 @@ int irs_label_surface_distance(const int16_t* seg_fixed, int Cf, const int16_t* 
                                size_t workspace_bytes, long long* counts, double* sums, int C, int D, int H, int W,
                                void* stream);
 
+/* Split-R-hat of a vector field over chains (absent in the reference; Gelman et al., BDA3 section 11.4), from online moments.
+ * Layouts: x (C,3,D,H,W) fp32; mean / m2 (2,C,3,D,H,W) fp32, the Welford state of each half of each chain's samples.
+ *  - irs_chain_moments_update: folds x into half `half` (0 or 1) of every chain; k >= 1 = samples in that half after this one
+ *    (k = 1 overwrites whatever the half held).  One launch.
+ *  - irs_split_rhat: n >= 2 = samples per half.  rhat (D,H,W): per voxel the largest over the three components of
+ *    sqrt(var+ / W), W = mean of M2 / (n - 1) over the 2C sequences, var+ = (n - 1) / n W + (variance of the sequence means);
+ *    1 where W = B = 0, +inf where W = 0 < B; never NaN.  mask (D,H,W) uint8 or NULL (whole volume).  summary: 5 doubles
+ *    on the device {voxels in the mask, voxels with rhat > thr0, with rhat > thr1, max, sum of rhat}.  ws: device
+ *    workspace of irs_split_rhat_workspace bytes.  Deterministic (fixed-order reduction, no float atomics); no host sync. */
+int irs_chain_moments_update(const float* x, int C, int D, int H, int W, int half, int k, float* mean, float* m2, void* stream);
+int irs_split_rhat_workspace(int C, int D, int H, int W, size_t* bytes);
+int irs_split_rhat(const float* mean, const float* m2, int C, int n, const uint8_t* mask, float thr0, float thr1, float* rhat,
+                   double* summary, void* ws, size_t ws_bytes, int D, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * fused transition (Trainer._SGLD_transition, trainer/trainer.py:291-356)
  * ---------------------------------------------------------------------------------------------- */

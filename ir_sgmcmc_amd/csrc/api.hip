@@ -625,6 +625,37 @@ int irs_label_surface_distance(const int16_t* seg_fixed, int Cf, const int16_t* 
 }
 
 // ================================================================================================
+// split-R-hat over chains (diag_kernels.hip)
+// ================================================================================================
+int irs_chain_moments_update(const float* x, int C, int D, int H, int W, int half, int k, float* mean, float* m2, void* stream) {
+    if (!x || !mean || !m2 || !dims_ok(C, D, H, W)) return fail("irs_chain_moments_update: bad arguments");
+    if (half != 0 && half != 1) return fail("irs_chain_moments_update: half must be 0 or 1, got %d", half);
+    if (k < 1) return fail("irs_chain_moments_update: k must be >= 1, got %d", k);
+    const int64_t n = (int64_t)C * 3 * D * H * W;
+    launch_chain_moments(x, mean + half * n, m2 + half * n, n, k, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_split_rhat_workspace(int C, int D, int H, int W, size_t* bytes) {
+    if (!bytes || !dims_ok(C, D, H, W)) return fail("irs_split_rhat_workspace: bad arguments");
+    *bytes = sizeof(double) * 5 * (size_t)split_rhat_blocks((int64_t)D * H * W);
+    return 0;
+}
+
+int irs_split_rhat(const float* mean, const float* m2, int C, int n, const uint8_t* mask, float thr0, float thr1, float* rhat,
+                   double* summary, void* ws, size_t ws_bytes, int D, int H, int W, void* stream) {
+    if (!mean || !m2 || !rhat || !summary || !ws || !dims_ok(C, D, H, W)) return fail("irs_split_rhat: bad arguments");
+    if (n < 2) return fail("irs_split_rhat: n = %d samples per half chain, at least 2 needed", n);
+    const int64_t V = (int64_t)D * H * W;
+    const size_t need = sizeof(double) * 5 * (size_t)split_rhat_blocks(V);
+    if (ws_bytes < need) return fail("irs_split_rhat: workspace of %zu bytes, %zu needed (irs_split_rhat_workspace)", ws_bytes, need);
+    launch_split_rhat(mean, m2, C, n, mask, thr0, thr1, rhat, summary, (double*)ws, V, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // context
 // ================================================================================================
 

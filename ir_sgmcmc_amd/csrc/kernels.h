@@ -149,6 +149,15 @@ void launch_surface_distance(const int16_t* fixed, int64_t f_stride, const int16
                              const float spacing[3], const SurfPassArgs& a, long long* counts, double* sums, Vol vol,
                              hipStream_t st);
 
+// ---- diag_kernels.hip: split-R-hat over chains (absent in the reference; BDA3 section 11.4)
+// Welford update of one half's (mean, m2) with the sample x, all flat arrays of n floats; k = samples in the half after this one
+void launch_chain_moments(const float* x, float* mean, float* m2, int64_t n, int k, hipStream_t st);
+// mean / m2: (2,C,3,V); rhat: V floats; summary: 5 doubles {voxels, above thr0, above thr1, max, sum};
+// partials: 5 * split_rhat_blocks(V) doubles
+int split_rhat_blocks(int64_t V);
+void launch_split_rhat(const float* mean, const float* m2, int C, int n, const uint8_t* mask, float thr0, float thr1, float* rhat,
+                       double* summary, double* partials, int64_t V, hipStream_t st);
+
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h
 }  // namespace irs

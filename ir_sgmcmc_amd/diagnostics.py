@@ -1,0 +1,113 @@
+"""Convergence diagnostics of the MCMC stage (absent in the reference): split-R-hat of the displacement, per voxel.
+
+Each chain's recorded samples are split into two halves (the middle one of an odd count goes to neither), and per half
+and chain a Welford mean / M2 is kept on the device (ops.chain_moments_update): 48 * C * D * H * W bytes, whatever the
+number of samples.  At the end, ops.split_rhat turns the 2C sequences into the classic split-R-hat of Gelman et al.
+(BDA3 section 11.4), the largest over the three displacement components, and a masked summary.
+"""
+import torch
+
+from . import ops
+
+
+def diagnostics_period(cfg_trainer):
+    """`trainer.convergence_diagnostics` -> the recording period P, or None when the option is off.
+    Absent / false: off.  true: P = log_period_MCMC.  {"period": P}: that P.  Refuses a config whose chains would give fewer
+    than 2 samples per half (N = no_samples_MCMC // P recorded samples per chain, N // 2 per half)."""
+    opt = cfg_trainer.get('convergence_diagnostics', False)
+    if opt is None or opt is False:
+        return None
+    if opt is True:
+        period = int(cfg_trainer['log_period_MCMC'])
+    elif isinstance(opt, dict) and set(opt) <= {'period'}:
+        period = int(opt.get('period', cfg_trainer['log_period_MCMC']))
+    else:
+        raise ValueError(f'trainer.convergence_diagnostics must be true, false or {{"period": P}}, got {opt!r}')
+    if period < 1:
+        raise ValueError(f'trainer.convergence_diagnostics: the period must be >= 1, got {period}')
+    no_samples = int(cfg_trainer['no_samples_MCMC'])
+    if no_samples // period // 2 < 2:
+        raise ValueError(f'trainer.convergence_diagnostics: no_samples_MCMC = {no_samples} with period {period} records '
+                         f'{no_samples // period} samples per chain; split-R-hat needs at least 4 (2 per half)')
+    return period
+
+
+def is_recorded(sample_no, no_iters_burn_in, period):
+    """the post-burn-in transitions the diagnostic records: (sample_no - burn-in) % period == 0"""
+    return sample_no > no_iters_burn_in and (sample_no - no_iters_burn_in) % period == 0
+
+
+def recorded_steps(no_iters_burn_in, no_samples_MCMC, period):
+    """every sample_no the trainer records, in order (no_samples_MCMC // period of them)"""
+    first = no_iters_burn_in + 1
+    return [s for s in range(first, first + no_samples_MCMC) if is_recorded(s, no_iters_burn_in, period)]
+
+
+class ChainMoments:
+    """Per-chain, per-half Welford moments of the displacement and the split-R-hat they give.
+
+    `record(displacement)` takes the (C,3,D,H,W) float32 sample of every chain; the i-th call goes to the half
+    `schedule(N)[i]` says.  `rhat()` needs all N calls."""
+
+    def __init__(self, no_chains, dims, n_per_chain, device):
+        self.no_chains, self.dims, self.n_per_chain = int(no_chains), tuple(int(d) for d in dims), int(n_per_chain)
+        if self.n_per_chain // 2 < 2:
+            raise ValueError(f'split-R-hat needs at least 4 recorded samples per chain (2 per half), got {self.n_per_chain}')
+        self.n = self.n_per_chain // 2
+        self.device = device
+        self._schedule = self.schedule(self.n_per_chain)
+        shape = (2, self.no_chains, 3, *self.dims)
+        self.mean = torch.zeros(shape, device=device, dtype=torch.float32)
+        self.m2 = torch.zeros(shape, device=device, dtype=torch.float32)
+        self.count = 0  # calls of record() so far
+
+    @staticmethod
+    def schedule(N):
+        """where the i-th of N recorded samples goes: (half, k), k = samples in that half after it; None for the middle
+        sample of an odd N.  Samples 0 .. N//2 - 1 form half 0, the last N//2 half 1."""
+        n = N // 2
+        out = []
+        for i in range(N):
+            if i < n:
+                out.append((0, i + 1))
+            elif i >= N - n:
+                out.append((1, i - (N - n) + 1))
+            else:
+                out.append(None)
+        return out
+
+    def record(self, displacement):
+        if self.count >= self.n_per_chain:
+            raise RuntimeError(f'ChainMoments.record: all {self.n_per_chain} samples are recorded already')
+        slot = self._schedule[self.count]
+        if slot is not None:
+            ops.chain_moments_update(displacement, self.mean, self.m2, *slot)
+        self.count += 1
+
+    def rhat(self, mask=None, thresholds=(1.01, 1.1)):
+        """-> (map (D,H,W) float32 on the device, summary dict).  One device-to-host read (the summary)."""
+        if self.count != self.n_per_chain:
+            raise RuntimeError(f'ChainMoments.rhat: {self.count} of {self.n_per_chain} samples recorded')
+        if mask is not None:
+            mask = mask.to(self.device)
+            mask = mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
+        rhat, s = ops.split_rhat(self.mean, self.m2, self.n, mask, thresholds)
+        voxels, above0, above1, mx, total = s.tolist()
+        voxels = int(voxels)
+        summary = {'voxels': voxels, 'max': mx if voxels else float('nan'), 'mean': total / voxels if voxels else float('nan')}
+        for t, c in zip(thresholds, (above0, above1)):
+            summary[f'above_{t:g}'] = int(c)
+            summary[f'frac_above_{t:g}'] = c / voxels if voxels else float('nan')
+        return rhat, summary
+
+    def state_dict(self):
+        return {'mean': self.mean.detach().cpu(), 'm2': self.m2.detach().cpu(), 'count': self.count,
+                'n_per_chain': self.n_per_chain}
+
+    def load_state_dict(self, sd):
+        if int(sd['n_per_chain']) != self.n_per_chain or tuple(sd['mean'].shape) != tuple(self.mean.shape):
+            raise ValueError(f'chain moments of {tuple(sd["mean"].shape)} / {int(sd["n_per_chain"])} samples per chain do '
+                             f'not match this run ({tuple(self.mean.shape)} / {self.n_per_chain})')
+        self.mean.copy_(sd['mean'])
+        self.m2.copy_(sd['m2'])
+        self.count = int(sd['count'])

@@ -103,3 +103,13 @@ def save_sample(save_dirs, spacing, sample_no, im_moving_warped_batch, displacem
     save_im(save_dirs, spacing, im_moving_warped_batch[0, 0], f'{prefix}_im_moving_warped', model)
     save_field(save_dirs, spacing, displacement_batch[0] * spacing[0], f'{prefix}_displacement', model)
     save_im(save_dirs, spacing, log_det_J_batch[0], f'{prefix}_log_det_J', model)
+
+
+def save_rhat(logger, save_dirs, spacing, rhat, mask, model='MCMC'):
+    """split-R-hat map of the displacement (absent in the reference), plain and masked as the std map is:
+    samples/{model}_rhat.nii.gz and samples/{model}_rhat_masked.nii.gz (0 outside the mask)"""
+    folder = _folder(save_dirs, 'samples')
+    mask = mask.reshape(rhat.shape).to(rhat.device) != 0
+    logger.info(f'{model} split R-hat min.: {float(rhat.min()):.4f}, max.: {float(rhat.max()):.4f}')
+    save_im_to_disk(rhat, path.join(folder, f'{model}_rhat.nii.gz'), spacing)
+    save_im_to_disk(rhat.where(mask, rhat.new_zeros(())), path.join(folder, f'{model}_rhat_masked.nii.gz'), spacing)

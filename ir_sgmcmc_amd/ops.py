@@ -238,3 +238,42 @@ def label_surface_distance(seg_fixed, seg_moving, labels, spacing):
     empty = (counts == 0).any(dim=1)
     asd = 0.5 * (sums[:, 0] / counts[:, 0].clamp(min=1) + sums[:, 1] / counts[:, 1].clamp(min=1))
     return torch.where(empty, torch.full_like(asd, math.inf), asd).view(Cn, n)
+
+
+def chain_moments_update(x, mean, m2, half, k):
+    """Welford update of half `half` of every chain's split-R-hat moments with the sample x (absent in the reference).
+    x (C,3,D,H,W) float32; mean / m2 (2,C,3,D,H,W) float32, updated in place; k = samples in that half after this one."""
+    lib = L.load()
+    Cn, D, H, W = _dims5(x, 3)
+    for name, t in (('mean', mean), ('m2', m2)):
+        if tuple(t.shape) != (2, Cn, 3, D, H, W):
+            raise L.IrsError(f'{name} must have shape {(2, Cn, 3, D, H, W)}, got {tuple(t.shape)}')
+    L.check(lib.irs_chain_moments_update(L.dev_ptr(x, torch.float32), Cn, D, H, W, int(half), int(k),
+                                         L.dev_ptr(mean, torch.float32), L.dev_ptr(m2, torch.float32), L.stream_ptr()))
+
+
+def split_rhat(mean, m2, n, mask=None, thresholds=(1.01, 1.1)):
+    """Split-R-hat (BDA3 section 11.4) from the per-half moments of chain_moments_update, n samples per half.
+    mask (D,H,W) bool / uint8 or None.  -> (rhat (D,H,W) float32, summary (5,) float64 on the device: voxels in the mask,
+    voxels above thresholds[0], above thresholds[1], max, sum).  No host synchronisation."""
+    lib = L.load()
+    if mean.dim() != 6 or mean.shape[0] != 2 or mean.shape[2] != 3 or tuple(m2.shape) != tuple(mean.shape):
+        raise L.IrsError(f'mean / m2 must have shape (2,C,3,D,H,W), got {tuple(mean.shape)} / {tuple(m2.shape)}')
+    Cn, D, H, W = mean.shape[1], mean.shape[3], mean.shape[4], mean.shape[5]
+    if mask is not None:
+        if mask.numel() != D * H * W or mask.dtype not in (torch.bool, torch.uint8):
+            raise L.IrsError(f'mask must be a bool / uint8 ({D},{H},{W}) volume, got {mask.dtype} {tuple(mask.shape)}')
+        mask = mask.reshape(D, H, W).contiguous()
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    if len(thresholds) != 2:
+        raise L.IrsError('split_rhat takes two thresholds')
+    nbytes = C.c_size_t()
+    L.check(lib.irs_split_rhat_workspace(Cn, D, H, W, C.byref(nbytes)))
+    dev = mean.device
+    ws = torch.empty(nbytes.value, device=dev, dtype=torch.uint8)
+    rhat = torch.empty((D, H, W), device=dev, dtype=torch.float32)
+    summary = torch.empty(5, device=dev, dtype=torch.float64)
+    L.check(lib.irs_split_rhat(L.dev_ptr(mean, torch.float32), L.dev_ptr(m2, torch.float32), Cn, int(n),
+                               L.dev_ptr(mask, torch.uint8, True), float(thresholds[0]), float(thresholds[1]), L.dev_ptr(rhat),
+                               L.dev_ptr(summary), L.dev_ptr(ws), nbytes.value, D, H, W, L.stream_ptr()))
+    return rhat, summary

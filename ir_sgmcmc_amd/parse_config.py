@@ -11,6 +11,7 @@ from pathlib import Path
 import numpy as np
 
 from .data_loader import data_loaders as module_data
+from .diagnostics import diagnostics_period
 from .logger import setup_logging
 from .model import distributions as model_distr
 from .model import loss as model_loss
@@ -90,6 +91,8 @@ class ConfigParser:
             m += [f'MCMC/chain_{i}/{t}' for t in ('data_term', 'reg_term', 'VD/alpha', 'reg/energy', 'no_non_diffeomorphic_voxels')]
             m += [f'MCMC/chain_{i}/ASD/{s}' for s in self.structures_dict]
             m += [f'MCMC/chain_{i}/DSC/{s}' for s in self.structures_dict]
+        if diagnostics_period(self['trainer']) is not None:
+            m += [f'MCMC/R_hat/{k}' for k in ('max', 'mean', 'frac_above_1.01', 'frac_above_1.1')]
         return m
 
     def init_transformation_and_registration_modules(self):

@@ -17,8 +17,9 @@ import numpy as np
 import torch
 
 from ..base import BaseTrainer
+from ..diagnostics import ChainMoments, diagnostics_period, is_recorded
 from ..engine import EngineConfig, TransitionEngine
-from ..logger import save_displacement_mean_and_std_dev, save_sample
+from ..logger import save_displacement_mean_and_std_dev, save_rhat, save_sample
 from ..utils import calc_norm, calc_no_non_diffeomorphic_voxels, calc_metrics, sample_q_v
 from .vi import VIMixin
 
@@ -56,6 +57,10 @@ class Trainer(VIMixin, BaseTrainer):
         self.engine = None
         self.v_curr_state, self.SGLD_params = None, None
         self._scalars_cache, self._outputs = None, None
+        # split-R-hat of the displacement (diagnostics.py): None when trainer.convergence_diagnostics is off
+        self.diagnostics_period = diagnostics_period(cfg_trainer)
+        self._chain_moments = None
+        self.rhat, self.rhat_summary = None, None
 
     # ---------------------------------------------------------------- engine plumbing
     def _engine_config(self):
@@ -151,7 +156,8 @@ class Trainer(VIMixin, BaseTrainer):
                 'tau': self.SGLD_params['tau'], 'engine_state': bytes(ctypes.string_at(ctypes.byref(st), ctypes.sizeof(st))),
                 'sample_no': getattr(self, '_sample_no', 0),
                 'moments': {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in getattr(self, '_moments', {}).items()},
-                'config_name': self.config['name']}
+                'config_name': self.config['name'],
+                **({'chain_moments': self._chain_moments.state_dict()} if self._chain_moments is not None else {})}
 
     def load_state_dict(self, sd):
         import ctypes
@@ -169,6 +175,13 @@ class Trainer(VIMixin, BaseTrainer):
         self.SGLD_params = {'tau': sd['tau'], 'sigma': self._sigma if self._sigma is not None else torch.ones_like(self.v_curr_state)}
         self._sample_no = int(sd['sample_no'])
         self._moments = {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in sd.get('moments', {}).items()}
+        if self._chain_moments is not None:
+            if 'chain_moments' in sd:
+                self._chain_moments.load_state_dict(sd['chain_moments'])
+            elif any(is_recorded(s, self.no_iters_burn_in, self.diagnostics_period) for s in range(1, self._sample_no + 1)):
+                raise ValueError(f'the checkpoint at sample {self._sample_no} holds no chain moments (written with '
+                                 f'trainer.convergence_diagnostics off) but this run records from sample '
+                                 f'{self.no_iters_burn_in + self.diagnostics_period} on')
         self.sync_parameters()
 
     def save_checkpoint(self, file_path):
@@ -272,6 +285,9 @@ class Trainer(VIMixin, BaseTrainer):
         checkpoint_period, save_samples = int(cfg_trainer.get('checkpoint_period', 0)), bool(cfg_trainer.get('save_samples', False))
         spacing = self.data_loader.im_spacing if getattr(self.data_loader, 'im_spacing', None) is not None else torch.ones(3)
         first = 1
+        if self.diagnostics_period is not None:
+            self._chain_moments = ChainMoments(self.no_chains, self._outputs['displacement'].shape[2:],
+                                               self.no_samples_MCMC // self.diagnostics_period, self.device)
         if cfg_trainer.get('resume'):
             self.load_checkpoint(cfg_trainer['resume'])
             first = self._sample_no + 1
@@ -333,6 +349,9 @@ class Trainer(VIMixin, BaseTrainer):
                         log(f'chain {idx}, sample {sample_no}: detected {no_folds} voxels where the sampled '
                             f'transformation is not diffeomorphic; exiting..')
                         raise SystemExit(1)
+            if self._chain_moments is not None and is_recorded(sample_no, self.no_iters_burn_in, self.diagnostics_period):
+                self.engine.flush()  # as above: the buffer holds sample `sample_no` once nothing is pending
+                self._chain_moments.record(output['displacement'])
             if checkpoint_period and sample_no % checkpoint_period == 0:
                 self._sample_no, self._moments = sample_no, {'mean': mean, 'm2': m2, 'n': n_rec}
                 folder = self.config.save_dirs['checkpoints']
@@ -344,6 +363,8 @@ class Trainer(VIMixin, BaseTrainer):
         if n_rec > 0 and cfg_trainer.get('save_outputs', True):
             save_displacement_mean_and_std_dev(self.logger, self.config.save_dirs, spacing, self.displacement_mean,
                                                self.displacement_std, moving.get('mask', fixed['mask'])[0].to(mean.dtype), 'MCMC')  # trainer.py:461-462: the MOVING mask
+        if self._chain_moments is not None:
+            self._finish_diagnostics(moving.get('mask', fixed['mask'])[0], spacing, cfg_trainer.get('save_outputs', True))
 
         # speed test (trainer.py:467-476): 100 x [transition + nearest-neighbour warp of the segmentation]
         n_speed = 100
@@ -357,6 +378,19 @@ class Trainer(VIMixin, BaseTrainer):
         torch.cuda.synchronize()
         self.MCMC_sampling_speed = self.no_chains * n_speed / (time.perf_counter() - start)
         log(f'\nMCMC sampling speed: {self.MCMC_sampling_speed:.2f} samples/sec')
+
+    def _finish_diagnostics(self, mask, spacing, save_outputs):
+        """split-R-hat map and its summary over the moving mask (the std map's mask) -> self.rhat / self.rhat_summary,
+        the MCMC/R_hat/* metrics and, with save_outputs, samples/MCMC_rhat[_masked].nii.gz"""
+        self.rhat, self.rhat_summary = self._chain_moments.rhat(mask)
+        s = self.rhat_summary
+        for key in ('max', 'mean', 'frac_above_1.01', 'frac_above_1.1'):
+            self.metrics.update(f'MCMC/R_hat/{key}', s[key])
+        self.logger.info(f'split R-hat over {s["voxels"]} masked voxels ({self.no_chains} chains, '
+                         f'{self._chain_moments.n} samples per half): max {s["max"]:.4f}, mean {s["mean"]:.4f}, '
+                         f'{100 * s["frac_above_1.01"]:.2f} % above 1.01, {100 * s["frac_above_1.1"]:.2f} % above 1.1')
+        if save_outputs:
+            save_rhat(self.logger, self.config.save_dirs, spacing, self.rhat, mask, 'MCMC')
 
     def _run_model(self):
         for fixed, moving, var_params_q_v in self.data_loader:
