@@ -145,6 +145,25 @@ int irs_split_rhat_workspace(int C, int D, int H, int W, size_t* bytes);
 int irs_split_rhat(const float* mean, const float* m2, int C, int n, const uint8_t* mask, float thr0, float thr1, float* rhat,
                    double* summary, void* ws, size_t ws_bytes, int D, int H, int W, void* stream);
 
+/* Split effective sample size and MCSE of the posterior mean (absent in the reference; BDA3 section 11.5), from the moments
+ * above and an online variogram.  Layouts: x (C,3,D,H,W); ring (L,C,3,D,H,W), the last L samples of the current half;
+ * vsum (L,3,D,H,W), vsum[t-1] = sum over both halves and all chains of (x_i - x_{i-t})^2; all fp32.  C <= IRS_MAX_CHAINS.
+ *  - irs_chain_variogram_update: k >= 1 = the same k as irs_chain_moments_update (position in the current half after x).
+ *    For t = 1 .. min(k-1, L): vsum[t-1] += sum over chains of (x - ring[(k-1-t) mod L])^2; then ring[(k-1) mod L] = x.
+ *    One launch, no atomics: two identical call sequences are bit-identical.
+ *  - irs_split_ess: n >= 4 samples per half, L >= 1 lags in vsum (L' = min(L, n-1) are used).  Per component
+ *    var+ = (n-1)/n W + B/n as for R-hat, rho_t = 1 - vsum[t-1] / (2C (n-t)) / (2 var+), tau = 1 + 2 sum_{t<=T} rho_t with
+ *    T the first odd T with T + 2 <= L' and rho_{T+1} + rho_{T+2} < 0 (else the largest odd T <= L': truncated),
+ *    ESS = mn / tau capped at mn max(1, log10 mn) (m = 2C), MCSE = sqrt(var+ / ESS).  var+ = 0 gives ESS = mn, MCSE = 0;
+ *    non-finite moments or sums give ESS = 0, MCSE = +inf; never NaN.  ess (D,H,W): the smallest over the three components,
+ *    mcse (D,H,W): the largest.  mask (D,H,W) uint8 or NULL.  summary: 5 doubles on the device {voxels in the mask, voxels
+ *    with ESS < threshold, voxels with a truncated component, min ESS, sum of ESS}.  ws: irs_split_ess_workspace bytes.
+ *    Deterministic (fixed-order reduction, no float atomics); no host sync. */
+int irs_chain_variogram_update(const float* x, int C, int D, int H, int W, int k, int L, float* ring, float* vsum, void* stream);
+int irs_split_ess_workspace(int C, int D, int H, int W, size_t* bytes);
+int irs_split_ess(const float* mean, const float* m2, const float* vsum, int C, int n, int L, const uint8_t* mask, float threshold,
+                  float* ess, float* mcse, double* summary, void* ws, size_t ws_bytes, int D, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * fused transition (Trainer._SGLD_transition, trainer/trainer.py:291-356)
  * ---------------------------------------------------------------------------------------------- */

@@ -135,6 +135,9 @@ SIGNATURES = {
     'irs_chain_moments_update': [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     'irs_split_rhat_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
     'irs_split_rhat': [_P, _P, _I, _I, _P, C.c_float, C.c_float, _P, _P, _P, C.c_size_t, _I, _I, _I, _P],
+    'irs_chain_variogram_update': [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    'irs_split_ess_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
+    'irs_split_ess': [_P, _P, _P, _I, _I, _I, _P, C.c_float, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _P],
     'irs_create': [C.POINTER(IrsConfig), C.POINTER(_P)],
     'irs_destroy': [_P],
     'irs_workspace_bytes': [_P],

@@ -656,6 +656,40 @@ int irs_split_rhat(const float* mean, const float* m2, int C, int n, const uint8
 }
 
 // ================================================================================================
+// split ESS and MCSE over chains (diag_kernels.hip)
+// ================================================================================================
+int irs_chain_variogram_update(const float* x, int C, int D, int H, int W, int k, int L, float* ring, float* vsum, void* stream) {
+    if (!x || !ring || !vsum || !dims_ok(C, D, H, W)) return fail("irs_chain_variogram_update: bad arguments");
+    if (C > IRS_MAX_CHAINS) return fail("irs_chain_variogram_update: %d chains, at most %d", C, IRS_MAX_CHAINS);
+    if (k < 1) return fail("irs_chain_variogram_update: k must be >= 1, got %d", k);
+    if (L < 1) return fail("irs_chain_variogram_update: L must be >= 1, got %d", L);
+    launch_chain_variogram(x, ring, vsum, C, (int64_t)3 * D * H * W, L, k, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_split_ess_workspace(int C, int D, int H, int W, size_t* bytes) {
+    if (!bytes || !dims_ok(C, D, H, W)) return fail("irs_split_ess_workspace: bad arguments");
+    *bytes = sizeof(double) * 5 * (size_t)split_rhat_blocks((int64_t)D * H * W);
+    return 0;
+}
+
+int irs_split_ess(const float* mean, const float* m2, const float* vsum, int C, int n, int L, const uint8_t* mask, float threshold,
+                  float* ess, float* mcse, double* summary, void* ws, size_t ws_bytes, int D, int H, int W, void* stream) {
+    if (!mean || !m2 || !vsum || !ess || !mcse || !summary || !ws || !dims_ok(C, D, H, W))
+        return fail("irs_split_ess: bad arguments");
+    if (L < 1) return fail("irs_split_ess: L must be >= 1, got %d", L);
+    if (n - 1 < 3)
+        return fail("irs_split_ess: n = %d samples per half chain, at least 4 needed (the truncation rule reads lags 1 to 3)", n);
+    const int64_t V = (int64_t)D * H * W;
+    const size_t need = sizeof(double) * 5 * (size_t)split_rhat_blocks(V);
+    if (ws_bytes < need) return fail("irs_split_ess: workspace of %zu bytes, %zu needed (irs_split_ess_workspace)", ws_bytes, need);
+    launch_split_ess(mean, m2, vsum, C, n, L, mask, threshold, ess, mcse, summary, (double*)ws, V, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // context
 // ================================================================================================
 

@@ -149,7 +149,7 @@ void launch_surface_distance(const int16_t* fixed, int64_t f_stride, const int16
                              const float spacing[3], const SurfPassArgs& a, long long* counts, double* sums, Vol vol,
                              hipStream_t st);
 
-// ---- diag_kernels.hip: split-R-hat over chains (absent in the reference; BDA3 section 11.4)
+// ---- diag_kernels.hip: split-R-hat and split ESS over chains (absent in the reference; BDA3 sections 11.4-11.5)
 // Welford update of one half's (mean, m2) with the sample x, all flat arrays of n floats; k = samples in the half after this one
 void launch_chain_moments(const float* x, float* mean, float* m2, int64_t n, int k, hipStream_t st);
 // mean / m2: (2,C,3,V); rhat: V floats; summary: 5 doubles {voxels, above thr0, above thr1, max, sum};
@@ -157,6 +157,13 @@ void launch_chain_moments(const float* x, float* mean, float* m2, int64_t n, int
 int split_rhat_blocks(int64_t V);
 void launch_split_rhat(const float* mean, const float* m2, int C, int n, const uint8_t* mask, float thr0, float thr1, float* rhat,
                        double* summary, double* partials, int64_t V, hipStream_t st);
+// split ESS (BDA3 section 11.5).  x (C,E), ring (L,C,E), vsum (L,E) with E = 3V; k = position in the current half after x:
+// vsum[t-1] += sum over chains of (x - ring[(k-1-t) mod L])^2 for t = 1 .. min(k-1, L), then ring[(k-1) mod L] = x
+void launch_chain_variogram(const float* x, float* ring, float* vsum, int C, int64_t E, int L, int k, hipStream_t st);
+// ess / mcse: V floats; summary: 5 doubles {voxels, ESS below thr, truncated, min ESS, sum of ESS};
+// partials: 5 * split_rhat_blocks(V) doubles
+void launch_split_ess(const float* mean, const float* m2, const float* vsum, int C, int n, int L, const uint8_t* mask, float thr,
+                      float* ess, float* mcse, double* summary, double* partials, int64_t V, hipStream_t st);
 
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h

@@ -1,10 +1,18 @@
-"""Convergence diagnostics of the MCMC stage (absent in the reference): split-R-hat of the displacement, per voxel.
+"""Convergence diagnostics of the MCMC stage (absent in the reference): split-R-hat, and optionally the split effective
+sample size (ESS) and the Monte Carlo standard error (MCSE) of the posterior mean, of the displacement, per voxel.
 
 Each chain's recorded samples are split into two halves (the middle one of an odd count goes to neither), and per half
 and chain a Welford mean / M2 is kept on the device (ops.chain_moments_update): 48 * C * D * H * W bytes, whatever the
 number of samples.  At the end, ops.split_rhat turns the 2C sequences into the classic split-R-hat of Gelman et al.
 (BDA3 section 11.4), the largest over the three displacement components, and a masked summary.
+
+With ESS on, a ring of the last L samples and the lag sums of squared differences (the variogram) are kept as well
+(ops.chain_variogram_update): 4 * L * (C + 1) * 3 * D * H * W more bytes.  ops.split_ess turns them and the moments into
+BDA3's split ESS (section 11.5) with its truncation rule, and the MCSE sqrt(var+ / ESS).
 """
+import math
+import numbers
+
 import torch
 
 from . import ops
@@ -19,10 +27,10 @@ def diagnostics_period(cfg_trainer):
         return None
     if opt is True:
         period = int(cfg_trainer['log_period_MCMC'])
-    elif isinstance(opt, dict) and set(opt) <= {'period'}:
+    elif isinstance(opt, dict) and set(opt) <= {'period', 'ess'}:
         period = int(opt.get('period', cfg_trainer['log_period_MCMC']))
     else:
-        raise ValueError(f'trainer.convergence_diagnostics must be true, false or {{"period": P}}, got {opt!r}')
+        raise ValueError(f'trainer.convergence_diagnostics must be true, false or {{"period": P, "ess": ...}}, got {opt!r}')
     if period < 1:
         raise ValueError(f'trainer.convergence_diagnostics: the period must be >= 1, got {period}')
     no_samples = int(cfg_trainer['no_samples_MCMC'])
@@ -30,6 +38,55 @@ def diagnostics_period(cfg_trainer):
         raise ValueError(f'trainer.convergence_diagnostics: no_samples_MCMC = {no_samples} with period {period} records '
                          f'{no_samples // period} samples per chain; split-R-hat needs at least 4 (2 per half)')
     return period
+
+
+ESS_DEFAULTS = {'max_lag': 32, 'threshold': 400.0}
+
+
+def _number(v):
+    return isinstance(v, numbers.Real) and not isinstance(v, bool)
+
+
+def ess_options(cfg_trainer):
+    """`trainer.convergence_diagnostics` -> None when the split ESS is off, else {'max_lag': L, 'threshold': X}.
+    Off unless the option is a dict with "ess": true (the defaults, max_lag 32 and threshold 400) or "ess": {"max_lag": L,
+    "threshold": X} (either key may be left out).  Refuses max_lag < 3, unknown keys, non-numeric values, and a config whose
+    chains would give fewer than 4 samples per half (the truncation rule reads lags 1 to 3)."""
+    period = diagnostics_period(cfg_trainer)
+    opt = cfg_trainer.get('convergence_diagnostics')
+    if period is None or not isinstance(opt, dict):
+        return None
+    ess = opt.get('ess', False)
+    if ess is None or ess is False:
+        return None
+    out = dict(ESS_DEFAULTS)
+    if isinstance(ess, dict):
+        unknown = set(ess) - set(ESS_DEFAULTS)
+        if unknown:
+            raise ValueError(f'trainer.convergence_diagnostics.ess: unknown keys {sorted(unknown)}; '
+                             f'known: {sorted(ESS_DEFAULTS)}')
+        for key, v in ess.items():
+            if not _number(v) or not math.isfinite(v):
+                raise ValueError(f'trainer.convergence_diagnostics.ess.{key} must be a finite number, got {v!r}')
+        if 'max_lag' in ess:
+            if int(ess['max_lag']) != ess['max_lag']:
+                raise ValueError(f'trainer.convergence_diagnostics.ess.max_lag must be an integer, got {ess["max_lag"]!r}')
+            out['max_lag'] = int(ess['max_lag'])
+        if 'threshold' in ess:
+            out['threshold'] = float(ess['threshold'])
+    elif ess is not True:
+        raise ValueError(f'trainer.convergence_diagnostics.ess must be true, false or {{"max_lag": L, "threshold": X}}, '
+                         f'got {ess!r}')
+    if out['max_lag'] < 3:
+        raise ValueError(f'trainer.convergence_diagnostics.ess.max_lag must be >= 3 (the truncation rule reads lags 1 to 3), '
+                         f'got {out["max_lag"]}')
+    if out['threshold'] <= 0:
+        raise ValueError(f'trainer.convergence_diagnostics.ess.threshold must be > 0, got {out["threshold"]}')
+    no_samples = int(cfg_trainer['no_samples_MCMC'])
+    if no_samples // period // 2 < 4:
+        raise ValueError(f'trainer.convergence_diagnostics.ess: no_samples_MCMC = {no_samples} with period {period} records '
+                         f'{no_samples // period} samples per chain; the split ESS needs at least 8 (4 per half)')
+    return out
 
 
 def is_recorded(sample_no, no_iters_burn_in, period):
@@ -44,12 +101,13 @@ def recorded_steps(no_iters_burn_in, no_samples_MCMC, period):
 
 
 class ChainMoments:
-    """Per-chain, per-half Welford moments of the displacement and the split-R-hat they give.
+    """Per-chain, per-half Welford moments of the displacement and the split-R-hat they give; with `max_lag` set, also the
+    online variogram of each half and the split ESS / MCSE.
 
     `record(displacement)` takes the (C,3,D,H,W) float32 sample of every chain; the i-th call goes to the half
-    `schedule(N)[i]` says.  `rhat()` needs all N calls."""
+    `schedule(N)[i]` says.  `rhat()` and `ess()` need all N calls."""
 
-    def __init__(self, no_chains, dims, n_per_chain, device):
+    def __init__(self, no_chains, dims, n_per_chain, device, max_lag=None):
         self.no_chains, self.dims, self.n_per_chain = int(no_chains), tuple(int(d) for d in dims), int(n_per_chain)
         if self.n_per_chain // 2 < 2:
             raise ValueError(f'split-R-hat needs at least 4 recorded samples per chain (2 per half), got {self.n_per_chain}')
@@ -60,6 +118,16 @@ class ChainMoments:
         self.mean = torch.zeros(shape, device=device, dtype=torch.float32)
         self.m2 = torch.zeros(shape, device=device, dtype=torch.float32)
         self.count = 0  # calls of record() so far
+        self.max_lag = None if max_lag is None else int(max_lag)
+        self.ring, self.vsum = None, None
+        if self.max_lag is not None:
+            if self.max_lag < 1:
+                raise ValueError(f'max_lag must be >= 1, got {self.max_lag}')
+            if self.n - 1 < 3:
+                raise ValueError(f'the split ESS needs at least 8 recorded samples per chain (4 per half), '
+                                 f'got {self.n_per_chain}')
+            self.ring = torch.zeros((self.max_lag, self.no_chains, 3, *self.dims), device=device, dtype=torch.float32)
+            self.vsum = torch.zeros((self.max_lag, 3, *self.dims), device=device, dtype=torch.float32)
 
     @staticmethod
     def schedule(N):
@@ -82,6 +150,8 @@ class ChainMoments:
         slot = self._schedule[self.count]
         if slot is not None:
             ops.chain_moments_update(displacement, self.mean, self.m2, *slot)
+            if self.max_lag is not None:
+                ops.chain_variogram_update(displacement, self.ring, self.vsum, slot[1])
         self.count += 1
 
     def rhat(self, mask=None, thresholds=(1.01, 1.1)):
@@ -100,14 +170,42 @@ class ChainMoments:
             summary[f'frac_above_{t:g}'] = c / voxels if voxels else float('nan')
         return rhat, summary
 
+    def ess(self, mask=None, threshold=400.0):
+        """-> (ESS map, MCSE map, both (D,H,W) float32 on the device, summary dict).  One device-to-host read (the summary)."""
+        if self.max_lag is None:
+            raise RuntimeError('ChainMoments.ess: built without max_lag, so no variogram was kept')
+        if self.count != self.n_per_chain:
+            raise RuntimeError(f'ChainMoments.ess: {self.count} of {self.n_per_chain} samples recorded')
+        if mask is not None:
+            mask = mask.to(self.device)
+            mask = mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
+        ess, mcse, s = ops.split_ess(self.mean, self.m2, self.vsum, self.n, mask, threshold)
+        voxels, below, truncated, mn, total = s.tolist()
+        voxels = int(voxels)
+        nan = float('nan')
+        summary = {'voxels': voxels, 'min': mn if voxels else nan, 'mean': total / voxels if voxels else nan,
+                   f'below_{threshold:g}': int(below), f'frac_below_{threshold:g}': below / voxels if voxels else nan,
+                   'truncated': int(truncated), 'frac_truncated': truncated / voxels if voxels else nan}
+        return ess, mcse, summary
+
     def state_dict(self):
-        return {'mean': self.mean.detach().cpu(), 'm2': self.m2.detach().cpu(), 'count': self.count,
-                'n_per_chain': self.n_per_chain}
+        sd = {'mean': self.mean.detach().cpu(), 'm2': self.m2.detach().cpu(), 'count': self.count,
+              'n_per_chain': self.n_per_chain}
+        if self.max_lag is not None:
+            sd.update(ring=self.ring.detach().cpu(), vsum=self.vsum.detach().cpu(), max_lag=self.max_lag)
+        return sd
 
     def load_state_dict(self, sd):
         if int(sd['n_per_chain']) != self.n_per_chain or tuple(sd['mean'].shape) != tuple(self.mean.shape):
             raise ValueError(f'chain moments of {tuple(sd["mean"].shape)} / {int(sd["n_per_chain"])} samples per chain do '
                              f'not match this run ({tuple(self.mean.shape)} / {self.n_per_chain})')
+        max_lag = sd.get('max_lag')
+        if max_lag != self.max_lag and int(sd['count']) > 0:
+            raise ValueError(f'chain moments with ESS max_lag {max_lag} (None: ESS off) after {int(sd["count"])} recorded '
+                             f'samples do not match this run (max_lag {self.max_lag})')
         self.mean.copy_(sd['mean'])
         self.m2.copy_(sd['m2'])
+        if self.max_lag is not None and max_lag == self.max_lag:
+            self.ring.copy_(sd['ring'])
+            self.vsum.copy_(sd['vsum'])
         self.count = int(sd['count'])

@@ -113,3 +113,15 @@ def save_rhat(logger, save_dirs, spacing, rhat, mask, model='MCMC'):
     logger.info(f'{model} split R-hat min.: {float(rhat.min()):.4f}, max.: {float(rhat.max()):.4f}')
     save_im_to_disk(rhat, path.join(folder, f'{model}_rhat.nii.gz'), spacing)
     save_im_to_disk(rhat.where(mask, rhat.new_zeros(())), path.join(folder, f'{model}_rhat_masked.nii.gz'), spacing)
+
+
+def save_ess(logger, save_dirs, spacing, ess, mcse, mask, model='MCMC'):
+    """split ESS and MCSE maps of the displacement (absent in the reference), plain and masked as the std map is:
+    samples/{model}_ess[_masked].nii.gz and samples/{model}_mcse[_masked].nii.gz (0 outside the mask)"""
+    folder = _folder(save_dirs, 'samples')
+    mask = mask.reshape(ess.shape).to(ess.device) != 0
+    logger.info(f'{model} split ESS min.: {float(ess.min()):.1f}, max.: {float(ess.max()):.1f}; '
+                f'MCSE max.: {float(mcse.max()):.4g}')
+    for name, im in (('ess', ess), ('mcse', mcse)):
+        save_im_to_disk(im, path.join(folder, f'{model}_{name}.nii.gz'), spacing)
+        save_im_to_disk(im.where(mask, im.new_zeros(())), path.join(folder, f'{model}_{name}_masked.nii.gz'), spacing)

@@ -277,3 +277,48 @@ def split_rhat(mean, m2, n, mask=None, thresholds=(1.01, 1.1)):
                                L.dev_ptr(mask, torch.uint8, True), float(thresholds[0]), float(thresholds[1]), L.dev_ptr(rhat),
                                L.dev_ptr(summary), L.dev_ptr(ws), nbytes.value, D, H, W, L.stream_ptr()))
     return rhat, summary
+
+
+def chain_variogram_update(x, ring, vsum, k):
+    """Online variogram of every chain's split sequences for the split ESS (absent in the reference; BDA3 section 11.5).
+    x (C,3,D,H,W) float32; ring (L,C,3,D,H,W) and vsum (L,3,D,H,W) float32, updated in place; k = position in the current
+    half after x (as for chain_moments_update): vsum[t-1] += sum over chains of (x - x_{-t})^2 for t <= min(k-1, L)."""
+    lib = L.load()
+    Cn, D, H, W = _dims5(x, 3)
+    if ring.dim() != 6 or tuple(ring.shape[1:]) != (Cn, 3, D, H, W):
+        raise L.IrsError(f'ring must have shape (L,{Cn},3,{D},{H},{W}), got {tuple(ring.shape)}')
+    Lg = ring.shape[0]
+    if tuple(vsum.shape) != (Lg, 3, D, H, W):
+        raise L.IrsError(f'vsum must have shape {(Lg, 3, D, H, W)}, got {tuple(vsum.shape)}')
+    L.check(lib.irs_chain_variogram_update(L.dev_ptr(x, torch.float32), Cn, D, H, W, int(k), Lg, L.dev_ptr(ring, torch.float32),
+                                           L.dev_ptr(vsum, torch.float32), L.stream_ptr()))
+
+
+def split_ess(mean, m2, vsum, n, mask=None, threshold=400.0):
+    """Split ESS and MCSE of the posterior mean (BDA3 section 11.5) from the per-half moments of chain_moments_update and the
+    lag sums of chain_variogram_update, n samples per half.  mask (D,H,W) bool / uint8 or None.
+    -> (ess (D,H,W) float32: min over the components, mcse (D,H,W) float32: max over the components, summary (5,) float64
+    on the device: voxels in the mask, voxels with ESS < threshold, voxels with a truncated component, min ESS, sum of ESS).
+    No host synchronisation."""
+    lib = L.load()
+    if mean.dim() != 6 or mean.shape[0] != 2 or mean.shape[2] != 3 or tuple(m2.shape) != tuple(mean.shape):
+        raise L.IrsError(f'mean / m2 must have shape (2,C,3,D,H,W), got {tuple(mean.shape)} / {tuple(m2.shape)}')
+    Cn, D, H, W = mean.shape[1], mean.shape[3], mean.shape[4], mean.shape[5]
+    if vsum.dim() != 5 or tuple(vsum.shape[1:]) != (3, D, H, W):
+        raise L.IrsError(f'vsum must have shape (L,3,{D},{H},{W}), got {tuple(vsum.shape)}')
+    if mask is not None:
+        if mask.numel() != D * H * W or mask.dtype not in (torch.bool, torch.uint8):
+            raise L.IrsError(f'mask must be a bool / uint8 ({D},{H},{W}) volume, got {mask.dtype} {tuple(mask.shape)}')
+        mask = mask.reshape(D, H, W).contiguous()
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    nbytes = C.c_size_t()
+    L.check(lib.irs_split_ess_workspace(Cn, D, H, W, C.byref(nbytes)))
+    dev = mean.device
+    ws = torch.empty(nbytes.value, device=dev, dtype=torch.uint8)
+    ess = torch.empty((D, H, W), device=dev, dtype=torch.float32)
+    mcse = torch.empty((D, H, W), device=dev, dtype=torch.float32)
+    summary = torch.empty(5, device=dev, dtype=torch.float64)
+    L.check(lib.irs_split_ess(L.dev_ptr(mean, torch.float32), L.dev_ptr(m2, torch.float32), L.dev_ptr(vsum, torch.float32), Cn,
+                              int(n), vsum.shape[0], L.dev_ptr(mask, torch.uint8, True), float(threshold), L.dev_ptr(ess),
+                              L.dev_ptr(mcse), L.dev_ptr(summary), L.dev_ptr(ws), nbytes.value, D, H, W, L.stream_ptr()))
+    return ess, mcse, summary

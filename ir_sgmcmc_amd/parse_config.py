@@ -11,7 +11,7 @@ from pathlib import Path
 import numpy as np
 
 from .data_loader import data_loaders as module_data
-from .diagnostics import diagnostics_period
+from .diagnostics import diagnostics_period, ess_options
 from .logger import setup_logging
 from .model import distributions as model_distr
 from .model import loss as model_loss
@@ -93,6 +93,9 @@ class ConfigParser:
             m += [f'MCMC/chain_{i}/DSC/{s}' for s in self.structures_dict]
         if diagnostics_period(self['trainer']) is not None:
             m += [f'MCMC/R_hat/{k}' for k in ('max', 'mean', 'frac_above_1.01', 'frac_above_1.1')]
+            ess = ess_options(self['trainer'])
+            if ess is not None:
+                m += [f'MCMC/ESS/{k}' for k in ('min', 'mean', f'frac_below_{ess["threshold"]:g}', 'frac_truncated')]
         return m
 
     def init_transformation_and_registration_modules(self):

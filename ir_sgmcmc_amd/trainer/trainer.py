@@ -17,9 +17,9 @@ import numpy as np
 import torch
 
 from ..base import BaseTrainer
-from ..diagnostics import ChainMoments, diagnostics_period, is_recorded
+from ..diagnostics import ChainMoments, diagnostics_period, ess_options, is_recorded
 from ..engine import EngineConfig, TransitionEngine
-from ..logger import save_displacement_mean_and_std_dev, save_rhat, save_sample
+from ..logger import save_displacement_mean_and_std_dev, save_ess, save_rhat, save_sample
 from ..utils import calc_norm, calc_no_non_diffeomorphic_voxels, calc_metrics, sample_q_v
 from .vi import VIMixin
 
@@ -61,6 +61,9 @@ class Trainer(VIMixin, BaseTrainer):
         self.diagnostics_period = diagnostics_period(cfg_trainer)
         self._chain_moments = None
         self.rhat, self.rhat_summary = None, None
+        # split ESS / MCSE on top of it: None when its "ess" key is off
+        self.ess_options = ess_options(cfg_trainer)
+        self.ess, self.mcse, self.ess_summary = None, None, None
 
     # ---------------------------------------------------------------- engine plumbing
     def _engine_config(self):
@@ -287,7 +290,8 @@ class Trainer(VIMixin, BaseTrainer):
         first = 1
         if self.diagnostics_period is not None:
             self._chain_moments = ChainMoments(self.no_chains, self._outputs['displacement'].shape[2:],
-                                               self.no_samples_MCMC // self.diagnostics_period, self.device)
+                                               self.no_samples_MCMC // self.diagnostics_period, self.device,
+                                               max_lag=self.ess_options['max_lag'] if self.ess_options else None)
         if cfg_trainer.get('resume'):
             self.load_checkpoint(cfg_trainer['resume'])
             first = self._sample_no + 1
@@ -381,7 +385,8 @@ class Trainer(VIMixin, BaseTrainer):
 
     def _finish_diagnostics(self, mask, spacing, save_outputs):
         """split-R-hat map and its summary over the moving mask (the std map's mask) -> self.rhat / self.rhat_summary,
-        the MCMC/R_hat/* metrics and, with save_outputs, samples/MCMC_rhat[_masked].nii.gz"""
+        the MCMC/R_hat/* metrics and, with save_outputs, samples/MCMC_rhat[_masked].nii.gz; then, with ESS on, the same for
+        the split ESS and MCSE maps"""
         self.rhat, self.rhat_summary = self._chain_moments.rhat(mask)
         s = self.rhat_summary
         for key in ('max', 'mean', 'frac_above_1.01', 'frac_above_1.1'):
@@ -391,6 +396,18 @@ class Trainer(VIMixin, BaseTrainer):
                          f'{100 * s["frac_above_1.01"]:.2f} % above 1.01, {100 * s["frac_above_1.1"]:.2f} % above 1.1')
         if save_outputs:
             save_rhat(self.logger, self.config.save_dirs, spacing, self.rhat, mask, 'MCMC')
+        if self.ess_options is None:
+            return
+        thr = self.ess_options['threshold']
+        self.ess, self.mcse, self.ess_summary = self._chain_moments.ess(mask, thr)
+        s = self.ess_summary
+        for key in ('min', 'mean', f'frac_below_{thr:g}', 'frac_truncated'):
+            self.metrics.update(f'MCMC/ESS/{key}', s[key])
+        self.logger.info(f'split ESS over {s["voxels"]} masked voxels (max_lag {self._chain_moments.max_lag}): '
+                         f'min {s["min"]:.1f}, mean {s["mean"]:.1f}, {100 * s[f"frac_below_{thr:g}"]:.2f} % below {thr:g}, '
+                         f'{100 * s["frac_truncated"]:.2f} % truncated')
+        if save_outputs:
+            save_ess(self.logger, self.config.save_dirs, spacing, self.ess, self.mcse, mask, 'MCMC')
 
     def _run_model(self):
         for fixed, moving, var_params_q_v in self.data_loader:

@@ -139,6 +139,21 @@ def calc_split_rhat(samples, mask=None, thresholds=(1.01, 1.1)):
 
 
 @torch.no_grad()
+def calc_split_ess(samples, mask=None, max_lag=32, threshold=400.0):
+    """split ESS and MCSE of the displacement samples (absent in the reference): samples (C, N, 3, D, H, W) on the device,
+    every chain's N samples in order; mask (D,H,W) or None.  -> (ESS map, MCSE map, summary dict), as
+    diagnostics.ChainMoments.ess."""
+    from ..diagnostics import ChainMoments
+    if samples.dim() != 6 or samples.shape[2] != 3:
+        raise ValueError(f'samples must have shape (C, N, 3, D, H, W), got {tuple(samples.shape)}')
+    C, N = samples.shape[:2]
+    cm = ChainMoments(C, samples.shape[3:], N, samples.device, max_lag=max_lag)
+    for i in range(N):
+        cm.record(samples[:, i].float().contiguous())
+    return cm.ess(mask, threshold)
+
+
+@torch.no_grad()
 def calc_DSC_GPU(no_samples, seg_fixed, seg_moving, structures_dict):
     """Dice scores on the device (utils/util.py:123-148)"""
     DSC = torch.zeros(no_samples, len(structures_dict))
