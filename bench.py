@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- SG-MCMC transitions/s of the HIP path on synthetic volumes (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 256] [--loss gmm|ssd] [--decomp slab|chains] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 256] [--loss gmm|ssd] [--decomp slab|chains] [--dump-outputs DIR] [--full]
 
 A "step" is one full `_SGLD_transition` (noise + Sobolev, 12-step scaling and squaring, warp, LCC/GMM data term with
 virtual decimation, regulariser, backward, SGLD update) over one synthetic fixed/moving pair resident in HBM, with
@@ -14,12 +14,18 @@ chain / max-over-ranks wall time.  `--decomp chains` is the other, trivial, deco
 data-path collective (weak scaling).  Without a launcher (no WORLD_SIZE in the environment) `--gpus N` starts the N ranks
 itself, as child processes of torch.distributed.run, before anything touches a GPU.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the adjoint of one squaring step): algorithmic
-bytes per launch (36 B/voxel: read dL/dd_{k+1} 12 + read d_k 12 + write dL/dd_k 12) over its average duration measured
-with HIP events on the launch stream inside `irs_transition_timed`.  `cpu_baseline` times the CPU oracle (torch, all
-host cores) on a bounded sample and is a reported baseline, not a target.  `also` carries what a registration costs away
-from the headline's best case (N = 1 only): the SSD loss of config 4, a chain started from a displaced field, a chain with a
-sigma-field preconditioner (pSGLD, MCMC_init 'VI'), 128^3 with its own roofline fraction, and a sustained run of >= 500 transitions.
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set up, warm up, time the K steps, write
+`--dump-outputs`, print the line (`value`, `ms_per_step`, `config`, `transition_roofline` from the timed steps, the slab
+set-up for N > 1).  Everything that takes runs of its own comes with `--full`, after the timed steps:
+
+  `roofline` is for the dominant kernel (the adjoint of one squaring step): algorithmic bytes per launch (36 B/voxel: read
+  dL/dd_{k+1} 12 + read d_k 12 + write dL/dd_k 12) over its average duration measured with HIP events on the launch stream
+  inside `irs_transition_timed` (with `exp_step_fwd` and `stage_ms`).  N = 1: the seg-warp speed and `device_copy_GBps`;
+  `cpu_baseline` times the CPU oracle (torch, all host cores) on a bounded sample and is a reported baseline, not a target
+  (`--no-cpu-baseline` skips it).  `also` carries what a registration costs away from the headline's best case (`--no-extras`
+  skips it): the SSD loss of config 4, a chain started from a displaced field, a chain with a sigma-field preconditioner
+  (pSGLD, MCMC_init 'VI'), 128^3 with its own roofline fraction, and a sustained run of >= 500 transitions.  N > 1: every
+  rank's own time per transition and the hand-over timeline of one sampled transition (`slab.round_wait_us`).
 """
 import argparse
 import json
@@ -250,8 +256,12 @@ def main():
                     help='slab mode: interior / boundary split around an exchange (overlap with more launches); auto = time both, keep the faster')
     ap.add_argument('--ghost-max', type=int, default=0, help='slab mode: widest ghost zone of one exchange (0 = library default)')
     ap.add_argument('--watchdog', type=int, default=420, help='N > 1: seconds after which a run that has not finished dumps its stacks and exits (0 = off)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the `also` workloads (SSD, displaced start, 128^3, sustained run)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure what takes runs of its own: per-stage HIP-event timings and the '
+                         'dominant kernel\'s roofline, the seg-warp speed and device copy rate, the CPU baseline, the `also` workloads '
+                         '(N = 1), the per-rank hand-over timeline (N > 1)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the `also` workloads (SSD, displaced start, 128^3, sustained run)')
     ap.add_argument('--cpu-size', type=int, default=256, help='edge of the CPU-baseline volume (capped at --size); 256: one transition takes ~25 s on 16 cores')
     ap.add_argument('--cpu-reps', type=int, default=1)
     ap.add_argument('--cpu-reps-128', type=int, default=5, help='timed 128^3 transitions of the CPU oracle (after 3 warm-up) reported next to the bench-size one; 0 = skip')
@@ -460,6 +470,7 @@ def main():
     slab_diag = None
     if slab:
         slab_status = eng.status()   # mispredictions are reported in the output line (`slab`), not fatal: the chain was repaired
+    if slab and args.full:
         # What makes a first run on a node diagnosable (outside the timed region): every rank's own time per transition, and the
         # hand-over timeline of one more transition on a scratch copy of the field -- per exchange round and all-reduce, how long the
         # communication stream took from "data ready" to "delivered" and how long the compute stream STALLED at the launch that
@@ -487,9 +498,9 @@ def main():
             mine['gather_error'] = f'{type(e).__name__}: {e}'
             slab_diag = [mine]
 
-    # ---- side measurements on rank 0 (outside the timed region) ------------------------------------------------------------
+    # ---- --full: side measurements on rank 0 (outside the timed region) -----------------------------------------------------
     extras = {}
-    if world == 1:
+    if world == 1 and args.full:
         # (1) the reference's own speed definition (trainer.py:467-476): every sample also warps the segmentation
         #     (nearest neighbour) with the sampled transformation
         from ir_sgmcmc_amd.ops import warp
@@ -521,7 +532,7 @@ def main():
 
     # per-stage HIP-event timings of the fused single-GPU launch sequence (rank 0, outside the timed region)
     tm = None
-    if rank == 0:
+    if rank == 0 and args.full:
         timing_eng, tf, tmv, tv = eng, fixed, moving, v
         if slab:  # the slab engine holds slab-local arrays: the events come from a fused engine on the whole volume
             timing_eng = TransitionEngine(engine_config(N, args.loss, 1234), dev)
@@ -543,13 +554,8 @@ def main():
         dist.barrier()
 
     if rank == 0:
-        steps = cfg.no_steps
-        bwd_kernel_ms = tm['exp_bwd_primary_avg_ms']  # mean duration of exp_bwd_march_kernel<false,1> alone (HIP events)
-        fwd_kernel_ms = tm['exp_fwd_ms'] / steps
         ms_per_step = 1e3 * elapsed / args.steps
         value = (1 if slab else world) * args.steps / elapsed
-        achieved = BWD_STEP_BYTES_PER_VOXEL * V / (bwd_kernel_ms * 1e-3) / 1e9
-        traffic, traffic_src = traffic_from_profile(N)
         if slab:
             via = {'rccl': 'RCCL send/recv', 'ipc': 'peer-mapped landing buffers (producer-side stores, sequence flags)' + (' -- all ranks on ONE device' if shared_device else ''),
                    'rehearsal': 'gloo with host staging (one-GPU REHEARSAL of the schedule, not a measurement)'}[transport]
@@ -564,19 +570,26 @@ def main():
             'config': {'workload': workload_name(N, args.loss), 'volume': [N, N, N],
                        'init': args.init + (f' amp {args.init_amp}' if args.init != 'identity' else ''),
                        'chains': 1 if (slab or world == 1) else world, 'parallelism': para},
-            'roofline': {'bound': 'hbm', 'kernel': 'exp_bwd_march_kernel<false,1> (adjoint of one squaring step)',
-                         'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
-                         'traffic': traffic, 'traffic_from_committed_profile': traffic_src,
-                         'algorithmic_bytes_per_launch': BWD_STEP_BYTES_PER_VOXEL * V, 'avg_launch_ms': bwd_kernel_ms,
-                         'measured_on': 'whole volume, one GPU (HIP events around the launch)'},
             'transition_roofline': {'algorithmic_bytes': BYTES_PER_VOXEL[args.loss] * V,
                                     'frac_of_device_copy': (BYTES_PER_VOXEL[args.loss] * V / (ms_per_step * 1e-3) / 1e9 / extras['device_copy_GBps']) if 'device_copy_GBps' in extras else None,
                                     'achieved_GBps': BYTES_PER_VOXEL[args.loss] * V / (ms_per_step * 1e-3) / 1e9,
                                     'frac_of_8TBps': BYTES_PER_VOXEL[args.loss] * V / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS / (world if slab else 1)},
-            'exp_step_fwd': {'avg_launch_ms': fwd_kernel_ms,
-                             'achieved_GBps': FWD_STEP_BYTES_PER_VOXEL * V / (fwd_kernel_ms * 1e-3) / 1e9},
-            'stage_ms': tm, 'workspace_GB': eng.workspace_bytes / 1e9, **extras,
+            'workspace_GB': eng.workspace_bytes / 1e9,
         }
+        if tm is not None:   # --full
+            bwd_kernel_ms = tm['exp_bwd_primary_avg_ms']  # mean duration of exp_bwd_march_kernel<false,1> alone (HIP events)
+            fwd_kernel_ms = tm['exp_fwd_ms'] / cfg.no_steps
+            achieved = BWD_STEP_BYTES_PER_VOXEL * V / (bwd_kernel_ms * 1e-3) / 1e9
+            traffic, traffic_src = traffic_from_profile(N)
+            out['roofline'] = {'bound': 'hbm', 'kernel': 'exp_bwd_march_kernel<false,1> (adjoint of one squaring step)',
+                               'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
+                               'traffic': traffic, 'traffic_from_committed_profile': traffic_src,
+                               'algorithmic_bytes_per_launch': BWD_STEP_BYTES_PER_VOXEL * V, 'avg_launch_ms': bwd_kernel_ms,
+                               'measured_on': 'whole volume, one GPU (HIP events around the launch)'}
+            out['exp_step_fwd'] = {'avg_launch_ms': fwd_kernel_ms,
+                                   'achieved_GBps': FWD_STEP_BYTES_PER_VOXEL * V / (fwd_kernel_ms * 1e-3) / 1e9}
+            out['stage_ms'] = tm
+        out.update(extras)
         if slab_failure:
             out['slab_transport_failure'] = slab_failure
         if slab:
@@ -584,13 +597,15 @@ def main():
             out['slab'] = {'transport': transport, 'transport_info': comm.describe(), 'transport_trials_ms': trials, 'ipc_preflight': preflight_info, 'interior_boundary_split': split_on, 'split_trials_ms': split_trials, 'planes_owned': eng.b - eng.a, 'planes_held': eng.hi - eng.lo, 'ghost_max': eng.ghost_max,
                            'exchange_rounds_per_transition': st['exchanges'] / max(st['transitions'], 1),
                            'MB_sent_per_transition_rank0': st['exchanged_bytes'] / max(st['transitions'], 1) / 1e6,
-                           'exact_transitions': st['exact_transitions'], 'mispredictions': st['mispredictions'],
-                           'ms_per_transition_by_rank': {'min': min(d['ms_per_transition'] for d in slab_diag), 'max': max(d['ms_per_transition'] for d in slab_diag),
-                                                         'all': [round(d['ms_per_transition'], 4) for d in slab_diag]},
-                           # per rank, one sampled transition: [kind + stage ('e' exchange of buffer IRS_SB_*, 'a' all-reduce IRS_AR_*), adjoint step,
-                           # ghost planes, hand-over us on the communication stream, stall us of the compute stream]
-                           'round_wait_us': [{k: d.get(k) for k in ('rank', 'transition_us', 'handover_us', 'stall_us', 'rounds', 'timeline_error', 'gather_error') if k in d} for d in slab_diag]}
-        if world == 1 and not args.no_extras:
+                           'exact_transitions': st['exact_transitions'], 'mispredictions': st['mispredictions']}
+            if slab_diag is not None:   # --full
+                out['slab'].update(
+                    ms_per_transition_by_rank={'min': min(d['ms_per_transition'] for d in slab_diag), 'max': max(d['ms_per_transition'] for d in slab_diag),
+                                               'all': [round(d['ms_per_transition'], 4) for d in slab_diag]},
+                    # per rank, one sampled transition: [kind + stage ('e' exchange of buffer IRS_SB_*, 'a' all-reduce IRS_AR_*), adjoint step,
+                    # ghost planes, hand-over us on the communication stream, stall us of the compute stream]
+                    round_wait_us=[{k: d.get(k) for k in ('rank', 'transition_us', 'handover_us', 'stall_us', 'rounds', 'timeline_error', 'gather_error') if k in d} for d in slab_diag])
+        if args.full and world == 1 and not args.no_extras:
             also = {}
             print('[bench] extras: SSD, displaced start, 128^3, sustained run ...', file=sys.stderr, flush=True)
             del eng
@@ -612,7 +627,7 @@ def main():
                                                                sigma='field, 0.5 everywhere', note='C = 2 chains + pSGLD preconditioner: configs/experiment1 semantics at its own size')
             also['sustained'] = dict(side_run(N, args.loss, 'identity', 0.0, 500, 5, dev), note='500 consecutive transitions from the identity')
             out['also'] = also
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # 3 warm-up + >= 5 timed transitions at 128^3 and >= 1 at 256^3 (the workload itself): both reported,
             # `value` is the one measured at the bench size (or the largest size asked for, scaled by the voxel count)
             n_cpu = min(args.cpu_size, N)

@@ -27,12 +27,26 @@ def _run(args, env_extra, timeout=420, expect_rc=0):
 
 
 def test_bench_one_gpu_line_contract():
-    d = _run(['--gpus', '1', '--size', '64', '--steps', '10', '--warmup', '2', '--no-cpu-baseline', '--no-extras'], {})
+    d = _run(['--gpus', '1', '--size', '64', '--steps', '10', '--warmup', '2', '--no-cpu-baseline', '--no-extras', '--full'], {})
     assert d['n_gpus'] == 1 and d['steps'] == 10 and d['warmup'] == 2 and d['unit'] == 'transitions/s'
     assert d['higher_is_better'] is True and d['vs_baseline'] is None and d['dtype'] == 'f32' and d['data'] == 'synthetic'
     assert abs(d['value'] - 1e3 / d['ms_per_step']) < 1e-6 * d['value']      # value = transitions / max-over-ranks wall time
     assert d['roofline']['bound'] == 'hbm' and 0.0 < d['roofline']['frac'] < 1.0
     assert d['config']['volume'] == [64, 64, 64] and 'workload' in d['config']
+
+
+def test_bench_plain_run_is_lean():
+    """without --full the run is set-up, warm-up, the timed steps and the line: the same headline fields, nothing that takes
+    runs of its own (per-stage events, device copy, seg warp, CPU baseline, side workloads)"""
+    d = _run(['--gpus', '1', '--size', '64', '--steps', '10', '--warmup', '2'], {})
+    assert d['n_gpus'] == 1 and d['steps'] == 10 and d['warmup'] == 2 and d['unit'] == 'transitions/s'
+    assert d['higher_is_better'] is True and d['vs_baseline'] is None and d['dtype'] == 'f32' and d['data'] == 'synthetic'
+    assert d['metric'] == 'SG-MCMC transitions/sec (full _SGLD_transition)'
+    assert abs(d['value'] - 1e3 / d['ms_per_step']) < 1e-6 * d['value']
+    assert d['config']['volume'] == [64, 64, 64] and 'workload' in d['config']
+    for k in ('roofline', 'exp_step_fwd', 'stage_ms', 'device_copy_GBps', 'with_transformation_output_and_seg_warp', 'cpu_baseline', 'also'):
+        assert k not in d, k
+    assert d['transition_roofline']['frac_of_device_copy'] is None and d['transition_roofline']['achieved_GBps'] > 0
 
 
 def test_bench_two_ranks_ipc():
@@ -83,8 +97,8 @@ def test_bench_auto_transport_survives_a_preflight_child_that_dies():
 
 
 def test_bench_four_ranks_ipc():
-    """middle ranks with two neighbours, through the script"""
-    d = _run(['--gpus', '4', '--size', '64', '--steps', '4', '--warmup', '2', '--no-cpu-baseline'], {'IRS_BENCH_DEVICE': '0'})
+    """middle ranks with two neighbours, through the script (--full: with the per-rank times and hand-over timeline)"""
+    d = _run(['--gpus', '4', '--size', '64', '--steps', '4', '--warmup', '2', '--full', '--no-cpu-baseline'], {'IRS_BENCH_DEVICE': '0'})
     assert d['n_gpus'] == 4 and d['scaling'] == 'strong' and d['slab']['transport'] == 'ipc'
     assert d['slab']['planes_owned'] == 16 and d['slab']['mispredictions'] == 0 and d['value'] > 0
     # the self-diagnosis of a first run on a node: every rank's own time, and per hand-over of one sampled transition how long the
