@@ -164,6 +164,31 @@ int irs_split_ess_workspace(int C, int D, int H, int W, size_t* bytes);
 int irs_split_ess(const float* mean, const float* m2, const float* vsum, int C, int n, int L, const uint8_t* mask, float threshold,
                   float* ess, float* mcse, double* summary, void* ws, size_t ws_bytes, int D, int H, int W, void* stream);
 
+/* Posterior label maps of the propagated segmentation (absent in the reference): per-voxel counts of K structures over n
+ * records (one chain's nearest-neighbour warp of the moving segmentation at one recorded step), whatever n is.  Structure j
+ * is label value labels[j] (HOST int32, K in 1 .. IRS_MAX_LABELS, distinct, in the int16 range); every other value of a map,
+ * 0 and negative values included, is the extra class "other".  64-bit indexing throughout.
+ *  - irs_label_posterior_update: seg (C,1,D,H,W) int16, C in 1 .. IRS_MAX_CHAINS; counts (K,D,H,W) int32, += 1 where a record
+ *    carries the structure; volume (K,2) double {mean, M2}: Welford state of the per-record volumes (voxels carrying the
+ *    structure), folded with k = records_before + c + 1 for c = 0 .. C-1 (k = 1 overwrites it).  records_before >= 0 and
+ *    records_before + C <= INT32_MAX.  One stream pass plus a one-block fold; no atomics whose result depends on order.
+ *  - irs_label_posterior_finalize: n >= 1 records; seg_fixed (D,H,W) int16; mask (D,H,W) uint8 or NULL (whole volume).  Per
+ *    voxel, c_other = n - sum_j c_j; entropy (D,H,W) float32: -sum p ln p over the K + 1 classes in nats (in double); map_label
+ *    (D,H,W) int16: the label value of the class with the largest count, ties to the first of (other, structure 0, ...),
+ *    0 for other.  summary (K, 6 + 3*IRS_LABEL_BINS) int64, y = [seg_fixed = labels[j]]: S0 = |y|, S1 = sum c_j,
+ *    S2 = sum c_j y, S3 = |MAP = j|, S4 = |MAP = j and y|, S5 = |0 < c_j < n|, then per bin b = min(c_j B / n, B - 1) of the
+ *    pairs with c_j > 0 or y: pairs, sum c_j, sum y.  mask_summary: 4 doubles {voxels in the mask, sum of the stored entropy
+ *    over them, its max (0 when empty), voxels anywhere with sum_j c_j > n (non-zero: n is wrong)}.
+ *    Deterministic (exact integer sums, fixed-order float sums); no host sync.
+ *  ws: device workspace of irs_label_posterior_workspace bytes (it covers both calls for the same C, K and volume). */
+#define IRS_LABEL_BINS 10
+int irs_label_posterior_workspace(int C, int K, int D, int H, int W, size_t* bytes);
+int irs_label_posterior_update(const int16_t* seg, int C, int D, int H, int W, const int32_t* labels, int K, int32_t* counts,
+                               double* volume, int records_before, void* ws, size_t ws_bytes, void* stream);
+int irs_label_posterior_finalize(const int32_t* counts, int K, int D, int H, int W, int n, const int32_t* labels,
+                                 const int16_t* seg_fixed, const uint8_t* mask, float* entropy, int16_t* map_label,
+                                 long long* summary, double* mask_summary, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * fused transition (Trainer._SGLD_transition, trainer/trainer.py:291-356)
  * ---------------------------------------------------------------------------------------------- */

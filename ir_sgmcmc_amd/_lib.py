@@ -16,6 +16,7 @@ IRS_MAX_COMPONENTS = 8
 IRS_MAX_CHAINS = 8
 IRS_MAX_HALF_WIDTH = 4
 IRS_MAX_LABELS = 64
+IRS_LABEL_BINS = 10
 IRS_DATA_GMM_LCC, IRS_DATA_SSD = 0, 1
 IRS_REG_L2, IRS_REG_LOGNORMAL, IRS_REG_STUDENT, IRS_REG_LOGNORMAL_L2 = 0, 1, 2, 3
 
@@ -138,6 +139,9 @@ SIGNATURES = {
     'irs_chain_variogram_update': [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     'irs_split_ess_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
     'irs_split_ess': [_P, _P, _P, _I, _I, _I, _P, C.c_float, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _P],
+    'irs_label_posterior_workspace': [_I, _I, _I, _I, _I, C.POINTER(C.c_size_t)],
+    'irs_label_posterior_update': [_P, _I, _I, _I, _I, _I32P, _I, _P, _P, _I, _P, C.c_size_t, _P],
+    'irs_label_posterior_finalize': [_P, _I, _I, _I, _I, _I, _I32P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],
     'irs_create': [C.POINTER(IrsConfig), C.POINTER(_P)],
     'irs_destroy': [_P],
     'irs_workspace_bytes': [_P],

@@ -690,6 +690,85 @@ int irs_split_ess(const float* mean, const float* m2, const float* vsum, int C, 
 }
 
 // ================================================================================================
+// posterior label maps (label_kernels.hip)
+// ================================================================================================
+}  // extern "C"
+
+namespace {
+
+// the volume of a label-posterior call: dims of at least 1 (a record may be one row of voxels), < 2^30 voxels
+bool label_dims_ok(int D, int H, int W) { return D >= 1 && H >= 1 && W >= 1 && (int64_t)D * H * W < ((int64_t)1 << 30); }
+
+// 1 .. IRS_MAX_LABELS distinct labels in the int16 range -> lab
+int label_table(const char* who, const int32_t* labels, int K, SurfLabels* lab) {
+    if (!labels_ok(labels, K)) return fail("%s: 1..%d labels in the int16 range", who, IRS_MAX_LABELS);
+    for (int i = 0; i < K; ++i)
+        for (int j = 0; j < i; ++j)
+            if (labels[i] == labels[j]) return fail("%s: label %d appears twice", who, labels[i]);
+    *lab = SurfLabels{};
+    memcpy(lab->v, labels, sizeof(int32_t) * K);
+    return 0;
+}
+
+size_t label_update_ws(int C, int K, int64_t V) { return sizeof(int32_t) * (size_t)C * K * label_update_partials_blocks(V); }
+
+size_t label_finalize_ws(int K, int64_t V) {
+    return (sizeof(long long) * (size_t)K * (6 + 3 * IRS_LABEL_BINS) + 4 * sizeof(double)) * label_finalize_blocks(V);
+}
+
+}  // namespace
+
+extern "C" {
+
+int irs_label_posterior_workspace(int C, int K, int D, int H, int W, size_t* bytes) {
+    if (!bytes || C < 1 || C > IRS_MAX_CHAINS || K < 1 || K > IRS_MAX_LABELS || !label_dims_ok(D, H, W))
+        return fail("irs_label_posterior_workspace: bad arguments");
+    const int64_t V = (int64_t)D * H * W;
+    *bytes = std::max(label_update_ws(C, K, V), label_finalize_ws(K, V));
+    return 0;
+}
+
+int irs_label_posterior_update(const int16_t* seg, int C, int D, int H, int W, const int32_t* labels, int K, int32_t* counts,
+                               double* volume, int records_before, void* ws, size_t ws_bytes, void* stream) {
+    if (!seg || !counts || !volume || !ws || !label_dims_ok(D, H, W)) return fail("irs_label_posterior_update: bad arguments");
+    if (C < 1 || C > IRS_MAX_CHAINS) return fail("irs_label_posterior_update: C = %d chains, 1..%d", C, IRS_MAX_CHAINS);
+    if (records_before < 0) return fail("irs_label_posterior_update: records_before = %d < 0", records_before);
+    if ((int64_t)records_before + C > INT32_MAX)
+        return fail("irs_label_posterior_update: %d records + %d chains overflow the int32 record count", records_before, C);
+    SurfLabels lab;
+    if (label_table("irs_label_posterior_update", labels, K, &lab)) return 1;
+    const int64_t V = (int64_t)D * H * W;
+    const size_t need = label_update_ws(C, K, V);
+    if (ws_bytes < need)
+        return fail("irs_label_posterior_update: workspace of %zu bytes, %zu needed (irs_label_posterior_workspace)", ws_bytes, need);
+    launch_label_update(seg, C, V, lab, K, counts, volume, records_before, (int32_t*)ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_label_posterior_finalize(const int32_t* counts, int K, int D, int H, int W, int n, const int32_t* labels,
+                                 const int16_t* seg_fixed, const uint8_t* mask, float* entropy, int16_t* map_label,
+                                 long long* summary, double* mask_summary, void* ws, size_t ws_bytes, void* stream) {
+    if (!counts || !seg_fixed || !entropy || !map_label || !summary || !mask_summary || !ws || !label_dims_ok(D, H, W))
+        return fail("irs_label_posterior_finalize: bad arguments");
+    if (n < 1) return fail("irs_label_posterior_finalize: n = %d records, at least 1 needed", n);
+    SurfLabels lab;
+    if (label_table("irs_label_posterior_finalize", labels, K, &lab)) return 1;
+    const int64_t V = (int64_t)D * H * W;
+    const size_t need = label_finalize_ws(K, V);
+    if (ws_bytes < need)
+        return fail("irs_label_posterior_finalize: workspace of %zu bytes, %zu needed (irs_label_posterior_workspace)", ws_bytes,
+                    need);
+    const int blocks = label_finalize_blocks(V);
+    long long* partials = (long long*)ws;
+    double* dpartials = (double*)(partials + (size_t)K * (6 + 3 * IRS_LABEL_BINS) * blocks);
+    launch_label_finalize(counts, K, V, n, lab, seg_fixed, mask, entropy, map_label, summary, mask_summary, partials, dpartials,
+                          (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // context
 // ================================================================================================
 

@@ -165,6 +165,19 @@ void launch_chain_variogram(const float* x, float* ring, float* vsum, int C, int
 void launch_split_ess(const float* mean, const float* m2, const float* vsum, int C, int n, int L, const uint8_t* mask, float thr,
                       float* ess, float* mcse, double* summary, double* partials, int64_t V, hipStream_t st);
 
+// ---- label_kernels.hip: posterior label maps of the propagated segmentation (absent in the reference)
+// seg (C,V) int16; counts (K,V) int32, += 1 per record; volume (K,2) double {mean, M2} of the per-record volumes, folded with
+// k = records_before + c + 1; partials: C * K int32 per block of the update (label_update_partials_blocks(V) blocks at most)
+int label_update_partials_blocks(int64_t V);
+void launch_label_update(const int16_t* seg, int C, int64_t V, const SurfLabels& lab, int K, int32_t* counts, double* volume,
+                         int records_before, int32_t* partials, hipStream_t st);
+// entropy (V) float32, map_label (V) int16, summary (K, 6 + 3 * IRS_LABEL_BINS) int64, mask_summary 4 doubles;
+// partials: K * (6 + 3 * IRS_LABEL_BINS) int64 and dpartials: 4 doubles per block (label_finalize_blocks(V) blocks)
+int label_finalize_blocks(int64_t V);
+void launch_label_finalize(const int32_t* counts, int K, int64_t V, int n, const SurfLabels& lab, const int16_t* seg_fixed,
+                           const uint8_t* mask, float* entropy, int16_t* map_label, long long* summary, double* mask_summary,
+                           long long* partials, double* dpartials, hipStream_t st);
+
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h
 }  // namespace irs

@@ -9,9 +9,15 @@ number of samples.  At the end, ops.split_rhat turns the 2C sequences into the c
 With ESS on, a ring of the last L samples and the lag sums of squared differences (the variogram) are kept as well
 (ops.chain_variogram_update): 4 * L * (C + 1) * 3 * D * H * W more bytes.  ops.split_ess turns them and the moments into
 BDA3's split ESS (section 11.5) with its truncation rule, and the MCSE sqrt(var+ / ESS).
+
+The posterior label maps (LabelPosterior) follow the same pattern for the propagated segmentation: per-voxel counts of every
+structure over the recorded warps (ops.label_posterior_update), 4 * K * D * H * W bytes whatever the number of records, and
+at the end the entropy and MAP maps, soft Dice, Dice of the MAP, volume spread and calibration (ops.label_posterior_finalize).
 """
 import math
 import numbers
+
+import numpy as np
 
 import torch
 
@@ -209,3 +215,149 @@ class ChainMoments:
             self.ring.copy_(sd['ring'])
             self.vsum.copy_(sd['vsum'])
         self.count = int(sd['count'])
+
+
+LABEL_OPTION_KEYS = ('period', 'prob_maps')
+LABEL_STRUCTURE_METRICS = ('soft_DSC', 'DSC_MAP', 'vol_mean', 'vol_std', 'uncertain_vol', 'ECE')
+MAX_RECORDS = 2 ** 31 - 1  # the int32 counts
+
+
+def label_posterior_options(cfg_trainer):
+    """`trainer.label_posterior` -> None when off, else {'period': P, 'prob_maps': bool}.
+    Absent / false / null: off.  true: P = log_period_MCMC.  {"period": P, "prob_maps": bool}: either key may be left out.
+    Refuses unknown keys, a non-integer P or P < 1, a non-bool prob_maps, a config that records no step
+    (no_samples_MCMC // P < 1) and one that would record more than 2^31 - 1 maps."""
+    opt = cfg_trainer.get('label_posterior', False)
+    if opt is None or opt is False:
+        return None
+    out = {'period': None, 'prob_maps': False}
+    if isinstance(opt, dict):
+        unknown = set(opt) - set(LABEL_OPTION_KEYS)
+        if unknown:
+            raise ValueError(f'trainer.label_posterior: unknown keys {sorted(unknown)}; known: {list(LABEL_OPTION_KEYS)}')
+        if 'period' in opt:
+            p = opt['period']
+            if isinstance(p, bool) or not isinstance(p, numbers.Integral):
+                raise ValueError(f'trainer.label_posterior.period must be an integer, got {p!r}')
+            out['period'] = int(p)
+        if 'prob_maps' in opt:
+            if not isinstance(opt['prob_maps'], bool):
+                raise ValueError(f'trainer.label_posterior.prob_maps must be true or false, got {opt["prob_maps"]!r}')
+            out['prob_maps'] = opt['prob_maps']
+    elif opt is not True:
+        raise ValueError(f'trainer.label_posterior must be true, false or {{"period": P, "prob_maps": bool}}, got {opt!r}')
+    if out['period'] is None:
+        out['period'] = int(cfg_trainer['log_period_MCMC'])
+    if out['period'] < 1:
+        raise ValueError(f'trainer.label_posterior: the period must be >= 1, got {out["period"]}')
+    no_samples = int(cfg_trainer['no_samples_MCMC'])
+    steps = no_samples // out['period']
+    if steps < 1:
+        raise ValueError(f'trainer.label_posterior: no_samples_MCMC = {no_samples} with period {out["period"]} records no step')
+    records = steps * int(cfg_trainer.get('no_chains', 1))
+    if records > MAX_RECORDS:
+        raise ValueError(f'trainer.label_posterior: {steps} steps of {cfg_trainer.get("no_chains", 1)} chains are {records} '
+                         f'records; the counts hold at most {MAX_RECORDS}')
+    return out
+
+
+def _nan_div(a, b):
+    return a / b if b else float('nan')
+
+
+def label_summary(raw, volume, n, mask_summary, names, spacing):
+    """the derived quantities of DESIGN.md section 6 from the finalize's integer sums (host numpy / floats):
+    raw (K, 6 + 3B) int64, volume (K, 2) float64 {mean, M2}, n records, mask_summary {voxels, entropy sum, max, ...},
+    spacing (sx, sy, sz) -> {'records', 'voxels', 'entropy_mean', 'entropy_max', 'ECE', 'structures': {name: {soft_DSC,
+    DSC_MAP, vol_mean, vol_std, uncertain_vol, ECE}}}"""
+    raw = np.asarray(raw, dtype=np.int64)
+    volume = np.asarray(volume, dtype=np.float64)
+    v = float(np.prod([float(x) for x in spacing]))
+    bins = raw[:, 6:].reshape(len(names), -1, 3)  # (K, B, {pairs, sum c, sum y})
+    structures = {}
+    for j, name in enumerate(names):
+        S0, S1, S2, S3, S4, S5 = (int(x) for x in raw[j, :6])
+        pairs = int(bins[j, :, 0].sum())
+        ece = float(np.abs(bins[j, :, 1] / n - bins[j, :, 2]).sum())
+        structures[name] = {'soft_DSC': _nan_div(2.0 * S2, S1 + n * S0), 'DSC_MAP': _nan_div(2.0 * S4, S3 + S0),
+                            'vol_mean': float(volume[j, 0]) * v,
+                            'vol_std': math.sqrt(float(volume[j, 1]) / max(n - 1, 1)) * v,
+                            'uncertain_vol': S5 * v, 'ECE': _nan_div(ece, pairs)}
+    pooled = bins.sum(axis=0)
+    voxels = int(mask_summary[0])
+    return {'records': int(n), 'voxels': voxels,
+            'entropy_mean': _nan_div(float(mask_summary[1]), voxels),
+            'entropy_max': float(mask_summary[2]) if voxels else float('nan'),
+            'ECE': _nan_div(float(np.abs(pooled[:, 1] / n - pooled[:, 2]).sum()), int(pooled[:, 0].sum())),
+            'structures': structures}
+
+
+class LabelPosterior:
+    """Per-voxel counts of every structure of `structures_dict` over the recorded warps of the moving segmentation, and the
+    Welford moments of each structure's per-record volume, on the device (4 K D H W + 16 K bytes whatever the number of
+    records).  `record(seg_warped)` takes the (C,1,D,H,W) int16 maps of one step, chains in order; `finalize` gives the
+    entropy and MAP maps and the summary; `probabilities()` the (K,D,H,W) label probabilities."""
+
+    def __init__(self, structures_dict, dims, device):
+        self.names = list(structures_dict)
+        self.labels = [int(structures_dict[k]) for k in self.names]
+        if not 1 <= len(self.labels) <= 64:
+            raise ValueError(f'label posterior: 1 to 64 structures, got {len(self.labels)}')
+        if len(set(self.labels)) != len(self.labels):
+            raise ValueError(f'label posterior: the label values {self.labels} are not distinct')
+        self.dims = tuple(int(d) for d in dims)
+        self.device = device
+        self.counts = torch.zeros((len(self.labels), *self.dims), device=device, dtype=torch.int32)
+        self.volume = torch.zeros((len(self.labels), 2), device=device, dtype=torch.float64)
+        self.records = 0
+
+    def record(self, seg_warped):
+        C = seg_warped.shape[0]
+        if self.records + C > MAX_RECORDS:
+            raise ValueError(f'label posterior: {self.records} + {C} records exceed {MAX_RECORDS}')
+        ops.label_posterior_update(seg_warped, self.labels, self.counts, self.volume, self.records)
+        self.records += C
+
+    def finalize(self, seg_fixed, mask=None, spacing=(1.0, 1.0, 1.0)):
+        """-> (entropy (D,H,W) float32, map_label (D,H,W) int16, both on the device, summary dict of label_summary).
+        The entropy statistics are over `mask` (the FIXED mask: the maps live on the fixed grid).  One device-to-host read."""
+        from . import _lib as L
+        if self.records < 1:
+            raise RuntimeError('LabelPosterior.finalize: nothing recorded')
+        if mask is not None:
+            mask = mask.to(self.device)
+            mask = mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
+        entropy, map_label, raw, ms = ops.label_posterior_finalize(self.counts, self.records, self.labels,
+                                                                   seg_fixed.to(self.device), mask)
+        host = torch.cat([raw.reshape(-1).view(torch.float64), ms, self.volume.reshape(-1)]).cpu()
+        KC = raw.numel()
+        raw_h = host[:KC].view(torch.int64).reshape(raw.shape).numpy()
+        ms_h = host[KC:KC + 4].numpy()
+        vol_h = host[KC + 4:].reshape(-1, 2).numpy()
+        if ms_h[3] != 0:
+            raise L.IrsError(f'label posterior: {int(ms_h[3])} voxels hold more than the {self.records} records counted: '
+                             f'the counts and the record number disagree')
+        summary = label_summary(raw_h, vol_h, self.records, ms_h, self.names,
+                                spacing.tolist() if hasattr(spacing, 'tolist') else spacing)
+        summary['raw'] = raw_h
+        return entropy, map_label, summary
+
+    def probabilities(self):
+        """-> (K,D,H,W) float32 on the device: counts / n"""
+        if self.records < 1:
+            raise RuntimeError('LabelPosterior.probabilities: nothing recorded')
+        return self.counts.float() / self.records
+
+    def state_dict(self):
+        return {'counts': self.counts.detach().cpu(), 'volume': self.volume.detach().cpu(), 'records': self.records,
+                'labels': list(self.labels)}
+
+    def load_state_dict(self, sd):
+        if [int(x) for x in sd['labels']] != self.labels:
+            raise ValueError(f'label posterior of labels {list(sd["labels"])} does not match this run ({self.labels})')
+        if tuple(sd['counts'].shape) != tuple(self.counts.shape):
+            raise ValueError(f'label posterior of shape {tuple(sd["counts"].shape)} does not match this run '
+                             f'({tuple(self.counts.shape)})')
+        self.counts.copy_(sd['counts'])
+        self.volume.copy_(sd['volume'])
+        self.records = int(sd['records'])

@@ -125,3 +125,18 @@ def save_ess(logger, save_dirs, spacing, ess, mcse, mask, model='MCMC'):
     for name, im in (('ess', ess), ('mcse', mcse)):
         save_im_to_disk(im, path.join(folder, f'{model}_{name}.nii.gz'), spacing)
         save_im_to_disk(im.where(mask, im.new_zeros(())), path.join(folder, f'{model}_{name}_masked.nii.gz'), spacing)
+
+
+def save_label_posterior(logger, save_dirs, spacing, entropy, map_label, mask, prob=None, names=(), model='MCMC'):
+    """posterior label maps of the propagated segmentation (absent in the reference): samples/{model}_seg_entropy.nii.gz,
+    {model}_seg_entropy_masked.nii.gz (0 outside the FIXED mask), {model}_seg_MAP.nii.gz (int16) and, with `prob` (K,D,H,W),
+    {model}_seg_prob_{name}.nii.gz (float32) per structure"""
+    folder = _folder(save_dirs, 'samples')
+    mask = mask.reshape(entropy.shape).to(entropy.device) != 0
+    logger.info(f'{model} segmentation entropy max.: {float(entropy.max()):.4f} nats')
+    save_im_to_disk(entropy, path.join(folder, f'{model}_seg_entropy.nii.gz'), spacing)
+    save_im_to_disk(entropy.where(mask, entropy.new_zeros(())), path.join(folder, f'{model}_seg_entropy_masked.nii.gz'), spacing)
+    save_im_to_disk(map_label, path.join(folder, f'{model}_seg_MAP.nii.gz'), spacing)
+    if prob is not None:
+        for name, p in zip(names, prob):
+            save_im_to_disk(p, path.join(folder, f'{model}_seg_prob_{name}.nii.gz'), spacing)

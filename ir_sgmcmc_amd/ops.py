@@ -322,3 +322,65 @@ def split_ess(mean, m2, vsum, n, mask=None, threshold=400.0):
                               int(n), vsum.shape[0], L.dev_ptr(mask, torch.uint8, True), float(threshold), L.dev_ptr(ess),
                               L.dev_ptr(mcse), L.dev_ptr(summary), L.dev_ptr(ws), nbytes.value, D, H, W, L.stream_ptr()))
     return ess, mcse, summary
+
+
+def _label_table(labels):
+    labels = [int(x) for x in labels]
+    return (C.c_int32 * max(len(labels), 1))(*labels), len(labels)
+
+
+def label_posterior_update(seg_warped, labels, counts, volume, records_before):
+    """Fold one recorded step into the posterior label maps (absent in the reference): seg_warped (C,1,D,H,W) int16, every
+    chain's nearest-neighbour warp of the moving segmentation; labels: the K label values; counts (K,D,H,W) int32 += 1 where
+    a map carries the structure; volume (K,2) float64 {mean, M2} of the per-record volumes, Welford-folded in chain order
+    after `records_before` records.  No host synchronisation."""
+    lib = L.load()
+    if seg_warped.dim() != 5 or seg_warped.shape[1] != 1:
+        raise L.IrsError(f'seg_warped must have shape (C,1,D,H,W), got {tuple(seg_warped.shape)}')
+    Cn, D, H, W = seg_warped.shape[0], *seg_warped.shape[2:]
+    lab, K = _label_table(labels)
+    if tuple(counts.shape) != (K, D, H, W) or counts.dtype != torch.int32:
+        raise L.IrsError(f'counts must be a ({K},{D},{H},{W}) int32 tensor, got {counts.dtype} {tuple(counts.shape)}')
+    if tuple(volume.shape) != (K, 2) or volume.dtype != torch.float64:
+        raise L.IrsError(f'volume must be a ({K},2) float64 tensor, got {volume.dtype} {tuple(volume.shape)}')
+    nbytes = C.c_size_t()
+    L.check(lib.irs_label_posterior_workspace(Cn, K, D, H, W, C.byref(nbytes)))
+    ws = torch.empty(nbytes.value, device=seg_warped.device, dtype=torch.uint8)
+    L.check(lib.irs_label_posterior_update(L.dev_ptr(seg_warped, torch.int16), Cn, D, H, W, lab, K,
+                                           L.dev_ptr(counts, torch.int32), L.dev_ptr(volume, torch.float64), int(records_before),
+                                           L.dev_ptr(ws), nbytes.value, L.stream_ptr()))
+
+
+def label_posterior_finalize(counts, n, labels, seg_fixed, mask=None):
+    """Entropy and MAP maps and the whole-volume sums of the posterior label maps after n records (absent in the reference).
+    counts (K,D,H,W) int32; seg_fixed (D,H,W) int16 (a leading (1,1) is accepted); mask (D,H,W) bool / uint8 or None.
+    -> (entropy (D,H,W) float32, map_label (D,H,W) int16, summary (K, 6 + 3 * IRS_LABEL_BINS) int64, mask_summary (4,)
+    float64), all on the device: include/irsgmcmc.h gives the columns.  No host synchronisation."""
+    lib = L.load()
+    if counts.dim() != 4:
+        raise L.IrsError(f'counts must have shape (K,D,H,W), got {tuple(counts.shape)}')
+    K, D, H, W = counts.shape
+    lab, nl = _label_table(labels)
+    if nl != K:
+        raise L.IrsError(f'{nl} labels for {K} count planes')
+    if seg_fixed.numel() != D * H * W or seg_fixed.shape[-3:] != (D, H, W):
+        raise L.IrsError(f'seg_fixed must be a ({D},{H},{W}) volume, got {tuple(seg_fixed.shape)}')
+    seg_fixed = seg_fixed.reshape(D, H, W).contiguous()
+    if mask is not None:
+        if mask.numel() != D * H * W or mask.dtype not in (torch.bool, torch.uint8):
+            raise L.IrsError(f'mask must be a bool / uint8 ({D},{H},{W}) volume, got {mask.dtype} {tuple(mask.shape)}')
+        mask = mask.reshape(D, H, W).contiguous()
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    nbytes = C.c_size_t()
+    L.check(lib.irs_label_posterior_workspace(1, K, D, H, W, C.byref(nbytes)))
+    dev = counts.device
+    ws = torch.empty(nbytes.value, device=dev, dtype=torch.uint8)
+    entropy = torch.empty((D, H, W), device=dev, dtype=torch.float32)
+    map_label = torch.empty((D, H, W), device=dev, dtype=torch.int16)
+    summary = torch.empty((K, 6 + 3 * L.IRS_LABEL_BINS), device=dev, dtype=torch.int64)
+    mask_summary = torch.empty(4, device=dev, dtype=torch.float64)
+    L.check(lib.irs_label_posterior_finalize(L.dev_ptr(counts, torch.int32), K, D, H, W, int(n), lab,
+                                             L.dev_ptr(seg_fixed, torch.int16), L.dev_ptr(mask, torch.uint8, True),
+                                             L.dev_ptr(entropy), L.dev_ptr(map_label), L.dev_ptr(summary),
+                                             L.dev_ptr(mask_summary), L.dev_ptr(ws), nbytes.value, L.stream_ptr()))
+    return entropy, map_label, summary, mask_summary

@@ -11,7 +11,7 @@ from pathlib import Path
 import numpy as np
 
 from .data_loader import data_loaders as module_data
-from .diagnostics import diagnostics_period, ess_options
+from .diagnostics import LABEL_STRUCTURE_METRICS, diagnostics_period, ess_options, label_posterior_options
 from .logger import setup_logging
 from .model import distributions as model_distr
 from .model import loss as model_loss
@@ -96,6 +96,10 @@ class ConfigParser:
             ess = ess_options(self['trainer'])
             if ess is not None:
                 m += [f'MCMC/ESS/{k}' for k in ('min', 'mean', f'frac_below_{ess["threshold"]:g}', 'frac_truncated')]
+        if label_posterior_options(self['trainer']) is not None:
+            for s in self.structures_dict:
+                m += [f'MCMC/seg/{s}/{k}' for k in LABEL_STRUCTURE_METRICS]
+            m += [f'MCMC/seg/{k}' for k in ('entropy_mean', 'entropy_max', 'ECE')]
         return m
 
     def init_transformation_and_registration_modules(self):

@@ -17,9 +17,10 @@ import numpy as np
 import torch
 
 from ..base import BaseTrainer
-from ..diagnostics import ChainMoments, diagnostics_period, ess_options, is_recorded
+from ..diagnostics import (ChainMoments, LABEL_STRUCTURE_METRICS, LabelPosterior, diagnostics_period, ess_options, is_recorded,
+                           label_posterior_options)
 from ..engine import EngineConfig, TransitionEngine
-from ..logger import save_displacement_mean_and_std_dev, save_ess, save_rhat, save_sample
+from ..logger import save_displacement_mean_and_std_dev, save_ess, save_label_posterior, save_rhat, save_sample
 from ..utils import calc_norm, calc_no_non_diffeomorphic_voxels, calc_metrics, sample_q_v
 from .vi import VIMixin
 
@@ -64,6 +65,11 @@ class Trainer(VIMixin, BaseTrainer):
         # split ESS / MCSE on top of it: None when its "ess" key is off
         self.ess_options = ess_options(cfg_trainer)
         self.ess, self.mcse, self.ess_summary = None, None, None
+        # posterior label maps of the propagated segmentation (diagnostics.LabelPosterior): None when trainer.label_posterior
+        # is off
+        self.label_options = label_posterior_options(cfg_trainer)
+        self._label_posterior = None
+        self.label_entropy, self.label_map, self.label_summary = None, None, None
 
     # ---------------------------------------------------------------- engine plumbing
     def _engine_config(self):
@@ -160,7 +166,8 @@ class Trainer(VIMixin, BaseTrainer):
                 'sample_no': getattr(self, '_sample_no', 0),
                 'moments': {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in getattr(self, '_moments', {}).items()},
                 'config_name': self.config['name'],
-                **({'chain_moments': self._chain_moments.state_dict()} if self._chain_moments is not None else {})}
+                **({'chain_moments': self._chain_moments.state_dict()} if self._chain_moments is not None else {}),
+                **({'label_posterior': self._label_posterior.state_dict()} if self._label_posterior is not None else {})}
 
     def load_state_dict(self, sd):
         import ctypes
@@ -185,6 +192,14 @@ class Trainer(VIMixin, BaseTrainer):
                 raise ValueError(f'the checkpoint at sample {self._sample_no} holds no chain moments (written with '
                                  f'trainer.convergence_diagnostics off) but this run records from sample '
                                  f'{self.no_iters_burn_in + self.diagnostics_period} on')
+        if self._label_posterior is not None:
+            period = self.label_options['period']
+            if 'label_posterior' in sd:
+                self._label_posterior.load_state_dict(sd['label_posterior'])
+            elif any(is_recorded(s, self.no_iters_burn_in, period) for s in range(1, self._sample_no + 1)):
+                raise ValueError(f'the checkpoint at sample {self._sample_no} holds no label posterior (written with '
+                                 f'trainer.label_posterior off) but this run records from sample '
+                                 f'{self.no_iters_burn_in + period} on')
         self.sync_parameters()
 
     def save_checkpoint(self, file_path):
@@ -292,6 +307,11 @@ class Trainer(VIMixin, BaseTrainer):
             self._chain_moments = ChainMoments(self.no_chains, self._outputs['displacement'].shape[2:],
                                                self.no_samples_MCMC // self.diagnostics_period, self.device,
                                                max_lag=self.ess_options['max_lag'] if self.ess_options else None)
+        if self.label_options is not None:
+            if 'seg' not in fixed or 'seg' not in moving:
+                raise ValueError('trainer.label_posterior needs the fixed and the moving segmentation ("seg" in both); '
+                                 f'fixed has {sorted(fixed)}, moving has {sorted(moving)}')
+            self._label_posterior = LabelPosterior(self.structures_dict, self._outputs['displacement'].shape[2:], self.device)
         if cfg_trainer.get('resume'):
             self.load_checkpoint(cfg_trainer['resume'])
             first = self._sample_no + 1
@@ -304,6 +324,7 @@ class Trainer(VIMixin, BaseTrainer):
             loss_terms, output, aux = self._SGLD_transition(fixed, moving, data_loss, reg_loss, like_reference=False)
             if sample_no == self.no_iters_burn_in:
                 log('ENDED BURNING IN')
+            seg_warped = None  # the warped segmentation of this step, when the Dice / ASD branch builds it
             self.writer.set_step(sample_no)
             if (sample_no - 1) % every == 0:
                 st = self.sync_parameters()
@@ -356,6 +377,11 @@ class Trainer(VIMixin, BaseTrainer):
             if self._chain_moments is not None and is_recorded(sample_no, self.no_iters_burn_in, self.diagnostics_period):
                 self.engine.flush()  # as above: the buffer holds sample `sample_no` once nothing is pending
                 self._chain_moments.record(output['displacement'])
+            if self._label_posterior is not None and is_recorded(sample_no, self.no_iters_burn_in, self.label_options['period']):
+                self.engine.flush()  # as above
+                if seg_warped is None:
+                    seg_warped = self.registration_module(moving['seg'], output['transformation'])
+                self._label_posterior.record(seg_warped)
             if checkpoint_period and sample_no % checkpoint_period == 0:
                 self._sample_no, self._moments = sample_no, {'mean': mean, 'm2': m2, 'n': n_rec}
                 folder = self.config.save_dirs['checkpoints']
@@ -369,6 +395,8 @@ class Trainer(VIMixin, BaseTrainer):
                                                self.displacement_std, moving.get('mask', fixed['mask'])[0].to(mean.dtype), 'MCMC')  # trainer.py:461-462: the MOVING mask
         if self._chain_moments is not None:
             self._finish_diagnostics(moving.get('mask', fixed['mask'])[0], spacing, cfg_trainer.get('save_outputs', True))
+        if self._label_posterior is not None:
+            self._finish_label_posterior(fixed, spacing, cfg_trainer.get('save_outputs', True))
 
         # speed test (trainer.py:467-476): 100 x [transition + nearest-neighbour warp of the segmentation]
         n_speed = 100
@@ -408,6 +436,26 @@ class Trainer(VIMixin, BaseTrainer):
                          f'{100 * s["frac_truncated"]:.2f} % truncated')
         if save_outputs:
             save_ess(self.logger, self.config.save_dirs, spacing, self.ess, self.mcse, mask, 'MCMC')
+
+    def _finish_label_posterior(self, fixed, spacing, save_outputs):
+        """entropy and MAP maps of the propagated segmentation and their summary -> self.label_entropy / label_map /
+        label_summary, the MCMC/seg/* metrics and, with save_outputs, samples/MCMC_seg_*.nii.gz.  The maps live on the fixed
+        grid, so the entropy statistics are over the FIXED mask (the std map uses the moving one)."""
+        mask = fixed['mask'][0]
+        lp = self._label_posterior
+        self.label_entropy, self.label_map, self.label_summary = lp.finalize(fixed['seg'][0], mask, spacing)
+        s = self.label_summary
+        for name, st in s['structures'].items():
+            for key in LABEL_STRUCTURE_METRICS:
+                self.metrics.update(f'MCMC/seg/{name}/{key}', st[key])
+        for key in ('entropy_mean', 'entropy_max', 'ECE'):
+            self.metrics.update(f'MCMC/seg/{key}', s[key])
+        self.logger.info(f'label posterior of {s["records"]} warped segmentations: entropy over {s["voxels"]} masked voxels '
+                         f'mean {s["entropy_mean"]:.4f}, max {s["entropy_max"]:.4f} nats; pooled ECE {s["ECE"]:.4f}')
+        if save_outputs:
+            prob = lp.probabilities() if self.label_options['prob_maps'] else None
+            save_label_posterior(self.logger, self.config.save_dirs, spacing, self.label_entropy, self.label_map, mask, prob,
+                                 lp.names, 'MCMC')
 
     def _run_model(self):
         for fixed, moving, var_params_q_v in self.data_loader:

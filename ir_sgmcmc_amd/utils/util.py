@@ -154,6 +154,21 @@ def calc_split_ess(samples, mask=None, max_lag=32, threshold=400.0):
 
 
 @torch.no_grad()
+def calc_label_posterior(seg_samples, seg_fixed, structures_dict, spacing, mask=None):
+    """posterior label maps of segmentation samples (absent in the reference): seg_samples (C, N, 1, D, H, W) int16 on the
+    device, every chain's N warped maps in order (recorded step by step, chains in order within a step); seg_fixed (D,H,W)
+    int16; mask (D,H,W) or None.  -> (entropy, map_label, summary dict), as diagnostics.LabelPosterior.finalize."""
+    from ..diagnostics import LabelPosterior
+    if seg_samples.dim() != 6 or seg_samples.shape[2] != 1:
+        raise ValueError(f'seg_samples must have shape (C, N, 1, D, H, W), got {tuple(seg_samples.shape)}')
+    C, N = seg_samples.shape[:2]
+    lp = LabelPosterior(structures_dict, seg_samples.shape[3:], seg_samples.device)
+    for i in range(N):
+        lp.record(seg_samples[:, i].contiguous())
+    return lp.finalize(seg_fixed, mask, spacing)
+
+
+@torch.no_grad()
 def calc_DSC_GPU(no_samples, seg_fixed, seg_moving, structures_dict):
     """Dice scores on the device (utils/util.py:123-148)"""
     DSC = torch.zeros(no_samples, len(structures_dict))
