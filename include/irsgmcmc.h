@@ -189,6 +189,32 @@ int irs_label_posterior_finalize(const int32_t* counts, int K, int D, int H, int
                                  const int16_t* seg_fixed, const uint8_t* mask, float* entropy, int16_t* map_label,
                                  long long* summary, double* mask_summary, void* ws, size_t ws_bytes, void* stream);
 
+/* Jacobian posterior maps (absent in the reference, which turns log det J into one fold count per sample at its call site
+ * utils/util.py:72-91,209-212): per voxel, over n records (one chain's transformation at one recorded step), the number of
+ * folded records and the Welford mean / M2 of log det J over the others, whatever n is.  det J is the one irs_log_det_jacobian
+ * computes (the same device function); a record is folded at a voxel when !(det > 0), i.e. det <= 0 or NaN -- the per-sample
+ * NaN count of irs_log_det_jacobian leaves out det == 0 exactly, whose log is -inf.
+ *  - irs_jacobian_posterior_update: transformation (C,3,D,H,W) float32 in [-1,1] coordinates, C in 1 .. IRS_MAX_CHAINS,
+ *    every dim >= 2; folds (D,H,W) int32, mean and m2 (D,H,W) float32, updated in place with the C records in chain order.
+ *    records_before >= 0 records were folded in before, records_before + C <= INT32_MAX; records_before = 0 overwrites the
+ *    fold count, and a voxel's first valid record (records_before - folds = 0 before it) overwrites its mean / m2.  One
+ *    launch, one voxel per thread, no atomics.
+ *  - irs_jacobian_posterior_finalize: n >= 1 records, k = n - folds valid ones.  fold_prob (D,H,W) float32 = folds / n
+ *    (divided in double); logJ_mean = mean and logJ_std = sqrt(m2 / max(k - 1, 1)), NaN where k < 1.  mask (D,H,W) uint8 or
+ *    NULL (whole volume).  isummary: IRS_JACOBIAN_SUMMARY_INTS int64 over the mask {voxels, voxels with folds > 0, voxels with
+ *    k < 1, sum of folds}.  fsummary: IRS_JACOBIAN_SUMMARY_FLOATS doubles over the stored float32 maps in the mask {max
+ *    fold_prob, min logJ_mean, max logJ_mean, sum of logJ_std, max logJ_std}, the last four over voxels with k >= 1; a
+ *    maximum nothing entered is -inf, a minimum +inf.  ws: IRS_JACOBIAN_WS_BYTES of device memory.  Deterministic (exact
+ *    integer sums, fixed-order double sums and min / max); no host sync. */
+#define IRS_JACOBIAN_SUMMARY_INTS 4
+#define IRS_JACOBIAN_SUMMARY_FLOATS 5
+#define IRS_JACOBIAN_WS_BYTES (1024 * (IRS_JACOBIAN_SUMMARY_INTS + IRS_JACOBIAN_SUMMARY_FLOATS) * 8)
+int irs_jacobian_posterior_update(const float* transformation, int C, int D, int H, int W, int32_t* folds, float* mean, float* m2,
+                                  int records_before, void* stream);
+int irs_jacobian_posterior_finalize(const int32_t* folds, const float* mean, const float* m2, int D, int H, int W, int n,
+                                    const uint8_t* mask, float* fold_prob, float* logJ_mean, float* logJ_std, long long* isummary,
+                                    double* fsummary, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * fused transition (Trainer._SGLD_transition, trainer/trainer.py:291-356)
  * ---------------------------------------------------------------------------------------------- */

@@ -769,6 +769,36 @@ int irs_label_posterior_finalize(const int32_t* counts, int K, int D, int H, int
 }
 
 // ================================================================================================
+// Jacobian posterior maps (jacobian_kernels.hip)
+// ================================================================================================
+int irs_jacobian_posterior_update(const float* transformation, int C, int D, int H, int W, int32_t* folds, float* mean, float* m2,
+                                  int records_before, void* stream) {
+    if (!transformation || !folds || !mean || !m2 || !dims_ok(C, D, H, W)) return fail("irs_jacobian_posterior_update: bad arguments");
+    if (C > IRS_MAX_CHAINS) return fail("irs_jacobian_posterior_update: C = %d chains, 1..%d", C, IRS_MAX_CHAINS);
+    if (records_before < 0) return fail("irs_jacobian_posterior_update: records_before = %d < 0", records_before);
+    if ((int64_t)records_before + C > INT32_MAX)
+        return fail("irs_jacobian_posterior_update: %d records + %d chains overflow the int32 fold count", records_before, C);
+    launch_jacobian_update(transformation, C, folds, mean, m2, records_before, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_jacobian_posterior_finalize(const int32_t* folds, const float* mean, const float* m2, int D, int H, int W, int n,
+                                    const uint8_t* mask, float* fold_prob, float* logJ_mean, float* logJ_std, long long* isummary,
+                                    double* fsummary, void* ws, size_t ws_bytes, void* stream) {
+    if (!folds || !mean || !m2 || !fold_prob || !logJ_mean || !logJ_std || !isummary || !fsummary || !ws || !dims_ok(1, D, H, W))
+        return fail("irs_jacobian_posterior_finalize: bad arguments");
+    if (n < 1) return fail("irs_jacobian_posterior_finalize: n = %d records, at least 1 needed", n);
+    if (ws_bytes < (size_t)IRS_JACOBIAN_WS_BYTES)
+        return fail("irs_jacobian_posterior_finalize: workspace of %zu bytes, %zu needed (IRS_JACOBIAN_WS_BYTES)", ws_bytes,
+                    (size_t)IRS_JACOBIAN_WS_BYTES);
+    launch_jacobian_finalize(folds, mean, m2, (int64_t)D * H * W, n, mask, fold_prob, logJ_mean, logJ_std, isummary, fsummary, ws,
+                             (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // context
 // ================================================================================================
 

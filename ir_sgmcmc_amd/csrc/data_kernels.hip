@@ -4,6 +4,7 @@
 //   data term and d/dz with the updated mixture              (model/loss.py:87-100)
 //   regulariser energy, its adjoint stencil and the SGLD/SGD update (utils/diff_op.py:78-96; model/loss.py:152-161;
 //                                                             utils/functions.py:83-84; trainer.py:349-351)
+#include "jacobian_device.h"
 #include "kernels.h"
 #include "scalar_kernels.h"
 
@@ -153,10 +154,7 @@ void launch_sgld_update(float* v, const float* sigma, const float* g_d0, const f
 // ------------------------------------------------------------------------------------------------
 // GradientOperator.forward (utils/diff_op.py:78-96): nabla[c, a, z, y, x, comp] = d v_comp / d axis_a
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float fwd_diff(const float* __restrict__ f, int64_t p, int pos, int n, int64_t stride) {
-    return pos + 1 < n ? f[p + stride] - f[p] : f[p] - f[p - stride];  // replicated last difference
-}
-
+// (fwd_diff, the replicated forward difference, lives in jacobian_device.h)
 __global__ __launch_bounds__(kBlock) void gradient_operator_kernel(const float* __restrict__ v, float* __restrict__ nabla,
                                                                    int transformation, Vol vol) {
     IRS_VOXEL(vol, chain, x, y, z, p);
@@ -189,20 +187,7 @@ __global__ __launch_bounds__(kBlock) void log_det_kernel(const float* __restrict
     int bad = 0;
     if (x < vol.W && y < vol.H) {
         const int64_t p = ((int64_t)z * vol.H + y) * vol.W + x;
-        const int64_t cb = (int64_t)chain * 3 * vol.V;
-        const int64_t plane = (int64_t)vol.W * vol.H;
-        const float sp[3] = {2.0f / (float)(vol.W - 1), 2.0f / (float)(vol.H - 1), 2.0f / (float)(vol.D - 1)};
-        float n[3][3];  // n[a][comp]
-#pragma unroll
-        for (int comp = 0; comp < 3; ++comp) {
-            const float* f = t + cb + comp * vol.V;
-            n[0][comp] = fwd_diff(f, p, x, vol.W, 1) / sp[0];
-            n[1][comp] = fwd_diff(f, p, y, vol.H, vol.W) / sp[1];
-            n[2][comp] = fwd_diff(f, p, z, vol.D, plane) / sp[2];
-        }
-        // nabla_x = n[.][0], nabla_y = n[.][1], nabla_z = n[.][2]; formula of utils/util.py:84-89
-        const float det = n[0][0] * n[1][1] * n[2][2] + n[0][1] * n[1][2] * n[2][0] + n[0][2] * n[1][0] * n[2][1] -
-                          n[2][0] * n[1][1] * n[0][2] - n[2][1] * n[1][2] * n[0][0] - n[2][2] * n[1][0] * n[0][1];
+        const float det = det_jacobian(t + (int64_t)chain * 3 * vol.V, p, x, y, z, vol);  // jacobian_device.h
         const float ld = logf(det);
         if (log_det) log_det[(int64_t)chain * vol.V + p] = ld;
         bad = ld != ld;

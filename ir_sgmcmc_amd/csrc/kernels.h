@@ -178,6 +178,18 @@ void launch_label_finalize(const int32_t* counts, int K, int64_t V, int n, const
                            const uint8_t* mask, float* entropy, int16_t* map_label, long long* summary, double* mask_summary,
                            long long* partials, double* dpartials, hipStream_t st);
 
+// ---- jacobian_kernels.hip: Jacobian posterior maps (absent in the reference); det J from jacobian_device.h
+// t (C,3,V) float32; folds (V) int32, mean / m2 (V) float32: fold count and Welford moments of log det J over the valid records,
+// the C chains folded in order after `records_before` records
+void launch_jacobian_update(const float* t, int C, int32_t* folds, float* mean, float* m2, int records_before, Vol vol,
+                            hipStream_t st);
+// fold_prob / logj_mean / logj_std (V) float32; isummary IRS_JACOBIAN_SUMMARY_INTS int64, fsummary IRS_JACOBIAN_SUMMARY_FLOATS
+// doubles; ws: IRS_JACOBIAN_WS_BYTES (the per-block partials of jacobian_finalize_blocks(V) blocks)
+int jacobian_finalize_blocks(int64_t V);
+void launch_jacobian_finalize(const int32_t* folds, const float* mean, const float* m2, int64_t V, int n, const uint8_t* mask,
+                              float* fold_prob, float* logj_mean, float* logj_std, long long* isummary, double* fsummary,
+                              void* ws, hipStream_t st);
+
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h
 }  // namespace irs

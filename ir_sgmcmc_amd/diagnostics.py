@@ -13,6 +13,11 @@ BDA3's split ESS (section 11.5) with its truncation rule, and the MCSE sqrt(var+
 The posterior label maps (LabelPosterior) follow the same pattern for the propagated segmentation: per-voxel counts of every
 structure over the recorded warps (ops.label_posterior_update), 4 * K * D * H * W bytes whatever the number of records, and
 at the end the entropy and MAP maps, soft Dice, Dice of the MAP, volume spread and calibration (ops.label_posterior_finalize).
+
+The Jacobian posterior (JacobianPosterior) does the same for the Jacobian determinant of the sampled transformation: per voxel
+the number of recorded transformations that fold there and the Welford moments of log det J over the others
+(ops.jacobian_posterior_update), 12 * D * H * W bytes whatever the number of records, and at the end the fold probability, the
+mean and the std of log det J and their summary over the fixed mask (ops.jacobian_posterior_finalize).
 """
 import math
 import numbers
@@ -360,4 +365,110 @@ class LabelPosterior:
                              f'({tuple(self.counts.shape)})')
         self.counts.copy_(sd['counts'])
         self.volume.copy_(sd['volume'])
+        self.records = int(sd['records'])
+
+
+JACOBIAN_OPTION_KEYS = ('period',)
+JACOBIAN_METRICS = ('fold_prob_max', 'fold_prob_mean', 'folded_voxels', 'always_folded', 'logJ_std_mean', 'logJ_std_max')
+
+
+def jacobian_posterior_options(cfg_trainer):
+    """`trainer.jacobian_posterior` -> None when off, else {'period': P}.
+    Absent / false / null: off.  true: P = log_period_MCMC.  {"period": P}: that P (the key may be left out).
+    Refuses unknown keys, a non-integer P or P < 1, a config that records no step (no_samples_MCMC // P < 1) and one that
+    would record more than 2^31 - 1 transformations."""
+    opt = cfg_trainer.get('jacobian_posterior', False)
+    if opt is None or opt is False:
+        return None
+    period = None
+    if isinstance(opt, dict):
+        unknown = set(opt) - set(JACOBIAN_OPTION_KEYS)
+        if unknown:
+            raise ValueError(f'trainer.jacobian_posterior: unknown keys {sorted(unknown)}; known: {list(JACOBIAN_OPTION_KEYS)}')
+        if 'period' in opt:
+            p = opt['period']
+            if isinstance(p, bool) or not isinstance(p, numbers.Integral):
+                raise ValueError(f'trainer.jacobian_posterior.period must be an integer, got {p!r}')
+            period = int(p)
+    elif opt is not True:
+        raise ValueError(f'trainer.jacobian_posterior must be true, false or {{"period": P}}, got {opt!r}')
+    if period is None:
+        period = int(cfg_trainer['log_period_MCMC'])
+    if period < 1:
+        raise ValueError(f'trainer.jacobian_posterior: the period must be >= 1, got {period}')
+    no_samples = int(cfg_trainer['no_samples_MCMC'])
+    steps = no_samples // period
+    if steps < 1:
+        raise ValueError(f'trainer.jacobian_posterior: no_samples_MCMC = {no_samples} with period {period} records no step')
+    records = steps * int(cfg_trainer.get('no_chains', 1))
+    if records > MAX_RECORDS:
+        raise ValueError(f'trainer.jacobian_posterior: {steps} steps of {cfg_trainer.get("no_chains", 1)} chains are {records} '
+                         f'records; the fold counts hold at most {MAX_RECORDS}')
+    return {'period': period}
+
+
+def jacobian_summary(isummary, fsummary, n):
+    """the summary of DESIGN.md section 6 from the finalize's reduced columns (host ints / floats): isummary {voxels, folded
+    voxels, always folded, fold records}, fsummary {max fold_prob, min / max logJ_mean, sum / max logJ_std}, n records.
+    An empty mask gives NaN; so do the logJ entries when no masked voxel has a valid record."""
+    voxels, folded, always, fold_records = (int(x) for x in isummary)
+    fp_max, lm_min, lm_max, ls_sum, ls_max = (float(x) for x in fsummary)
+    valid = voxels - always  # voxels with at least one valid record
+    nan = float('nan')
+    return {'records': int(n), 'voxels': voxels, 'folded_voxels': folded, 'always_folded': always, 'fold_records': fold_records,
+            'fold_prob_max': fp_max if voxels else nan, 'fold_prob_mean': _nan_div(fold_records, int(n) * voxels),
+            'logJ_mean_min': lm_min if valid else nan, 'logJ_mean_max': lm_max if valid else nan,
+            'logJ_std_mean': _nan_div(ls_sum, valid), 'logJ_std_max': ls_max if valid else nan}
+
+
+class JacobianPosterior:
+    """Per voxel, the number of recorded transformations that fold there and the Welford mean / M2 of log det J over those
+    that do not, on the device (12 D H W bytes whatever the number of records).  `record(transformation)` takes the
+    (C,3,D,H,W) float32 transformations of one step, chains in order; `finalize` gives the fold probability, the mean and
+    the std of log det J, and the summary over a mask."""
+
+    def __init__(self, dims, device):
+        self.dims = tuple(int(d) for d in dims)
+        if len(self.dims) != 3 or min(self.dims) < 2:
+            raise ValueError(f'Jacobian posterior: three dims of at least 2, got {self.dims}')
+        self.device = device
+        self.folds = torch.zeros(self.dims, device=device, dtype=torch.int32)
+        self.mean = torch.zeros(self.dims, device=device, dtype=torch.float32)
+        self.m2 = torch.zeros(self.dims, device=device, dtype=torch.float32)
+        self.records = 0
+
+    def record(self, transformation):
+        C = transformation.shape[0]
+        if self.records + C > MAX_RECORDS:
+            raise ValueError(f'Jacobian posterior: {self.records} + {C} records exceed {MAX_RECORDS}')
+        ops.jacobian_posterior_update(transformation, self.folds, self.mean, self.m2, self.records)
+        self.records += C
+
+    def finalize(self, mask=None):
+        """-> (fold_prob, logJ_mean, logJ_std, all (D,H,W) float32 on the device, summary dict of jacobian_summary).
+        One device-to-host read (the summary)."""
+        if self.records < 1:
+            raise RuntimeError('JacobianPosterior.finalize: nothing recorded')
+        if mask is not None:
+            mask = mask.to(self.device)
+            mask = mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
+        fold_prob, logj_mean, logj_std, isum, fsum = ops.jacobian_posterior_finalize(self.folds, self.mean, self.m2, self.records,
+                                                                                    mask)
+        host = torch.cat([isum.view(torch.float64), fsum]).cpu()
+        ni = isum.numel()
+        summary = jacobian_summary(host[:ni].view(torch.int64).tolist(), host[ni:].tolist(), self.records)
+        return fold_prob, logj_mean, logj_std, summary
+
+    def state_dict(self):
+        return {'folds': self.folds.detach().cpu(), 'mean': self.mean.detach().cpu(), 'm2': self.m2.detach().cpu(),
+                'records': self.records}
+
+    def load_state_dict(self, sd):
+        for key in ('folds', 'mean', 'm2'):
+            if tuple(sd[key].shape) != self.dims:
+                raise ValueError(f'Jacobian posterior of shape {tuple(sd[key].shape)} ({key}) does not match this run '
+                                 f'({self.dims})')
+        self.folds.copy_(sd['folds'])
+        self.mean.copy_(sd['mean'])
+        self.m2.copy_(sd['m2'])
         self.records = int(sd['records'])

@@ -140,3 +140,15 @@ def save_label_posterior(logger, save_dirs, spacing, entropy, map_label, mask, p
     if prob is not None:
         for name, p in zip(names, prob):
             save_im_to_disk(p, path.join(folder, f'{model}_seg_prob_{name}.nii.gz'), spacing)
+
+
+def save_jacobian_posterior(logger, save_dirs, spacing, fold_prob, logJ_mean, logJ_std, mask, model='MCMC'):
+    """Jacobian posterior maps (absent in the reference): samples/{model}_fold_prob.nii.gz, {model}_logJ_mean[_masked].nii.gz
+    and {model}_logJ_std[_masked].nii.gz (float32; the masked ones 0 outside the FIXED mask; NaN where every record folds)"""
+    folder = _folder(save_dirs, 'samples')
+    mask = mask.reshape(fold_prob.shape).to(fold_prob.device) != 0
+    logger.info(f'{model} fold probability max.: {float(fold_prob.max()):.4f}')
+    save_im_to_disk(fold_prob, path.join(folder, f'{model}_fold_prob.nii.gz'), spacing)
+    for name, im in (('logJ_mean', logJ_mean), ('logJ_std', logJ_std)):
+        save_im_to_disk(im, path.join(folder, f'{model}_{name}.nii.gz'), spacing)
+        save_im_to_disk(im.where(mask, im.new_zeros(())), path.join(folder, f'{model}_{name}_masked.nii.gz'), spacing)

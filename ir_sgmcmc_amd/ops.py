@@ -384,3 +384,55 @@ def label_posterior_finalize(counts, n, labels, seg_fixed, mask=None):
                                              L.dev_ptr(entropy), L.dev_ptr(map_label), L.dev_ptr(summary),
                                              L.dev_ptr(mask_summary), L.dev_ptr(ws), nbytes.value, L.stream_ptr()))
     return entropy, map_label, summary, mask_summary
+
+
+def _volume_mask(mask, D, H, W):
+    if mask is None:
+        return None
+    if mask.numel() != D * H * W or mask.dtype not in (torch.bool, torch.uint8):
+        raise L.IrsError(f'mask must be a bool / uint8 ({D},{H},{W}) volume, got {mask.dtype} {tuple(mask.shape)}')
+    mask = mask.reshape(D, H, W).contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def _jacobian_state(folds, mean, m2, shape):
+    for name, t, dtype in (('folds', folds, torch.int32), ('mean', mean, torch.float32), ('m2', m2, torch.float32)):
+        if tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+            raise L.IrsError(f'{name} must be a {tuple(shape)} {dtype} tensor, got {t.dtype} {tuple(t.shape)}')
+
+
+def jacobian_posterior_update(transformation, folds, mean, m2, records_before):
+    """Fold one recorded step into the Jacobian posterior (absent in the reference, which keeps one fold count per sample:
+    utils/util.py:209-212): transformation (C,3,D,H,W) float32 in normalised coordinates, every chain's sample; folds (D,H,W)
+    int32 += 1 where a record's det J is not > 0; mean / m2 (D,H,W) float32: Welford moments of log det J over the other
+    records, folded in chain order after `records_before` records.  No host synchronisation."""
+    lib = L.load()
+    Cn, D, H, W = _dims5(transformation, 3)
+    _jacobian_state(folds, mean, m2, (D, H, W))
+    L.check(lib.irs_jacobian_posterior_update(L.dev_ptr(transformation, torch.float32), Cn, D, H, W,
+                                              L.dev_ptr(folds, torch.int32), L.dev_ptr(mean, torch.float32),
+                                              L.dev_ptr(m2, torch.float32), int(records_before), L.stream_ptr()))
+
+
+def jacobian_posterior_finalize(folds, mean, m2, n, mask=None):
+    """The maps and the masked summary of the Jacobian posterior after n records (absent in the reference).  folds (D,H,W)
+    int32, mean / m2 (D,H,W) float32; mask (D,H,W) bool / uint8 or None.  -> (fold_prob, logJ_mean, logJ_std, all (D,H,W)
+    float32, isummary (4,) int64, fsummary (5,) float64), all on the device: include/irsgmcmc.h gives the columns.
+    No host synchronisation."""
+    lib = L.load()
+    if folds.dim() != 3:
+        raise L.IrsError(f'folds must have shape (D,H,W), got {tuple(folds.shape)}')
+    D, H, W = folds.shape
+    _jacobian_state(folds, mean, m2, (D, H, W))
+    mask = _volume_mask(mask, D, H, W)
+    dev = folds.device
+    ws = torch.empty(L.IRS_JACOBIAN_WS_BYTES, device=dev, dtype=torch.uint8)
+    fold_prob, logj_mean, logj_std = (torch.empty((D, H, W), device=dev, dtype=torch.float32) for _ in range(3))
+    isummary = torch.empty(L.IRS_JACOBIAN_SUMMARY_INTS, device=dev, dtype=torch.int64)
+    fsummary = torch.empty(L.IRS_JACOBIAN_SUMMARY_FLOATS, device=dev, dtype=torch.float64)
+    L.check(lib.irs_jacobian_posterior_finalize(L.dev_ptr(folds, torch.int32), L.dev_ptr(mean, torch.float32),
+                                                L.dev_ptr(m2, torch.float32), D, H, W, int(n),
+                                                L.dev_ptr(mask, torch.uint8, True), L.dev_ptr(fold_prob), L.dev_ptr(logj_mean),
+                                                L.dev_ptr(logj_std), L.dev_ptr(isummary), L.dev_ptr(fsummary), L.dev_ptr(ws),
+                                                L.IRS_JACOBIAN_WS_BYTES, L.stream_ptr()))
+    return fold_prob, logj_mean, logj_std, isummary, fsummary

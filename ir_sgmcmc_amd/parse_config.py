@@ -11,7 +11,8 @@ from pathlib import Path
 import numpy as np
 
 from .data_loader import data_loaders as module_data
-from .diagnostics import LABEL_STRUCTURE_METRICS, diagnostics_period, ess_options, label_posterior_options
+from .diagnostics import (JACOBIAN_METRICS, LABEL_STRUCTURE_METRICS, diagnostics_period, ess_options, jacobian_posterior_options,
+                          label_posterior_options)
 from .logger import setup_logging
 from .model import distributions as model_distr
 from .model import loss as model_loss
@@ -100,6 +101,8 @@ class ConfigParser:
             for s in self.structures_dict:
                 m += [f'MCMC/seg/{s}/{k}' for k in LABEL_STRUCTURE_METRICS]
             m += [f'MCMC/seg/{k}' for k in ('entropy_mean', 'entropy_max', 'ECE')]
+        if jacobian_posterior_options(self['trainer']) is not None:
+            m += [f'MCMC/jacobian/{k}' for k in JACOBIAN_METRICS]
         return m
 
     def init_transformation_and_registration_modules(self):

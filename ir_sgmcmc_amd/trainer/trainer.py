@@ -17,10 +17,11 @@ import numpy as np
 import torch
 
 from ..base import BaseTrainer
-from ..diagnostics import (ChainMoments, LABEL_STRUCTURE_METRICS, LabelPosterior, diagnostics_period, ess_options, is_recorded,
-                           label_posterior_options)
+from ..diagnostics import (ChainMoments, JACOBIAN_METRICS, JacobianPosterior, LABEL_STRUCTURE_METRICS, LabelPosterior,
+                           diagnostics_period, ess_options, is_recorded, jacobian_posterior_options, label_posterior_options)
 from ..engine import EngineConfig, TransitionEngine
-from ..logger import save_displacement_mean_and_std_dev, save_ess, save_label_posterior, save_rhat, save_sample
+from ..logger import (save_displacement_mean_and_std_dev, save_ess, save_jacobian_posterior, save_label_posterior, save_rhat,
+                      save_sample)
 from ..utils import calc_norm, calc_no_non_diffeomorphic_voxels, calc_metrics, sample_q_v
 from .vi import VIMixin
 
@@ -70,6 +71,10 @@ class Trainer(VIMixin, BaseTrainer):
         self.label_options = label_posterior_options(cfg_trainer)
         self._label_posterior = None
         self.label_entropy, self.label_map, self.label_summary = None, None, None
+        # Jacobian posterior maps (diagnostics.JacobianPosterior): None when trainer.jacobian_posterior is off
+        self.jacobian_options = jacobian_posterior_options(cfg_trainer)
+        self._jacobian_posterior = None
+        self.jacobian_fold_prob, self.jacobian_logJ_mean, self.jacobian_logJ_std, self.jacobian_summary = None, None, None, None
 
     # ---------------------------------------------------------------- engine plumbing
     def _engine_config(self):
@@ -167,7 +172,8 @@ class Trainer(VIMixin, BaseTrainer):
                 'moments': {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in getattr(self, '_moments', {}).items()},
                 'config_name': self.config['name'],
                 **({'chain_moments': self._chain_moments.state_dict()} if self._chain_moments is not None else {}),
-                **({'label_posterior': self._label_posterior.state_dict()} if self._label_posterior is not None else {})}
+                **({'label_posterior': self._label_posterior.state_dict()} if self._label_posterior is not None else {}),
+                **({'jacobian_posterior': self._jacobian_posterior.state_dict()} if self._jacobian_posterior is not None else {})}
 
     def load_state_dict(self, sd):
         import ctypes
@@ -199,6 +205,14 @@ class Trainer(VIMixin, BaseTrainer):
             elif any(is_recorded(s, self.no_iters_burn_in, period) for s in range(1, self._sample_no + 1)):
                 raise ValueError(f'the checkpoint at sample {self._sample_no} holds no label posterior (written with '
                                  f'trainer.label_posterior off) but this run records from sample '
+                                 f'{self.no_iters_burn_in + period} on')
+        if self._jacobian_posterior is not None:
+            period = self.jacobian_options['period']
+            if 'jacobian_posterior' in sd:
+                self._jacobian_posterior.load_state_dict(sd['jacobian_posterior'])
+            elif any(is_recorded(s, self.no_iters_burn_in, period) for s in range(1, self._sample_no + 1)):
+                raise ValueError(f'the checkpoint at sample {self._sample_no} holds no Jacobian posterior (written with '
+                                 f'trainer.jacobian_posterior off) but this run records from sample '
                                  f'{self.no_iters_burn_in + period} on')
         self.sync_parameters()
 
@@ -312,6 +326,8 @@ class Trainer(VIMixin, BaseTrainer):
                 raise ValueError('trainer.label_posterior needs the fixed and the moving segmentation ("seg" in both); '
                                  f'fixed has {sorted(fixed)}, moving has {sorted(moving)}')
             self._label_posterior = LabelPosterior(self.structures_dict, self._outputs['displacement'].shape[2:], self.device)
+        if self.jacobian_options is not None:
+            self._jacobian_posterior = JacobianPosterior(self._outputs['transformation'].shape[2:], self.device)
         if cfg_trainer.get('resume'):
             self.load_checkpoint(cfg_trainer['resume'])
             first = self._sample_no + 1
@@ -382,6 +398,9 @@ class Trainer(VIMixin, BaseTrainer):
                 if seg_warped is None:
                     seg_warped = self.registration_module(moving['seg'], output['transformation'])
                 self._label_posterior.record(seg_warped)
+            if self._jacobian_posterior is not None and is_recorded(sample_no, self.no_iters_burn_in, self.jacobian_options['period']):
+                self.engine.flush()  # as above
+                self._jacobian_posterior.record(output['transformation'])
             if checkpoint_period and sample_no % checkpoint_period == 0:
                 self._sample_no, self._moments = sample_no, {'mean': mean, 'm2': m2, 'n': n_rec}
                 folder = self.config.save_dirs['checkpoints']
@@ -397,6 +416,8 @@ class Trainer(VIMixin, BaseTrainer):
             self._finish_diagnostics(moving.get('mask', fixed['mask'])[0], spacing, cfg_trainer.get('save_outputs', True))
         if self._label_posterior is not None:
             self._finish_label_posterior(fixed, spacing, cfg_trainer.get('save_outputs', True))
+        if self._jacobian_posterior is not None:
+            self._finish_jacobian_posterior(fixed, spacing, cfg_trainer.get('save_outputs', True))
 
         # speed test (trainer.py:467-476): 100 x [transition + nearest-neighbour warp of the segmentation]
         n_speed = 100
@@ -456,6 +477,25 @@ class Trainer(VIMixin, BaseTrainer):
             prob = lp.probabilities() if self.label_options['prob_maps'] else None
             save_label_posterior(self.logger, self.config.save_dirs, spacing, self.label_entropy, self.label_map, mask, prob,
                                  lp.names, 'MCMC')
+
+    def _finish_jacobian_posterior(self, fixed, spacing, save_outputs):
+        """fold probability, mean and std of log det J and their summary -> self.jacobian_fold_prob / jacobian_logJ_mean /
+        jacobian_logJ_std / jacobian_summary, the MCMC/jacobian/* metrics and, with save_outputs, samples/MCMC_fold_prob.nii.gz
+        and samples/MCMC_logJ_{mean,std}[_masked].nii.gz.  The maps live on the fixed grid, so the summary is over the FIXED
+        mask, as for the label posterior."""
+        mask = fixed['mask'][0]
+        jp = self._jacobian_posterior
+        self.jacobian_fold_prob, self.jacobian_logJ_mean, self.jacobian_logJ_std, self.jacobian_summary = jp.finalize(mask)
+        s = self.jacobian_summary
+        for key in JACOBIAN_METRICS:
+            self.metrics.update(f'MCMC/jacobian/{key}', s[key])
+        self.logger.info(f'Jacobian posterior of {s["records"]} transformations over {s["voxels"]} masked voxels: '
+                         f'{s["folded_voxels"]} voxels fold in some record ({s["always_folded"]} in all), fold probability '
+                         f'max {s["fold_prob_max"]:.4f}, mean {s["fold_prob_mean"]:.3g}; std of log det J mean '
+                         f'{s["logJ_std_mean"]:.4f}, max {s["logJ_std_max"]:.4f}')
+        if save_outputs:
+            save_jacobian_posterior(self.logger, self.config.save_dirs, spacing, self.jacobian_fold_prob, self.jacobian_logJ_mean,
+                                    self.jacobian_logJ_std, mask, 'MCMC')
 
     def _run_model(self):
         for fixed, moving, var_params_q_v in self.data_loader:

@@ -169,6 +169,21 @@ def calc_label_posterior(seg_samples, seg_fixed, structures_dict, spacing, mask=
 
 
 @torch.no_grad()
+def calc_jacobian_posterior(transformations, mask=None):
+    """Jacobian posterior maps of transformation samples (absent in the reference): transformations (n,3,D,H,W) float32 on the
+    device, in normalised coordinates, the n records in order; mask (D,H,W) or None.  -> (fold_prob, logJ_mean, logJ_std,
+    summary dict), as diagnostics.JacobianPosterior.finalize."""
+    from .. import _lib as L
+    from ..diagnostics import JacobianPosterior
+    if transformations.dim() != 5 or transformations.shape[1] != 3:
+        raise ValueError(f'transformations must have shape (n, 3, D, H, W), got {tuple(transformations.shape)}')
+    jp = JacobianPosterior(transformations.shape[2:], transformations.device)
+    for i in range(0, transformations.shape[0], L.IRS_MAX_CHAINS):  # one launch folds up to IRS_MAX_CHAINS records, in order
+        jp.record(transformations[i:i + L.IRS_MAX_CHAINS].float().contiguous())
+    return jp.finalize(mask)
+
+
+@torch.no_grad()
 def calc_DSC_GPU(no_samples, seg_fixed, seg_moving, structures_dict):
     """Dice scores on the device (utils/util.py:123-148)"""
     DSC = torch.zeros(no_samples, len(structures_dict))
