@@ -215,6 +215,36 @@ int irs_jacobian_posterior_finalize(const int32_t* folds, const float* mean, con
                                     const uint8_t* mask, float* fold_prob, float* logJ_mean, float* logJ_std, long long* isummary,
                                     double* fsummary, void* ws, size_t ws_bytes, void* stream);
 
+/* Displacement covariance posterior (absent in the reference, whose displacement std is three per-component numbers): per
+ * voxel, over n records (one chain's displacement at one recorded step, pooled over chains), the Welford mean and the six
+ * co-moments of the displacement, and from them the principal spreads and the major direction of its 3 x 3 sample covariance.
+ *  - irs_displacement_covariance_update: displacement (C,3,D,H,W) float32 in normalised coordinates, C in 1 ..
+ *    IRS_MAX_CHAINS, every dim >= 2; mean (3,D,H,W) and comoment (6,D,H,W: xx, yy, zz, xy, xz, yz) float32, updated in place
+ *    with the C records in chain order: delta_a = x_a - mean_a, mean_a += delta_a / (float)k, comoment_ab += delta_a *
+ *    (x_b - mean_b) with the new mean_b.  records_before >= 0 records were folded in before, records_before + C <= INT32_MAX;
+ *    records_before = 0 overwrites the state (mean = x, comoment = 0), which is then never read.  Non-finite inputs propagate.
+ *    One launch, each thread owns its voxels, no atomics.
+ *  - irs_displacement_covariance_finalize: n >= 1 records; scale: 3 host floats, finite and > 0, one per channel.  Per voxel,
+ *    in double, S_ab = scale_a scale_b comoment_ab / max(n - 1, 1) is diagonalised by 5 cyclic Jacobi sweeps over the pairs
+ *    (0,1), (0,2), (1,2); the eigenvalues are sorted descending and clamped at 0.  std (3,D,H,W) float32: their square roots.
+ *    direction (3,D,H,W) float32: the unit eigenvector of the largest one, its stored component of largest magnitude positive
+ *    (the lowest channel on a tie), the zero vector where that eigenvalue is 0.  anisotropy (D,H,W) float32: the fractional
+ *    anisotropy sqrt(3/2 sum (l_i - mean l)^2 / sum l_i^2), 0 where the denominator is 0.  A voxel whose state holds a
+ *    non-finite value gives NaN in all seven planes.  mask (D,H,W) uint8 or NULL (whole volume).  isummary:
+ *    IRS_COVARIANCE_SUMMARY_INTS int64 over the mask {voxels, voxels with a non-finite state}.  fsummary:
+ *    IRS_COVARIANCE_SUMMARY_FLOATS doubles over the stored float32 maps of the other masked voxels {sum std[0], max std[0],
+ *    sum sqrt(std[0]^2 + std[1]^2 + std[2]^2), sum anisotropy, max anisotropy, sum |direction[0]|, sum |direction[1]|,
+ *    sum |direction[2]|}; a maximum nothing entered is -inf.  ws: IRS_COVARIANCE_WS_BYTES of device memory.  Deterministic
+ *    (exact integer sums, fixed-order double sums and maxima); no host sync. */
+#define IRS_COVARIANCE_SUMMARY_INTS 2
+#define IRS_COVARIANCE_SUMMARY_FLOATS 8
+#define IRS_COVARIANCE_WS_BYTES (1024 * (IRS_COVARIANCE_SUMMARY_INTS + IRS_COVARIANCE_SUMMARY_FLOATS) * 8)
+int irs_displacement_covariance_update(const float* displacement, int C, int D, int H, int W, float* mean, float* comoment,
+                                       int records_before, void* stream);
+int irs_displacement_covariance_finalize(const float* mean, const float* comoment, int D, int H, int W, int n, const float* scale,
+                                         const uint8_t* mask, float* std, float* direction, float* anisotropy, long long* isummary,
+                                         double* fsummary, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * fused transition (Trainer._SGLD_transition, trainer/trainer.py:291-356)
  * ---------------------------------------------------------------------------------------------- */

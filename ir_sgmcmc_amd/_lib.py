@@ -19,6 +19,8 @@ IRS_MAX_LABELS = 64
 IRS_LABEL_BINS = 10
 IRS_JACOBIAN_SUMMARY_INTS, IRS_JACOBIAN_SUMMARY_FLOATS = 4, 5
 IRS_JACOBIAN_WS_BYTES = 1024 * (IRS_JACOBIAN_SUMMARY_INTS + IRS_JACOBIAN_SUMMARY_FLOATS) * 8
+IRS_COVARIANCE_SUMMARY_INTS, IRS_COVARIANCE_SUMMARY_FLOATS = 2, 8
+IRS_COVARIANCE_WS_BYTES = 1024 * (IRS_COVARIANCE_SUMMARY_INTS + IRS_COVARIANCE_SUMMARY_FLOATS) * 8
 IRS_DATA_GMM_LCC, IRS_DATA_SSD = 0, 1
 IRS_REG_L2, IRS_REG_LOGNORMAL, IRS_REG_STUDENT, IRS_REG_LOGNORMAL_L2 = 0, 1, 2, 3
 
@@ -146,6 +148,8 @@ SIGNATURES = {
     'irs_label_posterior_finalize': [_P, _I, _I, _I, _I, _I, _I32P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],
     'irs_jacobian_posterior_update': [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P],
     'irs_jacobian_posterior_finalize': [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],
+    'irs_displacement_covariance_update': [_P, _I, _I, _I, _I, _P, _P, _I, _P],
+    'irs_displacement_covariance_finalize': [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],
     'irs_create': [C.POINTER(IrsConfig), C.POINTER(_P)],
     'irs_destroy': [_P],
     'irs_workspace_bytes': [_P],

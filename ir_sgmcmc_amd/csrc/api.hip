@@ -799,6 +799,39 @@ int irs_jacobian_posterior_finalize(const int32_t* folds, const float* mean, con
 }
 
 // ================================================================================================
+// displacement covariance posterior (covariance_kernels.hip)
+// ================================================================================================
+int irs_displacement_covariance_update(const float* displacement, int C, int D, int H, int W, float* mean, float* comoment,
+                                       int records_before, void* stream) {
+    if (!displacement || !mean || !comoment || !dims_ok(C, D, H, W)) return fail("irs_displacement_covariance_update: bad arguments");
+    if (C > IRS_MAX_CHAINS) return fail("irs_displacement_covariance_update: C = %d chains, 1..%d", C, IRS_MAX_CHAINS);
+    if (records_before < 0) return fail("irs_displacement_covariance_update: records_before = %d < 0", records_before);
+    if ((int64_t)records_before + C > INT32_MAX)
+        return fail("irs_displacement_covariance_update: %d records + %d chains overflow the int32 record count", records_before, C);
+    launch_covariance_update(displacement, C, mean, comoment, records_before, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_displacement_covariance_finalize(const float* mean, const float* comoment, int D, int H, int W, int n, const float* scale,
+                                         const uint8_t* mask, float* stdev, float* direction, float* anisotropy, long long* isummary,
+                                         double* fsummary, void* ws, size_t ws_bytes, void* stream) {
+    if (!mean || !comoment || !scale || !stdev || !direction || !anisotropy || !isummary || !fsummary || !ws || !dims_ok(1, D, H, W))
+        return fail("irs_displacement_covariance_finalize: bad arguments");
+    if (n < 1) return fail("irs_displacement_covariance_finalize: n = %d records, at least 1 needed", n);
+    for (int a = 0; a < 3; ++a)
+        if (!(scale[a] > 0.0f) || !isfinite(scale[a]))
+            return fail("irs_displacement_covariance_finalize: scale[%d] = %g, a finite value > 0 needed", a, (double)scale[a]);
+    if (ws_bytes < (size_t)IRS_COVARIANCE_WS_BYTES)
+        return fail("irs_displacement_covariance_finalize: workspace of %zu bytes, %zu needed (IRS_COVARIANCE_WS_BYTES)", ws_bytes,
+                    (size_t)IRS_COVARIANCE_WS_BYTES);
+    launch_covariance_finalize(mean, comoment, (int64_t)D * H * W, n, scale, mask, stdev, direction, anisotropy, isummary, fsummary, ws,
+                               (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // context
 // ================================================================================================
 

@@ -190,6 +190,17 @@ void launch_jacobian_finalize(const int32_t* folds, const float* mean, const flo
                               float* fold_prob, float* logj_mean, float* logj_std, long long* isummary, double* fsummary,
                               void* ws, hipStream_t st);
 
+// ---- covariance_kernels.hip: displacement covariance posterior (absent in the reference); arithmetic in covariance_device.h
+// x (C,3,V) float32; mean (3,V), comoment (6,V: xx, yy, zz, xy, xz, yz) float32: Welford moments, the C chains folded in order
+// after `records_before` records
+void launch_covariance_update(const float* x, int C, float* mean, float* comoment, int records_before, Vol vol, hipStream_t st);
+// stdev / direction (3,V), anisotropy (V) float32; scale: 3 host floats; isummary IRS_COVARIANCE_SUMMARY_INTS int64, fsummary
+// IRS_COVARIANCE_SUMMARY_FLOATS doubles; ws: IRS_COVARIANCE_WS_BYTES (the partials of covariance_finalize_blocks(V) blocks)
+int covariance_finalize_blocks(int64_t V);
+void launch_covariance_finalize(const float* mean, const float* comoment, int64_t V, int n, const float* scale, const uint8_t* mask,
+                                float* stdev, float* direction, float* anisotropy, long long* isummary, double* fsummary, void* ws,
+                                hipStream_t st);
+
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h
 }  // namespace irs

@@ -18,6 +18,11 @@ The Jacobian posterior (JacobianPosterior) does the same for the Jacobian determ
 the number of recorded transformations that fold there and the Welford moments of log det J over the others
 (ops.jacobian_posterior_update), 12 * D * H * W bytes whatever the number of records, and at the end the fold probability, the
 mean and the std of log det J and their summary over the fixed mask (ops.jacobian_posterior_finalize).
+
+The displacement covariance (DisplacementCovariance) keeps the second moment of the displacement itself, pooled over chains as
+the displacement mean / std is: per voxel the Welford mean and the six co-moments (ops.displacement_covariance_update),
+36 * D * H * W bytes whatever the number of records, and at the end the principal spreads, the major direction and the
+fractional anisotropy of the 3 x 3 sample covariance and their summary over a mask (ops.displacement_covariance_finalize).
 """
 import math
 import numbers
@@ -471,4 +476,124 @@ class JacobianPosterior:
         self.folds.copy_(sd['folds'])
         self.mean.copy_(sd['mean'])
         self.m2.copy_(sd['m2'])
+        self.records = int(sd['records'])
+
+
+COVARIANCE_OPTION_KEYS = ('period',)
+COVARIANCE_METRICS = ('std_major_mean', 'std_major_max', 'std_total_mean', 'anisotropy_mean', 'anisotropy_max', 'dir_x', 'dir_y',
+                      'dir_z')
+
+
+def displacement_covariance_options(cfg_trainer):
+    """`trainer.displacement_covariance` -> None when off, else {'period': P}.
+    Absent / false / null: off.  true: P = log_period_MCMC.  {"period": P}: that P (the key may be left out).
+    Refuses unknown keys, a non-integer P or P < 1, a config that records no step (no_samples_MCMC // P < 1) and one that
+    would record more than 2^31 - 1 displacements."""
+    opt = cfg_trainer.get('displacement_covariance', False)
+    if opt is None or opt is False:
+        return None
+    period = None
+    if isinstance(opt, dict):
+        unknown = set(opt) - set(COVARIANCE_OPTION_KEYS)
+        if unknown:
+            raise ValueError(f'trainer.displacement_covariance: unknown keys {sorted(unknown)}; known: '
+                             f'{list(COVARIANCE_OPTION_KEYS)}')
+        if 'period' in opt:
+            p = opt['period']
+            if isinstance(p, bool) or not isinstance(p, numbers.Integral):
+                raise ValueError(f'trainer.displacement_covariance.period must be an integer, got {p!r}')
+            period = int(p)
+    elif opt is not True:
+        raise ValueError(f'trainer.displacement_covariance must be true, false or {{"period": P}}, got {opt!r}')
+    if period is None:
+        period = int(cfg_trainer['log_period_MCMC'])
+    if period < 1:
+        raise ValueError(f'trainer.displacement_covariance: the period must be >= 1, got {period}')
+    no_samples = int(cfg_trainer['no_samples_MCMC'])
+    steps = no_samples // period
+    if steps < 1:
+        raise ValueError(f'trainer.displacement_covariance: no_samples_MCMC = {no_samples} with period {period} records no step')
+    records = steps * int(cfg_trainer.get('no_chains', 1))
+    if records > MAX_RECORDS:
+        raise ValueError(f'trainer.displacement_covariance: {steps} steps of {cfg_trainer.get("no_chains", 1)} chains are '
+                         f'{records} records; the record count holds at most {MAX_RECORDS}')
+    return {'period': period}
+
+
+def covariance_summary(isummary, fsummary, n):
+    """the summary of DESIGN.md section 6 from the finalize's reduced columns (host ints / floats): isummary {voxels, voxels
+    with a non-finite state}, fsummary {sum / max std[0], sum of the total std, sum / max anisotropy, sums of |direction_c|}
+    over the finite masked voxels, n records.  The float entries are NaN for an empty mask or when no masked voxel is finite;
+    dir_x / dir_y / dir_z are the mean absolute components of the major direction: which axis carries the uncertainty."""
+    voxels, nonfinite = (int(x) for x in isummary)
+    s_sum, s_max, t_sum, a_sum, a_max, dx, dy, dz = (float(x) for x in fsummary)
+    finite = voxels - nonfinite
+    nan = float('nan')
+    return {'records': int(n), 'voxels': voxels, 'nonfinite_voxels': nonfinite,
+            'std_major_mean': _nan_div(s_sum, finite), 'std_major_max': s_max if finite else nan,
+            'std_total_mean': _nan_div(t_sum, finite), 'anisotropy_mean': _nan_div(a_sum, finite),
+            'anisotropy_max': a_max if finite else nan,
+            'dir_x': _nan_div(dx, finite), 'dir_y': _nan_div(dy, finite), 'dir_z': _nan_div(dz, finite)}
+
+
+class DisplacementCovariance:
+    """Per voxel, the Welford mean (3,D,H,W) and the co-moments (6,D,H,W: xx, yy, zz, xy, xz, yz) of the displacement over the
+    recorded samples, pooled over chains, on the device (36 D H W bytes whatever the number of records).
+    `record(displacement)` takes the (C,3,D,H,W) float32 displacements of one step, chains in order; `finalize` gives the
+    principal standard deviations, the major direction, the fractional anisotropy and the summary over a mask."""
+
+    def __init__(self, dims, device):
+        self.dims = tuple(int(d) for d in dims)
+        if len(self.dims) != 3 or min(self.dims) < 2:
+            raise ValueError(f'displacement covariance: three dims of at least 2, got {self.dims}')
+        self.device = device
+        self.mean = torch.zeros((3,) + self.dims, device=device, dtype=torch.float32)
+        self.comoment = torch.zeros((6,) + self.dims, device=device, dtype=torch.float32)
+        self.records = 0
+
+    def default_scale(self):
+        """normalised coordinates -> voxels, channels x, y, z: (W - 1) / 2, (H - 1) / 2, (D - 1) / 2"""
+        D, H, W = self.dims
+        return ((W - 1) / 2, (H - 1) / 2, (D - 1) / 2)
+
+    def record(self, displacement):
+        C = displacement.shape[0]
+        if self.records + C > MAX_RECORDS:
+            raise ValueError(f'displacement covariance: {self.records} + {C} records exceed {MAX_RECORDS}')
+        ops.displacement_covariance_update(displacement, self.mean, self.comoment, self.records)
+        self.records += C
+
+    def covariance(self):
+        """-> (6,D,H,W) float32: the sample covariance in normalised units, comoment / max(n - 1, 1)"""
+        if self.records < 1:
+            raise RuntimeError('DisplacementCovariance.covariance: nothing recorded')
+        return self.comoment / max(self.records - 1, 1)
+
+    def finalize(self, mask=None, scale=None):
+        """-> (std (3,D,H,W), direction (3,D,H,W), anisotropy (D,H,W), float32 on the device, summary dict of
+        covariance_summary).  scale: three positive floats, one per channel (default: voxel units).  One device-to-host
+        read (the summary)."""
+        if self.records < 1:
+            raise RuntimeError('DisplacementCovariance.finalize: nothing recorded')
+        if mask is not None:
+            mask = mask.to(self.device)
+            mask = mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
+        scale = self.default_scale() if scale is None else tuple(float(s) for s in scale)
+        std, direction, anisotropy, isum, fsum = ops.displacement_covariance_finalize(self.mean, self.comoment, self.records,
+                                                                                      scale, mask)
+        host = torch.cat([isum.view(torch.float64), fsum]).cpu()
+        ni = isum.numel()
+        summary = covariance_summary(host[:ni].view(torch.int64).tolist(), host[ni:].tolist(), self.records)
+        return std, direction, anisotropy, summary
+
+    def state_dict(self):
+        return {'mean': self.mean.detach().cpu(), 'comoment': self.comoment.detach().cpu(), 'records': self.records}
+
+    def load_state_dict(self, sd):
+        for key, ch in (('mean', 3), ('comoment', 6)):
+            if tuple(sd[key].shape) != (ch,) + self.dims:
+                raise ValueError(f'displacement covariance of shape {tuple(sd[key].shape)} ({key}) does not match this run '
+                                 f'({(ch,) + self.dims})')
+        self.mean.copy_(sd['mean'])
+        self.comoment.copy_(sd['comoment'])
         self.records = int(sd['records'])

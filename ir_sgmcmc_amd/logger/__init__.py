@@ -152,3 +152,17 @@ def save_jacobian_posterior(logger, save_dirs, spacing, fold_prob, logJ_mean, lo
     for name, im in (('logJ_mean', logJ_mean), ('logJ_std', logJ_std)):
         save_im_to_disk(im, path.join(folder, f'{model}_{name}.nii.gz'), spacing)
         save_im_to_disk(im.where(mask, im.new_zeros(())), path.join(folder, f'{model}_{name}_masked.nii.gz'), spacing)
+
+
+def save_displacement_covariance(logger, save_dirs, spacing, std, direction, anisotropy, mask, model='MCMC'):
+    """principal spread of the displacement posterior (absent in the reference): samples/{model}_disp_std_major[_masked].nii.gz,
+    {model}_disp_std_minor[_masked].nii.gz and {model}_disp_anisotropy[_masked].nii.gz (float32, the std in the units of the
+    finalize's scale; the masked ones 0 outside the mask), and samples/{model}_disp_direction.vtk: the major direction scaled
+    by the major std, as a field"""
+    folder = _folder(save_dirs, 'samples')
+    mask = mask.reshape(anisotropy.shape).to(anisotropy.device) != 0
+    logger.info(f'{model} displacement major std max.: {float(std[0].max()):.4f}, anisotropy max.: {float(anisotropy.max()):.4f}')
+    for name, im in (('disp_std_major', std[0]), ('disp_std_minor', std[2]), ('disp_anisotropy', anisotropy)):
+        save_im_to_disk(im, path.join(folder, f'{model}_{name}.nii.gz'), spacing)
+        save_im_to_disk(im.where(mask, im.new_zeros(())), path.join(folder, f'{model}_{name}_masked.nii.gz'), spacing)
+    save_field_to_disk(direction * std[0], path.join(folder, f'{model}_disp_direction.vtk'), spacing)

@@ -436,3 +436,51 @@ def jacobian_posterior_finalize(folds, mean, m2, n, mask=None):
                                                 L.dev_ptr(logj_std), L.dev_ptr(isummary), L.dev_ptr(fsummary), L.dev_ptr(ws),
                                                 L.IRS_JACOBIAN_WS_BYTES, L.stream_ptr()))
     return fold_prob, logj_mean, logj_std, isummary, fsummary
+
+
+def _covariance_state(mean, comoment, shape):
+    D, H, W = shape
+    for name, t, ch in (('mean', mean, 3), ('comoment', comoment, 6)):
+        if tuple(t.shape) != (ch, D, H, W) or t.dtype != torch.float32:
+            raise L.IrsError(f'{name} must be a {(ch, D, H, W)} torch.float32 tensor, got {t.dtype} {tuple(t.shape)}')
+
+
+def displacement_covariance_update(displacement, mean, comoment, records_before):
+    """Fold one recorded step into the displacement covariance posterior (absent in the reference, which keeps three
+    per-component standard deviations): displacement (C,3,D,H,W) float32 in normalised coordinates, every chain's sample; mean
+    (3,D,H,W) and comoment (6,D,H,W: xx, yy, zz, xy, xz, yz) float32: the Welford moments, folded in chain order after
+    `records_before` records (0 overwrites the state).  No host synchronisation."""
+    lib = L.load()
+    Cn, D, H, W = _dims5(displacement, 3)
+    _covariance_state(mean, comoment, (D, H, W))
+    L.check(lib.irs_displacement_covariance_update(L.dev_ptr(displacement, torch.float32), Cn, D, H, W,
+                                                   L.dev_ptr(mean, torch.float32), L.dev_ptr(comoment, torch.float32),
+                                                   int(records_before), L.stream_ptr()))
+
+
+def displacement_covariance_finalize(mean, comoment, n, scale, mask=None):
+    """The maps and the masked summary of the displacement covariance posterior after n records (absent in the reference).
+    mean (3,D,H,W), comoment (6,D,H,W) float32; scale: three positive floats, one per channel; mask (D,H,W) bool / uint8 or
+    None.  -> (std (3,D,H,W), direction (3,D,H,W), anisotropy (D,H,W), all float32, isummary (2,) int64, fsummary (8,)
+    float64), all on the device: include/irsgmcmc.h gives the columns.  No host synchronisation."""
+    lib = L.load()
+    if mean.dim() != 4:
+        raise L.IrsError(f'mean must have shape (3,D,H,W), got {tuple(mean.shape)}')
+    D, H, W = mean.shape[1:]
+    _covariance_state(mean, comoment, (D, H, W))
+    mask = _volume_mask(mask, D, H, W)
+    scale = [float(s) for s in scale]
+    if len(scale) != 3:
+        raise L.IrsError(f'scale must hold three floats, got {len(scale)}')
+    dev = mean.device
+    ws = torch.empty(L.IRS_COVARIANCE_WS_BYTES, device=dev, dtype=torch.uint8)
+    std, direction = (torch.empty((3, D, H, W), device=dev, dtype=torch.float32) for _ in range(2))
+    anisotropy = torch.empty((D, H, W), device=dev, dtype=torch.float32)
+    isummary = torch.empty(L.IRS_COVARIANCE_SUMMARY_INTS, device=dev, dtype=torch.int64)
+    fsummary = torch.empty(L.IRS_COVARIANCE_SUMMARY_FLOATS, device=dev, dtype=torch.float64)
+    L.check(lib.irs_displacement_covariance_finalize(L.dev_ptr(mean, torch.float32), L.dev_ptr(comoment, torch.float32), D, H, W,
+                                                     int(n), (C.c_float * 3)(*scale), L.dev_ptr(mask, torch.uint8, True),
+                                                     L.dev_ptr(std), L.dev_ptr(direction), L.dev_ptr(anisotropy),
+                                                     L.dev_ptr(isummary), L.dev_ptr(fsummary), L.dev_ptr(ws),
+                                                     L.IRS_COVARIANCE_WS_BYTES, L.stream_ptr()))
+    return std, direction, anisotropy, isummary, fsummary

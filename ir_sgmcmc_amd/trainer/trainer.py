@@ -17,11 +17,12 @@ import numpy as np
 import torch
 
 from ..base import BaseTrainer
-from ..diagnostics import (ChainMoments, JACOBIAN_METRICS, JacobianPosterior, LABEL_STRUCTURE_METRICS, LabelPosterior,
-                           diagnostics_period, ess_options, is_recorded, jacobian_posterior_options, label_posterior_options)
+from ..diagnostics import (COVARIANCE_METRICS, ChainMoments, DisplacementCovariance, JACOBIAN_METRICS, JacobianPosterior,
+                           LABEL_STRUCTURE_METRICS, LabelPosterior, diagnostics_period, displacement_covariance_options,
+                           ess_options, is_recorded, jacobian_posterior_options, label_posterior_options)
 from ..engine import EngineConfig, TransitionEngine
-from ..logger import (save_displacement_mean_and_std_dev, save_ess, save_jacobian_posterior, save_label_posterior, save_rhat,
-                      save_sample)
+from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_ess, save_jacobian_posterior,
+                      save_label_posterior, save_rhat, save_sample)
 from ..utils import calc_norm, calc_no_non_diffeomorphic_voxels, calc_metrics, sample_q_v
 from .vi import VIMixin
 
@@ -75,6 +76,11 @@ class Trainer(VIMixin, BaseTrainer):
         self.jacobian_options = jacobian_posterior_options(cfg_trainer)
         self._jacobian_posterior = None
         self.jacobian_fold_prob, self.jacobian_logJ_mean, self.jacobian_logJ_std, self.jacobian_summary = None, None, None, None
+        # displacement covariance (diagnostics.DisplacementCovariance): None when trainer.displacement_covariance is off
+        self.covariance_options = displacement_covariance_options(cfg_trainer)
+        self._displacement_covariance = None
+        self.displacement_cov_std, self.displacement_cov_direction = None, None
+        self.displacement_cov_anisotropy, self.displacement_cov_summary = None, None
 
     # ---------------------------------------------------------------- engine plumbing
     def _engine_config(self):
@@ -173,7 +179,9 @@ class Trainer(VIMixin, BaseTrainer):
                 'config_name': self.config['name'],
                 **({'chain_moments': self._chain_moments.state_dict()} if self._chain_moments is not None else {}),
                 **({'label_posterior': self._label_posterior.state_dict()} if self._label_posterior is not None else {}),
-                **({'jacobian_posterior': self._jacobian_posterior.state_dict()} if self._jacobian_posterior is not None else {})}
+                **({'jacobian_posterior': self._jacobian_posterior.state_dict()} if self._jacobian_posterior is not None else {}),
+                **({'displacement_covariance': self._displacement_covariance.state_dict()}
+                   if self._displacement_covariance is not None else {})}
 
     def load_state_dict(self, sd):
         import ctypes
@@ -213,6 +221,14 @@ class Trainer(VIMixin, BaseTrainer):
             elif any(is_recorded(s, self.no_iters_burn_in, period) for s in range(1, self._sample_no + 1)):
                 raise ValueError(f'the checkpoint at sample {self._sample_no} holds no Jacobian posterior (written with '
                                  f'trainer.jacobian_posterior off) but this run records from sample '
+                                 f'{self.no_iters_burn_in + period} on')
+        if self._displacement_covariance is not None:
+            period = self.covariance_options['period']
+            if 'displacement_covariance' in sd:
+                self._displacement_covariance.load_state_dict(sd['displacement_covariance'])
+            elif any(is_recorded(s, self.no_iters_burn_in, period) for s in range(1, self._sample_no + 1)):
+                raise ValueError(f'the checkpoint at sample {self._sample_no} holds no displacement covariance (written with '
+                                 f'trainer.displacement_covariance off) but this run records from sample '
                                  f'{self.no_iters_burn_in + period} on')
         self.sync_parameters()
 
@@ -328,6 +344,8 @@ class Trainer(VIMixin, BaseTrainer):
             self._label_posterior = LabelPosterior(self.structures_dict, self._outputs['displacement'].shape[2:], self.device)
         if self.jacobian_options is not None:
             self._jacobian_posterior = JacobianPosterior(self._outputs['transformation'].shape[2:], self.device)
+        if self.covariance_options is not None:
+            self._displacement_covariance = DisplacementCovariance(self._outputs['displacement'].shape[2:], self.device)
         if cfg_trainer.get('resume'):
             self.load_checkpoint(cfg_trainer['resume'])
             first = self._sample_no + 1
@@ -401,6 +419,10 @@ class Trainer(VIMixin, BaseTrainer):
             if self._jacobian_posterior is not None and is_recorded(sample_no, self.no_iters_burn_in, self.jacobian_options['period']):
                 self.engine.flush()  # as above
                 self._jacobian_posterior.record(output['transformation'])
+            if self._displacement_covariance is not None and is_recorded(sample_no, self.no_iters_burn_in,
+                                                                         self.covariance_options['period']):
+                self.engine.flush()  # as above
+                self._displacement_covariance.record(output['displacement'])
             if checkpoint_period and sample_no % checkpoint_period == 0:
                 self._sample_no, self._moments = sample_no, {'mean': mean, 'm2': m2, 'n': n_rec}
                 folder = self.config.save_dirs['checkpoints']
@@ -418,6 +440,9 @@ class Trainer(VIMixin, BaseTrainer):
             self._finish_label_posterior(fixed, spacing, cfg_trainer.get('save_outputs', True))
         if self._jacobian_posterior is not None:
             self._finish_jacobian_posterior(fixed, spacing, cfg_trainer.get('save_outputs', True))
+        if self._displacement_covariance is not None:
+            self._finish_displacement_covariance(moving.get('mask', fixed['mask'])[0], spacing,
+                                                 cfg_trainer.get('save_outputs', True))
 
         # speed test (trainer.py:467-476): 100 x [transition + nearest-neighbour warp of the segmentation]
         n_speed = 100
@@ -496,6 +521,27 @@ class Trainer(VIMixin, BaseTrainer):
         if save_outputs:
             save_jacobian_posterior(self.logger, self.config.save_dirs, spacing, self.jacobian_fold_prob, self.jacobian_logJ_mean,
                                     self.jacobian_logJ_std, mask, 'MCMC')
+
+    def _finish_displacement_covariance(self, mask, spacing, save_outputs):
+        """principal standard deviations (voxels), major direction and fractional anisotropy of the displacement posterior and
+        their summary -> self.displacement_cov_std / displacement_cov_direction / displacement_cov_anisotropy /
+        displacement_cov_summary, the MCMC/covariance/* metrics and, with save_outputs, samples/MCMC_disp_std_{major,minor}
+        [_masked].nii.gz, MCMC_disp_anisotropy[_masked].nii.gz and MCMC_disp_direction.vtk.  The summary is over the mask the
+        displacement std map uses."""
+        dc = self._displacement_covariance
+        (self.displacement_cov_std, self.displacement_cov_direction, self.displacement_cov_anisotropy,
+         self.displacement_cov_summary) = dc.finalize(mask)
+        s = self.displacement_cov_summary
+        for key in COVARIANCE_METRICS:
+            self.metrics.update(f'MCMC/covariance/{key}', s[key])
+        self.logger.info(f'displacement covariance of {s["records"]} samples over {s["voxels"]} masked voxels '
+                         f'({s["nonfinite_voxels"]} non-finite): major std mean {s["std_major_mean"]:.4f}, max '
+                         f'{s["std_major_max"]:.4f} voxels, total std mean {s["std_total_mean"]:.4f}; anisotropy mean '
+                         f'{s["anisotropy_mean"]:.4f}, max {s["anisotropy_max"]:.4f}; mean |direction| x {s["dir_x"]:.3f}, '
+                         f'y {s["dir_y"]:.3f}, z {s["dir_z"]:.3f}')
+        if save_outputs:
+            save_displacement_covariance(self.logger, self.config.save_dirs, spacing, self.displacement_cov_std,
+                                         self.displacement_cov_direction, self.displacement_cov_anisotropy, mask, 'MCMC')
 
     def _run_model(self):
         for fixed, moving, var_params_q_v in self.data_loader:

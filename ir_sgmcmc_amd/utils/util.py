@@ -184,6 +184,21 @@ def calc_jacobian_posterior(transformations, mask=None):
 
 
 @torch.no_grad()
+def calc_displacement_covariance(displacements, mask=None, scale=None):
+    """Principal spread and direction of displacement samples (absent in the reference): displacements (n,3,D,H,W) float32 on
+    the device, in normalised coordinates, the n records in order; mask (D,H,W) or None; scale: three floats, one per channel
+    (default: voxel units).  -> (std, direction, anisotropy, summary dict), as diagnostics.DisplacementCovariance.finalize."""
+    from .. import _lib as L
+    from ..diagnostics import DisplacementCovariance
+    if displacements.dim() != 5 or displacements.shape[1] != 3:
+        raise ValueError(f'displacements must have shape (n, 3, D, H, W), got {tuple(displacements.shape)}')
+    dc = DisplacementCovariance(displacements.shape[2:], displacements.device)
+    for i in range(0, displacements.shape[0], L.IRS_MAX_CHAINS):  # one launch folds up to IRS_MAX_CHAINS records, in order
+        dc.record(displacements[i:i + L.IRS_MAX_CHAINS].float().contiguous())
+    return dc.finalize(mask, scale)
+
+
+@torch.no_grad()
 def calc_DSC_GPU(no_samples, seg_fixed, seg_moving, structures_dict):
     """Dice scores on the device (utils/util.py:123-148)"""
     DSC = torch.zeros(no_samples, len(structures_dict))
