@@ -245,6 +245,43 @@ int irs_displacement_covariance_finalize(const float* mean, const float* comomen
                                          const uint8_t* mask, float* std, float* direction, float* anisotropy, long long* isummary,
                                          double* fsummary, void* ws, size_t ws_bytes, void* stream);
 
+/* Displacement credible intervals (absent in the reference, which keeps moments only): per voxel and channel a histogram of
+ * the displacement over the records (one chain's displacement at one recorded step, pooled over chains), and from it the
+ * quantiles of given probabilities and the width of the band between the first and the last of them.
+ *  - irs_displacement_quantiles_update: displacement (C,3,D,H,W) float32 in normalised coordinates, C in 1 ..
+ *    IRS_MAX_CHAINS, every dim >= 2; centre (3,D,H,W) float32; hist (3,bins,D,H,W) uint16, bin-major; bins even in
+ *    IRS_QUANTILE_MIN_BINS .. IRS_QUANTILE_MAX_BINS; inv_width: 3 host floats, finite and > 0, one per channel.  Every record
+ *    adds one count per voxel and channel a to the bin, in float32,
+ *        t = floorf((x_a - centre_a) * inv_width_a);  t = fminf(fmaxf(t, -bins), bins);  bin = min(max((int)t + bins / 2, 0), bins - 1)
+ *    so bin b with 0 < b < bins - 1 covers [centre + (b - bins/2) w, centre + (b - bins/2 + 1) w) and bins 0 and bins - 1 are
+ *    open-ended; a NaN counts into bin 0.  records_before = 0 writes centre from chain 0 and overwrites hist, which is then
+ *    never read.  records_before >= 0 and records_before + C <= IRS_QUANTILE_MAX_RECORDS, so a count never wraps.  Counts
+ *    commute: the histogram does not depend on the order of chains or steps.  One launch, each thread owns its voxels, no atomics.
+ *  - irs_displacement_quantiles_finalize: n in 1 .. IRS_QUANTILE_MAX_RECORDS records; width, scale: 3 host floats each,
+ *    finite and > 0; probs: P host doubles, 2 <= P <= IRS_QUANTILE_MAX_PROBS, strictly increasing in (0,1).  Per voxel,
+ *    channel and probability p, with r = p n in double and b the first bin whose cumulative count cum_b >= r:
+ *        q = scale_a (centre_a + ((b - bins/2) + (r - cum_{b-1}) / count_b) width_a)
+ *    in double, stored as float32, NaN (out of range) where b is 0 or bins - 1.  quantiles (P,3,D,H,W) float32.  ci_width
+ *    (D,H,W) float32: sqrt(sum_a (q_last,a - q_first,a)^2) of the stored quantiles, in double; NaN where any quantile of the
+ *    voxel is.  mask (D,H,W) uint8 or NULL (whole volume).  isummary: IRS_QUANTILE_SUMMARY_INTS int64 over the mask {voxels,
+ *    voxels with an out-of-range quantile, samples in bins 0 and bins - 1 summed over the channels}.  fsummary:
+ *    IRS_QUANTILE_SUMMARY_FLOATS doubles over the stored float32 maps of the other masked voxels {sum ci_width, max ci_width,
+ *    sum |q_last - q_first| of channel 0, 1, 2}; a maximum nothing entered is -inf.  ws: IRS_QUANTILE_WS_BYTES of device
+ *    memory.  Deterministic (exact integer sums, fixed-order double sums and maxima); no host sync. */
+#define IRS_QUANTILE_MIN_BINS 4
+#define IRS_QUANTILE_MAX_BINS 256 /* bins even */
+#define IRS_QUANTILE_MAX_PROBS 8
+#define IRS_QUANTILE_MAX_RECORDS 65535
+#define IRS_QUANTILE_SUMMARY_INTS 3
+#define IRS_QUANTILE_SUMMARY_FLOATS 5
+#define IRS_QUANTILE_WS_BYTES (1024 * (IRS_QUANTILE_SUMMARY_INTS + IRS_QUANTILE_SUMMARY_FLOATS) * 8)
+int irs_displacement_quantiles_update(const float* displacement, int C, int D, int H, int W, float* centre, uint16_t* hist,
+                                      int bins, const float* inv_width, int records_before, void* stream);
+int irs_displacement_quantiles_finalize(const float* centre, const uint16_t* hist, int bins, int D, int H, int W, int n,
+                                        const float* width, const float* scale, const double* probs, int P, const uint8_t* mask,
+                                        float* quantiles, float* ci_width, long long* isummary, double* fsummary, void* ws,
+                                        size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * fused transition (Trainer._SGLD_transition, trainer/trainer.py:291-356)
  * ---------------------------------------------------------------------------------------------- */

@@ -832,6 +832,64 @@ int irs_displacement_covariance_finalize(const float* mean, const float* comomen
 }
 
 // ================================================================================================
+// displacement credible intervals (quantile_kernels.hip)
+// ================================================================================================
+static bool quantile_bins_ok(int bins) { return bins >= IRS_QUANTILE_MIN_BINS && bins <= IRS_QUANTILE_MAX_BINS && bins % 2 == 0; }
+static bool positive_finite(float v) { return v > 0.0f && isfinite(v); }
+
+int irs_displacement_quantiles_update(const float* displacement, int C, int D, int H, int W, float* centre, uint16_t* hist,
+                                      int bins, const float* inv_width, int records_before, void* stream) {
+    if (!displacement || !centre || !hist || !inv_width || !dims_ok(C, D, H, W))
+        return fail("irs_displacement_quantiles_update: bad arguments");
+    if (C > IRS_MAX_CHAINS) return fail("irs_displacement_quantiles_update: C = %d chains, 1..%d", C, IRS_MAX_CHAINS);
+    if (!quantile_bins_ok(bins))
+        return fail("irs_displacement_quantiles_update: bins = %d, an even number in %d..%d needed", bins, IRS_QUANTILE_MIN_BINS,
+                    IRS_QUANTILE_MAX_BINS);
+    for (int a = 0; a < 3; ++a)
+        if (!positive_finite(inv_width[a]))
+            return fail("irs_displacement_quantiles_update: inv_width[%d] = %g, a finite value > 0 needed", a, (double)inv_width[a]);
+    if (records_before < 0) return fail("irs_displacement_quantiles_update: records_before = %d < 0", records_before);
+    if ((int64_t)records_before + C > IRS_QUANTILE_MAX_RECORDS)
+        return fail("irs_displacement_quantiles_update: %d records + %d chains exceed the %d a uint16 count holds", records_before, C,
+                    IRS_QUANTILE_MAX_RECORDS);
+    launch_quantile_update(displacement, C, centre, hist, bins, inv_width, records_before, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_displacement_quantiles_finalize(const float* centre, const uint16_t* hist, int bins, int D, int H, int W, int n,
+                                        const float* width, const float* scale, const double* probs, int P, const uint8_t* mask,
+                                        float* quantiles, float* ci_width, long long* isummary, double* fsummary, void* ws,
+                                        size_t ws_bytes, void* stream) {
+    if (!centre || !hist || !width || !scale || !probs || !quantiles || !ci_width || !isummary || !fsummary || !ws ||
+        !dims_ok(1, D, H, W))
+        return fail("irs_displacement_quantiles_finalize: bad arguments");
+    if (!quantile_bins_ok(bins))
+        return fail("irs_displacement_quantiles_finalize: bins = %d, an even number in %d..%d needed", bins, IRS_QUANTILE_MIN_BINS,
+                    IRS_QUANTILE_MAX_BINS);
+    if (n < 1 || n > IRS_QUANTILE_MAX_RECORDS)
+        return fail("irs_displacement_quantiles_finalize: n = %d records, 1..%d needed", n, IRS_QUANTILE_MAX_RECORDS);
+    if (P < 2 || P > IRS_QUANTILE_MAX_PROBS)
+        return fail("irs_displacement_quantiles_finalize: P = %d probabilities, 2..%d needed", P, IRS_QUANTILE_MAX_PROBS);
+    for (int j = 0; j < P; ++j)
+        if (!(probs[j] > 0.0 && probs[j] < 1.0) || (j > 0 && !(probs[j] > probs[j - 1])))
+            return fail("irs_displacement_quantiles_finalize: probs[%d] = %g, strictly increasing values in (0,1) needed", j, probs[j]);
+    for (int a = 0; a < 3; ++a) {
+        if (!positive_finite(width[a]))
+            return fail("irs_displacement_quantiles_finalize: width[%d] = %g, a finite value > 0 needed", a, (double)width[a]);
+        if (!positive_finite(scale[a]))
+            return fail("irs_displacement_quantiles_finalize: scale[%d] = %g, a finite value > 0 needed", a, (double)scale[a]);
+    }
+    if (ws_bytes < (size_t)IRS_QUANTILE_WS_BYTES)
+        return fail("irs_displacement_quantiles_finalize: workspace of %zu bytes, %zu needed (IRS_QUANTILE_WS_BYTES)", ws_bytes,
+                    (size_t)IRS_QUANTILE_WS_BYTES);
+    launch_quantile_finalize(centre, hist, bins, (int64_t)D * H * W, n, width, scale, probs, P, mask, quantiles, ci_width, isummary,
+                             fsummary, ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // context
 // ================================================================================================
 

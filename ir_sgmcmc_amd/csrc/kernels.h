@@ -201,6 +201,18 @@ void launch_covariance_finalize(const float* mean, const float* comoment, int64_
                                 float* stdev, float* direction, float* anisotropy, long long* isummary, double* fsummary, void* ws,
                                 hipStream_t st);
 
+// ---- quantile_kernels.hip: displacement credible intervals (absent in the reference); arithmetic in quantile_device.h
+// x (C,3,V) float32; centre (3,V) float32, hist (3,bins,V) uint16: the C chains counted after `records_before` records
+// (0: centre = chain 0 and hist overwritten); inv_width: 3 host floats
+void launch_quantile_update(const float* x, int C, float* centre, uint16_t* hist, int bins, const float* inv_width,
+                            int records_before, Vol vol, hipStream_t st);
+// quantiles (P,3,V), ci_width (V) float32; width, scale: 3 host floats each; probs: P host doubles; isummary
+// IRS_QUANTILE_SUMMARY_INTS int64, fsummary IRS_QUANTILE_SUMMARY_FLOATS doubles; ws: IRS_QUANTILE_WS_BYTES (the partials of
+// at most 1024 blocks)
+void launch_quantile_finalize(const float* centre, const uint16_t* hist, int bins, int64_t V, int n, const float* width,
+                              const float* scale, const double* probs, int P, const uint8_t* mask, float* quantiles,
+                              float* ci_width, long long* isummary, double* fsummary, void* ws, hipStream_t st);
+
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h
 }  // namespace irs

@@ -23,6 +23,11 @@ The displacement covariance (DisplacementCovariance) keeps the second moment of 
 the displacement mean / std is: per voxel the Welford mean and the six co-moments (ops.displacement_covariance_update),
 36 * D * H * W bytes whatever the number of records, and at the end the principal spreads, the major direction and the
 fractional anisotropy of the 3 x 3 sample covariance and their summary over a mask (ops.displacement_covariance_finalize).
+
+The displacement quantiles (DisplacementQuantiles) are what no moment gives: per voxel and channel a histogram of the
+displacement around the first record (ops.displacement_quantiles_update), 12 + 6 * bins bytes per voxel whatever the number of
+records, and at the end the quantiles of given probabilities, the width of the credible band between the first and the last
+and its summary over a mask (ops.displacement_quantiles_finalize).
 """
 import math
 import numbers
@@ -597,3 +602,195 @@ class DisplacementCovariance:
         self.mean.copy_(sd['mean'])
         self.comoment.copy_(sd['comoment'])
         self.records = int(sd['records'])
+
+
+QUANTILE_OPTION_KEYS = ('period', 'probs', 'bins', 'bin_width')
+QUANTILE_METRICS = ('width_mean', 'width_max', 'width_x', 'width_y', 'width_z', 'out_of_range_frac', 'clipped_frac')
+QUANTILE_MAX_RECORDS = 65535  # the uint16 counts (IRS_QUANTILE_MAX_RECORDS)
+QUANTILE_DEFAULTS = {'probs': (0.05, 0.5, 0.95), 'bins': 64, 'bin_width': 0.125}
+
+
+def _quantile_probs(probs, what):
+    if isinstance(probs, (str, bytes)) or not hasattr(probs, '__len__'):
+        raise ValueError(f'{what}: probs must be a list of probabilities, got {probs!r}')
+    if any(isinstance(p, bool) or not isinstance(p, numbers.Real) for p in probs):
+        raise ValueError(f'{what}: probs must be numbers, got {list(probs)!r}')
+    probs = tuple(float(p) for p in probs)
+    if not 2 <= len(probs) <= 8:
+        raise ValueError(f'{what}: 2 to 8 probabilities, got {len(probs)}')
+    if not all(0.0 < p < 1.0 for p in probs) or any(b <= a for a, b in zip(probs, probs[1:])):
+        raise ValueError(f'{what}: probs must be strictly increasing in (0,1), got {list(probs)}')
+    return probs
+
+
+def _quantile_bins(bins, what):
+    if isinstance(bins, bool) or not isinstance(bins, numbers.Integral):
+        raise ValueError(f'{what}: bins must be an integer, got {bins!r}')
+    if not 4 <= bins <= 256 or bins % 2:
+        raise ValueError(f'{what}: bins must be an even number in 4..256, got {bins}')
+    return int(bins)
+
+
+def _quantile_bin_width(w, what):
+    if isinstance(w, bool) or not isinstance(w, numbers.Real) or not (math.isfinite(w) and w > 0):
+        raise ValueError(f'{what}: bin_width must be a finite number > 0, got {w!r}')
+    return float(w)
+
+
+def displacement_quantiles_options(cfg_trainer):
+    """`trainer.displacement_quantiles` -> None when off, else {'period': P, 'probs': (...), 'bins': B, 'bin_width': w}.
+    Absent / false / null: off.  true: P = log_period_MCMC, probs (0.05, 0.5, 0.95), 64 bins of 0.125 voxels.  A dict sets any
+    of the four keys.  Refuses unknown keys, a non-integer P or P < 1, probs that are not 2 to 8 strictly increasing numbers in
+    (0,1), bins that are not an even integer in 4..256, a bin_width that is not a finite number > 0, a config that records no
+    step (no_samples_MCMC // P < 1) and one that would record more than 65535 displacements (a uint16 count)."""
+    what = 'trainer.displacement_quantiles'
+    opt = cfg_trainer.get('displacement_quantiles', False)
+    if opt is None or opt is False:
+        return None
+    out = {'period': None, **QUANTILE_DEFAULTS}
+    if isinstance(opt, dict):
+        unknown = set(opt) - set(QUANTILE_OPTION_KEYS)
+        if unknown:
+            raise ValueError(f'{what}: unknown keys {sorted(unknown)}; known: {list(QUANTILE_OPTION_KEYS)}')
+        if 'period' in opt:
+            p = opt['period']
+            if isinstance(p, bool) or not isinstance(p, numbers.Integral):
+                raise ValueError(f'{what}.period must be an integer, got {p!r}')
+            out['period'] = int(p)
+        if 'probs' in opt:
+            out['probs'] = opt['probs']
+        if 'bins' in opt:
+            out['bins'] = opt['bins']
+        if 'bin_width' in opt:
+            out['bin_width'] = opt['bin_width']
+    elif opt is not True:
+        raise ValueError(f'{what} must be true, false or a dict of {list(QUANTILE_OPTION_KEYS)}, got {opt!r}')
+    out['probs'] = _quantile_probs(out['probs'], what)
+    out['bins'] = _quantile_bins(out['bins'], what)
+    out['bin_width'] = _quantile_bin_width(out['bin_width'], what)
+    if out['period'] is None:
+        out['period'] = int(cfg_trainer['log_period_MCMC'])
+    period = out['period']
+    if period < 1:
+        raise ValueError(f'{what}: the period must be >= 1, got {period}')
+    no_samples = int(cfg_trainer['no_samples_MCMC'])
+    steps = no_samples // period
+    if steps < 1:
+        raise ValueError(f'{what}: no_samples_MCMC = {no_samples} with period {period} records no step')
+    records = steps * int(cfg_trainer.get('no_chains', 1))
+    if records > QUANTILE_MAX_RECORDS:
+        raise ValueError(f'{what}: {steps} steps of {cfg_trainer.get("no_chains", 1)} chains are {records} records; a uint16 count '
+                         f'holds at most {QUANTILE_MAX_RECORDS}: raise `period`')
+    return out
+
+
+def quantiles_summary(isummary, fsummary, n):
+    """the summary of DESIGN.md section 6 from the finalize's reduced columns (host ints / floats): isummary {voxels, voxels
+    with an out-of-range quantile, samples in the two open-ended bins}, fsummary {sum / max of the band's width, sums of the
+    per-channel widths} over the in-range masked voxels, n records.  The means are over the in-range masked voxels and NaN
+    when there is none; out_of_range_frac = out-of-range voxels / voxels and clipped_frac = clipped samples / (3 n voxels)
+    are NaN for an empty mask."""
+    voxels, out_of_range, clipped = (int(x) for x in isummary)
+    w_sum, w_max, wx, wy, wz = (float(x) for x in fsummary)
+    inside = voxels - out_of_range
+    nan = float('nan')
+    return {'records': int(n), 'voxels': voxels, 'out_of_range_voxels': out_of_range, 'clipped_samples': clipped,
+            'width_mean': _nan_div(w_sum, inside), 'width_max': w_max if inside else nan,
+            'width_x': _nan_div(wx, inside), 'width_y': _nan_div(wy, inside), 'width_z': _nan_div(wz, inside),
+            'out_of_range_frac': _nan_div(out_of_range, voxels), 'clipped_frac': _nan_div(clipped, 3 * int(n) * voxels)}
+
+
+class DisplacementQuantiles:
+    """Per voxel and channel, a histogram of the displacement over the recorded samples, pooled over chains, on the device:
+    `centre` (3,D,H,W) float32, the displacement of the very first record, and `hist` (3,bins,D,H,W) uint16, bin-major (one
+    bin of one channel is a contiguous volume).  That is 12 + 6 * bins bytes per voxel whatever the number of records: 396
+    bytes per voxel at 64 bins, 6.6 GB at 256^3.  A count is a uint16, so at most 65535 records are taken.
+
+    `bin_width` is in the units of `scale` (three positive floats, one per channel; default: voxels, as
+    DisplacementCovariance.default_scale): channel a's bins are width_a = float32(bin_width / scale_a) wide in normalised
+    coordinates, and inv_width_a = float32(1) / width_a, computed once, in float32, on the host.  Bins 0 and bins - 1 are
+    open-ended; a quantile that falls into one of them is out of range and reported as NaN.
+    `record(displacement)` takes the (C,3,D,H,W) float32 displacements of one step; `finalize(probs)` gives the quantile
+    maps, the width of the band between the first and the last probability and the summary over a mask."""
+
+    def __init__(self, dims, device, bins=64, bin_width=0.125, scale=None):
+        self.dims = tuple(int(d) for d in dims)
+        if len(self.dims) != 3 or min(self.dims) < 2:
+            raise ValueError(f'displacement quantiles: three dims of at least 2, got {self.dims}')
+        self.device = device
+        self.bins = _quantile_bins(bins, 'displacement quantiles')
+        self.bin_width = _quantile_bin_width(bin_width, 'displacement quantiles')
+        scale = self.default_scale() if scale is None else tuple(float(s) for s in scale)
+        if len(scale) != 3 or not all(math.isfinite(s) and s > 0 for s in scale):
+            raise ValueError(f'displacement quantiles: scale must hold three finite floats > 0, got {scale}')
+        self.scale = scale
+        with np.errstate(all='ignore'):
+            self.width = tuple(np.float32(self.bin_width / s) for s in scale)
+            self.inv_width = tuple(np.float32(1) / w for w in self.width)
+        if not all(np.isfinite(w) and w > 0 and np.isfinite(i) and i > 0 for w, i in zip(self.width, self.inv_width)):
+            raise ValueError(f'displacement quantiles: bin_width {self.bin_width} over scale {scale} is not a float32 width')
+        self.centre = torch.zeros((3,) + self.dims, device=device, dtype=torch.float32)
+        self.hist = torch.zeros((3, self.bins) + self.dims, device=device, dtype=torch.int16).view(torch.uint16)
+        self.records = 0
+
+    @staticmethod
+    def bytes_per_voxel(bins):
+        return 12 + 6 * int(bins)
+
+    def state_bytes(self):
+        D, H, W = self.dims
+        return self.bytes_per_voxel(self.bins) * D * H * W
+
+    def default_scale(self):
+        """normalised coordinates -> voxels, channels x, y, z: (W - 1) / 2, (H - 1) / 2, (D - 1) / 2"""
+        D, H, W = self.dims
+        return ((W - 1) / 2, (H - 1) / 2, (D - 1) / 2)
+
+    def record(self, displacement):
+        C = displacement.shape[0]
+        if self.records + C > QUANTILE_MAX_RECORDS:
+            raise ValueError(f'displacement quantiles: {self.records} + {C} records exceed the {QUANTILE_MAX_RECORDS} a uint16 '
+                             f'count holds')
+        ops.displacement_quantiles_update(displacement, self.centre, self.hist, self.inv_width, self.records)
+        self.records += C
+
+    def histogram(self):
+        """-> (3,bins,D,H,W) int32 on the device: the counts; every voxel and channel sums to `records`"""
+        if self.records < 1:
+            raise RuntimeError('DisplacementQuantiles.histogram: nothing recorded')
+        return self.hist.view(torch.int16).to(torch.int32) & 0xFFFF
+
+    def finalize(self, probs, mask=None):
+        """-> (quantiles (P,3,D,H,W), ci_width (D,H,W), float32 on the device, in the units of `scale`, NaN where out of
+        range; summary dict of quantiles_summary).  One device-to-host read (the summary)."""
+        if self.records < 1:
+            raise RuntimeError('DisplacementQuantiles.finalize: nothing recorded')
+        probs = _quantile_probs(probs, 'displacement quantiles')
+        if mask is not None:
+            mask = mask.to(self.device)
+            mask = mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
+        quantiles, ci_width, isum, fsum = ops.displacement_quantiles_finalize(self.centre, self.hist, self.records, self.width,
+                                                                              self.scale, probs, mask)
+        host = torch.cat([isum.view(torch.float64), fsum]).cpu()
+        ni = isum.numel()
+        summary = quantiles_summary(host[:ni].view(torch.int64).tolist(), host[ni:].tolist(), self.records)
+        return quantiles, ci_width, summary
+
+    def state_dict(self):
+        return {'centre': self.centre.detach().cpu(), 'hist': self.hist.detach().cpu(), 'records': self.records,
+                'bins': self.bins, 'bin_width': self.bin_width}
+
+    def load_state_dict(self, sd):
+        if int(sd['bins']) != self.bins or float(sd['bin_width']) != self.bin_width:
+            raise ValueError(f'displacement quantiles with {sd["bins"]} bins of width {sd["bin_width"]} do not match this run '
+                             f'({self.bins} bins of width {self.bin_width})')
+        for key, lead, dtype in (('centre', (3,), torch.float32), ('hist', (3, self.bins), torch.uint16)):
+            if tuple(sd[key].shape) != lead + self.dims or sd[key].dtype != dtype:
+                raise ValueError(f'displacement quantiles of shape {tuple(sd[key].shape)} {sd[key].dtype} ({key}) do not match '
+                                 f'this run ({lead + self.dims} {dtype})')
+        records = int(sd['records'])
+        if not 0 <= records <= QUANTILE_MAX_RECORDS:
+            raise ValueError(f'displacement quantiles: {records} records, 0..{QUANTILE_MAX_RECORDS} expected')
+        self.centre.copy_(sd['centre'])
+        self.hist.view(torch.int16).copy_(sd['hist'].view(torch.int16))
+        self.records = records

@@ -166,3 +166,23 @@ def save_displacement_covariance(logger, save_dirs, spacing, std, direction, ani
         save_im_to_disk(im, path.join(folder, f'{model}_{name}.nii.gz'), spacing)
         save_im_to_disk(im.where(mask, im.new_zeros(())), path.join(folder, f'{model}_{name}_masked.nii.gz'), spacing)
     save_field_to_disk(direction * std[0], path.join(folder, f'{model}_disp_direction.vtk'), spacing)
+
+
+def save_displacement_quantiles(logger, save_dirs, spacing, probs, quantiles, ci_width, mask, model='MCMC'):
+    """credible intervals of the displacement posterior (absent in the reference): samples/{model}_disp_q{PP}.vtk, one field
+    per probability (PP the probability in percent, `g` formatting, the dot replaced by `p`: q5, q50, q95, q2p5; NaN where out
+    of range), and samples/{model}_disp_ci_width[_masked].nii.gz (float32, in the units of the quantiles; the masked one 0
+    outside the mask)"""
+    folder = _folder(save_dirs, 'samples')
+    mask = mask.reshape(ci_width.shape).to(ci_width.device) != 0
+    finite = ci_width[~ci_width.isnan()]
+    logger.info(f'{model} displacement credible band width max.: {float(finite.max()) if finite.numel() else float("nan"):.4f}')
+    for p, q in zip(probs, quantiles):
+        save_field_to_disk(q, path.join(folder, f'{model}_disp_q{quantile_tag(p)}.vtk'), spacing)
+    save_im_to_disk(ci_width, path.join(folder, f'{model}_disp_ci_width.nii.gz'), spacing)
+    save_im_to_disk(ci_width.where(mask, ci_width.new_zeros(())), path.join(folder, f'{model}_disp_ci_width_masked.nii.gz'), spacing)
+
+
+def quantile_tag(p):
+    """0.05 -> '5', 0.5 -> '50', 0.025 -> '2p5'"""
+    return f'{100.0 * float(p):g}'.replace('.', 'p')

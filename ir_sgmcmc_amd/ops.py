@@ -484,3 +484,75 @@ def displacement_covariance_finalize(mean, comoment, n, scale, mask=None):
                                                      L.dev_ptr(isummary), L.dev_ptr(fsummary), L.dev_ptr(ws),
                                                      L.IRS_COVARIANCE_WS_BYTES, L.stream_ptr()))
     return std, direction, anisotropy, isummary, fsummary
+
+
+def _quantile_state(centre, hist, bins, shape):
+    D, H, W = shape
+    bins = int(bins)
+    if not (L.IRS_QUANTILE_MIN_BINS <= bins <= L.IRS_QUANTILE_MAX_BINS) or bins % 2:
+        raise L.IrsError(f'bins must be an even number in {L.IRS_QUANTILE_MIN_BINS}..{L.IRS_QUANTILE_MAX_BINS}, got {bins}')
+    if tuple(centre.shape) != (3, D, H, W) or centre.dtype != torch.float32:
+        raise L.IrsError(f'centre must be a {(3, D, H, W)} torch.float32 tensor, got {centre.dtype} {tuple(centre.shape)}')
+    if tuple(hist.shape) != (3, bins, D, H, W) or hist.dtype != torch.uint16:
+        raise L.IrsError(f'hist must be a {(3, bins, D, H, W)} torch.uint16 tensor, got {hist.dtype} {tuple(hist.shape)}')
+    return bins
+
+
+def _three_positive(name, values):
+    values = [float(v) for v in values]
+    if len(values) != 3 or not all(math.isfinite(v) and v > 0 for v in values):
+        raise L.IrsError(f'{name} must hold three finite floats > 0, got {values}')
+    return (C.c_float * 3)(*values)
+
+
+def displacement_quantiles_update(displacement, centre, hist, inv_width, records_before):
+    """Count one recorded step into the displacement histograms behind the credible intervals (absent in the reference, which
+    keeps moments only): displacement (C,3,D,H,W) float32 in normalised coordinates, every chain's sample; centre (3,D,H,W)
+    float32 and hist (3,bins,D,H,W) uint16, bin-major; inv_width: three positive floats, one per channel (rounded to float32).
+    `records_before` records were counted before: 0 writes centre from chain 0 and overwrites hist; records_before + C may
+    not exceed IRS_QUANTILE_MAX_RECORDS, what a uint16 count holds.  include/irsgmcmc.h gives the bin of a value.  No host
+    synchronisation."""
+    lib = L.load()
+    Cn, D, H, W = _dims5(displacement, 3)
+    bins = _quantile_state(centre, hist, hist.shape[1] if hist.dim() == 5 else 0, (D, H, W))
+    records_before = int(records_before)
+    if records_before < 0 or records_before + Cn > L.IRS_QUANTILE_MAX_RECORDS:
+        raise L.IrsError(f'{records_before} + {Cn} records: a uint16 count holds 0..{L.IRS_QUANTILE_MAX_RECORDS}')
+    L.check(lib.irs_displacement_quantiles_update(L.dev_ptr(displacement, torch.float32), Cn, D, H, W,
+                                                  L.dev_ptr(centre, torch.float32), L.dev_ptr(hist, torch.uint16), bins,
+                                                  _three_positive('inv_width', inv_width), records_before, L.stream_ptr()))
+
+
+def displacement_quantiles_finalize(centre, hist, n, width, scale, probs, mask=None):
+    """The quantile maps, the width of the credible band and its masked summary after n records (absent in the reference).
+    centre (3,D,H,W) float32, hist (3,bins,D,H,W) uint16; width, scale: three positive floats each, one per channel; probs:
+    2..IRS_QUANTILE_MAX_PROBS strictly increasing probabilities in (0,1); mask (D,H,W) bool / uint8 or None.  -> (quantiles
+    (P,3,D,H,W), ci_width (D,H,W), float32, isummary (3,) int64, fsummary (5,) float64), all on the device:
+    include/irsgmcmc.h gives the definitions and the columns.  No host synchronisation."""
+    lib = L.load()
+    if centre.dim() != 4:
+        raise L.IrsError(f'centre must have shape (3,D,H,W), got {tuple(centre.shape)}')
+    D, H, W = centre.shape[1:]
+    bins = _quantile_state(centre, hist, hist.shape[1] if hist.dim() == 5 else 0, (D, H, W))
+    mask = _volume_mask(mask, D, H, W)
+    probs = [float(p) for p in probs]
+    if not 2 <= len(probs) <= L.IRS_QUANTILE_MAX_PROBS:
+        raise L.IrsError(f'probs must hold 2..{L.IRS_QUANTILE_MAX_PROBS} probabilities, got {len(probs)}')
+    if not all(0.0 < p < 1.0 for p in probs) or any(b <= a for a, b in zip(probs, probs[1:])):
+        raise L.IrsError(f'probs must be strictly increasing in (0,1), got {probs}')
+    n = int(n)
+    if not 1 <= n <= L.IRS_QUANTILE_MAX_RECORDS:
+        raise L.IrsError(f'n = {n} records, 1..{L.IRS_QUANTILE_MAX_RECORDS} needed')
+    width, scale = _three_positive('width', width), _three_positive('scale', scale)
+    dev, P = centre.device, len(probs)
+    ws = torch.empty(L.IRS_QUANTILE_WS_BYTES, device=dev, dtype=torch.uint8)
+    quantiles = torch.empty((P, 3, D, H, W), device=dev, dtype=torch.float32)
+    ci_width = torch.empty((D, H, W), device=dev, dtype=torch.float32)
+    isummary = torch.empty(L.IRS_QUANTILE_SUMMARY_INTS, device=dev, dtype=torch.int64)
+    fsummary = torch.empty(L.IRS_QUANTILE_SUMMARY_FLOATS, device=dev, dtype=torch.float64)
+    L.check(lib.irs_displacement_quantiles_finalize(L.dev_ptr(centre, torch.float32), L.dev_ptr(hist, torch.uint16), bins, D, H, W,
+                                                    n, width, scale, (C.c_double * P)(*probs), P,
+                                                    L.dev_ptr(mask, torch.uint8, True), L.dev_ptr(quantiles),
+                                                    L.dev_ptr(ci_width), L.dev_ptr(isummary), L.dev_ptr(fsummary), L.dev_ptr(ws),
+                                                    L.IRS_QUANTILE_WS_BYTES, L.stream_ptr()))
+    return quantiles, ci_width, isummary, fsummary

@@ -11,8 +11,9 @@ from pathlib import Path
 import numpy as np
 
 from .data_loader import data_loaders as module_data
-from .diagnostics import (COVARIANCE_METRICS, JACOBIAN_METRICS, LABEL_STRUCTURE_METRICS, diagnostics_period,
-                          displacement_covariance_options, ess_options, jacobian_posterior_options, label_posterior_options)
+from .diagnostics import (COVARIANCE_METRICS, JACOBIAN_METRICS, LABEL_STRUCTURE_METRICS, QUANTILE_METRICS, diagnostics_period,
+                          displacement_covariance_options, displacement_quantiles_options, ess_options,
+                          jacobian_posterior_options, label_posterior_options)
 from .logger import setup_logging
 from .model import distributions as model_distr
 from .model import loss as model_loss
@@ -105,6 +106,8 @@ class ConfigParser:
             m += [f'MCMC/jacobian/{k}' for k in JACOBIAN_METRICS]
         if displacement_covariance_options(self['trainer']) is not None:
             m += [f'MCMC/covariance/{k}' for k in COVARIANCE_METRICS]
+        if displacement_quantiles_options(self['trainer']) is not None:
+            m += [f'MCMC/quantiles/{k}' for k in QUANTILE_METRICS]
         return m
 
     def init_transformation_and_registration_modules(self):

@@ -17,12 +17,13 @@ import numpy as np
 import torch
 
 from ..base import BaseTrainer
-from ..diagnostics import (COVARIANCE_METRICS, ChainMoments, DisplacementCovariance, JACOBIAN_METRICS, JacobianPosterior,
-                           LABEL_STRUCTURE_METRICS, LabelPosterior, diagnostics_period, displacement_covariance_options,
-                           ess_options, is_recorded, jacobian_posterior_options, label_posterior_options)
+from ..diagnostics import (COVARIANCE_METRICS, ChainMoments, DisplacementCovariance, DisplacementQuantiles, JACOBIAN_METRICS,
+                           JacobianPosterior, LABEL_STRUCTURE_METRICS, LabelPosterior, QUANTILE_METRICS, diagnostics_period,
+                           displacement_covariance_options, displacement_quantiles_options, ess_options, is_recorded,
+                           jacobian_posterior_options, label_posterior_options)
 from ..engine import EngineConfig, TransitionEngine
-from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_ess, save_jacobian_posterior,
-                      save_label_posterior, save_rhat, save_sample)
+from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_quantiles, save_ess,
+                      save_jacobian_posterior, save_label_posterior, save_rhat, save_sample)
 from ..utils import calc_norm, calc_no_non_diffeomorphic_voxels, calc_metrics, sample_q_v
 from .vi import VIMixin
 
@@ -81,6 +82,10 @@ class Trainer(VIMixin, BaseTrainer):
         self._displacement_covariance = None
         self.displacement_cov_std, self.displacement_cov_direction = None, None
         self.displacement_cov_anisotropy, self.displacement_cov_summary = None, None
+        # displacement credible intervals (diagnostics.DisplacementQuantiles): None when trainer.displacement_quantiles is off
+        self.quantiles_options = displacement_quantiles_options(cfg_trainer)
+        self._displacement_quantiles = None
+        self.displacement_quantiles, self.displacement_ci_width, self.displacement_quantiles_summary = None, None, None
 
     # ---------------------------------------------------------------- engine plumbing
     def _engine_config(self):
@@ -181,7 +186,9 @@ class Trainer(VIMixin, BaseTrainer):
                 **({'label_posterior': self._label_posterior.state_dict()} if self._label_posterior is not None else {}),
                 **({'jacobian_posterior': self._jacobian_posterior.state_dict()} if self._jacobian_posterior is not None else {}),
                 **({'displacement_covariance': self._displacement_covariance.state_dict()}
-                   if self._displacement_covariance is not None else {})}
+                   if self._displacement_covariance is not None else {}),
+                **({'displacement_quantiles': self._displacement_quantiles.state_dict()}
+                   if self._displacement_quantiles is not None else {})}
 
     def load_state_dict(self, sd):
         import ctypes
@@ -229,6 +236,14 @@ class Trainer(VIMixin, BaseTrainer):
             elif any(is_recorded(s, self.no_iters_burn_in, period) for s in range(1, self._sample_no + 1)):
                 raise ValueError(f'the checkpoint at sample {self._sample_no} holds no displacement covariance (written with '
                                  f'trainer.displacement_covariance off) but this run records from sample '
+                                 f'{self.no_iters_burn_in + period} on')
+        if self._displacement_quantiles is not None:
+            period = self.quantiles_options['period']
+            if 'displacement_quantiles' in sd:
+                self._displacement_quantiles.load_state_dict(sd['displacement_quantiles'])
+            elif any(is_recorded(s, self.no_iters_burn_in, period) for s in range(1, self._sample_no + 1)):
+                raise ValueError(f'the checkpoint at sample {self._sample_no} holds no displacement quantiles (written with '
+                                 f'trainer.displacement_quantiles off) but this run records from sample '
                                  f'{self.no_iters_burn_in + period} on')
         self.sync_parameters()
 
@@ -346,6 +361,13 @@ class Trainer(VIMixin, BaseTrainer):
             self._jacobian_posterior = JacobianPosterior(self._outputs['transformation'].shape[2:], self.device)
         if self.covariance_options is not None:
             self._displacement_covariance = DisplacementCovariance(self._outputs['displacement'].shape[2:], self.device)
+        if self.quantiles_options is not None:
+            q = self.quantiles_options
+            self._displacement_quantiles = DisplacementQuantiles(self._outputs['displacement'].shape[2:], self.device, q['bins'],
+                                                                 q['bin_width'])
+            self.logger.info(f'displacement quantiles: {q["bins"]} bins of {q["bin_width"]:g} voxels, '
+                             f'{self._displacement_quantiles.bytes_per_voxel(q["bins"])} bytes per voxel, '
+                             f'{self._displacement_quantiles.state_bytes() / 1e6:.1f} MB on the device')
         if cfg_trainer.get('resume'):
             self.load_checkpoint(cfg_trainer['resume'])
             first = self._sample_no + 1
@@ -423,6 +445,10 @@ class Trainer(VIMixin, BaseTrainer):
                                                                          self.covariance_options['period']):
                 self.engine.flush()  # as above
                 self._displacement_covariance.record(output['displacement'])
+            if self._displacement_quantiles is not None and is_recorded(sample_no, self.no_iters_burn_in,
+                                                                        self.quantiles_options['period']):
+                self.engine.flush()  # as above
+                self._displacement_quantiles.record(output['displacement'])
             if checkpoint_period and sample_no % checkpoint_period == 0:
                 self._sample_no, self._moments = sample_no, {'mean': mean, 'm2': m2, 'n': n_rec}
                 folder = self.config.save_dirs['checkpoints']
@@ -443,6 +469,9 @@ class Trainer(VIMixin, BaseTrainer):
         if self._displacement_covariance is not None:
             self._finish_displacement_covariance(moving.get('mask', fixed['mask'])[0], spacing,
                                                  cfg_trainer.get('save_outputs', True))
+        if self._displacement_quantiles is not None:
+            self._finish_displacement_quantiles(moving.get('mask', fixed['mask'])[0], spacing,
+                                                cfg_trainer.get('save_outputs', True))
 
         # speed test (trainer.py:467-476): 100 x [transition + nearest-neighbour warp of the segmentation]
         n_speed = 100
@@ -542,6 +571,30 @@ class Trainer(VIMixin, BaseTrainer):
         if save_outputs:
             save_displacement_covariance(self.logger, self.config.save_dirs, spacing, self.displacement_cov_std,
                                          self.displacement_cov_direction, self.displacement_cov_anisotropy, mask, 'MCMC')
+
+    def _finish_displacement_quantiles(self, mask, spacing, save_outputs):
+        """quantiles of the displacement posterior (voxels) at the option's probabilities, the width of the band between the
+        first and the last and their summary -> self.displacement_quantiles / displacement_ci_width /
+        displacement_quantiles_summary, the MCMC/quantiles/* metrics and, with save_outputs, samples/MCMC_disp_q{PP}.vtk and
+        MCMC_disp_ci_width[_masked].nii.gz.  The summary is over the mask the displacement std map uses."""
+        dq, opt = self._displacement_quantiles, self.quantiles_options
+        self.displacement_quantiles, self.displacement_ci_width, self.displacement_quantiles_summary = dq.finalize(opt['probs'], mask)
+        s = self.displacement_quantiles_summary
+        for key in QUANTILE_METRICS:
+            self.metrics.update(f'MCMC/quantiles/{key}', s[key])
+        lo, hi = opt['probs'][0], opt['probs'][-1]
+        self.logger.info(f'displacement quantiles of {s["records"]} samples over {s["voxels"]} masked voxels: width of the '
+                         f'{100 * lo:g} % - {100 * hi:g} % band mean {s["width_mean"]:.4f}, max {s["width_max"]:.4f} voxels '
+                         f'(x {s["width_x"]:.4f}, y {s["width_y"]:.4f}, z {s["width_z"]:.4f}); {s["out_of_range_voxels"]} voxels '
+                         f'out of range ({100 * s["out_of_range_frac"]:.3f} %), {100 * s["clipped_frac"]:.3f} % of the samples '
+                         f'in the open-ended bins')
+        if s['out_of_range_frac'] > 0:
+            self.logger.warning(f'displacement quantiles: {s["out_of_range_voxels"]} masked voxels have a quantile outside the '
+                                f'{opt["bins"]} bins of {opt["bin_width"]:g} voxels around the first sample and are NaN in the '
+                                f'maps: raise trainer.displacement_quantiles.bin_width (or bins)')
+        if save_outputs:
+            save_displacement_quantiles(self.logger, self.config.save_dirs, spacing, opt['probs'], self.displacement_quantiles,
+                                        self.displacement_ci_width, mask, 'MCMC')
 
     def _run_model(self):
         for fixed, moving, var_params_q_v in self.data_loader:

@@ -199,6 +199,23 @@ def calc_displacement_covariance(displacements, mask=None, scale=None):
 
 
 @torch.no_grad()
+def calc_displacement_quantiles(displacements, probs=(0.05, 0.5, 0.95), mask=None, bins=64, bin_width=0.125, scale=None):
+    """Per-voxel quantiles of displacement samples and the width of the band between the first and the last (absent in the
+    reference): displacements (n,3,D,H,W) float32 on the device, in normalised coordinates, n <= 65535 records, the first one
+    the centre of the histograms; probs: 2 to 8 increasing probabilities; mask (D,H,W) or None; bins of `bin_width` in the units
+    of `scale` (three floats, one per channel; default: voxels).  -> (quantiles (P,3,D,H,W), ci_width (D,H,W), summary dict), as
+    diagnostics.DisplacementQuantiles.finalize."""
+    from .. import _lib as L
+    from ..diagnostics import DisplacementQuantiles
+    if displacements.dim() != 5 or displacements.shape[1] != 3:
+        raise ValueError(f'displacements must have shape (n, 3, D, H, W), got {tuple(displacements.shape)}')
+    dq = DisplacementQuantiles(displacements.shape[2:], displacements.device, bins, bin_width, scale)
+    for i in range(0, displacements.shape[0], L.IRS_MAX_CHAINS):  # one launch counts up to IRS_MAX_CHAINS records
+        dq.record(displacements[i:i + L.IRS_MAX_CHAINS].float().contiguous())
+    return dq.finalize(probs, mask)
+
+
+@torch.no_grad()
 def calc_DSC_GPU(no_samples, seg_fixed, seg_moving, structures_dict):
     """Dice scores on the device (utils/util.py:123-148)"""
     DSC = torch.zeros(no_samples, len(structures_dict))
