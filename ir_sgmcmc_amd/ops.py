@@ -99,10 +99,24 @@ def ffd_adjoint(g_dense, cps):
     return g_cp
 
 
+def _chain_volumes(name, t, like_name, Cn, D, H, W, shared_ok=True):
+    """t must be (Cn,1,D,H,W) -- or (1,1,D,H,W), one volume shared by the chains, where the ABI takes a chain count for it"""
+    if t.dim() != 5 or t.shape[1] != 1 or t.shape[0] not in ((1, Cn) if shared_ok else (Cn,)) or tuple(t.shape[2:]) != (D, H, W):
+        raise L.IrsError(f'{name} shape {tuple(t.shape)} does not match {like_name}: '
+                         f'({"1 or " if shared_ok else ""}{Cn},1,{D},{H},{W}) expected')
+
+
+def _jitter_draws(unif, d_last):
+    if unif is not None and tuple(unif.shape) != tuple(d_last.shape):
+        raise L.IrsError(f'unif shape {tuple(unif.shape)} does not match d_last {tuple(d_last.shape)}')
+
+
 def warp_displacement(im, d_last, unif=None, alpha=0.0, seed=0, iteration=0):
     """Trilinear warp at id + d_last (+ uniform jitter): registration_module(im, transformation_with_noise)."""
     lib = L.load()
     Cn, D, H, W = _dims5(d_last, 3)
+    _chain_volumes('image', im, 'd_last', Cn, D, H, W)
+    _jitter_draws(unif, d_last)
     out = torch.empty((Cn, 1, D, H, W), device=d_last.device, dtype=torch.float32)
     L.check(lib.irs_warp_fwd(L.dev_ptr(im, torch.float32), im.shape[0], L.dev_ptr(d_last, torch.float32),
                              L.dev_ptr(unif, torch.float32, True), float(alpha), L.dev_ptr(out), Cn, D, H, W, seed,
@@ -113,6 +127,9 @@ def warp_displacement(im, d_last, unif=None, alpha=0.0, seed=0, iteration=0):
 def warp_displacement_bwd(im, d_last, g_warped, unif=None, alpha=0.0, seed=0, iteration=0):
     lib = L.load()
     Cn, D, H, W = _dims5(d_last, 3)
+    _chain_volumes('image', im, 'd_last', Cn, D, H, W)
+    _chain_volumes('g_warped', g_warped, 'd_last', Cn, D, H, W, shared_ok=False)
+    _jitter_draws(unif, d_last)
     g_d = torch.empty_like(d_last)
     L.check(lib.irs_warp_bwd(L.dev_ptr(im, torch.float32), im.shape[0], L.dev_ptr(d_last, torch.float32),
                              L.dev_ptr(unif, torch.float32, True), float(alpha),
@@ -157,6 +174,7 @@ def lcc_normalise(im, s, want_sigma=False):
 def lcc_map_fwd(fhat, warped, s):
     lib = L.load()
     Cn, D, H, W = _dims5(warped, 1)
+    _chain_volumes('fhat', fhat, 'warped', Cn, D, H, W)
     z = torch.empty_like(warped)
     sig = torch.empty_like(warped)
     L.check(lib.irs_lcc_map_fwd(L.dev_ptr(fhat, torch.float32), fhat.shape[0], L.dev_ptr(warped, torch.float32),
@@ -167,6 +185,9 @@ def lcc_map_fwd(fhat, warped, s):
 def lcc_map_bwd(fhat, z, sigma_m, g_z, s):
     lib = L.load()
     Cn, D, H, W = _dims5(z, 1)
+    _chain_volumes('fhat', fhat, 'z', Cn, D, H, W)
+    _chain_volumes('sigma_m', sigma_m, 'z', Cn, D, H, W, shared_ok=False)
+    _chain_volumes('g_z', g_z, 'z', Cn, D, H, W, shared_ok=False)
     g = torch.empty_like(z)
     L.check(lib.irs_lcc_map_bwd(L.dev_ptr(fhat, torch.float32), fhat.shape[0], L.dev_ptr(z, torch.float32),
                                 L.dev_ptr(sigma_m, torch.float32), L.dev_ptr(g_z.contiguous(), torch.float32), L.dev_ptr(g),
