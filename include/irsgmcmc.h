@@ -32,6 +32,7 @@ extern "C" {
 #define IRS_MAX_CHAINS 8
 #define IRS_MAX_HALF_WIDTH 4 /* Sobolev / LCC half widths up to 4 */
 #define IRS_MAX_LABELS 64    /* labels of one surface-distance call */
+#define IRS_HAUSDORFF_MAX_PERCENTILES 4 /* percentiles of one irs_label_hausdorff_distance call */
 
 enum { IRS_DATA_GMM_LCC = 0, IRS_DATA_SSD = 1 };
 enum { IRS_REG_L2 = 0, IRS_REG_LOGNORMAL = 1, IRS_REG_STUDENT = 2, IRS_REG_LOGNORMAL_L2 = 3 };
@@ -130,6 +131,28 @@ int irs_label_surface_distance(const int16_t* seg_fixed, int Cf, const int16_t* 
                                int n_labels, const float* spacing, const int32_t* boxes, void* workspace,
                                size_t workspace_bytes, long long* counts, double* sums, int C, int D, int H, int W,
                                void* stream);
+
+/* Hausdorff and percentile surface distances of the same contours with the same distances (absent in the reference, which
+ * logs only the average; sitk.HausdorffDistanceImageFilter.GetHausdorffDistance is the maximum).  Per pair p and direction:
+ * S_AB = { d(a, B) : a in A }, S_BA likewise.  The directed percentile q in (0, 100] of a set of n distances is its ascending
+ * order statistic of 0-based index k = min(max((int64)ceil(q * (double)n / 100.0) - 1, 0), n - 1), evaluated in double in
+ * that order (numpy's method='inverted_cdf'): the smallest distance within which at least q % of the contour voxels lie.  The
+ * directed maximum is the percentile at q = 100.  Selection is exact, on the float32 squared distances of the transform; the
+ * value written is sqrt((double)d2) of the selected float.
+ *  - boxes: from irs_label_boxes, copied to the host, as for irs_label_surface_distance (no other read-back: the ranks are
+ *    formed on the device from the counts); irs_hausdorff_workspace sizes the workspace for Q percentiles.
+ *  - percentiles: HOST, Q in 0..IRS_HAUSDORFF_MAX_PERCENTILES values, each in (0, 100], strictly increasing.
+ *  - counts, sums: as irs_label_surface_distance writes them, bit-identical.
+ *  - hd (P,2) doubles: hd[2p] = max over A of d(., B), hd[2p+1] = max over B of d(., A); taken as a maximum of the distances,
+ *    not by the selection.  hd_pct (Q,P,2) doubles, [(q * P + p) * 2 + direction]; may be NULL when Q == 0.
+ *  - every directed value of a pair is +inf when A or B is empty; NaN is never written.  The symmetric distances are the
+ *    larger of the two directions.  Deterministic (integer atomics only, no float atomics).  Device outputs; blocking only
+ *    for the upload of the per-pair table. */
+int irs_hausdorff_workspace(const int32_t* boxes, int n_pairs, int Q, int D, int H, int W, size_t* bytes);
+int irs_label_hausdorff_distance(const int16_t* seg_fixed, int Cf, const int16_t* seg_moving, const int32_t* labels,
+                                 int n_labels, const float* spacing, const int32_t* boxes, void* workspace,
+                                 size_t workspace_bytes, const double* percentiles, int Q, long long* counts, double* sums,
+                                 double* hd, double* hd_pct, int C, int D, int H, int W, void* stream);
 
 /* Split-R-hat of a vector field over chains (absent in the reference; Gelman et al., BDA3 section 11.4), from online moments.
  * Layouts: x (C,3,D,H,W) fp32; mean / m2 (2,C,3,D,H,W) fp32, the Welford state of each half of each chain's samples.

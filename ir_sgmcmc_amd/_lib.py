@@ -16,6 +16,7 @@ IRS_MAX_COMPONENTS = 8
 IRS_MAX_CHAINS = 8
 IRS_MAX_HALF_WIDTH = 4
 IRS_MAX_LABELS = 64
+IRS_HAUSDORFF_MAX_PERCENTILES = 4
 IRS_LABEL_BINS = 10
 IRS_JACOBIAN_SUMMARY_INTS, IRS_JACOBIAN_SUMMARY_FLOATS = 4, 5
 IRS_JACOBIAN_WS_BYTES = 1024 * (IRS_JACOBIAN_SUMMARY_INTS + IRS_JACOBIAN_SUMMARY_FLOATS) * 8
@@ -140,6 +141,9 @@ SIGNATURES = {
     'irs_surface_distance_workspace': [_I32P, _I, _I, _I, _I, C.POINTER(C.c_size_t)],
     'irs_label_surface_distance': [_P, _I, _P, _I32P, _I, C.POINTER(C.c_float), _I32P, _P, C.c_size_t, _P, _P, _I, _I, _I, _I,
                                    _P],
+    'irs_hausdorff_workspace': [_I32P, _I, _I, _I, _I, _I, C.POINTER(C.c_size_t)],
+    'irs_label_hausdorff_distance': [_P, _I, _P, _I32P, _I, C.POINTER(C.c_float), _I32P, _P, C.c_size_t, C.POINTER(C.c_double), _I,
+                                     _P, _P, _P, _P, _I, _I, _I, _I, _P],
     'irs_chain_moments_update': [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     'irs_split_rhat_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
     'irs_split_rhat': [_P, _P, _I, _I, _P, C.c_float, C.c_float, _P, _P, _P, C.c_size_t, _I, _I, _I, _P],

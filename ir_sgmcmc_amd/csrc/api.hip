@@ -624,6 +624,122 @@ int irs_label_surface_distance(const int16_t* seg_fixed, int Cf, const int16_t* 
     return 0;
 }
 
+}  // extern "C"
+
+// ================================================================================================
+// Hausdorff and percentile surface distances (metric_kernels.hip pass D with KEEP + hausdorff_kernels.hip)
+// ================================================================================================
+namespace {
+
+constexpr int64_t kHdSliceVoxels = 65536;  // voxels of the largest box per histogram block ...
+constexpr int kHdMaxSlices = 256;          // ... up to this many blocks per (pair, direction)
+
+// the ASD workspace, then the per-task maxima, the histograms and the per-rank state of the selection
+struct HdLayout {
+    SurfLayout s;
+    int slices = 1;
+    size_t maxpart_off = 0, hist_off = 0, hist_bytes = 0, prefix_off = 0, rank_off = 0, bytes = 0;
+};
+
+int hausdorff_layout(const int32_t* boxes, int P, int Q, int D, int H, int W, HdLayout* out) {
+    if (Q < 0 || Q > IRS_HAUSDORFF_MAX_PERCENTILES)
+        return fail("irs_label_hausdorff_distance: 0..%d percentiles, got %d", IRS_HAUSDORFF_MAX_PERCENTILES, Q);
+    HdLayout& h = *out;
+    if (surface_layout(boxes, P, D, H, W, &h.s)) return 1;
+    int64_t largest = 1;
+    for (int p = 0; p < P; ++p) largest = std::max(largest, h.s.plan[p + 1].vox - h.s.plan[p].vox);
+    h.slices = (int)std::min<int64_t>((largest + kHdSliceVoxels - 1) / kHdSliceVoxels, kHdMaxSlices);
+    size_t off = h.s.bytes;
+    h.maxpart_off = off;
+    off = surf_align(off + sizeof(uint32_t) * 2 * (size_t)h.s.tasks[2]);
+    h.hist_off = off;
+    h.hist_bytes = sizeof(uint32_t) * 256 * 4 * 2 * (size_t)P * Q;
+    off = surf_align(off + h.hist_bytes);
+    h.prefix_off = off;
+    off = surf_align(off + sizeof(uint32_t) * 2 * (size_t)P * Q);
+    h.rank_off = off;
+    off = surf_align(off + sizeof(long long) * 2 * (size_t)P * Q);
+    h.bytes = off;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int irs_hausdorff_workspace(const int32_t* boxes, int n_pairs, int Q, int D, int H, int W, size_t* bytes) {
+    if (!bytes) return fail("irs_hausdorff_workspace: null argument");
+    HdLayout h;
+    if (hausdorff_layout(boxes, n_pairs, Q, D, H, W, &h)) return 1;
+    *bytes = h.bytes;
+    return 0;
+}
+
+int irs_label_hausdorff_distance(const int16_t* seg_fixed, int Cf, const int16_t* seg_moving, const int32_t* labels,
+                                 int n_labels, const float* spacing, const int32_t* boxes, void* workspace,
+                                 size_t workspace_bytes, const double* percentiles, int Q, long long* counts, double* sums,
+                                 double* hd, double* hd_pct, int C, int D, int H, int W, void* stream) {
+    if (!seg_fixed || !seg_moving || !spacing || !workspace || !counts || !sums || !hd || !dims_ok(C, D, H, W) ||
+        C > IRS_MAX_CHAINS || (Cf != 1 && Cf != C))
+        return fail("irs_label_hausdorff_distance: bad arguments");
+    if (!labels_ok(labels, n_labels)) return fail("irs_label_hausdorff_distance: 1..%d labels in the int16 range", IRS_MAX_LABELS);
+    for (int a = 0; a < 3; ++a)
+        if (!(spacing[a] > 0.0f) || !isfinite(spacing[a])) return fail("irs_label_hausdorff_distance: spacing must be positive");
+    HdLayout h;
+    if (hausdorff_layout(boxes, C * n_labels, Q, D, H, W, &h)) return 1;
+    if (Q > 0 && (!percentiles || !hd_pct)) return fail("irs_label_hausdorff_distance: %d percentiles need percentiles and hd_pct", Q);
+    for (int r = 0; r < Q; ++r)
+        if (!(percentiles[r] > 0.0) || !(percentiles[r] <= 100.0) || (r > 0 && !(percentiles[r] > percentiles[r - 1])))
+            return fail("irs_label_hausdorff_distance: percentiles must lie in (0, 100] and increase strictly");
+    if (workspace_bytes < h.bytes)
+        return fail("irs_label_hausdorff_distance: workspace of %zu bytes, %zu needed (irs_hausdorff_workspace)", workspace_bytes, h.bytes);
+    const SurfLayout& s = h.s;
+    const hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = (uint8_t*)workspace;
+    // as irs_label_surface_distance: the small table is waited for so that the host vector may go
+    HIP_TRY(hipMemcpyAsync(ws, s.plan.data(), sizeof(SurfPair) * s.plan.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h.hist_bytes) HIP_TRY(hipMemsetAsync(ws + h.hist_off, 0, h.hist_bytes, st));
+    SurfPassArgs a = {};
+    a.plan = (const SurfPair*)ws;
+    a.P = C * n_labels;
+    for (int pass = 0; pass < 3; ++pass) {
+        a.tasks[pass] = s.tasks[pass];
+        a.line[pass] = s.line[pass];
+        a.env_scratch[pass] = s.slots[pass] ? (float*)(ws + s.env_off[pass]) : nullptr;
+        a.env_slots[pass] = s.slots[pass];
+    }
+    a.lanes = s.lanes;
+    a.memb = ws + s.memb_off;
+    a.gA = (float*)(ws + s.ga_off);
+    a.gB = (float*)(ws + s.gb_off);
+    a.partials = (double*)(ws + s.partials_off);
+    a.maxpart = (uint32_t*)(ws + h.maxpart_off);  // pass D keeps the squared distances
+    SurfLabels lab = {};
+    memcpy(lab.v, labels, sizeof(int32_t) * n_labels);
+    const Vol vol = make_vol(D, H, W);
+    launch_surface_distance(seg_fixed, Cf == 1 ? 0 : vol.V, seg_moving, lab, n_labels, spacing, a, counts, sums, vol, st);
+    HdArgs g = {};
+    g.plan = a.plan;
+    g.P = a.P;
+    g.Q = Q;
+    g.slices = h.slices;
+    for (int r = 0; r < Q; ++r) g.pct[r] = percentiles[r];
+    g.memb = a.memb;
+    g.gA = a.gA;
+    g.gB = a.gB;
+    g.counts = counts;
+    g.maxpart = a.maxpart;
+    g.hist = (uint32_t*)(ws + h.hist_off);
+    g.prefix = (uint32_t*)(ws + h.prefix_off);
+    g.rank = (long long*)(ws + h.rank_off);
+    g.hd = hd;
+    g.hd_pct = hd_pct;
+    launch_hausdorff_select(g, st);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 // ================================================================================================
 // split-R-hat over chains (diag_kernels.hip)
 // ================================================================================================

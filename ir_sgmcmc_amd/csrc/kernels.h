@@ -144,10 +144,33 @@ struct SurfPassArgs {
     float* gA;
     float* gB;
     double* partials;     // 4 per task of pass D: nA, nB, sum A->B, sum B->A
+    uint32_t* maxpart;    // NULL: the ASD alone.  Else pass D keeps the squared distances in gA / gB and writes 2 per task: the
+                          // largest d2 (float bits) over A of the distance to B, over B of the distance to A
 };
 void launch_surface_distance(const int16_t* fixed, int64_t f_stride, const int16_t* moving, const SurfLabels& lab, int L,
                              const float spacing[3], const SurfPassArgs& a, long long* counts, double* sums, Vol vol,
                              hipStream_t st);
+
+// ---- hausdorff_kernels.hip: exact order statistics of the contour distances that pass D kept (maxpart != NULL above)
+// Direction 0 = the distances of the voxels of A to B (membership bit 1, values in gB), direction 1 = of B to A (bit 2, gA).
+// MSB-first radix select on the float bits, 8 bits per pass: per pass one histogram launch (blocks = slices x 2P, integer
+// counts in LDS, then integer global atomics) and one scan launch that narrows every rank to its bin.
+struct HdArgs {
+    const SurfPair* plan;
+    int P, Q, slices;
+    double pct[IRS_HAUSDORFF_MAX_PERCENTILES];
+    const uint8_t* memb;
+    const float* gA;
+    const float* gB;
+    const long long* counts;  // (P,2) of the reduction: |A|, |B|
+    const uint32_t* maxpart;
+    uint32_t* hist;           // [4 passes][2P][Q][256], zero on entry
+    uint32_t* prefix;         // [2P][Q]: the key bits fixed so far
+    long long* rank;          // [2P][Q]: 0-based rank among the keys that share the prefix; -1: an empty contour
+    double* hd;               // (P,2)
+    double* hd_pct;           // (Q,P,2)
+};
+void launch_hausdorff_select(const HdArgs& a, hipStream_t st);
 
 // ---- diag_kernels.hip: split-R-hat and split ESS over chains (absent in the reference; BDA3 sections 11.4-11.5)
 // Welford update of one half's (mean, m2) with the sample x, all flat arrays of n floats; k = samples in the half after this one

@@ -11,6 +11,8 @@
 //    to kSurfLdsLine) or in a global scratch slot with the same layout (longer lines).
 //  - pass D writes no distance map: it adds the distances at the contour voxels into per-task partial sums (double),
 //    which one block per pair reduces in fixed order.  No atomics touch a float: two calls are bit-identical.
+//  - pass D with KEEP (the Hausdorff distances, hausdorff_kernels.hip) also writes the squared distances back in place and
+//    keeps the largest one at the contour voxels of each direction per task, as the bits of the float.
 #include <limits.h>
 
 #include <algorithm>
@@ -180,9 +182,17 @@ __device__ __forceinline__ int lower_envelope(const float* __restrict__ g, int64
     return k;
 }
 
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_down((int)v, off, kWave));
+    return v;
+}
+
 // passes H (LAST = false: along y, in place) and D (LAST = true: along z, ends in the partial sums of the task).
 // A wavefront per task (pair, plane or row, 64-wide x chunk); grid-stride over the tasks.
-template <bool IN_LDS, bool LAST>
+// KEEP (pass D only): the squared distances are also written back in place -- safe, a lane has finished lower_envelope over
+// its whole column before the scan, as pass H relies on -- and the largest key of each direction goes to a.maxpart.
+template <bool IN_LDS, bool LAST, bool KEEP = false>
 __global__ __launch_bounds__(kWave) void surf_pass_fh_kernel(SurfPassArgs a, float w2) {
     extern __shared__ float lds[];
     constexpr int pass = LAST ? 2 : 1;
@@ -204,6 +214,7 @@ __global__ __launch_bounds__(kWave) void surf_pass_fh_kernel(SurfPassArgs a, flo
         const int64_t stride = LAST ? (int64_t)q.ny * q.nx : q.nx;
         const int64_t base = q.vox + (LAST ? (int64_t)o * q.nx : (int64_t)o * q.ny * q.nx) + xx;
         double acc[4] = {0.0, 0.0, 0.0, 0.0};  // |A|, |B|, sum over A of d(., B), sum over B of d(., A)
+        uint32_t mx[2] = {0u, 0u};             // KEEP: max over A of d2(., B), max over B of d2(., A), as float bits
         for (int fn = 0; fn < 2 && act; ++fn) {  // fn 0: distances to A, fn 1: distances to B
             float* g = (fn == 0 ? a.gA : a.gB) + base;
             const int k = lower_envelope(g, stride, n, w2, ez, ef, ev, ls);
@@ -218,10 +229,12 @@ __global__ __launch_bounds__(kWave) void surf_pass_fh_kernel(SurfPassArgs a, flo
                 if (!LAST) {
                     g[i * stride] = d;
                 } else {
+                    if (KEEP) g[i * stride] = d;
                     const int mm = a.memb[base + i * stride];
                     if (mm & (fn == 0 ? 2 : 1)) {
                         acc[1 - fn] += 1.0;
                         acc[3 - fn] += sqrt((double)d);
+                        if (KEEP) mx[1 - fn] = max(mx[1 - fn], __float_as_uint(d));  // d >= 0: the bits order as the floats
                     }
                 }
             }
@@ -232,6 +245,14 @@ __global__ __launch_bounds__(kWave) void surf_pass_fh_kernel(SurfPassArgs a, flo
             if (lane == 0)
 #pragma unroll
                 for (int v = 0; v < 4; ++v) a.partials[t * 4 + v] = acc[v];
+            if (KEEP) {
+                mx[0] = wave_max(mx[0]);
+                mx[1] = wave_max(mx[1]);
+                if (lane == 0) {
+                    a.maxpart[t * 2] = mx[0];
+                    a.maxpart[t * 2 + 1] = mx[1];
+                }
+            }
         }
     }
 }
@@ -281,10 +302,12 @@ void launch_surface_distance(const int16_t* fixed, int64_t f_stride, const int16
             const dim3 grid(grid_for(a.tasks[pass], 1, 65536));
             const size_t lds = (size_t)3 * a.line[pass] * kWave * sizeof(float);
             if (pass == 1) hipLaunchKernelGGL((surf_pass_fh_kernel<true, false>), grid, dim3(kWave), lds, st, a, w2);
+            else if (a.maxpart) hipLaunchKernelGGL((surf_pass_fh_kernel<true, true, true>), grid, dim3(kWave), lds, st, a, w2);
             else hipLaunchKernelGGL((surf_pass_fh_kernel<true, true>), grid, dim3(kWave), lds, st, a, w2);
         } else {
             const dim3 grid(a.env_slots[pass]);
             if (pass == 1) hipLaunchKernelGGL((surf_pass_fh_kernel<false, false>), grid, dim3(kWave), 0, st, a, w2);
+            else if (a.maxpart) hipLaunchKernelGGL((surf_pass_fh_kernel<false, true, true>), grid, dim3(kWave), 0, st, a, w2);
             else hipLaunchKernelGGL((surf_pass_fh_kernel<false, true>), grid, dim3(kWave), 0, st, a, w2);
         }
     }

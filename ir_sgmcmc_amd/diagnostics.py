@@ -28,6 +28,9 @@ The displacement quantiles (DisplacementQuantiles) are what no moment gives: per
 displacement around the first record (ops.displacement_quantiles_update), 12 + 6 * bins bytes per voxel whatever the number of
 records, and at the end the quantiles of given probabilities, the width of the credible band between the first and the last
 and its summary over a mask (ops.displacement_quantiles_finalize).
+
+The Hausdorff option (hausdorff_options) is of another kind: it keeps no state.  It adds the Hausdorff and percentile surface
+distances of the propagated segmentation to the point-estimate metrics wherever the ASD is logged.
 """
 import math
 import numbers
@@ -794,3 +797,39 @@ class DisplacementQuantiles:
         self.centre.copy_(sd['centre'])
         self.hist.view(torch.int16).copy_(sd['hist'].view(torch.int16))
         self.records = records
+
+
+HAUSDORFF_MAX_PERCENTILES = 4  # IRS_HAUSDORFF_MAX_PERCENTILES
+
+
+def hausdorff_options(cfg_trainer):
+    """`trainer.hausdorff` -> None when off, else {'percentiles': (q, ...)}.
+    Absent / false / null: off.  true: the percentiles (95,).  {"percentiles": [95, 99]}: those.  Refuses unknown keys and
+    percentiles that are not 0 to 4 strictly increasing finite numbers in (0, 100]."""
+    what = 'trainer.hausdorff'
+    opt = cfg_trainer.get('hausdorff', False)
+    if opt is None or opt is False:
+        return None
+    pct = (95.0,)
+    if isinstance(opt, dict):
+        unknown = set(opt) - {'percentiles'}
+        if unknown:
+            raise ValueError(f"{what}: unknown keys {sorted(unknown)}; known: ['percentiles']")
+        if 'percentiles' in opt:
+            pct = opt['percentiles']
+            if not isinstance(pct, (list, tuple)) or len(pct) > HAUSDORFF_MAX_PERCENTILES:
+                raise ValueError(f'{what}.percentiles must be a list of 0 to {HAUSDORFF_MAX_PERCENTILES} numbers, got {pct!r}')
+            for q in pct:
+                if not _number(q) or not math.isfinite(q) or not 0 < q <= 100:
+                    raise ValueError(f'{what}.percentiles must lie in (0, 100], got {q!r}')
+            if any(b <= a for a, b in zip(pct, pct[1:])):
+                raise ValueError(f'{what}.percentiles must increase strictly, got {pct!r}')
+            pct = tuple(float(q) for q in pct)
+    elif opt is not True:
+        raise ValueError(f'{what} must be true, false or {{"percentiles": [...]}}, got {opt!r}')
+    return {'percentiles': pct}
+
+
+def hausdorff_metric_names(options):
+    """the metric names next to 'ASD' that the option adds: 'HD', then 'HD95' and the like"""
+    return ['HD'] + [f'HD{q:g}' for q in options['percentiles']]

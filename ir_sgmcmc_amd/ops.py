@@ -261,6 +261,52 @@ def label_surface_distance(seg_fixed, seg_moving, labels, spacing):
     return torch.where(empty, torch.full_like(asd, math.inf), asd).view(Cn, n)
 
 
+def label_hausdorff_distance(seg_fixed, seg_moving, labels, spacing, percentiles=(95,)):
+    """Hausdorff and percentile surface distances per chain and label, next to the ASD of label_surface_distance, from the same
+    contours and the same exact distance transform (absent in the reference; sitk's GetHausdorffDistance is the maximum).
+    Arguments as label_surface_distance; percentiles: 0 to 4 strictly increasing values in (0, 100].  The directed percentile q
+    of the n distances of one contour to the other is their ascending order statistic of 0-based index
+    min(max(ceil(q * n / 100) - 1, 0), n - 1) (numpy's method='inverted_cdf'), selected exactly on the device.
+    -> dict of float64 device tensors: 'asd' (C, L), bit-identical to label_surface_distance; 'hd' (C, L) and 'hd_directed'
+    (C, L, 2) ([..., 0]: max over the fixed contour of the distance to the moving one, [..., 1]: the reverse); 'hd_pct'
+    (Q, C, L) and 'hd_pct_directed' (Q, C, L, 2).  The symmetric values are the larger of the two directions; everything is
+    inf where a contour is empty.  One device-to-host read: the boxes that size the workspace."""
+    lib = L.load()
+    Cn, D, H, W = _dims5(seg_moving, 1)
+    if seg_fixed.dim() != 5 or seg_fixed.shape[1] != 1 or seg_fixed.shape[0] not in (1, Cn) or tuple(seg_fixed.shape[2:]) != (D, H, W):
+        raise L.IrsError(f'fixed segmentation {tuple(seg_fixed.shape)} does not match the moving one {tuple(seg_moving.shape)}')
+    f, m = L.dev_ptr(seg_fixed, torch.int16), L.dev_ptr(seg_moving, torch.int16)
+    labels = [int(x) for x in labels]
+    sp = [float(x) for x in (spacing.tolist() if hasattr(spacing, 'tolist') else spacing)]
+    if len(sp) != 3:
+        raise L.IrsError(f'spacing must have 3 entries, got {len(sp)}')
+    pct = [float(x) for x in percentiles]
+    Q = len(pct)
+    n = len(labels)
+    lab = (C.c_int32 * max(n, 1))(*labels)
+    P = Cn * n
+    dev = seg_moving.device
+    boxes = torch.empty((max(P, 1), 6), device=dev, dtype=torch.int32)
+    L.check(lib.irs_label_boxes(f, seg_fixed.shape[0], m, lab, n, L.dev_ptr(boxes), Cn, D, H, W, L.stream_ptr()))
+    boxes_h = boxes.cpu()
+    bp = C.cast(C.c_void_p(boxes_h.data_ptr()), C.POINTER(C.c_int32))
+    nbytes = C.c_size_t()
+    L.check(lib.irs_hausdorff_workspace(bp, P, Q, D, H, W, C.byref(nbytes)))
+    ws = torch.empty(nbytes.value, device=dev, dtype=torch.uint8)
+    counts = torch.empty((P, 2), device=dev, dtype=torch.int64)
+    sums = torch.empty((P, 2), device=dev, dtype=torch.float64)
+    hd = torch.empty((P, 2), device=dev, dtype=torch.float64)
+    hd_pct = torch.empty((Q, P, 2), device=dev, dtype=torch.float64)
+    L.check(lib.irs_label_hausdorff_distance(f, seg_fixed.shape[0], m, lab, n, (C.c_float * 3)(*sp), bp, L.dev_ptr(ws), nbytes.value,
+                                             (C.c_double * max(Q, 1))(*pct), Q, L.dev_ptr(counts), L.dev_ptr(sums), L.dev_ptr(hd),
+                                             L.dev_ptr(hd_pct) if Q else None, Cn, D, H, W, L.stream_ptr()))
+    empty = (counts == 0).any(dim=1)
+    asd = 0.5 * (sums[:, 0] / counts[:, 0].clamp(min=1) + sums[:, 1] / counts[:, 1].clamp(min=1))
+    return {'asd': torch.where(empty, torch.full_like(asd, math.inf), asd).view(Cn, n),
+            'hd': hd.max(dim=1).values.view(Cn, n), 'hd_directed': hd.view(Cn, n, 2),
+            'hd_pct': hd_pct.max(dim=2).values.view(Q, Cn, n), 'hd_pct_directed': hd_pct.view(Q, Cn, n, 2)}
+
+
 def chain_moments_update(x, mean, m2, half, k):
     """Welford update of half `half` of every chain's split-R-hat moments with the sample x (absent in the reference).
     x (C,3,D,H,W) float32; mean / m2 (2,C,3,D,H,W) float32, updated in place; k = samples in that half after this one."""

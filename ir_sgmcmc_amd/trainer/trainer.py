@@ -19,12 +19,12 @@ import torch
 from ..base import BaseTrainer
 from ..diagnostics import (COVARIANCE_METRICS, ChainMoments, DisplacementCovariance, DisplacementQuantiles, JACOBIAN_METRICS,
                            JacobianPosterior, LABEL_STRUCTURE_METRICS, LabelPosterior, QUANTILE_METRICS, diagnostics_period,
-                           displacement_covariance_options, displacement_quantiles_options, ess_options, is_recorded,
-                           jacobian_posterior_options, label_posterior_options)
+                           displacement_covariance_options, displacement_quantiles_options, ess_options, hausdorff_options,
+                           is_recorded, jacobian_posterior_options, label_posterior_options)
 from ..engine import EngineConfig, TransitionEngine
 from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_quantiles, save_ess,
                       save_jacobian_posterior, save_label_posterior, save_rhat, save_sample)
-from ..utils import calc_norm, calc_no_non_diffeomorphic_voxels, calc_metrics, sample_q_v
+from ..utils import calc_norm, calc_no_non_diffeomorphic_voxels, sample_q_v
 from .vi import VIMixin
 
 
@@ -86,6 +86,8 @@ class Trainer(VIMixin, BaseTrainer):
         self.quantiles_options = displacement_quantiles_options(cfg_trainer)
         self._displacement_quantiles = None
         self.displacement_quantiles, self.displacement_ci_width, self.displacement_quantiles_summary = None, None, None
+        # Hausdorff and percentile surface distances next to every logged ASD: None when trainer.hausdorff is off
+        self.hausdorff_options = hausdorff_options(cfg_trainer)
 
     # ---------------------------------------------------------------- engine plumbing
     def _engine_config(self):
@@ -410,11 +412,8 @@ class Trainer(VIMixin, BaseTrainer):
                 no_folds, log_det_J = calc_no_non_diffeomorphic_voxels(transformation, self.diff_op)
                 if 'seg' in moving and 'seg' in fixed and self.structures_dict:
                     seg_warped = self.registration_module(moving['seg'], transformation)
-                    ASD, DSC = calc_metrics(fixed['seg'], seg_warped, self.structures_dict, spacing, no_samples=self.no_chains)
-                    for idx in range(self.no_chains):
-                        for j, name in enumerate(self.structures_dict):
-                            self.metrics.update(f'MCMC/chain_{idx}/ASD/{name}', float(ASD[idx][j]))
-                            self.metrics.update(f'MCMC/chain_{idx}/DSC/{name}', float(DSC[idx][j]))
+                    self._log_segmentation_metrics([f'MCMC/chain_{idx}' for idx in range(self.no_chains)], fixed['seg'], seg_warped,
+                                                   spacing)
                 no_voxels = int(np.prod(displacement.shape[2:]))
                 if save_samples:
                     for idx in range(self.no_chains):

@@ -12,10 +12,11 @@ import time
 
 import torch
 
+from ..diagnostics import hausdorff_metric_names
 from ..logger import (save_displacement_mean_and_std_dev, save_field, save_fixed_im, save_fixed_mask, save_im, save_moving_im,
                       save_moving_mask, save_sample)
-from ..utils import (SobolevGrad, add_noise_uniform_field, calc_metrics, calc_no_non_diffeomorphic_voxels, calc_posterior_statistics,
-                     calc_VD_factor, max_field_update, rescale_residuals, sample_q_v)
+from ..utils import (SobolevGrad, add_noise_uniform_field, calc_DSC_GPU, calc_metrics, calc_no_non_diffeomorphic_voxels,
+                     calc_posterior_statistics, calc_surface_metrics, calc_VD_factor, max_field_update, rescale_residuals, sample_q_v)
 from ..utils.functions import Sobolev_kernel_1D
 
 
@@ -204,10 +205,7 @@ class VIMixin:
                     self.metrics.update(f'VI/train/max_updates/{key}', max_field_update(prev[key], var_params_q_v[key])[0].item())
                 if (iter_no % self.log_period_VI == 0 or iter_no == self.no_iters_VI) and 'seg' in moving and self.structures_dict:
                     seg_warped = self.registration_module(moving['seg'], output['transformation'].detach())
-                    ASD, DSC = calc_metrics(fixed['seg'], seg_warped, self.structures_dict, spacing)
-                    for j, structure in enumerate(self.structures_dict):
-                        self.metrics.update(f'VI/train/ASD/{structure}', float(ASD[0][j]))
-                        self.metrics.update(f'VI/train/DSC/{structure}', float(DSC[0][j]))
+                    self._log_segmentation_metrics(('VI/train',), fixed['seg'], seg_warped, spacing)
 
     @torch.no_grad()
     def _test_VI(self, fixed, moving, var_params_q_v):
@@ -225,10 +223,7 @@ class VIMixin:
             self.metrics.update('VI/test/no_non_diffeomorphic_voxels', int(no_folds.sum()))
             warped = self.registration_module(moving['im'], transformation)
             if 'seg' in moving and self.structures_dict:
-                ASD, DSC = calc_metrics(fixed['seg'], self.registration_module(moving['seg'], transformation), self.structures_dict, spacing)
-                for j, structure in enumerate(self.structures_dict):
-                    self.metrics.update(f'VI/test/ASD/{structure}', float(ASD[0][j]))
-                    self.metrics.update(f'VI/test/DSC/{structure}', float(DSC[0][j]))
+                self._log_segmentation_metrics(('VI/test',), fixed['seg'], self.registration_module(moving['seg'], transformation), spacing)
             if save:
                 save_sample(self.config.save_dirs, spacing, n, warped, displacement, log_det_J, 'VI')
         transformation, displacement = self.transformation_module(self._smooth(var_params_q_v['mu']))
@@ -260,10 +255,28 @@ class VIMixin:
         if 'seg' not in fixed or 'seg' not in moving or not self.structures_dict:
             return
         self.writer.set_step(0)
-        ASD, DSC = calc_metrics(fixed['seg'], moving['seg'], self.structures_dict, self._spacing())
-        for j, structure in enumerate(self.structures_dict):
-            self.metrics.update(f'VI/train/ASD/{structure}', float(ASD[0][j]))
-            self.metrics.update(f'VI/train/DSC/{structure}', float(DSC[0][j]))
+        self._log_segmentation_metrics(('VI/train',), fixed['seg'], moving['seg'], self._spacing())
+
+    def _log_segmentation_metrics(self, prefixes, seg_fixed, seg_moving, spacing):
+        """ASD and Dice of the first len(prefixes) maps of seg_moving under `{prefix}/ASD/{structure}` and `.../DSC/...`.  With
+        trainer.hausdorff on, `{prefix}/HD/{structure}` and `{prefix}/HD{q:g}/{structure}` as well, and the ASD comes from the
+        same device call (calc_surface_metrics) instead of calc_metrics'; Dice is computed as before."""
+        n = len(prefixes)
+        if self.hausdorff_options is None:
+            ASD, DSC = calc_metrics(seg_fixed, seg_moving, self.structures_dict, spacing, no_samples=n)
+            surface = {'ASD': ASD}
+        else:
+            sm = calc_surface_metrics(seg_fixed, seg_moving, self.structures_dict, spacing, self.hausdorff_options['percentiles'],
+                                      no_samples=n)
+            surface = dict(zip(['ASD'] + hausdorff_metric_names(self.hausdorff_options), [sm['ASD'], sm['HD'], *sm['HDp']]))
+            seg_moving = seg_moving[:n]
+            DSC = calc_DSC_GPU(n, seg_fixed.expand_as(seg_moving) if seg_fixed.shape[0] == 1 else seg_fixed, seg_moving,
+                               self.structures_dict)
+        for idx, prefix in enumerate(prefixes):
+            for j, structure in enumerate(self.structures_dict):
+                for key, values in surface.items():
+                    self.metrics.update(f'{prefix}/{key}/{structure}', float(values[idx][j]))
+                self.metrics.update(f'{prefix}/DSC/{structure}', float(DSC[idx][j]))
 
     def _spacing(self):
         sp = getattr(self.data_loader, 'im_spacing', None)

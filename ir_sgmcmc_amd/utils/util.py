@@ -241,6 +241,18 @@ def calc_metrics(seg_fixed, seg_moving, structures_dict, spacing, GPU=True, no_s
     return ASD, DSC
 
 
+@torch.no_grad()
+def calc_surface_metrics(seg_fixed, seg_moving, structures_dict, spacing, percentiles=(95,), no_samples=1):
+    """average, Hausdorff and percentile surface distances from one device call (ops.label_hausdorff_distance; the reference
+    logs the average only) -> {'ASD': [no_samples, L], 'HD': [no_samples, L], 'HDp': [Q, no_samples, L]}, numpy float64.  The ASD
+    is the one calc_metrics returns, bit for bit."""
+    seg_moving = seg_moving[:no_samples].contiguous()
+    shared = seg_fixed.shape[0] == 1 or seg_fixed.stride(0) == 0  # one volume, or .expand()-ed chains sharing it
+    seg_fixed = seg_fixed[:1].contiguous() if shared else seg_fixed[:no_samples].contiguous()
+    out = _ops.label_hausdorff_distance(seg_fixed, seg_moving, list(structures_dict.values()), spacing, percentiles)
+    return {'ASD': out['asd'].cpu().numpy(), 'HD': out['hd'].cpu().numpy(), 'HDp': out['hd_pct'].cpu().numpy()}
+
+
 def rescale_residuals(res, mask, data_loss):
     """VD-rescaled residual x = sum_k r_k (z / sigma_k)^2 (utils/util.py:330-347).  The reference obtains it as
     sum_k s_k * d(-log p)/d(s_k) with a nested backward; the closed form with the responsibilities r_k is the same number."""
