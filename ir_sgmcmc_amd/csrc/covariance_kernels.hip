@@ -8,19 +8,22 @@
 //    16-byte accesses measured no faster: DESIGN.md section 6.)
 //  - finalize: a grid-stride stream over voxels diagonalises the covariance in double (a fixed number of cyclic Jacobi
 //    sweeps, no data-dependent trip count) and writes the seven planes; the summary over the mask stays in registers and is
-//    reduced lane by lane, wavefront by wavefront and, in a second one-block launch, block by block.  The grids depend on the
-//    volume only, so two identical call sequences are bit-identical.
-#include <algorithm>
-
+//    reduced by summary_device.h.
 #include "covariance_device.h"
 #include "kernels.h"
+#include "summary_device.h"
 
 namespace irs {
 namespace {
 
-constexpr int kCovInts = IRS_COVARIANCE_SUMMARY_INTS, kCovFloats = IRS_COVARIANCE_SUMMARY_FLOATS;
-constexpr int kCovMaxBlocks = IRS_COVARIANCE_WS_BYTES / (kCovInts + kCovFloats) / 8;
-constexpr int kCovG = kBlock / kWave;
+// the summary columns: integer sums {voxels, voxels with a non-finite state}; then doubles over the stored float32 maps of
+// the finite voxels {sum std[0], max std[0], sum sqrt(std0^2 + std1^2 + std2^2), sum anisotropy, max anisotropy,
+// sum |direction_x|, |direction_y|, |direction_z|}.  The maxima never see a NaN.
+struct CovarianceSummary {
+    static constexpr int kInts = IRS_COVARIANCE_SUMMARY_INTS, kFloats = IRS_COVARIANCE_SUMMARY_FLOATS;
+    static constexpr Col kind(int j) { return j == 1 || j == 4 ? Col::Max : Col::Sum; }
+};
+using CovAcc = SummaryAcc<CovarianceSummary>;
 
 // x (C,3,V) float32; mean (3,V), comoment (6,V) float32.  One voxel per thread.
 __global__ __launch_bounds__(kBlock) void covariance_update_kernel(const float* __restrict__ x, int C, float* __restrict__ mean,
@@ -44,53 +47,6 @@ __global__ __launch_bounds__(kBlock) void covariance_update_kernel(const float* 
     for (int a = 0; a < 6; ++a) comoment[a * vol.V + p] = M[a];
 }
 
-__device__ __forceinline__ double cov_wave_max(double v) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, kWave));
-    return v;
-}
-__device__ __forceinline__ long long cov_wave_sum_ll(long long v) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    return v;
-}
-
-// column j of the summary: integer sums {voxels, voxels with a non-finite state}; then doubles over the stored float32 maps
-// of the finite voxels {sum std[0], max std[0], sum sqrt(std0^2 + std1^2 + std2^2), sum anisotropy, max anisotropy,
-// sum |direction_x|, |direction_y|, |direction_z|}.  The maxima start at -inf and never see a NaN.
-struct CovAcc {
-    long long i[kCovInts];
-    double f[kCovFloats];
-};
-__device__ __forceinline__ bool cov_is_max(int j) { return j == 1 || j == 4; }
-__device__ __forceinline__ CovAcc cov_identity() { return CovAcc{{0, 0}, {0.0, -INFINITY, 0.0, 0.0, -INFINITY, 0.0, 0.0, 0.0}}; }
-__device__ __forceinline__ void cov_merge(CovAcc& a, const CovAcc& b) {
-#pragma unroll
-    for (int j = 0; j < kCovInts; ++j) a.i[j] += b.i[j];
-#pragma unroll
-    for (int j = 0; j < kCovFloats; ++j) a.f[j] = cov_is_max(j) ? fmax(a.f[j], b.f[j]) : a.f[j] + b.f[j];
-}
-
-// thread 0 ends with the block's accumulator: lanes by the shuffle butterfly, then the wavefronts in order
-__device__ __forceinline__ void cov_block_reduce(CovAcc& a, CovAcc* smem) {
-#pragma unroll
-    for (int j = 0; j < kCovInts; ++j) a.i[j] = cov_wave_sum_ll(a.i[j]);
-#pragma unroll
-    for (int j = 0; j < kCovFloats; ++j) a.f[j] = cov_is_max(j) ? cov_wave_max(a.f[j]) : wave_sum(a.f[j]);
-    const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-    if (lane == 0) smem[wid] = a;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < kCovG; ++w) cov_merge(a, smem[w]);
-}
-
-__device__ __forceinline__ void cov_store(const CovAcc& a, long long* ip, double* fp) {
-#pragma unroll
-    for (int j = 0; j < kCovInts; ++j) ip[j] = a.i[j];
-#pragma unroll
-    for (int j = 0; j < kCovFloats; ++j) fp[j] = a.f[j];
-}
-
 struct CovScale {
     double s[3];
 };
@@ -102,8 +58,8 @@ __global__ __launch_bounds__(kBlock) void covariance_finalize_kernel(const float
                                                                      float* __restrict__ stdev, float* __restrict__ direction,
                                                                      float* __restrict__ anisotropy, long long* __restrict__ ipart,
                                                                      double* __restrict__ fpart) {
-    __shared__ CovAcc smem[kCovG];
-    CovAcc a = cov_identity();
+    __shared__ CovAcc smem[CovAcc::kG];
+    CovAcc a = CovAcc::identity();
     const double inv = 1.0 / (double)(n > 1 ? n - 1 : 1);
     const double sc[3] = {scale.s[0], scale.s[1], scale.s[2]};
     for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < V; v += (int64_t)gridDim.x * kBlock) {
@@ -136,32 +92,11 @@ __global__ __launch_bounds__(kBlock) void covariance_finalize_kernel(const float
             }
         }
     }
-    cov_block_reduce(a, smem);
-    if (threadIdx.x == 0) cov_store(a, ipart + (int64_t)blockIdx.x * kCovInts, fpart + (int64_t)blockIdx.x * kCovFloats);
-}
-
-// one block: thread i takes blocks i, i + 256, ... in order, then the block reduction above
-__global__ __launch_bounds__(kBlock) void covariance_summary_reduce_kernel(const long long* __restrict__ ipart,
-                                                                           const double* __restrict__ fpart, int nblocks,
-                                                                           long long* __restrict__ isummary,
-                                                                           double* __restrict__ fsummary) {
-    __shared__ CovAcc smem[kCovG];
-    CovAcc a = cov_identity();
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
-        CovAcc o;
-#pragma unroll
-        for (int j = 0; j < kCovInts; ++j) o.i[j] = ipart[(int64_t)b * kCovInts + j];
-#pragma unroll
-        for (int j = 0; j < kCovFloats; ++j) o.f[j] = fpart[(int64_t)b * kCovFloats + j];
-        cov_merge(a, o);
-    }
-    cov_block_reduce(a, smem);
-    if (threadIdx.x == 0) cov_store(a, isummary, fsummary);
+    a.block_reduce(smem);
+    if (threadIdx.x == 0) a.store(ipart, fpart, blockIdx.x);
 }
 
 }  // namespace
-
-int covariance_finalize_blocks(int64_t V) { return (int)std::min<int64_t>((V + kBlock - 1) / kBlock, kCovMaxBlocks); }
 
 void launch_covariance_update(const float* x, int C, float* mean, float* comoment, int records_before, Vol vol, hipStream_t st) {
     hipLaunchKernelGGL(covariance_update_kernel, vox_grid(vol, 1), dim3(kBlock), 0, st, x, C, mean, comoment, records_before, vol);
@@ -170,13 +105,11 @@ void launch_covariance_update(const float* x, int C, float* mean, float* comomen
 void launch_covariance_finalize(const float* mean, const float* comoment, int64_t V, int n, const float* scale, const uint8_t* mask,
                                 float* stdev, float* direction, float* anisotropy, long long* isummary, double* fsummary, void* ws,
                                 hipStream_t st) {
-    const int blocks = covariance_finalize_blocks(V);
-    long long* ipart = (long long*)ws;
-    double* fpart = (double*)(ipart + (size_t)kCovInts * blocks);
+    const SummaryPartials<CovarianceSummary> part(V, ws, IRS_COVARIANCE_WS_BYTES);
     const CovScale sc{{(double)scale[0], (double)scale[1], (double)scale[2]}};
-    hipLaunchKernelGGL(covariance_finalize_kernel, dim3(blocks), dim3(kBlock), 0, st, mean, comoment, V, n, sc, mask, stdev, direction,
-                       anisotropy, ipart, fpart);
-    hipLaunchKernelGGL(covariance_summary_reduce_kernel, dim3(1), dim3(kBlock), 0, st, ipart, fpart, blocks, isummary, fsummary);
+    hipLaunchKernelGGL(covariance_finalize_kernel, dim3(part.blocks), dim3(kBlock), 0, st, mean, comoment, V, n, sc, mask, stdev,
+                       direction, anisotropy, part.ipart, part.fpart);
+    part.reduce(isummary, fsummary, st);
 }
 
 }  // namespace irs

@@ -5,20 +5,22 @@
 //    kernels.  The thread loads its folds / mean / m2 once, folds every chain's det (jacobian_device.h: the arithmetic of the
 //    per-sample fold count) into them in chain order, and stores once.  Each thread owns its voxel: plain read-modify-writes.
 //  - finalize: a grid-stride stream over voxels writes the three maps; the summary over the mask stays in registers (exact
-//    integer counts, double sums of the stored float32 values, min / max) and is reduced lane by lane, wavefront by wavefront
-//    and, in a second one-block launch, block by block.  The grids depend on the volume only, so two identical call sequences
-//    are bit-identical.
-#include <algorithm>
-
+//    integer counts, double sums of the stored float32 values, min / max) and is reduced by summary_device.h.
 #include "jacobian_device.h"
 #include "kernels.h"
+#include "summary_device.h"
 
 namespace irs {
 namespace {
 
-constexpr int kJacMaxBlocks = IRS_JACOBIAN_WS_BYTES / (IRS_JACOBIAN_SUMMARY_INTS + IRS_JACOBIAN_SUMMARY_FLOATS) / 8;
-constexpr int kJacInts = IRS_JACOBIAN_SUMMARY_INTS, kJacFloats = IRS_JACOBIAN_SUMMARY_FLOATS;
-constexpr int kJacG = kBlock / kWave;
+// the summary columns: integer sums {voxels, folded voxels, always folded, fold records}; then doubles {max fold_prob,
+// min logJ_mean, max logJ_mean, sum logJ_std, max logJ_std}.  fmin / fmax never see a NaN here: voxels without a valid
+// record are left out of float columns 1 .. 4.
+struct JacobianSummary {
+    static constexpr int kInts = IRS_JACOBIAN_SUMMARY_INTS, kFloats = IRS_JACOBIAN_SUMMARY_FLOATS;
+    static constexpr Col kind(int j) { return j == 1 ? Col::Min : j == 3 ? Col::Sum : Col::Max; }
+};
+using JacAcc = SummaryAcc<JacobianSummary>;
 
 // t (C,3,V) float32; folds (V) int32, mean / m2 (V) float32.  A record is folded when !(det > 0): det <= 0 or NaN.
 __global__ __launch_bounds__(kBlock) void jacobian_update_kernel(const float* __restrict__ t, int C, int32_t* __restrict__ folds,
@@ -52,74 +54,15 @@ __global__ __launch_bounds__(kBlock) void jacobian_update_kernel(const float* __
     m2[p] = s;
 }
 
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, kWave));
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, kWave));
-    return v;
-}
-__device__ __forceinline__ long long wave_sum_ll(long long v) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    return v;
-}
-
-// column j of the summary: 0 .. 3 integer sums {voxels, folded voxels, always folded, fold records}; then doubles
-// {max fold_prob, min logJ_mean, max logJ_mean, sum logJ_std, max logJ_std}.  Identities: 0, +inf for the min, -inf for the
-// maxima (fmin / fmax never see a NaN here: voxels without a valid record are left out of columns 5 .. 8).
-struct JacAcc {
-    long long i[kJacInts];
-    double f[kJacFloats];
-};
-__device__ __forceinline__ JacAcc jac_identity() {
-    return JacAcc{{0, 0, 0, 0}, {-INFINITY, INFINITY, -INFINITY, 0.0, -INFINITY}};
-}
-__device__ __forceinline__ void jac_merge(JacAcc& a, const JacAcc& b) {
-#pragma unroll
-    for (int j = 0; j < kJacInts; ++j) a.i[j] += b.i[j];
-    a.f[0] = fmax(a.f[0], b.f[0]);
-    a.f[1] = fmin(a.f[1], b.f[1]);
-    a.f[2] = fmax(a.f[2], b.f[2]);
-    a.f[3] += b.f[3];
-    a.f[4] = fmax(a.f[4], b.f[4]);
-}
-
-// thread 0 ends with the block's accumulator: lanes by the shuffle butterfly, then the wavefronts in order
-__device__ __forceinline__ void jac_block_reduce(JacAcc& a, JacAcc* smem) {
-#pragma unroll
-    for (int j = 0; j < kJacInts; ++j) a.i[j] = wave_sum_ll(a.i[j]);
-    a.f[0] = wave_max(a.f[0]);
-    a.f[1] = wave_min(a.f[1]);
-    a.f[2] = wave_max(a.f[2]);
-    a.f[3] = wave_sum(a.f[3]);
-    a.f[4] = wave_max(a.f[4]);
-    const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-    if (lane == 0) smem[wid] = a;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < kJacG; ++w) jac_merge(a, smem[w]);
-}
-
-__device__ __forceinline__ void jac_store(const JacAcc& a, long long* ip, double* fp) {
-#pragma unroll
-    for (int j = 0; j < kJacInts; ++j) ip[j] = a.i[j];
-#pragma unroll
-    for (int j = 0; j < kJacFloats; ++j) fp[j] = a.f[j];
-}
-
 // folds (V) int32, mean / m2 (V) float32 after n records -> fold_prob, logJ_mean, logJ_std (V) float32 and, per block, the
-// summary columns over the mask: ipart kJacInts int64, fpart kJacFloats doubles
+// summary columns over the mask: one row of partials
 __global__ __launch_bounds__(kBlock) void jacobian_finalize_kernel(const int32_t* __restrict__ folds, const float* __restrict__ mean,
                                                                    const float* __restrict__ m2, int64_t V, int n,
                                                                    const uint8_t* __restrict__ mask, float* __restrict__ fold_prob,
                                                                    float* __restrict__ logj_mean, float* __restrict__ logj_std,
                                                                    long long* __restrict__ ipart, double* __restrict__ fpart) {
-    __shared__ JacAcc smem[kJacG];
-    JacAcc a = jac_identity();
+    __shared__ JacAcc smem[JacAcc::kG];
+    JacAcc a = JacAcc::identity();
     const double inv_n = 1.0 / (double)n;
     const float nan = __builtin_nanf("");
     for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < V; v += (int64_t)gridDim.x * kBlock) {
@@ -145,32 +88,11 @@ __global__ __launch_bounds__(kBlock) void jacobian_finalize_kernel(const int32_t
             }
         }
     }
-    jac_block_reduce(a, smem);
-    if (threadIdx.x == 0) jac_store(a, ipart + (int64_t)blockIdx.x * kJacInts, fpart + (int64_t)blockIdx.x * kJacFloats);
-}
-
-// one block: thread i takes blocks i, i + 256, ... in order, then the block reduction above
-__global__ __launch_bounds__(kBlock) void jacobian_summary_reduce_kernel(const long long* __restrict__ ipart,
-                                                                         const double* __restrict__ fpart, int nblocks,
-                                                                         long long* __restrict__ isummary,
-                                                                         double* __restrict__ fsummary) {
-    __shared__ JacAcc smem[kJacG];
-    JacAcc a = jac_identity();
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
-        JacAcc o;
-#pragma unroll
-        for (int j = 0; j < kJacInts; ++j) o.i[j] = ipart[(int64_t)b * kJacInts + j];
-#pragma unroll
-        for (int j = 0; j < kJacFloats; ++j) o.f[j] = fpart[(int64_t)b * kJacFloats + j];
-        jac_merge(a, o);
-    }
-    jac_block_reduce(a, smem);
-    if (threadIdx.x == 0) jac_store(a, isummary, fsummary);
+    a.block_reduce(smem);
+    if (threadIdx.x == 0) a.store(ipart, fpart, blockIdx.x);
 }
 
 }  // namespace
-
-int jacobian_finalize_blocks(int64_t V) { return (int)std::min<int64_t>((V + kBlock - 1) / kBlock, kJacMaxBlocks); }
 
 void launch_jacobian_update(const float* t, int C, int32_t* folds, float* mean, float* m2, int records_before, Vol vol,
                             hipStream_t st) {
@@ -180,12 +102,10 @@ void launch_jacobian_update(const float* t, int C, int32_t* folds, float* mean, 
 void launch_jacobian_finalize(const int32_t* folds, const float* mean, const float* m2, int64_t V, int n, const uint8_t* mask,
                               float* fold_prob, float* logj_mean, float* logj_std, long long* isummary, double* fsummary,
                               void* ws, hipStream_t st) {
-    const int blocks = jacobian_finalize_blocks(V);
-    long long* ipart = (long long*)ws;
-    double* fpart = (double*)(ipart + (size_t)kJacInts * blocks);
-    hipLaunchKernelGGL(jacobian_finalize_kernel, dim3(blocks), dim3(kBlock), 0, st, folds, mean, m2, V, n, mask, fold_prob,
-                       logj_mean, logj_std, ipart, fpart);
-    hipLaunchKernelGGL(jacobian_summary_reduce_kernel, dim3(1), dim3(kBlock), 0, st, ipart, fpart, blocks, isummary, fsummary);
+    const SummaryPartials<JacobianSummary> part(V, ws, IRS_JACOBIAN_WS_BYTES);
+    hipLaunchKernelGGL(jacobian_finalize_kernel, dim3(part.blocks), dim3(kBlock), 0, st, folds, mean, m2, V, n, mask, fold_prob,
+                       logj_mean, logj_std, part.ipart, part.fpart);
+    part.reduce(isummary, fsummary, st);
 }
 
 }  // namespace irs

@@ -207,8 +207,7 @@ void launch_label_finalize(const int32_t* counts, int K, int64_t V, int n, const
 void launch_jacobian_update(const float* t, int C, int32_t* folds, float* mean, float* m2, int records_before, Vol vol,
                             hipStream_t st);
 // fold_prob / logj_mean / logj_std (V) float32; isummary IRS_JACOBIAN_SUMMARY_INTS int64, fsummary IRS_JACOBIAN_SUMMARY_FLOATS
-// doubles; ws: IRS_JACOBIAN_WS_BYTES (the per-block partials of jacobian_finalize_blocks(V) blocks)
-int jacobian_finalize_blocks(int64_t V);
+// doubles; ws: IRS_JACOBIAN_WS_BYTES (the per-block partials of at most 1024 blocks: summary_device.h)
 void launch_jacobian_finalize(const int32_t* folds, const float* mean, const float* m2, int64_t V, int n, const uint8_t* mask,
                               float* fold_prob, float* logj_mean, float* logj_std, long long* isummary, double* fsummary,
                               void* ws, hipStream_t st);
@@ -218,8 +217,7 @@ void launch_jacobian_finalize(const int32_t* folds, const float* mean, const flo
 // after `records_before` records
 void launch_covariance_update(const float* x, int C, float* mean, float* comoment, int records_before, Vol vol, hipStream_t st);
 // stdev / direction (3,V), anisotropy (V) float32; scale: 3 host floats; isummary IRS_COVARIANCE_SUMMARY_INTS int64, fsummary
-// IRS_COVARIANCE_SUMMARY_FLOATS doubles; ws: IRS_COVARIANCE_WS_BYTES (the partials of covariance_finalize_blocks(V) blocks)
-int covariance_finalize_blocks(int64_t V);
+// IRS_COVARIANCE_SUMMARY_FLOATS doubles; ws: IRS_COVARIANCE_WS_BYTES (the partials of at most 1024 blocks)
 void launch_covariance_finalize(const float* mean, const float* comoment, int64_t V, int n, const float* scale, const uint8_t* mask,
                                 float* stdev, float* direction, float* anisotropy, long long* isummary, double* fsummary, void* ws,
                                 hipStream_t st);

@@ -12,20 +12,23 @@
 //  - finalize: a grid-stride stream over voxels walks the B planes of each channel (coalesced reads, 16 planes loaded ahead
 //    of their use), compares the running count with the next pending integer threshold ceil(p n) (cum >= p n exactly when
 //    cum >= ceil(p n), and the thresholds are sorted), interpolates in double where a threshold is crossed, and writes the
-//    P x 3 quantile planes and the width plane; the summary over the mask stays in registers and is reduced lane by lane,
-//    wavefront by wavefront and, in a second one-block launch, block by block.  The grids depend on the volume only, so two
-//    identical call sequences are bit-identical.
-#include <algorithm>
-
+//    P x 3 quantile planes and the width plane; the summary over the mask stays in registers and is reduced by
+//    summary_device.h.
 #include "kernels.h"
 #include "quantile_device.h"
+#include "summary_device.h"
 
 namespace irs {
 namespace {
 
-constexpr int kQInts = IRS_QUANTILE_SUMMARY_INTS, kQFloats = IRS_QUANTILE_SUMMARY_FLOATS;
-constexpr int kQMaxBlocks = IRS_QUANTILE_WS_BYTES / (kQInts + kQFloats) / 8;
-constexpr int kQG = kBlock / kWave;
+// the summary columns: integer sums over the mask {voxels, voxels with an out-of-range quantile, samples in the two
+// open-ended bins}; then doubles over the stored float32 maps of the in-range masked voxels {sum ci_width, max ci_width,
+// sum of the per-channel widths x, y, z}.  The maximum never sees a NaN.
+struct QuantileSummary {
+    static constexpr int kInts = IRS_QUANTILE_SUMMARY_INTS, kFloats = IRS_QUANTILE_SUMMARY_FLOATS;
+    static constexpr Col kind(int j) { return j == 1 ? Col::Max : Col::Sum; }
+};
+using QAcc = SummaryAcc<QuantileSummary>;
 constexpr int kQMaxProbs = IRS_QUANTILE_MAX_PROBS;
 constexpr int kQBatch = 16;  // bin planes a finalize thread loads before it uses the first
 
@@ -94,53 +97,6 @@ __global__ __launch_bounds__(kBlock) void quantile_update_kernel(const float* __
     }
 }
 
-__device__ __forceinline__ double q_wave_max(double v) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, kWave));
-    return v;
-}
-__device__ __forceinline__ long long q_wave_sum_ll(long long v) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    return v;
-}
-
-// the summary columns: integer sums over the mask {voxels, voxels with an out-of-range quantile, samples in the two
-// open-ended bins}; then doubles over the stored float32 maps of the in-range masked voxels {sum ci_width, max ci_width,
-// sum of the per-channel widths x, y, z}.  The maximum starts at -inf and never sees a NaN.
-struct QAcc {
-    long long i[kQInts];
-    double f[kQFloats];
-};
-__device__ __forceinline__ bool q_is_max(int j) { return j == 1; }
-__device__ __forceinline__ QAcc q_identity() { return QAcc{{0, 0, 0}, {0.0, -INFINITY, 0.0, 0.0, 0.0}}; }
-__device__ __forceinline__ void q_merge(QAcc& a, const QAcc& b) {
-#pragma unroll
-    for (int j = 0; j < kQInts; ++j) a.i[j] += b.i[j];
-#pragma unroll
-    for (int j = 0; j < kQFloats; ++j) a.f[j] = q_is_max(j) ? fmax(a.f[j], b.f[j]) : a.f[j] + b.f[j];
-}
-
-// thread 0 ends with the block's accumulator: lanes by the shuffle butterfly, then the wavefronts in order
-__device__ __forceinline__ void q_block_reduce(QAcc& a, QAcc* smem) {
-#pragma unroll
-    for (int j = 0; j < kQInts; ++j) a.i[j] = q_wave_sum_ll(a.i[j]);
-#pragma unroll
-    for (int j = 0; j < kQFloats; ++j) a.f[j] = q_is_max(j) ? q_wave_max(a.f[j]) : wave_sum(a.f[j]);
-    const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-    if (lane == 0) smem[wid] = a;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < kQG; ++w) q_merge(a, smem[w]);
-}
-
-__device__ __forceinline__ void q_store(const QAcc& a, long long* ip, double* fp) {
-#pragma unroll
-    for (int j = 0; j < kQInts; ++j) ip[j] = a.i[j];
-#pragma unroll
-    for (int j = 0; j < kQFloats; ++j) fp[j] = a.f[j];
-}
-
 struct QParams {
     double r[kQMaxProbs];  // p n
     int kth[kQMaxProbs];   // ceil(p n): the running count reaches r exactly when it reaches this
@@ -153,8 +109,8 @@ __global__ __launch_bounds__(kBlock) void quantile_finalize_kernel(const float* 
                                                                    int64_t V, QParams prm, const uint8_t* __restrict__ mask,
                                                                    float* __restrict__ quantiles, float* __restrict__ ci_width,
                                                                    long long* __restrict__ ipart, double* __restrict__ fpart) {
-    __shared__ QAcc smem[kQG];
-    QAcc acc = q_identity();
+    __shared__ QAcc smem[QAcc::kG];
+    QAcc acc = QAcc::identity();
     const int B = prm.B, P = prm.P;
     const float nan = __builtin_nanf("");
     for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < V; v += (int64_t)gridDim.x * kBlock) {
@@ -215,35 +171,14 @@ __global__ __launch_bounds__(kBlock) void quantile_finalize_kernel(const float* 
             }
         }
     }
-    q_block_reduce(acc, smem);
-    if (threadIdx.x == 0) q_store(acc, ipart + (int64_t)blockIdx.x * kQInts, fpart + (int64_t)blockIdx.x * kQFloats);
-}
-
-// one block: thread i takes blocks i, i + 256, ... in order, then the block reduction above
-__global__ __launch_bounds__(kBlock) void quantile_summary_reduce_kernel(const long long* __restrict__ ipart,
-                                                                         const double* __restrict__ fpart, int nblocks,
-                                                                         long long* __restrict__ isummary,
-                                                                         double* __restrict__ fsummary) {
-    __shared__ QAcc smem[kQG];
-    QAcc a = q_identity();
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) {
-        QAcc o;
-#pragma unroll
-        for (int j = 0; j < kQInts; ++j) o.i[j] = ipart[(int64_t)b * kQInts + j];
-#pragma unroll
-        for (int j = 0; j < kQFloats; ++j) o.f[j] = fpart[(int64_t)b * kQFloats + j];
-        q_merge(a, o);
-    }
-    q_block_reduce(a, smem);
-    if (threadIdx.x == 0) q_store(a, isummary, fsummary);
+    acc.block_reduce(smem);
+    if (threadIdx.x == 0) acc.store(ipart, fpart, blockIdx.x);
 }
 
 template <int C>
 void launch_update(const float* x, float* centre, uint16_t* hist, int B, QInvWidth iw, int records_before, Vol vol, hipStream_t st) {
     hipLaunchKernelGGL(quantile_update_kernel<C>, vox_grid(vol, 1), dim3(kBlock), 0, st, x, centre, hist, B, iw, records_before, vol);
 }
-
-int quantile_finalize_blocks(int64_t V) { return (int)std::min<int64_t>((V + kBlock - 1) / kBlock, kQMaxBlocks); }
 
 }  // namespace
 
@@ -266,9 +201,7 @@ void launch_quantile_update(const float* x, int C, float* centre, uint16_t* hist
 void launch_quantile_finalize(const float* centre, const uint16_t* hist, int bins, int64_t V, int n, const float* width,
                               const float* scale, const double* probs, int P, const uint8_t* mask, float* quantiles,
                               float* ci_width, long long* isummary, double* fsummary, void* ws, hipStream_t st) {
-    const int blocks = quantile_finalize_blocks(V);
-    long long* ipart = (long long*)ws;
-    double* fpart = (double*)(ipart + (size_t)kQInts * blocks);
+    const SummaryPartials<QuantileSummary> part(V, ws, IRS_QUANTILE_WS_BYTES);
     QParams prm{};
     for (int j = 0; j < kQMaxProbs; ++j) {
         prm.r[j] = j < P ? probs[j] * (double)n : 0.0;
@@ -280,9 +213,9 @@ void launch_quantile_finalize(const float* centre, const uint16_t* hist, int bin
     }
     prm.P = P;
     prm.B = bins;
-    hipLaunchKernelGGL(quantile_finalize_kernel, dim3(blocks), dim3(kBlock), 0, st, centre, hist, V, prm, mask, quantiles, ci_width,
-                       ipart, fpart);
-    hipLaunchKernelGGL(quantile_summary_reduce_kernel, dim3(1), dim3(kBlock), 0, st, ipart, fpart, blocks, isummary, fsummary);
+    hipLaunchKernelGGL(quantile_finalize_kernel, dim3(part.blocks), dim3(kBlock), 0, st, centre, hist, V, prm, mask, quantiles,
+                       ci_width, part.ipart, part.fpart);
+    part.reduce(isummary, fsummary, st);
 }
 
 }  // namespace irs

@@ -124,6 +124,86 @@ def recorded_steps(no_iters_burn_in, no_samples_MCMC, period):
     return [s for s in range(first, first + no_samples_MCMC) if is_recorded(s, no_iters_burn_in, period)]
 
 
+def _bool_mask(mask, device):
+    """a mask (or None) on `device` as the bool / uint8 volume the operators take: any other dtype counts where it is != 0"""
+    if mask is None:
+        return None
+    mask = mask.to(device)
+    return mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
+
+
+def _host_summary(isum, fsum):
+    """the int64 and the float64 summary vectors of a finalize in ONE device-to-host copy -> (list of ints, list of floats)"""
+    host = torch.cat([isum.view(torch.float64), fsum]).cpu()
+    ni = isum.numel()
+    return host[:ni].view(torch.int64).tolist(), host[ni:].tolist()
+
+
+def voxel_scale(dims):
+    """normalised coordinates -> voxels, channels x, y, z: (W - 1) / 2, (H - 1) / 2, (D - 1) / 2"""
+    D, H, W = dims
+    return ((W - 1) / 2, (H - 1) / 2, (D - 1) / 2)
+
+
+MAX_RECORDS = 2 ** 31 - 1  # the int32 counts
+
+
+def _record_options(cfg_trainer, key, known, form, ceiling, holds, own_keys=lambda opt: {}):
+    """The skeleton the `trainer.<key>` options of the per-voxel recorders share -> None when off, else {'period': P, **own}.
+    Absent / false / null: off.  true: P = log_period_MCMC.  A dict of `known` keys: "period" may be left out.  Refuses
+    unknown keys, a non-integer P or P < 1, a config that records no step (no_samples_MCMC // P < 1) and one that would
+    record more than `ceiling` (`holds`: the words of that message).  `own_keys(dict)` validates the option's other keys
+    ({} for true) and returns their values; `form` is how the message for anything else spells the accepted dict."""
+    what = f'trainer.{key}'
+    opt = cfg_trainer.get(key, False)
+    if opt is None or opt is False:
+        return None
+    period = None
+    if isinstance(opt, dict):
+        unknown = set(opt) - set(known)
+        if unknown:
+            raise ValueError(f'{what}: unknown keys {sorted(unknown)}; known: {list(known)}')
+        if 'period' in opt:
+            p = opt['period']
+            if isinstance(p, bool) or not isinstance(p, numbers.Integral):
+                raise ValueError(f'{what}.period must be an integer, got {p!r}')
+            period = int(p)
+    elif opt is not True:
+        raise ValueError(f'{what} must be true, false or {form}, got {opt!r}')
+    out = {'period': period, **own_keys(opt if isinstance(opt, dict) else {})}
+    if period is None:
+        out['period'] = period = int(cfg_trainer['log_period_MCMC'])
+    if period < 1:
+        raise ValueError(f'{what}: the period must be >= 1, got {period}')
+    no_samples = int(cfg_trainer['no_samples_MCMC'])
+    steps = no_samples // period
+    if steps < 1:
+        raise ValueError(f'{what}: no_samples_MCMC = {no_samples} with period {period} records no step')
+    records = steps * int(cfg_trainer.get('no_chains', 1))
+    if records > ceiling:
+        raise ValueError(f'{what}: {steps} steps of {cfg_trainer.get("no_chains", 1)} chains are {records} records; '
+                         f'{holds.format(ceiling)}')
+    return out
+
+
+class _Recorder:
+    """What the per-voxel posterior accumulators share: `records`, the number of samples taken so far, the ceiling
+    `record()` checks before `_update(sample)` folds the C samples of one step in, and the guard of what needs a record."""
+    noun, max_records, exceed = None, MAX_RECORDS, 'exceed {}'
+    records = 0
+
+    def record(self, sample):
+        C = sample.shape[0]
+        if self.records + C > self.max_records:
+            raise ValueError(f'{self.noun}: {self.records} + {C} records {self.exceed.format(self.max_records)}')
+        self._update(sample)
+        self.records += C
+
+    def _need_records(self, method):
+        if self.records < 1:
+            raise RuntimeError(f'{type(self).__name__}.{method}: nothing recorded')
+
+
 class ChainMoments:
     """Per-chain, per-half Welford moments of the displacement and the split-R-hat they give; with `max_lag` set, also the
     online variogram of each half and the split ESS / MCSE.
@@ -182,10 +262,7 @@ class ChainMoments:
         """-> (map (D,H,W) float32 on the device, summary dict).  One device-to-host read (the summary)."""
         if self.count != self.n_per_chain:
             raise RuntimeError(f'ChainMoments.rhat: {self.count} of {self.n_per_chain} samples recorded')
-        if mask is not None:
-            mask = mask.to(self.device)
-            mask = mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
-        rhat, s = ops.split_rhat(self.mean, self.m2, self.n, mask, thresholds)
+        rhat, s = ops.split_rhat(self.mean, self.m2, self.n, _bool_mask(mask, self.device), thresholds)
         voxels, above0, above1, mx, total = s.tolist()
         voxels = int(voxels)
         summary = {'voxels': voxels, 'max': mx if voxels else float('nan'), 'mean': total / voxels if voxels else float('nan')}
@@ -200,10 +277,7 @@ class ChainMoments:
             raise RuntimeError('ChainMoments.ess: built without max_lag, so no variogram was kept')
         if self.count != self.n_per_chain:
             raise RuntimeError(f'ChainMoments.ess: {self.count} of {self.n_per_chain} samples recorded')
-        if mask is not None:
-            mask = mask.to(self.device)
-            mask = mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
-        ess, mcse, s = ops.split_ess(self.mean, self.m2, self.vsum, self.n, mask, threshold)
+        ess, mcse, s = ops.split_ess(self.mean, self.m2, self.vsum, self.n, _bool_mask(mask, self.device), threshold)
         voxels, below, truncated, mn, total = s.tolist()
         voxels = int(voxels)
         nan = float('nan')
@@ -237,7 +311,6 @@ class ChainMoments:
 
 LABEL_OPTION_KEYS = ('period', 'prob_maps')
 LABEL_STRUCTURE_METRICS = ('soft_DSC', 'DSC_MAP', 'vol_mean', 'vol_std', 'uncertain_vol', 'ECE')
-MAX_RECORDS = 2 ** 31 - 1  # the int32 counts
 
 
 def label_posterior_options(cfg_trainer):
@@ -245,38 +318,13 @@ def label_posterior_options(cfg_trainer):
     Absent / false / null: off.  true: P = log_period_MCMC.  {"period": P, "prob_maps": bool}: either key may be left out.
     Refuses unknown keys, a non-integer P or P < 1, a non-bool prob_maps, a config that records no step
     (no_samples_MCMC // P < 1) and one that would record more than 2^31 - 1 maps."""
-    opt = cfg_trainer.get('label_posterior', False)
-    if opt is None or opt is False:
-        return None
-    out = {'period': None, 'prob_maps': False}
-    if isinstance(opt, dict):
-        unknown = set(opt) - set(LABEL_OPTION_KEYS)
-        if unknown:
-            raise ValueError(f'trainer.label_posterior: unknown keys {sorted(unknown)}; known: {list(LABEL_OPTION_KEYS)}')
-        if 'period' in opt:
-            p = opt['period']
-            if isinstance(p, bool) or not isinstance(p, numbers.Integral):
-                raise ValueError(f'trainer.label_posterior.period must be an integer, got {p!r}')
-            out['period'] = int(p)
-        if 'prob_maps' in opt:
-            if not isinstance(opt['prob_maps'], bool):
-                raise ValueError(f'trainer.label_posterior.prob_maps must be true or false, got {opt["prob_maps"]!r}')
-            out['prob_maps'] = opt['prob_maps']
-    elif opt is not True:
-        raise ValueError(f'trainer.label_posterior must be true, false or {{"period": P, "prob_maps": bool}}, got {opt!r}')
-    if out['period'] is None:
-        out['period'] = int(cfg_trainer['log_period_MCMC'])
-    if out['period'] < 1:
-        raise ValueError(f'trainer.label_posterior: the period must be >= 1, got {out["period"]}')
-    no_samples = int(cfg_trainer['no_samples_MCMC'])
-    steps = no_samples // out['period']
-    if steps < 1:
-        raise ValueError(f'trainer.label_posterior: no_samples_MCMC = {no_samples} with period {out["period"]} records no step')
-    records = steps * int(cfg_trainer.get('no_chains', 1))
-    if records > MAX_RECORDS:
-        raise ValueError(f'trainer.label_posterior: {steps} steps of {cfg_trainer.get("no_chains", 1)} chains are {records} '
-                         f'records; the counts hold at most {MAX_RECORDS}')
-    return out
+    def own_keys(opt):
+        if not isinstance(opt.get('prob_maps', False), bool):
+            raise ValueError(f'trainer.label_posterior.prob_maps must be true or false, got {opt["prob_maps"]!r}')
+        return {'prob_maps': opt.get('prob_maps', False)}
+
+    return _record_options(cfg_trainer, 'label_posterior', LABEL_OPTION_KEYS, '{"period": P, "prob_maps": bool}', MAX_RECORDS,
+                           'the counts hold at most {}', own_keys)
 
 
 def _nan_div(a, b):
@@ -310,11 +358,12 @@ def label_summary(raw, volume, n, mask_summary, names, spacing):
             'structures': structures}
 
 
-class LabelPosterior:
+class LabelPosterior(_Recorder):
     """Per-voxel counts of every structure of `structures_dict` over the recorded warps of the moving segmentation, and the
     Welford moments of each structure's per-record volume, on the device (4 K D H W + 16 K bytes whatever the number of
     records).  `record(seg_warped)` takes the (C,1,D,H,W) int16 maps of one step, chains in order; `finalize` gives the
     entropy and MAP maps and the summary; `probabilities()` the (K,D,H,W) label probabilities."""
+    noun = 'label posterior'
 
     def __init__(self, structures_dict, dims, device):
         self.names = list(structures_dict)
@@ -327,26 +376,17 @@ class LabelPosterior:
         self.device = device
         self.counts = torch.zeros((len(self.labels), *self.dims), device=device, dtype=torch.int32)
         self.volume = torch.zeros((len(self.labels), 2), device=device, dtype=torch.float64)
-        self.records = 0
 
-    def record(self, seg_warped):
-        C = seg_warped.shape[0]
-        if self.records + C > MAX_RECORDS:
-            raise ValueError(f'label posterior: {self.records} + {C} records exceed {MAX_RECORDS}')
+    def _update(self, seg_warped):
         ops.label_posterior_update(seg_warped, self.labels, self.counts, self.volume, self.records)
-        self.records += C
 
     def finalize(self, seg_fixed, mask=None, spacing=(1.0, 1.0, 1.0)):
         """-> (entropy (D,H,W) float32, map_label (D,H,W) int16, both on the device, summary dict of label_summary).
         The entropy statistics are over `mask` (the FIXED mask: the maps live on the fixed grid).  One device-to-host read."""
         from . import _lib as L
-        if self.records < 1:
-            raise RuntimeError('LabelPosterior.finalize: nothing recorded')
-        if mask is not None:
-            mask = mask.to(self.device)
-            mask = mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
+        self._need_records('finalize')
         entropy, map_label, raw, ms = ops.label_posterior_finalize(self.counts, self.records, self.labels,
-                                                                   seg_fixed.to(self.device), mask)
+                                                                   seg_fixed.to(self.device), _bool_mask(mask, self.device))
         host = torch.cat([raw.reshape(-1).view(torch.float64), ms, self.volume.reshape(-1)]).cpu()
         KC = raw.numel()
         raw_h = host[:KC].view(torch.int64).reshape(raw.shape).numpy()
@@ -362,8 +402,7 @@ class LabelPosterior:
 
     def probabilities(self):
         """-> (K,D,H,W) float32 on the device: counts / n"""
-        if self.records < 1:
-            raise RuntimeError('LabelPosterior.probabilities: nothing recorded')
+        self._need_records('probabilities')
         return self.counts.float() / self.records
 
     def state_dict(self):
@@ -390,34 +429,8 @@ def jacobian_posterior_options(cfg_trainer):
     Absent / false / null: off.  true: P = log_period_MCMC.  {"period": P}: that P (the key may be left out).
     Refuses unknown keys, a non-integer P or P < 1, a config that records no step (no_samples_MCMC // P < 1) and one that
     would record more than 2^31 - 1 transformations."""
-    opt = cfg_trainer.get('jacobian_posterior', False)
-    if opt is None or opt is False:
-        return None
-    period = None
-    if isinstance(opt, dict):
-        unknown = set(opt) - set(JACOBIAN_OPTION_KEYS)
-        if unknown:
-            raise ValueError(f'trainer.jacobian_posterior: unknown keys {sorted(unknown)}; known: {list(JACOBIAN_OPTION_KEYS)}')
-        if 'period' in opt:
-            p = opt['period']
-            if isinstance(p, bool) or not isinstance(p, numbers.Integral):
-                raise ValueError(f'trainer.jacobian_posterior.period must be an integer, got {p!r}')
-            period = int(p)
-    elif opt is not True:
-        raise ValueError(f'trainer.jacobian_posterior must be true, false or {{"period": P}}, got {opt!r}')
-    if period is None:
-        period = int(cfg_trainer['log_period_MCMC'])
-    if period < 1:
-        raise ValueError(f'trainer.jacobian_posterior: the period must be >= 1, got {period}')
-    no_samples = int(cfg_trainer['no_samples_MCMC'])
-    steps = no_samples // period
-    if steps < 1:
-        raise ValueError(f'trainer.jacobian_posterior: no_samples_MCMC = {no_samples} with period {period} records no step')
-    records = steps * int(cfg_trainer.get('no_chains', 1))
-    if records > MAX_RECORDS:
-        raise ValueError(f'trainer.jacobian_posterior: {steps} steps of {cfg_trainer.get("no_chains", 1)} chains are {records} '
-                         f'records; the fold counts hold at most {MAX_RECORDS}')
-    return {'period': period}
+    return _record_options(cfg_trainer, 'jacobian_posterior', JACOBIAN_OPTION_KEYS, '{"period": P}', MAX_RECORDS,
+                           'the fold counts hold at most {}')
 
 
 def jacobian_summary(isummary, fsummary, n):
@@ -434,11 +447,12 @@ def jacobian_summary(isummary, fsummary, n):
             'logJ_std_mean': _nan_div(ls_sum, valid), 'logJ_std_max': ls_max if valid else nan}
 
 
-class JacobianPosterior:
+class JacobianPosterior(_Recorder):
     """Per voxel, the number of recorded transformations that fold there and the Welford mean / M2 of log det J over those
     that do not, on the device (12 D H W bytes whatever the number of records).  `record(transformation)` takes the
     (C,3,D,H,W) float32 transformations of one step, chains in order; `finalize` gives the fold probability, the mean and
     the std of log det J, and the summary over a mask."""
+    noun = 'Jacobian posterior'
 
     def __init__(self, dims, device):
         self.dims = tuple(int(d) for d in dims)
@@ -448,29 +462,17 @@ class JacobianPosterior:
         self.folds = torch.zeros(self.dims, device=device, dtype=torch.int32)
         self.mean = torch.zeros(self.dims, device=device, dtype=torch.float32)
         self.m2 = torch.zeros(self.dims, device=device, dtype=torch.float32)
-        self.records = 0
 
-    def record(self, transformation):
-        C = transformation.shape[0]
-        if self.records + C > MAX_RECORDS:
-            raise ValueError(f'Jacobian posterior: {self.records} + {C} records exceed {MAX_RECORDS}')
+    def _update(self, transformation):
         ops.jacobian_posterior_update(transformation, self.folds, self.mean, self.m2, self.records)
-        self.records += C
 
     def finalize(self, mask=None):
         """-> (fold_prob, logJ_mean, logJ_std, all (D,H,W) float32 on the device, summary dict of jacobian_summary).
         One device-to-host read (the summary)."""
-        if self.records < 1:
-            raise RuntimeError('JacobianPosterior.finalize: nothing recorded')
-        if mask is not None:
-            mask = mask.to(self.device)
-            mask = mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
+        self._need_records('finalize')
         fold_prob, logj_mean, logj_std, isum, fsum = ops.jacobian_posterior_finalize(self.folds, self.mean, self.m2, self.records,
-                                                                                    mask)
-        host = torch.cat([isum.view(torch.float64), fsum]).cpu()
-        ni = isum.numel()
-        summary = jacobian_summary(host[:ni].view(torch.int64).tolist(), host[ni:].tolist(), self.records)
-        return fold_prob, logj_mean, logj_std, summary
+                                                                                    _bool_mask(mask, self.device))
+        return fold_prob, logj_mean, logj_std, jacobian_summary(*_host_summary(isum, fsum), self.records)
 
     def state_dict(self):
         return {'folds': self.folds.detach().cpu(), 'mean': self.mean.detach().cpu(), 'm2': self.m2.detach().cpu(),
@@ -497,35 +499,8 @@ def displacement_covariance_options(cfg_trainer):
     Absent / false / null: off.  true: P = log_period_MCMC.  {"period": P}: that P (the key may be left out).
     Refuses unknown keys, a non-integer P or P < 1, a config that records no step (no_samples_MCMC // P < 1) and one that
     would record more than 2^31 - 1 displacements."""
-    opt = cfg_trainer.get('displacement_covariance', False)
-    if opt is None or opt is False:
-        return None
-    period = None
-    if isinstance(opt, dict):
-        unknown = set(opt) - set(COVARIANCE_OPTION_KEYS)
-        if unknown:
-            raise ValueError(f'trainer.displacement_covariance: unknown keys {sorted(unknown)}; known: '
-                             f'{list(COVARIANCE_OPTION_KEYS)}')
-        if 'period' in opt:
-            p = opt['period']
-            if isinstance(p, bool) or not isinstance(p, numbers.Integral):
-                raise ValueError(f'trainer.displacement_covariance.period must be an integer, got {p!r}')
-            period = int(p)
-    elif opt is not True:
-        raise ValueError(f'trainer.displacement_covariance must be true, false or {{"period": P}}, got {opt!r}')
-    if period is None:
-        period = int(cfg_trainer['log_period_MCMC'])
-    if period < 1:
-        raise ValueError(f'trainer.displacement_covariance: the period must be >= 1, got {period}')
-    no_samples = int(cfg_trainer['no_samples_MCMC'])
-    steps = no_samples // period
-    if steps < 1:
-        raise ValueError(f'trainer.displacement_covariance: no_samples_MCMC = {no_samples} with period {period} records no step')
-    records = steps * int(cfg_trainer.get('no_chains', 1))
-    if records > MAX_RECORDS:
-        raise ValueError(f'trainer.displacement_covariance: {steps} steps of {cfg_trainer.get("no_chains", 1)} chains are '
-                         f'{records} records; the record count holds at most {MAX_RECORDS}')
-    return {'period': period}
+    return _record_options(cfg_trainer, 'displacement_covariance', COVARIANCE_OPTION_KEYS, '{"period": P}', MAX_RECORDS,
+                           'the record count holds at most {}')
 
 
 def covariance_summary(isummary, fsummary, n):
@@ -544,11 +519,12 @@ def covariance_summary(isummary, fsummary, n):
             'dir_x': _nan_div(dx, finite), 'dir_y': _nan_div(dy, finite), 'dir_z': _nan_div(dz, finite)}
 
 
-class DisplacementCovariance:
+class DisplacementCovariance(_Recorder):
     """Per voxel, the Welford mean (3,D,H,W) and the co-moments (6,D,H,W: xx, yy, zz, xy, xz, yz) of the displacement over the
     recorded samples, pooled over chains, on the device (36 D H W bytes whatever the number of records).
     `record(displacement)` takes the (C,3,D,H,W) float32 displacements of one step, chains in order; `finalize` gives the
     principal standard deviations, the major direction, the fractional anisotropy and the summary over a mask."""
+    noun = 'displacement covariance'
 
     def __init__(self, dims, device):
         self.dims = tuple(int(d) for d in dims)
@@ -557,42 +533,27 @@ class DisplacementCovariance:
         self.device = device
         self.mean = torch.zeros((3,) + self.dims, device=device, dtype=torch.float32)
         self.comoment = torch.zeros((6,) + self.dims, device=device, dtype=torch.float32)
-        self.records = 0
 
     def default_scale(self):
-        """normalised coordinates -> voxels, channels x, y, z: (W - 1) / 2, (H - 1) / 2, (D - 1) / 2"""
-        D, H, W = self.dims
-        return ((W - 1) / 2, (H - 1) / 2, (D - 1) / 2)
+        return voxel_scale(self.dims)
 
-    def record(self, displacement):
-        C = displacement.shape[0]
-        if self.records + C > MAX_RECORDS:
-            raise ValueError(f'displacement covariance: {self.records} + {C} records exceed {MAX_RECORDS}')
+    def _update(self, displacement):
         ops.displacement_covariance_update(displacement, self.mean, self.comoment, self.records)
-        self.records += C
 
     def covariance(self):
         """-> (6,D,H,W) float32: the sample covariance in normalised units, comoment / max(n - 1, 1)"""
-        if self.records < 1:
-            raise RuntimeError('DisplacementCovariance.covariance: nothing recorded')
+        self._need_records('covariance')
         return self.comoment / max(self.records - 1, 1)
 
     def finalize(self, mask=None, scale=None):
         """-> (std (3,D,H,W), direction (3,D,H,W), anisotropy (D,H,W), float32 on the device, summary dict of
         covariance_summary).  scale: three positive floats, one per channel (default: voxel units).  One device-to-host
         read (the summary)."""
-        if self.records < 1:
-            raise RuntimeError('DisplacementCovariance.finalize: nothing recorded')
-        if mask is not None:
-            mask = mask.to(self.device)
-            mask = mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
+        self._need_records('finalize')
         scale = self.default_scale() if scale is None else tuple(float(s) for s in scale)
         std, direction, anisotropy, isum, fsum = ops.displacement_covariance_finalize(self.mean, self.comoment, self.records,
-                                                                                      scale, mask)
-        host = torch.cat([isum.view(torch.float64), fsum]).cpu()
-        ni = isum.numel()
-        summary = covariance_summary(host[:ni].view(torch.int64).tolist(), host[ni:].tolist(), self.records)
-        return std, direction, anisotropy, summary
+                                                                                      scale, _bool_mask(mask, self.device))
+        return std, direction, anisotropy, covariance_summary(*_host_summary(isum, fsum), self.records)
 
     def state_dict(self):
         return {'mean': self.mean.detach().cpu(), 'comoment': self.comoment.detach().cpu(), 'records': self.records}
@@ -647,44 +608,14 @@ def displacement_quantiles_options(cfg_trainer):
     (0,1), bins that are not an even integer in 4..256, a bin_width that is not a finite number > 0, a config that records no
     step (no_samples_MCMC // P < 1) and one that would record more than 65535 displacements (a uint16 count)."""
     what = 'trainer.displacement_quantiles'
-    opt = cfg_trainer.get('displacement_quantiles', False)
-    if opt is None or opt is False:
-        return None
-    out = {'period': None, **QUANTILE_DEFAULTS}
-    if isinstance(opt, dict):
-        unknown = set(opt) - set(QUANTILE_OPTION_KEYS)
-        if unknown:
-            raise ValueError(f'{what}: unknown keys {sorted(unknown)}; known: {list(QUANTILE_OPTION_KEYS)}')
-        if 'period' in opt:
-            p = opt['period']
-            if isinstance(p, bool) or not isinstance(p, numbers.Integral):
-                raise ValueError(f'{what}.period must be an integer, got {p!r}')
-            out['period'] = int(p)
-        if 'probs' in opt:
-            out['probs'] = opt['probs']
-        if 'bins' in opt:
-            out['bins'] = opt['bins']
-        if 'bin_width' in opt:
-            out['bin_width'] = opt['bin_width']
-    elif opt is not True:
-        raise ValueError(f'{what} must be true, false or a dict of {list(QUANTILE_OPTION_KEYS)}, got {opt!r}')
-    out['probs'] = _quantile_probs(out['probs'], what)
-    out['bins'] = _quantile_bins(out['bins'], what)
-    out['bin_width'] = _quantile_bin_width(out['bin_width'], what)
-    if out['period'] is None:
-        out['period'] = int(cfg_trainer['log_period_MCMC'])
-    period = out['period']
-    if period < 1:
-        raise ValueError(f'{what}: the period must be >= 1, got {period}')
-    no_samples = int(cfg_trainer['no_samples_MCMC'])
-    steps = no_samples // period
-    if steps < 1:
-        raise ValueError(f'{what}: no_samples_MCMC = {no_samples} with period {period} records no step')
-    records = steps * int(cfg_trainer.get('no_chains', 1))
-    if records > QUANTILE_MAX_RECORDS:
-        raise ValueError(f'{what}: {steps} steps of {cfg_trainer.get("no_chains", 1)} chains are {records} records; a uint16 count '
-                         f'holds at most {QUANTILE_MAX_RECORDS}: raise `period`')
-    return out
+
+    def own_keys(opt):
+        own = {**QUANTILE_DEFAULTS, **{k: v for k, v in opt.items() if k != 'period'}}
+        return {'probs': _quantile_probs(own['probs'], what), 'bins': _quantile_bins(own['bins'], what),
+                'bin_width': _quantile_bin_width(own['bin_width'], what)}
+
+    return _record_options(cfg_trainer, 'displacement_quantiles', QUANTILE_OPTION_KEYS, f'a dict of {list(QUANTILE_OPTION_KEYS)}',
+                           QUANTILE_MAX_RECORDS, 'a uint16 count holds at most {}: raise `period`', own_keys)
 
 
 def quantiles_summary(isummary, fsummary, n):
@@ -703,7 +634,7 @@ def quantiles_summary(isummary, fsummary, n):
             'out_of_range_frac': _nan_div(out_of_range, voxels), 'clipped_frac': _nan_div(clipped, 3 * int(n) * voxels)}
 
 
-class DisplacementQuantiles:
+class DisplacementQuantiles(_Recorder):
     """Per voxel and channel, a histogram of the displacement over the recorded samples, pooled over chains, on the device:
     `centre` (3,D,H,W) float32, the displacement of the very first record, and `hist` (3,bins,D,H,W) uint16, bin-major (one
     bin of one channel is a contiguous volume).  That is 12 + 6 * bins bytes per voxel whatever the number of records: 396
@@ -715,6 +646,7 @@ class DisplacementQuantiles:
     open-ended; a quantile that falls into one of them is out of range and reported as NaN.
     `record(displacement)` takes the (C,3,D,H,W) float32 displacements of one step; `finalize(probs)` gives the quantile
     maps, the width of the band between the first and the last probability and the summary over a mask."""
+    noun, max_records, exceed = 'displacement quantiles', QUANTILE_MAX_RECORDS, 'exceed the {} a uint16 count holds'
 
     def __init__(self, dims, device, bins=64, bin_width=0.125, scale=None):
         self.dims = tuple(int(d) for d in dims)
@@ -734,7 +666,6 @@ class DisplacementQuantiles:
             raise ValueError(f'displacement quantiles: bin_width {self.bin_width} over scale {scale} is not a float32 width')
         self.centre = torch.zeros((3,) + self.dims, device=device, dtype=torch.float32)
         self.hist = torch.zeros((3, self.bins) + self.dims, device=device, dtype=torch.int16).view(torch.uint16)
-        self.records = 0
 
     @staticmethod
     def bytes_per_voxel(bins):
@@ -745,39 +676,24 @@ class DisplacementQuantiles:
         return self.bytes_per_voxel(self.bins) * D * H * W
 
     def default_scale(self):
-        """normalised coordinates -> voxels, channels x, y, z: (W - 1) / 2, (H - 1) / 2, (D - 1) / 2"""
-        D, H, W = self.dims
-        return ((W - 1) / 2, (H - 1) / 2, (D - 1) / 2)
+        return voxel_scale(self.dims)
 
-    def record(self, displacement):
-        C = displacement.shape[0]
-        if self.records + C > QUANTILE_MAX_RECORDS:
-            raise ValueError(f'displacement quantiles: {self.records} + {C} records exceed the {QUANTILE_MAX_RECORDS} a uint16 '
-                             f'count holds')
+    def _update(self, displacement):
         ops.displacement_quantiles_update(displacement, self.centre, self.hist, self.inv_width, self.records)
-        self.records += C
 
     def histogram(self):
         """-> (3,bins,D,H,W) int32 on the device: the counts; every voxel and channel sums to `records`"""
-        if self.records < 1:
-            raise RuntimeError('DisplacementQuantiles.histogram: nothing recorded')
+        self._need_records('histogram')
         return self.hist.view(torch.int16).to(torch.int32) & 0xFFFF
 
     def finalize(self, probs, mask=None):
         """-> (quantiles (P,3,D,H,W), ci_width (D,H,W), float32 on the device, in the units of `scale`, NaN where out of
         range; summary dict of quantiles_summary).  One device-to-host read (the summary)."""
-        if self.records < 1:
-            raise RuntimeError('DisplacementQuantiles.finalize: nothing recorded')
+        self._need_records('finalize')
         probs = _quantile_probs(probs, 'displacement quantiles')
-        if mask is not None:
-            mask = mask.to(self.device)
-            mask = mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
         quantiles, ci_width, isum, fsum = ops.displacement_quantiles_finalize(self.centre, self.hist, self.records, self.width,
-                                                                              self.scale, probs, mask)
-        host = torch.cat([isum.view(torch.float64), fsum]).cpu()
-        ni = isum.numel()
-        summary = quantiles_summary(host[:ni].view(torch.int64).tolist(), host[ni:].tolist(), self.records)
-        return quantiles, ci_width, summary
+                                                                              self.scale, probs, _bool_mask(mask, self.device))
+        return quantiles, ci_width, quantiles_summary(*_host_summary(isum, fsum), self.records)
 
     def state_dict(self):
         return {'centre': self.centre.detach().cpu(), 'hist': self.hist.detach().cpu(), 'records': self.records,

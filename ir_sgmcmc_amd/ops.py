@@ -319,6 +319,15 @@ def chain_moments_update(x, mean, m2, half, k):
                                          L.dev_ptr(mean, torch.float32), L.dev_ptr(m2, torch.float32), L.stream_ptr()))
 
 
+def _volume_mask(mask, D, H, W):
+    if mask is None:
+        return None
+    if mask.numel() != D * H * W or mask.dtype not in (torch.bool, torch.uint8):
+        raise L.IrsError(f'mask must be a bool / uint8 ({D},{H},{W}) volume, got {mask.dtype} {tuple(mask.shape)}')
+    mask = mask.reshape(D, H, W).contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
 def split_rhat(mean, m2, n, mask=None, thresholds=(1.01, 1.1)):
     """Split-R-hat (BDA3 section 11.4) from the per-half moments of chain_moments_update, n samples per half.
     mask (D,H,W) bool / uint8 or None.  -> (rhat (D,H,W) float32, summary (5,) float64 on the device: voxels in the mask,
@@ -327,11 +336,7 @@ def split_rhat(mean, m2, n, mask=None, thresholds=(1.01, 1.1)):
     if mean.dim() != 6 or mean.shape[0] != 2 or mean.shape[2] != 3 or tuple(m2.shape) != tuple(mean.shape):
         raise L.IrsError(f'mean / m2 must have shape (2,C,3,D,H,W), got {tuple(mean.shape)} / {tuple(m2.shape)}')
     Cn, D, H, W = mean.shape[1], mean.shape[3], mean.shape[4], mean.shape[5]
-    if mask is not None:
-        if mask.numel() != D * H * W or mask.dtype not in (torch.bool, torch.uint8):
-            raise L.IrsError(f'mask must be a bool / uint8 ({D},{H},{W}) volume, got {mask.dtype} {tuple(mask.shape)}')
-        mask = mask.reshape(D, H, W).contiguous()
-        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    mask = _volume_mask(mask, D, H, W)
     if len(thresholds) != 2:
         raise L.IrsError('split_rhat takes two thresholds')
     nbytes = C.c_size_t()
@@ -373,11 +378,7 @@ def split_ess(mean, m2, vsum, n, mask=None, threshold=400.0):
     Cn, D, H, W = mean.shape[1], mean.shape[3], mean.shape[4], mean.shape[5]
     if vsum.dim() != 5 or tuple(vsum.shape[1:]) != (3, D, H, W):
         raise L.IrsError(f'vsum must have shape (L,3,{D},{H},{W}), got {tuple(vsum.shape)}')
-    if mask is not None:
-        if mask.numel() != D * H * W or mask.dtype not in (torch.bool, torch.uint8):
-            raise L.IrsError(f'mask must be a bool / uint8 ({D},{H},{W}) volume, got {mask.dtype} {tuple(mask.shape)}')
-        mask = mask.reshape(D, H, W).contiguous()
-        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    mask = _volume_mask(mask, D, H, W)
     nbytes = C.c_size_t()
     L.check(lib.irs_split_ess_workspace(Cn, D, H, W, C.byref(nbytes)))
     dev = mean.device
@@ -433,11 +434,7 @@ def label_posterior_finalize(counts, n, labels, seg_fixed, mask=None):
     if seg_fixed.numel() != D * H * W or seg_fixed.shape[-3:] != (D, H, W):
         raise L.IrsError(f'seg_fixed must be a ({D},{H},{W}) volume, got {tuple(seg_fixed.shape)}')
     seg_fixed = seg_fixed.reshape(D, H, W).contiguous()
-    if mask is not None:
-        if mask.numel() != D * H * W or mask.dtype not in (torch.bool, torch.uint8):
-            raise L.IrsError(f'mask must be a bool / uint8 ({D},{H},{W}) volume, got {mask.dtype} {tuple(mask.shape)}')
-        mask = mask.reshape(D, H, W).contiguous()
-        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    mask = _volume_mask(mask, D, H, W)
     nbytes = C.c_size_t()
     L.check(lib.irs_label_posterior_workspace(1, K, D, H, W, C.byref(nbytes)))
     dev = counts.device
@@ -451,15 +448,6 @@ def label_posterior_finalize(counts, n, labels, seg_fixed, mask=None):
                                              L.dev_ptr(entropy), L.dev_ptr(map_label), L.dev_ptr(summary),
                                              L.dev_ptr(mask_summary), L.dev_ptr(ws), nbytes.value, L.stream_ptr()))
     return entropy, map_label, summary, mask_summary
-
-
-def _volume_mask(mask, D, H, W):
-    if mask is None:
-        return None
-    if mask.numel() != D * H * W or mask.dtype not in (torch.bool, torch.uint8):
-        raise L.IrsError(f'mask must be a bool / uint8 ({D},{H},{W}) volume, got {mask.dtype} {tuple(mask.shape)}')
-    mask = mask.reshape(D, H, W).contiguous()
-    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
 
 
 def _jacobian_state(folds, mean, m2, shape):

@@ -12,6 +12,7 @@ HIP stream (ir_sgmcmc_amd/csrc/api.hip: transition_impl).  The hyper-parameters 
 the device state once (`_engine_init`) and read back lazily (`sync_parameters`) when something logs them.
 """
 import time
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -26,6 +27,13 @@ from ..logger import (save_displacement_covariance, save_displacement_mean_and_s
                       save_jacobian_posterior, save_label_posterior, save_rhat, save_sample)
 from ..utils import calc_norm, calc_no_non_diffeomorphic_voxels, sample_q_v
 from .vi import VIMixin
+
+
+# A posterior recorder of the MCMC stage (Trainer._recorders): its checkpoint key, its state object (diagnostics.py), its
+# period, the trainer.<option> that switches it on, the noun of the resume error, the transition output it records
+# ('displacement', 'transformation' or 'seg_warped': the warped moving segmentation), its _finish_* method and what that
+# takes first ('fixed': the fixed image's dict, 'moving_mask': the mask of the displacement std map)
+Recorder = namedtuple('Recorder', 'key state period option noun records finish takes')
 
 
 class LazyScalar:
@@ -171,6 +179,22 @@ class Trainer(VIMixin, BaseTrainer):
             self._scalars_cache = self.engine.scalars()
         return self._scalars_cache
 
+    def _recorders(self):
+        """the active recorders, in the order they record and finish: moments, labels, Jacobian, covariance, quantiles"""
+        period = lambda options: options and options['period']
+        rows = (('chain_moments', self._chain_moments, self.diagnostics_period, 'convergence_diagnostics', 'chain moments',
+                 'displacement', self._finish_diagnostics, 'moving_mask'),
+                ('label_posterior', self._label_posterior, period(self.label_options), 'label_posterior', 'label posterior',
+                 'seg_warped', self._finish_label_posterior, 'fixed'),
+                ('jacobian_posterior', self._jacobian_posterior, period(self.jacobian_options), 'jacobian_posterior',
+                 'Jacobian posterior', 'transformation', self._finish_jacobian_posterior, 'fixed'),
+                ('displacement_covariance', self._displacement_covariance, period(self.covariance_options),
+                 'displacement_covariance', 'displacement covariance', 'displacement', self._finish_displacement_covariance,
+                 'moving_mask'),
+                ('displacement_quantiles', self._displacement_quantiles, period(self.quantiles_options), 'displacement_quantiles',
+                 'displacement quantiles', 'displacement', self._finish_displacement_quantiles, 'moving_mask'))
+        return [Recorder(*row) for row in rows if row[1] is not None]
+
     # ---------------------------------------------------------------- checkpoint / resume (absent in the reference)
     def state_dict(self):
         """Everything a chain needs to continue bit-for-bit: the velocity field, the SGLD pre-conditioner, the device-side
@@ -184,13 +208,7 @@ class Trainer(VIMixin, BaseTrainer):
                 'sample_no': getattr(self, '_sample_no', 0),
                 'moments': {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in getattr(self, '_moments', {}).items()},
                 'config_name': self.config['name'],
-                **({'chain_moments': self._chain_moments.state_dict()} if self._chain_moments is not None else {}),
-                **({'label_posterior': self._label_posterior.state_dict()} if self._label_posterior is not None else {}),
-                **({'jacobian_posterior': self._jacobian_posterior.state_dict()} if self._jacobian_posterior is not None else {}),
-                **({'displacement_covariance': self._displacement_covariance.state_dict()}
-                   if self._displacement_covariance is not None else {}),
-                **({'displacement_quantiles': self._displacement_quantiles.state_dict()}
-                   if self._displacement_quantiles is not None else {})}
+                **{r.key: r.state.state_dict() for r in self._recorders()}}
 
     def load_state_dict(self, sd):
         import ctypes
@@ -208,45 +226,13 @@ class Trainer(VIMixin, BaseTrainer):
         self.SGLD_params = {'tau': sd['tau'], 'sigma': self._sigma if self._sigma is not None else torch.ones_like(self.v_curr_state)}
         self._sample_no = int(sd['sample_no'])
         self._moments = {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in sd.get('moments', {}).items()}
-        if self._chain_moments is not None:
-            if 'chain_moments' in sd:
-                self._chain_moments.load_state_dict(sd['chain_moments'])
-            elif any(is_recorded(s, self.no_iters_burn_in, self.diagnostics_period) for s in range(1, self._sample_no + 1)):
-                raise ValueError(f'the checkpoint at sample {self._sample_no} holds no chain moments (written with '
-                                 f'trainer.convergence_diagnostics off) but this run records from sample '
-                                 f'{self.no_iters_burn_in + self.diagnostics_period} on')
-        if self._label_posterior is not None:
-            period = self.label_options['period']
-            if 'label_posterior' in sd:
-                self._label_posterior.load_state_dict(sd['label_posterior'])
-            elif any(is_recorded(s, self.no_iters_burn_in, period) for s in range(1, self._sample_no + 1)):
-                raise ValueError(f'the checkpoint at sample {self._sample_no} holds no label posterior (written with '
-                                 f'trainer.label_posterior off) but this run records from sample '
-                                 f'{self.no_iters_burn_in + period} on')
-        if self._jacobian_posterior is not None:
-            period = self.jacobian_options['period']
-            if 'jacobian_posterior' in sd:
-                self._jacobian_posterior.load_state_dict(sd['jacobian_posterior'])
-            elif any(is_recorded(s, self.no_iters_burn_in, period) for s in range(1, self._sample_no + 1)):
-                raise ValueError(f'the checkpoint at sample {self._sample_no} holds no Jacobian posterior (written with '
-                                 f'trainer.jacobian_posterior off) but this run records from sample '
-                                 f'{self.no_iters_burn_in + period} on')
-        if self._displacement_covariance is not None:
-            period = self.covariance_options['period']
-            if 'displacement_covariance' in sd:
-                self._displacement_covariance.load_state_dict(sd['displacement_covariance'])
-            elif any(is_recorded(s, self.no_iters_burn_in, period) for s in range(1, self._sample_no + 1)):
-                raise ValueError(f'the checkpoint at sample {self._sample_no} holds no displacement covariance (written with '
-                                 f'trainer.displacement_covariance off) but this run records from sample '
-                                 f'{self.no_iters_burn_in + period} on')
-        if self._displacement_quantiles is not None:
-            period = self.quantiles_options['period']
-            if 'displacement_quantiles' in sd:
-                self._displacement_quantiles.load_state_dict(sd['displacement_quantiles'])
-            elif any(is_recorded(s, self.no_iters_burn_in, period) for s in range(1, self._sample_no + 1)):
-                raise ValueError(f'the checkpoint at sample {self._sample_no} holds no displacement quantiles (written with '
-                                 f'trainer.displacement_quantiles off) but this run records from sample '
-                                 f'{self.no_iters_burn_in + period} on')
+        for r in self._recorders():
+            if r.key in sd:
+                r.state.load_state_dict(sd[r.key])
+            elif any(is_recorded(s, self.no_iters_burn_in, r.period) for s in range(1, self._sample_no + 1)):
+                raise ValueError(f'the checkpoint at sample {self._sample_no} holds no {r.noun} (written with '
+                                 f'trainer.{r.option} off) but this run records from sample '
+                                 f'{self.no_iters_burn_in + r.period} on')
         self.sync_parameters()
 
     def save_checkpoint(self, file_path):
@@ -376,6 +362,7 @@ class Trainer(VIMixin, BaseTrainer):
             if self._moments:
                 mean, m2, n_rec = self._moments['mean'], self._moments['m2'], int(self._moments['n'])
             log(f'resumed from {cfg_trainer["resume"]} at sample {self._sample_no}')
+        recorders = self._recorders()
         for sample_no in range(first, n_total + 1):
             if sample_no < self.no_iters_burn_in and sample_no % self.log_period_MCMC == 0:
                 log(f'burn-in sample no. {sample_no}/{self.no_iters_burn_in}')
@@ -429,25 +416,13 @@ class Trainer(VIMixin, BaseTrainer):
                         log(f'chain {idx}, sample {sample_no}: detected {no_folds} voxels where the sampled '
                             f'transformation is not diffeomorphic; exiting..')
                         raise SystemExit(1)
-            if self._chain_moments is not None and is_recorded(sample_no, self.no_iters_burn_in, self.diagnostics_period):
-                self.engine.flush()  # as above: the buffer holds sample `sample_no` once nothing is pending
-                self._chain_moments.record(output['displacement'])
-            if self._label_posterior is not None and is_recorded(sample_no, self.no_iters_burn_in, self.label_options['period']):
-                self.engine.flush()  # as above
-                if seg_warped is None:
+            due = [r for r in recorders if is_recorded(sample_no, self.no_iters_burn_in, r.period)]
+            if due:
+                self.engine.flush()  # as above: the buffers hold sample `sample_no` once nothing is pending
+            for r in due:
+                if r.records == 'seg_warped' and seg_warped is None:
                     seg_warped = self.registration_module(moving['seg'], output['transformation'])
-                self._label_posterior.record(seg_warped)
-            if self._jacobian_posterior is not None and is_recorded(sample_no, self.no_iters_burn_in, self.jacobian_options['period']):
-                self.engine.flush()  # as above
-                self._jacobian_posterior.record(output['transformation'])
-            if self._displacement_covariance is not None and is_recorded(sample_no, self.no_iters_burn_in,
-                                                                         self.covariance_options['period']):
-                self.engine.flush()  # as above
-                self._displacement_covariance.record(output['displacement'])
-            if self._displacement_quantiles is not None and is_recorded(sample_no, self.no_iters_burn_in,
-                                                                        self.quantiles_options['period']):
-                self.engine.flush()  # as above
-                self._displacement_quantiles.record(output['displacement'])
+                r.state.record(seg_warped if r.records == 'seg_warped' else output[r.records])
             if checkpoint_period and sample_no % checkpoint_period == 0:
                 self._sample_no, self._moments = sample_no, {'mean': mean, 'm2': m2, 'n': n_rec}
                 folder = self.config.save_dirs['checkpoints']
@@ -459,18 +434,9 @@ class Trainer(VIMixin, BaseTrainer):
         if n_rec > 0 and cfg_trainer.get('save_outputs', True):
             save_displacement_mean_and_std_dev(self.logger, self.config.save_dirs, spacing, self.displacement_mean,
                                                self.displacement_std, moving.get('mask', fixed['mask'])[0].to(mean.dtype), 'MCMC')  # trainer.py:461-462: the MOVING mask
-        if self._chain_moments is not None:
-            self._finish_diagnostics(moving.get('mask', fixed['mask'])[0], spacing, cfg_trainer.get('save_outputs', True))
-        if self._label_posterior is not None:
-            self._finish_label_posterior(fixed, spacing, cfg_trainer.get('save_outputs', True))
-        if self._jacobian_posterior is not None:
-            self._finish_jacobian_posterior(fixed, spacing, cfg_trainer.get('save_outputs', True))
-        if self._displacement_covariance is not None:
-            self._finish_displacement_covariance(moving.get('mask', fixed['mask'])[0], spacing,
-                                                 cfg_trainer.get('save_outputs', True))
-        if self._displacement_quantiles is not None:
-            self._finish_displacement_quantiles(moving.get('mask', fixed['mask'])[0], spacing,
-                                                cfg_trainer.get('save_outputs', True))
+        for r in recorders:
+            r.finish(fixed if r.takes == 'fixed' else moving.get('mask', fixed['mask'])[0], spacing,
+                     cfg_trainer.get('save_outputs', True))
 
         # speed test (trainer.py:467-476): 100 x [transition + nearest-neighbour warp of the segmentation]
         n_speed = 100

@@ -117,6 +117,20 @@ def test_random_cases_match_the_restatement(C, steps, shape, recipe, with_mask):
     check_summary(s, n, std, d, fa, mask)
 
 
+# 263 blocks of partials: threads 0 .. 6 of the second stage fold two blocks each, and V % 256 != 0; 270 400 voxels: more than
+# 1024 blocks x 256, so the first stage's grid-stride loop wraps, with a ragged tail.  The smallest shapes on either path.
+@pytest.mark.parametrize('shape', [(41, 40, 41), (65, 64, 65)])
+def test_summary_reduction_past_one_round_of_either_stage(shape):
+    records = draw_records('anisotropic', 3, shape, case_seed(3, 1, shape, 'anisotropic'))
+    dc = DisplacementCovariance(shape, DEV)
+    dc.record(torch.from_numpy(records).to(DEV).contiguous())
+    for mask in (case_mask(shape), None):
+        std, d, fa, summary = dc.finalize(None if mask is None else torch.from_numpy(mask).to(DEV))
+        print(summary)
+        assert summary['nonfinite_voxels'] == 0  # every masked voxel enters the float columns
+        check_summary(summary, 3, std.cpu().numpy(), d.cpu().numpy(), fa.cpu().numpy(), mask)
+
+
 def test_a_scale_of_its_own_and_the_covariance_tensor():
     shape = (9, 6, 70)
     records = draw_records('anisotropic', 6, shape, 31)

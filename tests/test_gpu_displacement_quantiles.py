@@ -135,6 +135,29 @@ def test_in_range_quantiles_are_within_a_bin_of_the_order_statistic(C, steps, sh
     assert np.array_equal(q8[1], q[0]) and np.array_equal(q8[3], q[1]) and np.array_equal(q8[6], q[2])
 
 
+# 263 blocks of partials: threads 0 .. 6 of the second stage fold two blocks each, and V % 256 != 0; 270 400 voxels: more than
+# 1024 blocks x 256, so the first stage's grid-stride loop wraps, with a ragged tail.  The smallest shapes on either path.
+@pytest.mark.parametrize('shape', [(41, 40, 41), (65, 64, 65)])
+def test_summary_reduction_past_one_round_of_either_stage(shape):
+    """the summary against the restatement of the DEVICE's stored maps and histogram, as check_outputs pins the reduction.
+    16 bins (29 MB of state at the larger shape) of 0.125 voxels reach 0.875 voxels either side of the centre; with noise of
+    0.75 voxels the restatement has about 86 % of the voxels in range, so no column of the summary is empty"""
+    records = draw_records(3, shape, case_seed(3, 1, shape, 16), noise=0.75)
+    dq = DisplacementQuantiles(shape, DEV, 16, BIN_WIDTH)
+    dq.record(torch.from_numpy(records).to(DEV).contiguous())
+    for mask in (case_mask(shape), None):
+        ref = quantiles_np(records, PROBS, bins=16, mask=mask)['summary']
+        assert 0 < 2 * ref['out_of_range_voxels'] <= ref['voxels'] and ref['clipped_samples'] > 0  # a condition on the inputs
+        q, ci, summary = dq.finalize(PROBS, None if mask is None else torch.from_numpy(mask).to(DEV))
+        want = summary_np(3, hist_np(dq), q.cpu().numpy(), ci.cpu().numpy(), mask)
+        print({key: (summary[key], want[key]) for key in INT_KEYS + FLOAT_KEYS})
+        for key in INT_KEYS:
+            assert summary[key] == want[key], (key, summary[key], want[key])
+        for key in FLOAT_KEYS:
+            g, w = summary[key], want[key]
+            assert (math.isnan(g) and math.isnan(w)) or abs(g - w) <= 1e-6 * abs(w), (key, g, w)
+
+
 def test_the_clipping_case():
     Cn, steps, shape, bins = CLIP_CASE
     n = Cn * steps

@@ -161,6 +161,28 @@ def test_two_update_sequences_and_two_finalize_calls_are_bit_identical():
     assert r1[3].dtype == torch.int64 and int(r1[3][0]) == int(mask.sum()) and r1[4].dtype == torch.float64
 
 
+# 263 blocks of partials: threads 0 .. 6 of the second stage fold two blocks each, and V % 256 != 0; 270 400 voxels: more than
+# 1024 blocks x 256, so the first stage's grid-stride loop wraps, with a ragged tail.  The smallest shapes on either path.
+@pytest.mark.parametrize('shape', [(41, 40, 41), (65, 64, 65)])
+def test_summary_reduction_past_one_round_of_either_stage(shape):
+    """the summary against the restatement of the DEVICE's stored maps, as check_against_restatement pins the reduction:
+    integers exactly, floats to 1e-6 relative, NaN where the restatement has NaN"""
+    records = draw_records('folding', 3, shape, case_seed(3, 1, shape, 'folding'))
+    jp = JacobianPosterior(shape, DEV)
+    jp.record(torch.from_numpy(records).to(DEV).contiguous())
+    folds = jp.folds.cpu().numpy()
+    for mask in (np.random.default_rng(shape[2]).random(shape) < 0.6, None):
+        fp, lm, ls, summary = jp.finalize(None if mask is None else torch.from_numpy(mask).to(DEV))
+        want = summary_np(folds, 3, fp.cpu().numpy(), lm.cpu().numpy(), ls.cpu().numpy(), mask)
+        print({key: (summary[key], want[key]) for key in INT_KEYS + FLOAT_KEYS})
+        assert 0 < want['folded_voxels'] and want['always_folded'] < want['voxels']  # every column has something to reduce
+        for key in INT_KEYS:
+            assert summary[key] == want[key], (key, summary[key], want[key])
+        for key in FLOAT_KEYS:
+            g, w = summary[key], want[key]
+            assert (math.isnan(g) and math.isnan(w)) or abs(g - w) <= 1e-6 * abs(w), (key, g, w)
+
+
 @pytest.mark.parametrize('recipe', RECIPES)
 def test_fold_count_agrees_with_the_per_sample_operator(recipe):
     shape = (17, 16, 33)
