@@ -16,6 +16,8 @@
 //             (correct for any displacement).  Which kernel does the work of a step is decided on the device.
 #include "kernels.h"
 
+#include <type_traits>
+
 namespace irs {
 
 #ifndef IRS_ETX
@@ -55,10 +57,14 @@ struct Lay3 {
     int em;
 };
 __host__ __device__ __forceinline__ Lay3 lay3(int aos, int64_t V) { return aos ? Lay3{1, 3} : Lay3{V, 1}; }
-template <int L>
-struct LayC {  // a layout bit set as a type: the marching tiles instantiate their body per layout
-    static constexpr int value = L;
-};
+
+// Launchers: a run-time choice becomes a template argument by handing it to a generic lambda as a type.
+template <int N>
+using Int = std::integral_constant<int, N>;
+template <class F>
+static void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{}); else f(std::false_type{});
+}
 
 __device__ __forceinline__ void atomic_max_nonneg(unsigned* addr, float v) {
     // non-negative floats order like their bit patterns
@@ -712,29 +718,27 @@ void launch_exp_step_bwd_lds(const float* G, const float* dk, float* gout, bool 
     }
     // the persistent grid is ONE resident set of workgroups (asked from the runtime once per variant): a grid that is not a
     // multiple of it leaves a partial last round in which most of the chip idles
-#define IRS_BWD(P, HH)                                                                                                           \
-    do {                                                                                                                         \
-        static int resident = 0;                                                                                                 \
-        if (!resident) {                                                                                                         \
-            int per_cu = 0, dev = 0, cus = 0;                                                                                    \
-            if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && \
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, exp_bwd_lds_kernel<P, HH>, kExpBlock, 0) == hipSuccess && per_cu > 0 && cus > 0) \
-                resident = per_cu * cus;                                                                                         \
-            else                                                                                                                 \
-                resident = kExpGridCap;                                                                                          \
-        }                                                                                                                        \
-        const dim3 g_((unsigned)(tz.total < resident ? tz.total : resident));                                                    \
-        hipLaunchKernelGGL((exp_bwd_lds_kernel<P, HH>), g_, dim3(kExpBlock), 0, st, G, dk, gout, vol, lin, sc, dmax, tz, gather_radius, gscale, lay, cmm, (const float*)boxes); \
-    } while (0)
+    auto launch = [&](auto P, auto HH) {
+        constexpr bool kP = decltype(P)::value;
+        constexpr int kH = decltype(HH)::value;
+        static int resident = 0;  // (one per instantiation)
+        if (!resident) {
+            int per_cu = 0, dev = 0, cus = 0;
+            if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+                hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, exp_bwd_lds_kernel<kP, kH>, kExpBlock, 0) == hipSuccess && per_cu > 0 && cus > 0)
+                resident = per_cu * cus;
+            else
+                resident = kExpGridCap;
+        }
+        const dim3 g_((unsigned)(tz.total < resident ? tz.total : resident));
+        hipLaunchKernelGGL((exp_bwd_lds_kernel<kP, kH>), g_, dim3(kExpBlock), 0, st, G, dk, gout, vol, lin, sc, dmax, tz, gather_radius, gscale, lay, cmm, (const float*)boxes);
+    };
     // With the gather variants in front (gather_radius >= 2) the staged box of d around the tile is of little use (sources
     // and taps are far away): H = 0 stages nothing (49 KB of accumulators instead of 111 KB of LDS -> three workgroups per CU)
     if (gather_radius >= 2 || global_knobs().lds_from == 2) halo = 0;
-    if (prescale_in) {
-        if (halo <= 0) IRS_BWD(true, 0); else if (halo <= 1) IRS_BWD(true, 1); else IRS_BWD(true, 2);
-    } else {
-        if (halo <= 0) IRS_BWD(false, 0); else if (halo <= 1) IRS_BWD(false, 1); else IRS_BWD(false, 2);
-    }
-#undef IRS_BWD
+    with_bool(prescale_in, [&](auto P) {
+        if (halo <= 0) launch(P, Int<0>{}); else if (halo <= 1) launch(P, Int<1>{}); else launch(P, Int<2>{});
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -773,57 +777,14 @@ constexpr int MTX = IRS_MTX, MTY = IRS_MTY, kMarchBlock = MTX * MTY;
 // The radius-1 adjoint only runs for max|d_k| < 1 (selected on the device from the exact bound): the eight corners of a voxel's
 // own sample then ALWAYS sit in the ring, and the global-memory fallback for taps that leave it is dead code -- which stays in
 // (1): compiled out (0) the kernel is 3 VGPRs smaller and 7 % SLOWER (219 against 204 us per launch, two same-box A/B runs).
-// Compile-time layouts in the adjoint (as in the forward step, where they removed a wait from the middle of the prefetch and gave
-// 5 %): measured 221 against 204 us per radius-1 launch (24 bytes of scratch at the 128-VGPR limit) -- 0
-#ifndef IRS_BWD_LAYC
-#define IRS_BWD_LAYC 0
-#endif
-#ifndef IRS_BWD_TAPS
-#define IRS_BWD_TAPS 0  // 1: the eight corner reads of the own term as single ds_read_b64 / ds_read_b32 (volatile, as IRS_FWD_TAPS); A/B in round 5
-#endif
-#ifndef IRS_FWD_REC16
-#define IRS_FWD_REC16 0
-#endif
-#ifndef IRS_FWD_FMA
-// The 24 tap products of a sample accumulated with fused multiply-adds (round 5).  The COORDINATE arithmetic -- positions, cell
-// indices, weights: what decides which cell a sample falls into and what the reference's gradient is compared against -- keeps
-// ATen's order (common.h: axis_tap); the accumulation a += t * w rounds once instead of twice per tap.  Until round 4 it was kept
-// FMA-free for bit-identity with ATen's CPU sampler; measured now that the LDS is no longer what the kernel waits for: 87.0-88.1
-// against 93.5-94.8 us per step at 256^3, 4.296-4.331 against 4.385-4.404 ms per transition, 2 spilled VGPRs instead of 10 --
-// and every parity test with unchanged margins (256^3: 1.037e-4 voxels against the oracle, as before; the 32^3 fixtures go from
-// exactly 0 to 1.6e-6 of a tolerance of 1e-4): profiles/r05_fwdfma_ab.txt, profiles/parity_report_r05.json.
-#define IRS_FWD_FMA 1
-#endif
-#ifndef IRS_FWD_BUFLOAD
-#define IRS_FWD_BUFLOAD 0  // marching forward step: staging loads as buffer loads; A/B in round 5
-#endif
-#ifndef IRS_BWD_BUFLOAD
-#define IRS_BWD_BUFLOAD 0  // marching adjoint: staging loads as buffer loads (descriptor + 32-bit lane offset); A/B in round 5
-#endif
-#ifndef IRS_BWD_R1_FALLBACK
-#define IRS_BWD_R1_FALLBACK 1
-#endif
-#ifndef IRS_BWD_PEEL
-// radius-1 adjoint: run-in plane steps update only the accumulators whose output plane is inside the segment (6 of the 30
-// accumulator updates of an 8-plane segment land outside it).  Built in round 5 as asked (per-mask instantiations of the gather
-// behind a wave-uniform dispatch; the full gather, commit and own-term blocks unchanged instruction for instruction,
-// tools/debug/isa_block_diff.py; chains bit-identical) and measured SLOWER on one box, three / two alternating repetitions:
-// 128^3 36.6-37.2 against 35.5-35.8 us per launch, 256^3 223-229 against 215-218 (profiles/r05_peel_ab.txt) -- the kernel grows from
-// 2 687 to 4 363 instructions and the dispatch sits in front of every gather.  Off.
-#define IRS_BWD_PEEL 0
-#endif
-// hat of (r + c) for a relative position r and a compile-time integer offset c.
-template <int R>
-__device__ __forceinline__ float rel_hat(float r, int c);
-
-// hat function max(0, 1 - |t|).  v_med3_f32 folds into the clamp output modifier of the subtraction (one VALU op);
-// HIP's __saturatef compiles to two compares and two selects.
+// (Tried on these kernels and not kept -- compile-time layouts in the adjoint, a run-in peel of its gather, single reads of its
+// own-term corners, buffer loads for the staging, 16-byte ring records in the forward step: DESIGN.md, "Round-5 measurements and
+// experiments".)
+//
 // load p[byte_off / 4] with the address written as (uniform 64-bit base) + (32-bit lane byte offset).  Planes are < 4 GiB, so a
 // 32-bit byte offset always suffices.  (What the compiler makes of it in the marching kernels is NOT the global_load saddr form the
 // expression invites: the sum is formed in the block in front of the layout branch, so each staging load costs one v_lshl_add_u64
-// and the lane offsets live in 64-bit VGPR pairs -- 146 of the adjoint's 148 global loads, as the round-4 review found in the ISA.
-// Buffer loads -- descriptor in SGPRs, 32-bit lane offset: IRS_BWD_BUFLOAD / IRS_FWD_BUFLOAD -- remove both (122 instead of 128
-// VGPRs in the adjoint, 28 VALU instructions fewer in its loop) and measured no faster: profiles/r05_bufload_ab.txt.)
+// and the lane offsets live in 64-bit VGPR pairs -- 146 of the adjoint's 148 global loads, as the round-4 review found in the ISA.)
 __device__ __forceinline__ float ld_off(const float* __restrict__ base, unsigned byte_off) {
     return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
 }
@@ -840,25 +801,12 @@ __device__ __forceinline__ void st3_off(float* __restrict__ base, unsigned byte_
 __device__ __forceinline__ void st_off(float* __restrict__ base, unsigned byte_off, float v) {
     *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte_off) = v;
 }
-// buffer loads: a raw descriptor over "everything from `base` on" (in SGPRs: the base is wave-uniform), 32-bit lane byte offset
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const float* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)0xFFFFFFFFu, 0x00020000);
-}
-__device__ __forceinline__ float buf_ld1(const float* __restrict__ base, unsigned byte_off) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(buf_rsrc(base), (int)byte_off, 0, 0));
-}
-__device__ __forceinline__ F3 buf_ld3(const float* __restrict__ base, unsigned byte_off) {
-    typedef unsigned U3 __attribute__((ext_vector_type(3)));
-    const U3 v = __builtin_amdgcn_raw_buffer_load_b96(buf_rsrc(base), (int)byte_off, 0, 0);
-    F3 f;
-    f.x = __uint_as_float(v.x);
-    f.y = __uint_as_float(v.y);
-    f.z = __uint_as_float(v.z);
-    return f;
-}
+// hat function max(0, 1 - |t|).  v_med3_f32 folds into the clamp output modifier of the subtraction (one VALU op);
+// HIP's __saturatef compiles to two compares and two selects.
 __device__ __forceinline__ float clamp01(float t) { return __builtin_amdgcn_fmed3f(t, 0.0f, 1.0f); }
 __device__ __forceinline__ float hat01(float t) { return clamp01(1.0f - fabsf(t)); }
 
+// hat of (r + c) for a relative position r and a compile-time integer offset c.
 template <int R>
 __device__ __forceinline__ float rel_hat(float r, int c) {
     if (R == 1 && c == 1) return clamp01(-r);
@@ -973,10 +921,10 @@ __device__ __forceinline__ void exp_bwd_march_tile(const float* __restrict__ G, 
     seg_range(vol, seg, seg_len, z0, z1);
     const int64_t V = vol.V;
     const int64_t cb = (int64_t)chain * 3 * V;
-    auto run = [&](auto LC) {  // layouts as compile-time constants (see the forward tile), or (< 0) the run-time ones
-    constexpr int LAYC = decltype(LC)::value;
-    const int lay_ = LAYC < 0 ? lay : LAYC;
-    const Lay3 LD = lay3(lay_ & 1, V), LG = lay3(lay_ & 2, V), LO = lay3(lay_ & 4, V);
+    // (The body stays inside a lambda, the shape it had when compile-time layouts were tried on it -- slower: DESIGN.md, "Round-5
+    // measurements and experiments" -- : written straight into the function the same statements compile to another schedule.)
+    auto run = [&]() {
+    const Lay3 LD = lay3(lay & 1, V), LG = lay3(lay & 2, V), LO = lay3(lay & 4, V);
     if (R == 2 && hs > R) {  // the any-radius kernel was not launched for this step and the bound outgrew the ring
         const int gx = ox + (int)(threadIdx.x % MTX), gy = oy + (int)(threadIdx.x / MTX);
         if (gx < vol.W && gy < vol.H)
@@ -1025,38 +973,6 @@ __device__ __forceinline__ void exp_bwd_march_tile(const float* __restrict__ G, 
         const float* __restrict__ p3_ = Gx_ + zo * LG.em;
         const float* __restrict__ p4_ = Gy_ + zo * LG.em;
         const float* __restrict__ p5_ = Gz_ + zo * LG.em;
-        if (IRS_BWD_BUFLOAD && R == 1) {
-        // the staging loads as BUFFER loads: descriptor of the plane in SGPRs, 32-bit lane offset -- no 64-bit VALU address arithmetic
-        // and no 64-bit lane-offset pairs (the global_load form cost one v_lshl_add_u64 per load and six VGPR pairs: the address is
-        // formed in the block in front of the layout branch, so instruction selection never saw base + offset at the load)
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            if (sxy[it] < 0) continue;
-            const unsigned g = (unsigned)sxy[it] * 4u, gd = g * (unsigned)LD.em, gg = g * (unsigned)LG.em;
-            if (LD.em == 3) {
-                const F3 v = buf_ld3(p0_, gd);
-                pre[it][0] = v.x;
-                pre[it][1] = v.y;
-                pre[it][2] = v.z;
-            } else {
-                pre[it][0] = buf_ld1(p0_, gd);
-                pre[it][1] = buf_ld1(p1_, gd);
-                pre[it][2] = buf_ld1(p2_, gd);
-            }
-            if (LG.em == 3) {
-                const F3 v = buf_ld3(p3_, gg);
-                pre[it][3] = v.x;
-                pre[it][4] = v.y;
-                pre[it][5] = v.z;
-            } else {
-                pre[it][3] = buf_ld1(p3_, gg);
-                pre[it][4] = buf_ld1(p4_, gg);
-                pre[it][5] = buf_ld1(p5_, gg);
-            }
-            if (gs_) pgs[it] = buf_ld1(gs_ + zo, g);
-        }
-        return;
-        }
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             if (sxy[it] < 0) continue;
@@ -1171,13 +1087,9 @@ __device__ __forceinline__ void exp_bwd_march_tile(const float* __restrict__ G, 
                 own_zg[0] = q_zg[co];
                 own_g[0] = q_g[co];
             }
-            // ---- contributions of source plane s to output planes s-R .. s+R
-            // MK: which of those output planes lie inside the segment (bit oo + R).  The run-in steps of a segment reach one or
-            // two of them only, and on a small volume or a thin slab the run-in is a quarter of all plane steps (8-plane
-            // segments: 10 steps, 6 of their 30 accumulator updates land outside) -- those steps run an instantiation that leaves
-            // the other accumulators alone (IRS_BWD_PEEL; same operations in the same order for every plane that is stored)
-            auto gather = [&](auto MK) {
-                constexpr int MASK = decltype(MK)::value;
+            // ---- contributions of source plane s to output planes s-R .. s+R (all of them, also in the run-in steps of a segment
+            // where some lie outside it: a peeled run-in measured slower, DESIGN.md "Round-5 measurements and experiments")
+            auto gather = [&]() {
 #pragma unroll IRS_GATHER_UNROLL_Y
                 for (int dy = 0; dy <= 2 * R; ++dy)
 #pragma unroll
@@ -1196,7 +1108,6 @@ __device__ __forceinline__ void exp_bwd_march_tile(const float* __restrict__ G, 
                         const float2 rzg = q_zg[ri], g01 = q_g[ri];
 #pragma unroll
                         for (int oo = -R; oo <= R; ++oo) {
-                            if (!((MASK >> (oo + R)) & 1)) continue;
                             const int a = (PH + oo + NP) % NP;  // accumulator of output plane s + oo (static index)
                             const float w = hxy * rel_hat<R>(rzg.x, -oo);
                             acc01[a].x = fmaf(w, g01.x, acc01[a].x);
@@ -1205,20 +1116,7 @@ __device__ __forceinline__ void exp_bwd_march_tile(const float* __restrict__ G, 
                         }
                     }
             };
-            if (s >= 0 && s < vol.D && col_in) {
-                constexpr int ALL = (1 << NP) - 1;
-                if (R == 1 && IRS_BWD_PEEL) {
-                    const int m = (s - 1 >= z0 && s - 1 < z1 ? 1 : 0) | (s >= z0 && s < z1 ? 2 : 0) | (s + 1 >= z0 && s + 1 < z1 ? 4 : 0);  // wave-uniform
-                    if (m == ALL) gather(LayC<ALL>{});
-                    else if (m == 4) gather(LayC<4>{});
-                    else if (m == 6) gather(LayC<6>{});
-                    else if (m == 3) gather(LayC<3>{});
-                    else if (m == 1) gather(LayC<1>{});
-                    else gather(LayC<ALL>{});  // (segments of one or two planes: 2, 5 never occur, a lone 2 is rare)
-                } else {
-                    gather(LayC<ALL>{});
-                }
-            }
+            if (s >= 0 && s < vol.D && col_in) gather();
             IRS_BT(5);
             // ---- output plane zo = s - R is complete
             {
@@ -1245,8 +1143,7 @@ __device__ __forceinline__ void exp_bwd_march_tile(const float* __restrict__ G, 
                     // the "+1" corners are read unconditionally: where ATen clamps them (i0 = n-1) their weight is exactly 0 and
                     // the ring holds a finite halo value there
                     const int bx0 = lx + R + rx0, by0 = ly + R + ry0;
-                    const bool in_ring = (R == 1 && !IRS_BWD_R1_FALLBACK) ||
-                                         ((unsigned)bx0 < (unsigned)(PX - 1) && (unsigned)by0 < (unsigned)(M::PY - 1) && rel >= -R && rel < R);
+                    const bool in_ring = (unsigned)bx0 < (unsigned)(PX - 1) && (unsigned)by0 < (unsigned)(M::PY - 1) && rel >= -R && rel < R;
                     float dot[2][2][2];
                     auto ring_dots = [&]() {
                         int sl0 = ((a - R + NP) % NP) * PN, sl1 = ((a - R + 1 + NP) % NP) * PN;  // rel == -R
@@ -1263,15 +1160,8 @@ __device__ __forceinline__ void exp_bwd_march_tile(const float* __restrict__ G, 
                             for (int cy = 0; cy < 2; ++cy)
 #pragma unroll
                                 for (int cx = 0; cx < 2; ++cx) {
-#if IRS_BWD_TAPS == 1
-                                    typedef float VF2 __attribute__((ext_vector_type(2)));
-                                    const VF2 tv = *(const volatile __attribute__((address_space(3))) VF2*)(&q_d[bs + cy * PX + cx]);
-                                    const float2 v01 = make_float2(tv.x, tv.y);
-                                    const float vz = *(const volatile __attribute__((address_space(3))) float*)(&q_dz[bs + cy * PX + cx]);
-#else
                                     const float2 v01 = q_d[bs + cy * PX + cx];
                                     const float vz = q_dz[bs + cy * PX + cx];
-#endif
                                     dot[cz][cy][cx] = fmaf(vz, G2, fmaf(v01.y, G1, v01.x * G0));
                                 }
                         }
@@ -1329,17 +1219,7 @@ __device__ __forceinline__ void exp_bwd_march_tile(const float* __restrict__ G, 
         }
     }
     };  // run
-#if IRS_BWD_LAYC
-    switch (lay & 7) {  // the combinations the library produces (ctx.h: bwd_lay; 0 = the planar operator API)
-        case 0: run(LayC<0>{}); break;
-        case 2: run(LayC<2>{}); break;
-        case 5: run(LayC<5>{}); break;
-        case 7: run(LayC<7>{}); break;
-        default: run(LayC<-1>{}); break;
-    }
-#else
-    run(LayC<-1>{});
-#endif
+    run();
 }
 
 // One tile per workgroup for the common radius-1 variant (XCD-aware order); the rarely selected variants are launched on a
@@ -1384,10 +1264,14 @@ void launch_exp_step_bwd_march(const float* G, const float* dk, float* gout, boo
         log_launch("exp_bwd_march_kernel<R=1>", MTX, MTY, total, kMarchBlock, seg_len, 2, vol.nz + vol.nzb, C,
                    resident_blocks((const void*)exp_bwd_march_kernel<false, 1>, kMarchBlock, &cache_l));
     }
-#define IRS_BWM(P, RR, LO, GRID, SEG, NSEG, TILES, TOTAL) hipLaunchKernelGGL((exp_bwd_march_kernel<P, RR>), dim3(GRID), dim3(kMarchBlock), 0, st, G, dk, gout, vol, lin, sc, dmax, SEG, NSEG, LO, r2_owns_rest ? 1 : 0, (GRID) == (TOTAL) ? swz_run : 0, TILES, gscale, lay)
+    // a chain whose bound asks for a ring radius in (r_lo, RR] is this launch's; a grid of all tiles is placed XCD-aware
+    auto launch = [&](auto P, auto RR, int r_lo, int grid, int seg, int nseg_, dim3 tiles_, int total_) {
+        hipLaunchKernelGGL((exp_bwd_march_kernel<decltype(P)::value, decltype(RR)::value>), dim3(grid), dim3(kMarchBlock), 0, st, G, dk, gout, vol,
+                           lin, sc, dmax, seg, nseg_, r_lo, r2_owns_rest ? 1 : 0, grid == total_ ? swz_run : 0, tiles_, gscale, lay);
+    };
     // the radius-1 kernel first (the one the roofline is quoted on: `after_primary` brackets exactly its launch), then the
     // rarely selected radius-2 variant on the small persistent grid
-    if (prescale_in) IRS_BWM(true, 1, 0, total, seg_len, nseg, tiles, total); else IRS_BWM(false, 1, 0, total, seg_len, nseg, tiles, total);
+    with_bool(prescale_in, [&](auto P) { launch(P, Int<1>{}, 0, total, seg_len, nseg, tiles, total); });
     if (after_primary) (void)hipEventRecord(after_primary, st);
     if (max_radius >= 2) {
         // its own segments: the variant walks its tiles on a persistent grid of what the chip holds of IT (three workgroups per CU,
@@ -1400,9 +1284,8 @@ void launch_exp_step_bwd_march(const float* G, const float* dk, float* gout, boo
         const dim3 tiles2(tiles.x, tiles.y, (unsigned)(nseg2 * C));
         const int total2 = (int)(tiles2.x * tiles2.y * tiles2.z);
         const int rare = total2 < kRareGrid ? total2 : kRareGrid;
-        if (prescale_in) IRS_BWM(true, 2, 1, rare, seg2, nseg2, tiles2, total2); else IRS_BWM(false, 2, 1, rare, seg2, nseg2, tiles2, total2);
+        with_bool(prescale_in, [&](auto P) { launch(P, Int<2>{}, 1, rare, seg2, nseg2, tiles2, total2); });
     }
-#undef IRS_BWM
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1425,16 +1308,21 @@ void launch_exp_step_bwd_march(const float* G, const float* dk, float* gout, boo
 #ifndef IRS_FWD_WAVES
 #define IRS_FWD_WAVES 4
 #endif
-#ifndef IRS_FWD_TAPS
-// How the eight corner taps of a sample leave the LDS ring.  0: plain reads -- the compiler pairs the cx = 0 / 1 corners into
-// ds_read2_b64 + ds_read2_b32.  1 (round 5): every corner its own ds_read_b64 + ds_read_b32, through VOLATILE LDS pointers (the
-// load / store optimiser leaves volatile accesses unpaired; the compiler still counts and schedules them).  A ds_read2_b64 holds the
+// How the eight corner taps of a sample leave the LDS ring: every corner its own ds_read_b64 + ds_read_b32, through VOLATILE LDS
+// pointers (the load / store optimiser leaves volatile accesses unpaired; the compiler still counts and schedules them).  Plain
+// reads are paired by the compiler into ds_read2_b64 + ds_read2_b32 for the cx = 0 / 1 corners, and a ds_read2_b64 holds the
 // LDS for 8 cycles where two ds_read_b64 take 4, and is banked per 16 lanes (MI355X_MICROARCH.md, LDS table): with per-lane cell
 // shifts the isolated tap pattern costs 99 against 69 clocks per wave tap-set (tools/probes/lds_tap_probe.hip, white shifts; 71
 // against 60 with runs of four lanes), and this kernel 95.8 against 104.5 us per launch at 256^3 on one box (profiles/r05_fwd_taps_ab.txt).
 // Same values, same products, same order of the additions: chains bit-identical (tools/debug/chain_bits.py).
-#define IRS_FWD_TAPS 1
-#endif
+//
+// The 24 tap products of a sample are accumulated with fused multiply-adds.  The COORDINATE arithmetic -- positions, cell
+// indices, weights: what decides which cell a sample falls into and what the reference's gradient is compared against -- keeps
+// ATen's order (common.h: axis_tap); the accumulation a += t * w rounds once instead of twice per tap.  Until round 4 it was kept
+// FMA-free for bit-identity with ATen's CPU sampler; measured once the LDS was no longer what the kernel waits for: 87.0-88.1
+// against 93.5-94.8 us per step at 256^3, 4.296-4.331 against 4.385-4.404 ms per transition, 2 spilled VGPRs instead of 10 --
+// and every parity test with unchanged margins (256^3: 1.037e-4 voxels against the oracle, as before; the 32^3 fixtures go from
+// exactly 0 to 1.6e-6 of a tolerance of 1e-4): profiles/r05_fwdfma_ab.txt, profiles/parity_report_r05.json.
 // FROWS is a template parameter of the radius-1 kernel: two rows per thread (256 threads) where the launch fills the chip; ONE row
 // per thread (512 threads, 8 waves per tile) on small volumes and thin slabs, where a launch has a workgroup or two per CU and
 // twice the waves per tile hide more of a plane step's latency (128^3: 22.9 against 24.7 us per step; at 256^3 it loses, 142
@@ -1478,16 +1366,9 @@ __device__ __forceinline__ void exp_fwd_march_tile(const float* __restrict__ din
     constexpr int PX = M::PX, PN = M::PN, NIT = M::NIT, PITCH = M::PITCH, PNP = M::PNP, kFwdBlock = M::kFwdBlock;
     // ring of 2R+2 slots: one more than a sample can reach, so that the commit of the next source plane never overwrites
     // a plane another wavefront is still sampling -> ONE barrier per plane instead of two
-    // (IRS_FWD_REC16, A/B of round 5: 16-byte records (d0, d1, d2, -), one ds_read_b128 per tap -- the layout the tap probe ranks
-    // first in isolation.  At 16 bytes per record only 2R+1 slots fit the 40 KB that four workgroups per CU allow, so the one-barrier
-    // trick above goes: a second barrier per plane step.  Radius-1 kernel with one plane of prefetch only.)
-    // (IRS_FWD_REC16 = 2: also the one-row variant of small launches -- two workgroups of 512 threads per CU either way, so it keeps
-    // its spare slot and its single barrier at 51 KB)
-    constexpr bool REC16 = R == 1 && ((IRS_FWD_REC16 >= 1 && PF == 1) || IRS_FWD_REC16 >= 2);
-    constexpr int NS = REC16 && PF == 1 ? M::NP : M::NP + 1;
-    __shared__ float2 r_xy[REC16 ? 1 : NS * PNP];  // (d0, d1): one ds_read_b64 per tap
-    __shared__ float r_z[REC16 ? 1 : NS * PNP];    // d2
-    __shared__ float4 r_q[REC16 ? NS * PNP : 1];
+    constexpr int NS = M::NP + 1;
+    __shared__ float2 r_xy[NS * PNP];  // (d0, d1): one ds_read_b64 per tap
+    __shared__ float r_z[NS * PNP];    // d2
     __shared__ float red[3 * (kFwdBlock / kWave)];
     const int tile_ = xcd_swizzle_runs(tile_id, (int)(tiles.x * tiles.y * tiles.z), swz_run);
     const int tbx = tile_ % tiles.x, tby = (tile_ / tiles.x) % tiles.y, tbz = tile_ / (tiles.x * tiles.y);
@@ -1536,18 +1417,7 @@ __device__ __forceinline__ void exp_fwd_march_tile(const float* __restrict__ din
         for (int it = 0; it < NIT; ++it) {
             if (sxy[it] < 0) continue;
             const unsigned g = (unsigned)sxy[it] * 4u * (unsigned)LD.em;
-            if (IRS_FWD_BUFLOAD) {  // buffer loads: plane descriptor in SGPRs + 32-bit lane offset (see the adjoint's staging)
-                if (LD.em == 3) {
-                    const F3 v = buf_ld3(px_, g);
-                    pre[it][0] = v.x;
-                    pre[it][1] = v.y;
-                    pre[it][2] = v.z;
-                } else {
-                    pre[it][0] = buf_ld1(px_, g);
-                    pre[it][1] = buf_ld1(py_, g);
-                    pre[it][2] = buf_ld1(pz_, g);
-                }
-            } else if (LD.em == 3) {
+            if (LD.em == 3) {
                 const F3 v = ld3_off(px_, g);
                 pre[it][0] = v.x;
                 pre[it][1] = v.y;
@@ -1564,12 +1434,6 @@ __device__ __forceinline__ void exp_fwd_march_tile(const float* __restrict__ din
         for (int it = 0; it < NIT; ++it) {
             if (sxy[it] < 0) continue;
             const int i = slot * PNP + sld[it];
-            if (REC16) {
-                r_q[i] = make_float4(PRESCALE ? prescale(pre[it][0], sc.nm1[0], sc.rnm1[0], sc.inv_pow) : pre[it][0],
-                                     PRESCALE ? prescale(pre[it][1], sc.nm1[1], sc.rnm1[1], sc.inv_pow) : pre[it][1],
-                                     PRESCALE ? prescale(pre[it][2], sc.nm1[2], sc.rnm1[2], sc.inv_pow) : pre[it][2], 0.0f);
-                continue;
-            }
             r_xy[i] = make_float2(PRESCALE ? prescale(pre[it][0], sc.nm1[0], sc.rnm1[0], sc.inv_pow) : pre[it][0],
                                   PRESCALE ? prescale(pre[it][1], sc.nm1[1], sc.rnm1[1], sc.inv_pow) : pre[it][1]);
             r_z[i] = PRESCALE ? prescale(pre[it][2], sc.nm1[2], sc.rnm1[2], sc.inv_pow) : pre[it][2];
@@ -1629,19 +1493,8 @@ __device__ __forceinline__ void exp_fwd_march_tile(const float* __restrict__ din
                 const float liny = liny_[j];
                 const int a = (PH - R + NS) % NS;  // slot of plane zo (compile-time)
                 const int ci = a * PNP + (ly + R) * PITCH + (lx + R);
-                float d0, d1, d2;
-                if (REC16) {
-                    typedef float VF4 __attribute__((ext_vector_type(4)));  // (volatile: a plain read of three components becomes a ds_read_b96, 8 LDS cycles)
-                    const VF4 c4 = *(const volatile __attribute__((address_space(3))) VF4*)(&r_q[ci]);
-                    d0 = c4.x;
-                    d1 = c4.y;
-                    d2 = c4.z;
-                } else {
-                    const float2 dxy = r_xy[ci];
-                    d0 = dxy.x;
-                    d1 = dxy.y;
-                    d2 = r_z[ci];
-                }
+                const float2 dxy = r_xy[ci];
+                const float d0 = dxy.x, d1 = dxy.y, d2 = r_z[ci];
                 const AxisTap tx = axis_tap(__fadd_rn(linx, d0), vol.W);
                 const AxisTap ty = axis_tap(__fadd_rn(liny, d1), vol.H);
                 const AxisTap tz = axis_tap(__fadd_rn(linz, d2), vol.D);
@@ -1670,33 +1523,12 @@ __device__ __forceinline__ void exp_fwd_march_tile(const float* __restrict__ din
 #pragma unroll
                             for (int cx = 0; cx < 2; ++cx) {
                                 const float w = __fmul_rn(wxy[cy][cx], cz ? tz.w1 : tz.w0);
-                                float2 t2;
-                                float t1;
-                                if (REC16) {
-                                    typedef float VF4 __attribute__((ext_vector_type(4)));
-                                    const VF4 tv = *(const volatile __attribute__((address_space(3))) VF4*)(&r_q[bs + cy * PITCH + cx]);
-                                    t2 = make_float2(tv.x, tv.y);
-                                    t1 = tv.z;
-                                } else {
-#if IRS_FWD_TAPS == 1
-                                    typedef float VF2 __attribute__((ext_vector_type(2)));
-                                    const VF2 tv = *(const volatile __attribute__((address_space(3))) VF2*)(&r_xy[bs + cy * PITCH + cx]);
-                                    t2 = make_float2(tv.x, tv.y);
-                                    t1 = *(const volatile __attribute__((address_space(3))) float*)(&r_z[bs + cy * PITCH + cx]);
-#else
-                                    t2 = r_xy[bs + cy * PITCH + cx];
-                                    t1 = r_z[bs + cy * PITCH + cx];
-#endif
-                                }
-#if IRS_FWD_FMA
-                                a0 = fmaf(t2.x, w, a0);
-                                a1 = fmaf(t2.y, w, a1);
+                                typedef float VF2 __attribute__((ext_vector_type(2)));  // single, unpaired reads: see the comment above MarchF
+                                const VF2 tv = *(const volatile __attribute__((address_space(3))) VF2*)(&r_xy[bs + cy * PITCH + cx]);
+                                const float t1 = *(const volatile __attribute__((address_space(3))) float*)(&r_z[bs + cy * PITCH + cx]);
+                                a0 = fmaf(tv.x, w, a0);
+                                a1 = fmaf(tv.y, w, a1);
                                 a2 = fmaf(t1, w, a2);
-#else
-                                a0 = __fadd_rn(a0, __fmul_rn(t2.x, w));
-                                a1 = __fadd_rn(a1, __fmul_rn(t2.y, w));
-                                a2 = __fadd_rn(a2, __fmul_rn(t1, w));
-#endif
                             }
                     }
                 };
@@ -1716,15 +1548,9 @@ __device__ __forceinline__ void exp_fwd_march_tile(const float* __restrict__ din
                             for (int cx = 0; cx < 2; ++cx) {
                                 const float w = __fmul_rn(__fmul_rn(cx ? tx.w1 : tx.w0, cy ? ty.w1 : ty.w0), cz ? tz.w1 : tz.w0);
                                 const int64_t idx = (((int64_t)(cz ? tz.i1 : tz.i0) * vol.H + (cy ? ty.i1 : ty.i0)) * vol.W + (cx ? tx.i1 : tx.i0)) * LD.em;
-#if IRS_FWD_FMA
                                 a0 = fmaf(ldp<PRESCALE>(dx_, idx, sc.nm1[0], sc.rnm1[0], sc.inv_pow), w, a0);
                                 a1 = fmaf(ldp<PRESCALE>(dy_, idx, sc.nm1[1], sc.rnm1[1], sc.inv_pow), w, a1);
                                 a2 = fmaf(ldp<PRESCALE>(dz_, idx, sc.nm1[2], sc.rnm1[2], sc.inv_pow), w, a2);
-#else
-                                a0 = __fadd_rn(a0, __fmul_rn(ldp<PRESCALE>(dx_, idx, sc.nm1[0], sc.rnm1[0], sc.inv_pow), w));
-                                a1 = __fadd_rn(a1, __fmul_rn(ldp<PRESCALE>(dy_, idx, sc.nm1[1], sc.rnm1[1], sc.inv_pow), w));
-                                a2 = __fadd_rn(a2, __fmul_rn(ldp<PRESCALE>(dz_, idx, sc.nm1[2], sc.rnm1[2], sc.inv_pow), w));
-#endif
                             }
                 }
                 const int64_t pl = (int64_t)zo * vol.H * vol.W * LO.em;
@@ -1746,7 +1572,6 @@ __device__ __forceinline__ void exp_fwd_march_tile(const float* __restrict__ din
             IRS_TR(5);
             ++trace_it;
 #endif
-            if (NS == M::NP) __syncthreads();  // (a ring without the spare slot: the next commit overwrites the oldest plane of this step)
         }
     }
 #ifdef IRS_FWD_TRACE
@@ -1782,10 +1607,10 @@ __device__ __forceinline__ void exp_fwd_march_tile(const float* __restrict__ din
     }
     };  // run
     switch (lay & 5) {
-        case 0: run(LayC<0>{}); break;
-        case 1: run(LayC<1>{}); break;
-        case 4: run(LayC<4>{}); break;
-        default: run(LayC<5>{}); break;
+        case 0: run(Int<0>{}); break;
+        case 1: run(Int<1>{}); break;
+        case 4: run(Int<4>{}); break;
+        default: run(Int<5>{}); break;
     }
 }
 
@@ -1805,242 +1630,8 @@ __global__ __launch_bounds__(FTX * FTY / FROWS, R == 1 ? IRS_FWD_WAVES : 1) void
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// forward step of SMALL launches, TWO planes per marching step (round 5, late).  The one-row-per-thread kernel above pays its
-// per-step fixed work -- barrier, loop, the wait for the newest loads, the z coordinate -- once per plane (0.5 of the 1.9 us of a
-// plane step at 128^3, profiles/r05_phase_trace_128.txt); here a step commits planes s and s + 1, passes ONE barrier and samples
-// the output planes s - 1 and s.  Radius 1, one row per thread (512 threads), ring of SIX slots (the planes s - 2 .. s + 1 being
-// sampled and the two the next step commits before its barrier: 58 KB, two workgroups per CU as before), the loads of the next
-// step's two planes in flight during the sampling.  The arithmetic of an output -- taps, weights, order of the FMAs -- is the
-// one-plane kernel's: chains bit-identical (tools/debug/chain_bits.py).
-// MEASURED (profiles/r05_fwd_z2_ab.txt): 0.835-0.839 against 0.842-0.845 ms per transition at 128^3 (-0.7 %), 0.678-0.680 against
-// 0.680-0.681 with two chains, flat at 96^3 / 64^3 and on slab ranks of 4 / 8 -- the per-step fixed work is not what the small
-// forward step loses to; what remains per row is the staging (660 halo elements on 512 threads: two passes, the second 29 % full)
-// and the sampling itself.  Below the round's 1 % line: built, kept behind `fwd_z2`, OFF.
-// (A second form staged the halo planes of both source planes as ONE list -- three passes of the 512 threads, 86 % of the lanes,
-// instead of four -- : digests equal again, 0.836-0.838 against 0.835-0.838 ms, no gain at all; not kept.)
-// ------------------------------------------------------------------------------------------------
-template <bool PRESCALE>
-__device__ __forceinline__ void exp_fwd_march_tile_z2(const float* __restrict__ din, float* __restrict__ dout, const Vol vol,
-                                                      const Lin lin, const Scale3L sc, const unsigned* __restrict__ dmax_in,
-                                                      unsigned* __restrict__ dmax_out, const int seg_len, const int nseg,
-                                                      const int h_lo, const int h_hi, const int swz_run, const int tile_id,
-                                                      const dim3 tiles, const int lay) {
-    constexpr int R = 1;
-    using M = MarchF<R, 1>;
-    constexpr int PX = M::PX, PN = M::PN, NIT = M::NIT, PITCH = M::PITCH, PNP = M::PNP, kFwdBlock = M::kFwdBlock;
-    constexpr int NS = 6;
-    __shared__ float2 r_xy[NS * PNP];  // (d0, d1)
-    __shared__ float r_z[NS * PNP];    // d2
-    __shared__ float red[3 * (kFwdBlock / kWave)];
-    const int tile_ = xcd_swizzle_runs(tile_id, (int)(tiles.x * tiles.y * tiles.z), swz_run);
-    const int tbx = tile_ % tiles.x, tby = (tile_ / tiles.x) % tiles.y, tbz = tile_ / (tiles.x * tiles.y);
-    const int chain = tbz / nseg, seg = tbz % nseg;
-    if (dmax_in) {
-        const int need = max(max((int)ceilf(__uint_as_float(dmax_in[chain * 4 + 0])), (int)ceilf(__uint_as_float(dmax_in[chain * 4 + 1]))),
-                             (int)ceilf(__uint_as_float(dmax_in[chain * 4 + 2])));
-        if (need <= h_lo || need > h_hi) return;
-    }
-    const int ox = tbx * FTX, oy = tby * FTY;
-    int z0, z1;
-    seg_range(vol, seg, seg_len, z0, z1);
-    const int64_t V = vol.V;
-    const int64_t cb = (int64_t)chain * 3 * V;
-    auto run = [&](auto LC) {  // layouts as compile-time constants (see exp_fwd_march_tile)
-    constexpr int LAYC = decltype(LC)::value;
-    const Lay3 LD = lay3(LAYC & 1, V), LO = lay3(LAYC & 4, V);
-    const float* __restrict__ dx_ = din + cb;
-    const float* __restrict__ dy_ = dx_ + LD.cs;
-    const float* __restrict__ dz_ = dy_ + LD.cs;
-    float* __restrict__ o = dout + cb;
-    const int lx = threadIdx.x % FTX, ly = threadIdx.x / FTX;
-    const int x = ox + lx, y = oy + ly;
-    const bool live = x < vol.W && y < vol.H;
-    const float linx = x < vol.W ? lin.x[x] : 0.0f;
-    const float liny = lin.y[min(y, vol.H - 1)];
-
-    int sxy[NIT], sld[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int i = threadIdx.x + it * kFwdBlock;
-        const int px = i % PX, py = i / PX;
-        const int cx = min(max(ox - R + px, 0), vol.W - 1), cy = min(max(oy - R + py, 0), vol.H - 1);
-        sxy[it] = i < PN ? cy * vol.W + cx : -1;
-        sld[it] = py * PITCH + px;
-    }
-    float pre[2][NIT][3];
-    auto prefetch = [&](int s, float (&pre)[NIT][3]) {
-        const int sc_ = min(max(s, 0), vol.D - 1);  // planes outside the volume replicate the border plane
-        const int64_t zo = (int64_t)sc_ * vol.H * vol.W * LD.em;
-        const float* __restrict__ px_ = dx_ + zo;
-        const float* __restrict__ py_ = dy_ + zo;
-        const float* __restrict__ pz_ = dz_ + zo;
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            if (sxy[it] < 0) continue;
-            const unsigned g = (unsigned)sxy[it] * 4u * (unsigned)LD.em;
-            if (LD.em == 3) {
-                const F3 v = ld3_off(px_, g);
-                pre[it][0] = v.x;
-                pre[it][1] = v.y;
-                pre[it][2] = v.z;
-            } else {
-                pre[it][0] = ld_off(px_, g);
-                pre[it][1] = ld_off(py_, g);
-                pre[it][2] = ld_off(pz_, g);
-            }
-        }
-    };
-    auto commit = [&](int slot, const float (&pre)[NIT][3]) {
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            if (sxy[it] < 0) continue;
-            const int i = slot * PNP + sld[it];
-            r_xy[i] = make_float2(PRESCALE ? prescale(pre[it][0], sc.nm1[0], sc.rnm1[0], sc.inv_pow) : pre[it][0],
-                                  PRESCALE ? prescale(pre[it][1], sc.nm1[1], sc.rnm1[1], sc.inv_pow) : pre[it][1]);
-            r_z[i] = PRESCALE ? prescale(pre[it][2], sc.nm1[2], sc.rnm1[2], sc.inv_pow) : pre[it][2];
-        }
-    };
-
-    float m0 = 0.0f, m1 = 0.0f, m2 = 0.0f;
-    // one output of plane zo, whose own value sits in ring slot `a` (a compile-time constant at every call site)
-    auto sample = [&](const int zo, const int a, const float linz) {
-        const int ci = a * PNP + (ly + R) * PITCH + (lx + R);
-        const float2 dxy = r_xy[ci];
-        const float d0 = dxy.x, d1 = dxy.y, d2 = r_z[ci];
-        const AxisTap tx = axis_tap(__fadd_rn(linx, d0), vol.W);
-        const AxisTap ty = axis_tap(__fadd_rn(liny, d1), vol.H);
-        const AxisTap tz = axis_tap(__fadd_rn(linz, d2), vol.D);
-        const int bx0 = tx.i0 - (ox - R), by0 = ty.i0 - (oy - R), rel = tz.i0 - zo;
-        const bool in_ring = (unsigned)bx0 < (unsigned)(PX - 1) && (unsigned)by0 < (unsigned)(M::PY - 1) && rel >= -R && rel < R;
-        float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
-        auto ring_taps = [&]() {
-            const float wxy[2][2] = {{__fmul_rn(tx.w0, ty.w0), __fmul_rn(tx.w1, ty.w0)}, {__fmul_rn(tx.w0, ty.w1), __fmul_rn(tx.w1, ty.w1)}};
-            // rel is -1 or 0: planes zo - 1, zo or zo, zo + 1
-            const int sl0 = (rel == 0 ? a : (a - 1 + NS) % NS) * PNP, sl1 = (rel == 0 ? (a + 1) % NS : a) * PNP;
-            const int off = by0 * PITCH + bx0;
-#pragma unroll
-            for (int cz = 0; cz < 2; ++cz) {
-                const int bs = (cz ? sl1 : sl0) + off;
-#pragma unroll
-                for (int cy = 0; cy < 2; ++cy)
-#pragma unroll
-                    for (int cx = 0; cx < 2; ++cx) {
-                        const float w = __fmul_rn(wxy[cy][cx], cz ? tz.w1 : tz.w0);
-                        typedef float VF2 __attribute__((ext_vector_type(2)));  // single reads: see IRS_FWD_TAPS
-                        const VF2 tv = *(const volatile __attribute__((address_space(3))) VF2*)(&r_xy[bs + cy * PITCH + cx]);
-                        const float t1 = *(const volatile __attribute__((address_space(3))) float*)(&r_z[bs + cy * PITCH + cx]);
-                        a0 = fmaf(tv.x, w, a0);
-                        a1 = fmaf(tv.y, w, a1);
-                        a2 = fmaf(t1, w, a2);
-                    }
-            }
-        };
-        if (__all(in_ring)) {
-            ring_taps();
-        } else if (in_ring) {
-            ring_taps();
-        } else {
-#pragma unroll
-            for (int cz = 0; cz < 2; ++cz)
-#pragma unroll
-                for (int cy = 0; cy < 2; ++cy)
-#pragma unroll
-                    for (int cx = 0; cx < 2; ++cx) {
-                        const float w = __fmul_rn(__fmul_rn(cx ? tx.w1 : tx.w0, cy ? ty.w1 : ty.w0), cz ? tz.w1 : tz.w0);
-                        const int64_t idx = (((int64_t)(cz ? tz.i1 : tz.i0) * vol.H + (cy ? ty.i1 : ty.i0)) * vol.W + (cx ? tx.i1 : tx.i0)) * LD.em;
-                        a0 = fmaf(ldp<PRESCALE>(dx_, idx, sc.nm1[0], sc.rnm1[0], sc.inv_pow), w, a0);
-                        a1 = fmaf(ldp<PRESCALE>(dy_, idx, sc.nm1[1], sc.rnm1[1], sc.inv_pow), w, a1);
-                        a2 = fmaf(ldp<PRESCALE>(dz_, idx, sc.nm1[2], sc.rnm1[2], sc.inv_pow), w, a2);
-                    }
-        }
-        const int64_t pl = (int64_t)zo * vol.H * vol.W * LO.em;
-        const unsigned g = (unsigned)(y * vol.W + x) * 4u * (unsigned)LO.em;
-        const float r0 = __fadd_rn(d0, a0), r1 = __fadd_rn(d1, a1), r2 = __fadd_rn(d2, a2);
-        if (LO.em == 3) {
-            st3_off(o + pl, g, r0, r1, r2);
-        } else {
-            st_off(o + pl, g, r0);
-            st_off(o + LO.cs + pl, g, r1);
-            st_off(o + 2 * LO.cs + pl, g, r2);
-        }
-        m0 = fmaxf(m0, fabsf(r0));
-        m1 = fmaxf(m1, fabsf(r1));
-        m2 = fmaxf(m2, fabsf(r2));
-    };
-
-    // planes sbase .. slast are staged, two per step: step i commits sbase + 2 i and sbase + 2 i + 1 (a plane beyond slast is a clamped,
-    // harmless re-read that nothing samples) and samples the outputs one plane behind each
-    const int sbase = z0 - R, slast = z1 - 1 + R;
-    float linz_a = lin.z[min(max(sbase - R, 0), vol.D - 1)], linz_b = lin.z[min(max(sbase + 1 - R, 0), vol.D - 1)];
-    prefetch(sbase, pre[0]);
-    prefetch(sbase + 1, pre[1]);
-    for (int sb = sbase; sb <= slast; sb += NS) {
-#pragma unroll
-        for (int PH = 0; PH < NS; PH += 2) {
-            const int s = sb + PH;
-            if (s > slast) break;
-            commit(PH, pre[0]);
-            commit(PH + 1, pre[1]);
-            const float lz0 = linz_a, lz1 = linz_b;
-            linz_a = lin.z[min(max(s + 2 - R, 0), vol.D - 1)];  // (before the prefetch: the load counter completes in order)
-            linz_b = lin.z[min(max(s + 3 - R, 0), vol.D - 1)];
-            if (s + 2 <= slast) {
-                prefetch(s + 2, pre[0]);
-                prefetch(s + 3, pre[1]);
-            }
-            __syncthreads();
-            const int zo = s - R;
-            if (live && zo >= z0 && zo < z1) sample(zo, (PH - R + NS) % NS, lz0);
-            if (live && zo + 1 >= z0 && zo + 1 < z1) sample(zo + 1, PH, lz1);
-        }
-    }
-    if (dmax_out) {
-        m0 *= 0.5f * sc.nm1[0];
-        m1 *= 0.5f * sc.nm1[1];
-        m2 *= 0.5f * sc.nm1[2];
-#pragma unroll
-        for (int off = kWave / 2; off > 0; off >>= 1) {
-            m0 = fmaxf(m0, __shfl_down(m0, off, kWave));
-            m1 = fmaxf(m1, __shfl_down(m1, off, kWave));
-            m2 = fmaxf(m2, __shfl_down(m2, off, kWave));
-        }
-        const int wid = threadIdx.x / kWave;
-        if ((threadIdx.x & (kWave - 1)) == 0) {
-            red[wid] = m0;
-            red[(kFwdBlock / kWave) + wid] = m1;
-            red[2 * (kFwdBlock / kWave) + wid] = m2;
-        }
-        __syncthreads();
-        if (threadIdx.x < 3) {
-            float m = 0.0f;
-#pragma unroll
-            for (int w = 0; w < kFwdBlock / kWave; ++w) m = fmaxf(m, red[threadIdx.x * (kFwdBlock / kWave) + w]);
-            unsigned* slot = dmax_out + chain * 4 + threadIdx.x;
-            if (__float_as_uint(m) > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomic_max_nonneg(slot, m);
-        }
-    }
-    };  // run
-    switch (lay & 5) {
-        case 0: run(LayC<0>{}); break;
-        case 1: run(LayC<1>{}); break;
-        case 4: run(LayC<4>{}); break;
-        default: run(LayC<5>{}); break;
-    }
-}
-
-template <bool PRESCALE>
-__global__ __launch_bounds__(FTX * FTY, IRS_FWD_WAVES) void exp_fwd_march_z2_kernel(const float* __restrict__ din, float* __restrict__ dout, Vol vol, Lin lin,
-                                                                        Scale3L sc, const unsigned* __restrict__ dmax_in,
-                                                                        unsigned* __restrict__ dmax_out, int seg_len, int nseg, int h_lo,
-                                                                        int h_hi, int swz_run, dim3 tiles, int lay) {
-    const int total = (int)(tiles.x * tiles.y * tiles.z);
-    for (int id = blockIdx.x; id < total; id += gridDim.x) {
-        exp_fwd_march_tile_z2<PRESCALE>(din, dout, vol, lin, sc, dmax_in, dmax_out, seg_len, nseg, h_lo, h_hi, swz_run, id, tiles, lay);
-        __syncthreads();  // the ring and the reduction scratch are reused by the next tile
-    }
-}
-
+// (A radius-1 kernel that marches TWO planes per step was built for small launches and measured flat: DESIGN.md, "Round-5
+// measurements and experiments".)
 void launch_exp_step_fwd_march(const float* din, float* dout, bool prescale_in, int no_steps, int C, Vol vol, Lin lin,
                                const unsigned* dmax_in, unsigned* dmax_out, bool only_r1, int lay, hipStream_t st) {
     const int seg_env = global_knobs().march_seg_fwd;
@@ -2073,14 +1664,6 @@ void launch_exp_step_fwd_march(const float* din, float* dout, bool prescale_in, 
                    small ? resident_blocks((const void*)exp_fwd_march_kernel<false, 1, 1, 2>, FTX * FTY, &cache_ls)
                          : resident_blocks((const void*)exp_fwd_march_kernel<false, 1, FROWS_BIG, 1>, FTX * FTY / FROWS_BIG, &cache_lb));
     }
-#define IRS_FWM(P, RR, LO, HI, GRID) hipLaunchKernelGGL((exp_fwd_march_kernel<P, RR>), dim3(GRID), dim3(FTX * FTY / FROWS_BIG), 0, st, din, dout, vol, lin, sc, dmax_in, dmax_out, seg_len, nseg, LO, HI, (GRID) == total ? swz_run : 0, tiles, lay)
-#define IRS_FWM2(P, LO, HI, GRID) hipLaunchKernelGGL((exp_fwd_march_kernel<P, 2>), dim3(GRID), dim3(FTX * FTY / FROWS_BIG), 0, st, din, dout, vol, lin, sc, dmax_in, dmax_out, seg2, nseg2, LO, HI, (GRID) == total2 ? swz_run : 0, tiles2, lay)
-#define IRS_FW2(P, LO, HI, GRID) hipLaunchKernelGGL((exp_fwd_march_kernel<P, 2, 1>), dim3(GRID), dim3(FTX * FTY), 0, st, din, dout, vol, lin, sc, dmax_in, dmax_out, seg2, nseg2, LO, HI, (GRID) == total2 ? swz_run : 0, tiles2, lay)
-#define IRS_FWS(P, LO, HI)                                                                                                      \
-    if (global_knobs().fwd_z2) hipLaunchKernelGGL((exp_fwd_march_z2_kernel<P>), dim3(total), dim3(FTX * FTY), 0, st, din, dout, vol, lin, sc, dmax_in, dmax_out, seg_len, nseg, LO, HI, swz_run, tiles, lay); \
-    else if (global_knobs().fwd_pf >= 2) IRS_FWS_(P, 2, LO, HI);                                                                \
-    else IRS_FWS_(P, 1, LO, HI)
-#define IRS_FWS_(P, PFF, LO, HI) hipLaunchKernelGGL((exp_fwd_march_kernel<P, 1, 1, PFF>), dim3(total), dim3(FTX * FTY), 0, st, din, dout, vol, lin, sc, dmax_in, dmax_out, seg_len, nseg, LO, HI, swz_run, tiles, lay)
     // the radius-2 variant's own segments (as for the adjoint): a persistent grid of what the chip holds of it, four run-in planes
     const bool r2_rows1 = global_knobs().fwd_r2_rows1 != 0;
     int seg2 = seg_len;
@@ -2098,21 +1681,25 @@ void launch_exp_step_fwd_march(const float* din, float* dout, bool prescale_in, 
     const dim3 tiles2(tiles.x, tiles.y, (unsigned)(nseg2 * C));
     const int total2 = (int)(tiles2.x * tiles2.y * tiles2.z);
     const int rare = total2 < res2 ? total2 : (int)res2;
-    if (!dmax_in || only_r1) {  // no bound / predicted small: the radius-1 ring is correct for any displacement (far taps go to global memory)
-        if (small) { if (prescale_in) IRS_FWS(true, -1, 1 << 30); else IRS_FWS(false, -1, 1 << 30); }
-        else if (prescale_in) IRS_FWM(true, 1, -1, 1 << 30, total); else IRS_FWM(false, 1, -1, 1 << 30, total);
-    } else {
-        if (small) { if (prescale_in) IRS_FWS(true, -1, 1); else IRS_FWS(false, -1, 1); }
-        else if (prescale_in) IRS_FWM(true, 1, -1, 1, total); else IRS_FWM(false, 1, -1, 1, total);
+    // a chain whose bound asks for a ring radius in (h_lo, h_hi] is this launch's; a grid of all tiles is placed XCD-aware
+    auto launch = [&](auto P, auto RR, auto ROWS, auto PF, int h_lo, int h_hi, int grid, int seg, int nseg_, dim3 tiles_, int total_) {
+        constexpr int kRows = decltype(ROWS)::value;
+        hipLaunchKernelGGL((exp_fwd_march_kernel<decltype(P)::value, decltype(RR)::value, kRows, decltype(PF)::value>), dim3(grid),
+                           dim3(FTX * FTY / kRows), 0, st, din, dout, vol, lin, sc, dmax_in, dmax_out, seg, nseg_, h_lo, h_hi,
+                           grid == total_ ? swz_run : 0, tiles_, lay);
+    };
+    // no bound / predicted small: the radius-1 ring is correct for any displacement (far taps go to global memory) and runs alone
+    const bool r1_only = !dmax_in || only_r1;
+    with_bool(prescale_in, [&](auto P) {
+        auto r1 = [&](auto ROWS, auto PF) { launch(P, Int<1>{}, ROWS, PF, -1, r1_only ? 1 << 30 : 1, total, seg_len, nseg, tiles, total); };
+        if (!small) r1(Int<FROWS_BIG>{}, Int<1>{});
+        else if (global_knobs().fwd_pf >= 2) r1(Int<1>{}, Int<2>{});
+        else r1(Int<1>{}, Int<1>{});
+        if (r1_only) return;
         // radius-2 ring: 59 KB, two workgroups per CU -- with one output row per thread they are 16 waves instead of 8
-        if (global_knobs().fwd_r2_rows1) { if (prescale_in) IRS_FW2(true, 1, 1 << 30, rare); else IRS_FW2(false, 1, 1 << 30, rare); }
-        else if (prescale_in) IRS_FWM2(true, 1, 1 << 30, rare); else IRS_FWM2(false, 1, 1 << 30, rare);
-    }
-#undef IRS_FWM2
-#undef IRS_FWS
-#undef IRS_FWS_
-#undef IRS_FW2
-#undef IRS_FWM
+        auto r2 = [&](auto ROWS) { launch(P, Int<2>{}, ROWS, Int<1>{}, 1, 1 << 30, rare, seg2, nseg2, tiles2, total2); };
+        if (r2_rows1) r2(Int<1>{}); else r2(Int<FROWS_BIG>{});
+    });
 }
 
 // per-chain max |d| (voxels, per axis) of a field -- used by the stateless adjoint, which has no forward by-product

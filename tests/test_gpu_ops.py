@@ -129,6 +129,33 @@ def test_svf_exp_forward(dims, amp):
     assert maxdiff(d, d_ref) < 2e-5 * max(1.0, float(d_ref.abs().max()))
 
 
+def test_svf_exp_forward_radius1_variants_agree():
+    """The radius-1 forward step has three launch shapes -- two output rows per thread, one row with two planes of loads in
+    flight, one row with one -- each in a prescaling (step 0) and a plain instantiation: six kernels that must give the same
+    bits.  (19, 13, 70): one full and one ragged 64-wide tile, a ragged second tile row, three 8-plane segments of which the
+    last is short; a field that reaches 3 voxels sends taps of the later steps out of the ring to the global-memory path."""
+    dims, no_steps = (19, 13, 70), 4
+    v = smooth_field(2, dims, 1.0, 6)
+    vox = 0.5 * (torch.tensor([dims[2], dims[1], dims[0]], dtype=torch.float32) - 1.0).view(1, 3, 1, 1, 1)
+
+    def reach(d):
+        return float((d.cpu() * vox).abs().max())
+    v = v * (3.0 / float(v.abs().max()))   # the velocity is in voxels, and d_last = v + O(|v| |grad v|): about 3 voxels
+    from ir_sgmcmc_amd._lib import option_set
+    outs = []
+    try:
+        for rows1, pf in ((0, 2), (1, 2), (1, 1)):
+            option_set('fwd_rows1', rows1)   # process-wide switches of the stateless operator (irs_option_set)
+            option_set('fwd_pf', pf)
+            outs.append(G.svf_exp_fwd(dev(v), no_steps, want_outputs=False)[2])
+    finally:
+        option_set('fwd_rows1', -1)
+        option_set('fwd_pf', 2)
+    assert 2.0 < reach(outs[0][-1]) < 4.0 and reach(outs[0][-2]) > 1.0   # the last step's input leaves the radius-1 ring
+    assert torch.equal(outs[1], outs[0])
+    assert torch.equal(outs[2], outs[0])
+
+
 @pytest.mark.parametrize('dims,amp', [((16, 16, 16), 2.0), ((16, 16, 16), 25.0), ((10, 14, 22), 6.0)])
 @pytest.mark.parametrize('upstream', ['smooth', 'white'])
 def test_svf_exp_backward(dims, amp, upstream):

@@ -10,7 +10,7 @@
 //   layout 3  16-byte records (d0, d1, d2, -), one ds_read_b128 per corner
 //   layout 4  float2 (d0, d1) + float2 (d2[x], d2[x + 1]): three ds_read_b64 per corner PAIR
 //   layout 6  layout 0's arrays through volatile LDS pointers: single ds_read_b64 + ds_read_b32 issued by the COMPILER (no pairing, its
-//             own waits) -- the form the kernel ships (IRS_FWD_TAPS=3)
+//             own waits) -- the form the kernel ships
 //   layout 5  layout 1's arrays, FIXED columns x - 1, x, x + 1 in the lane's two rows and planes (12 corner reads, 4 of them
 //             with weight 0): no per-lane x shift, so no bank conflict whatever the field does
 //   pitch     row pitch in records (80 = the shipped 16-record alignment of 66; 66 = unpadded; 81 / 82 = a row start rotated by one
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(kBlock, 4) void tap_probe(float* __restrict__ out, 
             const int ctr = a * PNP + (ly + R) * PITCH + lx + R;
             const int off = by0 * PITCH + bx0;
             if (LAYOUT == 6) {  // layout 0's arrays read through volatile LDS pointers: the compiler issues, counts and schedules the reads, but
-                                // its load / store optimiser leaves volatile accesses unpaired -- what IRS_FWD_TAPS=3 does in the kernel
+                                // its load / store optimiser leaves volatile accesses unpaired -- what the forward squaring step does
                 typedef const volatile __attribute__((address_space(3))) f2* VQ;
                 typedef const volatile __attribute__((address_space(3))) float* VZ;
                 const VQ q = (VQ)(reinterpret_cast<const f2*>(xy));
