@@ -305,6 +305,55 @@ int irs_displacement_quantiles_finalize(const float* centre, const uint16_t* his
                                         float* quantiles, float* ci_width, long long* isummary, double* fsummary, void* ws,
                                         size_t ws_bytes, void* stream);
 
+/* Inverse transformation and inverse-consistency error (absent in the reference, which only evaluates the forward map).  For
+ * a stationary velocity field exp(-v) is the inverse of exp(v); how well the squaring steps at fp32 invert is what the error
+ * maps say.
+ *  - irs_svf_exp_inverse: exp(-v) by scaling and squaring.  v (C,3,D,H,W) float32 in voxel units, every dim >= 2, no_steps in
+ *    1 .. 30, as irs_svf_exp_fwd; scratch: 2 x (C,3,D,H,W) float32 workspace (two fields, not no_steps of them: nothing is
+ *    kept for a backward).  -v is written into scratch[1]; step 0 reads it and writes scratch[0], later steps ping-pong.
+ *    transformation ([-1,1] coordinates) / displacement (voxels): (C,3,D,H,W) outputs, either may be NULL.  The launches are
+ *    those of irs_svf_exp_fwd: bit-identical to irs_svf_exp_fwd called on -v.  Deterministic; no host sync.
+ *  - irs_inverse_consistency: per chain and voxel x, r = d_a(x) + trilinear(d_b)(t_a(x)).  t_a (C,3,D,H,W) float32: a
+ *    transformation in [-1,1] coordinates; d_a, d_b (C,3,D,H,W) float32: displacements in one common linear unit (the
+ *    `displacement` outputs are in voxels); C in 1 .. IRS_MAX_CHAINS, every dim >= 2.  The three channels of d_b are sampled
+ *    at t_a(x) with the trilinear sampler of the squaring step and the warp (border clamp, align_corners, the same
+ *    expressions).  residual (C,3,D,H,W) float32 or NULL: r.  norm (C,1,D,H,W) float32 or NULL: sqrt(sum_c (scale_c r_c)^2),
+ *    every product, sum and the root rounded to float32 in that order.  scale: 3 host floats, finite and > 0, one per
+ *    channel.  mask: uint8, (mask_chains,1,D,H,W) with mask_chains 1 (shared) or C, or NULL (whole volume; mask_chains is
+ *    then ignored).  isummary (C, IRS_ICE_SUMMARY_INTS) int64 per chain over the mask {voxels, voxels with a non-finite
+ *    norm}; fsummary (C, IRS_ICE_SUMMARY_FLOATS) doubles over the other masked voxels {sum norm, sum norm^2, max norm}; a
+ *    maximum nothing entered is -inf.  ws: IRS_ICE_WS_BYTES of device memory.  Called as (t, d, d_inv) of (phi, phi^-1) it
+ *    gives phi^-1 o phi - id on the fixed grid; as (t_inv, d_inv, d) it gives phi o phi^-1 - id on the moving grid.
+ *    Deterministic (exact integer sums, fixed-order double sums and maxima: one row of partials per block, one reduce per
+ *    chain); no atomics; no host sync.
+ *  - irs_inverse_consistency_update: norm (C,1,D,H,W) float32, C in 1 .. IRS_MAX_CHAINS; mean, peak (D,H,W) float32, updated
+ *    in place with the C maps in chain order: k = records_before + c + 1, mean += (x - mean) / (float)k (k = 1: mean = x),
+ *    peak = fmaxf(peak, x) over the finite x only.  records_before >= 0, records_before + C <= INT32_MAX; records_before = 0
+ *    overwrites the state, which is then never read.  Non-finite values propagate into mean; peak is NaN where no value
+ *    was ever finite.  One launch, each thread owns its voxels, no atomics; no host sync.
+ *  - irs_inverse_consistency_finalize: masked summary of the two maps.  mask (D,H,W) uint8 or NULL (whole volume); threshold:
+ *    finite and > 0, in the unit of the maps.  isummary: IRS_ICE_MAP_SUMMARY_INTS int64 over the mask {voxels, voxels with a
+ *    non-finite mean, voxels with peak > threshold}; fsummary: IRS_ICE_MAP_SUMMARY_FLOATS doubles {sum mean, max mean} over
+ *    the masked voxels with a finite mean and {max peak} over those with a finite peak; a maximum nothing entered is -inf.
+ *    ws: IRS_ICE_MAP_WS_BYTES of device memory.  Deterministic (exact integer sums, fixed-order double sums and maxima); no
+ *    host sync. */
+#define IRS_ICE_SUMMARY_INTS 2
+#define IRS_ICE_SUMMARY_FLOATS 3
+#define IRS_ICE_WS_BYTES (IRS_MAX_CHAINS * 1024 * (IRS_ICE_SUMMARY_INTS + IRS_ICE_SUMMARY_FLOATS) * 8)
+#define IRS_ICE_MAP_SUMMARY_INTS 3
+#define IRS_ICE_MAP_SUMMARY_FLOATS 3
+#define IRS_ICE_MAP_WS_BYTES (1024 * (IRS_ICE_MAP_SUMMARY_INTS + IRS_ICE_MAP_SUMMARY_FLOATS) * 8)
+int irs_svf_exp_inverse(const float* v, float* scratch, float* transformation, float* displacement, int no_steps, int C, int D,
+                        int H, int W, void* stream);
+int irs_inverse_consistency(const float* t_a, const float* d_a, const float* d_b, const float* scale, const uint8_t* mask,
+                            int mask_chains, float* residual, float* norm, long long* isummary, double* fsummary, void* ws,
+                            size_t ws_bytes, int C, int D, int H, int W, void* stream);
+int irs_inverse_consistency_update(const float* norm, int C, int D, int H, int W, float* mean, float* peak, int records_before,
+                                   void* stream);
+int irs_inverse_consistency_finalize(const float* mean, const float* peak, int D, int H, int W, const uint8_t* mask,
+                                     float threshold, long long* isummary, double* fsummary, void* ws, size_t ws_bytes,
+                                     void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * fused transition (Trainer._SGLD_transition, trainer/trainer.py:291-356)
  * ---------------------------------------------------------------------------------------------- */

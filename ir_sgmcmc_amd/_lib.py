@@ -25,6 +25,10 @@ IRS_COVARIANCE_WS_BYTES = 1024 * (IRS_COVARIANCE_SUMMARY_INTS + IRS_COVARIANCE_S
 IRS_QUANTILE_MIN_BINS, IRS_QUANTILE_MAX_BINS, IRS_QUANTILE_MAX_PROBS, IRS_QUANTILE_MAX_RECORDS = 4, 256, 8, 65535
 IRS_QUANTILE_SUMMARY_INTS, IRS_QUANTILE_SUMMARY_FLOATS = 3, 5
 IRS_QUANTILE_WS_BYTES = 1024 * (IRS_QUANTILE_SUMMARY_INTS + IRS_QUANTILE_SUMMARY_FLOATS) * 8
+IRS_ICE_SUMMARY_INTS, IRS_ICE_SUMMARY_FLOATS = 2, 3
+IRS_ICE_WS_BYTES = IRS_MAX_CHAINS * 1024 * (IRS_ICE_SUMMARY_INTS + IRS_ICE_SUMMARY_FLOATS) * 8
+IRS_ICE_MAP_SUMMARY_INTS, IRS_ICE_MAP_SUMMARY_FLOATS = 3, 3
+IRS_ICE_MAP_WS_BYTES = 1024 * (IRS_ICE_MAP_SUMMARY_INTS + IRS_ICE_MAP_SUMMARY_FLOATS) * 8
 IRS_DATA_GMM_LCC, IRS_DATA_SSD = 0, 1
 IRS_REG_L2, IRS_REG_LOGNORMAL, IRS_REG_STUDENT, IRS_REG_LOGNORMAL_L2 = 0, 1, 2, 3
 
@@ -160,6 +164,10 @@ SIGNATURES = {
     'irs_displacement_quantiles_update': [_P, _I, _I, _I, _I, _P, _P, _I, C.POINTER(C.c_float), _I, _P],
     'irs_displacement_quantiles_finalize': [_P, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                             C.POINTER(C.c_double), _I, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],
+    'irs_svf_exp_inverse': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    'irs_inverse_consistency': [_P, _P, _P, C.POINTER(C.c_float), _P, _I, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _P],
+    'irs_inverse_consistency_update': [_P, _I, _I, _I, _I, _P, _P, _I, _P],
+    'irs_inverse_consistency_finalize': [_P, _P, _I, _I, _I, _P, _F, _P, _P, _P, C.c_size_t, _P],
     'irs_create': [C.POINTER(IrsConfig), C.POINTER(_P)],
     'irs_destroy': [_P],
     'irs_workspace_bytes': [_P],

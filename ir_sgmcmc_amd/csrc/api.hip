@@ -1005,6 +1005,72 @@ int irs_displacement_quantiles_finalize(const float* centre, const uint16_t* his
 }
 
 // ================================================================================================
+// inverse transformation and inverse-consistency error (inverse_kernels.hip)
+// ================================================================================================
+int irs_svf_exp_inverse(const float* v, float* scratch, float* transformation, float* displacement, int no_steps, int C, int D,
+                        int H, int W, void* stream) {
+    if (!v || !scratch || !dims_ok(C, D, H, W) || no_steps < 1 || no_steps > 30) return fail("irs_svf_exp_inverse: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const Vol vol = make_vol(D, H, W);
+    Lin lin;
+    if (cached_lin(D, H, W, st, &lin)) return fail("irs_svf_exp_inverse: identity grid allocation failed");
+    const int64_t field = (int64_t)C * 3 * vol.V;
+    float* buf[2] = {scratch, scratch + field};
+    launch_negate(v, buf[1], field, st);
+    for (int k = 0; k < no_steps; ++k)  // step 0: buf[1] -> buf[0]; then ping-pong
+        launch_exp_step_fwd_march(buf[(k + 1) & 1], buf[k & 1], k == 0, no_steps, C, vol, lin, nullptr, nullptr, false, 0, st);
+    if (transformation || displacement) launch_svf_outputs(buf[(no_steps - 1) & 1], transformation, displacement, C, vol, lin, st);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_inverse_consistency(const float* t_a, const float* d_a, const float* d_b, const float* scale, const uint8_t* mask,
+                            int mask_chains, float* residual, float* norm, long long* isummary, double* fsummary, void* ws,
+                            size_t ws_bytes, int C, int D, int H, int W, void* stream) {
+    if (!t_a || !d_a || !d_b || !scale || !isummary || !fsummary || !ws || !dims_ok(C, D, H, W))
+        return fail("irs_inverse_consistency: bad arguments");
+    if (C > IRS_MAX_CHAINS) return fail("irs_inverse_consistency: C = %d chains, 1..%d", C, IRS_MAX_CHAINS);
+    if (mask && mask_chains != 1 && mask_chains != C)
+        return fail("irs_inverse_consistency: mask of %d chains, 1 or %d needed", mask_chains, C);
+    for (int a = 0; a < 3; ++a)
+        if (!positive_finite(scale[a]))
+            return fail("irs_inverse_consistency: scale[%d] = %g, a finite value > 0 needed", a, (double)scale[a]);
+    if (ws_bytes < (size_t)IRS_ICE_WS_BYTES)
+        return fail("irs_inverse_consistency: workspace of %zu bytes, %zu needed (IRS_ICE_WS_BYTES)", ws_bytes, (size_t)IRS_ICE_WS_BYTES);
+    launch_inverse_consistency(t_a, d_a, d_b, scale, mask, mask_chains, residual, norm, isummary, fsummary, ws, C, make_vol(D, H, W),
+                               (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_inverse_consistency_update(const float* norm, int C, int D, int H, int W, float* mean, float* peak, int records_before,
+                                   void* stream) {
+    if (!norm || !mean || !peak || !dims_ok(C, D, H, W)) return fail("irs_inverse_consistency_update: bad arguments");
+    if (C > IRS_MAX_CHAINS) return fail("irs_inverse_consistency_update: C = %d chains, 1..%d", C, IRS_MAX_CHAINS);
+    if (records_before < 0) return fail("irs_inverse_consistency_update: records_before = %d < 0", records_before);
+    if ((int64_t)records_before + C > INT32_MAX)
+        return fail("irs_inverse_consistency_update: %d records + %d chains overflow the int32 record count", records_before, C);
+    launch_inverse_consistency_update(norm, C, (int64_t)D * H * W, mean, peak, records_before, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_inverse_consistency_finalize(const float* mean, const float* peak, int D, int H, int W, const uint8_t* mask,
+                                     float threshold, long long* isummary, double* fsummary, void* ws, size_t ws_bytes,
+                                     void* stream) {
+    if (!mean || !peak || !isummary || !fsummary || !ws || !dims_ok(1, D, H, W))
+        return fail("irs_inverse_consistency_finalize: bad arguments");
+    if (!positive_finite(threshold))
+        return fail("irs_inverse_consistency_finalize: threshold = %g, a finite value > 0 needed", (double)threshold);
+    if (ws_bytes < (size_t)IRS_ICE_MAP_WS_BYTES)
+        return fail("irs_inverse_consistency_finalize: workspace of %zu bytes, %zu needed (IRS_ICE_MAP_WS_BYTES)", ws_bytes,
+                    (size_t)IRS_ICE_MAP_WS_BYTES);
+    launch_inverse_consistency_finalize(mean, peak, (int64_t)D * H * W, mask, threshold, isummary, fsummary, ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // context
 // ================================================================================================
 

@@ -234,6 +234,22 @@ void launch_quantile_finalize(const float* centre, const uint16_t* hist, int bin
                               const float* scale, const double* probs, int P, const uint8_t* mask, float* quantiles,
                               float* ci_width, long long* isummary, double* fsummary, void* ws, hipStream_t st);
 
+// ---- inverse_kernels.hip: inverse transformation and inverse-consistency error (absent in the reference)
+void launch_negate(const float* in, float* out, int64_t n, hipStream_t st);
+// t_a, d_a, d_b (C,3,V) float32; scale: 3 host floats; mask (mask_chains,V) uint8 or nullptr; residual (C,3,V) / norm (C,V) or
+// nullptr; isummary (C, IRS_ICE_SUMMARY_INTS) int64, fsummary (C, IRS_ICE_SUMMARY_FLOATS) doubles; ws: IRS_ICE_WS_BYTES (per
+// chain the partials of at most 1024 blocks)
+void launch_inverse_consistency(const float* t_a, const float* d_a, const float* d_b, const float* scale, const uint8_t* mask,
+                                int mask_chains, float* residual, float* norm, long long* isummary, double* fsummary, void* ws,
+                                int C, Vol vol, hipStream_t st);
+// norm (C,V) float32 -> mean / peak (V) float32: Welford mean and running maximum of the finite values, the C chains folded in
+// order after `records_before` records
+void launch_inverse_consistency_update(const float* norm, int C, int64_t V, float* mean, float* peak, int records_before,
+                                       hipStream_t st);
+// isummary IRS_ICE_MAP_SUMMARY_INTS int64, fsummary IRS_ICE_MAP_SUMMARY_FLOATS doubles; ws: IRS_ICE_MAP_WS_BYTES
+void launch_inverse_consistency_finalize(const float* mean, const float* peak, int64_t V, const uint8_t* mask, float threshold,
+                                         long long* isummary, double* fsummary, void* ws, hipStream_t st);
+
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h
 }  // namespace irs

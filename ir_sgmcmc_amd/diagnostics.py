@@ -29,6 +29,11 @@ displacement around the first record (ops.displacement_quantiles_update), 12 + 6
 records, and at the end the quantiles of given probabilities, the width of the credible band between the first and the last
 and its summary over a mask (ops.displacement_quantiles_finalize).
 
+The inverse consistency (InverseConsistency) checks what a stationary velocity field promises: exp(-v) inverts exp(v).  At a
+recorded step it integrates -v (ops.svf_exp_inverse), composes the two maps in both orders (ops.inverse_consistency) and folds
+the norm of phi^-1 o phi - id (fixed grid) and of phi o phi^-1 - id (moving grid), in voxels, into a per-voxel Welford mean and
+a running maximum (ops.inverse_consistency_update): 16 * D * H * W bytes whatever the number of records.
+
 The Hausdorff option (hausdorff_options) is of another kind: it keeps no state.  It adds the Hausdorff and percentile surface
 distances of the propagated segmentation to the point-estimate metrics wherever the ASD is logged.
 """
@@ -713,6 +718,145 @@ class DisplacementQuantiles(_Recorder):
         self.centre.copy_(sd['centre'])
         self.hist.view(torch.int16).copy_(sd['hist'].view(torch.int16))
         self.records = records
+
+
+ICE_OPTION_KEYS = ('period', 'threshold', 'moving_space_dice')
+ICE_DEFAULTS = {'threshold': 0.5, 'moving_space_dice': False}  # 0.5 voxels: where a nearest-neighbour label flips
+ICE_SPACES = ('fixed', 'moving')
+
+
+def inverse_consistency_options(cfg_trainer):
+    """`trainer.inverse_consistency` -> None when off, else {'period': P, 'threshold': t, 'moving_space_dice': bool}.
+    Absent / false / null: off.  true: P = log_period_MCMC, threshold 0.5 voxels, no moving-space Dice.  A dict sets any of
+    the three keys.  Refuses unknown keys, a non-integer P or P < 1, a threshold that is not a finite number > 0, a non-bool
+    moving_space_dice, a config that records no step (no_samples_MCMC // P < 1) and one that would record more than 2^31 - 1
+    maps."""
+    what = 'trainer.inverse_consistency'
+
+    def own_keys(opt):
+        own = {**ICE_DEFAULTS, **{k: v for k, v in opt.items() if k != 'period'}}
+        t = own['threshold']
+        if not _number(t) or not (math.isfinite(t) and t > 0):
+            raise ValueError(f'{what}.threshold must be a finite number > 0 (voxels), got {t!r}')
+        if not isinstance(own['moving_space_dice'], bool):
+            raise ValueError(f'{what}.moving_space_dice must be true or false, got {own["moving_space_dice"]!r}')
+        return {'threshold': float(t), 'moving_space_dice': own['moving_space_dice']}
+
+    return _record_options(cfg_trainer, 'inverse_consistency', ICE_OPTION_KEYS,
+                           '{"period": P, "threshold": t, "moving_space_dice": bool}', MAX_RECORDS,
+                           'the record count holds at most {}', own_keys)
+
+
+def ice_chain_summary(isummary, fsummary):
+    """one chain's row of ops.inverse_consistency's summary (host ints / floats) -> {'voxels', 'nonfinite_voxels', 'mean',
+    'rms', 'max'} over the finite masked voxels, NaN when there is none"""
+    voxels, nonfinite = (int(x) for x in isummary)
+    total, total_sq, mx = (float(x) for x in fsummary)
+    finite = voxels - nonfinite
+    return {'voxels': voxels, 'nonfinite_voxels': nonfinite, 'mean': _nan_div(total, finite),
+            'rms': math.sqrt(total_sq / finite) if finite else float('nan'), 'max': mx if finite else float('nan')}
+
+
+def ice_map_summary(isummary, fsummary, n, threshold):
+    """the summary of DESIGN.md section 6 from ops.inverse_consistency_finalize's columns (host ints / floats): isummary
+    {voxels, voxels with a non-finite mean, voxels with peak > threshold}, fsummary {sum / max of the mean map, max of the peak
+    map}, n records.  'mean' is the mean of the mean map over its finite masked voxels, 'max' the largest peak;
+    frac_above_<threshold> = voxels whose peak exceeds it / voxels.  NaN for an empty mask or when nothing is finite."""
+    voxels, nonfinite, above = (int(x) for x in isummary)
+    m_sum, m_max, p_max = (float(x) for x in fsummary)
+    finite = voxels - nonfinite
+    nan = float('nan')
+    return {'records': int(n), 'voxels': voxels, 'nonfinite_voxels': nonfinite, 'mean': _nan_div(m_sum, finite),
+            'mean_max': m_max if finite else nan, 'max': p_max if math.isfinite(p_max) else nan,
+            f'above_{threshold:g}': above, f'frac_above_{threshold:g}': _nan_div(above, voxels)}
+
+
+class InverseConsistency(_Recorder):
+    """Per voxel, the Welford mean and the running maximum of the inverse-consistency error of the recorded samples, in voxels,
+    for both orders of composition: `mean['fixed']` / `peak['fixed']` of |phi^-1 o phi - id| on the fixed grid and
+    `mean['moving']` / `peak['moving']` of |phi o phi^-1 - id| on the moving grid, all (D,H,W) float32 on the device (16 D H W
+    bytes whatever the number of records).  `record((v, transformation, displacement))` takes the dense velocity (voxel
+    units), the forward transformation ([-1,1] coordinates) and the forward displacement (voxels) of one step, each
+    (C,3,D,H,W) float32: it integrates -v, composes in both orders and folds the 2 C norm maps in.  `last` keeps the per-chain
+    summaries of that step over `step_masks` (a dict of the two masks, or None) and `last_inverse` the inverse
+    (transformation, displacement) of that step; `finalize` gives the summaries of the four maps."""
+    noun = 'inverse consistency'
+
+    def __init__(self, dims, device, no_steps=12, step_masks=None):
+        self.dims = tuple(int(d) for d in dims)
+        if len(self.dims) != 3 or min(self.dims) < 2:
+            raise ValueError(f'inverse consistency: three dims of at least 2, got {self.dims}')
+        self.device, self.no_steps = device, int(no_steps)
+        self.step_masks = {k: None if step_masks is None else _bool_mask(step_masks.get(k), device) for k in ICE_SPACES}
+        self.mean = {k: torch.zeros(self.dims, device=device, dtype=torch.float32) for k in ICE_SPACES}
+        self.peak = {k: torch.zeros(self.dims, device=device, dtype=torch.float32) for k in ICE_SPACES}
+        self.last, self.last_inverse = None, None
+
+    def record(self, sample):
+        v, transformation, displacement = sample
+        if not (tuple(v.shape) == tuple(transformation.shape) == tuple(displacement.shape)):
+            raise ValueError(f'inverse consistency: velocity {tuple(v.shape)}, transformation {tuple(transformation.shape)} and '
+                             f'displacement {tuple(displacement.shape)} differ in shape')
+        C = v.shape[0]
+        if self.records + C > self.max_records:
+            raise ValueError(f'{self.noun}: {self.records} + {C} records {self.exceed.format(self.max_records)}')
+        self._update(v, transformation, displacement)
+        self.records += C
+
+    def _update(self, v, transformation, displacement):
+        t_inv, d_inv = ops.svf_exp_inverse(v.contiguous(), self.no_steps)
+        self.last_inverse = (t_inv, d_inv)
+        pairs = {'fixed': (transformation, displacement, d_inv), 'moving': (t_inv, d_inv, displacement)}
+        step = {}
+        for key in ICE_SPACES:
+            norm, _, isum, fsum = ops.inverse_consistency(*pairs[key], mask=self.step_masks[key])
+            ops.inverse_consistency_update(norm, self.mean[key], self.peak[key], self.records)
+            step[key] = (isum, fsum)
+        self.last = step
+
+    def last_summaries(self):
+        """-> {'fixed': [per-chain dict of ice_chain_summary], 'moving': [...]} of the last recorded step.  One device-to-host
+        read."""
+        self._need_records('last_summaries')
+        (fi, ff), (mi, mf) = self.last['fixed'], self.last['moving']
+        C = fi.shape[0]
+        ints, floats = _host_summary(torch.cat([fi.reshape(-1), mi.reshape(-1)]), torch.cat([ff.reshape(-1), mf.reshape(-1)]))
+        ni, nf = fi.shape[1], ff.shape[1]
+        out = {}
+        for s, key in enumerate(ICE_SPACES):
+            out[key] = [ice_chain_summary(ints[(s * C + c) * ni:(s * C + c + 1) * ni], floats[(s * C + c) * nf:(s * C + c + 1) * nf])
+                        for c in range(C)]
+        return out
+
+    def finalize(self, masks=None, threshold=0.5):
+        """masks: {'fixed': mask, 'moving': mask} (either may be missing / None: the whole volume).  -> {'fixed': summary,
+        'moving': summary} of ice_map_summary, the fixed-grid maps over the fixed mask and the moving-grid maps over the moving
+        mask.  One device-to-host read."""
+        self._need_records('finalize')
+        masks = masks or {}
+        res = [ops.inverse_consistency_finalize(self.mean[k], self.peak[k], threshold, _bool_mask(masks.get(k), self.device))
+               for k in ICE_SPACES]
+        ints, floats = _host_summary(torch.cat([r[0] for r in res]), torch.cat([r[1] for r in res]))
+        ni, nf = res[0][0].numel(), res[0][1].numel()
+        return {k: ice_map_summary(ints[s * ni:(s + 1) * ni], floats[s * nf:(s + 1) * nf], self.records, threshold)
+                for s, k in enumerate(ICE_SPACES)}
+
+    def state_dict(self):
+        sd = {'records': self.records}
+        for k in ICE_SPACES:
+            sd[f'mean_{k}'], sd[f'peak_{k}'] = self.mean[k].detach().cpu(), self.peak[k].detach().cpu()
+        return sd
+
+    def load_state_dict(self, sd):
+        for k in ICE_SPACES:
+            for name in (f'mean_{k}', f'peak_{k}'):
+                if tuple(sd[name].shape) != self.dims:
+                    raise ValueError(f'inverse consistency of shape {tuple(sd[name].shape)} ({name}) does not match this run '
+                                     f'({self.dims})')
+        for k in ICE_SPACES:
+            self.mean[k].copy_(sd[f'mean_{k}'])
+            self.peak[k].copy_(sd[f'peak_{k}'])
+        self.records = int(sd['records'])
 
 
 HAUSDORFF_MAX_PERCENTILES = 4  # IRS_HAUSDORFF_MAX_PERCENTILES

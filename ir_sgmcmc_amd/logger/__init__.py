@@ -186,3 +186,16 @@ def save_displacement_quantiles(logger, save_dirs, spacing, probs, quantiles, ci
 def quantile_tag(p):
     """0.05 -> '5', 0.5 -> '50', 0.025 -> '2p5'"""
     return f'{100.0 * float(p):g}'.replace('.', 'p')
+
+
+def save_inverse_consistency(logger, save_dirs, spacing, mean, peak, masks, model='MCMC'):
+    """inverse-consistency error maps in voxels (absent in the reference): samples/{model}_ICE_{fixed,moving}_{mean,max}
+    [_masked].nii.gz (float32).  `mean` / `peak` / `masks`: dicts with the keys 'fixed' (|phi^-1 o phi - id| on the fixed grid,
+    masked by the FIXED mask) and 'moving' (|phi o phi^-1 - id| on the moving grid, masked by the MOVING mask); the masked maps
+    are 0 outside their mask"""
+    folder = _folder(save_dirs, 'samples')
+    for space in ('fixed', 'moving'):
+        mask = masks[space].reshape(mean[space].shape).to(mean[space].device) != 0
+        for name, im in (('mean', mean[space]), ('max', peak[space])):
+            save_im_to_disk(im, path.join(folder, f'{model}_ICE_{space}_{name}.nii.gz'), spacing)
+            save_im_to_disk(im.where(mask, im.new_zeros(())), path.join(folder, f'{model}_ICE_{space}_{name}_masked.nii.gz'), spacing)

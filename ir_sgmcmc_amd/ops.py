@@ -611,3 +611,94 @@ def displacement_quantiles_finalize(centre, hist, n, width, scale, probs, mask=N
                                                     L.dev_ptr(ci_width), L.dev_ptr(isummary), L.dev_ptr(fsummary), L.dev_ptr(ws),
                                                     L.IRS_QUANTILE_WS_BYTES, L.stream_ptr()))
     return quantiles, ci_width, isummary, fsummary
+
+
+def svf_exp_inverse(v, no_steps=12):
+    """The inverse of SVF_3D.forward's map: exp(-v) by the same scaling and squaring (absent in the reference, which only
+    evaluates the forward map).  v (C,3,D,H,W) float32 in voxel units.  -> (transformation in [-1,1] coordinates, displacement
+    in voxels), bit-identical to svf_exp_fwd(-v); the workspace is two fields, nothing is kept for a backward.  No host
+    synchronisation."""
+    lib = L.load()
+    Cn, D, H, W = _dims5(v, 3)
+    scratch = torch.empty((2,) + tuple(v.shape), device=v.device, dtype=torch.float32)
+    t, d = torch.empty_like(v), torch.empty_like(v)
+    L.check(lib.irs_svf_exp_inverse(L.dev_ptr(v, torch.float32), L.dev_ptr(scratch), L.dev_ptr(t), L.dev_ptr(d), int(no_steps), Cn,
+                                    D, H, W, L.stream_ptr()))
+    return t, d
+
+
+def inverse_consistency(t_a, d_a, d_b, scale=None, mask=None, want_residual=False):
+    """Inverse-consistency error of a pair of maps (absent in the reference): per chain and voxel r = d_a(x) +
+    trilinear(d_b)(t_a(x)).  t_a (C,3,D,H,W) float32: a transformation in [-1,1] coordinates; d_a, d_b (C,3,D,H,W) float32:
+    displacements in one common unit; scale: three positive floats, one per channel (default 1: the unit of the
+    displacements); mask: bool / uint8, (1 or C,1,D,H,W) or (D,H,W), or None.  -> (norm (C,1,D,H,W) float32 =
+    sqrt(sum_c (scale_c r_c)^2), residual (C,3,D,H,W) float32 or None, isummary (C,2) int64, fsummary (C,3) float64), all on
+    the device: include/irsgmcmc.h gives the columns.  (t, d, d_inv) gives phi^-1 o phi - id on the fixed grid, (t_inv, d_inv,
+    d) gives phi o phi^-1 - id on the moving grid.  No host synchronisation."""
+    lib = L.load()
+    Cn, D, H, W = _dims5(t_a, 3)
+    for name, t in (('d_a', d_a), ('d_b', d_b)):
+        if tuple(t.shape) != tuple(t_a.shape):
+            raise L.IrsError(f'{name} shape {tuple(t.shape)} does not match t_a {tuple(t_a.shape)}')
+    mask_chains = 1
+    if mask is not None:
+        if mask.dtype not in (torch.bool, torch.uint8) or mask.numel() not in (D * H * W, Cn * D * H * W) or \
+                tuple(mask.shape[-3:]) != (D, H, W):
+            raise L.IrsError(f'mask must be a bool / uint8 (1 or {Cn},1,{D},{H},{W}) tensor, got {mask.dtype} {tuple(mask.shape)}')
+        mask_chains = mask.numel() // (D * H * W)
+        mask = mask.contiguous()
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    dev = t_a.device
+    ws = torch.empty(L.IRS_ICE_WS_BYTES, device=dev, dtype=torch.uint8)
+    norm = torch.empty((Cn, 1, D, H, W), device=dev, dtype=torch.float32)
+    residual = torch.empty_like(t_a) if want_residual else None
+    isummary = torch.empty((Cn, L.IRS_ICE_SUMMARY_INTS), device=dev, dtype=torch.int64)
+    fsummary = torch.empty((Cn, L.IRS_ICE_SUMMARY_FLOATS), device=dev, dtype=torch.float64)
+    L.check(lib.irs_inverse_consistency(L.dev_ptr(t_a, torch.float32), L.dev_ptr(d_a, torch.float32), L.dev_ptr(d_b, torch.float32),
+                                        _three_positive('scale', (1.0, 1.0, 1.0) if scale is None else scale),
+                                        L.dev_ptr(mask, torch.uint8, True), mask_chains, L.dev_ptr(residual, None, True),
+                                        L.dev_ptr(norm), L.dev_ptr(isummary), L.dev_ptr(fsummary), L.dev_ptr(ws),
+                                        L.IRS_ICE_WS_BYTES, Cn, D, H, W, L.stream_ptr()))
+    return norm, residual, isummary, fsummary
+
+
+def _ice_state(mean, peak, shape):
+    for name, t in (('mean', mean), ('peak', peak)):
+        if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32:
+            raise L.IrsError(f'{name} must be a {tuple(shape)} torch.float32 tensor, got {t.dtype} {tuple(t.shape)}')
+
+
+def inverse_consistency_update(norm, mean, peak, records_before):
+    """Fold one recorded step of inverse-consistency norm maps into their per-voxel posterior (absent in the reference): norm
+    (C,1,D,H,W) float32, every chain's map; mean / peak (D,H,W) float32: the Welford mean and the running maximum of the
+    finite values, folded in chain order after `records_before` records (0 overwrites the state).  Non-finite values
+    propagate into mean; peak is NaN where no value was ever finite.  No host synchronisation."""
+    lib = L.load()
+    Cn, D, H, W = _dims5(norm, 1)
+    _ice_state(mean, peak, (D, H, W))
+    L.check(lib.irs_inverse_consistency_update(L.dev_ptr(norm, torch.float32), Cn, D, H, W, L.dev_ptr(mean, torch.float32),
+                                               L.dev_ptr(peak, torch.float32), int(records_before), L.stream_ptr()))
+
+
+def inverse_consistency_finalize(mean, peak, threshold, mask=None):
+    """The masked summary of the mean and peak inverse-consistency maps (absent in the reference).  mean / peak (D,H,W)
+    float32; threshold: a finite float > 0 in the unit of the maps; mask (D,H,W) bool / uint8 or None.  -> (isummary (3,) int64
+    {voxels, voxels with a non-finite mean, voxels with peak > threshold}, fsummary (3,) float64 {sum mean, max mean, max
+    peak}), on the device.  No host synchronisation."""
+    lib = L.load()
+    if mean.dim() != 3:
+        raise L.IrsError(f'mean must have shape (D,H,W), got {tuple(mean.shape)}')
+    D, H, W = mean.shape
+    _ice_state(mean, peak, (D, H, W))
+    mask = _volume_mask(mask, D, H, W)
+    threshold = float(threshold)
+    if not (math.isfinite(threshold) and threshold > 0):
+        raise L.IrsError(f'threshold must be a finite float > 0, got {threshold}')
+    dev = mean.device
+    ws = torch.empty(L.IRS_ICE_MAP_WS_BYTES, device=dev, dtype=torch.uint8)
+    isummary = torch.empty(L.IRS_ICE_MAP_SUMMARY_INTS, device=dev, dtype=torch.int64)
+    fsummary = torch.empty(L.IRS_ICE_MAP_SUMMARY_FLOATS, device=dev, dtype=torch.float64)
+    L.check(lib.irs_inverse_consistency_finalize(L.dev_ptr(mean, torch.float32), L.dev_ptr(peak, torch.float32), D, H, W,
+                                                 L.dev_ptr(mask, torch.uint8, True), threshold, L.dev_ptr(isummary),
+                                                 L.dev_ptr(fsummary), L.dev_ptr(ws), L.IRS_ICE_MAP_WS_BYTES, L.stream_ptr()))
+    return isummary, fsummary

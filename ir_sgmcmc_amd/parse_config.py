@@ -11,9 +11,10 @@ from pathlib import Path
 import numpy as np
 
 from .data_loader import data_loaders as module_data
-from .diagnostics import (COVARIANCE_METRICS, JACOBIAN_METRICS, LABEL_STRUCTURE_METRICS, QUANTILE_METRICS, diagnostics_period,
-                          displacement_covariance_options, displacement_quantiles_options, ess_options, hausdorff_metric_names,
-                          hausdorff_options, jacobian_posterior_options, label_posterior_options)
+from .diagnostics import (COVARIANCE_METRICS, ICE_SPACES, JACOBIAN_METRICS, LABEL_STRUCTURE_METRICS, QUANTILE_METRICS,
+                          diagnostics_period, displacement_covariance_options, displacement_quantiles_options, ess_options,
+                          hausdorff_metric_names, hausdorff_options, inverse_consistency_options, jacobian_posterior_options,
+                          label_posterior_options)
 from .logger import setup_logging
 from .model import distributions as model_distr
 from .model import loss as model_loss
@@ -111,6 +112,13 @@ class ConfigParser:
             m += [f'MCMC/covariance/{k}' for k in COVARIANCE_METRICS]
         if displacement_quantiles_options(self['trainer']) is not None:
             m += [f'MCMC/quantiles/{k}' for k in QUANTILE_METRICS]
+        ice = inverse_consistency_options(self['trainer'])
+        if ice is not None:
+            for i in range(C):
+                m += [f'MCMC/chain_{i}/ICE/{space}/{k}' for space in ICE_SPACES for k in ('mean', 'max')]
+                if ice['moving_space_dice']:
+                    m += [f'MCMC/chain_{i}/DSC_inverse/{s}' for s in self.structures_dict]
+            m += [f'MCMC/ICE/{space}/{k}' for space in ICE_SPACES for k in ('mean', 'max', f'frac_above_{ice["threshold"]:g}')]
         return m
 
     def init_transformation_and_registration_modules(self):

@@ -18,21 +18,24 @@ import numpy as np
 import torch
 
 from ..base import BaseTrainer
-from ..diagnostics import (COVARIANCE_METRICS, ChainMoments, DisplacementCovariance, DisplacementQuantiles, JACOBIAN_METRICS,
-                           JacobianPosterior, LABEL_STRUCTURE_METRICS, LabelPosterior, QUANTILE_METRICS, diagnostics_period,
-                           displacement_covariance_options, displacement_quantiles_options, ess_options, hausdorff_options,
-                           is_recorded, jacobian_posterior_options, label_posterior_options)
+from .. import ops
+from ..diagnostics import (COVARIANCE_METRICS, ChainMoments, DisplacementCovariance, DisplacementQuantiles, ICE_SPACES,
+                           InverseConsistency, JACOBIAN_METRICS, JacobianPosterior, LABEL_STRUCTURE_METRICS, LabelPosterior,
+                           QUANTILE_METRICS, diagnostics_period, displacement_covariance_options, displacement_quantiles_options,
+                           ess_options, hausdorff_options, inverse_consistency_options, is_recorded, jacobian_posterior_options,
+                           label_posterior_options)
 from ..engine import EngineConfig, TransitionEngine
 from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_quantiles, save_ess,
-                      save_jacobian_posterior, save_label_posterior, save_rhat, save_sample)
-from ..utils import calc_norm, calc_no_non_diffeomorphic_voxels, sample_q_v
+                      save_field, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_rhat, save_sample)
+from ..utils import calc_DSC_GPU, calc_norm, calc_no_non_diffeomorphic_voxels, sample_q_v
 from .vi import VIMixin
 
 
 # A posterior recorder of the MCMC stage (Trainer._recorders): its checkpoint key, its state object (diagnostics.py), its
-# period, the trainer.<option> that switches it on, the noun of the resume error, the transition output it records
-# ('displacement', 'transformation' or 'seg_warped': the warped moving segmentation), its _finish_* method and what that
-# takes first ('fixed': the fixed image's dict, 'moving_mask': the mask of the displacement std map)
+# period, the trainer.<option> that switches it on, the noun of the resume error, what it records of a transition (an
+# output: 'displacement', 'transformation'; 'seg_warped': the warped moving segmentation; 'velocity': the dense velocity the
+# exponential integrated; or a tuple of these, recorded as a tuple), its _finish_* method and what that takes first ('fixed':
+# the fixed image's dict, 'moving_mask': the mask of the displacement std map, 'masks': {'fixed': ..., 'moving': ...})
 Recorder = namedtuple('Recorder', 'key state period option noun records finish takes')
 
 
@@ -96,6 +99,11 @@ class Trainer(VIMixin, BaseTrainer):
         self.displacement_quantiles, self.displacement_ci_width, self.displacement_quantiles_summary = None, None, None
         # Hausdorff and percentile surface distances next to every logged ASD: None when trainer.hausdorff is off
         self.hausdorff_options = hausdorff_options(cfg_trainer)
+        # inverse transformation and inverse-consistency error maps (diagnostics.InverseConsistency): None when
+        # trainer.inverse_consistency is off
+        self.ice_options = inverse_consistency_options(cfg_trainer)
+        self._inverse_consistency = None
+        self.ice_summary = None
 
     # ---------------------------------------------------------------- engine plumbing
     def _engine_config(self):
@@ -180,7 +188,8 @@ class Trainer(VIMixin, BaseTrainer):
         return self._scalars_cache
 
     def _recorders(self):
-        """the active recorders, in the order they record and finish: moments, labels, Jacobian, covariance, quantiles"""
+        """the active recorders, in the order they record and finish: moments, labels, Jacobian, covariance, quantiles,
+        inverse consistency"""
         period = lambda options: options and options['period']
         rows = (('chain_moments', self._chain_moments, self.diagnostics_period, 'convergence_diagnostics', 'chain moments',
                  'displacement', self._finish_diagnostics, 'moving_mask'),
@@ -192,7 +201,9 @@ class Trainer(VIMixin, BaseTrainer):
                  'displacement_covariance', 'displacement covariance', 'displacement', self._finish_displacement_covariance,
                  'moving_mask'),
                 ('displacement_quantiles', self._displacement_quantiles, period(self.quantiles_options), 'displacement_quantiles',
-                 'displacement quantiles', 'displacement', self._finish_displacement_quantiles, 'moving_mask'))
+                 'displacement quantiles', 'displacement', self._finish_displacement_quantiles, 'moving_mask'),
+                ('inverse_consistency', self._inverse_consistency, period(self.ice_options), 'inverse_consistency',
+                 'inverse consistency', ('velocity', 'transformation', 'displacement'), self._finish_inverse_consistency, 'masks'))
         return [Recorder(*row) for row in rows if row[1] is not None]
 
     # ---------------------------------------------------------------- checkpoint / resume (absent in the reference)
@@ -356,6 +367,12 @@ class Trainer(VIMixin, BaseTrainer):
             self.logger.info(f'displacement quantiles: {q["bins"]} bins of {q["bin_width"]:g} voxels, '
                              f'{self._displacement_quantiles.bytes_per_voxel(q["bins"])} bytes per voxel, '
                              f'{self._displacement_quantiles.state_bytes() / 1e6:.1f} MB on the device')
+        masks = {'fixed': fixed['mask'][0], 'moving': moving.get('mask', fixed['mask'])[0]}
+        if self.ice_options is not None:
+            self._inverse_consistency = InverseConsistency(self._outputs['displacement'].shape[2:], self.device,
+                                                           getattr(self.transformation_module, 'no_steps', 12), masks)
+        ice_dice = (self.ice_options is not None and self.ice_options['moving_space_dice'] and 'seg' in moving and 'seg' in fixed
+                    and bool(self.structures_dict))
         if cfg_trainer.get('resume'):
             self.load_checkpoint(cfg_trainer['resume'])
             first = self._sample_no + 1
@@ -370,6 +387,7 @@ class Trainer(VIMixin, BaseTrainer):
             if sample_no == self.no_iters_burn_in:
                 log('ENDED BURNING IN')
             seg_warped = None  # the warped segmentation of this step, when the Dice / ASD branch builds it
+            logged = False  # a step whose sample is logged (and, with save_samples, saved)
             self.writer.set_step(sample_no)
             if (sample_no - 1) % every == 0:
                 st = self.sync_parameters()
@@ -395,6 +413,7 @@ class Trainer(VIMixin, BaseTrainer):
                 # kernel-variant prediction is re-run by a LATER call, and until then the output buffers hold an earlier sample
                 # (one sync per log_period; normally a no-op)
                 self.engine.flush()
+                logged = True
                 transformation, displacement = output['transformation'], output['displacement']
                 no_folds, log_det_J = calc_no_non_diffeomorphic_voxels(transformation, self.diff_op)
                 if 'seg' in moving and 'seg' in fixed and self.structures_dict:
@@ -422,7 +441,31 @@ class Trainer(VIMixin, BaseTrainer):
             for r in due:
                 if r.records == 'seg_warped' and seg_warped is None:
                     seg_warped = self.registration_module(moving['seg'], output['transformation'])
-                r.state.record(seg_warped if r.records == 'seg_warped' else output[r.records])
+                pick = lambda name: (seg_warped if name == 'seg_warped' else
+                                     self._dense_velocity(output) if name == 'velocity' else output[name])
+                r.state.record(tuple(pick(n) for n in r.records) if isinstance(r.records, tuple) else pick(r.records))
+            if self._inverse_consistency is not None:
+                ice = self._inverse_consistency
+                recorded = any(r.state is ice for r in due)
+                if recorded:
+                    for space, chains in ice.last_summaries().items():
+                        for idx, cs in enumerate(chains):
+                            self.metrics.update(f'MCMC/chain_{idx}/ICE/{space}/mean', cs['mean'])
+                            self.metrics.update(f'MCMC/chain_{idx}/ICE/{space}/max', cs['max'])
+                if logged and (ice_dice or save_samples):
+                    # the inverse map of this sample: the recorder's when it just integrated it, else integrated here
+                    t_inv, d_inv = ice.last_inverse if recorded else ops.svf_exp_inverse(self._dense_velocity(output), ice.no_steps)
+                    if ice_dice:  # the fixed segmentation carried into the moving image's space
+                        seg_inv = self.registration_module(fixed['seg'], t_inv)
+                        DSC = calc_DSC_GPU(self.no_chains, moving['seg'].expand_as(seg_inv), seg_inv, self.structures_dict)
+                        for idx in range(self.no_chains):
+                            for j, structure in enumerate(self.structures_dict):
+                                self.metrics.update(f'MCMC/chain_{idx}/DSC_inverse/{structure}', float(DSC[idx][j]))
+                    if save_samples:
+                        for idx in range(self.no_chains):
+                            save_field(self.config.save_dirs, spacing, d_inv[idx] * spacing[0],
+                                       f'chain_{idx}_sample_{sample_no:07}_displacement_inverse', 'MCMC')
+                ice.last_inverse = None  # two fields: not kept between steps
             if checkpoint_period and sample_no % checkpoint_period == 0:
                 self._sample_no, self._moments = sample_no, {'mean': mean, 'm2': m2, 'n': n_rec}
                 folder = self.config.save_dirs['checkpoints']
@@ -435,7 +478,7 @@ class Trainer(VIMixin, BaseTrainer):
             save_displacement_mean_and_std_dev(self.logger, self.config.save_dirs, spacing, self.displacement_mean,
                                                self.displacement_std, moving.get('mask', fixed['mask'])[0].to(mean.dtype), 'MCMC')  # trainer.py:461-462: the MOVING mask
         for r in recorders:
-            r.finish(fixed if r.takes == 'fixed' else moving.get('mask', fixed['mask'])[0], spacing,
+            r.finish(fixed if r.takes == 'fixed' else masks if r.takes == 'masks' else masks['moving'], spacing,
                      cfg_trainer.get('save_outputs', True))
 
         # speed test (trainer.py:467-476): 100 x [transition + nearest-neighbour warp of the segmentation]
@@ -560,6 +603,33 @@ class Trainer(VIMixin, BaseTrainer):
         if save_outputs:
             save_displacement_quantiles(self.logger, self.config.save_dirs, spacing, opt['probs'], self.displacement_quantiles,
                                         self.displacement_ci_width, mask, 'MCMC')
+
+    def _dense_velocity(self, output):
+        """the velocity field the forward exponential of this transition integrated, (C,3,D,H,W) in voxel units: the recorded
+        sample itself for SVF_3D, its B-spline up-sampling for SVFFD_3D"""
+        v = output['curr_state']
+        if self.config['transformation_module']['type'] == 'SVFFD_3D':
+            return ops.ffd_up(v.contiguous(), tuple(self._outputs['displacement'].shape[2:]),
+                              tuple(self.config['transformation_module']['args']['cps']))
+        return v
+
+    def _finish_inverse_consistency(self, masks, spacing, save_outputs):
+        """mean and peak maps of the inverse-consistency error (voxels) in both orders and their summaries -> self.ice_summary
+        ({'records', 'fixed': {...}, 'moving': {...}}), the MCMC/ICE/{fixed,moving}/* metrics and, with save_outputs,
+        samples/MCMC_ICE_{fixed,moving}_{mean,max}[_masked].nii.gz.  |phi^-1 o phi - id| lives on the fixed grid and is summarised
+        over the FIXED mask; |phi o phi^-1 - id| lives on the moving grid and is summarised over the MOVING mask."""
+        ice, thr = self._inverse_consistency, self.ice_options['threshold']
+        summary = ice.finalize(masks, thr)
+        self.ice_summary = {'records': ice.records, 'threshold': thr, **summary}
+        for space in ICE_SPACES:
+            s = summary[space]
+            for key in ('mean', 'max', f'frac_above_{thr:g}'):
+                self.metrics.update(f'MCMC/ICE/{space}/{key}', s[key])
+            self.logger.info(f'inverse consistency of {s["records"]} samples on the {space} grid over {s["voxels"]} masked voxels '
+                             f'({s["nonfinite_voxels"]} non-finite): mean {s["mean"]:.3g}, max {s["max"]:.3g} voxels, '
+                             f'{100 * s[f"frac_above_{thr:g}"]:.3f} % of the voxels above {thr:g} in some sample')
+        if save_outputs:
+            save_inverse_consistency(self.logger, self.config.save_dirs, spacing, ice.mean, ice.peak, masks, 'MCMC')
 
     def _run_model(self):
         for fixed, moving, var_params_q_v in self.data_loader:

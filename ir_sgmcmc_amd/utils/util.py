@@ -216,6 +216,22 @@ def calc_displacement_quantiles(displacements, probs=(0.05, 0.5, 0.95), mask=Non
 
 
 @torch.no_grad()
+def calc_inverse_consistency(v, transformation_module):
+    """Inverse-consistency error of the map a transformation module makes of the velocity v (absent in the reference): v
+    (C,3,...) float32 on the device, what `transformation_module` (SVF_3D or SVFFD_3D) takes.  -> {'fixed': |phi^-1 o phi - id|,
+    'moving': |phi o phi^-1 - id|, both (C,1,D,H,W) float32 in voxels, 'transformation_inverse', 'displacement_inverse':
+    (C,3,D,H,W)}.  For SVFFD_3D the dense velocity is the B-spline up-sampling of v: what the forward exponential integrates."""
+    svf = getattr(transformation_module, 'SVF_3D', transformation_module)
+    dense = transformation_module.cubic_B_spline_FFD(v) if hasattr(transformation_module, 'cubic_B_spline_FFD') else v
+    dense = dense.float().contiguous()
+    transformation, displacement = svf(dense)
+    t_inv, d_inv = _ops.svf_exp_inverse(dense, getattr(svf, 'no_steps', 12))
+    return {'fixed': _ops.inverse_consistency(transformation, displacement, d_inv)[0],
+            'moving': _ops.inverse_consistency(t_inv, d_inv, displacement)[0],
+            'transformation_inverse': t_inv, 'displacement_inverse': d_inv}
+
+
+@torch.no_grad()
 def calc_DSC_GPU(no_samples, seg_fixed, seg_moving, structures_dict):
     """Dice scores on the device (utils/util.py:123-148)"""
     DSC = torch.zeros(no_samples, len(structures_dict))
