@@ -354,6 +354,29 @@ int irs_inverse_consistency_finalize(const float* mean, const float* peak, int D
                                      float threshold, long long* isummary, double* fsummary, void* ws, size_t ws_bytes,
                                      void* stream);
 
+/* Native-resolution outputs (absent in the reference, whose outputs all live on the registration grid): a sampled
+ * transformation applied on the image's own voxel grid.  The data set pads the native volume `native` = (n0, n1, n2) by
+ * `padding` = (p0, p1, p2) voxels on both sides of each axis (P_a = n_a + 2 p_a) and resizes the padded volume to the
+ * registration grid `dims` = (m0, m1, m2) trilinearly with align_corners, so native index i_a sits at grid coordinate
+ * (i_a + p_a) (m_a - 1) / (P_a - 1) and a normalised displacement u_a is u_a (P_a - 1) / 2 padded native voxels.
+ *  - irs_native_warp: per chain and native voxel, grid_sample (border, align_corners) of the PADDED native volume at identity +
+ *    the displacement resized trilinearly (align_corners) from `dims` to P, cropped to the native box; the pad holds `fill`
+ *    for the image and 0 for the segmentation and the mask.  Neither the padded volumes nor the resized field are ever
+ *    formed: one launch walks the native grid, interpolates the three channels of the displacement at the voxel's grid
+ *    coordinate, forms the source position r_a = (i_a + p_a) + u_a (P_a - 1) / 2 (one product, one sum: a zero displacement
+ *    returns the moving volumes bit for bit), clamps it to [0, P_a - 1] and reads the taps from the unpadded volumes, a tap
+ *    outside the native box being the fill.  displacement (C,3,m0,m1,m2) float32 in [-1,1] coordinates, channel 0 the last
+ *    axis; C in 1 .. IRS_MAX_CHAINS; native: every n_a >= 1, fewer than 2^30 voxels; padding: every p_a >= 0; P_a >= 2; dims:
+ *    every m_a >= 2.  im float32 / seg int16 / mask uint8: (Cim,1,n0,n1,n2) with Cim 1 (shared by the chains) or C, each
+ *    NULL when its output is.  im_out float32 (trilinear) / seg_out int16 / mask_out uint8 (nearest, half to even as
+ *    irs_warp_nearest_*): (C,1,n0,n1,n2) or NULL.  displacement_out (C,3,n0,n1,n2) float32 or NULL: the interpolated
+ *    displacement times scale[c], three finite host floats, one per channel ((P_a - 1) / 2 of the channel's axis for native
+ *    voxels, times the zoom for mm; NULL with a NULL output).  fill: finite.  At least one output must be asked for.
+ *    Deterministic; no atomics; no host sync. */
+int irs_native_warp(const float* displacement, int C, const int32_t* dims, const int32_t* native, const int32_t* padding,
+                    const float* im, const int16_t* seg, const uint8_t* mask, int Cim, float fill, const float* scale,
+                    float* im_out, int16_t* seg_out, uint8_t* mask_out, float* displacement_out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * fused transition (Trainer._SGLD_transition, trainer/trainer.py:291-356)
  * ---------------------------------------------------------------------------------------------- */

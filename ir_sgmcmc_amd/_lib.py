@@ -168,6 +168,7 @@ SIGNATURES = {
     'irs_inverse_consistency': [_P, _P, _P, C.POINTER(C.c_float), _P, _I, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _P],
     'irs_inverse_consistency_update': [_P, _I, _I, _I, _I, _P, _P, _I, _P],
     'irs_inverse_consistency_finalize': [_P, _P, _I, _I, _I, _P, _F, _P, _P, _P, C.c_size_t, _P],
+    'irs_native_warp': [_P, _I, _I32P, _I32P, _I32P, _P, _P, _P, _I, _F, C.POINTER(C.c_float), _P, _P, _P, _P, _P],
     'irs_create': [C.POINTER(IrsConfig), C.POINTER(_P)],
     'irs_destroy': [_P],
     'irs_workspace_bytes': [_P],

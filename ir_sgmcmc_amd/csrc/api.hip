@@ -1071,6 +1071,55 @@ int irs_inverse_consistency_finalize(const float* mean, const float* peak, int D
 }
 
 // ================================================================================================
+// native-resolution outputs (native_kernels.hip)
+// ================================================================================================
+int irs_native_warp(const float* displacement, int C, const int32_t* dims, const int32_t* native, const int32_t* padding,
+                    const float* im, const int16_t* seg, const uint8_t* mask, int Cim, float fill, const float* scale,
+                    float* im_out, int16_t* seg_out, uint8_t* mask_out, float* displacement_out, void* stream) {
+    if (!displacement || !dims || !native || !padding) return fail("irs_native_warp: bad arguments");
+    if (C < 1 || C > IRS_MAX_CHAINS) return fail("irs_native_warp: C = %d chains, 1..%d", C, IRS_MAX_CHAINS);
+    if (Cim != 1 && Cim != C) return fail("irs_native_warp: moving volumes of %d chains, 1 or %d needed", Cim, C);
+    if (!im_out && !seg_out && !mask_out && !displacement_out) return fail("irs_native_warp: no output requested");
+    if ((im_out && !im) || (seg_out && !seg) || (mask_out && !mask))
+        return fail("irs_native_warp: an output is requested of a moving volume that is NULL");
+    if (displacement_out && !scale) return fail("irs_native_warp: displacement_out needs scale");
+    NativeGeom gm;
+    int64_t voxels = 1;
+    for (int a = 0; a < 3; ++a) {
+        const int64_t P = (int64_t)native[a] + 2 * (int64_t)padding[a];
+        if (native[a] < 1) return fail("irs_native_warp: native[%d] = %d < 1", a, native[a]);
+        if (padding[a] < 0) return fail("irs_native_warp: padding[%d] = %d < 0", a, padding[a]);
+        if (P < 2) return fail("irs_native_warp: padded extent %lld of axis %d, >= 2 needed", (long long)P, a);
+        if (dims[a] < 2) return fail("irs_native_warp: dims[%d] = %d < 2", a, dims[a]);
+        if (P >= ((int64_t)1 << 24)) return fail("irs_native_warp: padded extent %lld of axis %d is not exact in float32", (long long)P, a);
+        voxels *= native[a];
+        gm.n[a] = native[a];
+        gm.p[a] = padding[a];
+        gm.P[a] = (int)P;
+        gm.m[a] = dims[a];
+        gm.grid_step[a] = (float)((double)(dims[a] - 1) / (double)(P - 1));
+        gm.half_extent[a] = 0.5f * (float)(P - 1);
+        gm.out_scale[a] = 0.0f;
+        if (voxels >= ((int64_t)1 << 30)) return fail("irs_native_warp: the native volume must have fewer than 2^30 voxels");
+    }
+    if (!dims_ok(C, dims[0], dims[1], dims[2])) return fail("irs_native_warp: bad dims");
+    // the launch is one block row per (chain, plane) and per four rows of a plane
+    if ((int64_t)native[0] * C > 65535 || (native[1] + 3) / 4 > 65535)
+        return fail("irs_native_warp: native shape (%d, %d, %d) x %d chains exceeds the launch grid", native[0], native[1], native[2], C);
+    if (displacement_out)
+        for (int c = 0; c < 3; ++c) {
+            if (!isfinite(scale[c])) return fail("irs_native_warp: scale[%d] = %g, a finite value needed", c, (double)scale[c]);
+            gm.out_scale[c] = scale[c];
+        }
+    if (!isfinite(fill)) return fail("irs_native_warp: fill = %g, a finite value needed", (double)fill);
+    gm.fill = fill;
+    launch_native_warp(displacement, im_out ? im : nullptr, seg_out ? seg : nullptr, mask_out ? mask : nullptr,
+                       Cim == 1 ? 0 : voxels, im_out, seg_out, mask_out, displacement_out, gm, C, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // context
 // ================================================================================================
 

@@ -250,6 +250,21 @@ void launch_inverse_consistency_update(const float* norm, int C, int64_t V, floa
 void launch_inverse_consistency_finalize(const float* mean, const float* peak, int64_t V, const uint8_t* mask, float threshold,
                                          long long* isummary, double* fsummary, void* ws, hipStream_t st);
 
+// ---- native_kernels.hip: the transformation applied on the image's own voxel grid (absent in the reference)
+// Axis order (D, H, W) in every array of three but out_scale, which is per channel (channel c belongs to axis 2 - c).
+struct NativeGeom {
+    int n[3], p[3], P[3], m[3];  // native shape, padding per side, padded extent n + 2 p, registration grid
+    float grid_step[3];          // (m - 1) / (P - 1): grid voxels per padded native voxel
+    float half_extent[3];        // (P - 1) / 2: padded native voxels per unit of normalised displacement
+    float out_scale[3];          // factor of the displacement output
+    float fill;                  // what the pad of the image holds
+};
+// u (C,3,m) float32; im float32 / seg int16 / mask uint8: (1 or C, n) with moving_stride 0 or n0 n1 n2, or nullptr; the
+// outputs (C,n) and disp_out (C,3,n), or nullptr; a volume must be given for every output asked for, at least one output
+void launch_native_warp(const float* u, const float* im, const int16_t* seg, const uint8_t* mask, int64_t moving_stride,
+                        float* im_out, int16_t* seg_out, uint8_t* mask_out, float* disp_out, const NativeGeom& gm, int C,
+                        hipStream_t st);
+
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h
 }  // namespace irs

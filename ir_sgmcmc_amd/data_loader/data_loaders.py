@@ -15,6 +15,8 @@ class SyntheticDataLoader:
         self.sigma_v_init, self.u_v_init, self.seed = sigma_v_init, u_v_init, seed
         self.im_spacing = None
 
+    native = None  # no volumes at another resolution than `dims` (BiobankDataLoader.native)
+
     @property
     def dims_v(self):
         return control_grid_size(self.dims, self.cps) if self.cps else self.dims
@@ -60,6 +62,11 @@ class BiobankDataLoader(SyntheticDataLoader):
     @im_spacing.setter
     def im_spacing(self, value):   # the synthetic base class assigns None in its constructor
         pass
+
+    @property
+    def native(self):
+        """BiobankDataset.native_pair, the pair at its own resolution (a callable), or None on the synthetic fallback"""
+        return self.dataset.native_pair if self.dataset is not None else None
 
     def __iter__(self):
         if self.dataset is None:

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from ..native import NativeGrid
 from ..ops import control_grid_size
 from ..utils.imageio import read_nifti
 
@@ -24,6 +25,7 @@ class BiobankDataset:
         self.dims_im = (1, *self.dims)
         self.dims_v = (3, *self.dims) if cps is None else (3, *control_grid_size(self.dims, cps))
         self.padding, self.im_spacing = None, None
+        self.zooms = None  # the header zooms of the first volume read, in the axis order of its array
 
         im_filenames = self._get_filenames(im_paths)
         mask_filenames = self._get_filenames(path.join(im_paths, 'masks'))
@@ -46,9 +48,11 @@ class BiobankDataset:
         return ['' for _ in range(2)]
 
     def _padded(self, file_path):
-        arr, _ = read_nifti(file_path, np.float32)
+        arr, zooms = read_nifti(file_path, np.float32)
         if arr.ndim != 3:
             raise ValueError(f'{file_path}: expected a 3-D volume, got shape {arr.shape}')
+        if self.zooms is None:
+            self.zooms = zooms
         if self.im_spacing is None:
             self.im_spacing = torch.tensor(max(arr.shape) / np.asarray(self.dims), dtype=torch.float32)
         if self.padding is None:
@@ -67,6 +71,30 @@ class BiobankDataset:
 
     def _load(self, triple):
         return {'im': self._get_image(triple['im']), 'mask': self._get_mask(triple['mask']), 'seg': self._get_seg(triple['seg'])}
+
+    def native_pair(self, idx=0):
+        """The pair at its own resolution (absent in the reference, which keeps the resized volumes only): the files are read
+        again here, nothing is held by the data set.  -> {'fixed': {...}, 'moving': {...}, 'grid': NativeGrid, 'fill': {'fixed':
+        f, 'moving': f}}; the dicts hold the UNPADDED 'im' float32, 'mask' bool and 'seg' int16 tensors of shape (1, *native
+        shape), 'fill' the minimum each image is padded with, and the grid carries the header zooms of the fixed image.  The data
+        set applies ONE padding to every volume, so volumes of different shapes are refused."""
+        triples = {'fixed': self.im_mask_seg_triples[0], 'moving': self.im_mask_seg_triples[idx + 1]}
+        out, shape, zooms, fill = {}, None, None, {}
+        for side, triple in triples.items():
+            out[side] = {}
+            for key, dtype in (('im', torch.float32), ('mask', torch.bool), ('seg', torch.int16)):
+                arr, z = read_nifti(triple[key], np.float32)
+                if arr.ndim != 3:
+                    raise ValueError(f'{triple[key]}: expected a 3-D volume, got shape {arr.shape}')
+                if shape is None:
+                    shape, zooms = arr.shape, z
+                elif arr.shape != shape:
+                    raise ValueError(f'{triple[key]}: shape {arr.shape} differs from {shape} of {triples["fixed"]["im"]}; the '
+                                     f'native-resolution outputs need fixed and moving volumes of one shape (the data set pads '
+                                     f'them all alike)')
+                out[side][key] = torch.from_numpy(arr).to(dtype).unsqueeze(0)
+            fill[side] = float(out[side]['im'].min())
+        return {**out, 'grid': NativeGrid.from_shape(shape, self.dims, zooms), 'fill': fill}
 
     def __getitem__(self, idx):
         fixed = self._load(self.im_mask_seg_triples[0])

@@ -36,6 +36,10 @@ a running maximum (ops.inverse_consistency_update): 16 * D * H * W bytes whateve
 
 The Hausdorff option (hausdorff_options) is of another kind: it keeps no state.  It adds the Hausdorff and percentile surface
 distances of the propagated segmentation to the point-estimate metrics wherever the ASD is logged.
+
+The native-resolution option (native_resolution_options) keeps no state either: at a logged step it carries the sampled
+transformation to the image's own voxel grid (ops.native_warp, native.NativeGrid) and logs Dice and the surface distances there,
+in mm under the header zooms.
 """
 import math
 import numbers
@@ -893,3 +897,43 @@ def hausdorff_options(cfg_trainer):
 def hausdorff_metric_names(options):
     """the metric names next to 'ASD' that the option adds: 'HD', then 'HD95' and the like"""
     return ['HD'] + [f'HD{q:g}' for q in options['percentiles']]
+
+
+NATIVE_OPTION_KEYS = ('period', 'save')
+NATIVE_SAVE_KEYS = ('im', 'seg', 'displacement')
+
+
+def native_resolution_options(cfg_trainer, data_loader=None):
+    """`trainer.native_resolution` -> None when off, else {'period': P or None, 'save': (...)}.
+    Absent / false / null: off.  true: the native metrics at every logged step, the warped image of a saved sample.
+    {"period": P, "save": [...]}: also at every P-th step after the burn-in; `save` lists what a saved sample writes on the
+    native grid, a subset of "im", "seg", "displacement".  Refuses unknown keys, a non-integer P or P < 1, a `save` that is not
+    a list of those names and -- when `data_loader` is given -- a loader without native volumes (`data_loader.native` None:
+    the synthetic pair, which has no resolution but `dims`)."""
+    what = 'trainer.native_resolution'
+    opt = cfg_trainer.get('native_resolution', False)
+    if opt is None or opt is False:
+        return None
+    period, save = None, ('im',)
+    if isinstance(opt, dict):
+        unknown = set(opt) - set(NATIVE_OPTION_KEYS)
+        if unknown:
+            raise ValueError(f'{what}: unknown keys {sorted(unknown)}; known: {list(NATIVE_OPTION_KEYS)}')
+        if 'period' in opt:
+            p = opt['period']
+            if isinstance(p, bool) or not isinstance(p, numbers.Integral):
+                raise ValueError(f'{what}.period must be an integer, got {p!r}')
+            if p < 1:
+                raise ValueError(f'{what}: the period must be >= 1, got {p}')
+            period = int(p)
+        if 'save' in opt:
+            save = opt['save']
+            if not isinstance(save, (list, tuple)) or any(s not in NATIVE_SAVE_KEYS for s in save) or len(set(save)) != len(save):
+                raise ValueError(f'{what}.save must be a list of distinct names out of {list(NATIVE_SAVE_KEYS)}, got {save!r}')
+            save = tuple(s for s in NATIVE_SAVE_KEYS if s in save)
+    elif opt is not True:
+        raise ValueError(f'{what} must be true, false or {{"period": P, "save": [...]}}, got {opt!r}')
+    if data_loader is not None and getattr(data_loader, 'native', None) is None:
+        raise ValueError(f'{what}: the data loader ({type(data_loader).__name__}) has no native volumes -- the synthetic pair exists '
+                         f'at `dims` only; the option needs a BiobankDataLoader reading NIfTI files')
+    return {'period': period, 'save': save}

@@ -199,3 +199,25 @@ def save_inverse_consistency(logger, save_dirs, spacing, mean, peak, masks, mode
         for name, im in (('mean', mean[space]), ('max', peak[space])):
             save_im_to_disk(im, path.join(folder, f'{model}_ICE_{space}_{name}.nii.gz'), spacing)
             save_im_to_disk(im.where(mask, im.new_zeros(())), path.join(folder, f'{model}_ICE_{space}_{name}_masked.nii.gz'), spacing)
+
+
+def save_native_sample(save_dirs, zooms, sample_no, chain_no, im=None, seg=None, displacement_mm=None, model='MCMC'):
+    """one sample on the image's own voxel grid (absent in the reference): samples/{model}/chain_{c}_sample_{N}
+    _im_moving_warped_native.nii.gz (float32), _seg_moving_warped_native.nii.gz (int16) and _displacement_native.vtk (mm), each
+    when given; `zooms`: the header zooms in the axis order of the arrays, written as the files' spacing"""
+    prefix = f'chain_{chain_no}_sample_{sample_no:07}'
+    if im is not None:
+        save_im(save_dirs, zooms, im, f'{prefix}_im_moving_warped_native', model)
+    if seg is not None:
+        save_im(save_dirs, zooms, seg, f'{prefix}_seg_moving_warped_native', model)
+    if displacement_mm is not None:
+        save_field(save_dirs, zooms, displacement_mm, f'{prefix}_displacement_native', model)
+
+
+def save_native_mean(logger, save_dirs, zooms, displacement_mm, im_warped, model='MCMC'):
+    """the posterior-mean displacement carried to the image's own voxel grid, in mm, and the native moving image warped by it
+    (absent in the reference): samples/{model}_sample_mean_native.vtk and samples/{model}_im_moving_warped_mean_native.nii.gz"""
+    folder = _folder(save_dirs, 'samples')
+    logger.info(f'{model} native displacement mean min.: {float(displacement_mm.min()):.2f}, max.: {float(displacement_mm.max()):.2f} mm')
+    save_field_to_disk(displacement_mm, path.join(folder, f'{model}_sample_mean_native.vtk'), zooms)
+    save_im_to_disk(im_warped, path.join(folder, f'{model}_im_moving_warped_mean_native.nii.gz'), zooms)

@@ -702,3 +702,60 @@ def inverse_consistency_finalize(mean, peak, threshold, mask=None):
                                                  L.dev_ptr(mask, torch.uint8, True), threshold, L.dev_ptr(isummary),
                                                  L.dev_ptr(fsummary), L.dev_ptr(ws), L.IRS_ICE_MAP_WS_BYTES, L.stream_ptr()))
     return isummary, fsummary
+
+
+def native_warp(displacement, grid, im=None, seg=None, mask=None, fill=None, want_displacement=None):
+    """A sampled transformation applied on the image's own voxel grid (absent in the reference, whose outputs all live on the
+    registration grid).  displacement (C,3,*grid.dims) float32 in [-1,1] coordinates; grid: a native.NativeGrid; im float32 /
+    seg int16 / mask bool or uint8: the UNPADDED native moving volumes, (1 or C,1,*grid.shape) with one leading size for all of
+    them, or None; fill: what the data set padded the image with (its minimum; default: the minimum of `im`, one host
+    read-back); want_displacement: None, or the three per-channel factors of the displacement output (grid.voxel_scale() for
+    native voxels, grid.mm_scale() for mm).  -> a dict with 'im' (C,1,*shape) float32 (trilinear), 'seg' int16 / 'mask' (nearest)
+    and 'displacement' (C,3,*shape) float32, each present when asked for: grid_sample (border, align_corners) of the padded
+    native volume at identity + the displacement resized to the padded extent, cropped to the native box, in ONE launch that
+    forms neither the padded volumes nor the resized field (include/irsgmcmc.h: irs_native_warp).  No host synchronisation
+    when `fill` is given."""
+    lib = L.load()
+    Cn, D, H, W = _dims5(displacement, 3)
+    if (D, H, W) != tuple(grid.dims):
+        raise L.IrsError(f'displacement {tuple(displacement.shape)} is not on the registration grid {tuple(grid.dims)}')
+    n = tuple(grid.shape)
+    given = [(k, t) for k, t in (('im', im), ('seg', seg), ('mask', mask)) if t is not None]
+    if not given and want_displacement is None:
+        raise L.IrsError('native_warp: nothing asked for (im, seg, mask and want_displacement are all None)')
+    dtypes = {'im': (torch.float32,), 'seg': (torch.int16,), 'mask': (torch.bool, torch.uint8)}
+    for k, t in given:
+        _chain_volumes(k, t, 'the native grid', Cn, *n)
+        if t.dtype not in dtypes[k]:
+            raise L.IrsError(f'{k} must be {" / ".join(str(d) for d in dtypes[k])}, got {t.dtype}')
+        if t.shape[0] != given[0][1].shape[0]:
+            raise L.IrsError(f'the moving volumes must share their leading size: {given[0][0]} has {given[0][1].shape[0]}, '
+                             f'{k} has {t.shape[0]}')
+    if im is not None and fill is None:
+        fill = float(im.min())
+    fill = 0.0 if fill is None else float(fill)
+    if not math.isfinite(fill):
+        raise L.IrsError(f'fill must be finite, got {fill}')
+    scale = None
+    if want_displacement is not None:
+        scale = [float(s) for s in want_displacement]
+        if len(scale) != 3 or not all(math.isfinite(s) for s in scale):
+            raise L.IrsError(f'want_displacement must hold three finite floats, got {scale}')
+        scale = (C.c_float * 3)(*scale)
+    dev = displacement.device
+    out = {}
+    if im is not None:
+        out['im'] = torch.empty((Cn, 1, *n), device=dev, dtype=torch.float32)
+    if seg is not None:
+        out['seg'] = torch.empty((Cn, 1, *n), device=dev, dtype=torch.int16)
+    if mask is not None:
+        out['mask'] = torch.empty((Cn, 1, *n), device=dev, dtype=mask.dtype)
+    if scale is not None:
+        out['displacement'] = torch.empty((Cn, 3, *n), device=dev, dtype=torch.float32)
+    i3 = lambda v: (C.c_int32 * 3)(*[int(x) for x in v])
+    L.check(lib.irs_native_warp(L.dev_ptr(displacement, torch.float32), Cn, i3(grid.dims), i3(n), i3(grid.padding),
+                                L.dev_ptr(im, None, True), L.dev_ptr(seg, None, True), L.dev_ptr(mask, None, True),
+                                given[0][1].shape[0] if given else 1, fill, scale, L.dev_ptr(out.get('im'), None, True),
+                                L.dev_ptr(out.get('seg'), None, True), L.dev_ptr(out.get('mask'), None, True),
+                                L.dev_ptr(out.get('displacement'), None, True), L.stream_ptr()))
+    return out

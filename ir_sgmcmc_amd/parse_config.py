@@ -14,7 +14,7 @@ from .data_loader import data_loaders as module_data
 from .diagnostics import (COVARIANCE_METRICS, ICE_SPACES, JACOBIAN_METRICS, LABEL_STRUCTURE_METRICS, QUANTILE_METRICS,
                           diagnostics_period, displacement_covariance_options, displacement_quantiles_options, ess_options,
                           hausdorff_metric_names, hausdorff_options, inverse_consistency_options, jacobian_posterior_options,
-                          label_posterior_options)
+                          label_posterior_options, native_resolution_options)
 from .logger import setup_logging
 from .model import distributions as model_distr
 from .model import loss as model_loss
@@ -91,12 +91,16 @@ class ConfigParser:
         C = self['trainer']['no_chains']
         m = [f'MCMC/GMM/scale_{i}' for i in range(K)] + [f'MCMC/GMM/proportion_{i}' for i in range(K)] + ['MCMC/avg_loss']
         hausdorff = hausdorff_options(self['trainer'])
+        native = native_resolution_options(self['trainer']) is not None
         for i in range(C):
             m += [f'MCMC/chain_{i}/{t}' for t in ('data_term', 'reg_term', 'VD/alpha', 'reg/energy', 'no_non_diffeomorphic_voxels')]
             m += [f'MCMC/chain_{i}/ASD/{s}' for s in self.structures_dict]
             if hausdorff is not None:
                 m += [f'MCMC/chain_{i}/{k}/{s}' for k in hausdorff_metric_names(hausdorff) for s in self.structures_dict]
             m += [f'MCMC/chain_{i}/DSC/{s}' for s in self.structures_dict]
+            if native:
+                surface = ['ASD'] + (hausdorff_metric_names(hausdorff) if hausdorff is not None else [])
+                m += [f'MCMC/chain_{i}/native/{k}/{s}' for k in surface + ['DSC'] for s in self.structures_dict]
         if diagnostics_period(self['trainer']) is not None:
             m += [f'MCMC/R_hat/{k}' for k in ('max', 'mean', 'frac_above_1.01', 'frac_above_1.1')]
             ess = ess_options(self['trainer'])

@@ -23,11 +23,12 @@ from ..diagnostics import (COVARIANCE_METRICS, ChainMoments, DisplacementCovaria
                            InverseConsistency, JACOBIAN_METRICS, JacobianPosterior, LABEL_STRUCTURE_METRICS, LabelPosterior,
                            QUANTILE_METRICS, diagnostics_period, displacement_covariance_options, displacement_quantiles_options,
                            ess_options, hausdorff_options, inverse_consistency_options, is_recorded, jacobian_posterior_options,
-                           label_posterior_options)
+                           label_posterior_options, native_resolution_options)
 from ..engine import EngineConfig, TransitionEngine
 from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_quantiles, save_ess,
-                      save_field, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_rhat, save_sample)
-from ..utils import calc_DSC_GPU, calc_norm, calc_no_non_diffeomorphic_voxels, sample_q_v
+                      save_field, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_native_mean,
+                      save_native_sample, save_rhat, save_sample)
+from ..utils import calc_DSC_GPU, calc_norm, calc_no_non_diffeomorphic_voxels, sample_q_v, transform_coordinates
 from .vi import VIMixin
 
 
@@ -104,6 +105,10 @@ class Trainer(VIMixin, BaseTrainer):
         self.ice_options = inverse_consistency_options(cfg_trainer)
         self._inverse_consistency = None
         self.ice_summary = None
+        # outputs on the image's own voxel grid (ops.native_warp): None when trainer.native_resolution is off.  No state: the
+        # native volumes go to the device in _run_MCMC
+        self.native_options = native_resolution_options(cfg_trainer, data_loader)
+        self._native = None
 
     # ---------------------------------------------------------------- engine plumbing
     def _engine_config(self):
@@ -373,6 +378,8 @@ class Trainer(VIMixin, BaseTrainer):
                                                            getattr(self.transformation_module, 'no_steps', 12), masks)
         ice_dice = (self.ice_options is not None and self.ice_options['moving_space_dice'] and 'seg' in moving and 'seg' in fixed
                     and bool(self.structures_dict))
+        if self.native_options is not None:
+            self._native_init()
         if cfg_trainer.get('resume'):
             self.load_checkpoint(cfg_trainer['resume'])
             first = self._sample_no + 1
@@ -435,6 +442,10 @@ class Trainer(VIMixin, BaseTrainer):
                         log(f'chain {idx}, sample {sample_no}: detected {no_folds} voxels where the sampled '
                             f'transformation is not diffeomorphic; exiting..')
                         raise SystemExit(1)
+            if self._native is not None and (logged or (self.native_options['period'] is not None and
+                                                        is_recorded(sample_no, self.no_iters_burn_in, self.native_options['period']))):
+                self.engine.flush()  # as above
+                self._log_native(sample_no, output['displacement'], logged and save_samples)
             due = [r for r in recorders if is_recorded(sample_no, self.no_iters_burn_in, r.period)]
             if due:
                 self.engine.flush()  # as above: the buffers hold sample `sample_no` once nothing is pending
@@ -477,6 +488,11 @@ class Trainer(VIMixin, BaseTrainer):
         if n_rec > 0 and cfg_trainer.get('save_outputs', True):
             save_displacement_mean_and_std_dev(self.logger, self.config.save_dirs, spacing, self.displacement_mean,
                                                self.displacement_std, moving.get('mask', fixed['mask'])[0].to(mean.dtype), 'MCMC')  # trainer.py:461-462: the MOVING mask
+        if self._native is not None and n_rec > 0 and cfg_trainer.get('save_outputs', True):
+            nat = self._native
+            out = ops.native_warp(transform_coordinates(mean.unsqueeze(0)).contiguous(), nat['grid'], im=nat['moving_im'],
+                                  fill=nat['fill'], want_displacement=nat['grid'].mm_scale())
+            save_native_mean(self.logger, self.config.save_dirs, nat['grid'].zooms, out['displacement'][0], out['im'][0, 0], 'MCMC')
         for r in recorders:
             r.finish(fixed if r.takes == 'fixed' else masks if r.takes == 'masks' else masks['moving'], spacing,
                      cfg_trainer.get('save_outputs', True))
@@ -603,6 +619,36 @@ class Trainer(VIMixin, BaseTrainer):
         if save_outputs:
             save_displacement_quantiles(self.logger, self.config.save_dirs, spacing, opt['probs'], self.displacement_quantiles,
                                         self.displacement_ci_width, mask, 'MCMC')
+
+    def _native_init(self):
+        """the pair at its own resolution -> the device, once: the moving image and segmentation that are warped, the fixed
+        segmentation they are compared with, the geometry and the value the moving image is padded with"""
+        pair = self.data_loader.native()
+        to = lambda t: t.unsqueeze(0).contiguous().to(self.device)
+        self._native = {'grid': pair['grid'], 'fill': pair['fill']['moving'], 'moving_im': to(pair['moving']['im']),
+                        'moving_seg': to(pair['moving']['seg']), 'fixed_seg': to(pair['fixed']['seg'])}
+        g = pair['grid']
+        self.logger.info(f'native resolution: {g.shape} voxels of {g.zooms} mm, padded by {g.padding} to {g.padded}, '
+                         f'registered at {g.dims}')
+
+    def _log_native(self, sample_no, displacement, save):
+        """the sample carried to the image's own voxel grid in ONE launch: the warped native moving segmentation -> the metrics
+        MCMC/chain_i/native/{DSC,ASD[,HD,HD{q}]}/{structure}, the surface distances in mm under the header zooms; with `save`
+        also what trainer.native_resolution.save lists.  displacement: (C,3,*dims) in voxels of the registration grid, as the
+        transition returns it"""
+        nat, opt = self._native, self.native_options
+        grid = nat['grid']
+        want = set(opt['save']) if save else set()
+        out = ops.native_warp(transform_coordinates(displacement).contiguous(), grid, seg=nat['moving_seg'],
+                              im=nat['moving_im'] if 'im' in want else None, fill=nat['fill'],
+                              want_displacement=grid.mm_scale() if 'displacement' in want else None)
+        if self.structures_dict:
+            self._log_segmentation_metrics([f'MCMC/chain_{idx}/native' for idx in range(self.no_chains)], nat['fixed_seg'],
+                                           out['seg'], grid.spacing_xyz())
+        for idx in range(self.no_chains if save else 0):
+            save_native_sample(self.config.save_dirs, grid.zooms, sample_no, idx, im=out['im'][idx, 0] if 'im' in want else None,
+                               seg=out['seg'][idx, 0] if 'seg' in want else None,
+                               displacement_mm=out['displacement'][idx] if 'displacement' in want else None)
 
     def _dense_velocity(self, output):
         """the velocity field the forward exponential of this transition integrated, (C,3,D,H,W) in voxel units: the recorded

@@ -269,6 +269,25 @@ def calc_surface_metrics(seg_fixed, seg_moving, structures_dict, spacing, percen
     return {'ASD': out['asd'].cpu().numpy(), 'HD': out['hd'].cpu().numpy(), 'HDp': out['hd_pct'].cpu().numpy()}
 
 
+@torch.no_grad()
+def calc_native_metrics(displacement, grid, seg_fixed, seg_moving, structures_dict, percentiles=None):
+    """Dice scores and surface distances on the image's own voxel grid, in real mm (absent in the reference, which measures on
+    the registration grid with a surrogate isotropic spacing): displacement (C,3,*grid.dims) float32 in [-1,1] coordinates;
+    grid: a native.NativeGrid; seg_fixed / seg_moving: the UNPADDED native segmentations, (1,1,*grid.shape) int16 on the
+    device.  The moving segmentation is carried to the native grid (ops.native_warp, nearest) and compared with the fixed one
+    under the header zooms (grid.spacing_xyz()).  -> {'seg': (C,1,*grid.shape) int16, 'DSC': [C, L], 'ASD': [C, L]} and, with
+    `percentiles` (a tuple, possibly empty), 'HD': [C, L] and 'HDp': [Q, C, L]; numpy arrays, as calc_metrics /
+    calc_surface_metrics return them."""
+    seg = _ops.native_warp(displacement, grid, seg=seg_moving)['seg']
+    C, spacing = seg.shape[0], grid.spacing_xyz()
+    if percentiles is None:
+        ASD, DSC = calc_metrics(seg_fixed, seg, structures_dict, spacing, no_samples=C)
+        return {'seg': seg, 'DSC': DSC, 'ASD': ASD}
+    out = calc_surface_metrics(seg_fixed, seg, structures_dict, spacing, percentiles, no_samples=C)
+    fixed = seg_fixed[:1].expand_as(seg) if seg_fixed.shape[0] == 1 else seg_fixed
+    return {'seg': seg, 'DSC': calc_DSC_GPU(C, fixed, seg, structures_dict), **out}
+
+
 def rescale_residuals(res, mask, data_loss):
     """VD-rescaled residual x = sum_k r_k (z / sigma_k)^2 (utils/util.py:330-347).  The reference obtains it as
     sum_k s_k * d(-log p)/d(s_k) with a nested backward; the closed form with the responsibilities r_k is the same number."""
