@@ -377,6 +377,37 @@ int irs_native_warp(const float* displacement, int C, const int32_t* dims, const
                     const float* im, const int16_t* seg, const uint8_t* mask, int Cim, float fill, const float* scale,
                     float* im_out, int16_t* seg_out, uint8_t* mask_out, float* displacement_out, void* stream);
 
+/* Intensity similarity (absent in the reference, which reports only its loss terms and segmentation metrics): per chain the
+ * joint intensity histogram of the fixed image and a (warped) moving image and, from ONE pass over the two volumes, MSE, the
+ * global normalised cross-correlation, mutual information and normalised mutual information.
+ *  - fixed (Cf,1,D,H,W) float32 with Cf 1 (shared by the chains) or C; moving (C,1,D,H,W) float32, C in 1 .. IRS_MAX_CHAINS;
+ *    mask (1,1,D,H,W) uint8 shared by the chains, or NULL; every dim >= 1, fewer than 2^30 voxels.  A voxel takes part when
+ *    the mask is set there (or is NULL) and both intensities are finite; masked voxels with a non-finite intensity are only
+ *    counted (n_nonfinite).
+ *  - binning, in float32: inv_w = (float)bins / (hi - lo) on the host, t = (x - lo) * inv_w (a difference, then a product),
+ *    b = min(bins - 1, max(0, (int)floorf(t))); bins in IRS_SIMILARITY_MIN_BINS .. IRS_SIMILARITY_MAX_BINS; both ranges finite
+ *    with hi > lo.  Values outside [lo, hi] fall into the end bins and the voxel is counted in n_clipped; x == hi is in bin
+ *    bins - 1 and not clipped.
+ *  - hist (C,bins,bins) int32 or NULL (the workspace then holds it): hist[c][bf][bm] over the voxels of chain c taking part.
+ *    Exact: integer adds only.
+ *  - stats (C, IRS_SIMILARITY_STATS) double: n, n_nonfinite, n_clipped, mse, ncc, h_fixed, h_moving, h_joint, mi, nmi.
+ *    Entropies in nats from the counts, p = count / n: h_joint = -sum p ln p over the non-empty cells, h_fixed / h_moving the
+ *    same over the row / column sums; mi = h_fixed + h_moving - h_joint; nmi = (h_fixed + h_moving) / h_joint (Studholme), NaN
+ *    when h_joint == 0.  mse = sum (f - m)^2 / n with the difference formed in double.  ncc = (sum fm / n - mean_f mean_m) /
+ *    sqrt(var_f var_m) from the raw double sums, NaN when a variance is <= 0.  n == 0: a zero histogram, NaN from mse on.
+ *  - ws: irs_image_similarity_workspace(C, bins) bytes of device memory, 16-byte aligned (at most IRS_SIMILARITY_WS_BYTES).
+ *  Deterministic (integer histogram, double sums merged in a fixed order); no host sync. */
+#define IRS_SIMILARITY_STATS 10
+#define IRS_SIMILARITY_MIN_BINS 2
+#define IRS_SIMILARITY_MAX_BINS 128
+#define IRS_SIMILARITY_MAX_BLOCKS 1024 /* rows of per-block partial sums in the workspace */
+#define IRS_SIMILARITY_WS_BYTES \
+    (IRS_MAX_CHAINS * IRS_SIMILARITY_MAX_BINS * IRS_SIMILARITY_MAX_BINS * 4 + IRS_SIMILARITY_MAX_BLOCKS * (3 + 6) * 8)
+int irs_image_similarity_workspace(int C, int bins, size_t* bytes);
+int irs_image_similarity(const float* fixed, int Cf, const float* moving, int C, const uint8_t* mask, int D, int H, int W,
+                         float f_lo, float f_hi, float m_lo, float m_hi, int bins, int32_t* hist, double* stats, void* ws,
+                         size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * fused transition (Trainer._SGLD_transition, trainer/trainer.py:291-356)
  * ---------------------------------------------------------------------------------------------- */

@@ -67,6 +67,7 @@ static Knobs knobs_from_env() {
     k.slab_exact = env_or("IRS_SLAB_EXACT", k.slab_exact);
     k.slab_force_h = env_or("IRS_SLAB_FORCE_H", k.slab_force_h);
     k.launch_log = env_or("IRS_LAUNCH_LOG", k.launch_log);
+    k.similarity_aggregate = env_or("IRS_SIMILARITY_AGGREGATE", k.similarity_aggregate);
     k.chain_overlap = env_or("IRS_CHAIN_OVERLAP", k.chain_overlap);
     k.data_batch = env_or("IRS_DATA_BATCH", k.data_batch);
     return k;
@@ -121,7 +122,7 @@ int knob_set(Knobs& k, const char* name, int value, bool on_context) {
         {"fwd_rows1", &Knobs::fwd_rows1, KN_GLOBAL}, {"coarse_box", &Knobs::coarse_box, KN_GLOBAL}, {"lds_from", &Knobs::lds_from, KN_GLOBAL},
         {"fwd_pf", &Knobs::fwd_pf, KN_GLOBAL}, {"tile_box", &Knobs::tile_box, KN_GLOBAL}, {"fwd_r2_rows1", &Knobs::fwd_r2_rows1, KN_GLOBAL}, {"sobolev_tile", &Knobs::sobolev_tile, KN_GLOBAL},
         {"march_seg", &Knobs::march_seg, KN_GLOBAL}, {"march_seg_fwd", &Knobs::march_seg_fwd, KN_GLOBAL}, {"swz_run", &Knobs::swz_run, KN_GLOBAL},
-        {"sobolev_seg", &Knobs::sobolev_seg, KN_GLOBAL}, {"ps_rows", &Knobs::ps_rows, KN_GLOBAL}, {"launch_log", &Knobs::launch_log, KN_GLOBAL},
+        {"sobolev_seg", &Knobs::sobolev_seg, KN_GLOBAL}, {"ps_rows", &Knobs::ps_rows, KN_GLOBAL}, {"launch_log", &Knobs::launch_log, KN_GLOBAL}, {"similarity_aggregate", &Knobs::similarity_aggregate, KN_GLOBAL},
         {"seg_fit", &Knobs::seg_fit, KN_LAYOUT}, {"seg_min_blocks", &Knobs::seg_min_blocks, KN_LAYOUT}, {"seg_min_len", &Knobs::seg_min_len, KN_LAYOUT},
         {"lcc_seg", &Knobs::lcc_seg, KN_LAYOUT}, {"stats_seg", &Knobs::stats_seg, KN_LAYOUT}, {"update_seg", &Knobs::update_seg, KN_LAYOUT},
     };
@@ -1115,6 +1116,59 @@ int irs_native_warp(const float* displacement, int C, const int32_t* dims, const
     gm.fill = fill;
     launch_native_warp(displacement, im_out ? im : nullptr, seg_out ? seg : nullptr, mask_out ? mask : nullptr,
                        Cim == 1 ? 0 : voxels, im_out, seg_out, mask_out, displacement_out, gm, C, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
+// intensity similarity (similarity_kernels.hip)
+// ================================================================================================
+static size_t similarity_hist_bytes(int C, int bins) { return ((size_t)C * bins * bins * sizeof(int32_t) + 15) & ~(size_t)15; }
+static size_t similarity_partials_bytes() { return (size_t)IRS_SIMILARITY_MAX_BLOCKS * (3 + 6) * 8; }
+
+int irs_image_similarity_workspace(int C, int bins, size_t* bytes) {
+    if (!bytes) return fail("irs_image_similarity_workspace: bad arguments");
+    if (C < 1 || C > IRS_MAX_CHAINS) return fail("irs_image_similarity_workspace: C = %d chains, 1..%d", C, IRS_MAX_CHAINS);
+    if (bins < IRS_SIMILARITY_MIN_BINS || bins > IRS_SIMILARITY_MAX_BINS)
+        return fail("irs_image_similarity_workspace: bins = %d, %d..%d", bins, IRS_SIMILARITY_MIN_BINS, IRS_SIMILARITY_MAX_BINS);
+    *bytes = similarity_hist_bytes(C, bins) + similarity_partials_bytes();
+    return 0;
+}
+
+int irs_image_similarity(const float* fixed, int Cf, const float* moving, int C, const uint8_t* mask, int D, int H, int W,
+                         float f_lo, float f_hi, float m_lo, float m_hi, int bins, int32_t* hist, double* stats, void* ws,
+                         size_t ws_bytes, void* stream) {
+    if (!fixed || !moving || !stats || !ws) return fail("irs_image_similarity: bad arguments");
+    if (C < 1 || C > IRS_MAX_CHAINS) return fail("irs_image_similarity: C = %d chains, 1..%d", C, IRS_MAX_CHAINS);
+    if (Cf != 1 && Cf != C) return fail("irs_image_similarity: fixed image of %d chains, 1 or %d needed", Cf, C);
+    if (bins < IRS_SIMILARITY_MIN_BINS || bins > IRS_SIMILARITY_MAX_BINS)
+        return fail("irs_image_similarity: bins = %d, %d..%d", bins, IRS_SIMILARITY_MIN_BINS, IRS_SIMILARITY_MAX_BINS);
+    if (D < 1 || H < 1 || W < 1) return fail("irs_image_similarity: dims (%d, %d, %d), every one >= 1 needed", D, H, W);
+    const int64_t V = (int64_t)D * H * W;
+    if (V >= ((int64_t)1 << 30)) return fail("irs_image_similarity: the volume must have fewer than 2^30 voxels");
+    SimBins bn;
+    bn.bins = bins;
+    const float lo[2] = {f_lo, m_lo}, hi[2] = {f_hi, m_hi};
+    float inv[2];
+    for (int k = 0; k < 2; ++k) {
+        const char* who = k == 0 ? "fixed" : "moving";
+        if (!isfinite(lo[k]) || !isfinite(hi[k]) || !(hi[k] > lo[k]))
+            return fail("irs_image_similarity: %s range [%g, %g], finite bounds with hi > lo needed", who, (double)lo[k], (double)hi[k]);
+        const float width = hi[k] - lo[k];  // fp32, as the definition states it
+        inv[k] = (float)bins / width;
+        if (!isfinite(inv[k]) || !(inv[k] > 0.0f))
+            return fail("irs_image_similarity: %s range [%g, %g] is too wide or too narrow for float32 bins", who, (double)lo[k], (double)hi[k]);
+    }
+    bn.f_lo = f_lo, bn.f_hi = f_hi, bn.f_inv = inv[0];
+    bn.m_lo = m_lo, bn.m_hi = m_hi, bn.m_inv = inv[1];
+    const size_t hist_bytes = similarity_hist_bytes(C, bins), need = hist_bytes + similarity_partials_bytes();
+    if (ws_bytes < need)
+        return fail("irs_image_similarity: workspace of %zu bytes, %zu needed (irs_image_similarity_workspace)", ws_bytes, need);
+    if ((uintptr_t)ws & 15) return fail("irs_image_similarity: the workspace must be 16-byte aligned");
+    long long* ipart = (long long*)((char*)ws + hist_bytes);
+    double* fpart = (double*)(ipart + (size_t)IRS_SIMILARITY_MAX_BLOCKS * 3);
+    launch_image_similarity(fixed, Cf == 1 ? 0 : V, moving, mask, V, C, bn, hist ? hist : (int32_t*)ws, stats, ipart, fpart,
+                            (hipStream_t)stream);
     LAUNCH_CHECK();
     return 0;
 }

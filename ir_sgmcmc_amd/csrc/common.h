@@ -106,6 +106,7 @@ struct Knobs {
     int chain_overlap = 0;     // IRS_CHAIN_OVERLAP     C > 1: data term of chain c on a side stream, overlapping the statistics of chain c + 1
                                //                       (round 5, asked for; measured SLOWER: 0.728 against 0.711 ms per chain-transition at 128^3
                                //                       C = 2, 1.931 against 1.917 at 192^3, three alternating runs -- off; read when a context is created)
+    int similarity_aggregate = 1;  // IRS_SIMILARITY_AGGREGATE  joint histogram: a wavefront whose voxels all fall into one joint bin adds their number with one LDS add (0: plain LDS atomics always)
     int launch_log = 0;        // IRS_LAUNCH_LOG        print the shape of every distinct marching launch once (stderr; tools/launch_shapes.py)
 };
 Knobs& global_knobs();                                   // api.hip; initialised from the environment on first use
@@ -301,8 +302,8 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
-// reduce NV values per thread across the block; result valid in thread 0.  smem: NV * (kBlock/kWave) doubles.
-template <int NV>
+// reduce NV values per thread across the block of NW wavefronts; result valid in thread 0.  smem: NV * NW doubles.
+template <int NV, int NW = kBlock / kWave>
 __device__ __forceinline__ void block_sum(double (&v)[NV], double* smem) {
     const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
     // the butterfly of wave_sum, one LEVEL for all NV values at a time: value by value it is a chain of 6 NV dependent
@@ -317,14 +318,14 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double* smem) {
     }
 #pragma unroll
     for (int i = 0; i < NV; ++i)
-        if (lane == 0) smem[i * (kBlock / kWave) + wid] = v[i];
+        if (lane == 0) smem[i * NW + wid] = v[i];
     __syncthreads();
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             double s = 0.0;
 #pragma unroll
-            for (int w = 0; w < kBlock / kWave; ++w) s += smem[i * (kBlock / kWave) + w];
+            for (int w = 0; w < NW; ++w) s += smem[i * NW + w];
             v[i] = s;
         }
     }

@@ -265,6 +265,17 @@ void launch_native_warp(const float* u, const float* im, const int16_t* seg, con
                         float* im_out, int16_t* seg_out, uint8_t* mask_out, float* disp_out, const NativeGeom& gm, int C,
                         hipStream_t st);
 
+// ---- similarity_kernels.hip: joint intensity histogram, MI / NMI, MSE and NCC of two images (absent in the reference)
+struct SimBins {
+    int bins;
+    float f_lo, f_hi, f_inv;  // range of the fixed image and bins / (hi - lo), formed in fp32
+    float m_lo, m_hi, m_inv;  // of the moving image
+};
+// fixed (1 or C,V) with fixed_stride 0 or V; moving (C,V); mask (V) uint8 or nullptr; hist (C,bins,bins) int32 (zeroed on the
+// stream here); stats (C, IRS_SIMILARITY_STATS); ipart / fpart: IRS_SIMILARITY_MAX_BLOCKS rows of 3 int64 / 6 doubles
+void launch_image_similarity(const float* fixed, int64_t fixed_stride, const float* moving, const uint8_t* mask, int64_t V, int C,
+                             const SimBins& bn, int32_t* hist, double* stats, long long* ipart, double* fpart, hipStream_t st);
+
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h
 }  // namespace irs

@@ -40,6 +40,10 @@ distances of the propagated segmentation to the point-estimate metrics wherever 
 The native-resolution option (native_resolution_options) keeps no state either: at a logged step it carries the sampled
 transformation to the image's own voxel grid (ops.native_warp, native.NativeGrid) and logs Dice and the surface distances there,
 in mm under the header zooms.
+
+The intensity-similarity option (image_similarity_options) keeps no state either: at a logged step it compares the fixed image
+with the warped moving image the transition produced (ops.image_similarity: joint histogram, MI / NMI, MSE, NCC in one pass) --
+the only figures of registration quality that need no segmentation.
 """
 import math
 import numbers
@@ -937,3 +941,47 @@ def native_resolution_options(cfg_trainer, data_loader=None):
         raise ValueError(f'{what}: the data loader ({type(data_loader).__name__}) has no native volumes -- the synthetic pair exists '
                          f'at `dims` only; the option needs a BiobankDataLoader reading NIfTI files')
     return {'period': period, 'save': save}
+
+
+SIMILARITY_OPTION_KEYS = ('bins', 'period')
+SIMILARITY_METRICS = ('MSE', 'NCC', 'MI', 'NMI')  # the logged ones, in this order; ops.SIMILARITY_COLUMNS in lower case
+
+
+def image_similarity_options(cfg_trainer):
+    """`trainer.image_similarity` -> None when off, else {'bins': B, 'period': P or None}.
+    Absent / false / null: off.  true: 64 bins, evaluated at every logged step.  {"bins": B, "period": P}: B bins per image
+    (2 .. 128) and also at every P-th step after the burn-in.  Refuses unknown keys, a non-integer B or a B outside 2 .. 128, a
+    non-integer P or P < 1."""
+    what = 'trainer.image_similarity'
+    opt = cfg_trainer.get('image_similarity', False)
+    if opt is None or opt is False:
+        return None
+    bins, period = 64, None
+    if isinstance(opt, dict):
+        unknown = set(opt) - set(SIMILARITY_OPTION_KEYS)
+        if unknown:
+            raise ValueError(f'{what}: unknown keys {sorted(unknown)}; known: {list(SIMILARITY_OPTION_KEYS)}')
+        if 'bins' in opt:
+            b = opt['bins']
+            if isinstance(b, bool) or not isinstance(b, numbers.Integral):
+                raise ValueError(f'{what}.bins must be an integer, got {b!r}')
+            if not 2 <= b <= 128:
+                raise ValueError(f'{what}: bins must be in 2 .. 128, got {b}')
+            bins = int(b)
+        if 'period' in opt:
+            p = opt['period']
+            if isinstance(p, bool) or not isinstance(p, numbers.Integral):
+                raise ValueError(f'{what}.period must be an integer, got {p!r}')
+            if p < 1:
+                raise ValueError(f'{what}: the period must be >= 1, got {p}')
+            period = int(p)
+    elif opt is not True:
+        raise ValueError(f'{what} must be true, false or {{"bins": B, "period": P}}, got {opt!r}')
+    return {'bins': bins, 'period': period}
+
+
+def image_similarity_metric_names(no_chains):
+    """the metric names the option adds: the unregistered pair at step 0, every chain's sampled transformation, the
+    posterior-mean displacement"""
+    prefixes = ['VI/train/similarity'] + [f'MCMC/chain_{i}/similarity' for i in range(no_chains)] + ['MCMC/similarity_of_mean']
+    return [f'{p}/{k}' for p in prefixes for k in SIMILARITY_METRICS]

@@ -759,3 +759,52 @@ def native_warp(displacement, grid, im=None, seg=None, mask=None, fill=None, wan
                                 L.dev_ptr(out.get('seg'), None, True), L.dev_ptr(out.get('mask'), None, True),
                                 L.dev_ptr(out.get('displacement'), None, True), L.stream_ptr()))
     return out
+
+
+SIMILARITY_COLUMNS = ('n', 'n_nonfinite', 'n_clipped', 'mse', 'ncc', 'h_fixed', 'h_moving', 'h_joint', 'mi', 'nmi')
+
+
+def intensity_ranges(*images):
+    """(lo, hi) of the finite values of every image, as Python floats: ONE host read-back for all of them"""
+    ext = []
+    for im in images:
+        finite = torch.isfinite(im)
+        ext += [torch.where(finite, im, math.inf).min(), torch.where(finite, im, -math.inf).max()]
+    ext = torch.stack(ext).tolist()
+    return [(ext[2 * i], ext[2 * i + 1]) for i in range(len(images))]
+
+
+def image_similarity(fixed, moving, mask=None, bins=64, fixed_range=None, moving_range=None, want_hist=False):
+    """Intensity similarity of the fixed image and a (warped) moving image (absent in the reference): fixed (1 or C,1,D,H,W) and
+    moving (C,1,D,H,W) float32; mask (1,1,D,H,W) bool / uint8 shared by the chains, or None; bins in 2 .. 128; fixed_range /
+    moving_range: (lo, hi), finite with hi > lo -- None: the min / max of the finite values of that image (one host read-back;
+    with both ranges given the call does not synchronise).  -> {'stats': (C,10) float64 on the device, columns
+    SIMILARITY_COLUMNS[, 'hist': (C,bins,bins) int32, hist[c][bin of fixed][bin of moving]]}: the joint histogram and the
+    moment sums from ONE pass over the two volumes, then entropies, MI, NMI, MSE and the global NCC per chain
+    (include/irsgmcmc.h: irs_image_similarity)."""
+    lib = L.load()
+    Cn, D, H, W = _dims5(moving, 1)
+    _chain_volumes('fixed', fixed, 'moving', Cn, D, H, W)
+    if mask is not None:
+        if tuple(mask.shape) != (1, 1, D, H, W) or mask.dtype not in (torch.bool, torch.uint8):
+            raise L.IrsError(f'mask must be a bool / uint8 (1,1,{D},{H},{W}) volume, got {mask.dtype} {tuple(mask.shape)}')
+        mask = mask.contiguous()
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    if isinstance(bins, bool) or not isinstance(bins, int):
+        raise L.IrsError(f'bins must be an integer, got {bins!r}')
+    fixed_ptr, moving_ptr = L.dev_ptr(fixed, torch.float32), L.dev_ptr(moving, torch.float32)
+    missing = [im for im, r in ((fixed, fixed_range), (moving, moving_range)) if r is None]
+    found = iter(intensity_ranges(*missing)) if missing else None
+    f_lo, f_hi = (float(x) for x in (fixed_range if fixed_range is not None else next(found)))
+    m_lo, m_hi = (float(x) for x in (moving_range if moving_range is not None else next(found)))
+    nbytes = C.c_size_t()
+    L.check(lib.irs_image_similarity_workspace(Cn, bins, C.byref(nbytes)))
+    dev = moving.device
+    ws = torch.empty(nbytes.value, device=dev, dtype=torch.uint8)
+    out = {'stats': torch.empty((Cn, L.IRS_SIMILARITY_STATS), device=dev, dtype=torch.float64)}
+    if want_hist:
+        out['hist'] = torch.empty((Cn, bins, bins), device=dev, dtype=torch.int32)
+    L.check(lib.irs_image_similarity(fixed_ptr, fixed.shape[0], moving_ptr, Cn, L.dev_ptr(mask, torch.uint8, True), D, H, W,
+                                     f_lo, f_hi, m_lo, m_hi, bins, L.dev_ptr(out.get('hist'), None, True), L.dev_ptr(out['stats']),
+                                     L.dev_ptr(ws), nbytes.value, L.stream_ptr()))
+    return out

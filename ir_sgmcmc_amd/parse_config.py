@@ -13,8 +13,9 @@ import numpy as np
 from .data_loader import data_loaders as module_data
 from .diagnostics import (COVARIANCE_METRICS, ICE_SPACES, JACOBIAN_METRICS, LABEL_STRUCTURE_METRICS, QUANTILE_METRICS,
                           diagnostics_period, displacement_covariance_options, displacement_quantiles_options, ess_options,
-                          hausdorff_metric_names, hausdorff_options, inverse_consistency_options, jacobian_posterior_options,
-                          label_posterior_options, native_resolution_options)
+                          hausdorff_metric_names, hausdorff_options, image_similarity_metric_names, image_similarity_options,
+                          inverse_consistency_options, jacobian_posterior_options, label_posterior_options,
+                          native_resolution_options)
 from .logger import setup_logging
 from .model import distributions as model_distr
 from .model import loss as model_loss
@@ -123,6 +124,8 @@ class ConfigParser:
                 if ice['moving_space_dice']:
                     m += [f'MCMC/chain_{i}/DSC_inverse/{s}' for s in self.structures_dict]
             m += [f'MCMC/ICE/{space}/{k}' for space in ICE_SPACES for k in ('mean', 'max', f'frac_above_{ice["threshold"]:g}')]
+        if image_similarity_options(self['trainer']) is not None:
+            m += image_similarity_metric_names(C)
         return m
 
     def init_transformation_and_registration_modules(self):

@@ -22,13 +22,14 @@ from .. import ops
 from ..diagnostics import (COVARIANCE_METRICS, ChainMoments, DisplacementCovariance, DisplacementQuantiles, ICE_SPACES,
                            InverseConsistency, JACOBIAN_METRICS, JacobianPosterior, LABEL_STRUCTURE_METRICS, LabelPosterior,
                            QUANTILE_METRICS, diagnostics_period, displacement_covariance_options, displacement_quantiles_options,
-                           ess_options, hausdorff_options, inverse_consistency_options, is_recorded, jacobian_posterior_options,
-                           label_posterior_options, native_resolution_options)
+                           ess_options, hausdorff_options, image_similarity_options, inverse_consistency_options, is_recorded,
+                           jacobian_posterior_options, label_posterior_options, native_resolution_options, SIMILARITY_METRICS)
 from ..engine import EngineConfig, TransitionEngine
 from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_quantiles, save_ess,
                       save_field, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_native_mean,
                       save_native_sample, save_rhat, save_sample)
-from ..utils import calc_DSC_GPU, calc_norm, calc_no_non_diffeomorphic_voxels, sample_q_v, transform_coordinates
+from ..utils import (calc_DSC_GPU, calc_image_similarity, calc_norm, calc_no_non_diffeomorphic_voxels, init_identity_grid_3D,
+                     sample_q_v, transform_coordinates)
 from .vi import VIMixin
 
 
@@ -109,6 +110,11 @@ class Trainer(VIMixin, BaseTrainer):
         # native volumes go to the device in _run_MCMC
         self.native_options = native_resolution_options(cfg_trainer, data_loader)
         self._native = None
+        # label-free similarity of the fixed and the warped moving image (ops.image_similarity): None when
+        # trainer.image_similarity is off.  No state but the two intensity ranges, taken from the pair
+        self.similarity_options = image_similarity_options(cfg_trainer)
+        self._similarity_ranges, self._similarity_warned = None, False
+        self.similarity_summary = None
 
     # ---------------------------------------------------------------- engine plumbing
     def _engine_config(self):
@@ -380,6 +386,8 @@ class Trainer(VIMixin, BaseTrainer):
                     and bool(self.structures_dict))
         if self.native_options is not None:
             self._native_init()
+        if self.similarity_options is not None:
+            self._similarity_init(fixed, moving)
         if cfg_trainer.get('resume'):
             self.load_checkpoint(cfg_trainer['resume'])
             first = self._sample_no + 1
@@ -446,6 +454,11 @@ class Trainer(VIMixin, BaseTrainer):
                                                         is_recorded(sample_no, self.no_iters_burn_in, self.native_options['period']))):
                 self.engine.flush()  # as above
                 self._log_native(sample_no, output['displacement'], logged and save_samples)
+            if self.similarity_options is not None and (logged or (self.similarity_options['period'] is not None and is_recorded(
+                    sample_no, self.no_iters_burn_in, self.similarity_options['period']))):
+                self.engine.flush()  # as above
+                rows = self._image_similarity(fixed, output['im_moving_warped'])
+                self._log_similarity([f'MCMC/chain_{idx}/similarity' for idx in range(self.no_chains)], rows)
             due = [r for r in recorders if is_recorded(sample_no, self.no_iters_burn_in, r.period)]
             if due:
                 self.engine.flush()  # as above: the buffers hold sample `sample_no` once nothing is pending
@@ -493,6 +506,13 @@ class Trainer(VIMixin, BaseTrainer):
             out = ops.native_warp(transform_coordinates(mean.unsqueeze(0)).contiguous(), nat['grid'], im=nat['moving_im'],
                                   fill=nat['fill'], want_displacement=nat['grid'].mm_scale())
             save_native_mean(self.logger, self.config.save_dirs, nat['grid'].zooms, out['displacement'][0], out['im'][0, 0], 'MCMC')
+        if self.similarity_options is not None and n_rec > 0:
+            # the moving image under the posterior-mean displacement: identity + the mean in [-1, 1] coordinates
+            ident = init_identity_grid_3D(mean.shape[1:], self.device).permute(0, 4, 1, 2, 3)
+            warped = self.registration_module(moving['im'], (ident + transform_coordinates(mean.unsqueeze(0))).contiguous())
+            row = self._image_similarity(fixed, warped)[0]
+            self._log_similarity(['MCMC/similarity_of_mean'], [row])
+            self._similarity_summary('mean', row, f'the mean of {n_rec} samples')
         for r in recorders:
             r.finish(fixed if r.takes == 'fixed' else masks if r.takes == 'masks' else masks['moving'], spacing,
                      cfg_trainer.get('save_outputs', True))
@@ -649,6 +669,47 @@ class Trainer(VIMixin, BaseTrainer):
             save_native_sample(self.config.save_dirs, grid.zooms, sample_no, idx, im=out['im'][idx, 0] if 'im' in want else None,
                                seg=out['seg'][idx, 0] if 'seg' in want else None,
                                displacement_mm=out['displacement'][idx] if 'displacement' in want else None)
+
+    def _similarity_init(self, fixed, moving):
+        """the two intensity ranges the histograms are binned over: the finite min / max of the fixed and of the moving image
+        (trilinear interpolation with border padding cannot leave the moving range); one host read-back"""
+        self._similarity_ranges = ops.intensity_ranges(fixed['im'], moving['im'])
+        (f_lo, f_hi), (m_lo, m_hi) = self._similarity_ranges
+        self.logger.info(f'image similarity: {self.similarity_options["bins"]} bins over [{f_lo:g}, {f_hi:g}] (fixed) and '
+                         f'[{m_lo:g}, {m_hi:g}] (moving)')
+
+    def _image_similarity(self, fixed, moving_im):
+        """-> one dict per volume of moving_im (utils.calc_image_similarity) against fixed['im'] under fixed['mask'], all chains
+        in one call; one warning per run when a call clipped an intensity or met a non-finite one"""
+        rows = calc_image_similarity(fixed['im'], moving_im.contiguous(), fixed['mask'][:1], self.similarity_options['bins'],
+                                     *self._similarity_ranges)
+        if not self._similarity_warned and any(r['n_clipped'] > 0 or r['n_nonfinite'] > 0 for r in rows):
+            self._similarity_warned = True
+            self.logger.warning(f'image similarity: {max(r["n_clipped"] for r in rows)} voxels outside the intensity ranges (counted '
+                                f'in the end bins) and {max(r["n_nonfinite"] for r in rows)} with a non-finite intensity (left out); '
+                                f'not reported again in this run')
+        return rows
+
+    def _log_similarity(self, prefixes, rows):
+        for prefix, row in zip(prefixes, rows):
+            for key in SIMILARITY_METRICS:
+                self.metrics.update(f'{prefix}/{key}', row[key.lower()])
+
+    def _similarity_summary(self, name, row, what):
+        """self.similarity_summary[name] = the four numbers and the voxel count, and one log line"""
+        if self.similarity_summary is None:
+            self.similarity_summary = {}
+        self.similarity_summary[name] = {'n': row['n'], **{key: row[key.lower()] for key in SIMILARITY_METRICS}}
+        self.logger.info(f'image similarity of {what} over {row["n"]} masked voxels: ' +
+                         ', '.join(f'{key} {row[key.lower()]:.6g}' for key in SIMILARITY_METRICS))
+
+    def _log_similarity_unregistered(self, fixed, moving):
+        """step 0: the unregistered pair under VI/train/similarity/*, with or without segmentations"""
+        self._similarity_init(fixed, moving)
+        self.writer.set_step(0)
+        row = self._image_similarity(fixed, moving['im'][:1])[0]
+        self._log_similarity(['VI/train/similarity'], [row])
+        self._similarity_summary('unregistered', row, 'the unregistered pair')
 
     def _dense_velocity(self, output):
         """the velocity field the forward exponential of this transition integrated, (C,3,D,H,W) in voxel units: the recorded

@@ -251,7 +251,10 @@ class VIMixin:
 
     @torch.no_grad()
     def _metrics_init(self, fixed, moving):
-        """trainer.py:550-567, the metrics only: ASD and Dice of the unregistered pair at step 0"""
+        """trainer.py:550-567, the metrics only: ASD and Dice of the unregistered pair at step 0 -- and, with
+        trainer.image_similarity on, its intensity similarity, which needs no segmentation"""
+        if self.similarity_options is not None:
+            self._log_similarity_unregistered(fixed, moving)
         if 'seg' not in fixed or 'seg' not in moving or not self.structures_dict:
             return
         self.writer.set_step(0)

@@ -288,6 +288,16 @@ def calc_native_metrics(displacement, grid, seg_fixed, seg_moving, structures_di
     return {'seg': seg, 'DSC': calc_DSC_GPU(C, fixed, seg, structures_dict), **out}
 
 
+@torch.no_grad()
+def calc_image_similarity(fixed, moving, mask=None, bins=64, fixed_range=None, moving_range=None):
+    """Label-free similarity of the fixed image and a (warped) moving image (absent in the reference): fixed (1 or C,1,D,H,W),
+    moving (C,1,D,H,W) float32 on the device, mask (1,1,D,H,W) bool / uint8 or None; the ranges as ops.image_similarity takes
+    them.  -> one dict of Python numbers per chain, keyed by ops.SIMILARITY_COLUMNS ('n', 'n_nonfinite', 'n_clipped' as ints;
+    'mse', 'ncc', 'h_fixed', 'h_moving', 'h_joint', 'mi', 'nmi' as floats); one host read-back."""
+    stats = _ops.image_similarity(fixed, moving, mask, bins, fixed_range, moving_range)['stats'].tolist()
+    return [{k: int(x) if j < 3 else x for j, (k, x) in enumerate(zip(_ops.SIMILARITY_COLUMNS, row))} for row in stats]
+
+
 def rescale_residuals(res, mask, data_loss):
     """VD-rescaled residual x = sum_k r_k (z / sigma_k)^2 (utils/util.py:330-347).  The reference obtains it as
     sum_k s_k * d(-log p)/d(s_k) with a nested backward; the closed form with the responsibilities r_k is the same number."""
