@@ -408,6 +408,52 @@ int irs_image_similarity(const float* fixed, int Cf, const float* moving, int C,
                          float f_lo, float f_hi, float m_lo, float m_hi, int bins, int32_t* hist, double* stats, void* ws,
                          size_t ws_bytes, void* stream);
 
+/* Landmark propagation (absent in the reference, which has no point-set operator): a sampled displacement evaluated at K
+ * positions that are no voxel centres, and the posterior of the mapped landmarks with their target registration error (TRE).
+ * warped(x) = moving(x + d(x)): a point p of the fixed grid maps to p + d(p) in the moving image; points of the moving space
+ * are carried to the fixed space with the displacement of irs_svf_exp_inverse.
+ *  - irs_transform_points: points (K,3) float32 in [-1,1] coordinates (align_corners), component 0 = x (the last axis), K in
+ *    1 .. IRS_LANDMARK_MAX_POINTS; displacement (C,3,D,H,W) float32 in any linear unit, channel 0 the last axis, C in 1 ..
+ *    IRS_MAX_CHAINS, every dim >= 2; scale: 3 host floats, finite and > 0, one per channel; offset (K,3) float32 or NULL (= 0).
+ *    sampled (C,K,3) float32 or NULL: the three channels sampled at the point with the trilinear sampler of the squaring step
+ *    and the warp (border clamp, align_corners, the same expressions: index coordinate ((g + 1) * 0.5) * (n - 1), weights
+ *    (wx * wy) * wz, acc = acc + val * w over the corners x fastest, every operation rounded once to float32), so a point on a
+ *    voxel centre returns the stored value bit for bit and a point outside the box the border value.  mapped (C,K,3) float32
+ *    or NULL: scale_c * sampled_c + offset_c, one product and one sum, each rounded once; with the point's position in the
+ *    output unit as the offset this is the mapped point.  At least one of the two outputs must be given.  A point with a
+ *    non-finite coordinate gives NaN in all three components of both outputs and reads no tap.  One launch, one thread per
+ *    (chain, point); deterministic; no atomics; no host sync.
+ *  - irs_landmark_update: mapped (C,K,3) and target (K,3) float32 in one common unit.  The state is float64: mean (K,3),
+ *    comoment (K,6: xx, xy, xz, yy, yz, zz), tre_mean, tre_m2, tre_max (K), and count (K) int32.  Per landmark, the chains in
+ *    order; a sample takes part when its three components and the landmark's target are finite (else it is skipped and not
+ *    counted): k = ++count, delta = x - mean, mean += delta / k, comoment_ab += delta_a * (x_b - mean_b) with the new mean;
+ *    e = sqrt(sum_c (x_c - target_c)^2) in double, folded into tre_mean / tre_m2 the same way, tre_max = fmax(tre_max, e).
+ *    records_before >= 0 records were folded in before, records_before + C <= INT32_MAX; records_before = 0 overwrites the
+ *    state (all zero before the first sample), which is then never read.  One launch, each thread owns its landmarks, no
+ *    atomics.  Deterministic; no host sync.
+ *  - irs_landmark_finalize: out (K, IRS_LANDMARK_COLUMNS) doubles per landmark {count, tre_mean, tre_std = sqrt(tre_m2 /
+ *    max(count - 1, 1)), tre_max, tre_of_mean = |mean - target|, the three principal standard deviations of S = comoment /
+ *    max(count - 1, 1), descending (the 5 cyclic Jacobi sweeps of irs_displacement_covariance_finalize, eigenvalues clamped at
+ *    0 under the root), mahalanobis2 = sum_i ((mean - target) . e_i)^2 / l_i over the eigenpairs of S, pit = F3(mahalanobis2)
+ *    with F3(x) = erf(sqrt(x / 2)) - sqrt(2 x / pi) exp(-x / 2), the chi-square CDF with 3 degrees of freedom}.  count == 0:
+ *    every column but the first is NaN.  mahalanobis2 and pit are NaN when count < 4 or the smallest eigenvalue is <= 0.
+ *    isummary: IRS_LANDMARK_SUMMARY_INTS int64 {landmarks, landmarks with count == 0, landmarks with a finite pit}; fsummary:
+ *    IRS_LANDMARK_SUMMARY_FLOATS doubles over the landmarks with count > 0 {sum tre_of_mean, max tre_of_mean, sum tre_mean,
+ *    max tre_max}; a maximum nothing entered is -inf.  ws: IRS_LANDMARK_WS_BYTES of device memory.  Deterministic (exact
+ *    integer sums, fixed-order double sums and maxima); no host sync. */
+#define IRS_LANDMARK_MAX_POINTS (1 << 24)
+#define IRS_LANDMARK_COLUMNS 10
+#define IRS_LANDMARK_SUMMARY_INTS 3
+#define IRS_LANDMARK_SUMMARY_FLOATS 4
+#define IRS_LANDMARK_WS_BYTES (1024 * (IRS_LANDMARK_SUMMARY_INTS + IRS_LANDMARK_SUMMARY_FLOATS) * 8)
+int irs_transform_points(const float* points, int K, const float* displacement, int C, int D, int H, int W, const float* scale,
+                         const float* offset, float* sampled, float* mapped, void* stream);
+int irs_landmark_update(const float* mapped, const float* target, int C, int K, double* mean, double* comoment, double* tre_mean,
+                        double* tre_m2, double* tre_max, int32_t* count, int records_before, void* stream);
+int irs_landmark_finalize(const double* mean, const double* comoment, const double* tre_mean, const double* tre_m2,
+                          const double* tre_max, const int32_t* count, const float* target, int K, double* out, long long* isummary,
+                          double* fsummary, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * fused transition (Trainer._SGLD_transition, trainer/trainer.py:291-356)
  * ---------------------------------------------------------------------------------------------- */

@@ -29,6 +29,9 @@ IRS_ICE_SUMMARY_INTS, IRS_ICE_SUMMARY_FLOATS = 2, 3
 IRS_ICE_WS_BYTES = IRS_MAX_CHAINS * 1024 * (IRS_ICE_SUMMARY_INTS + IRS_ICE_SUMMARY_FLOATS) * 8
 IRS_ICE_MAP_SUMMARY_INTS, IRS_ICE_MAP_SUMMARY_FLOATS = 3, 3
 IRS_ICE_MAP_WS_BYTES = 1024 * (IRS_ICE_MAP_SUMMARY_INTS + IRS_ICE_MAP_SUMMARY_FLOATS) * 8
+IRS_LANDMARK_MAX_POINTS, IRS_LANDMARK_COLUMNS = 1 << 24, 10
+IRS_LANDMARK_SUMMARY_INTS, IRS_LANDMARK_SUMMARY_FLOATS = 3, 4
+IRS_LANDMARK_WS_BYTES = 1024 * (IRS_LANDMARK_SUMMARY_INTS + IRS_LANDMARK_SUMMARY_FLOATS) * 8
 IRS_SIMILARITY_STATS, IRS_SIMILARITY_MIN_BINS, IRS_SIMILARITY_MAX_BINS = 10, 2, 128
 IRS_DATA_GMM_LCC, IRS_DATA_SSD = 0, 1
 IRS_REG_L2, IRS_REG_LOGNORMAL, IRS_REG_STUDENT, IRS_REG_LOGNORMAL_L2 = 0, 1, 2, 3
@@ -172,6 +175,9 @@ SIGNATURES = {
     'irs_native_warp': [_P, _I, _I32P, _I32P, _I32P, _P, _P, _P, _I, _F, C.POINTER(C.c_float), _P, _P, _P, _P, _P],
     'irs_image_similarity_workspace': [_I, _I, C.POINTER(C.c_size_t)],
     'irs_image_similarity': [_P, _I, _P, _I, _P, _I, _I, _I, _F, _F, _F, _F, _I, _P, _P, _P, C.c_size_t, _P],
+    'irs_transform_points': [_P, _I, _P, _I, _I, _I, _I, C.POINTER(C.c_float), _P, _P, _P, _P],
+    'irs_landmark_update': [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P],
+    'irs_landmark_finalize': [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _P],
     'irs_create': [C.POINTER(IrsConfig), C.POINTER(_P)],
     'irs_destroy': [_P],
     'irs_workspace_bytes': [_P],

@@ -1121,6 +1121,55 @@ int irs_native_warp(const float* displacement, int C, const int32_t* dims, const
 }
 
 // ================================================================================================
+// landmark propagation (landmark_kernels.hip)
+// ================================================================================================
+static bool landmark_count_ok(int K) { return K >= 1 && K <= IRS_LANDMARK_MAX_POINTS; }
+
+int irs_transform_points(const float* points, int K, const float* displacement, int C, int D, int H, int W, const float* scale,
+                         const float* offset, float* sampled, float* mapped, void* stream) {
+    if (!points || !displacement || !scale) return fail("irs_transform_points: bad arguments");
+    if (!sampled && !mapped) return fail("irs_transform_points: no output requested");
+    if (!landmark_count_ok(K)) return fail("irs_transform_points: K = %d points, 1..%d", K, IRS_LANDMARK_MAX_POINTS);
+    if (C < 1 || C > IRS_MAX_CHAINS) return fail("irs_transform_points: C = %d chains, 1..%d", C, IRS_MAX_CHAINS);
+    if (!dims_ok(C, D, H, W)) return fail("irs_transform_points: bad dims (%d, %d, %d)", D, H, W);
+    for (int a = 0; a < 3; ++a)
+        if (!positive_finite(scale[a]))
+            return fail("irs_transform_points: scale[%d] = %g, a finite value > 0 needed", a, (double)scale[a]);
+    launch_transform_points(points, K, displacement, scale, offset, sampled, mapped, C, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_landmark_update(const float* mapped, const float* target, int C, int K, double* mean, double* comoment, double* tre_mean,
+                        double* tre_m2, double* tre_max, int32_t* count, int records_before, void* stream) {
+    if (!mapped || !target || !mean || !comoment || !tre_mean || !tre_m2 || !tre_max || !count)
+        return fail("irs_landmark_update: bad arguments");
+    if (!landmark_count_ok(K)) return fail("irs_landmark_update: K = %d landmarks, 1..%d", K, IRS_LANDMARK_MAX_POINTS);
+    if (C < 1 || C > IRS_MAX_CHAINS) return fail("irs_landmark_update: C = %d chains, 1..%d", C, IRS_MAX_CHAINS);
+    if (records_before < 0) return fail("irs_landmark_update: records_before = %d < 0", records_before);
+    if ((int64_t)records_before + C > INT32_MAX)
+        return fail("irs_landmark_update: %d records + %d chains overflow the int32 record count", records_before, C);
+    launch_landmark_update(mapped, target, C, K, mean, comoment, tre_mean, tre_m2, tre_max, count, records_before, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_landmark_finalize(const double* mean, const double* comoment, const double* tre_mean, const double* tre_m2,
+                          const double* tre_max, const int32_t* count, const float* target, int K, double* out, long long* isummary,
+                          double* fsummary, void* ws, size_t ws_bytes, void* stream) {
+    if (!mean || !comoment || !tre_mean || !tre_m2 || !tre_max || !count || !target || !out || !isummary || !fsummary || !ws)
+        return fail("irs_landmark_finalize: bad arguments");
+    if (!landmark_count_ok(K)) return fail("irs_landmark_finalize: K = %d landmarks, 1..%d", K, IRS_LANDMARK_MAX_POINTS);
+    if (ws_bytes < (size_t)IRS_LANDMARK_WS_BYTES)
+        return fail("irs_landmark_finalize: workspace of %zu bytes, %zu needed (IRS_LANDMARK_WS_BYTES)", ws_bytes,
+                    (size_t)IRS_LANDMARK_WS_BYTES);
+    launch_landmark_finalize(mean, comoment, tre_mean, tre_m2, tre_max, count, target, K, out, isummary, fsummary, ws,
+                             (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // intensity similarity (similarity_kernels.hip)
 // ================================================================================================
 static size_t similarity_hist_bytes(int C, int bins) { return ((size_t)C * bins * bins * sizeof(int32_t) + 15) & ~(size_t)15; }

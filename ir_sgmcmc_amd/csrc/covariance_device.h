@@ -78,6 +78,27 @@ struct CovMaps {
     bool finite;   // false: the state held a non-finite value and everything above is NaN
 };
 
+// the 3 x 3 symmetric eigen-solver: kCovSweeps cyclic Jacobi sweeps over the pairs (0,1), (0,2), (1,2) of the matrix with the
+// diagonal a00, a11, a22 and the off-diagonal a01, a02, a12 -> the eigenvalues l0 >= l1 >= l2 (as the sweeps leave them: a
+// rounded matrix need not be positive semi-definite) and their unit eigenvectors e0, e1, e2
+__host__ __device__ inline void cov_eigen(double a00, double a11, double a22, double a01, double a02, double a12, double& l0,
+                                          double& l1, double& l2, double (&e0)[3], double (&e1)[3], double (&e2)[3]) {
+    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+#pragma unroll
+    for (int sweep = 0; sweep < kCovSweeps; ++sweep) {
+        cov_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);  // (0,1); the third index is 2
+        cov_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);  // (0,2); the third index is 1
+        cov_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);  // (1,2); the third index is 0
+    }
+    l0 = a00, l1 = a11, l2 = a22;
+    e0[0] = v00, e0[1] = v10, e0[2] = v20;
+    e1[0] = v01, e1[1] = v11, e1[2] = v21;
+    e2[0] = v02, e2[1] = v12, e2[2] = v22;
+    cov_swap_if_less(l0, l1, e0, e1);
+    cov_swap_if_less(l0, l2, e0, e2);
+    cov_swap_if_less(l1, l2, e1, e2);
+}
+
 // mu, M: the state after n >= 1 records; inv = 1 / max(n - 1, 1); sc: the per-channel scale
 __host__ __device__ inline CovMaps cov_maps(const float (&mu)[3], const float (&M)[6], double inv, const double (&sc)[3]) {
     CovMaps o;
@@ -87,20 +108,10 @@ __host__ __device__ inline CovMaps cov_maps(const float (&mu)[3], const float (&
 #pragma unroll
     for (int i = 0; i < 6; ++i) chk += M[i] * 0.0f;
     o.finite = chk == 0.0f;
-    double a00 = sc[0] * sc[0] * (double)M[0] * inv, a11 = sc[1] * sc[1] * (double)M[1] * inv, a22 = sc[2] * sc[2] * (double)M[2] * inv;
-    double a01 = sc[0] * sc[1] * (double)M[3] * inv, a02 = sc[0] * sc[2] * (double)M[4] * inv, a12 = sc[1] * sc[2] * (double)M[5] * inv;
-    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
-#pragma unroll
-    for (int sweep = 0; sweep < kCovSweeps; ++sweep) {
-        cov_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);  // (0,1); the third index is 2
-        cov_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);  // (0,2); the third index is 1
-        cov_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);  // (1,2); the third index is 0
-    }
-    double l0 = a00, l1 = a11, l2 = a22;
-    double e0[3] = {v00, v10, v20}, e1[3] = {v01, v11, v21}, e2[3] = {v02, v12, v22};
-    cov_swap_if_less(l0, l1, e0, e1);
-    cov_swap_if_less(l0, l2, e0, e2);
-    cov_swap_if_less(l1, l2, e1, e2);
+    const double a00 = sc[0] * sc[0] * (double)M[0] * inv, a11 = sc[1] * sc[1] * (double)M[1] * inv, a22 = sc[2] * sc[2] * (double)M[2] * inv;
+    const double a01 = sc[0] * sc[1] * (double)M[3] * inv, a02 = sc[0] * sc[2] * (double)M[4] * inv, a12 = sc[1] * sc[2] * (double)M[5] * inv;
+    double l0, l1, l2, e0[3], e1[3], e2[3];
+    cov_eigen(a00, a11, a22, a01, a02, a12, l0, l1, l2, e0, e1, e2);
     l0 = fmax(l0, 0.0), l1 = fmax(l1, 0.0), l2 = fmax(l2, 0.0);  // a rounded M need not be positive semi-definite
     const float nan = __builtin_nanf("");
     o.std[0] = o.finite ? (float)sqrt(l0) : nan;

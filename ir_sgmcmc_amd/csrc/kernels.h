@@ -276,6 +276,21 @@ struct SimBins {
 void launch_image_similarity(const float* fixed, int64_t fixed_stride, const float* moving, const uint8_t* mask, int64_t V, int C,
                              const SimBins& bn, int32_t* hist, double* stats, long long* ipart, double* fpart, hipStream_t st);
 
+// ---- landmark_kernels.hip: a displacement sampled at K points, and the posterior of the mapped landmarks (absent in the reference)
+// points, offset (K,3) float32 (offset may be nullptr); displacement (C,3,V); scale: 3 host floats; sampled / mapped (C,K,3)
+// float32, either may be nullptr
+void launch_transform_points(const float* points, int K, const float* displacement, const float* scale, const float* offset,
+                             float* sampled, float* mapped, int C, Vol vol, hipStream_t st);
+// mapped (C,K,3), target (K,3) float32; mean (K,3), comoment (K,6: xx, xy, xz, yy, yz, zz), tre_mean / tre_m2 / tre_max (K)
+// float64, count (K) int32: the finite samples of the C chains folded in order (records_before == 0 overwrites)
+void launch_landmark_update(const float* mapped, const float* target, int C, int K, double* mean, double* comoment, double* tre_mean,
+                            double* tre_m2, double* tre_max, int32_t* count, int records_before, hipStream_t st);
+// out (K, IRS_LANDMARK_COLUMNS) doubles; isummary IRS_LANDMARK_SUMMARY_INTS int64, fsummary IRS_LANDMARK_SUMMARY_FLOATS
+// doubles; ws: IRS_LANDMARK_WS_BYTES (the partials of at most 1024 blocks)
+void launch_landmark_finalize(const double* mean, const double* comoment, const double* tre_mean, const double* tre_m2,
+                              const double* tre_max, const int32_t* count, const float* target, int K, double* out,
+                              long long* isummary, double* fsummary, void* ws, hipStream_t st);
+
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h
 }  // namespace irs

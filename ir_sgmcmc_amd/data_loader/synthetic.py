@@ -48,6 +48,19 @@ def synthetic_pair(dims, seed=0, noise=0.02):
     return pack(im_f), pack(im_m)
 
 
+FIXED_BLOBS = ((0.0, 0.0, 0.0), (0.3, -0.2, 0.1))          # the centres _blobs is called with above, normalised (z, y, x)
+MOVING_BLOBS = ((0.08, -0.04, 0.05), (0.36, -0.15, 0.12))
+
+
+def synthetic_landmarks(dims):
+    """The two blob centres of synthetic_pair as corresponding landmarks -> (fixed, moving), each a (2,3) float64 array of
+    registration-grid voxel indices in (D,H,W) order: ((g + 1) / 2) * (n - 1) of the normalised centres, not rounded."""
+    import numpy as np
+    nm1 = np.asarray([int(d) - 1 for d in dims], dtype=np.float64)
+    to_index = lambda blobs: (np.asarray(blobs, dtype=np.float64) + 1.0) / 2.0 * nm1
+    return to_index(FIXED_BLOBS), to_index(MOVING_BLOBS)
+
+
 def init_var_params(dims_v, sigma_v_init=0.5, u_v_init=0.1):
     """mu = 0, log_var = log(sigma^2), u = const (data_loader/datasets.py:57-68)."""
     shape = (3, *dims_v)

@@ -34,6 +34,12 @@ recorded step it integrates -v (ops.svf_exp_inverse), composes the two maps in b
 the norm of phi^-1 o phi - id (fixed grid) and of phi o phi^-1 - id (moving grid), in voxels, into a per-voxel Welford mean and
 a running maximum (ops.inverse_consistency_update): 16 * D * H * W bytes whatever the number of records.
 
+The landmark posterior (LandmarkPosterior) is the one diagnostic with an independent truth: corresponding landmarks.  At a
+recorded step it evaluates the sampled displacement at the K landmarks (ops.transform_points) and folds the mapped points and
+their distance to the corresponding points, the target registration error (TRE), into a float64 state of 14 K numbers
+(ops.landmark_update); at the end ops.landmark_finalize gives per landmark the TRE statistics, the principal spreads of the
+mapped point, its Mahalanobis distance to the truth and the probability integral transform behind the coverage figures.
+
 The Hausdorff option (hausdorff_options) is of another kind: it keeps no state.  It adds the Hausdorff and percentile surface
 distances of the propagated segmentation to the point-estimate metrics wherever the ASD is logged.
 
@@ -865,6 +871,217 @@ class InverseConsistency(_Recorder):
             self.mean[k].copy_(sd[f'mean_{k}'])
             self.peak[k].copy_(sd[f'peak_{k}'])
         self.records = int(sd['records'])
+
+
+LANDMARK_OPTION_KEYS = ('period', 'fixed', 'moving', 'index_base', 'coverage_levels', 'inverse', 'synthetic')
+LANDMARK_DEFAULTS = {'index_base': 0, 'coverage_levels': (0.5, 0.95), 'inverse': False, 'synthetic': False}
+LANDMARK_METRICS = ('of_mean_mean', 'of_mean_median', 'of_mean_max', 'sample_mean', 'sample_max')
+
+
+def _coverage_levels(levels, what):
+    if isinstance(levels, (str, bytes)) or not hasattr(levels, '__len__'):
+        raise ValueError(f'{what}: coverage_levels must be a list of levels, got {levels!r}')
+    if any(not _number(p) for p in levels):
+        raise ValueError(f'{what}: coverage_levels must be numbers, got {list(levels)!r}')
+    levels = tuple(float(p) for p in levels)
+    if not 1 <= len(levels) <= 8:
+        raise ValueError(f'{what}: 1 to 8 coverage levels, got {len(levels)}')
+    if not all(0.0 < p < 1.0 for p in levels) or any(b <= a for a, b in zip(levels, levels[1:])):
+        raise ValueError(f'{what}: coverage_levels must be strictly increasing in (0,1), got {list(levels)}')
+    return levels
+
+
+def landmark_options(cfg_trainer, data_loader=None):
+    """`trainer.landmarks` -> None when off, else {'period': P, 'fixed': indices or None, 'moving': indices or None,
+    'index_base': 0 | 1, 'coverage_levels': (...), 'inverse': bool, 'synthetic': bool}.
+    Absent / false / null: off.  A dict: "fixed" and "moving" name two landmark files (landmarks.read_points: voxel indices of
+    the native volumes, or of the registration grid for a loader without native volumes) with equal counts, read here into
+    (K,3) arrays; "synthetic": true stands in for both when the loader is the synthetic one (`data_loader.native` None) and
+    takes data_loader.synthetic_landmarks; "period" defaults to log_period_MCMC; "inverse": true also carries the moving
+    landmarks into the fixed space.  Refuses `true` (the files must be named), unknown keys, a non-integer P or P < 1, an
+    index_base other than 0 or 1, coverage_levels that are not 1 to 8 strictly increasing numbers in (0,1), a non-bool inverse
+    or synthetic, paths given together with synthetic, a missing path or file, a malformed file, unequal counts, "synthetic"
+    with a loader that reads files, a config that records no step and one that would record more than 2^31 - 1 samples."""
+    from .landmarks import read_points
+    what = 'trainer.landmarks'
+    if cfg_trainer.get('landmarks') is True:
+        raise ValueError(f'{what} must be false or a dict of {list(LANDMARK_OPTION_KEYS)} naming the two landmark files, got True')
+
+    def own_keys(opt):
+        own = {**LANDMARK_DEFAULTS, **{k: v for k, v in opt.items() if k != 'period'}}
+        if isinstance(own['index_base'], bool) or own['index_base'] not in (0, 1):
+            raise ValueError(f'{what}.index_base must be 0 or 1, got {own["index_base"]!r}')
+        for key in ('inverse', 'synthetic'):
+            if not isinstance(own[key], bool):
+                raise ValueError(f'{what}.{key} must be true or false, got {own[key]!r}')
+        out = {'index_base': int(own['index_base']), 'coverage_levels': _coverage_levels(own['coverage_levels'], what),
+               'inverse': own['inverse'], 'synthetic': own['synthetic'], 'fixed': None, 'moving': None}
+        if own['synthetic']:
+            if 'fixed' in own or 'moving' in own:
+                raise ValueError(f'{what}: "synthetic" stands in for the two files; "fixed" / "moving" must not be given with it')
+            if data_loader is not None and getattr(data_loader, 'native', None) is not None:
+                raise ValueError(f'{what}.synthetic: the data loader ({type(data_loader).__name__}) reads image files; its landmarks '
+                                 f'come from "fixed" and "moving" files')
+            return out
+        for key in ('fixed', 'moving'):
+            if not isinstance(own.get(key), str) or not own[key]:
+                raise ValueError(f'{what}.{key}: the path of the {key} landmark file is required, got {own.get(key)!r}')
+            try:
+                out[key] = read_points(own[key], out['index_base'])
+            except OSError as e:
+                raise ValueError(f'{what}.{key}: cannot read {own[key]!r} ({e})') from e
+        if len(out['fixed']) != len(out['moving']):
+            raise ValueError(f'{what}: {len(out["fixed"])} fixed and {len(out["moving"])} moving landmarks; corresponding '
+                             f'landmarks need equal counts')
+        return out
+
+    return _record_options(cfg_trainer, 'landmarks', LANDMARK_OPTION_KEYS, f'a dict of {list(LANDMARK_OPTION_KEYS)}', MAX_RECORDS,
+                           'the record count holds at most {}', own_keys)
+
+
+def landmark_metric_names(options, no_chains):
+    """the metric names the option adds: the unregistered pair at step 0, every chain's record, the final summary"""
+    names = [f'VI/train/TRE/{k}' for k in ('mean', 'median', 'max')]
+    for d in ('TRE', 'TRE_inverse') if options['inverse'] else ('TRE',):
+        names += [f'MCMC/chain_{i}/{d}/{k}' for i in range(no_chains) for k in ('mean', 'max')]
+        names += [f'MCMC/{d}/{k}' for k in LANDMARK_METRICS] + [f'MCMC/{d}/coverage_{p:g}' for p in options['coverage_levels']]
+        names.append(f'MCMC/{d}/error_spread_correlation')
+    return names
+
+
+class LandmarkPosterior(_Recorder):
+    """The posterior of K landmarks carried through the sampled transformation, and of their target registration error, on the
+    device in float64 (14 K numbers whatever the number of records).
+
+    points / targets: (K,3) [-1,1] coordinates in x, y, z component order (landmarks.grid_points) of the landmarks in the space
+    the displacement lives on and of the corresponding points in the space it maps to: fixed -> moving for the forward
+    displacement, moving -> fixed for the one of ops.svf_exp_inverse.  scale: [-1,1] units -> the output unit per channel
+    (default diagnostics.voxel_scale(dims): registration-grid voxels; NativeGrid.mm_scale() for mm); displacement_scale: what
+    one [-1,1] unit is in the unit of the recorded displacement (default voxel_scale(dims): the trainer's displacements are
+    in voxels; (1, 1, 1) for normalised ones).  `record(displacement)` takes the (C,3,D,H,W) float32 displacements of one
+    step, chains in order; `last_tre()` the per-chain mean and max TRE of that step; `finalize(levels)` the table and the
+    summary."""
+    noun = 'landmark posterior'
+
+    def __init__(self, points, targets, dims, device, scale=None, displacement_scale=None):
+        self.dims = tuple(int(d) for d in dims)
+        if len(self.dims) != 3 or min(self.dims) < 2:
+            raise ValueError(f'landmark posterior: three dims of at least 2, got {self.dims}')
+        points, targets = (np.asarray(a, dtype=np.float64) for a in (points, targets))
+        if points.ndim != 2 or points.shape[1] != 3 or points.shape != targets.shape or len(points) < 1:
+            raise ValueError(f'landmark posterior: points and targets must both be (K,3) with K >= 1, got {points.shape} and '
+                             f'{targets.shape}')
+        if not (np.isfinite(points).all() and np.isfinite(targets).all()):
+            raise ValueError('landmark posterior: the landmark coordinates must be finite')
+        three = lambda name, v: self._three(name, voxel_scale(self.dims) if v is None else v)
+        self.scale, self.displacement_scale = three('scale', scale), three('displacement_scale', displacement_scale)
+        self.field_scale = tuple(s / d for s, d in zip(self.scale, self.displacement_scale))
+        self.device, self.K = device, len(points)
+        to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+        sc = np.asarray(self.scale, dtype=np.float64)
+        self.points, self.offset, self.target = to_dev(points), to_dev(points * sc), to_dev(targets * sc)
+        self.state = ops.landmark_state(self.K, device)
+        self.last_mapped = None
+
+    @staticmethod
+    def _three(name, values):
+        values = tuple(float(v) for v in values)
+        if len(values) != 3 or not all(math.isfinite(v) and v > 0 for v in values):
+            raise ValueError(f'landmark posterior: {name} must hold three finite floats > 0, got {values}')
+        return values
+
+    def tre(self, mapped):
+        """(C,K,3) mapped points on the device -> (C,K) float64 distances to the targets on the host (one copy)"""
+        return (mapped.double() - self.target.double()).norm(dim=2).cpu()
+
+    def initial_tre(self):
+        """the TRE of the unregistered pair (zero displacement) per landmark, (K,) float64 on the host"""
+        return (self.offset.double() - self.target.double()).norm(dim=1).cpu()
+
+    def _update(self, displacement):
+        self.last_mapped = ops.transform_points(self.points, displacement.contiguous(), self.field_scale, self.offset)
+        ops.landmark_update(self.last_mapped, self.target, self.state, self.records)
+
+    def last_tre(self):
+        """-> (per-chain mean TRE, per-chain max TRE) of the record just taken over the landmarks with a finite mapped point,
+        two lists of C floats (NaN when a chain has none).  One K-element device-to-host copy."""
+        self._need_records('last_tre')
+        e = self.tre(self.last_mapped).numpy()
+        ok = np.isfinite(e)
+        mean = [float(r[m].mean()) if m.any() else float('nan') for r, m in zip(e, ok)]
+        peak = [float(r[m].max()) if m.any() else float('nan') for r, m in zip(e, ok)]
+        return mean, peak
+
+    def mean_points(self):
+        """-> (K,3) float64 on the device: the posterior-mean mapped points, in the output unit"""
+        self._need_records('mean_points')
+        return self.state['mean']
+
+    def finalize(self, levels=LANDMARK_DEFAULTS['coverage_levels']):
+        """-> (table (K,10) float64 numpy with the columns ops.LANDMARK_COLUMNS, summary dict of landmarks.landmark_summary).
+        One device-to-host read."""
+        from .landmarks import landmark_summary
+        self._need_records('finalize')
+        levels = _coverage_levels(levels, 'landmark posterior')
+        table, isum, fsum = ops.landmark_finalize(self.state, self.target)
+        host = torch.cat([isum.view(torch.float64), fsum, table.reshape(-1)]).cpu()
+        ni, nf = isum.numel(), fsum.numel()
+        table_h = host[ni + nf:].reshape(table.shape).numpy()
+        summary = landmark_summary(table_h, (host[:ni].view(torch.int64).tolist(), host[ni:ni + nf].tolist()), levels)
+        summary['records'] = self.records
+        return table_h, summary
+
+    def state_dict(self):
+        return {**{k: v.detach().cpu() for k, v in self.state.items()}, 'records': self.records,
+                'points': self.points.detach().cpu(), 'target': self.target.detach().cpu()}
+
+    def load_state_dict(self, sd):
+        for key in ('points', 'target'):
+            mine = getattr(self, key).detach().cpu()
+            if tuple(sd[key].shape) != tuple(mine.shape) or not torch.equal(sd[key], mine):
+                raise ValueError(f'landmark posterior: the {key} of the checkpoint ({tuple(sd[key].shape)}) are not those of this run '
+                                 f'({tuple(mine.shape)})')
+        for k, v in self.state.items():
+            if tuple(sd[k].shape) != tuple(v.shape) or sd[k].dtype != v.dtype:
+                raise ValueError(f'landmark posterior of shape {tuple(sd[k].shape)} {sd[k].dtype} ({k}) does not match this run '
+                                 f'({tuple(v.shape)} {v.dtype})')
+        for k, v in self.state.items():
+            v.copy_(sd[k])
+        self.records = int(sd['records'])
+
+
+class LandmarkPair:
+    """What `trainer.landmarks` records: `forward`, the fixed landmarks carried into the moving space by the sampled
+    displacement, and with "inverse" also `inverse`, the moving landmarks carried into the fixed space by the displacement of
+    exp(-v) (ops.svf_exp_inverse).  `record` takes the displacement, or (displacement, dense velocity) with an inverse."""
+
+    def __init__(self, forward, inverse=None, no_steps=12):
+        self.forward, self.inverse, self.no_steps = forward, inverse, int(no_steps)
+
+    @property
+    def records(self):
+        return self.forward.records
+
+    def directions(self):
+        return [('TRE', self.forward)] + ([('TRE_inverse', self.inverse)] if self.inverse is not None else [])
+
+    def record(self, sample):
+        if self.inverse is None:
+            self.forward.record(sample)
+            return
+        displacement, velocity = sample
+        self.forward.record(displacement)
+        self.inverse.record(ops.svf_exp_inverse(velocity.contiguous(), self.no_steps)[1])
+
+    def state_dict(self):
+        return {name: lp.state_dict() for name, lp in self.directions()}
+
+    def load_state_dict(self, sd):
+        if set(sd) != {name for name, _ in self.directions()}:
+            raise ValueError(f'landmark posterior: the checkpoint holds {sorted(sd)}, this run records '
+                             f'{[name for name, _ in self.directions()]} (trainer.landmarks.inverse differs)')
+        for name, lp in self.directions():
+            lp.load_state_dict(sd[name])
 
 
 HAUSDORFF_MAX_PERCENTILES = 4  # IRS_HAUSDORFF_MAX_PERCENTILES

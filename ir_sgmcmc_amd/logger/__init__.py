@@ -9,7 +9,7 @@ from os import path
 
 import numpy as np
 
-from ..utils.imageio import write_nifti, write_vtk_field, write_vtk_grid
+from ..utils.imageio import write_nifti, write_vtk_field, write_vtk_grid, write_vtk_points
 
 
 def setup_logging(save_dir=None, level=logging.INFO):
@@ -221,3 +221,20 @@ def save_native_mean(logger, save_dirs, zooms, displacement_mm, im_warped, model
     logger.info(f'{model} native displacement mean min.: {float(displacement_mm.min()):.2f}, max.: {float(displacement_mm.max()):.2f} mm')
     save_field_to_disk(displacement_mm, path.join(folder, f'{model}_sample_mean_native.vtk'), zooms)
     save_im_to_disk(im_warped, path.join(folder, f'{model}_im_moving_warped_mean_native.nii.gz'), zooms)
+
+
+def save_landmarks(logger, save_dirs, mean_points, table, columns, unit, model='MCMC', tag=''):
+    """the landmark posterior (absent in the reference): samples/{model}_landmarks{tag}.csv, one row per landmark under a header
+    line -- the posterior-mean mapped point (x, y, z) and the columns of ops.LANDMARK_COLUMNS, in `unit` -- and
+    samples/{model}_landmarks{tag}_mean.vtk, the mean points as legacy ASCII POLYDATA with the point scalars tre_of_mean,
+    std_major and pit"""
+    folder = _folder(save_dirs, 'samples')
+    mean_points, table, columns = _np(mean_points), _np(table), list(columns)
+    with open(path.join(folder, f'{model}_landmarks{tag}.csv'), 'w', newline='\n') as f:
+        f.write(','.join(['landmark', 'mean_x', 'mean_y', 'mean_z'] + columns) + '\n')
+        for k, (pt, row) in enumerate(zip(mean_points, table)):
+            f.write(','.join([str(k)] + [repr(float(v)) for v in pt] + [repr(float(v)) for v in row]) + '\n')
+    write_vtk_points(mean_points, path.join(folder, f'{model}_landmarks{tag}_mean.vtk'),
+                     [(name, table[:, columns.index(name)]) for name in ('tre_of_mean', 'std_major', 'pit')],
+                     title=f'posterior-mean landmarks ({unit})')
+    logger.info(f'{model} landmarks{tag}: {len(table)} rows in {unit} -> {model}_landmarks{tag}.csv, {model}_landmarks{tag}_mean.vtk')

@@ -808,3 +808,88 @@ def image_similarity(fixed, moving, mask=None, bins=64, fixed_range=None, moving
                                      f_lo, f_hi, m_lo, m_hi, bins, L.dev_ptr(out.get('hist'), None, True), L.dev_ptr(out['stats']),
                                      L.dev_ptr(ws), nbytes.value, L.stream_ptr()))
     return out
+
+
+LANDMARK_COLUMNS = ('count', 'tre_mean', 'tre_std', 'tre_max', 'tre_of_mean', 'std_major', 'std_middle', 'std_minor', 'mahalanobis2',
+                    'pit')
+LANDMARK_STATE = (('mean', 3, torch.float64), ('comoment', 6, torch.float64), ('tre_mean', None, torch.float64),
+                  ('tre_m2', None, torch.float64), ('tre_max', None, torch.float64), ('count', None, torch.int32))
+
+
+def _points(name, t, K=None):
+    if t.dim() != 2 or t.shape[1] != 3 or t.dtype != torch.float32 or (K is not None and t.shape[0] != K):
+        raise L.IrsError(f'{name} must be a ({"K" if K is None else K},3) torch.float32 tensor, got {t.dtype} {tuple(t.shape)}')
+    if not 1 <= t.shape[0] <= L.IRS_LANDMARK_MAX_POINTS:
+        raise L.IrsError(f'{name}: K = {t.shape[0]} points, 1..{L.IRS_LANDMARK_MAX_POINTS} needed')
+    return t.shape[0]
+
+
+def transform_points(points, displacement, scale=(1.0, 1.0, 1.0), offset=None, want_sampled=False):
+    """A displacement evaluated at K positions that need not be voxel centres (absent in the reference, which has no point-set
+    operator).  points (K,3) float32 in [-1,1] coordinates, component 0 = x (the last axis); displacement (C,3,D,H,W) float32
+    in any linear unit; scale: three positive floats, one per channel; offset (K,3) float32 or None (= 0).  -> mapped (C,K,3)
+    float32 = scale_c * sampled_c + offset_c, or (mapped, sampled) with want_sampled: sampled (C,K,3) is the field sampled
+    trilinearly at the point (border clamp, align_corners: a point on a voxel centre returns the stored value bit for bit).
+    With the point's position in the output unit as the offset, mapped is the mapped point: warped(x) = moving(x + d(x)), so
+    a point of the fixed grid lands in the moving image; the displacement of svf_exp_inverse carries points of the moving
+    space to the fixed one.  A point with a non-finite coordinate gives NaN rows.  include/irsgmcmc.h has the rounding
+    order.  No host synchronisation."""
+    lib = L.load()
+    Cn, D, H, W = _dims5(displacement, 3)
+    K = _points('points', points)
+    if offset is not None:
+        _points('offset', offset, K)
+    dev = displacement.device
+    mapped = torch.empty((Cn, K, 3), device=dev, dtype=torch.float32)
+    sampled = torch.empty((Cn, K, 3), device=dev, dtype=torch.float32) if want_sampled else None
+    L.check(lib.irs_transform_points(L.dev_ptr(points, torch.float32), K, L.dev_ptr(displacement, torch.float32), Cn, D, H, W,
+                                     _three_positive('scale', scale), L.dev_ptr(offset, torch.float32, True),
+                                     L.dev_ptr(sampled, None, True), L.dev_ptr(mapped), L.stream_ptr()))
+    return (mapped, sampled) if want_sampled else mapped
+
+
+def landmark_state(K, device):
+    """a fresh state of the landmark posterior: {'mean' (K,3), 'comoment' (K,6: xx, xy, xz, yy, yz, zz), 'tre_mean', 'tre_m2',
+    'tre_max' (K) float64, 'count' (K) int32}, all zero"""
+    return {name: torch.zeros((K,) if ch is None else (K, ch), device=device, dtype=dtype) for name, ch, dtype in LANDMARK_STATE}
+
+
+def _landmark_state(state, K):
+    for name, ch, dtype in LANDMARK_STATE:
+        t, shape = state[name], ((K,) if ch is None else (K, ch))
+        if tuple(t.shape) != shape or t.dtype != dtype:
+            raise L.IrsError(f'{name} must be a {shape} {dtype} tensor, got {t.dtype} {tuple(t.shape)}')
+    return [L.dev_ptr(state[name], dtype) for name, _, dtype in LANDMARK_STATE]
+
+
+def landmark_update(mapped, target, state, records_before):
+    """Fold one recorded step into the landmark posterior (absent in the reference): mapped (C,K,3) float32, every chain's
+    mapped landmarks; target (K,3) float32, the corresponding points in the same unit; state: the dict of landmark_state,
+    updated in place in float64 with the finite samples in chain order after `records_before` records (0 overwrites the
+    state).  A non-finite sample is skipped for that landmark and not counted.  No host synchronisation."""
+    lib = L.load()
+    if mapped.dim() != 3 or mapped.shape[2] != 3 or mapped.dtype != torch.float32:
+        raise L.IrsError(f'mapped must be a (C,K,3) torch.float32 tensor, got {mapped.dtype} {tuple(mapped.shape)}')
+    Cn, K = mapped.shape[:2]
+    _points('target', target, K)
+    L.check(lib.irs_landmark_update(L.dev_ptr(mapped, torch.float32), L.dev_ptr(target, torch.float32), Cn, K,
+                                    *_landmark_state(state, K), int(records_before), L.stream_ptr()))
+
+
+def landmark_finalize(state, target):
+    """The per-landmark table and the summary of the landmark posterior (absent in the reference).  state: the dict of
+    landmark_state; target (K,3) float32.  -> (table (K,10) float64 with the columns LANDMARK_COLUMNS, isummary (3,) int64
+    {landmarks, landmarks without a finite sample, landmarks with a finite pit}, fsummary (4,) float64 {sum / max
+    tre_of_mean, sum tre_mean, max tre_max} over the others), on the device: include/irsgmcmc.h gives the definitions.  No
+    host synchronisation."""
+    lib = L.load()
+    K = _points('target', target)
+    ptrs = _landmark_state(state, K)
+    dev = target.device
+    ws = torch.empty(L.IRS_LANDMARK_WS_BYTES, device=dev, dtype=torch.uint8)
+    table = torch.empty((K, L.IRS_LANDMARK_COLUMNS), device=dev, dtype=torch.float64)
+    isummary = torch.empty(L.IRS_LANDMARK_SUMMARY_INTS, device=dev, dtype=torch.int64)
+    fsummary = torch.empty(L.IRS_LANDMARK_SUMMARY_FLOATS, device=dev, dtype=torch.float64)
+    L.check(lib.irs_landmark_finalize(*ptrs, L.dev_ptr(target, torch.float32), K, L.dev_ptr(table), L.dev_ptr(isummary),
+                                      L.dev_ptr(fsummary), L.dev_ptr(ws), L.IRS_LANDMARK_WS_BYTES, L.stream_ptr()))
+    return table, isummary, fsummary

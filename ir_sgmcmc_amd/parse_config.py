@@ -15,7 +15,7 @@ from .diagnostics import (COVARIANCE_METRICS, ICE_SPACES, JACOBIAN_METRICS, LABE
                           diagnostics_period, displacement_covariance_options, displacement_quantiles_options, ess_options,
                           hausdorff_metric_names, hausdorff_options, image_similarity_metric_names, image_similarity_options,
                           inverse_consistency_options, jacobian_posterior_options, label_posterior_options,
-                          native_resolution_options)
+                          landmark_metric_names, landmark_options, native_resolution_options)
 from .logger import setup_logging
 from .model import distributions as model_distr
 from .model import loss as model_loss
@@ -126,6 +126,9 @@ class ConfigParser:
             m += [f'MCMC/ICE/{space}/{k}' for space in ICE_SPACES for k in ('mean', 'max', f'frac_above_{ice["threshold"]:g}')]
         if image_similarity_options(self['trainer']) is not None:
             m += image_similarity_metric_names(C)
+        landmarks = landmark_options(self['trainer'])
+        if landmarks is not None:
+            m += landmark_metric_names(landmarks, C)
         return m
 
     def init_transformation_and_registration_modules(self):

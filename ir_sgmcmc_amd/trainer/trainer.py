@@ -20,13 +20,14 @@ import torch
 from ..base import BaseTrainer
 from .. import ops
 from ..diagnostics import (COVARIANCE_METRICS, ChainMoments, DisplacementCovariance, DisplacementQuantiles, ICE_SPACES,
-                           InverseConsistency, JACOBIAN_METRICS, JacobianPosterior, LABEL_STRUCTURE_METRICS, LabelPosterior,
-                           QUANTILE_METRICS, diagnostics_period, displacement_covariance_options, displacement_quantiles_options,
+                           InverseConsistency, JACOBIAN_METRICS, JacobianPosterior, LABEL_STRUCTURE_METRICS, LANDMARK_METRICS,
+                           LabelPosterior, LandmarkPair, LandmarkPosterior, QUANTILE_METRICS, diagnostics_period, displacement_covariance_options, displacement_quantiles_options,
                            ess_options, hausdorff_options, image_similarity_options, inverse_consistency_options, is_recorded,
-                           jacobian_posterior_options, label_posterior_options, native_resolution_options, SIMILARITY_METRICS)
+                           jacobian_posterior_options, label_posterior_options, landmark_options, native_resolution_options,
+                           SIMILARITY_METRICS, voxel_scale)
 from ..engine import EngineConfig, TransitionEngine
 from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_quantiles, save_ess,
-                      save_field, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_native_mean,
+                      save_field, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_landmarks, save_native_mean,
                       save_native_sample, save_rhat, save_sample)
 from ..utils import (calc_DSC_GPU, calc_image_similarity, calc_norm, calc_no_non_diffeomorphic_voxels, init_identity_grid_3D,
                      sample_q_v, transform_coordinates)
@@ -115,6 +116,10 @@ class Trainer(VIMixin, BaseTrainer):
         self.similarity_options = image_similarity_options(cfg_trainer)
         self._similarity_ranges, self._similarity_warned = None, False
         self.similarity_summary = None
+        # landmark propagation and target registration error (diagnostics.LandmarkPosterior): None when trainer.landmarks is off
+        self.landmark_options = landmark_options(cfg_trainer, data_loader)
+        self._landmarks, self._landmark_unit = None, None
+        self.landmark_summary = None
 
     # ---------------------------------------------------------------- engine plumbing
     def _engine_config(self):
@@ -200,7 +205,7 @@ class Trainer(VIMixin, BaseTrainer):
 
     def _recorders(self):
         """the active recorders, in the order they record and finish: moments, labels, Jacobian, covariance, quantiles,
-        inverse consistency"""
+        inverse consistency, landmarks"""
         period = lambda options: options and options['period']
         rows = (('chain_moments', self._chain_moments, self.diagnostics_period, 'convergence_diagnostics', 'chain moments',
                  'displacement', self._finish_diagnostics, 'moving_mask'),
@@ -214,7 +219,10 @@ class Trainer(VIMixin, BaseTrainer):
                 ('displacement_quantiles', self._displacement_quantiles, period(self.quantiles_options), 'displacement_quantiles',
                  'displacement quantiles', 'displacement', self._finish_displacement_quantiles, 'moving_mask'),
                 ('inverse_consistency', self._inverse_consistency, period(self.ice_options), 'inverse_consistency',
-                 'inverse consistency', ('velocity', 'transformation', 'displacement'), self._finish_inverse_consistency, 'masks'))
+                 'inverse consistency', ('velocity', 'transformation', 'displacement'), self._finish_inverse_consistency, 'masks'),
+                ('landmarks', self._landmarks, period(self.landmark_options), 'landmarks', 'landmark posterior',
+                 ('displacement', 'velocity') if self.landmark_options and self.landmark_options['inverse'] else 'displacement',
+                 self._finish_landmarks, 'masks'))
         return [Recorder(*row) for row in rows if row[1] is not None]
 
     # ---------------------------------------------------------------- checkpoint / resume (absent in the reference)
@@ -388,6 +396,8 @@ class Trainer(VIMixin, BaseTrainer):
             self._native_init()
         if self.similarity_options is not None:
             self._similarity_init(fixed, moving)
+        if self.landmark_options is not None:
+            self._landmarks_init(self._outputs['displacement'].shape[2:])
         if cfg_trainer.get('resume'):
             self.load_checkpoint(cfg_trainer['resume'])
             first = self._sample_no + 1
@@ -490,6 +500,11 @@ class Trainer(VIMixin, BaseTrainer):
                             save_field(self.config.save_dirs, spacing, d_inv[idx] * spacing[0],
                                        f'chain_{idx}_sample_{sample_no:07}_displacement_inverse', 'MCMC')
                 ice.last_inverse = None  # two fields: not kept between steps
+            if self._landmarks is not None and any(r.state is self._landmarks for r in due):
+                for name, lp in self._landmarks.directions():
+                    for idx, (tre_mean, tre_max) in enumerate(zip(*lp.last_tre())):
+                        self.metrics.update(f'MCMC/chain_{idx}/{name}/mean', tre_mean)
+                        self.metrics.update(f'MCMC/chain_{idx}/{name}/max', tre_max)
             if checkpoint_period and sample_no % checkpoint_period == 0:
                 self._sample_no, self._moments = sample_no, {'mean': mean, 'm2': m2, 'n': n_rec}
                 folder = self.config.save_dirs['checkpoints']
@@ -710,6 +725,65 @@ class Trainer(VIMixin, BaseTrainer):
         row = self._image_similarity(fixed, moving['im'][:1])[0]
         self._log_similarity(['VI/train/similarity'], [row])
         self._similarity_summary('unregistered', row, 'the unregistered pair')
+
+    def _landmarks_init(self, dims):
+        """trainer.landmarks -> self._landmarks (diagnostics.LandmarkPair), once: the landmark files' voxel indices carried to
+        [-1,1] coordinates of the registration grid -- through the native geometry when the loader has native volumes (the TRE
+        is then in mm under the header zooms), else as indices of the registration grid (the TRE is in its voxels)"""
+        from ..data_loader.synthetic import synthetic_landmarks
+        from ..landmarks import grid_points, registration_grid_points
+        if self._landmarks is not None:
+            return
+        opt, dims = self.landmark_options, tuple(int(d) for d in dims)
+        native = getattr(self.data_loader, 'native', None)
+        if native is not None:
+            grid = self._native['grid'] if self._native is not None else native()['grid']
+            fixed_pts, moving_pts = grid_points(opt['fixed'], grid), grid_points(opt['moving'], grid)
+            scale, self._landmark_unit = grid.mm_scale(), 'mm'
+        else:
+            fixed_idx, moving_idx = synthetic_landmarks(dims) if opt['synthetic'] else (opt['fixed'], opt['moving'])
+            fixed_pts, moving_pts = registration_grid_points(fixed_idx, dims), registration_grid_points(moving_idx, dims)
+            scale, self._landmark_unit = voxel_scale(dims), 'voxels'
+        new = lambda points, targets: LandmarkPosterior(points, targets, dims, self.device, scale=scale)
+        self._landmarks = LandmarkPair(new(fixed_pts, moving_pts), new(moving_pts, fixed_pts) if opt['inverse'] else None,
+                                       getattr(self.transformation_module, 'no_steps', 12))
+        self.logger.info(f'landmarks: {len(fixed_pts)} pairs, TRE in {self._landmark_unit}' +
+                         (', both directions' if opt['inverse'] else ''))
+
+    def _log_landmarks_unregistered(self, fixed):
+        """step 0: the TRE of the unregistered pair (zero displacement) under VI/train/TRE/{mean,median,max}"""
+        self._landmarks_init(fixed['im'].shape[2:])
+        e = self._landmarks.forward.initial_tre().numpy()
+        self.writer.set_step(0)
+        for key, value in (('mean', e.mean()), ('median', np.median(e)), ('max', e.max())):
+            self.metrics.update(f'VI/train/TRE/{key}', float(value))
+        self.logger.info(f'TRE of the unregistered pair over {e.size} landmarks: mean {e.mean():.4g}, median {np.median(e):.4g}, '
+                         f'max {e.max():.4g} {self._landmark_unit}')
+
+    def _finish_landmarks(self, masks, spacing, save_outputs):
+        """the per-landmark table and the summary of the landmark posterior -> self.landmark_summary ({'unit', 'TRE': {...,
+        'columns', 'table'}[, 'TRE_inverse': {...}]}), the MCMC/TRE[_inverse]/* metrics and, with save_outputs,
+        samples/MCMC_landmarks[_inverse].csv and samples/MCMC_landmarks[_inverse]_mean.vtk.  The masks are not used: a landmark is a
+        point, not a voxel."""
+        levels = self.landmark_options['coverage_levels']
+        self.landmark_summary = {'unit': self._landmark_unit}
+        for name, lp in self._landmarks.directions():
+            table, s = lp.finalize(levels)
+            for key in LANDMARK_METRICS:
+                self.metrics.update(f'MCMC/{name}/{key}', s[key])
+            for level, value in s['coverage'].items():
+                self.metrics.update(f'MCMC/{name}/coverage_{level}', value)
+            self.metrics.update(f'MCMC/{name}/error_spread_correlation', s['error_spread_correlation'])
+            self.landmark_summary[name] = {**s, 'columns': list(ops.LANDMARK_COLUMNS), 'table': table.tolist()}
+            self.logger.info(f'landmark posterior ({name}) of {s["records"]} samples at {s["landmarks"]} landmarks '
+                             f'({s["empty_landmarks"]} without a finite sample), in {self._landmark_unit}: TRE of the mean '
+                             f'{s["of_mean_mean"]:.4g} (median {s["of_mean_median"]:.4g}, max {s["of_mean_max"]:.4g}), of the samples '
+                             f'{s["sample_mean"]:.4g} (max {s["sample_max"]:.4g}); coverage ' +
+                             ', '.join(f'{v:.3f} at {k}' for k, v in s['coverage'].items()) +
+                             f'; error / spread correlation {s["error_spread_correlation"]:.3f}')
+            if save_outputs:
+                save_landmarks(self.logger, self.config.save_dirs, lp.mean_points().cpu().numpy(), table, ops.LANDMARK_COLUMNS,
+                               self._landmark_unit, 'MCMC', '' if name == 'TRE' else '_inverse')
 
     def _dense_velocity(self, output):
         """the velocity field the forward exponential of this transition integrated, (C,3,D,H,W) in voxel units: the recorded

@@ -5,6 +5,7 @@ Formats are the ones the reference reads and writes:
     written by logger/logger.py:83-100 through nibabel (identity affine, units mm, zooms = spacing);
   * legacy VTK `.vtk`: vector fields as STRUCTURED_POINTS + VECTORS "field" (logger/logger.py:35-60) and sampling grids as
     STRUCTURED_GRID (logger/logger.py:63-80), both with x running fastest as VTK requires.
+  * point sets as legacy ASCII POLYDATA (`write_vtk_points`; absent in the reference).
 Arrays use the reference's index order [x][y][z] (nibabel's `get_fdata()`; SimpleITK's array transposed (2, 1, 0)).
 Host-side, numpy only; nothing here is on the SG-MCMC hot path.
 """
@@ -134,6 +135,32 @@ def write_vtk_grid(grid, path):
         f.write(f'DIMENSIONS {nx} {ny} {nz}\nPOINTS {nx * ny * nz} float\n'.encode())
         f.write(pts.astype('>f4').tobytes())
         f.write(b'\n')
+
+
+def write_vtk_points(points, path, scalars=None, title='points'):
+    """A point set -> legacy ASCII POLYDATA (absent in the reference, which writes no points): points (K,3) as POINTS of type
+    float, one per line, one VERTICES cell per point (a viewer draws cells, not bare points), and `scalars`, a dict or a
+    sequence of (name, K values), as POINT_DATA SCALARS of type float with the default lookup table.  Numbers are written with
+    nine significant digits, what a float32 needs; a NaN is written as `nan`."""
+    pts = np.asarray(points, dtype=np.float32)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError(f'points must have shape (K, 3), got {pts.shape}')
+    K = len(pts)
+    scalars = list(scalars.items()) if isinstance(scalars, dict) else list(scalars or ())
+    num = lambda v: f'{float(v):.9g}'
+    lines = ['# vtk DataFile Version 3.0', str(title), 'ASCII', 'DATASET POLYDATA', f'POINTS {K} float']
+    lines += [' '.join(num(v) for v in row) for row in pts]
+    lines.append(f'VERTICES {K} {2 * K}')
+    lines += [f'1 {i}' for i in range(K)]
+    if scalars:
+        lines.append(f'POINT_DATA {K}')
+    for name, values in scalars:
+        values = np.asarray(values, dtype=np.float32).reshape(-1)
+        if len(values) != K or not str(name) or any(ch.isspace() for ch in str(name)):
+            raise ValueError(f'scalars {name!r}: {len(values)} values for {K} points, or a name with blanks')
+        lines += [f'SCALARS {name} float 1', 'LOOKUP_TABLE default'] + [num(v) for v in values]
+    with open(path, 'w', newline='\n') as f:
+        f.write('\n'.join(lines) + '\n')
 
 
 def read_vtk_vectors(path):
