@@ -1,0 +1,1015 @@
+// C ABI (include/irsgmcmc.h), the stateless part: the error plumbing and every operator and diagnostic that needs no context --
+// argument validation (api_checks.h), workspace layout, launches.  No exceptions / aborts cross this boundary; errors come back
+// as codes + irs_last_error().  The switches are in knobs.hip, the context and the SG-MCMC transition in api_ctx.hip.
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <mutex>
+#include <vector>
+
+#include "api_checks.h"
+
+using namespace irs;
+
+namespace irs {
+
+static thread_local char g_err[512] = "";
+
+int fail(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return 1;
+}
+
+// `dense` / `g_dense` hold the planes [store_lo, store_lo + store_n) of the volume (whole volume: 0, D); up-sampling produces the
+// planes [w_lo, w_lo + w_n), the adjoint sums over them (a rank's own planes: partial control-grid gradients, all-reduced)
+int ffd_up(const float* v_cp, float* dense, float* tmp, int C, Vol vol, const int G[3], const SplineTaps spl[3], hipStream_t st,
+           int w_lo, int w_n, int store_lo, int store_n) {
+    // axis order of utils/transformation.py:146-149: tensor axis 2 (D, cps[0]), 3 (H, cps[1]), 4 (W, cps[2])
+    if (w_n < 0) { w_lo = 0; w_n = vol.D; }
+    if (store_n < 0) { store_lo = 0; store_n = vol.D; }
+    const int64_t CC = (int64_t)C * 3;
+    float* t1 = tmp;
+    float* t2 = tmp + CC * store_n * G[1] * G[2];
+    launch_ffd_axis(v_cp, t1, spl[0], false, CC, G[0], vol.D, (int64_t)G[1] * G[2], st, w_lo, w_n, store_lo, store_n);
+    launch_ffd_axis(t1, t2, spl[1], false, CC * store_n, G[1], vol.H, G[2], st);
+    launch_ffd_axis(t2, dense, spl[2], false, CC * store_n * vol.H, G[2], vol.W, 1, st);
+    return 0;
+}
+
+int ffd_adjoint(const float* g_dense, float* g_cp, float* tmp, int C, Vol vol, const int G[3], const SplineTaps spl[3],
+                hipStream_t st, int w_lo, int w_n, int store_lo, int store_n) {
+    if (w_n < 0) { w_lo = 0; w_n = vol.D; }
+    if (store_n < 0) { store_lo = 0; store_n = vol.D; }
+    const int64_t CC = (int64_t)C * 3;
+    float* t1 = tmp;
+    float* t2 = tmp + CC * store_n * vol.H * G[2];
+    launch_ffd_axis(g_dense, t1, spl[2], true, CC * store_n * vol.H, vol.W, G[2], 1, st);
+    launch_ffd_axis(t1, t2, spl[1], true, CC * store_n, vol.H, G[1], G[2], st);
+    launch_ffd_axis(t2, g_cp, spl[0], true, CC, vol.D, G[0], (int64_t)G[1] * G[2], st, w_lo, w_n, store_lo, store_n);
+    return 0;
+}
+
+}  // namespace irs
+
+extern "C" {
+
+const char* irs_last_error(void) { return irs::g_err; }
+const char* irs_version(void) { return "ir-sgmcmc-amd 0.1 (gfx950)"; }
+size_t irs_reduce_scratch_doubles(void) { return (size_t)kMaxPartialBlocks * IRS_MAX_CHAINS; }
+
+// ================================================================================================
+// stateless operators
+// ================================================================================================
+
+int irs_perturb_smooth(const float* v, const float* sigma, const float* eps, float tau, const float* kernel, int s,
+                       int C, int D, int H, int W, float* tmp, float* out, uint64_t seed, uint64_t iteration,
+                       void* stream) {
+    if (!v || !out || !dims_ok(C, D, H, W)) return fail("irs_perturb_smooth: bad arguments");
+    if (s < 0 || s > IRS_MAX_HALF_WIDTH || (s > 0 && (!kernel || !tmp))) return fail("irs_perturb_smooth: bad kernel/s");
+    hipStream_t st = (hipStream_t)stream;
+    const Vol vol = make_vol(D, H, W);
+    const size_t bytes = (size_t)C * 3 * vol.V * sizeof(float);
+    if (s == 0) {
+        if (tau >= 0.0f) launch_perturb(v, sigma, eps, sqrtf(2.0f * tau), out, C, vol, seed, iteration, nullptr, st);
+        else HIP_TRY(hipMemcpyAsync(out, v, bytes, hipMemcpyDeviceToDevice, st));
+        LAUNCH_CHECK();
+        return 0;
+    }
+    Taps taps;
+    taps.s = s;
+    for (int i = 0; i <= 2 * s; ++i) taps.k[i] = kernel[i];
+    const float* src = v;
+    if (tau >= 0.0f && global_knobs().fuse_noise) {  // the noise is generated while the smoothing kernel stages its planes
+        launch_perturb_sobolev_march(v, sigma, eps, (float)sqrt(2.0 * (double)tau), out, taps, C, vol, nullptr, 12, seed, iteration, nullptr, st);
+        LAUNCH_CHECK();
+        return 0;
+    }
+    if (tau >= 0.0f) {
+        launch_perturb(v, sigma, eps, (float)sqrt(2.0 * (double)tau), out, C, vol, seed, iteration, nullptr, st);
+        src = out;
+    }
+    if (src == out) {  // the marching kernel cannot run in place
+        HIP_TRY(hipMemcpyAsync(tmp, out, bytes, hipMemcpyDeviceToDevice, st));
+        src = tmp;
+    }
+    launch_sobolev_march(src, out, taps, C * 3, vol, nullptr, 12, st);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_svf_exp_fwd(const float* v, float* steps, float* transformation, float* displacement, int no_steps, int C,
+                    int D, int H, int W, void* stream) {
+    if (!v || !steps || !dims_ok(C, D, H, W) || no_steps < 1 || no_steps > 30) return fail("irs_svf_exp_fwd: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const Vol vol = make_vol(D, H, W);
+    Lin lin;
+    if (cached_lin(D, H, W, st, &lin)) return fail("irs_svf_exp_fwd: identity grid allocation failed");
+    const int64_t field = (int64_t)C * 3 * vol.V;
+    for (int k = 0; k < no_steps; ++k) {
+        const float* in = k == 0 ? v : steps + (int64_t)(k - 1) * field;
+        launch_exp_step_fwd_march(in, steps + (int64_t)k * field, k == 0, no_steps, C, vol, lin, nullptr, nullptr, false, 0, st);
+    }
+    if (transformation || displacement)
+        launch_svf_outputs(steps + (int64_t)(no_steps - 1) * field, transformation, displacement, C, vol, lin, st);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+static int exp_backward(const float* v, const float* steps, const float* g_last, float* gA, float* gB, int no_steps, int C,
+                        Vol vol, Lin lin, hipStream_t st, float** result) {
+    const int64_t field = (int64_t)C * 3 * vol.V;
+    const float* G = g_last;
+    float* bufs[2] = {gA, gB};
+    int cur = 0;
+    // Scratch of the stateless operator, one set PER DEVICE (a pointer of device 0 is no use to a launch on device 1), guarded
+    // by a mutex and regrown only after the WHOLE device has drained (another stream may still be reading the old block).
+    // [32 steps][8 chains][4] bounds + the coarse displacement extrema of the any-radius adjoint (kernels.h).
+    struct Scratch {
+        unsigned* dmax = nullptr;
+        float* cmm = nullptr;
+        size_t cmm_bytes = 0;
+    };
+    static Scratch per_device[64];
+    static std::mutex mu;
+    int dev_id = 0;
+    HIP_TRY(hipGetDevice(&dev_id));
+    if (dev_id < 0 || dev_id >= 64) return fail("irs_svf_exp_bwd: device ordinal %d out of range", dev_id);
+    unsigned* dmax;
+    float* cmm;
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        Scratch& sc = per_device[dev_id];
+        if (!sc.dmax) HIP_TRY(hipMalloc((void**)&sc.dmax, sizeof(unsigned) * 4 * IRS_MAX_CHAINS * 32));
+        if (coarse_minmax_bytes(vol, C) > sc.cmm_bytes) {
+            HIP_TRY(hipDeviceSynchronize());
+            if (sc.cmm) HIP_TRY(hipFree(sc.cmm));
+            sc.cmm = nullptr;
+            sc.cmm_bytes = 0;
+            HIP_TRY(hipMalloc((void**)&sc.cmm, coarse_minmax_bytes(vol, C)));
+            sc.cmm_bytes = coarse_minmax_bytes(vol, C);
+        }
+        dmax = sc.dmax;
+        cmm = sc.cmm;
+    }
+    if (C > IRS_MAX_CHAINS || no_steps > 32) return fail("irs_svf_exp_bwd: at most %d chains / 32 steps", IRS_MAX_CHAINS);
+    HIP_TRY(hipMemsetAsync(dmax, 0, sizeof(unsigned) * 4 * IRS_MAX_CHAINS * 32, st));
+    for (int k = no_steps - 1; k >= 0; --k) {
+        float* out = bufs[cur];
+        const float* dk = k == 0 ? v : steps + (int64_t)(k - 1) * field;
+        // every variant is launched (radius-1 / radius-2 gather, any-radius fixed-point scatter); the device picks by max|d_k|
+        launch_field_absmax(dk, k == 0, no_steps, dmax + (int64_t)k * IRS_MAX_CHAINS * 4, C, vol, st);
+        launch_exp_step_bwd_march(G, dk, out, k == 0, no_steps, C, vol, lin, dmax + (int64_t)k * IRS_MAX_CHAINS * 4, 2, false, nullptr, 0, nullptr, st);
+        launch_exp_step_bwd_lds(G, dk, out, k == 0, no_steps, C, vol, lin, dmax + (int64_t)k * IRS_MAX_CHAINS * 4, 2, 2, nullptr, 0, cmm, st);
+        G = out;
+        cur ^= 1;
+    }
+    *result = const_cast<float*>(G);
+    return 0;
+}
+
+int irs_svf_exp_bwd(const float* v, const float* steps, const float* g_last, float* scratch, float* g_v, int no_steps,
+                    int C, int D, int H, int W, void* stream) {
+    if (!v || !steps || !g_last || !scratch || !g_v || !dims_ok(C, D, H, W) || no_steps < 1 || no_steps > 30)
+        return fail("irs_svf_exp_bwd: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const Vol vol = make_vol(D, H, W);
+    Lin lin;
+    if (cached_lin(D, H, W, st, &lin)) return fail("irs_svf_exp_bwd: identity grid allocation failed");
+    const int64_t field = (int64_t)C * 3 * vol.V;
+    float* res = nullptr;
+    if (exp_backward(v, steps, g_last, scratch, scratch + field, no_steps, C, vol, lin, st, &res)) return 1;
+    float s[3];
+    prescale_factors(vol, no_steps, s);
+    launch_scale_channels(res, g_v, s[0], s[1], s[2], C, vol, st);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_ffd_up(const float* v_cp, float* dense, float* tmp, int C, int D, int H, int W, int c0, int c1, int c2,
+               void* stream) {
+    if (!v_cp || !dense || !tmp || !dims_ok(C, D, H, W) || c0 < 1 || c1 < 1 || c2 < 1 || c0 > 8 || c1 > 8 || c2 > 8)
+        return fail("irs_ffd_up: bad arguments");
+    const Vol vol = make_vol(D, H, W);
+    const int G[3] = {control_points(D, c0), control_points(H, c1), control_points(W, c2)};
+    const SplineTaps spl[3] = {make_spline(c0), make_spline(c1), make_spline(c2)};
+    ffd_up(v_cp, dense, tmp, C, vol, G, spl, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_ffd_adjoint(const float* g_dense, float* g_cp, float* tmp, int C, int D, int H, int W, int c0, int c1, int c2,
+                    void* stream) {
+    if (!g_dense || !g_cp || !tmp || !dims_ok(C, D, H, W) || c0 < 1 || c1 < 1 || c2 < 1 || c0 > 8 || c1 > 8 || c2 > 8)
+        return fail("irs_ffd_adjoint: bad arguments");
+    const Vol vol = make_vol(D, H, W);
+    const int G[3] = {control_points(D, c0), control_points(H, c1), control_points(W, c2)};
+    const SplineTaps spl[3] = {make_spline(c0), make_spline(c1), make_spline(c2)};
+    ffd_adjoint(g_dense, g_cp, tmp, C, vol, G, spl, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_warp_fwd(const float* im, int Cim, const float* d_last, const float* unif, float alpha, float* warped, int C,
+                 int D, int H, int W, uint64_t seed, uint64_t iteration, void* stream) {
+    if (!im || !d_last || !warped || !dims_ok(C, D, H, W) || !broadcast_ok(Cim, C)) return fail("irs_warp_fwd: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const Vol vol = make_vol(D, H, W);
+    Lin lin;
+    if (cached_lin(D, H, W, st, &lin)) return fail("irs_warp_fwd: identity grid allocation failed");
+    launch_warp_fwd(im, Cim == 1 ? 0 : vol.V, d_last, unif, alpha, warped, nullptr, 0, C, vol, lin, seed, iteration, nullptr, st);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_warp_bwd(const float* im, int Cim, const float* d_last, const float* unif, float alpha, const float* g_warped,
+                 float* g_d, int C, int D, int H, int W, uint64_t seed, uint64_t iteration, void* stream) {
+    if (!im || !d_last || !g_warped || !g_d || !dims_ok(C, D, H, W) || !broadcast_ok(Cim, C))
+        return fail("irs_warp_bwd: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const Vol vol = make_vol(D, H, W);
+    Lin lin;
+    if (cached_lin(D, H, W, st, &lin)) return fail("irs_warp_bwd: identity grid allocation failed");
+    launch_warp_bwd(im, Cim == 1 ? 0 : vol.V, d_last, unif, alpha, g_warped, g_d, C, vol, lin, seed, iteration, nullptr, st);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_warp_transformation(const float* im, int Cim, const float* transformation, float* warped, int C, int D, int H,
+                            int W, void* stream) {
+    if (!im || !transformation || !warped || !dims_ok(C, D, H, W) || !broadcast_ok(Cim, C))
+        return fail("irs_warp_transformation: bad arguments");
+    const Vol vol = make_vol(D, H, W);
+    launch_warp_transformation(im, Cim == 1 ? 0 : vol.V, transformation, warped, C, vol, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_warp_nearest_u8(const uint8_t* seg, int Cim, const float* transformation, uint8_t* out, int C, int D, int H,
+                        int W, void* stream) {
+    if (!seg || !transformation || !out || !dims_ok(C, D, H, W) || !broadcast_ok(Cim, C))
+        return fail("irs_warp_nearest_u8: bad arguments");
+    const Vol vol = make_vol(D, H, W);
+    launch_warp_nearest_u8(seg, Cim == 1 ? 0 : vol.V, transformation, out, C, vol, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_warp_nearest_i16(const int16_t* seg, int Cim, const float* transformation, int16_t* out, int C, int D, int H,
+                         int W, void* stream) {
+    if (!seg || !transformation || !out || !dims_ok(C, D, H, W) || !broadcast_ok(Cim, C))
+        return fail("irs_warp_nearest_i16: bad arguments");
+    const Vol vol = make_vol(D, H, W);
+    launch_warp_nearest_i16(seg, Cim == 1 ? 0 : vol.V, transformation, out, C, vol, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_lcc_normalise(const float* im, float* out, float* sigma_out, int s, int C, int D, int H, int W, void* stream) {
+    if (!im || !out || !dims_ok(C, D, H, W)) return fail("irs_lcc_normalise: bad arguments");
+    if (!lcc_ok(s, D, H, W)) return fail("irs_lcc_normalise: LCC half width must be 1 or 2 and smaller than half the volume");
+    launch_lcc_fwd_march(nullptr, 0, im, out, sigma_out, s, C, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_lcc_map_fwd(const float* fhat, int Cf, const float* warped, float* z, float* sigma_m, int s, int C, int D,
+                    int H, int W, void* stream) {
+    if (!fhat || !warped || !z || !sigma_m || !dims_ok(C, D, H, W) || !broadcast_ok(Cf, C))
+        return fail("irs_lcc_map_fwd: bad arguments");
+    if (!lcc_ok(s, D, H, W)) return fail("irs_lcc_map_fwd: LCC half width must be 1 or 2 and smaller than half the volume");
+    const Vol vol = make_vol(D, H, W);
+    launch_lcc_fwd_march(fhat, Cf == 1 ? 0 : vol.V, warped, z, sigma_m, s, C, vol, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_lcc_map_bwd(const float* fhat, int Cf, const float* z, const float* sigma_m, const float* g_z, float* g_warped,
+                    int s, int C, int D, int H, int W, void* stream) {
+    if (!fhat || !z || !sigma_m || !g_z || !g_warped || !dims_ok(C, D, H, W) || !broadcast_ok(Cf, C))
+        return fail("irs_lcc_map_bwd: bad arguments");
+    if (!lcc_ok(s, D, H, W)) return fail("irs_lcc_map_bwd: LCC half width must be 1 or 2 and smaller than half the volume");
+    const Vol vol = make_vol(D, H, W);
+    for (int c = 0; c < C; ++c)
+        launch_data_bwd(IRS_DATA_GMM_LCC, fhat + (Cf == 1 ? 0 : (int64_t)c * vol.V), 0, z + (int64_t)c * vol.V,
+                        sigma_m + (int64_t)c * vol.V, nullptr, 0, g_z + (int64_t)c * vol.V, nullptr, c,
+                        g_warped + (int64_t)c * vol.V, nullptr, s, 1, vol, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_reg_energy(const float* v, double* y_out, double* partials, int C, int D, int H, int W, void* stream) {
+    if (!v || !y_out || !partials || !dims_ok(C, D, H, W) || !chain_count_ok(C)) return fail("irs_reg_energy: bad arguments");
+    const Vol vol = make_vol(D, H, W);
+    launch_reg_energy(v, partials, C, vol, (hipStream_t)stream);
+    launch_reduce_partials(partials, energy_blocks(vol), C, y_out, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_gradient_operator(const float* v, float* nabla, int transformation, int C, int D, int H, int W, void* stream) {
+    if (!v || !nabla || !dims_ok(C, D, H, W)) return fail("irs_gradient_operator: bad arguments");
+    launch_gradient_operator(v, nabla, transformation, C, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_log_det_jacobian(const float* transformation, float* log_det, long long* nan_count, int C, int D, int H, int W,
+                         void* stream) {
+    if (!transformation || !nan_count || !dims_ok(C, D, H, W)) return fail("irs_log_det_jacobian: bad arguments");
+    launch_log_det_jacobian(transformation, log_det, nan_count, C, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
+// average surface distance (metric_kernels.hip)
+// ================================================================================================
+constexpr size_t kSurfScratchBudget = (size_t)256 << 20;  // envelope slots of lines longer than kSurfLdsLine
+constexpr int kSurfMaxSlots = 4096;
+
+static size_t surf_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// the per-pair table, the workspace layout and the launch shapes, from the host copy of the boxes
+struct SurfLayout {
+    std::vector<SurfPair> plan;
+    int64_t tasks[3] = {0, 0, 0};
+    int line[3] = {0, 0, 0};
+    int lanes = 1;
+    int slots[3] = {0, 0, 0};
+    size_t plan_off = 0, partials_off = 0, memb_off = 0, ga_off = 0, gb_off = 0, env_off[3] = {0, 0, 0}, bytes = 0;
+};
+
+static int surface_layout(const int32_t* boxes, int P, int D, int H, int W, SurfLayout* out) {
+    if (!boxes || P < 1 || !dims_ok(1, D, H, W)) return fail("irs_surface_distance: bad boxes / dims");
+    SurfLayout& s = *out;
+    s.plan.assign((size_t)P + 1, SurfPair{});
+    const int dims[3] = {D, H, W};
+    int64_t vox = 0;
+    int nx_max = 1;
+    for (int p = 0; p < P; ++p) {
+        const int32_t* b = boxes + 6 * (int64_t)p;
+        SurfPair& q = s.plan[p];
+        q.vox = vox;
+        q.tw = s.tasks[0];
+        q.th = s.tasks[1];
+        q.td = s.tasks[2];
+        if (b[0] > b[3]) continue;  // label in neither map
+        for (int a = 0; a < 3; ++a)
+            if (b[a] < 0 || b[a] > b[3 + a] || b[3 + a] >= dims[a]) return fail("irs_surface_distance: box %d out of the volume", p);
+        q.z0 = b[0], q.y0 = b[1], q.x0 = b[2];
+        q.nz = b[3] - b[0] + 1, q.ny = b[4] - b[1] + 1, q.nx = b[5] - b[2] + 1;
+        const int chunks = (q.nx + kWave - 1) / kWave;
+        vox += (int64_t)q.nz * q.ny * q.nx;
+        s.tasks[0] += (int64_t)q.nz * q.ny;
+        s.tasks[1] += (int64_t)q.nz * chunks;
+        s.tasks[2] += (int64_t)q.ny * chunks;
+        s.line[1] = std::max(s.line[1], q.ny);
+        s.line[2] = std::max(s.line[2], q.nz);
+        nx_max = std::max(nx_max, q.nx);
+    }
+    SurfPair& end = s.plan[P];
+    end.vox = vox;
+    end.tw = s.tasks[0];
+    end.th = s.tasks[1];
+    end.td = s.tasks[2];
+    s.lanes = std::min(nx_max, kWave);  // a lane at or above nx_max never holds an envelope
+    size_t off = surf_align(sizeof(SurfPair) * s.plan.size());
+    s.partials_off = off;
+    off = surf_align(off + sizeof(double) * 4 * (size_t)s.tasks[2]);
+    s.memb_off = off;
+    off = surf_align(off + (size_t)vox);
+    s.ga_off = off;
+    off = surf_align(off + sizeof(float) * (size_t)vox);
+    s.gb_off = off;
+    off = surf_align(off + sizeof(float) * (size_t)vox);
+    for (int pass = 1; pass <= 2; ++pass) {
+        if (s.line[pass] <= kSurfLdsLine || s.tasks[pass] == 0) continue;
+        const size_t slot = sizeof(float) * 3 * (size_t)s.line[pass] * s.lanes;
+        s.slots[pass] = (int)std::max<int64_t>(1, std::min<int64_t>({s.tasks[pass], (int64_t)(kSurfScratchBudget / slot), kSurfMaxSlots}));
+        s.env_off[pass] = off;
+        off = surf_align(off + slot * s.slots[pass]);
+    }
+    s.bytes = off;
+    return 0;
+}
+
+static bool labels_ok(const char* who, const int32_t* labels, int n) {
+    bool ok = labels && n >= 1 && n <= IRS_MAX_LABELS;
+    for (int i = 0; ok && i < n; ++i) ok = labels[i] >= INT16_MIN && labels[i] <= INT16_MAX;
+    return ok || !fail("%s: 1..%d labels in the int16 range", who, IRS_MAX_LABELS);
+}
+
+static SurfLabels surf_labels(const int32_t* labels, int n) {
+    SurfLabels lab = {};
+    memcpy(lab.v, labels, sizeof(int32_t) * n);
+    return lab;
+}
+
+// what irs_label_surface_distance and irs_label_hausdorff_distance ask of their host arrays alike
+static bool surf_arrays_ok(const char* who, const int32_t* labels, int n_labels, const float* spacing) {
+    if (!labels_ok(who, labels, n_labels)) return false;
+    for (int a = 0; a < 3; ++a)
+        if (!positive_finite(spacing[a])) return !fail("%s: spacing must be positive", who);
+    return true;
+}
+
+// the table is small; the copy is waited for so that the host vector may go (its source is pageable memory)
+static int upload_plan(uint8_t* ws, const SurfLayout& s, hipStream_t st) {
+    HIP_TRY(hipMemcpyAsync(ws, s.plan.data(), sizeof(SurfPair) * s.plan.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// the passes' views of a workspace laid out by surface_layout (the table uploaded at its head)
+static SurfPassArgs surf_pass_args(uint8_t* ws, const SurfLayout& s) {
+    SurfPassArgs a = {};
+    a.plan = (const SurfPair*)ws;
+    a.P = (int)s.plan.size() - 1;
+    for (int pass = 0; pass < 3; ++pass) {
+        a.tasks[pass] = s.tasks[pass];
+        a.line[pass] = s.line[pass];
+        a.env_scratch[pass] = s.slots[pass] ? (float*)(ws + s.env_off[pass]) : nullptr;
+        a.env_slots[pass] = s.slots[pass];
+    }
+    a.lanes = s.lanes;
+    a.memb = ws + s.memb_off;
+    a.gA = (float*)(ws + s.ga_off);
+    a.gB = (float*)(ws + s.gb_off);
+    a.partials = (double*)(ws + s.partials_off);
+    return a;
+}
+
+int irs_label_boxes(const int16_t* seg_fixed, int Cf, const int16_t* seg_moving, const int32_t* labels, int n_labels,
+                    int32_t* boxes, int C, int D, int H, int W, void* stream) {
+    if (!seg_fixed || !seg_moving || !boxes || !dims_ok(C, D, H, W) || !chain_count_ok(C) || !broadcast_ok(Cf, C))
+        return fail("irs_label_boxes: bad arguments");
+    if (!labels_ok(__func__, labels, n_labels)) return 1;
+    const Vol vol = make_vol(D, H, W);
+    launch_surface_boxes(seg_fixed, Cf == 1 ? 0 : vol.V, seg_moving, surf_labels(labels, n_labels), n_labels, boxes, C, vol,
+                         (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_surface_distance_workspace(const int32_t* boxes, int n_pairs, int D, int H, int W, size_t* bytes) {
+    if (!bytes) return fail("irs_surface_distance_workspace: null argument");
+    SurfLayout s;
+    if (surface_layout(boxes, n_pairs, D, H, W, &s)) return 1;
+    *bytes = s.bytes;
+    return 0;
+}
+
+int irs_label_surface_distance(const int16_t* seg_fixed, int Cf, const int16_t* seg_moving, const int32_t* labels,
+                               int n_labels, const float* spacing, const int32_t* boxes, void* workspace,
+                               size_t workspace_bytes, long long* counts, double* sums, int C, int D, int H, int W,
+                               void* stream) {
+    if (!seg_fixed || !seg_moving || !spacing || !workspace || !counts || !sums || !dims_ok(C, D, H, W) || !chain_count_ok(C) ||
+        !broadcast_ok(Cf, C))
+        return fail("irs_label_surface_distance: bad arguments");
+    if (!surf_arrays_ok(__func__, labels, n_labels, spacing)) return 1;
+    SurfLayout s;
+    if (surface_layout(boxes, C * n_labels, D, H, W, &s)) return 1;
+    if (!workspace_ok(__func__, workspace_bytes, s.bytes, "irs_surface_distance_workspace")) return 1;
+    const hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = (uint8_t*)workspace;
+    if (upload_plan(ws, s, st)) return 1;
+    const Vol vol = make_vol(D, H, W);
+    launch_surface_distance(seg_fixed, Cf == 1 ? 0 : vol.V, seg_moving, surf_labels(labels, n_labels), n_labels, spacing,
+                            surf_pass_args(ws, s), counts, sums, vol, st);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
+// Hausdorff and percentile surface distances (metric_kernels.hip pass D with KEEP + hausdorff_kernels.hip)
+// ================================================================================================
+constexpr int64_t kHdSliceVoxels = 65536;  // voxels of the largest box per histogram block ...
+constexpr int kHdMaxSlices = 256;          // ... up to this many blocks per (pair, direction)
+
+// the ASD workspace, then the per-task maxima, the histograms and the per-rank state of the selection
+struct HdLayout {
+    SurfLayout s;
+    int slices = 1;
+    size_t maxpart_off = 0, hist_off = 0, hist_bytes = 0, prefix_off = 0, rank_off = 0, bytes = 0;
+};
+
+static int hausdorff_layout(const int32_t* boxes, int P, int Q, int D, int H, int W, HdLayout* out) {
+    if (Q < 0 || Q > IRS_HAUSDORFF_MAX_PERCENTILES)
+        return fail("irs_label_hausdorff_distance: 0..%d percentiles, got %d", IRS_HAUSDORFF_MAX_PERCENTILES, Q);
+    HdLayout& h = *out;
+    if (surface_layout(boxes, P, D, H, W, &h.s)) return 1;
+    int64_t largest = 1;
+    for (int p = 0; p < P; ++p) largest = std::max(largest, h.s.plan[p + 1].vox - h.s.plan[p].vox);
+    h.slices = (int)std::min<int64_t>((largest + kHdSliceVoxels - 1) / kHdSliceVoxels, kHdMaxSlices);
+    size_t off = h.s.bytes;
+    h.maxpart_off = off;
+    off = surf_align(off + sizeof(uint32_t) * 2 * (size_t)h.s.tasks[2]);
+    h.hist_off = off;
+    h.hist_bytes = sizeof(uint32_t) * 256 * 4 * 2 * (size_t)P * Q;
+    off = surf_align(off + h.hist_bytes);
+    h.prefix_off = off;
+    off = surf_align(off + sizeof(uint32_t) * 2 * (size_t)P * Q);
+    h.rank_off = off;
+    off = surf_align(off + sizeof(long long) * 2 * (size_t)P * Q);
+    h.bytes = off;
+    return 0;
+}
+
+int irs_hausdorff_workspace(const int32_t* boxes, int n_pairs, int Q, int D, int H, int W, size_t* bytes) {
+    if (!bytes) return fail("irs_hausdorff_workspace: null argument");
+    HdLayout h;
+    if (hausdorff_layout(boxes, n_pairs, Q, D, H, W, &h)) return 1;
+    *bytes = h.bytes;
+    return 0;
+}
+
+int irs_label_hausdorff_distance(const int16_t* seg_fixed, int Cf, const int16_t* seg_moving, const int32_t* labels,
+                                 int n_labels, const float* spacing, const int32_t* boxes, void* workspace,
+                                 size_t workspace_bytes, const double* percentiles, int Q, long long* counts, double* sums,
+                                 double* hd, double* hd_pct, int C, int D, int H, int W, void* stream) {
+    if (!seg_fixed || !seg_moving || !spacing || !workspace || !counts || !sums || !hd || !dims_ok(C, D, H, W) ||
+        !chain_count_ok(C) || !broadcast_ok(Cf, C))
+        return fail("irs_label_hausdorff_distance: bad arguments");
+    if (!surf_arrays_ok(__func__, labels, n_labels, spacing)) return 1;
+    HdLayout h;
+    if (hausdorff_layout(boxes, C * n_labels, Q, D, H, W, &h)) return 1;
+    if (Q > 0 && (!percentiles || !hd_pct)) return fail("irs_label_hausdorff_distance: %d percentiles need percentiles and hd_pct", Q);
+    for (int r = 0; r < Q; ++r)
+        if (!(percentiles[r] > 0.0) || !(percentiles[r] <= 100.0) || (r > 0 && !(percentiles[r] > percentiles[r - 1])))
+            return fail("irs_label_hausdorff_distance: percentiles must lie in (0, 100] and increase strictly");
+    if (!workspace_ok(__func__, workspace_bytes, h.bytes, "irs_hausdorff_workspace")) return 1;
+    const hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = (uint8_t*)workspace;
+    if (upload_plan(ws, h.s, st)) return 1;
+    if (h.hist_bytes) HIP_TRY(hipMemsetAsync(ws + h.hist_off, 0, h.hist_bytes, st));
+    SurfPassArgs a = surf_pass_args(ws, h.s);
+    a.maxpart = (uint32_t*)(ws + h.maxpart_off);  // pass D keeps the squared distances
+    const Vol vol = make_vol(D, H, W);
+    launch_surface_distance(seg_fixed, Cf == 1 ? 0 : vol.V, seg_moving, surf_labels(labels, n_labels), n_labels, spacing, a, counts,
+                            sums, vol, st);
+    HdArgs g = {};
+    g.plan = a.plan;
+    g.P = a.P;
+    g.Q = Q;
+    g.slices = h.slices;
+    for (int r = 0; r < Q; ++r) g.pct[r] = percentiles[r];
+    g.memb = a.memb;
+    g.gA = a.gA;
+    g.gB = a.gB;
+    g.counts = counts;
+    g.maxpart = a.maxpart;
+    g.hist = (uint32_t*)(ws + h.hist_off);
+    g.prefix = (uint32_t*)(ws + h.prefix_off);
+    g.rank = (long long*)(ws + h.rank_off);
+    g.hd = hd;
+    g.hd_pct = hd_pct;
+    launch_hausdorff_select(g, st);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
+// split-R-hat over chains (diag_kernels.hip)
+// ================================================================================================
+int irs_chain_moments_update(const float* x, int C, int D, int H, int W, int half, int k, float* mean, float* m2, void* stream) {
+    if (!x || !mean || !m2 || !dims_ok(C, D, H, W)) return fail("irs_chain_moments_update: bad arguments");
+    if (half != 0 && half != 1) return fail("irs_chain_moments_update: half must be 0 or 1, got %d", half);
+    if (k < 1) return fail("irs_chain_moments_update: k must be >= 1, got %d", k);
+    const int64_t n = (int64_t)C * 3 * D * H * W;
+    launch_chain_moments(x, mean + half * n, m2 + half * n, n, k, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_split_rhat_workspace(int C, int D, int H, int W, size_t* bytes) {
+    if (!bytes || !dims_ok(C, D, H, W)) return fail("irs_split_rhat_workspace: bad arguments");
+    *bytes = sizeof(double) * 5 * (size_t)split_rhat_blocks((int64_t)D * H * W);
+    return 0;
+}
+
+int irs_split_rhat(const float* mean, const float* m2, int C, int n, const uint8_t* mask, float thr0, float thr1, float* rhat,
+                   double* summary, void* ws, size_t ws_bytes, int D, int H, int W, void* stream) {
+    if (!mean || !m2 || !rhat || !summary || !ws || !dims_ok(C, D, H, W)) return fail("irs_split_rhat: bad arguments");
+    if (n < 2) return fail("irs_split_rhat: n = %d samples per half chain, at least 2 needed", n);
+    const int64_t V = (int64_t)D * H * W;
+    const size_t need = sizeof(double) * 5 * (size_t)split_rhat_blocks(V);
+    if (!workspace_ok(__func__, ws_bytes, need, "irs_split_rhat_workspace")) return 1;
+    launch_split_rhat(mean, m2, C, n, mask, thr0, thr1, rhat, summary, (double*)ws, V, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
+// split ESS and MCSE over chains (diag_kernels.hip)
+// ================================================================================================
+int irs_chain_variogram_update(const float* x, int C, int D, int H, int W, int k, int L, float* ring, float* vsum, void* stream) {
+    if (!x || !ring || !vsum || !dims_ok(C, D, H, W)) return fail("irs_chain_variogram_update: bad arguments");
+    if (C > IRS_MAX_CHAINS) return fail("irs_chain_variogram_update: %d chains, at most %d", C, IRS_MAX_CHAINS);
+    if (k < 1) return fail("irs_chain_variogram_update: k must be >= 1, got %d", k);
+    if (L < 1) return fail("irs_chain_variogram_update: L must be >= 1, got %d", L);
+    launch_chain_variogram(x, ring, vsum, C, (int64_t)3 * D * H * W, L, k, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_split_ess_workspace(int C, int D, int H, int W, size_t* bytes) {
+    if (!bytes || !dims_ok(C, D, H, W)) return fail("irs_split_ess_workspace: bad arguments");
+    *bytes = sizeof(double) * 5 * (size_t)split_rhat_blocks((int64_t)D * H * W);
+    return 0;
+}
+
+int irs_split_ess(const float* mean, const float* m2, const float* vsum, int C, int n, int L, const uint8_t* mask, float threshold,
+                  float* ess, float* mcse, double* summary, void* ws, size_t ws_bytes, int D, int H, int W, void* stream) {
+    if (!mean || !m2 || !vsum || !ess || !mcse || !summary || !ws || !dims_ok(C, D, H, W))
+        return fail("irs_split_ess: bad arguments");
+    if (L < 1) return fail("irs_split_ess: L must be >= 1, got %d", L);
+    if (n - 1 < 3)
+        return fail("irs_split_ess: n = %d samples per half chain, at least 4 needed (the truncation rule reads lags 1 to 3)", n);
+    const int64_t V = (int64_t)D * H * W;
+    const size_t need = sizeof(double) * 5 * (size_t)split_rhat_blocks(V);
+    if (!workspace_ok(__func__, ws_bytes, need, "irs_split_ess_workspace")) return 1;
+    launch_split_ess(mean, m2, vsum, C, n, L, mask, threshold, ess, mcse, summary, (double*)ws, V, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
+// posterior label maps (label_kernels.hip)
+// ================================================================================================
+
+// the volume of a label-posterior call: dims of at least 1 (a record may be one row of voxels), < 2^30 voxels
+static bool label_dims_ok(int D, int H, int W) { return D >= 1 && H >= 1 && W >= 1 && (int64_t)D * H * W < ((int64_t)1 << 30); }
+
+// 1 .. IRS_MAX_LABELS distinct labels in the int16 range
+static bool distinct_labels_ok(const char* who, const int32_t* labels, int K) {
+    if (!labels_ok(who, labels, K)) return false;
+    for (int i = 0; i < K; ++i)
+        for (int j = 0; j < i; ++j)
+            if (labels[i] == labels[j]) return !fail("%s: label %d appears twice", who, labels[i]);
+    return true;
+}
+
+static size_t label_update_ws(int C, int K, int64_t V) { return sizeof(int32_t) * (size_t)C * K * label_update_partials_blocks(V); }
+
+static size_t label_finalize_ws(int K, int64_t V) {
+    return (sizeof(long long) * (size_t)K * (6 + 3 * IRS_LABEL_BINS) + 4 * sizeof(double)) * label_finalize_blocks(V);
+}
+
+int irs_label_posterior_workspace(int C, int K, int D, int H, int W, size_t* bytes) {
+    if (!bytes || !chain_count_ok(C) || K < 1 || K > IRS_MAX_LABELS || !label_dims_ok(D, H, W))
+        return fail("irs_label_posterior_workspace: bad arguments");
+    const int64_t V = (int64_t)D * H * W;
+    *bytes = std::max(label_update_ws(C, K, V), label_finalize_ws(K, V));
+    return 0;
+}
+
+int irs_label_posterior_update(const int16_t* seg, int C, int D, int H, int W, const int32_t* labels, int K, int32_t* counts,
+                               double* volume, int records_before, void* ws, size_t ws_bytes, void* stream) {
+    if (!seg || !counts || !volume || !ws || !label_dims_ok(D, H, W)) return fail("irs_label_posterior_update: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!records_ok(__func__, records_before, C, INT32_MAX, "overflow the int32 record count")) return 1;
+    if (!distinct_labels_ok(__func__, labels, K)) return 1;
+    const int64_t V = (int64_t)D * H * W;
+    const size_t need = label_update_ws(C, K, V);
+    if (!workspace_ok(__func__, ws_bytes, need, "irs_label_posterior_workspace")) return 1;
+    launch_label_update(seg, C, V, surf_labels(labels, K), K, counts, volume, records_before, (int32_t*)ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_label_posterior_finalize(const int32_t* counts, int K, int D, int H, int W, int n, const int32_t* labels,
+                                 const int16_t* seg_fixed, const uint8_t* mask, float* entropy, int16_t* map_label,
+                                 long long* summary, double* mask_summary, void* ws, size_t ws_bytes, void* stream) {
+    if (!counts || !seg_fixed || !entropy || !map_label || !summary || !mask_summary || !ws || !label_dims_ok(D, H, W))
+        return fail("irs_label_posterior_finalize: bad arguments");
+    if (n < 1) return fail("irs_label_posterior_finalize: n = %d records, at least 1 needed", n);
+    if (!distinct_labels_ok(__func__, labels, K)) return 1;
+    const int64_t V = (int64_t)D * H * W;
+    const size_t need = label_finalize_ws(K, V);
+    if (!workspace_ok(__func__, ws_bytes, need, "irs_label_posterior_workspace")) return 1;
+    const int blocks = label_finalize_blocks(V);
+    long long* partials = (long long*)ws;
+    double* dpartials = (double*)(partials + (size_t)K * (6 + 3 * IRS_LABEL_BINS) * blocks);
+    launch_label_finalize(counts, K, V, n, surf_labels(labels, K), seg_fixed, mask, entropy, map_label, summary, mask_summary, partials,
+                          dpartials, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
+// Jacobian posterior maps (jacobian_kernels.hip)
+// ================================================================================================
+int irs_jacobian_posterior_update(const float* transformation, int C, int D, int H, int W, int32_t* folds, float* mean, float* m2,
+                                  int records_before, void* stream) {
+    if (!transformation || !folds || !mean || !m2 || !dims_ok(C, D, H, W)) return fail("irs_jacobian_posterior_update: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!records_ok(__func__, records_before, C, INT32_MAX, "overflow the int32 fold count")) return 1;
+    launch_jacobian_update(transformation, C, folds, mean, m2, records_before, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_jacobian_posterior_finalize(const int32_t* folds, const float* mean, const float* m2, int D, int H, int W, int n,
+                                    const uint8_t* mask, float* fold_prob, float* logJ_mean, float* logJ_std, long long* isummary,
+                                    double* fsummary, void* ws, size_t ws_bytes, void* stream) {
+    if (!folds || !mean || !m2 || !fold_prob || !logJ_mean || !logJ_std || !isummary || !fsummary || !ws || !dims_ok(1, D, H, W))
+        return fail("irs_jacobian_posterior_finalize: bad arguments");
+    if (n < 1) return fail("irs_jacobian_posterior_finalize: n = %d records, at least 1 needed", n);
+    if (!workspace_ok(__func__, ws_bytes, (size_t)IRS_JACOBIAN_WS_BYTES, "IRS_JACOBIAN_WS_BYTES")) return 1;
+    launch_jacobian_finalize(folds, mean, m2, (int64_t)D * H * W, n, mask, fold_prob, logJ_mean, logJ_std, isummary, fsummary, ws,
+                             (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
+// displacement covariance posterior (covariance_kernels.hip)
+// ================================================================================================
+int irs_displacement_covariance_update(const float* displacement, int C, int D, int H, int W, float* mean, float* comoment,
+                                       int records_before, void* stream) {
+    if (!displacement || !mean || !comoment || !dims_ok(C, D, H, W)) return fail("irs_displacement_covariance_update: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!records_ok(__func__, records_before, C, INT32_MAX, "overflow the int32 record count")) return 1;
+    launch_covariance_update(displacement, C, mean, comoment, records_before, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_displacement_covariance_finalize(const float* mean, const float* comoment, int D, int H, int W, int n, const float* scale,
+                                         const uint8_t* mask, float* stdev, float* direction, float* anisotropy, long long* isummary,
+                                         double* fsummary, void* ws, size_t ws_bytes, void* stream) {
+    if (!mean || !comoment || !scale || !stdev || !direction || !anisotropy || !isummary || !fsummary || !ws || !dims_ok(1, D, H, W))
+        return fail("irs_displacement_covariance_finalize: bad arguments");
+    if (n < 1) return fail("irs_displacement_covariance_finalize: n = %d records, at least 1 needed", n);
+    if (!positive3(__func__, "scale", scale)) return 1;
+    if (!workspace_ok(__func__, ws_bytes, (size_t)IRS_COVARIANCE_WS_BYTES, "IRS_COVARIANCE_WS_BYTES")) return 1;
+    launch_covariance_finalize(mean, comoment, (int64_t)D * H * W, n, scale, mask, stdev, direction, anisotropy, isummary, fsummary, ws,
+                               (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
+// displacement credible intervals (quantile_kernels.hip)
+// ================================================================================================
+static bool quantile_bins_ok(int bins) { return bins >= IRS_QUANTILE_MIN_BINS && bins <= IRS_QUANTILE_MAX_BINS && bins % 2 == 0; }
+#define IRS_STR_(x) #x
+#define IRS_STR(x) IRS_STR_(x)
+
+int irs_displacement_quantiles_update(const float* displacement, int C, int D, int H, int W, float* centre, uint16_t* hist,
+                                      int bins, const float* inv_width, int records_before, void* stream) {
+    if (!displacement || !centre || !hist || !inv_width || !dims_ok(C, D, H, W))
+        return fail("irs_displacement_quantiles_update: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!quantile_bins_ok(bins))
+        return fail("irs_displacement_quantiles_update: bins = %d, an even number in %d..%d needed", bins, IRS_QUANTILE_MIN_BINS,
+                    IRS_QUANTILE_MAX_BINS);
+    if (!positive3(__func__, "inv_width", inv_width)) return 1;
+    if (!records_ok(__func__, records_before, C, IRS_QUANTILE_MAX_RECORDS,
+                    "exceed the " IRS_STR(IRS_QUANTILE_MAX_RECORDS) " a uint16 count holds"))
+        return 1;
+    launch_quantile_update(displacement, C, centre, hist, bins, inv_width, records_before, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_displacement_quantiles_finalize(const float* centre, const uint16_t* hist, int bins, int D, int H, int W, int n,
+                                        const float* width, const float* scale, const double* probs, int P, const uint8_t* mask,
+                                        float* quantiles, float* ci_width, long long* isummary, double* fsummary, void* ws,
+                                        size_t ws_bytes, void* stream) {
+    if (!centre || !hist || !width || !scale || !probs || !quantiles || !ci_width || !isummary || !fsummary || !ws ||
+        !dims_ok(1, D, H, W))
+        return fail("irs_displacement_quantiles_finalize: bad arguments");
+    if (!quantile_bins_ok(bins))
+        return fail("irs_displacement_quantiles_finalize: bins = %d, an even number in %d..%d needed", bins, IRS_QUANTILE_MIN_BINS,
+                    IRS_QUANTILE_MAX_BINS);
+    if (n < 1 || n > IRS_QUANTILE_MAX_RECORDS)
+        return fail("irs_displacement_quantiles_finalize: n = %d records, 1..%d needed", n, IRS_QUANTILE_MAX_RECORDS);
+    if (P < 2 || P > IRS_QUANTILE_MAX_PROBS)
+        return fail("irs_displacement_quantiles_finalize: P = %d probabilities, 2..%d needed", P, IRS_QUANTILE_MAX_PROBS);
+    for (int j = 0; j < P; ++j)
+        if (!(probs[j] > 0.0 && probs[j] < 1.0) || (j > 0 && !(probs[j] > probs[j - 1])))
+            return fail("irs_displacement_quantiles_finalize: probs[%d] = %g, strictly increasing values in (0,1) needed", j, probs[j]);
+    for (int a = 0; a < 3; ++a) {
+        if (!positive_finite(width[a]))
+            return fail("irs_displacement_quantiles_finalize: width[%d] = %g, a finite value > 0 needed", a, (double)width[a]);
+        if (!positive_finite(scale[a]))
+            return fail("irs_displacement_quantiles_finalize: scale[%d] = %g, a finite value > 0 needed", a, (double)scale[a]);
+    }
+    if (!workspace_ok(__func__, ws_bytes, (size_t)IRS_QUANTILE_WS_BYTES, "IRS_QUANTILE_WS_BYTES")) return 1;
+    launch_quantile_finalize(centre, hist, bins, (int64_t)D * H * W, n, width, scale, probs, P, mask, quantiles, ci_width, isummary,
+                             fsummary, ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
+// inverse transformation and inverse-consistency error (inverse_kernels.hip)
+// ================================================================================================
+int irs_svf_exp_inverse(const float* v, float* scratch, float* transformation, float* displacement, int no_steps, int C, int D,
+                        int H, int W, void* stream) {
+    if (!v || !scratch || !dims_ok(C, D, H, W) || no_steps < 1 || no_steps > 30) return fail("irs_svf_exp_inverse: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const Vol vol = make_vol(D, H, W);
+    Lin lin;
+    if (cached_lin(D, H, W, st, &lin)) return fail("irs_svf_exp_inverse: identity grid allocation failed");
+    const int64_t field = (int64_t)C * 3 * vol.V;
+    float* buf[2] = {scratch, scratch + field};
+    launch_negate(v, buf[1], field, st);
+    for (int k = 0; k < no_steps; ++k)  // step 0: buf[1] -> buf[0]; then ping-pong
+        launch_exp_step_fwd_march(buf[(k + 1) & 1], buf[k & 1], k == 0, no_steps, C, vol, lin, nullptr, nullptr, false, 0, st);
+    if (transformation || displacement) launch_svf_outputs(buf[(no_steps - 1) & 1], transformation, displacement, C, vol, lin, st);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_inverse_consistency(const float* t_a, const float* d_a, const float* d_b, const float* scale, const uint8_t* mask,
+                            int mask_chains, float* residual, float* norm, long long* isummary, double* fsummary, void* ws,
+                            size_t ws_bytes, int C, int D, int H, int W, void* stream) {
+    if (!t_a || !d_a || !d_b || !scale || !isummary || !fsummary || !ws || !dims_ok(C, D, H, W))
+        return fail("irs_inverse_consistency: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (mask && !broadcast_ok(mask_chains, C))
+        return fail("irs_inverse_consistency: mask of %d chains, 1 or %d needed", mask_chains, C);
+    if (!positive3(__func__, "scale", scale)) return 1;
+    if (!workspace_ok(__func__, ws_bytes, (size_t)IRS_ICE_WS_BYTES, "IRS_ICE_WS_BYTES")) return 1;
+    launch_inverse_consistency(t_a, d_a, d_b, scale, mask, mask_chains, residual, norm, isummary, fsummary, ws, C, make_vol(D, H, W),
+                               (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_inverse_consistency_update(const float* norm, int C, int D, int H, int W, float* mean, float* peak, int records_before,
+                                   void* stream) {
+    if (!norm || !mean || !peak || !dims_ok(C, D, H, W)) return fail("irs_inverse_consistency_update: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!records_ok(__func__, records_before, C, INT32_MAX, "overflow the int32 record count")) return 1;
+    launch_inverse_consistency_update(norm, C, (int64_t)D * H * W, mean, peak, records_before, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_inverse_consistency_finalize(const float* mean, const float* peak, int D, int H, int W, const uint8_t* mask,
+                                     float threshold, long long* isummary, double* fsummary, void* ws, size_t ws_bytes,
+                                     void* stream) {
+    if (!mean || !peak || !isummary || !fsummary || !ws || !dims_ok(1, D, H, W))
+        return fail("irs_inverse_consistency_finalize: bad arguments");
+    if (!positive_finite(threshold))
+        return fail("irs_inverse_consistency_finalize: threshold = %g, a finite value > 0 needed", (double)threshold);
+    if (!workspace_ok(__func__, ws_bytes, (size_t)IRS_ICE_MAP_WS_BYTES, "IRS_ICE_MAP_WS_BYTES")) return 1;
+    launch_inverse_consistency_finalize(mean, peak, (int64_t)D * H * W, mask, threshold, isummary, fsummary, ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
+// native-resolution outputs (native_kernels.hip)
+// ================================================================================================
+int irs_native_warp(const float* displacement, int C, const int32_t* dims, const int32_t* native, const int32_t* padding,
+                    const float* im, const int16_t* seg, const uint8_t* mask, int Cim, float fill, const float* scale,
+                    float* im_out, int16_t* seg_out, uint8_t* mask_out, float* displacement_out, void* stream) {
+    if (!displacement || !dims || !native || !padding) return fail("irs_native_warp: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!broadcast_ok(Cim, C)) return fail("irs_native_warp: moving volumes of %d chains, 1 or %d needed", Cim, C);
+    if (!im_out && !seg_out && !mask_out && !displacement_out) return fail("irs_native_warp: no output requested");
+    if ((im_out && !im) || (seg_out && !seg) || (mask_out && !mask))
+        return fail("irs_native_warp: an output is requested of a moving volume that is NULL");
+    if (displacement_out && !scale) return fail("irs_native_warp: displacement_out needs scale");
+    NativeGeom gm;
+    int64_t voxels = 1;
+    for (int a = 0; a < 3; ++a) {
+        const int64_t P = (int64_t)native[a] + 2 * (int64_t)padding[a];
+        if (native[a] < 1) return fail("irs_native_warp: native[%d] = %d < 1", a, native[a]);
+        if (padding[a] < 0) return fail("irs_native_warp: padding[%d] = %d < 0", a, padding[a]);
+        if (P < 2) return fail("irs_native_warp: padded extent %lld of axis %d, >= 2 needed", (long long)P, a);
+        if (dims[a] < 2) return fail("irs_native_warp: dims[%d] = %d < 2", a, dims[a]);
+        if (P >= ((int64_t)1 << 24)) return fail("irs_native_warp: padded extent %lld of axis %d is not exact in float32", (long long)P, a);
+        voxels *= native[a];
+        gm.n[a] = native[a];
+        gm.p[a] = padding[a];
+        gm.P[a] = (int)P;
+        gm.m[a] = dims[a];
+        gm.grid_step[a] = (float)((double)(dims[a] - 1) / (double)(P - 1));
+        gm.half_extent[a] = 0.5f * (float)(P - 1);
+        gm.out_scale[a] = 0.0f;
+        if (voxels >= ((int64_t)1 << 30)) return fail("irs_native_warp: the native volume must have fewer than 2^30 voxels");
+    }
+    if (!dims_ok(C, dims[0], dims[1], dims[2])) return fail("irs_native_warp: bad dims");
+    // the launch is one block row per (chain, plane) and per four rows of a plane
+    if ((int64_t)native[0] * C > 65535 || (native[1] + 3) / 4 > 65535)
+        return fail("irs_native_warp: native shape (%d, %d, %d) x %d chains exceeds the launch grid", native[0], native[1], native[2], C);
+    if (displacement_out)
+        for (int c = 0; c < 3; ++c) {
+            if (!isfinite(scale[c])) return fail("irs_native_warp: scale[%d] = %g, a finite value needed", c, (double)scale[c]);
+            gm.out_scale[c] = scale[c];
+        }
+    if (!isfinite(fill)) return fail("irs_native_warp: fill = %g, a finite value needed", (double)fill);
+    gm.fill = fill;
+    launch_native_warp(displacement, im_out ? im : nullptr, seg_out ? seg : nullptr, mask_out ? mask : nullptr,
+                       Cim == 1 ? 0 : voxels, im_out, seg_out, mask_out, displacement_out, gm, C, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
+// landmark propagation (landmark_kernels.hip)
+// ================================================================================================
+static bool landmark_count_ok(int K) { return K >= 1 && K <= IRS_LANDMARK_MAX_POINTS; }
+
+int irs_transform_points(const float* points, int K, const float* displacement, int C, int D, int H, int W, const float* scale,
+                         const float* offset, float* sampled, float* mapped, void* stream) {
+    if (!points || !displacement || !scale) return fail("irs_transform_points: bad arguments");
+    if (!sampled && !mapped) return fail("irs_transform_points: no output requested");
+    if (!landmark_count_ok(K)) return fail("irs_transform_points: K = %d points, 1..%d", K, IRS_LANDMARK_MAX_POINTS);
+    if (!chains_ok(__func__, C)) return 1;
+    if (!dims_ok(C, D, H, W)) return fail("irs_transform_points: bad dims (%d, %d, %d)", D, H, W);
+    if (!positive3(__func__, "scale", scale)) return 1;
+    launch_transform_points(points, K, displacement, scale, offset, sampled, mapped, C, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_landmark_update(const float* mapped, const float* target, int C, int K, double* mean, double* comoment, double* tre_mean,
+                        double* tre_m2, double* tre_max, int32_t* count, int records_before, void* stream) {
+    if (!mapped || !target || !mean || !comoment || !tre_mean || !tre_m2 || !tre_max || !count)
+        return fail("irs_landmark_update: bad arguments");
+    if (!landmark_count_ok(K)) return fail("irs_landmark_update: K = %d landmarks, 1..%d", K, IRS_LANDMARK_MAX_POINTS);
+    if (!chains_ok(__func__, C)) return 1;
+    if (!records_ok(__func__, records_before, C, INT32_MAX, "overflow the int32 record count")) return 1;
+    launch_landmark_update(mapped, target, C, K, mean, comoment, tre_mean, tre_m2, tre_max, count, records_before, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_landmark_finalize(const double* mean, const double* comoment, const double* tre_mean, const double* tre_m2,
+                          const double* tre_max, const int32_t* count, const float* target, int K, double* out, long long* isummary,
+                          double* fsummary, void* ws, size_t ws_bytes, void* stream) {
+    if (!mean || !comoment || !tre_mean || !tre_m2 || !tre_max || !count || !target || !out || !isummary || !fsummary || !ws)
+        return fail("irs_landmark_finalize: bad arguments");
+    if (!landmark_count_ok(K)) return fail("irs_landmark_finalize: K = %d landmarks, 1..%d", K, IRS_LANDMARK_MAX_POINTS);
+    if (!workspace_ok(__func__, ws_bytes, (size_t)IRS_LANDMARK_WS_BYTES, "IRS_LANDMARK_WS_BYTES")) return 1;
+    launch_landmark_finalize(mean, comoment, tre_mean, tre_m2, tre_max, count, target, K, out, isummary, fsummary, ws,
+                             (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
+// intensity similarity (similarity_kernels.hip)
+// ================================================================================================
+static size_t similarity_hist_bytes(int C, int bins) { return ((size_t)C * bins * bins * sizeof(int32_t) + 15) & ~(size_t)15; }
+static size_t similarity_partials_bytes() { return (size_t)IRS_SIMILARITY_MAX_BLOCKS * (3 + 6) * 8; }
+
+int irs_image_similarity_workspace(int C, int bins, size_t* bytes) {
+    if (!bytes) return fail("irs_image_similarity_workspace: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (bins < IRS_SIMILARITY_MIN_BINS || bins > IRS_SIMILARITY_MAX_BINS)
+        return fail("irs_image_similarity_workspace: bins = %d, %d..%d", bins, IRS_SIMILARITY_MIN_BINS, IRS_SIMILARITY_MAX_BINS);
+    *bytes = similarity_hist_bytes(C, bins) + similarity_partials_bytes();
+    return 0;
+}
+
+int irs_image_similarity(const float* fixed, int Cf, const float* moving, int C, const uint8_t* mask, int D, int H, int W,
+                         float f_lo, float f_hi, float m_lo, float m_hi, int bins, int32_t* hist, double* stats, void* ws,
+                         size_t ws_bytes, void* stream) {
+    if (!fixed || !moving || !stats || !ws) return fail("irs_image_similarity: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!broadcast_ok(Cf, C)) return fail("irs_image_similarity: fixed image of %d chains, 1 or %d needed", Cf, C);
+    if (bins < IRS_SIMILARITY_MIN_BINS || bins > IRS_SIMILARITY_MAX_BINS)
+        return fail("irs_image_similarity: bins = %d, %d..%d", bins, IRS_SIMILARITY_MIN_BINS, IRS_SIMILARITY_MAX_BINS);
+    if (D < 1 || H < 1 || W < 1) return fail("irs_image_similarity: dims (%d, %d, %d), every one >= 1 needed", D, H, W);
+    const int64_t V = (int64_t)D * H * W;
+    if (V >= ((int64_t)1 << 30)) return fail("irs_image_similarity: the volume must have fewer than 2^30 voxels");
+    SimBins bn;
+    bn.bins = bins;
+    const float lo[2] = {f_lo, m_lo}, hi[2] = {f_hi, m_hi};
+    float inv[2];
+    for (int k = 0; k < 2; ++k) {
+        const char* who = k == 0 ? "fixed" : "moving";
+        if (!isfinite(lo[k]) || !isfinite(hi[k]) || !(hi[k] > lo[k]))
+            return fail("irs_image_similarity: %s range [%g, %g], finite bounds with hi > lo needed", who, (double)lo[k], (double)hi[k]);
+        const float width = hi[k] - lo[k];  // fp32, as the definition states it
+        inv[k] = (float)bins / width;
+        if (!isfinite(inv[k]) || !(inv[k] > 0.0f))
+            return fail("irs_image_similarity: %s range [%g, %g] is too wide or too narrow for float32 bins", who, (double)lo[k], (double)hi[k]);
+    }
+    bn.f_lo = f_lo, bn.f_hi = f_hi, bn.f_inv = inv[0];
+    bn.m_lo = m_lo, bn.m_hi = m_hi, bn.m_inv = inv[1];
+    const size_t hist_bytes = similarity_hist_bytes(C, bins), need = hist_bytes + similarity_partials_bytes();
+    if (!workspace_ok(__func__, ws_bytes, need, "irs_image_similarity_workspace")) return 1;
+    if ((uintptr_t)ws & 15) return fail("irs_image_similarity: the workspace must be 16-byte aligned");
+    long long* ipart = (long long*)((char*)ws + hist_bytes);
+    double* fpart = (double*)(ipart + (size_t)IRS_SIMILARITY_MAX_BLOCKS * 3);
+    launch_image_similarity(fixed, Cf == 1 ? 0 : V, moving, mask, V, C, bn, hist ? hist : (int32_t*)ws, stats, ipart, fpart,
+                            (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"

@@ -109,8 +109,8 @@ struct Knobs {
     int similarity_aggregate = 1;  // IRS_SIMILARITY_AGGREGATE  joint histogram: a wavefront whose voxels all fall into one joint bin adds their number with one LDS add (0: plain LDS atomics always)
     int launch_log = 0;        // IRS_LAUNCH_LOG        print the shape of every distinct marching launch once (stderr; tools/launch_shapes.py)
 };
-Knobs& global_knobs();                                   // api.hip; initialised from the environment on first use
-int knob_set(Knobs& k, const char* name, int value, bool on_context);  // 0 on success (api.hip: scopes)
+Knobs& global_knobs();                                   // knobs.hip; initialised from the environment on first use
+int knob_set(Knobs& k, const char* name, int value, bool on_context);  // 0 on success (knobs.hip: scopes)
 
 // Segment length of the z-marching kernels.  32 planes amortise the run-in of a segment (2R .. 4S extra planes) when the
 // launch still has enough workgroups to fill 256 CUs; smaller volumes trade run-in overhead for parallelism, down to
@@ -167,7 +167,7 @@ inline int64_t resident_blocks(const void* kernel, int block, int* cache) {
 
 // IRS_LAUNCH_LOG=1: one stderr line per distinct (kernel, shape) -- workgroups, threads, segment length, run-in planes, plane steps a
 // workgroup marches, workgroups the chip holds at once -> rounds.  What a launch on a small volume or a thin slab looks like
-// ("where a small launch loses"); api.hip.
+// ("where a small launch loses"); knobs.hip.
 void log_launch(const char* kernel, int tile_x, int tile_y, int64_t blocks, int threads, int seg_len, int run_in, int planes_out,
                 int chains, int64_t resident);
 

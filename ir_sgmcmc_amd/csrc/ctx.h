@@ -1,4 +1,4 @@
-// The context behind include/irsgmcmc.h (shared by api.hip and slab.hip): workspace views, variant prediction, error plumbing.
+// The context behind include/irsgmcmc.h (shared by api_ops.hip, api_ctx.hip, knobs.hip and slab.hip): workspace views, variant prediction, error plumbing.
 #pragma once
 #include <stdlib.h>
 #include <string.h>
@@ -10,7 +10,7 @@ struct irs_comm;
 
 namespace irs {
 
-int fail(const char* fmt, ...);  // formats irs_last_error(), returns 1 (api.hip)
+int fail(const char* fmt, ...);  // formats irs_last_error(), returns 1 (api_ops.hip)
 
 #define HIP_TRY(expr)                                                                               \
     do {                                                                                            \
@@ -68,7 +68,7 @@ struct irs_ctx {
     hipEvent_t ev_bwd[64];
     hipEvent_t ra_ev[4];     // end of the last transitions: bounds how far the host may run ahead of the device
     // several chains: the data term of chain c runs on a side stream while the statistics of chain c + 1 run on the caller's
-    // (api.hip: the per-chain stage); created with the context when C > 1
+    // (api_ctx.hip: the per-chain stage); created with the context when C > 1
     hipStream_t side = nullptr;
     hipEvent_t ev_side[2 * IRS_MAX_CHAINS] = {};
     uint64_t n_enqueued = 0;
@@ -119,6 +119,23 @@ namespace irs {
 
 constexpr int kHintWords = 4 * IRS_MAX_CHAINS * 32 + 8;  // dmax scratch + [flags] (slab.hip: misprediction flag)
 
+// Largest of the n bounds (float bits) in a row of published hints -- pinned memory the device writes, read without
+// synchronisation.  *valid: every word is a float >= 0, +inf (nothing published yet) included, not NaN / garbage; what an invalid
+// row or an infinite maximum means is the caller's rule.
+inline float hint_row_max(const unsigned* row, int n, bool* valid) {
+    const volatile unsigned* h = row;
+    float m = 0.0f;
+    *valid = true;
+    for (int i = 0; i < n; ++i) {
+        const unsigned bits = h[i];
+        float f;
+        memcpy(&f, &bits, sizeof(f));
+        if (!(f >= 0.0f)) *valid = false;
+        m = f > m ? f : m;
+    }
+    return m;
+}
+
 // Host-side guess of "max |d_k| stays well below `bound`" from the bounds of the last transition the host has seen
 // finish (never waited for: stale by a transition or two, and displacements move by O(lr) per transition).  Only a launch
 // decision: the kernels that remain are correct for any displacement, so a wrong guess costs time, not parity.
@@ -126,16 +143,9 @@ inline bool predicted_below(const irs_ctx* c, int k, float bound) {
     const int mode = c->kn.predict_variants;
     if (mode == 2 || mode == 3) return true;
     if (!mode || !c->hint) return false;
-    const volatile unsigned* h = c->hint + (size_t)k * c->C * 4;
-    float m = 0.0f;
-    for (int i = 0; i < c->C * 4; ++i) {
-        const unsigned bits = h[i];
-        float f;
-        memcpy(&f, &bits, sizeof(f));
-        if (!(f >= 0.0f)) return false;  // NaN / garbage
-        m = f > m ? f : m;
-    }
-    return m < bound;
+    bool valid;
+    const float m = hint_row_max(c->hint + (size_t)k * c->C * 4, c->C * 4, &valid);
+    return valid && m < bound;
 }
 // (0.9: the radius-2 FORWARD variant only has work at max|d_k| >= 1, and the radius-1 kernel that remains reads a tap that leaves its
 // ring from global memory -- a bound that crosses 1 between this guess and the launch costs that one step some speed, nothing else.
@@ -149,9 +159,6 @@ inline bool bound_is_steady(const irs_ctx* c, int k) {
 }
 inline bool predicted_small(const irs_ctx* c, int k) {
     if (predicted_below(c, k, 0.9f)) return true;
-#ifdef IRS_NO_TREND
-    return false;
-#endif
     return c->kn.predict_variants == 1 && bound_is_steady(c, k) && predicted_below(c, k, 0.97f);
 }
 // "max |d_k| is nowhere near one voxel": the radius-2 ADJOINT variant is not even launched.  Unlike the guesses above this one
@@ -167,26 +174,15 @@ inline bool predicted_tiny(const irs_ctx* c, int k) {
     if (c->kn.predict_variants == 3) return true;  // test hook, always
     if (c->kn.predict_variants != 1) return false;
     if (predicted_below(c, k, 0.4f)) return true;
-#ifdef IRS_NO_TREND  // (A/B builds: the fixed rule alone)
-    return false;
-#endif
     return bound_is_steady(c, k) && predicted_below(c, k, 0.66f);
 }
 // refresh the observed trend of the published bounds (host side, unsynchronised reads of the pinned hint -- a hint, like the rest)
 inline void note_hint_trend(irs_ctx* c) {
     if (!c->hint) return;
     for (int k = 0; k < c->cfg.no_steps && k < 32; ++k) {
-        const volatile unsigned* h = c->hint + (size_t)k * c->C * 4;
-        float m = 0.0f;
-        bool ok = true;
-        for (int i = 0; i < c->C * 4; ++i) {
-            const unsigned bits = h[i];
-            float f;
-            memcpy(&f, &bits, sizeof(f));
-            if (!(f >= 0.0f) || f > 1.0e6f) ok = false;  // NaN / +inf (nothing published yet) / garbage
-            m = f > m ? f : m;
-        }
-        if (!ok) {
+        bool valid;
+        const float m = hint_row_max(c->hint + (size_t)k * c->C * 4, c->C * 4, &valid);
+        if (!valid || m > 1.0e6f) {  // NaN / +inf (nothing published yet) / garbage
             c->hint_trend[k] = false;
             c->hint_seen[k] = 0.0f;
             continue;
@@ -215,13 +211,15 @@ inline void prescale_factors(Vol vol, int no_steps, float s[3]) {
     s[2] = (float)(2.0 / (double)(vol.D - 1) * p);
 }
 
-// shared by irs_create and irs_slab_create (api.hip)
+// shared by irs_create and irs_slab_create (api_ctx.hip); a creation that fails half-way is torn down by irs_destroy
 int create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out);
 int check_io(const irs_ctx* c, const irs_io* io, const char* who);
+void context_born();  // knobs.hip: the count of live contexts that irs_option_set checks the layout switches against
+void context_gone();
 void slab_release(irs_ctx* c);  // slab.hip
 int slab_flush(irs_ctx* c, hipStream_t st);  // slab.hip
 void slab_drop_pending(irs_ctx* c);          // slab.hip
-// cubic B-spline FFD up-sampling / adjoint over the three axes (api.hip); the window arguments are for slab-local dense arrays
+// cubic B-spline FFD up-sampling / adjoint over the three axes (api_ops.hip); the window arguments are for slab-local dense arrays
 int ffd_up(const float* v_cp, float* dense, float* tmp, int C, Vol vol, const int G[3], const SplineTaps spl[3], hipStream_t st,
            int w_lo = 0, int w_n = -1, int store_lo = 0, int store_n = -1);
 int ffd_adjoint(const float* g_dense, float* g_cp, float* tmp, int C, Vol vol, const int G[3], const SplineTaps spl[3], hipStream_t st,

@@ -822,7 +822,7 @@ struct March {
 
 // Slow but always-correct adjoint of one squaring step for one (x, y) column over [z0, z1): every source within `hs` voxels is
 // read from global memory.  Lives only in the rarely selected radius-2 kernel, and only runs when the host did not launch the
-// any-radius LDS-scatter kernel for this step (it predicts the displacement bound from earlier transitions, see api.hip) and
+// any-radius LDS-scatter kernel for this step (it predicts the displacement bound from earlier transitions, see api_ctx.hip) and
 // the bound then turned out larger than 2 voxels -- a transient that costs time, never parity.
 template <bool PRESCALE>
 __device__ __forceinline__ void exp_bwd_generic_column(const float* __restrict__ Gc, const Lay3 LG, const float* __restrict__ gsc,

@@ -26,7 +26,7 @@ struct DevState {
     unsigned fails;               // transitions that ended as no-ops because an assumption about max|d_k| did not hold
     const unsigned* comm_err;     // slab over the peer-mapped transport: its sticky device error word (ipc.hip), else nullptr
     // the derived mixture constants as chain c's GMM step left them (chain_scalar_kernel, op bit 3): the data terms of ALL chains then
-    // run as one launch after the serial statistics -> step loop, each chain against its own snapshot (api.hip: data_batch)
+    // run as one launch after the serial statistics -> step loop, each chain against its own snapshot (api_ctx.hip: data_batch)
     float snapA[IRS_MAX_CHAINS][IRS_MAX_COMPONENTS];
     float snap_inv_var[IRS_MAX_CHAINS][IRS_MAX_COMPONENTS];
 };
@@ -43,7 +43,7 @@ __device__ __forceinline__ bool comm_bad(const DevState* s) {
 // bounds of earlier transitions, never waited for).  Every kernel that modifies persistent state -- the mixture and regulariser
 // Adam steps, the velocity update, the Philox counter -- checks the assumptions against the bounds the forward pass has just
 // measured; if one does not hold the transition becomes a NO-OP (no parameter, moment, counter or velocity changes), the
-// failure is counted, and the host re-runs the transition without assumptions when it sees the count (api.hip / slab.hip).
+// failure is counted, and the host re-runs the transition without assumptions when it sees the count (api_ctx.hip / slab.hip).
 struct Verdict {
     const unsigned* bounds;    // [steps + 1][C][4] max|d_k| per chain and axis (float bits); nullptr: nothing assumed
     int n, C;                  // squaring steps, chains

@@ -19,8 +19,8 @@
 #include <new>
 #include <vector>
 
+#include "api_checks.h"
 #include "comm.h"
-#include "ctx.h"
 
 using namespace irs;
 
@@ -236,7 +236,6 @@ struct Sched {
         ffd = cfg.cps[0] || cfg.cps[1] || cfg.cps[2];
         volv = ffd ? make_vol(control_points(cfg.dims[0], cfg.cps[0]), control_points(cfg.dims[1], cfg.cps[1]), control_points(cfg.dims[2], cfg.cps[2])) : vol;
     }
-    static int control_points(int n, int cps) { return (int)ceil((double)(n - 1) / (double)cps) + 1 + 2; }  // utils/util.py:61-69
     Vol W(int e) const { return window(vol, s.a - (s.has_lo ? e : 0), s.b + (s.has_hi ? e : 0)); }
     int step_buf_id(int k) const { return k < 0 ? (ffd ? IRS_SB_DENSE : IRS_SB_VS) : IRS_SB_STEP0 + k; }
     int nbuf_ = 2;  // gradient buffers of the adjoint (three on a slab of several ranks: plan_rounds)
@@ -750,16 +749,9 @@ int ghost_width_from_bound(float m, bool safety) {
 
 // global bound (all chains, all axes) of d_k in a slot of the plan hints
 float hint_bound(const irs_ctx* c, const unsigned* slot, int k) {
-    const volatile unsigned* h = slot + (size_t)k * c->C * 4;
-    float m = 0.0f;
-    for (int i = 0; i < c->C * 4; ++i) {
-        const unsigned bits = h[i];
-        float f;
-        memcpy(&f, &bits, sizeof(f));
-        if (!(f >= 0.0f)) return INFINITY;
-        m = f > m ? f : m;
-    }
-    return m;
+    bool valid;
+    const float m = hint_row_max(slot + (size_t)k * c->C * 4, c->C * 4, &valid);
+    return valid ? m : INFINITY;
 }
 
 // the measuring forward pass: the bound of d_k is all-reduced and read back before step k (one host synchronisation per step)

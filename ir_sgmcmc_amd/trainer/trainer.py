@@ -8,7 +8,7 @@ The VI stage (`_run_VI`, `_test_VI`, trainer/vi.py) is composed in torch from th
 composes it; it hands its hyper-parameters and optimiser moments to the fused engine before the MCMC stage.
 
 Inside `_SGLD_transition` nothing runs in torch: one call into the C ABI launches the whole transition on the current
-HIP stream (ir_sgmcmc_amd/csrc/api.hip: transition_impl).  The hyper-parameters of the loss objects are mirrored into
+HIP stream (ir_sgmcmc_amd/csrc/api_ctx.hip: transition_impl).  The hyper-parameters of the loss objects are mirrored into
 the device state once (`_engine_init`) and read back lazily (`sync_parameters`) when something logs them.
 """
 import time

@@ -420,7 +420,7 @@ def test_one_data_term_launch_for_all_chains_is_the_serial_chain(N, C, kw):
     """Several chains in one engine (every reference config runs two; trainer.py:316-330 steps the shared mixture chain after chain
     and evaluates each chain's data term with the mixture ITS step left).  By default the serial loop is statistics -> step only,
     every step leaves a snapshot of the mixture constants, and the data terms of all chains run as ONE launch behind the loop, each
-    chain against its snapshot (csrc/api.hip, `data_batch`).  Same arithmetic on the same values, same partial-sum slots: bit for
+    chain against its snapshot (csrc/api_ctx.hip, `data_batch`).  Same arithmetic on the same values, same partial-sum slots: bit for
     bit the chain of the serial form (`data_batch` 0) -- velocity, mixture and optimiser state, loss terms."""
     from ir_sgmcmc_amd.data_loader import synthetic_pair
     kw = dict(kw)
@@ -462,7 +462,7 @@ def test_one_data_term_launch_for_all_chains_is_the_serial_chain(N, C, kw):
 @pytest.mark.parametrize('data_loss', ['GMM', 'SSD'])
 def test_chain_overlap_never_changes_the_result(data_loss):
     """Several chains in one engine (every reference config runs two): the data term of chain c runs on a side stream while the
-    statistics of chain c + 1 run on the caller's; the mixture step in between waits for both (csrc/api.hip, `chain_overlap`; measured
+    statistics of chain c + 1 run on the caller's; the mixture step in between waits for both (csrc/api_ctx.hip, `chain_overlap`; measured
     slower than the serial form in round 5 and off by default -- the knob stays, and so does what it must never do).  Same
     kernels, same inputs, same order of every sum: the chain with the overlap is the chain without it, bit for bit -- velocity,
     mixture and optimiser state, loss terms."""

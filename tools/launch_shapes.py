@@ -1,6 +1,6 @@
 """The shape of every marching launch of one transition -- workgroups, threads, segment length, run-in planes, plane steps per
 workgroup, workgroups the chip holds at once, rounds -- at 256^3, at 128^3 (one and two chains) and for one rank of eight of a 256^3 slab run (32 owned
-planes of 256 x 256), as the launchers themselves report it under IRS_LAUNCH_LOG=1 (csrc/api.hip: log_launch).
+planes of 256 x 256), as the launchers themselves report it under IRS_LAUNCH_LOG=1 (csrc/knobs.hip: log_launch).
 
     python tools/launch_shapes.py            # on the GPU box; writes gpurun_out/r05_launch_shapes.json and prints a table
 """
