@@ -408,6 +408,56 @@ int irs_image_similarity(const float* fixed, int Cf, const float* moving, int C,
                          float f_lo, float f_hi, float m_lo, float m_hi, int bins, int32_t* hist, double* stats, void* ws,
                          size_t ws_bytes, void* stream);
 
+/* Local similarity maps (absent in the reference, whose only windowed quantity is the LCC normalisation inside its data
+ * term): where the fixed image and a (warped) moving image agree -- the local normalised cross-correlation (LNCC) and SSIM
+ * of every voxel's box window, their masked statistics, and the per-voxel posterior of the LNCC maps.
+ *  - irs_local_similarity.  Inputs: fixed (Cf,1,D,H,W) float32 with Cf 1 (shared by the chains) or C; moving (C,1,D,H,W)
+ *    float32, C in 1 .. IRS_MAX_CHAINS; mask (1,1,D,H,W) uint8 or NULL; every dim >= 1, fewer than 2^30 voxels; radius r in
+ *    1 .. IRS_LOCAL_MAX_RADIUS; four host doubles floor_f, floor_m, c1, c2, each finite and > 0.
+ *    Window: the (2r+1)^3 box around the voxel with every index clamped to the volume (replicate padding, the rule of the
+ *    reference's LCC convolutions), so n = (2r+1)^3 is the same for every voxel.  The mask plays no part in the window; it
+ *    only selects which voxels enter the statistics.
+ *    Window sums: for each voxel and chain the five sums S_f, S_m, S_ff, S_mm, S_fm over the window are formed in float64,
+ *    each float32 value converted to float64 first, so every product is exact.  mu_x = S_x / n, var_x = max(S_xx / n -
+ *    mu_x^2, 0), cov = S_fm / n - mu_f mu_m.
+ *    LNCC = clamp(cov / sqrt(var_f var_m), -1, 1) when var_f > floor_f and var_m > floor_m; otherwise the voxel is flat and
+ *    its LNCC is NaN.  SSIM = ((2 mu_f mu_m + c1)(2 cov + c2)) / ((mu_f^2 + mu_m^2 + c1)(var_f + var_m + c2)), defined at
+ *    flat voxels too.  A window holding any non-finite value of either image gives NaN in both maps at that voxel and
+ *    affects no other voxel.
+ *    Maps: lncc, ssim (C,1,D,H,W) float32; either may be NULL, and both when only the statistics are wanted.  Each stored
+ *    value is the float64 value rounded once to float32.  Maps are written at every voxel, masked or not.
+ *    stats (C, IRS_LOCAL_STATS) double: n, n_flat, n_nonfinite, lncc_mean, lncc_min, ssim_mean, ssim_min.  n counts the voxels
+ *    of the mask (all voxels when it is NULL) whose window is finite, n_nonfinite those whose window is not, n_flat the flat
+ *    ones among n.  The LNCC columns run over the n - n_flat defined voxels, the SSIM columns over the n voxels, all from the
+ *    float64 values before rounding.  A mean over nothing is NaN, a minimum over nothing +inf.
+ *    ws: IRS_LOCAL_WS_BYTES of device memory.  One launch for all chains and the second-stage reduction.  Deterministic: two
+ *    identical calls are bit-identical and chain c of a C-chain call is bit-identical to the single-chain call on that
+ *    chain's volumes (no float atomics, fixed-order sums, grids that depend on (D,H,W,C,r) only); no host sync.
+ *  - irs_local_similarity_update: lncc (C,1,D,H,W) float32, C in 1 .. IRS_MAX_CHAINS, every dim >= 1; the per-voxel state mean,
+ *    low (D,H,W) float32 and count (D,H,W) int32 (12 bytes per voxel), updated in place.  Per voxel the chains are folded in
+ *    order and a NaN sample is skipped: k = ++count, mean = mean + (x - mean) / (float)k, low = fminf(low, x), every operation
+ *    rounded once to float32.  records_before >= 0, records_before + C <= INT32_MAX; records_before = 0 overwrites the state
+ *    (count 0, mean 0, low +inf before the first sample), which is then never read.  Each thread owns its voxels, no atomics;
+ *    no host sync.
+ *  - irs_local_similarity_finalize: the summary of the state over the mask ((D,H,W) uint8, or NULL: the whole volume).
+ *    isummary: IRS_LOCAL_MAP_SUMMARY_INTS int64 {voxels, voxels with count == 0}; fsummary: IRS_LOCAL_MAP_SUMMARY_FLOATS
+ *    doubles over the voxels with count > 0 {sum of mean, min of mean, min of low}; a minimum nothing entered is +inf.  ws:
+ *    IRS_LOCAL_MAP_WS_BYTES of device memory.  Deterministic; no host sync. */
+#define IRS_LOCAL_MAX_RADIUS 4
+#define IRS_LOCAL_STATS 7
+#define IRS_LOCAL_MAX_BLOCKS 1024 /* rows of per-block partial statistics per chain in the workspace */
+#define IRS_LOCAL_WS_BYTES (IRS_MAX_CHAINS * IRS_LOCAL_MAX_BLOCKS * IRS_LOCAL_STATS * 8)
+#define IRS_LOCAL_MAP_SUMMARY_INTS 2
+#define IRS_LOCAL_MAP_SUMMARY_FLOATS 3
+#define IRS_LOCAL_MAP_WS_BYTES (1024 * (IRS_LOCAL_MAP_SUMMARY_INTS + IRS_LOCAL_MAP_SUMMARY_FLOATS) * 8)
+int irs_local_similarity(const float* fixed, int Cf, const float* moving, int C, const uint8_t* mask, int D, int H, int W,
+                         int radius, double floor_f, double floor_m, double c1, double c2, float* lncc, float* ssim,
+                         double* stats, void* ws, size_t ws_bytes, void* stream);
+int irs_local_similarity_update(const float* lncc, int C, int D, int H, int W, float* mean, float* low, int32_t* count,
+                                int records_before, void* stream);
+int irs_local_similarity_finalize(const float* mean, const float* low, const int32_t* count, const uint8_t* mask, int D, int H,
+                                  int W, long long* isummary, double* fsummary, void* ws, size_t ws_bytes, void* stream);
+
 /* Landmark propagation (absent in the reference, which has no point-set operator): a sampled displacement evaluated at K
  * positions that are no voxel centres, and the posterior of the mapped landmarks with their target registration error (TRE).
  * warped(x) = moving(x + d(x)): a point p of the fixed grid maps to p + d(p) in the moving image; points of the moving space

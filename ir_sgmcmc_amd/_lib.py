@@ -33,6 +33,10 @@ IRS_LANDMARK_MAX_POINTS, IRS_LANDMARK_COLUMNS = 1 << 24, 10
 IRS_LANDMARK_SUMMARY_INTS, IRS_LANDMARK_SUMMARY_FLOATS = 3, 4
 IRS_LANDMARK_WS_BYTES = 1024 * (IRS_LANDMARK_SUMMARY_INTS + IRS_LANDMARK_SUMMARY_FLOATS) * 8
 IRS_SIMILARITY_STATS, IRS_SIMILARITY_MIN_BINS, IRS_SIMILARITY_MAX_BINS = 10, 2, 128
+IRS_LOCAL_MAX_RADIUS, IRS_LOCAL_STATS, IRS_LOCAL_MAX_BLOCKS = 4, 7, 1024
+IRS_LOCAL_WS_BYTES = IRS_MAX_CHAINS * IRS_LOCAL_MAX_BLOCKS * IRS_LOCAL_STATS * 8
+IRS_LOCAL_MAP_SUMMARY_INTS, IRS_LOCAL_MAP_SUMMARY_FLOATS = 2, 3
+IRS_LOCAL_MAP_WS_BYTES = 1024 * (IRS_LOCAL_MAP_SUMMARY_INTS + IRS_LOCAL_MAP_SUMMARY_FLOATS) * 8
 IRS_DATA_GMM_LCC, IRS_DATA_SSD = 0, 1
 IRS_REG_L2, IRS_REG_LOGNORMAL, IRS_REG_STUDENT, IRS_REG_LOGNORMAL_L2 = 0, 1, 2, 3
 
@@ -178,6 +182,10 @@ SIGNATURES = {
     'irs_transform_points': [_P, _I, _P, _I, _I, _I, _I, C.POINTER(C.c_float), _P, _P, _P, _P],
     'irs_landmark_update': [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P],
     'irs_landmark_finalize': [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _P],
+    'irs_local_similarity': [_P, _I, _P, _I, _P, _I, _I, _I, _I, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P,
+                             C.c_size_t, _P],
+    'irs_local_similarity_update': [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P],
+    'irs_local_similarity_finalize': [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, C.c_size_t, _P],
     'irs_create': [C.POINTER(IrsConfig), C.POINTER(_P)],
     'irs_destroy': [_P],
     'irs_workspace_bytes': [_P],

@@ -1012,4 +1012,59 @@ int irs_image_similarity(const float* fixed, int Cf, const float* moving, int C,
     return 0;
 }
 
+// ================================================================================================
+// local similarity maps (local_similarity_kernels.hip)
+// ================================================================================================
+
+// the volume of a local-similarity call: dims of at least 1, < 2^30 voxels
+static bool local_dims_ok(const char* who, int D, int H, int W) {
+    if (D < 1 || H < 1 || W < 1) return !fail("%s: dims (%d, %d, %d), every one >= 1 needed", who, D, H, W);
+    return (int64_t)D * H * W < ((int64_t)1 << 30) || !fail("%s: the volume must have fewer than 2^30 voxels", who);
+}
+
+int irs_local_similarity(const float* fixed, int Cf, const float* moving, int C, const uint8_t* mask, int D, int H, int W,
+                         int radius, double floor_f, double floor_m, double c1, double c2, float* lncc, float* ssim,
+                         double* stats, void* ws, size_t ws_bytes, void* stream) {
+    if (!fixed || !moving || !stats || !ws) return fail("irs_local_similarity: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!broadcast_ok(Cf, C)) return fail("irs_local_similarity: fixed image of %d chains, 1 or %d needed", Cf, C);
+    if (radius < 1 || radius > IRS_LOCAL_MAX_RADIUS)
+        return fail("irs_local_similarity: radius = %d, 1..%d", radius, IRS_LOCAL_MAX_RADIUS);
+    const double values[4] = {floor_f, floor_m, c1, c2};
+    const char* names[4] = {"floor_f", "floor_m", "c1", "c2"};
+    for (int j = 0; j < 4; ++j)
+        if (!(values[j] > 0.0) || !isfinite(values[j]))
+            return fail("irs_local_similarity: %s = %g, a finite value > 0 needed", names[j], values[j]);
+    if (!local_dims_ok(__func__, D, H, W)) return 1;
+    const LocalGeom g = local_similarity_geometry(D, H, W, radius);
+    const size_t need = (size_t)C * g.blocks * IRS_LOCAL_STATS * 8;
+    if (!workspace_ok(__func__, ws_bytes, need, "IRS_LOCAL_WS_BYTES")) return 1;
+    const LocalConsts k = {floor_f, floor_m, c1, c2};
+    launch_local_similarity(fixed, Cf == 1 ? 0 : (int64_t)D * H * W, moving, mask, C, radius, g, k, lncc, ssim, stats, ws,
+                            (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_local_similarity_update(const float* lncc, int C, int D, int H, int W, float* mean, float* low, int32_t* count,
+                                int records_before, void* stream) {
+    if (!lncc || !mean || !low || !count) return fail("irs_local_similarity_update: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!local_dims_ok(__func__, D, H, W)) return 1;
+    if (!records_ok(__func__, records_before, C, INT32_MAX, "overflow the int32 sample count")) return 1;
+    launch_local_similarity_update(lncc, C, (int64_t)D * H * W, mean, low, count, records_before, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_local_similarity_finalize(const float* mean, const float* low, const int32_t* count, const uint8_t* mask, int D, int H,
+                                  int W, long long* isummary, double* fsummary, void* ws, size_t ws_bytes, void* stream) {
+    if (!mean || !low || !count || !isummary || !fsummary || !ws) return fail("irs_local_similarity_finalize: bad arguments");
+    if (!local_dims_ok(__func__, D, H, W)) return 1;
+    if (!workspace_ok(__func__, ws_bytes, (size_t)IRS_LOCAL_MAP_WS_BYTES, "IRS_LOCAL_MAP_WS_BYTES")) return 1;
+    launch_local_similarity_finalize(mean, low, count, (int64_t)D * H * W, mask, isummary, fsummary, ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 }  // extern "C"

@@ -291,6 +291,31 @@ void launch_landmark_finalize(const double* mean, const double* comoment, const 
                               const double* tre_max, const int32_t* count, const float* target, int K, double* out,
                               long long* isummary, double* fsummary, void* ws, hipStream_t st);
 
+// ---- local_similarity_kernels.hip: windowed LNCC / SSIM maps and the posterior of the LNCC maps (absent in the reference)
+struct LocalGeom {
+    int D, H, W;
+    int tiles_x, tiles;  // 32 x 8 tiles along x, and per plane
+    int seg_len, nwork;  // planes per z-segment; work items = tiles x segments
+    int blocks;          // blocks per chain = rows of partials per chain: min(nwork, IRS_LOCAL_MAX_BLOCKS)
+};
+struct LocalConsts {
+    double floor_f, floor_m, c1, c2;
+};
+// the launch shape of a volume: depends on (D, H, W, radius) only
+LocalGeom local_similarity_geometry(int D, int H, int W, int radius);
+// fixed (1 or C,V) with fixed_stride 0 or V; moving (C,V); mask (V) uint8 or nullptr; lncc / ssim (C,V) or nullptr; stats (C,
+// IRS_LOCAL_STATS); ws: C * g.blocks rows of 3 int64 + 4 doubles (at most IRS_LOCAL_WS_BYTES); radius in 1 .. IRS_LOCAL_MAX_RADIUS
+void launch_local_similarity(const float* fixed, int64_t fixed_stride, const float* moving, const uint8_t* mask, int C, int radius,
+                             const LocalGeom& g, const LocalConsts& k, float* lncc, float* ssim, double* stats, void* ws,
+                             hipStream_t st);
+// lncc (C,V) float32 -> mean / low (V) float32, count (V) int32: the samples that are no NaN folded in chain order
+// (records_before == 0 overwrites)
+void launch_local_similarity_update(const float* lncc, int C, int64_t V, float* mean, float* low, int32_t* count,
+                                    int records_before, hipStream_t st);
+// isummary IRS_LOCAL_MAP_SUMMARY_INTS int64, fsummary IRS_LOCAL_MAP_SUMMARY_FLOATS doubles; ws: IRS_LOCAL_MAP_WS_BYTES
+void launch_local_similarity_finalize(const float* mean, const float* low, const int32_t* count, int64_t V, const uint8_t* mask,
+                                      long long* isummary, double* fsummary, void* ws, hipStream_t st);
+
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h
 }  // namespace irs

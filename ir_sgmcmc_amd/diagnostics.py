@@ -50,6 +50,11 @@ in mm under the header zooms.
 The intensity-similarity option (image_similarity_options) keeps no state either: at a logged step it compares the fixed image
 with the warped moving image the transition produced (ops.image_similarity: joint histogram, MI / NMI, MSE, NCC in one pass) --
 the only figures of registration quality that need no segmentation.
+
+The local similarity (LocalSimilarity, local_similarity_options) is the one map that describes the match of intensities and not
+the transformation: at a logged step ops.local_similarity gives the windowed LNCC and SSIM of the fixed and the warped moving
+image, and at a recorded step the LNCC maps are folded into a per-voxel streaming mean, minimum and count
+(ops.local_similarity_update), 12 * D * H * W bytes whatever the number of records.
 """
 import math
 import numbers
@@ -1202,3 +1207,97 @@ def image_similarity_metric_names(no_chains):
     posterior-mean displacement"""
     prefixes = ['VI/train/similarity'] + [f'MCMC/chain_{i}/similarity' for i in range(no_chains)] + ['MCMC/similarity_of_mean']
     return [f'{p}/{k}' for p in prefixes for k in SIMILARITY_METRICS]
+
+
+LOCAL_OPTION_KEYS = ('radius', 'period', 'save')
+LOCAL_DEFAULTS = {'radius': 2, 'save': True}
+LOCAL_MAX_RADIUS = 4  # IRS_LOCAL_MAX_RADIUS
+LOCAL_METRICS = (('LNCC', 'lncc_mean'), ('LNCC_min', 'lncc_min'), ('SSIM', 'ssim_mean'))  # logged name, ops.LOCAL_COLUMNS name
+
+
+def local_similarity_options(cfg_trainer):
+    """`trainer.local_similarity` -> None when off, else {'period': P, 'radius': r, 'save': bool}.
+    Absent / false / null: off.  true: windows of radius 2, the statistics at every logged step, the LNCC posterior recorded
+    every log_period_MCMC-th step after the burn-in, the maps written.  {"radius": r, "period": P, "save": bool} sets any of
+    them.  Refuses unknown keys, a non-integer r or an r outside 1 .. 4, a non-integer P or P < 1, a non-bool save, a config
+    that records no step (no_samples_MCMC // P < 1) and one that would record more than 2^31 - 1 maps."""
+    what = 'trainer.local_similarity'
+
+    def own_keys(opt):
+        own = {**LOCAL_DEFAULTS, **{k: v for k, v in opt.items() if k != 'period'}}
+        r = own['radius']
+        if isinstance(r, bool) or not isinstance(r, numbers.Integral):
+            raise ValueError(f'{what}.radius must be an integer, got {r!r}')
+        if not 1 <= r <= LOCAL_MAX_RADIUS:
+            raise ValueError(f'{what}: radius must be in 1 .. {LOCAL_MAX_RADIUS}, got {r}')
+        if not isinstance(own['save'], bool):
+            raise ValueError(f'{what}.save must be true or false, got {own["save"]!r}')
+        return {'radius': int(r), 'save': own['save']}
+
+    return _record_options(cfg_trainer, 'local_similarity', LOCAL_OPTION_KEYS, '{"radius": r, "period": P, "save": bool}',
+                           MAX_RECORDS, 'the sample count holds at most {}', own_keys)
+
+
+def local_similarity_metric_names(no_chains):
+    """the metric names the option adds: the unregistered pair at step 0, every chain's sampled transformation, the
+    posterior-mean displacement"""
+    prefixes = (['VI/train/local_similarity'] + [f'MCMC/chain_{i}/local_similarity' for i in range(no_chains)] +
+                ['MCMC/local_similarity_of_mean'])
+    return [f'{p}/{k}' for p in prefixes for k, _ in LOCAL_METRICS]
+
+
+def local_map_summary(isummary, fsummary, n):
+    """the summary of the LNCC posterior from ops.local_similarity_finalize's columns (host ints / floats): isummary {voxels,
+    voxels without a defined sample}, fsummary {sum / min of the mean map, min of the minimum map} over the others, n records.
+    'lncc_mean' is the mean of the mean map; NaN when no masked voxel has a sample."""
+    voxels, empty = (int(x) for x in isummary)
+    m_sum, m_min, l_min = (float(x) for x in fsummary)
+    some = voxels - empty
+    nan = float('nan')
+    return {'records': int(n), 'voxels': voxels, 'empty_voxels': empty, 'lncc_mean': _nan_div(m_sum, some),
+            'lncc_mean_min': m_min if some else nan, 'lncc_min': l_min if some else nan}
+
+
+class LocalSimilarity(_Recorder):
+    """Per voxel, the streaming mean, the minimum and the number of the LNCC samples that are defined there (a sample is NaN
+    where its window is flat or holds a non-finite value, and is skipped): `mean`, `low` (D,H,W) float32 and `count` (D,H,W)
+    int32 on the device, 12 D H W bytes whatever the number of records.  A low mean says every sample disagrees with the fixed
+    image there; a high mean with a low minimum says the chain is unsure.  `record(lncc)` takes the (C,1,D,H,W) float32 LNCC
+    maps of one step (ops.local_similarity); `finalize(mask)` gives the two maps, NaN where nothing was ever defined, and
+    their summary over the mask."""
+    noun = 'local similarity'
+
+    def __init__(self, dims, device):
+        self.dims = tuple(int(d) for d in dims)
+        if len(self.dims) != 3 or min(self.dims) < 1:
+            raise ValueError(f'local similarity: three dims of at least 1, got {self.dims}')
+        self.device = device
+        self.mean = torch.zeros(self.dims, device=device, dtype=torch.float32)
+        self.low = torch.full(self.dims, math.inf, device=device, dtype=torch.float32)
+        self.count = torch.zeros(self.dims, device=device, dtype=torch.int32)
+
+    def _update(self, lncc):
+        ops.local_similarity_update(lncc.contiguous(), self.mean, self.low, self.count, self.records)
+
+    def finalize(self, mask=None):
+        """-> (mean, low (D,H,W) float32 with NaN where no sample was defined, summary of local_map_summary over the mask).  One
+        device-to-host read."""
+        self._need_records('finalize')
+        isum, fsum = ops.local_similarity_finalize(self.mean, self.low, self.count, _bool_mask(mask, self.device))
+        some = self.count > 0
+        nan = self.mean.new_full((), math.nan)
+        return self.mean.where(some, nan), self.low.where(some, nan), local_map_summary(*_host_summary(isum, fsum), self.records)
+
+    def state_dict(self):
+        return {'records': self.records, 'mean': self.mean.detach().cpu(), 'low': self.low.detach().cpu(),
+                'count': self.count.detach().cpu()}
+
+    def load_state_dict(self, sd):
+        for name in ('mean', 'low', 'count'):
+            if tuple(sd[name].shape) != self.dims:
+                raise ValueError(f'local similarity state of shape {tuple(sd[name].shape)} ({name}) does not match this run '
+                                 f'({self.dims})')
+        self.mean.copy_(sd['mean'])
+        self.low.copy_(sd['low'])
+        self.count.copy_(sd['count'])
+        self.records = int(sd['records'])

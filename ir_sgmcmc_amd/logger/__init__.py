@@ -238,3 +238,31 @@ def save_landmarks(logger, save_dirs, mean_points, table, columns, unit, model='
                      [(name, table[:, columns.index(name)]) for name in ('tre_of_mean', 'std_major', 'pit')],
                      title=f'posterior-mean landmarks ({unit})')
     logger.info(f'{model} landmarks{tag}: {len(table)} rows in {unit} -> {model}_landmarks{tag}.csv, {model}_landmarks{tag}_mean.vtk')
+
+
+def _nan_to_zero(im):
+    """-> (the map with 0 where it is NaN, how many voxels that was)"""
+    nan = im.isnan()
+    return im.where(~nan, im.new_zeros(())), int(nan.sum())
+
+
+def save_local_similarity_posterior(logger, save_dirs, spacing, mean, low, mask, model='MCMC'):
+    """the posterior of the LNCC maps (absent in the reference): samples/{model}_lncc_{mean,min}[_masked].nii.gz (float32; NaN --
+    no sample was defined there -- written as 0, the masked ones 0 outside the mask too)"""
+    folder = _folder(save_dirs, 'samples')
+    mask = mask.reshape(mean.shape).to(mean.device) != 0
+    for name, im in (('lncc_mean', mean), ('lncc_min', low)):
+        im, undefined = _nan_to_zero(im)
+        logger.info(f'{model}_{name}: {undefined} voxels without a defined sample written as 0')
+        save_im_to_disk(im, path.join(folder, f'{model}_{name}.nii.gz'), spacing)
+        save_im_to_disk(im.where(mask, im.new_zeros(())), path.join(folder, f'{model}_{name}_masked.nii.gz'), spacing)
+
+
+def save_local_similarity_of_mean(logger, save_dirs, spacing, lncc, ssim, model='MCMC'):
+    """the local similarity maps of the moving image under the posterior-mean displacement (absent in the reference):
+    samples/{model}_lncc_of_mean.nii.gz and samples/{model}_ssim_of_mean.nii.gz (float32; NaN written as 0)"""
+    folder = _folder(save_dirs, 'samples')
+    for name, im in (('lncc', lncc), ('ssim', ssim)):
+        im, undefined = _nan_to_zero(im)
+        logger.info(f'{model}_{name}_of_mean: {undefined} undefined voxels written as 0')
+        save_im_to_disk(im, path.join(folder, f'{model}_{name}_of_mean.nii.gz'), spacing)

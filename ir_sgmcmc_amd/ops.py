@@ -810,6 +810,100 @@ def image_similarity(fixed, moving, mask=None, bins=64, fixed_range=None, moving
     return out
 
 
+LOCAL_COLUMNS = ('n', 'n_flat', 'n_nonfinite', 'lncc_mean', 'lncc_min', 'ssim_mean', 'ssim_min')
+LOCAL_MAPS = ('lncc', 'ssim')
+
+
+def local_similarity_constants(fixed_range, moving_range):
+    """(floor_f, floor_m, c1, c2) of local_similarity from the two intensity ranges (lo, hi): a window is flat when its variance
+    is not above floor_x = (1e-3 (hi - lo))^2; with L = max(f_hi, m_hi) - min(f_lo, m_lo) the SSIM constants are c1 = (0.01 L)^2
+    and c2 = (0.03 L)^2.  Python floats (float64); both ranges finite with hi > lo."""
+    (f_lo, f_hi), (m_lo, m_hi) = ((float(x) for x in r) for r in (fixed_range, moving_range))
+    for name, lo, hi in (('fixed', f_lo, f_hi), ('moving', m_lo, m_hi)):
+        if not (math.isfinite(lo) and math.isfinite(hi) and hi > lo):
+            raise L.IrsError(f'{name} range [{lo}, {hi}]: finite bounds with hi > lo needed')
+    span = max(f_hi, m_hi) - min(f_lo, m_lo)
+    return (1e-3 * (f_hi - f_lo)) ** 2, (1e-3 * (m_hi - m_lo)) ** 2, (0.01 * span) ** 2, (0.03 * span) ** 2
+
+
+def local_similarity(fixed, moving, mask=None, radius=2, fixed_range=None, moving_range=None, want=LOCAL_MAPS):
+    """Where two images agree (absent in the reference): the local normalised cross-correlation and SSIM of every voxel's
+    (2 radius + 1)^3 box window with clamped indices.  fixed (1 or C,1,D,H,W) and moving (C,1,D,H,W) float32; mask (1,1,D,H,W)
+    bool / uint8 shared by the chains, or None: it selects the voxels of the statistics, never those of a window; radius in
+    1 .. 4; fixed_range / moving_range: (lo, hi), finite with hi > lo -- None: the min / max of the finite values of that image
+    (one host read-back; with both given the call does not synchronise) -- which give the flatness floors and the SSIM
+    constants (local_similarity_constants); want: which of 'lncc', 'ssim' to write.  -> {'stats': (C,7) float64 on the device,
+    columns LOCAL_COLUMNS[, 'lncc': (C,1,D,H,W) float32][, 'ssim': ...]}; LNCC is NaN where a window is flat, both maps where
+    it holds a non-finite value (include/irsgmcmc.h: irs_local_similarity)."""
+    lib = L.load()
+    Cn, D, H, W = _dims5(moving, 1)
+    _chain_volumes('fixed', fixed, 'moving', Cn, D, H, W)
+    if mask is not None:
+        if tuple(mask.shape) != (1, 1, D, H, W) or mask.dtype not in (torch.bool, torch.uint8):
+            raise L.IrsError(f'mask must be a bool / uint8 (1,1,{D},{H},{W}) volume, got {mask.dtype} {tuple(mask.shape)}')
+        mask = mask.contiguous()
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    if isinstance(radius, bool) or not isinstance(radius, int):
+        raise L.IrsError(f'radius must be an integer, got {radius!r}')
+    want = tuple(want)
+    if any(w not in LOCAL_MAPS for w in want):
+        raise L.IrsError(f'want must list names out of {LOCAL_MAPS}, got {want}')
+    fixed_ptr, moving_ptr = L.dev_ptr(fixed, torch.float32), L.dev_ptr(moving, torch.float32)
+    missing = [im for im, r in ((fixed, fixed_range), (moving, moving_range)) if r is None]
+    found = iter(intensity_ranges(*missing)) if missing else None
+    fixed_range = fixed_range if fixed_range is not None else next(found)
+    moving_range = moving_range if moving_range is not None else next(found)
+    consts = local_similarity_constants(fixed_range, moving_range)
+    dev = moving.device
+    ws = torch.empty(L.IRS_LOCAL_WS_BYTES, device=dev, dtype=torch.uint8)
+    out = {'stats': torch.empty((Cn, L.IRS_LOCAL_STATS), device=dev, dtype=torch.float64)}
+    for name in LOCAL_MAPS:
+        if name in want:
+            out[name] = torch.empty((Cn, 1, D, H, W), device=dev, dtype=torch.float32)
+    L.check(lib.irs_local_similarity(fixed_ptr, fixed.shape[0], moving_ptr, Cn, L.dev_ptr(mask, torch.uint8, True), D, H, W, radius,
+                                     *consts, L.dev_ptr(out.get('lncc'), None, True), L.dev_ptr(out.get('ssim'), None, True),
+                                     L.dev_ptr(out['stats']), L.dev_ptr(ws), L.IRS_LOCAL_WS_BYTES, L.stream_ptr()))
+    return out
+
+
+def _local_state(mean, low, count, shape):
+    for name, t, dtype in (('mean', mean, torch.float32), ('low', low, torch.float32), ('count', count, torch.int32)):
+        if tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+            raise L.IrsError(f'{name} must be a {tuple(shape)} {dtype} tensor, got {t.dtype} {tuple(t.shape)}')
+
+
+def local_similarity_update(lncc, mean, low, count, records_before):
+    """Fold one recorded step of LNCC maps into their per-voxel posterior (absent in the reference): lncc (C,1,D,H,W) float32,
+    every chain's map; mean / low (D,H,W) float32 and count (D,H,W) int32: the streaming mean, the minimum and the number of
+    the samples that are no NaN, folded in chain order after `records_before` records (0 overwrites the state).  No host
+    synchronisation."""
+    lib = L.load()
+    Cn, D, H, W = _dims5(lncc, 1)
+    _local_state(mean, low, count, (D, H, W))
+    L.check(lib.irs_local_similarity_update(L.dev_ptr(lncc, torch.float32), Cn, D, H, W, L.dev_ptr(mean), L.dev_ptr(low),
+                                            L.dev_ptr(count), int(records_before), L.stream_ptr()))
+
+
+def local_similarity_finalize(mean, low, count, mask=None):
+    """The masked summary of the LNCC posterior state (absent in the reference).  mean / low (D,H,W) float32, count (D,H,W)
+    int32; mask (D,H,W) bool / uint8 or None.  -> (isummary (2,) int64 {voxels, voxels with count == 0}, fsummary (3,) float64
+    {sum of mean, min of mean, min of low} over the voxels with count > 0), on the device.  No host synchronisation."""
+    lib = L.load()
+    if mean.dim() != 3:
+        raise L.IrsError(f'mean must have shape (D,H,W), got {tuple(mean.shape)}')
+    D, H, W = mean.shape
+    _local_state(mean, low, count, (D, H, W))
+    mask = _volume_mask(mask, D, H, W)
+    dev = mean.device
+    ws = torch.empty(L.IRS_LOCAL_MAP_WS_BYTES, device=dev, dtype=torch.uint8)
+    isummary = torch.empty(L.IRS_LOCAL_MAP_SUMMARY_INTS, device=dev, dtype=torch.int64)
+    fsummary = torch.empty(L.IRS_LOCAL_MAP_SUMMARY_FLOATS, device=dev, dtype=torch.float64)
+    L.check(lib.irs_local_similarity_finalize(L.dev_ptr(mean), L.dev_ptr(low), L.dev_ptr(count), L.dev_ptr(mask, torch.uint8, True),
+                                              D, H, W, L.dev_ptr(isummary), L.dev_ptr(fsummary), L.dev_ptr(ws),
+                                              L.IRS_LOCAL_MAP_WS_BYTES, L.stream_ptr()))
+    return isummary, fsummary
+
+
 LANDMARK_COLUMNS = ('count', 'tre_mean', 'tre_std', 'tre_max', 'tre_of_mean', 'std_major', 'std_middle', 'std_minor', 'mahalanobis2',
                     'pit')
 LANDMARK_STATE = (('mean', 3, torch.float64), ('comoment', 6, torch.float64), ('tre_mean', None, torch.float64),

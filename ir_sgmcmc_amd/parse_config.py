@@ -15,7 +15,8 @@ from .diagnostics import (COVARIANCE_METRICS, ICE_SPACES, JACOBIAN_METRICS, LABE
                           diagnostics_period, displacement_covariance_options, displacement_quantiles_options, ess_options,
                           hausdorff_metric_names, hausdorff_options, image_similarity_metric_names, image_similarity_options,
                           inverse_consistency_options, jacobian_posterior_options, label_posterior_options,
-                          landmark_metric_names, landmark_options, native_resolution_options)
+                          landmark_metric_names, landmark_options, local_similarity_metric_names, local_similarity_options,
+                          native_resolution_options)
 from .logger import setup_logging
 from .model import distributions as model_distr
 from .model import loss as model_loss
@@ -129,6 +130,8 @@ class ConfigParser:
         landmarks = landmark_options(self['trainer'])
         if landmarks is not None:
             m += landmark_metric_names(landmarks, C)
+        if local_similarity_options(self['trainer']) is not None:
+            m += local_similarity_metric_names(C)
         return m
 
     def init_transformation_and_registration_modules(self):

@@ -21,24 +21,27 @@ from ..base import BaseTrainer
 from .. import ops
 from ..diagnostics import (COVARIANCE_METRICS, ChainMoments, DisplacementCovariance, DisplacementQuantiles, ICE_SPACES,
                            InverseConsistency, JACOBIAN_METRICS, JacobianPosterior, LABEL_STRUCTURE_METRICS, LANDMARK_METRICS,
-                           LabelPosterior, LandmarkPair, LandmarkPosterior, QUANTILE_METRICS, diagnostics_period, displacement_covariance_options, displacement_quantiles_options,
+                           LOCAL_METRICS, LabelPosterior, LandmarkPair, LandmarkPosterior, LocalSimilarity, QUANTILE_METRICS,
+                           diagnostics_period, displacement_covariance_options, displacement_quantiles_options,
                            ess_options, hausdorff_options, image_similarity_options, inverse_consistency_options, is_recorded,
-                           jacobian_posterior_options, label_posterior_options, landmark_options, native_resolution_options,
-                           SIMILARITY_METRICS, voxel_scale)
+                           jacobian_posterior_options, label_posterior_options, landmark_options, local_similarity_options,
+                           native_resolution_options, SIMILARITY_METRICS, voxel_scale)
 from ..engine import EngineConfig, TransitionEngine
 from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_quantiles, save_ess,
-                      save_field, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_landmarks, save_native_mean,
-                      save_native_sample, save_rhat, save_sample)
+                      save_field, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_landmarks,
+                      save_local_similarity_of_mean, save_local_similarity_posterior, save_native_mean, save_native_sample, save_rhat,
+                      save_sample)
 from ..utils import (calc_DSC_GPU, calc_image_similarity, calc_norm, calc_no_non_diffeomorphic_voxels, init_identity_grid_3D,
-                     sample_q_v, transform_coordinates)
+                     local_similarity_rows, sample_q_v, transform_coordinates)
 from .vi import VIMixin
 
 
 # A posterior recorder of the MCMC stage (Trainer._recorders): its checkpoint key, its state object (diagnostics.py), its
 # period, the trainer.<option> that switches it on, the noun of the resume error, what it records of a transition (an
 # output: 'displacement', 'transformation'; 'seg_warped': the warped moving segmentation; 'velocity': the dense velocity the
-# exponential integrated; or a tuple of these, recorded as a tuple), its _finish_* method and what that takes first ('fixed':
-# the fixed image's dict, 'moving_mask': the mask of the displacement std map, 'masks': {'fixed': ..., 'moving': ...})
+# exponential integrated; 'lncc': the LNCC maps of the warped moving image; or a tuple of these, recorded as a tuple), its
+# _finish_* method and what that takes first ('fixed': the fixed image's dict, 'moving_mask': the mask of the displacement std
+# map, 'masks': {'fixed': ..., 'moving': ...})
 Recorder = namedtuple('Recorder', 'key state period option noun records finish takes')
 
 
@@ -120,6 +123,11 @@ class Trainer(VIMixin, BaseTrainer):
         self.landmark_options = landmark_options(cfg_trainer, data_loader)
         self._landmarks, self._landmark_unit = None, None
         self.landmark_summary = None
+        # local similarity maps of the fixed and the warped moving image and the posterior of the LNCC maps
+        # (ops.local_similarity, diagnostics.LocalSimilarity): None when trainer.local_similarity is off
+        self.local_options = local_similarity_options(cfg_trainer)
+        self._local_similarity, self._local_ranges, self._local_warned = None, None, False
+        self.local_lncc_mean, self.local_lncc_min, self.local_similarity_summary = None, None, None
 
     # ---------------------------------------------------------------- engine plumbing
     def _engine_config(self):
@@ -205,7 +213,7 @@ class Trainer(VIMixin, BaseTrainer):
 
     def _recorders(self):
         """the active recorders, in the order they record and finish: moments, labels, Jacobian, covariance, quantiles,
-        inverse consistency, landmarks"""
+        inverse consistency, landmarks, local similarity"""
         period = lambda options: options and options['period']
         rows = (('chain_moments', self._chain_moments, self.diagnostics_period, 'convergence_diagnostics', 'chain moments',
                  'displacement', self._finish_diagnostics, 'moving_mask'),
@@ -222,7 +230,9 @@ class Trainer(VIMixin, BaseTrainer):
                  'inverse consistency', ('velocity', 'transformation', 'displacement'), self._finish_inverse_consistency, 'masks'),
                 ('landmarks', self._landmarks, period(self.landmark_options), 'landmarks', 'landmark posterior',
                  ('displacement', 'velocity') if self.landmark_options and self.landmark_options['inverse'] else 'displacement',
-                 self._finish_landmarks, 'masks'))
+                 self._finish_landmarks, 'masks'),
+                ('local_similarity', self._local_similarity, period(self.local_options), 'local_similarity', 'local similarity',
+                 'lncc', self._finish_local_similarity, 'fixed'))
         return [Recorder(*row) for row in rows if row[1] is not None]
 
     # ---------------------------------------------------------------- checkpoint / resume (absent in the reference)
@@ -398,6 +408,9 @@ class Trainer(VIMixin, BaseTrainer):
             self._similarity_init(fixed, moving)
         if self.landmark_options is not None:
             self._landmarks_init(self._outputs['displacement'].shape[2:])
+        if self.local_options is not None:
+            self._local_init(fixed, moving)
+            self._local_similarity = LocalSimilarity(self._outputs['displacement'].shape[2:], self.device)
         if cfg_trainer.get('resume'):
             self.load_checkpoint(cfg_trainer['resume'])
             first = self._sample_no + 1
@@ -412,6 +425,7 @@ class Trainer(VIMixin, BaseTrainer):
             if sample_no == self.no_iters_burn_in:
                 log('ENDED BURNING IN')
             seg_warped = None  # the warped segmentation of this step, when the Dice / ASD branch builds it
+            lncc = None  # the LNCC maps of this step, when the logging branch forms them
             logged = False  # a step whose sample is logged (and, with save_samples, saved)
             self.writer.set_step(sample_no)
             if (sample_no - 1) % every == 0:
@@ -469,13 +483,19 @@ class Trainer(VIMixin, BaseTrainer):
                 self.engine.flush()  # as above
                 rows = self._image_similarity(fixed, output['im_moving_warped'])
                 self._log_similarity([f'MCMC/chain_{idx}/similarity' for idx in range(self.no_chains)], rows)
+            if self.local_options is not None and logged:
+                local = self._local_maps(fixed, output['im_moving_warped'], ('lncc',))
+                lncc = local['lncc']
+                self._log_local([f'MCMC/chain_{idx}/local_similarity' for idx in range(self.no_chains)], local['rows'])
             due = [r for r in recorders if is_recorded(sample_no, self.no_iters_burn_in, r.period)]
             if due:
                 self.engine.flush()  # as above: the buffers hold sample `sample_no` once nothing is pending
             for r in due:
                 if r.records == 'seg_warped' and seg_warped is None:
                     seg_warped = self.registration_module(moving['seg'], output['transformation'])
-                pick = lambda name: (seg_warped if name == 'seg_warped' else
+                if r.records == 'lncc' and lncc is None:
+                    lncc = self._local_maps(fixed, output['im_moving_warped'], ('lncc',))['lncc']
+                pick = lambda name: (seg_warped if name == 'seg_warped' else lncc if name == 'lncc' else
                                      self._dense_velocity(output) if name == 'velocity' else output[name])
                 r.state.record(tuple(pick(n) for n in r.records) if isinstance(r.records, tuple) else pick(r.records))
             if self._inverse_consistency is not None:
@@ -528,6 +548,15 @@ class Trainer(VIMixin, BaseTrainer):
             row = self._image_similarity(fixed, warped)[0]
             self._log_similarity(['MCMC/similarity_of_mean'], [row])
             self._similarity_summary('mean', row, f'the mean of {n_rec} samples')
+        if self.local_options is not None and n_rec > 0:
+            ident = init_identity_grid_3D(mean.shape[1:], self.device).permute(0, 4, 1, 2, 3)
+            warped = self.registration_module(moving['im'], (ident + transform_coordinates(mean.unsqueeze(0))).contiguous())
+            local = self._local_maps(fixed, warped)
+            self._log_local(['MCMC/local_similarity_of_mean'], local['rows'])
+            self._local_summary('mean', local['rows'][0], f'the mean of {n_rec} samples')
+            if cfg_trainer.get('save_outputs', True) and self.local_options['save']:
+                save_local_similarity_of_mean(self.logger, self.config.save_dirs, spacing, local['lncc'][0, 0], local['ssim'][0, 0],
+                                              'MCMC')
         for r in recorders:
             r.finish(fixed if r.takes == 'fixed' else masks if r.takes == 'masks' else masks['moving'], spacing,
                      cfg_trainer.get('save_outputs', True))
@@ -725,6 +754,68 @@ class Trainer(VIMixin, BaseTrainer):
         row = self._image_similarity(fixed, moving['im'][:1])[0]
         self._log_similarity(['VI/train/similarity'], [row])
         self._similarity_summary('unregistered', row, 'the unregistered pair')
+
+    def _local_init(self, fixed, moving):
+        """the two intensity ranges that give the flatness floors and the SSIM constants: the finite min / max of the fixed and
+        of the moving image (trilinear interpolation with border padding cannot leave the moving range); one host read-back"""
+        if self._local_ranges is not None:
+            return
+        self._local_ranges = ops.intensity_ranges(fixed['im'], moving['im'])
+        floor_f, floor_m, c1, c2 = ops.local_similarity_constants(*self._local_ranges)
+        r = self.local_options['radius']
+        self.logger.info(f'local similarity: windows of {2 * r + 1}^3 voxels, a window is flat below a variance of {floor_f:.3g} '
+                         f'(fixed) / {floor_m:.3g} (moving); SSIM constants {c1:.3g}, {c2:.3g}')
+
+    def _local_maps(self, fixed, moving_im, want=('lncc', 'ssim')):
+        """ops.local_similarity of every volume of moving_im against fixed['im'] under fixed['mask'], all chains in one call ->
+        its dict plus 'rows': one dict of statistics per volume (utils.local_similarity_rows); one warning per run when a
+        window held a non-finite value"""
+        out = ops.local_similarity(fixed['im'], moving_im.contiguous(), fixed['mask'][:1], self.local_options['radius'],
+                                   *self._local_ranges, want=want)
+        out['rows'] = local_similarity_rows(out['stats'])
+        if not self._local_warned and any(r['n_nonfinite'] > 0 for r in out['rows']):
+            self._local_warned = True
+            self.logger.warning(f'local similarity: {max(r["n_nonfinite"] for r in out["rows"])} masked voxels whose window holds a '
+                                f'non-finite intensity (NaN in the maps, left out of the statistics); not reported again in this run')
+        return out
+
+    def _log_local(self, prefixes, rows):
+        for prefix, row in zip(prefixes, rows):
+            for key, column in LOCAL_METRICS:
+                self.metrics.update(f'{prefix}/{key}', row[column])
+
+    def _local_summary(self, name, row, what):
+        """self.local_similarity_summary[name] = the statistics of one pair of maps, and one log line"""
+        if self.local_similarity_summary is None:
+            self.local_similarity_summary = {}
+        self.local_similarity_summary[name] = dict(row)
+        self.logger.info(f'local similarity of {what} over {row["n"]} masked voxels ({row["n_flat"]} flat): LNCC mean '
+                         f'{row["lncc_mean"]:.6g}, min {row["lncc_min"]:.6g}; SSIM mean {row["ssim_mean"]:.6g}, min '
+                         f'{row["ssim_min"]:.6g}')
+
+    def _log_local_unregistered(self, fixed, moving):
+        """step 0: the unregistered pair under VI/train/local_similarity/*, with or without segmentations"""
+        self._local_init(fixed, moving)
+        self.writer.set_step(0)
+        row = self._local_maps(fixed, moving['im'][:1], ())['rows'][0]
+        self._log_local(['VI/train/local_similarity'], [row])
+        self._local_summary('unregistered', row, 'the unregistered pair')
+
+    def _finish_local_similarity(self, fixed, spacing, save_outputs):
+        """mean and minimum of the recorded LNCC maps and their summary -> self.local_lncc_mean / local_lncc_min /
+        local_similarity_summary['posterior'] and, with save_outputs and the option's save,
+        samples/MCMC_lncc_{mean,min}[_masked].nii.gz.  The maps live on the fixed grid: the summary is over the FIXED mask."""
+        mask = fixed['mask'][0]
+        self.local_lncc_mean, self.local_lncc_min, s = self._local_similarity.finalize(mask)
+        if self.local_similarity_summary is None:
+            self.local_similarity_summary = {}
+        self.local_similarity_summary['posterior'] = s
+        self.logger.info(f'LNCC posterior of {s["records"]} samples over {s["voxels"]} masked voxels ({s["empty_voxels"]} never '
+                         f'defined): mean of the mean map {s["lncc_mean"]:.6g}, its minimum {s["lncc_mean_min"]:.6g}; lowest sample '
+                         f'{s["lncc_min"]:.6g}')
+        if save_outputs and self.local_options['save']:
+            save_local_similarity_posterior(self.logger, self.config.save_dirs, spacing, self.local_lncc_mean, self.local_lncc_min,
+                                            mask, 'MCMC')
 
     def _landmarks_init(self, dims):
         """trainer.landmarks -> self._landmarks (diagnostics.LandmarkPair), once: the landmark files' voxel indices carried to

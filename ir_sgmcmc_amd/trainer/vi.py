@@ -252,11 +252,14 @@ class VIMixin:
     @torch.no_grad()
     def _metrics_init(self, fixed, moving):
         """trainer.py:550-567, the metrics only: ASD and Dice of the unregistered pair at step 0 -- and, with
-        trainer.image_similarity on, its intensity similarity, and with trainer.landmarks its TRE, which need no segmentation"""
+        trainer.image_similarity on, its intensity similarity, with trainer.landmarks its TRE and with
+        trainer.local_similarity its local similarity, which need no segmentation"""
         if self.similarity_options is not None:
             self._log_similarity_unregistered(fixed, moving)
         if self.landmark_options is not None:
             self._log_landmarks_unregistered(fixed)
+        if self.local_options is not None:
+            self._log_local_unregistered(fixed, moving)
         if 'seg' not in fixed or 'seg' not in moving or not self.structures_dict:
             return
         self.writer.set_step(0)

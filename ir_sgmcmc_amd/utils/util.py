@@ -298,6 +298,20 @@ def calc_image_similarity(fixed, moving, mask=None, bins=64, fixed_range=None, m
     return [{k: int(x) if j < 3 else x for j, (k, x) in enumerate(zip(_ops.SIMILARITY_COLUMNS, row))} for row in stats]
 
 
+def local_similarity_rows(stats):
+    """the (C,7) stats of ops.local_similarity -> one dict of Python numbers per chain, keyed by ops.LOCAL_COLUMNS ('n', 'n_flat',
+    'n_nonfinite' as ints; 'lncc_mean', 'lncc_min', 'ssim_mean', 'ssim_min' as floats); one host read-back"""
+    return [{k: int(x) if j < 3 else x for j, (k, x) in enumerate(zip(_ops.LOCAL_COLUMNS, row))} for row in stats.tolist()]
+
+
+@torch.no_grad()
+def calc_local_similarity(fixed, moving, mask=None, radius=2, fixed_range=None, moving_range=None):
+    """Statistics of the local similarity maps of the fixed image and a (warped) moving image (absent in the reference): fixed
+    (1 or C,1,D,H,W), moving (C,1,D,H,W) float32 on the device, mask (1,1,D,H,W) bool / uint8 or None, radius in 1 .. 4; the
+    ranges as ops.local_similarity takes them.  -> one dict per chain (local_similarity_rows); no map is written."""
+    return local_similarity_rows(_ops.local_similarity(fixed, moving, mask, radius, fixed_range, moving_range, want=())['stats'])
+
+
 def rescale_residuals(res, mask, data_loss):
     """VD-rescaled residual x = sum_k r_k (z / sigma_k)^2 (utils/util.py:330-347).  The reference obtains it as
     sum_k s_k * d(-log p)/d(s_k) with a nested backward; the closed form with the responsibilities r_k is the same number."""
