@@ -117,7 +117,8 @@ int irs_log_det_jacobian(const float* transformation, float* log_det, long long*
  * seg_fixed: (Cf,1,D,H,W) int16, Cf in {1, C}; seg_moving: (C,1,D,H,W) int16; labels: n_labels (<= IRS_MAX_LABELS) HOST ints.
  * Pair p = c * n_labels + l.  Two steps with one read-back in between:
  *  1. irs_label_boxes: boxes (device, n_pairs x 6 int32) = {zmin, ymin, xmin, zmax, ymax, xmax} (inclusive) of the voxels
- *     labelled labels[l] in seg_fixed[c] or seg_moving[c]; zmin > zmax when there are none.
+ *     labelled labels[l] in seg_fixed[c] or seg_moving[c]; zmin > zmax when there are none.  Every dim >= 1 (the distance
+ *     calls below need dims of at least 2, the surface posterior takes the boxes of a thinner volume).
  *  2. the caller copies the boxes to the host; irs_surface_distance_workspace sizes the workspace from that copy;
  *     irs_label_surface_distance takes it (HOST pointer, validated) and writes, per pair, counts[2p] = |A|, counts[2p+1] = |B|
  *     (A, B: contours of the label in seg_fixed / seg_moving) and sums[2p] = sum over A of the distance to B, sums[2p+1] = sum
@@ -153,6 +154,43 @@ int irs_label_hausdorff_distance(const int16_t* seg_fixed, int Cf, const int16_t
                                  int n_labels, const float* spacing, const int32_t* boxes, void* workspace,
                                  size_t workspace_bytes, const double* percentiles, int Q, long long* counts, double* sums,
                                  double* hd, double* hd_pct, int C, int D, int H, int W, void* stream);
+
+/* Surface posterior (absent in the reference): where on the boundary of a structure the chain is unsure, and whether the warped
+ * structure is too large or too small there.  At every voxel x of the contour of label l in the shared fixed map, chain c of a
+ * recorded step gives the sample s_c(x) = sign * (float)sqrt((double)d2): d2 the float32 squared distance of the transform
+ * above from x to the nearest contour voxel of l in seg_moving[c]; sign -1 where seg_moving[c](x) == l (the fixed surface lies
+ * inside the warped structure), +1 otherwise; s = 0 where d2 == 0.  A chain whose map holds no voxel of l gives no sample.
+ * State: mean, m2 (D,H,W) float32 and count (D,H,W) int32, 12 bytes per voxel (a voxel has one fixed label); zero before the
+ * first update.  Every dim >= 1, < 2^30 voxels.
+ *  - irs_surface_posterior_update: seg_fixed (1,1,D,H,W) int16, seg_moving (C,1,D,H,W) int16, C in 1 .. IRS_MAX_CHAINS; labels:
+ *    1 .. IRS_MAX_LABELS distinct HOST ints; spacing as above; boxes: the HOST copy of irs_label_boxes(seg_fixed, Cf = 1, ...);
+ *    irs_surface_posterior_workspace sizes the workspace from it (the bytes of irs_hausdorff_workspace with Q = 0).  At every
+ *    fixed-contour voxel of a listed label, for the chains with a sample in ascending order:
+ *    k = ++count; delta = s - mean; mean = mean + delta / (float)k; m2 = m2 + delta * (s - mean), every operation rounded once
+ *    to float32, none contracted.  Other voxels are never touched.  A gather: each thread owns its voxel, no atomics; two calls
+ *    on the same inputs are bit-identical.  Blocking only for the upload of the per-pair table.  count must not pass INT32_MAX.
+ *  - irs_surface_posterior_finalize: bias, std (D,H,W) float32, written at every voxel: bias = mean, NaN where count == 0;
+ *    std = sqrtf(max(m2, 0) / (float)(count - 1)), NaN where count < 2.  mask (D,H,W) uint8 or NULL (the whole volume).
+ *    Per label, over the voxels of its fixed contour inside the mask: isummary (n_labels, IRS_SURFACE_SUMMARY_INTS) int64
+ *    {contour voxels, voxels with count >= 1, voxels with count >= 2, then per level q < n_levels the voxels with count >= 2
+ *    and |bias| <= z[q] * std, compared in double; the columns of the levels not asked for are 0}; fsummary (n_labels,
+ *    IRS_SURFACE_SUMMARY_FLOATS) doubles {sum bias, sum |bias|, sum bias^2, max |bias| over the voxels with count >= 1; sum std,
+ *    max std over those with count >= 2}, of the stored float32 values; a maximum nothing entered is -inf.  z: n_levels in
+ *    0 .. IRS_SURFACE_MAX_LEVELS HOST doubles, finite and > 0: the half-width of a normal band in standard deviations.  ws:
+ *    IRS_SURFACE_WS_BYTES of device memory.  Deterministic (fixed-order sums, no float atomics); no host sync. */
+#define IRS_SURFACE_MAX_LEVELS 4
+#define IRS_SURFACE_SUMMARY_INTS 7
+#define IRS_SURFACE_SUMMARY_FLOATS 6
+#define IRS_SURFACE_MAX_BLOCKS 512 /* rows of per-block partials per label in the workspace */
+#define IRS_SURFACE_WS_BYTES (IRS_MAX_LABELS * IRS_SURFACE_MAX_BLOCKS * (IRS_SURFACE_SUMMARY_INTS + IRS_SURFACE_SUMMARY_FLOATS) * 8)
+int irs_surface_posterior_workspace(const int32_t* boxes, int n_pairs, int D, int H, int W, size_t* bytes);
+int irs_surface_posterior_update(const int16_t* seg_fixed, const int16_t* seg_moving, const int32_t* labels, int n_labels,
+                                 const float* spacing, const int32_t* boxes, void* workspace, size_t workspace_bytes, float* mean,
+                                 float* m2, int32_t* count, int C, int D, int H, int W, void* stream);
+int irs_surface_posterior_finalize(const int16_t* seg_fixed, const int32_t* labels, int n_labels, const float* mean, const float* m2,
+                                   const int32_t* count, const uint8_t* mask, const double* z, int n_levels, float* bias, float* std,
+                                   long long* isummary, double* fsummary, void* ws, size_t ws_bytes, int D, int H, int W,
+                                   void* stream);
 
 /* Split-R-hat of a vector field over chains (absent in the reference; Gelman et al., BDA3 section 11.4), from online moments.
  * Layouts: x (C,3,D,H,W) fp32; mean / m2 (2,C,3,D,H,W) fp32, the Welford state of each half of each chain's samples.

@@ -37,6 +37,8 @@ IRS_LOCAL_MAX_RADIUS, IRS_LOCAL_STATS, IRS_LOCAL_MAX_BLOCKS = 4, 7, 1024
 IRS_LOCAL_WS_BYTES = IRS_MAX_CHAINS * IRS_LOCAL_MAX_BLOCKS * IRS_LOCAL_STATS * 8
 IRS_LOCAL_MAP_SUMMARY_INTS, IRS_LOCAL_MAP_SUMMARY_FLOATS = 2, 3
 IRS_LOCAL_MAP_WS_BYTES = 1024 * (IRS_LOCAL_MAP_SUMMARY_INTS + IRS_LOCAL_MAP_SUMMARY_FLOATS) * 8
+IRS_SURFACE_MAX_LEVELS, IRS_SURFACE_SUMMARY_INTS, IRS_SURFACE_SUMMARY_FLOATS, IRS_SURFACE_MAX_BLOCKS = 4, 7, 6, 512
+IRS_SURFACE_WS_BYTES = IRS_MAX_LABELS * IRS_SURFACE_MAX_BLOCKS * (IRS_SURFACE_SUMMARY_INTS + IRS_SURFACE_SUMMARY_FLOATS) * 8
 IRS_DATA_GMM_LCC, IRS_DATA_SSD = 0, 1
 IRS_REG_L2, IRS_REG_LOGNORMAL, IRS_REG_STUDENT, IRS_REG_LOGNORMAL_L2 = 0, 1, 2, 3
 
@@ -156,6 +158,10 @@ SIGNATURES = {
     'irs_hausdorff_workspace': [_I32P, _I, _I, _I, _I, _I, C.POINTER(C.c_size_t)],
     'irs_label_hausdorff_distance': [_P, _I, _P, _I32P, _I, C.POINTER(C.c_float), _I32P, _P, C.c_size_t, C.POINTER(C.c_double), _I,
                                      _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    'irs_surface_posterior_workspace': [_I32P, _I, _I, _I, _I, C.POINTER(C.c_size_t)],
+    'irs_surface_posterior_update': [_P, _P, _I32P, _I, C.POINTER(C.c_float), _I32P, _P, C.c_size_t, _P, _P, _P, _I, _I, _I, _I, _P],
+    'irs_surface_posterior_finalize': [_P, _I32P, _I, _P, _P, _P, _P, C.POINTER(C.c_double), _I, _P, _P, _P, _P, _P, C.c_size_t,
+                                       _I, _I, _I, _P],
     'irs_chain_moments_update': [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     'irs_split_rhat_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
     'irs_split_rhat': [_P, _P, _I, _I, _P, C.c_float, C.c_float, _P, _P, _P, C.c_size_t, _I, _I, _I, _P],

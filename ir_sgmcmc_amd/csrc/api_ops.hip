@@ -345,8 +345,12 @@ struct SurfLayout {
     size_t plan_off = 0, partials_off = 0, memb_off = 0, ga_off = 0, gb_off = 0, env_off[3] = {0, 0, 0}, bytes = 0;
 };
 
-static int surface_layout(const int32_t* boxes, int P, int D, int H, int W, SurfLayout* out) {
-    if (!boxes || P < 1 || !dims_ok(1, D, H, W)) return fail("irs_surface_distance: bad boxes / dims");
+// the volume of a call on label maps alone: dims of at least 1 (a map may be one row of voxels), < 2^30 voxels
+static bool label_dims_ok(int D, int H, int W) { return D >= 1 && H >= 1 && W >= 1 && (int64_t)D * H * W < ((int64_t)1 << 30); }
+
+// thin: dims of 1 are taken (the surface posterior; the distance calls keep the rule of the transition, dims of at least 2)
+static int surface_layout(const int32_t* boxes, int P, int D, int H, int W, SurfLayout* out, bool thin = false) {
+    if (!boxes || P < 1 || !(thin ? label_dims_ok(D, H, W) : dims_ok(1, D, H, W))) return fail("irs_surface_distance: bad boxes / dims");
     SurfLayout& s = *out;
     s.plan.assign((size_t)P + 1, SurfPair{});
     const int dims[3] = {D, H, W};
@@ -405,6 +409,15 @@ static bool labels_ok(const char* who, const int32_t* labels, int n) {
     return ok || !fail("%s: 1..%d labels in the int16 range", who, IRS_MAX_LABELS);
 }
 
+// 1 .. IRS_MAX_LABELS distinct labels in the int16 range
+static bool distinct_labels_ok(const char* who, const int32_t* labels, int K) {
+    if (!labels_ok(who, labels, K)) return false;
+    for (int i = 0; i < K; ++i)
+        for (int j = 0; j < i; ++j)
+            if (labels[i] == labels[j]) return !fail("%s: label %d appears twice", who, labels[i]);
+    return true;
+}
+
 static SurfLabels surf_labels(const int32_t* labels, int n) {
     SurfLabels lab = {};
     memcpy(lab.v, labels, sizeof(int32_t) * n);
@@ -447,7 +460,7 @@ static SurfPassArgs surf_pass_args(uint8_t* ws, const SurfLayout& s) {
 
 int irs_label_boxes(const int16_t* seg_fixed, int Cf, const int16_t* seg_moving, const int32_t* labels, int n_labels,
                     int32_t* boxes, int C, int D, int H, int W, void* stream) {
-    if (!seg_fixed || !seg_moving || !boxes || !dims_ok(C, D, H, W) || !chain_count_ok(C) || !broadcast_ok(Cf, C))
+    if (!seg_fixed || !seg_moving || !boxes || !label_dims_ok(D, H, W) || !chain_count_ok(C) || !broadcast_ok(Cf, C))
         return fail("irs_label_boxes: bad arguments");
     if (!labels_ok(__func__, labels, n_labels)) return 1;
     const Vol vol = make_vol(D, H, W);
@@ -499,11 +512,11 @@ struct HdLayout {
     size_t maxpart_off = 0, hist_off = 0, hist_bytes = 0, prefix_off = 0, rank_off = 0, bytes = 0;
 };
 
-static int hausdorff_layout(const int32_t* boxes, int P, int Q, int D, int H, int W, HdLayout* out) {
+static int hausdorff_layout(const int32_t* boxes, int P, int Q, int D, int H, int W, HdLayout* out, bool thin = false) {
     if (Q < 0 || Q > IRS_HAUSDORFF_MAX_PERCENTILES)
         return fail("irs_label_hausdorff_distance: 0..%d percentiles, got %d", IRS_HAUSDORFF_MAX_PERCENTILES, Q);
     HdLayout& h = *out;
-    if (surface_layout(boxes, P, D, H, W, &h.s)) return 1;
+    if (surface_layout(boxes, P, D, H, W, &h.s, thin)) return 1;
     int64_t largest = 1;
     for (int p = 0; p < P; ++p) largest = std::max(largest, h.s.plan[p + 1].vox - h.s.plan[p].vox);
     h.slices = (int)std::min<int64_t>((largest + kHdSliceVoxels - 1) / kHdSliceVoxels, kHdMaxSlices);
@@ -570,6 +583,63 @@ int irs_label_hausdorff_distance(const int16_t* seg_fixed, int Cf, const int16_t
     g.hd = hd;
     g.hd_pct = hd_pct;
     launch_hausdorff_select(g, st);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
+// surface posterior (metric_kernels.hip pass D with KEEP + surface_kernels.hip)
+// ================================================================================================
+int irs_surface_posterior_workspace(const int32_t* boxes, int n_pairs, int D, int H, int W, size_t* bytes) {
+    if (!bytes) return fail("irs_surface_posterior_workspace: null argument");
+    HdLayout h;
+    if (hausdorff_layout(boxes, n_pairs, 0, D, H, W, &h, true)) return 1;
+    *bytes = h.bytes;
+    return 0;
+}
+
+int irs_surface_posterior_update(const int16_t* seg_fixed, const int16_t* seg_moving, const int32_t* labels, int n_labels,
+                                 const float* spacing, const int32_t* boxes, void* workspace, size_t workspace_bytes, float* mean,
+                                 float* m2, int32_t* count, int C, int D, int H, int W, void* stream) {
+    if (!seg_fixed || !seg_moving || !spacing || !workspace || !mean || !m2 || !count || !label_dims_ok(D, H, W))
+        return fail("irs_surface_posterior_update: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!distinct_labels_ok(__func__, labels, n_labels)) return 1;
+    if (!positive3(__func__, "spacing", spacing)) return 1;
+    HdLayout h;
+    if (hausdorff_layout(boxes, C * n_labels, 0, D, H, W, &h, true)) return 1;
+    if (!workspace_ok(__func__, workspace_bytes, h.bytes, "irs_surface_posterior_workspace")) return 1;
+    const hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = (uint8_t*)workspace;
+    if (upload_plan(ws, h.s, st)) return 1;
+    SurfPassArgs a = surf_pass_args(ws, h.s);
+    a.maxpart = (uint32_t*)(ws + h.maxpart_off);  // pass D keeps the squared distances
+    const Vol vol = make_vol(D, H, W);
+    const SurfLabels lab = surf_labels(labels, n_labels);
+    launch_surface_distance(seg_fixed, 0, seg_moving, lab, n_labels, spacing, a, nullptr, nullptr, vol, st);
+    launch_surface_posterior_update(seg_fixed, seg_moving, lab, n_labels, a.plan, a.gB, C, mean, m2, count, vol, st);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_surface_posterior_finalize(const int16_t* seg_fixed, const int32_t* labels, int n_labels, const float* mean, const float* m2,
+                                   const int32_t* count, const uint8_t* mask, const double* z, int n_levels, float* bias, float* std,
+                                   long long* isummary, double* fsummary, void* ws, size_t ws_bytes, int D, int H, int W,
+                                   void* stream) {
+    if (!seg_fixed || !mean || !m2 || !count || !bias || !std || !isummary || !fsummary || !ws || !label_dims_ok(D, H, W))
+        return fail("irs_surface_posterior_finalize: bad arguments");
+    if (!distinct_labels_ok(__func__, labels, n_labels)) return 1;
+    if (n_levels < 0 || n_levels > IRS_SURFACE_MAX_LEVELS || (n_levels > 0 && !z))
+        return fail("irs_surface_posterior_finalize: 0..%d coverage levels with their z, got %d", IRS_SURFACE_MAX_LEVELS, n_levels);
+    SurfLevels lv = {};
+    lv.n = n_levels;
+    for (int q = 0; q < n_levels; ++q) {
+        if (!(z[q] > 0.0) || !isfinite(z[q])) return fail("irs_surface_posterior_finalize: z[%d] = %g, a finite value > 0 needed", q, z[q]);
+        lv.z[q] = z[q];
+    }
+    if (!workspace_ok(__func__, ws_bytes, (size_t)IRS_SURFACE_WS_BYTES, "IRS_SURFACE_WS_BYTES")) return 1;
+    launch_surface_posterior_finalize(seg_fixed, surf_labels(labels, n_labels), n_labels, mean, m2, count, mask, lv, bias, std,
+                                      isummary, fsummary, ws, make_vol(D, H, W), (hipStream_t)stream);
     LAUNCH_CHECK();
     return 0;
 }
@@ -642,18 +712,6 @@ int irs_split_ess(const float* mean, const float* m2, const float* vsum, int C, 
 // ================================================================================================
 // posterior label maps (label_kernels.hip)
 // ================================================================================================
-
-// the volume of a label-posterior call: dims of at least 1 (a record may be one row of voxels), < 2^30 voxels
-static bool label_dims_ok(int D, int H, int W) { return D >= 1 && H >= 1 && W >= 1 && (int64_t)D * H * W < ((int64_t)1 << 30); }
-
-// 1 .. IRS_MAX_LABELS distinct labels in the int16 range
-static bool distinct_labels_ok(const char* who, const int32_t* labels, int K) {
-    if (!labels_ok(who, labels, K)) return false;
-    for (int i = 0; i < K; ++i)
-        for (int j = 0; j < i; ++j)
-            if (labels[i] == labels[j]) return !fail("%s: label %d appears twice", who, labels[i]);
-    return true;
-}
 
 static size_t label_update_ws(int C, int K, int64_t V) { return sizeof(int32_t) * (size_t)C * K * label_update_partials_blocks(V); }
 

@@ -131,7 +131,8 @@ void launch_surface_boxes(const int16_t* fixed, int64_t f_stride, const int16_t*
                           int32_t* boxes, int C, Vol vol, hipStream_t st);
 // pass W (contours + 1-D distances), passes H and D (lower envelopes; D ends in the reduction) and the per-pair reduction.
 // env_scratch: NULL -> the envelopes of a pass live in LDS (its longest line <= kSurfLdsLine); else env_slots slots of
-// 3 * line * lanes floats each.
+// 3 * line * lanes floats each.  counts == NULL: the passes alone, without the per-pair reduction (surface_kernels.hip reads
+// the squared distances pass D kept).
 struct SurfPassArgs {
     const SurfPair* plan;
     int P;
@@ -171,6 +172,22 @@ struct HdArgs {
     double* hd_pct;           // (Q,P,2)
 };
 void launch_hausdorff_select(const HdArgs& a, hipStream_t st);
+
+// ---- surface_kernels.hip: surface posterior (absent in the reference): per fixed-contour voxel the Welford moments of the signed
+// distance to every chain's moving contour of the same label, from the squared distances pass D kept (maxpart != NULL above)
+// fixed (V) int16 shared by the chains, moving (C,V) int16; plan / gB: of the passes just run on the same maps with the pairs
+// c * L + l; mean / m2 (V) float32, count (V) int32, touched at the fixed-contour voxels of the listed labels only
+void launch_surface_posterior_update(const int16_t* fixed, const int16_t* moving, const SurfLabels& lab, int L, const SurfPair* plan,
+                                     const float* gB, int C, float* mean, float* m2, int32_t* count, Vol vol, hipStream_t st);
+struct SurfLevels {
+    double z[IRS_SURFACE_MAX_LEVELS];
+    int n;
+};
+// bias / std (V) float32; isummary (L, IRS_SURFACE_SUMMARY_INTS) int64, fsummary (L, IRS_SURFACE_SUMMARY_FLOATS) doubles;
+// ws: IRS_SURFACE_WS_BYTES (per label the partials of at most IRS_SURFACE_MAX_BLOCKS blocks)
+void launch_surface_posterior_finalize(const int16_t* fixed, const SurfLabels& lab, int L, const float* mean, const float* m2,
+                                       const int32_t* count, const uint8_t* mask, const SurfLevels& lv, float* bias, float* std,
+                                       long long* isummary, double* fsummary, void* ws, Vol vol, hipStream_t st);
 
 // ---- diag_kernels.hip: split-R-hat and split ESS over chains (absent in the reference; BDA3 sections 11.4-11.5)
 // Welford update of one half's (mean, m2) with the sample x, all flat arrays of n floats; k = samples in the half after this one

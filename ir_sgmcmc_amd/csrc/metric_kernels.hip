@@ -17,6 +17,7 @@
 
 #include <algorithm>
 
+#include "contour_device.h"
 #include "kernels.h"
 
 namespace irs {
@@ -24,15 +25,6 @@ namespace {
 
 constexpr float kInf = __builtin_huge_valf();
 constexpr int kNone = INT_MAX;  // 1-D distance when the line holds no contour voxel
-
-// sitk.LabelContour with face connectivity: a voxel of `lab` with an in-volume face neighbour that is not `lab`
-__device__ __forceinline__ bool on_contour(const int16_t* __restrict__ s, int z, int y, int x, int lab, const Vol& vol) {
-    const int64_t HW = (int64_t)vol.H * vol.W;
-    const int64_t i = z * HW + (int64_t)y * vol.W + x;
-    if (s[i] != lab) return false;
-    return (x > 0 && s[i - 1] != lab) || (x + 1 < vol.W && s[i + 1] != lab) || (y > 0 && s[i - vol.W] != lab) ||
-           (y + 1 < vol.H && s[i + vol.W] != lab) || (z > 0 && s[i - HW] != lab) || (z + 1 < vol.D && s[i + HW] != lab);
-}
 
 // the pair whose task range of `pass` holds task t (empty pairs own no task)
 __device__ __forceinline__ int find_pair(const SurfPair* __restrict__ plan, int P, int64_t t, int pass) {
@@ -311,7 +303,7 @@ void launch_surface_distance(const int16_t* fixed, int64_t f_stride, const int16
             else hipLaunchKernelGGL((surf_pass_fh_kernel<false, true>), grid, dim3(kWave), 0, st, a, w2);
         }
     }
-    hipLaunchKernelGGL(surf_reduce_kernel, dim3(a.P), dim3(kBlock), 0, st, a.partials, a.plan, counts, sums);
+    if (counts) hipLaunchKernelGGL(surf_reduce_kernel, dim3(a.P), dim3(kBlock), 0, st, a.partials, a.plan, counts, sums);
 }
 
 }  // namespace irs

@@ -55,6 +55,13 @@ The local similarity (LocalSimilarity, local_similarity_options) is the one map 
 the transformation: at a logged step ops.local_similarity gives the windowed LNCC and SSIM of the fixed and the warped moving
 image, and at a recorded step the LNCC maps are folded into a per-voxel streaming mean, minimum and count
 (ops.local_similarity_update), 12 * D * H * W bytes whatever the number of records.
+
+The surface posterior (SurfacePosterior, surface_posterior_options) is the surface counterpart of the landmark posterior, with
+the fixed segmentation as the truth: at a recorded step every voxel of the fixed contour of a structure takes each chain's
+signed distance to the same structure's contour in the warped moving segmentation (ops.surface_posterior_update, on the
+distances of the Hausdorff call) into a Welford mean and M2, 12 * D * H * W bytes whatever the number of records or structures;
+at the end ops.surface_posterior_finalize gives the bias and spread maps and, per structure, the mean signed distance, the
+spread and how often the normal band of the samples holds the fixed boundary.
 """
 import math
 import numbers
@@ -1299,5 +1306,143 @@ class LocalSimilarity(_Recorder):
                                  f'({self.dims})')
         self.mean.copy_(sd['mean'])
         self.low.copy_(sd['low'])
+        self.count.copy_(sd['count'])
+        self.records = int(sd['records'])
+
+
+SURFACE_OPTION_KEYS = ('period', 'coverage', 'save')
+SURFACE_DEFAULTS = {'coverage': (0.5, 0.9, 0.95), 'save': True}
+SURFACE_MAX_LEVELS = 4  # IRS_SURFACE_MAX_LEVELS
+SURFACE_METRICS = ('bias', 'abs_bias', 'std')  # logged per structure, before the coverage levels
+SURFACE_COUNTS = ('contour_voxels', 'sampled_voxels', 'spread_voxels')  # ops.SURFACE_INT_COLUMNS
+
+
+def _surface_coverage(levels, what):
+    if isinstance(levels, (str, bytes)) or not hasattr(levels, '__len__'):
+        raise ValueError(f'{what}: coverage must be a list of levels, got {levels!r}')
+    if any(not _number(p) for p in levels):
+        raise ValueError(f'{what}: coverage must be numbers, got {list(levels)!r}')
+    levels = tuple(float(p) for p in levels)
+    if len(levels) > SURFACE_MAX_LEVELS:
+        raise ValueError(f'{what}: 0 to {SURFACE_MAX_LEVELS} coverage levels, got {len(levels)}')
+    if not all(0.0 < p < 1.0 for p in levels) or any(b <= a for a, b in zip(levels, levels[1:])):
+        raise ValueError(f'{what}: coverage must be strictly increasing in (0,1), got {list(levels)}')
+    return levels
+
+
+def surface_posterior_options(cfg_trainer):
+    """`trainer.surface_posterior` -> None when off, else {'period': P, 'coverage': (...), 'save': bool}.
+    Absent / false / null: off.  true: recorded every log_period_MCMC-th step after the burn-in, coverage at 0.5, 0.9 and 0.95,
+    the maps written.  {"period": P, "coverage": [..], "save": bool} sets any of them.  Refuses unknown keys, a non-integer P or
+    P < 1, a coverage that is not 0 to 4 strictly increasing numbers in (0,1), a non-bool save, a config that records no step
+    (no_samples_MCMC // P < 1) and one that would record more than 2^31 - 1 samples."""
+    what = 'trainer.surface_posterior'
+
+    def own_keys(opt):
+        own = {**SURFACE_DEFAULTS, **{k: v for k, v in opt.items() if k != 'period'}}
+        if not isinstance(own['save'], bool):
+            raise ValueError(f'{what}.save must be true or false, got {own["save"]!r}')
+        return {'coverage': _surface_coverage(own['coverage'], what), 'save': own['save']}
+
+    return _record_options(cfg_trainer, 'surface_posterior', SURFACE_OPTION_KEYS, '{"period": P, "coverage": [..], "save": bool}',
+                           MAX_RECORDS, 'the sample count holds at most {}', own_keys)
+
+
+def surface_coverage_key(level):
+    """0.5 -> 'coverage_50', 0.95 -> 'coverage_95', 0.999 -> 'coverage_99.9'"""
+    return f'coverage_{round(100.0 * level, 6):g}'
+
+
+def surface_metric_names(options, structures):
+    """the metric names the option adds, written at the end of the run"""
+    keys = list(SURFACE_METRICS) + [surface_coverage_key(q) for q in options['coverage']]
+    return [f'MCMC/surface/{k}/{s}' for k in keys for s in structures]
+
+
+def surface_summary(isummary, fsummary, names, levels, n):
+    """the per-structure summary of the surface posterior from ops.surface_posterior_finalize's columns (host rows of ints /
+    floats, one per structure): -> {'records': n, 'structures': {name: {'bias' (mean signed distance), 'abs_bias', 'rms_bias',
+    'max_abs_bias' over the contour voxels with a sample; 'std', 'max_std', 'coverage_XX' (the fraction whose normal band of
+    that level holds the fixed boundary) over those with two; 'contour_voxels', 'sampled_voxels', 'spread_voxels'}}}.  NaN
+    where the structure has no contour voxel with enough samples."""
+    nan = float('nan')
+    structures = {}
+    for name, irow, frow in zip(names, isummary, fsummary):
+        irow = [int(x) for x in irow]
+        b_sum, ab_sum, b2_sum, ab_max, sd_sum, sd_max = (float(x) for x in frow)
+        contour, some, two = irow[:3]
+        st = {'bias': _nan_div(b_sum, some), 'abs_bias': _nan_div(ab_sum, some),
+              'rms_bias': math.sqrt(b2_sum / some) if some else nan, 'max_abs_bias': ab_max if some else nan,
+              'std': _nan_div(sd_sum, two), 'max_std': sd_max if two else nan}
+        for q, inside in zip(levels, irow[3:]):
+            st[surface_coverage_key(q)] = _nan_div(float(inside), two)
+        st.update(contour_voxels=contour, sampled_voxels=some, spread_voxels=two)
+        structures[name] = st
+    return {'records': int(n), 'structures': structures}
+
+
+class SurfacePosterior(_Recorder):
+    """Per voxel of the fixed contour of every structure of `structures_dict`, the Welford moments of the signed distance to
+    the same structure's contour in the recorded warps of the moving segmentation (ops.surface_posterior_update): `mean`, `m2`
+    (D,H,W) float32 and `count` (D,H,W) int32 on the device, 12 D H W bytes whatever the number of records or structures (a
+    voxel has one fixed label).  The mean is negative where the warped structure covers the fixed boundary (too large there),
+    positive where it falls short; the spread says where on the boundary the chain is unsure, in the unit of `spacing`.
+    `record(seg_warped)` takes the (C,1,D,H,W) int16 maps of one step, chains in order; `finalize(mask)` gives the two maps,
+    NaN off the contours, and the summary per structure."""
+    noun = 'surface posterior'
+
+    def __init__(self, seg_fixed, structures_dict, spacing, device):
+        self.names = list(structures_dict)
+        self.labels = [int(structures_dict[k]) for k in self.names]
+        if not 1 <= len(self.labels) <= 64:
+            raise ValueError(f'surface posterior: 1 to 64 structures, got {len(self.labels)}')
+        if len(set(self.labels)) != len(self.labels):
+            raise ValueError(f'surface posterior: the label values {self.labels} are not distinct')
+        self.spacing = tuple(float(x) for x in (spacing.tolist() if hasattr(spacing, 'tolist') else spacing))
+        if len(self.spacing) != 3 or not all(math.isfinite(x) and x > 0.0 for x in self.spacing):
+            raise ValueError(f'surface posterior: three finite spacings > 0, got {self.spacing}')
+        if seg_fixed.dim() == 3:
+            seg_fixed = seg_fixed[None, None]
+        if seg_fixed.dim() != 5 or tuple(seg_fixed.shape[:2]) != (1, 1) or seg_fixed.dtype != torch.int16:
+            raise ValueError(f'surface posterior: the fixed segmentation must be a (1,1,D,H,W) int16 volume, got '
+                             f'{seg_fixed.dtype} {tuple(seg_fixed.shape)}')
+        self.device = device
+        self.seg_fixed = seg_fixed.to(device).contiguous()
+        self.dims = tuple(int(d) for d in seg_fixed.shape[2:])
+        self.mean = torch.zeros(self.dims, device=device, dtype=torch.float32)
+        self.m2 = torch.zeros(self.dims, device=device, dtype=torch.float32)
+        self.count = torch.zeros(self.dims, device=device, dtype=torch.int32)
+
+    def _update(self, seg_warped):
+        ops.surface_posterior_update(self.seg_fixed, seg_warped.contiguous(), self.labels, self.spacing, self.mean, self.m2,
+                                     self.count)
+
+    def finalize(self, mask=None, coverage=SURFACE_DEFAULTS['coverage']):
+        """-> (bias, std (D,H,W) float32 on the device, NaN off the contours, summary dict of surface_summary over the mask).  One
+        device-to-host read."""
+        self._need_records('finalize')
+        coverage = _surface_coverage(coverage, 'surface posterior')
+        bias, std, isum, fsum = ops.surface_posterior_finalize(self.seg_fixed, self.labels, self.mean, self.m2, self.count,
+                                                               coverage, _bool_mask(mask, self.device))
+        ih, fh = _host_summary(isum.reshape(-1), fsum.reshape(-1))
+        ni, nf = isum.shape[1], fsum.shape[1]
+        rows = range(len(self.labels))
+        summary = surface_summary([ih[j * ni:(j + 1) * ni] for j in rows], [fh[j * nf:(j + 1) * nf] for j in rows], self.names,
+                                  coverage, self.records)
+        return bias, std, summary
+
+    def state_dict(self):
+        return {'records': self.records, 'labels': list(self.labels), 'mean': self.mean.detach().cpu(), 'm2': self.m2.detach().cpu(),
+                'count': self.count.detach().cpu()}
+
+    def load_state_dict(self, sd):
+        if [int(x) for x in sd['labels']] != self.labels:
+            raise ValueError(f'surface posterior of labels {list(sd["labels"])} does not match this run ({self.labels})')
+        for name in ('mean', 'm2', 'count'):
+            if tuple(sd[name].shape) != self.dims:
+                raise ValueError(f'surface posterior state of shape {tuple(sd[name].shape)} ({name}) does not match this run '
+                                 f'({self.dims})')
+        self.mean.copy_(sd['mean'])
+        self.m2.copy_(sd['m2'])
         self.count.copy_(sd['count'])
         self.records = int(sd['records'])

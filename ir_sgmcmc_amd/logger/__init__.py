@@ -266,3 +266,13 @@ def save_local_similarity_of_mean(logger, save_dirs, spacing, lncc, ssim, model=
         im, undefined = _nan_to_zero(im)
         logger.info(f'{model}_{name}_of_mean: {undefined} undefined voxels written as 0')
         save_im_to_disk(im, path.join(folder, f'{model}_{name}_of_mean.nii.gz'), spacing)
+
+
+def save_surface_posterior(logger, save_dirs, spacing, bias, std, model='MCMC'):
+    """the surface posterior (absent in the reference): samples/{model}_surface_bias.nii.gz and samples/{model}_surface_std.nii.gz
+    (float32).  The maps live on the contours of the fixed structures: NaN everywhere else, and in the std map where a contour
+    voxel has fewer than two samples, written as NaN so that a viewer shows the surfaces alone."""
+    folder = _folder(save_dirs, 'samples')
+    for name, im in (('surface_bias', bias), ('surface_std', std)):
+        logger.info(f'{model}_{name}: {int(np.isfinite(_np(im)).sum())} contour voxels hold a value, NaN elsewhere')
+        save_im_to_disk(im, path.join(folder, f'{model}_{name}.nii.gz'), spacing)

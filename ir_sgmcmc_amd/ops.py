@@ -307,6 +307,90 @@ def label_hausdorff_distance(seg_fixed, seg_moving, labels, spacing, percentiles
             'hd_pct': hd_pct.max(dim=2).values.view(Q, Cn, n), 'hd_pct_directed': hd_pct.view(Q, Cn, n, 2)}
 
 
+SURFACE_INT_COLUMNS = ('contour_voxels', 'sampled_voxels', 'spread_voxels')  # then one column per coverage level
+SURFACE_FLOAT_COLUMNS = ('bias_sum', 'abs_bias_sum', 'bias_sq_sum', 'abs_bias_max', 'std_sum', 'std_max')
+
+
+def _surface_state(mean, m2, count, shape):
+    for name, t, dtype in (('mean', mean, torch.float32), ('m2', m2, torch.float32), ('count', count, torch.int32)):
+        if tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+            raise L.IrsError(f'{name} must be a {tuple(shape)} {dtype} tensor, got {t.dtype} {tuple(t.shape)}')
+
+
+def _surface_labels(labels):
+    labels = [int(x) for x in labels]
+    return labels, (C.c_int32 * max(len(labels), 1))(*labels)
+
+
+def surface_posterior_update(seg_fixed, seg_moving, labels, spacing, mean, m2, count):
+    """Fold one recorded step into the surface posterior (absent in the reference).  seg_fixed (1,1,D,H,W) int16, the fixed
+    segmentation the chains share; seg_moving (C,1,D,H,W) int16, every chain's warped segmentation; labels: 1 to 64 distinct
+    values; spacing (sx, sy, sz) as label_surface_distance takes it; mean / m2 (D,H,W) float32 and count (D,H,W) int32, zero
+    before the first step, updated in place.  At every voxel of the fixed contour of a listed label each chain whose map holds
+    the label gives the sample s = sign * distance to the nearest voxel of the label's contour in that chain's map, the
+    distances of label_hausdorff_distance; sign -1 where the chain's map has the label at the voxel (the fixed surface lies
+    inside the warped structure: the structure came out too large there), +1 otherwise; 0 on the moving contour itself.  The
+    samples enter the Welford moments in chain order: include/irsgmcmc.h has the recurrence.  Other voxels are never touched.
+    One device-to-host read: the boxes that size the workspace."""
+    lib = L.load()
+    Cn, D, H, W = _dims5(seg_moving, 1)
+    if tuple(seg_fixed.shape) != (1, 1, D, H, W):
+        raise L.IrsError(f'fixed segmentation {tuple(seg_fixed.shape)} does not match the moving one {tuple(seg_moving.shape)}: '
+                         f'(1,1,{D},{H},{W}) expected')
+    _surface_state(mean, m2, count, (D, H, W))
+    f, m = L.dev_ptr(seg_fixed, torch.int16), L.dev_ptr(seg_moving, torch.int16)
+    ptrs = [L.dev_ptr(t) for t in (mean, m2, count)]
+    labels, lab = _surface_labels(labels)
+    sp = [float(x) for x in (spacing.tolist() if hasattr(spacing, 'tolist') else spacing)]
+    if len(sp) != 3:
+        raise L.IrsError(f'spacing must have 3 entries, got {len(sp)}')
+    n = len(labels)
+    P = Cn * n
+    dev = seg_moving.device
+    boxes = torch.empty((max(P, 1), 6), device=dev, dtype=torch.int32)
+    L.check(lib.irs_label_boxes(f, 1, m, lab, n, L.dev_ptr(boxes), Cn, D, H, W, L.stream_ptr()))
+    boxes_h = boxes.cpu()
+    bp = C.cast(C.c_void_p(boxes_h.data_ptr()), C.POINTER(C.c_int32))
+    nbytes = C.c_size_t()
+    L.check(lib.irs_surface_posterior_workspace(bp, P, D, H, W, C.byref(nbytes)))
+    ws = torch.empty(nbytes.value, device=dev, dtype=torch.uint8)
+    L.check(lib.irs_surface_posterior_update(f, m, lab, n, (C.c_float * 3)(*sp), bp, L.dev_ptr(ws), nbytes.value, *ptrs, Cn, D, H, W,
+                                             L.stream_ptr()))
+
+
+def surface_posterior_finalize(seg_fixed, labels, mean, m2, count, levels, mask=None):
+    """The maps and the per-label summary of the surface posterior (absent in the reference).  seg_fixed (1,1,D,H,W) int16; the
+    state of surface_posterior_update; levels: 0 to 4 strictly increasing coverage levels in (0, 1); mask (D,H,W) bool / uint8
+    or None.  -> (bias, std (D,H,W) float32: the mean of the samples, NaN where there is none, and their standard deviation,
+    NaN where there are fewer than two; isummary (L, 3 + 4) int64: SURFACE_INT_COLUMNS, then per level q the voxels with at
+    least two samples and |bias| <= z_q std, z_q = Phi^-1((1 + q) / 2); fsummary (L, 6) float64: SURFACE_FLOAT_COLUMNS), per
+    label over the voxels of its fixed contour inside the mask, on the device.  No host synchronisation."""
+    import statistics
+    lib = L.load()
+    if seg_fixed.dim() != 5 or tuple(seg_fixed.shape[:2]) != (1, 1):
+        raise L.IrsError(f'fixed segmentation must have shape (1,1,D,H,W), got {tuple(seg_fixed.shape)}')
+    D, H, W = seg_fixed.shape[2:]
+    _surface_state(mean, m2, count, (D, H, W))
+    mask = _volume_mask(mask, D, H, W)
+    labels, lab = _surface_labels(labels)
+    levels = [float(q) for q in levels]
+    if len(levels) > L.IRS_SURFACE_MAX_LEVELS or not all(0.0 < q < 1.0 for q in levels) or any(b <= a for a, b in zip(levels, levels[1:])):
+        raise L.IrsError(f'levels must be 0 to {L.IRS_SURFACE_MAX_LEVELS} strictly increasing values in (0,1), got {levels}')
+    z = [statistics.NormalDist().inv_cdf(0.5 * (1.0 + q)) for q in levels]
+    n = len(labels)
+    dev = seg_fixed.device
+    ptrs = [L.dev_ptr(seg_fixed, torch.int16), lab, n, L.dev_ptr(mean), L.dev_ptr(m2), L.dev_ptr(count), L.dev_ptr(mask, torch.uint8, True)]
+    ws = torch.empty(L.IRS_SURFACE_WS_BYTES, device=dev, dtype=torch.uint8)
+    bias = torch.empty((D, H, W), device=dev, dtype=torch.float32)
+    std = torch.empty((D, H, W), device=dev, dtype=torch.float32)
+    isummary = torch.empty((max(n, 1), L.IRS_SURFACE_SUMMARY_INTS), device=dev, dtype=torch.int64)
+    fsummary = torch.empty((max(n, 1), L.IRS_SURFACE_SUMMARY_FLOATS), device=dev, dtype=torch.float64)
+    L.check(lib.irs_surface_posterior_finalize(*ptrs, (C.c_double * max(len(z), 1))(*z), len(z), L.dev_ptr(bias), L.dev_ptr(std),
+                                               L.dev_ptr(isummary), L.dev_ptr(fsummary), L.dev_ptr(ws), L.IRS_SURFACE_WS_BYTES, D, H, W,
+                                               L.stream_ptr()))
+    return bias, std, isummary, fsummary
+
+
 def chain_moments_update(x, mean, m2, half, k):
     """Welford update of half `half` of every chain's split-R-hat moments with the sample x (absent in the reference).
     x (C,3,D,H,W) float32; mean / m2 (2,C,3,D,H,W) float32, updated in place; k = samples in that half after this one."""

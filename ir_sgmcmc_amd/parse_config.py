@@ -16,7 +16,7 @@ from .diagnostics import (COVARIANCE_METRICS, ICE_SPACES, JACOBIAN_METRICS, LABE
                           hausdorff_metric_names, hausdorff_options, image_similarity_metric_names, image_similarity_options,
                           inverse_consistency_options, jacobian_posterior_options, label_posterior_options,
                           landmark_metric_names, landmark_options, local_similarity_metric_names, local_similarity_options,
-                          native_resolution_options)
+                          native_resolution_options, surface_metric_names, surface_posterior_options)
 from .logger import setup_logging
 from .model import distributions as model_distr
 from .model import loss as model_loss
@@ -112,6 +112,9 @@ class ConfigParser:
             for s in self.structures_dict:
                 m += [f'MCMC/seg/{s}/{k}' for k in LABEL_STRUCTURE_METRICS]
             m += [f'MCMC/seg/{k}' for k in ('entropy_mean', 'entropy_max', 'ECE')]
+        surface = surface_posterior_options(self['trainer'])
+        if surface is not None:
+            m += surface_metric_names(surface, self.structures_dict)
         if jacobian_posterior_options(self['trainer']) is not None:
             m += [f'MCMC/jacobian/{k}' for k in JACOBIAN_METRICS]
         if displacement_covariance_options(self['trainer']) is not None:

@@ -22,6 +22,7 @@ from .. import ops
 from ..diagnostics import (COVARIANCE_METRICS, ChainMoments, DisplacementCovariance, DisplacementQuantiles, ICE_SPACES,
                            InverseConsistency, JACOBIAN_METRICS, JacobianPosterior, LABEL_STRUCTURE_METRICS, LANDMARK_METRICS,
                            LOCAL_METRICS, LabelPosterior, LandmarkPair, LandmarkPosterior, LocalSimilarity, QUANTILE_METRICS,
+                           SURFACE_METRICS, SurfacePosterior, surface_coverage_key, surface_posterior_options,
                            diagnostics_period, displacement_covariance_options, displacement_quantiles_options,
                            ess_options, hausdorff_options, image_similarity_options, inverse_consistency_options, is_recorded,
                            jacobian_posterior_options, label_posterior_options, landmark_options, local_similarity_options,
@@ -30,7 +31,7 @@ from ..engine import EngineConfig, TransitionEngine
 from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_quantiles, save_ess,
                       save_field, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_landmarks,
                       save_local_similarity_of_mean, save_local_similarity_posterior, save_native_mean, save_native_sample, save_rhat,
-                      save_sample)
+                      save_sample, save_surface_posterior)
 from ..utils import (calc_DSC_GPU, calc_image_similarity, calc_norm, calc_no_non_diffeomorphic_voxels, init_identity_grid_3D,
                      local_similarity_rows, sample_q_v, transform_coordinates)
 from .vi import VIMixin
@@ -90,6 +91,11 @@ class Trainer(VIMixin, BaseTrainer):
         self.label_options = label_posterior_options(cfg_trainer)
         self._label_posterior = None
         self.label_entropy, self.label_map, self.label_summary = None, None, None
+        # surface posterior of the propagated segmentation (diagnostics.SurfacePosterior): None when trainer.surface_posterior
+        # is off
+        self.surface_options = surface_posterior_options(cfg_trainer)
+        self._surface_posterior = None
+        self.surface_bias, self.surface_std, self.surface_summary = None, None, None
         # Jacobian posterior maps (diagnostics.JacobianPosterior): None when trainer.jacobian_posterior is off
         self.jacobian_options = jacobian_posterior_options(cfg_trainer)
         self._jacobian_posterior = None
@@ -212,13 +218,15 @@ class Trainer(VIMixin, BaseTrainer):
         return self._scalars_cache
 
     def _recorders(self):
-        """the active recorders, in the order they record and finish: moments, labels, Jacobian, covariance, quantiles,
-        inverse consistency, landmarks, local similarity"""
+        """the active recorders, in the order they record and finish: moments, labels, surfaces, Jacobian, covariance,
+        quantiles, inverse consistency, landmarks, local similarity"""
         period = lambda options: options and options['period']
         rows = (('chain_moments', self._chain_moments, self.diagnostics_period, 'convergence_diagnostics', 'chain moments',
                  'displacement', self._finish_diagnostics, 'moving_mask'),
                 ('label_posterior', self._label_posterior, period(self.label_options), 'label_posterior', 'label posterior',
                  'seg_warped', self._finish_label_posterior, 'fixed'),
+                ('surface_posterior', self._surface_posterior, period(self.surface_options), 'surface_posterior',
+                 'surface posterior', 'seg_warped', self._finish_surface_posterior, 'fixed'),
                 ('jacobian_posterior', self._jacobian_posterior, period(self.jacobian_options), 'jacobian_posterior',
                  'Jacobian posterior', 'transformation', self._finish_jacobian_posterior, 'fixed'),
                 ('displacement_covariance', self._displacement_covariance, period(self.covariance_options),
@@ -385,6 +393,11 @@ class Trainer(VIMixin, BaseTrainer):
                 raise ValueError('trainer.label_posterior needs the fixed and the moving segmentation ("seg" in both); '
                                  f'fixed has {sorted(fixed)}, moving has {sorted(moving)}')
             self._label_posterior = LabelPosterior(self.structures_dict, self._outputs['displacement'].shape[2:], self.device)
+        if self.surface_options is not None:
+            if 'seg' not in fixed or 'seg' not in moving:
+                raise ValueError('trainer.surface_posterior needs the fixed and the moving segmentation ("seg" in both); '
+                                 f'fixed has {sorted(fixed)}, moving has {sorted(moving)}')
+            self._surface_posterior = SurfacePosterior(fixed['seg'][:1], self.structures_dict, spacing, self.device)
         if self.jacobian_options is not None:
             self._jacobian_posterior = JacobianPosterior(self._outputs['transformation'].shape[2:], self.device)
         if self.covariance_options is not None:
@@ -619,6 +632,24 @@ class Trainer(VIMixin, BaseTrainer):
             prob = lp.probabilities() if self.label_options['prob_maps'] else None
             save_label_posterior(self.logger, self.config.save_dirs, spacing, self.label_entropy, self.label_map, mask, prob,
                                  lp.names, 'MCMC')
+
+    def _finish_surface_posterior(self, fixed, spacing, save_outputs):
+        """bias and spread maps of the structures' surfaces and their summary per structure -> self.surface_bias / surface_std /
+        surface_summary, the MCMC/surface/* metrics and, with save_outputs and the option's save,
+        samples/MCMC_surface_{bias,std}.nii.gz.  The maps live on the fixed grid, so the summary is over the FIXED mask, as for
+        the label posterior."""
+        sp = self._surface_posterior
+        self.surface_bias, self.surface_std, self.surface_summary = sp.finalize(fixed['mask'][0], self.surface_options['coverage'])
+        keys = list(SURFACE_METRICS) + [surface_coverage_key(q) for q in self.surface_options['coverage']]
+        for name, st in self.surface_summary['structures'].items():
+            for key in keys:
+                self.metrics.update(f'MCMC/surface/{key}/{name}', st[key])
+        seen = [st for st in self.surface_summary['structures'].values() if st['sampled_voxels']]
+        self.logger.info(f'surface posterior of {self.surface_summary["records"]} warped segmentations: {len(seen)} structures with a '
+                         f'sampled contour' + (f', mean signed distance {np.mean([st["bias"] for st in seen]):.4f}, mean |bias| '
+                                               f'{np.mean([st["abs_bias"] for st in seen]):.4f}' if seen else ''))
+        if save_outputs and self.surface_options['save']:
+            save_surface_posterior(self.logger, self.config.save_dirs, spacing, self.surface_bias, self.surface_std, 'MCMC')
 
     def _finish_jacobian_posterior(self, fixed, spacing, save_outputs):
         """fold probability, mean and std of log det J and their summary -> self.jacobian_fold_prob / jacobian_logJ_mean /

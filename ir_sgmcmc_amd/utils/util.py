@@ -169,6 +169,21 @@ def calc_label_posterior(seg_samples, seg_fixed, structures_dict, spacing, mask=
 
 
 @torch.no_grad()
+def calc_surface_posterior(seg_fixed, seg_samples, structures_dict, spacing, mask=None, coverage=(0.5, 0.9, 0.95)):
+    """surface posterior of segmentation samples (absent in the reference): seg_fixed (D,H,W) or (1,1,D,H,W) int16; seg_samples
+    (C, N, 1, D, H, W) int16 on the device, every chain's N warped maps in order (recorded step by step, chains in order within
+    a step); spacing (sx, sy, sz); mask (D,H,W) or None; coverage: 0 to 4 increasing levels in (0,1).  -> (bias, std (D,H,W)
+    float32 with NaN off the fixed contours, summary dict), as diagnostics.SurfacePosterior.finalize."""
+    from ..diagnostics import SurfacePosterior
+    if seg_samples.dim() != 6 or seg_samples.shape[2] != 1:
+        raise ValueError(f'seg_samples must have shape (C, N, 1, D, H, W), got {tuple(seg_samples.shape)}')
+    sp = SurfacePosterior(seg_fixed, structures_dict, spacing, seg_samples.device)
+    for i in range(seg_samples.shape[1]):
+        sp.record(seg_samples[:, i].contiguous())
+    return sp.finalize(mask, coverage)
+
+
+@torch.no_grad()
 def calc_jacobian_posterior(transformations, mask=None):
     """Jacobian posterior maps of transformation samples (absent in the reference): transformations (n,3,D,H,W) float32 on the
     device, in normalised coordinates, the n records in order; mask (D,H,W) or None.  -> (fold_prob, logJ_mean, logJ_std,
