@@ -662,6 +662,18 @@ int irs_transition(irs_ctx* ctx, const irs_io* io, void* stream);
 int irs_flush(irs_ctx* ctx, void* stream);
 /* transitions re-run so far because a prediction failed (statistics) */
 int irs_recovered_transitions(const irs_ctx* ctx, uint64_t* out);
+/* The sparse adjoint of a context on (the default) or off: with 0 the adjoint squaring steps march full columns, the launch sequence
+ * as it was before the plan existed -- the same numbers (A/B runs and parity tests).  A call of its own, not a row of irs_option_set:
+ * the state lives in the context next to the plan's buffers.  Takes effect with the next transition enqueued. */
+int irs_sparse_adjoint_set(irs_ctx* ctx, int on);
+/* What the sparse adjoint did in the LAST transition: the adjoint squaring steps march only
+ * the planes the gradient of the data term can reach -- per 32 x 8 tile column the z-range around the support of g_warped, widened
+ * by one voxel per step, found on the device -- as long as every step of the chain stays below one voxel of displacement.
+ * out: int32 [no_steps][no_chains][4] = whether the chain was marched sparsely, the piece length (planes) its columns were cut
+ * into, the pieces of the chain in the step's list, the planes in its run ranges (of dims[0] x tile columns).  All zero when
+ * switched off, on a slab context, before the first transition, and on a volume so small that the full-column launch already uses
+ * the shortest pieces (128^3 with one chain: the lists could only match them).  Calls irs_flush; blocking. */
+int irs_sparse_adjoint_get(irs_ctx* ctx, int32_t* out, void* stream);
 
 /* timing hook for bench.py: the same transition with hipEvents recorded on `stream` around the stages; blocking.
  * All times in milliseconds for THIS call. */

@@ -1,0 +1,126 @@
+// Splitting arithmetic of the sparse adjoint plan (adjoint_plan.hip): which planes of a tile column an adjoint squaring step
+// marches, which it only zero-fills, and how a column is cut into pieces.  Plain integer functions, host and device: the device
+// kernels and tests/csrc/adjoint_plan_check.cpp (a CPU program) run the same code.
+#pragma once
+
+#if defined(__HIPCC__)
+#define IRS_HD __host__ __device__ inline
+#else
+#define IRS_HD inline
+#endif
+
+namespace irs {
+
+#ifndef IRS_MTX
+#define IRS_MTX 32
+#define IRS_MTY 8
+#endif
+constexpr int kPlanTX = IRS_MTX, kPlanTY = IRS_MTY;  // the adjoint's tile column (exp_kernels.hip: MTX x MTY)
+#ifndef IRS_BWD_MAX_SEG
+#define IRS_BWD_MAX_SEG 64  // longest z-segment of the adjoint step (exp_kernels.hip)
+#endif
+constexpr int kPlanMaxLen = IRS_BWD_MAX_SEG;
+constexpr int kPlanMinLen = 8;     // shortest piece the length search may choose (two run-in planes per piece: 25 % at 8)
+constexpr int kPlanMinForced = 4;  // shortest piece a forced length (march_seg) may ask for; sizes the entry lists
+constexpr int kPlanStats = 4;      // per (step, chain): engaged, piece length, pieces, planes in run ranges
+
+// One unit of work of a step, on the planes [z0, z1) of tile column `tile` of `chain`: march them (fill == 0) or store zeros to them.
+// Marching and filling are separate entries: a workgroup that did both kept the fill's addresses alive across the tile body, and
+// the radius-1 kernel, which sits exactly at 128 VGPRs, then needed scratch memory -- 11 % slower per plane step.
+struct PlanEntry {
+    int chain, tile, z0, z1, fill, pad;
+};
+
+// A tile column of one step: run range [lo, hi) (empty: lo == hi) inside the written range [f0, f1).
+struct ColPlan {
+    int lo, hi, f0, f1;
+};
+
+IRS_HD int plan_min(int a, int b) { return a < b ? a : b; }
+IRS_HD int plan_max(int a, int b) { return a > b ? a : b; }
+
+// z-extent of one voxel column widened by the reach m of a step and clipped to the volume; (0, 0) if the column is empty.
+// The extent table holds (D - lo, hi) per column, both 0 for an empty one (integer maxima of a zeroed table).
+IRS_HD void plan_widen(int a, int b, int m, int D, int& lo, int& hi) {
+    lo = hi = 0;
+    if (b <= 0) return;
+    lo = plan_max(D - a - m, 0);
+    hi = plan_min(b + m, D);
+}
+
+// run range and what the next step reads of this column (`need`, empty: nlo >= nhi) -> the column's plan
+IRS_HD ColPlan plan_column(int lo, int hi, int nlo, int nhi) {
+    const bool run = hi > lo, need = nhi > nlo;
+    if (!run) return need ? ColPlan{nhi, nhi, nlo, nhi} : ColPlan{0, 0, 0, 0};
+    return ColPlan{lo, hi, need ? plan_min(lo, nlo) : lo, need ? plan_max(hi, nhi) : hi};
+}
+
+// The plan of tile column `col` (chain-major, then tile row, tile) of step k from the run ranges runs[step][column][2]: its own run
+// range and what step k - 1 reads of it -- the pieces of the column and of its 8 neighbours reach one plane beyond their own range
+// (and one voxel into the neighbouring columns); the update / FFD kernels read all of step 0's output.
+IRS_HD ColPlan plan_column_of(const int* runs, int k, int col, int C, int ntx, int nty, int D) {
+    const int tiles = ntx * nty, chain = col / tiles, tile = col - chain * tiles, tx = tile % ntx, ty = tile / ntx;
+    const int* r = runs + ((long long)k * C * tiles + col) * 2;
+    int nlo = 0, nhi = D;
+    if (k > 0) {
+        nlo = D;
+        nhi = 0;
+        const int* prev = runs + ((long long)(k - 1) * C + chain) * tiles * 2;
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dx = -1; dx <= 1; ++dx) {
+                // (a neighbour outside the grid folds onto a tile of the 3 x 3 block that is inside it: the hull is the same, and the
+                // nine loads do not wait for one another)
+                const int ux = plan_min(plan_max(tx + dx, 0), ntx - 1), uy = plan_min(plan_max(ty + dy, 0), nty - 1);
+                const int l = prev[(uy * ntx + ux) * 2], h = prev[(uy * ntx + ux) * 2 + 1];
+                if (h > l) {
+                    nlo = plan_min(nlo, plan_max(l - 1, 0));
+                    nhi = plan_max(nhi, plan_min(h + 1, D));
+                }
+            }
+    }
+    return plan_column(r[0], r[1], nlo, nhi);
+}
+
+IRS_HD int plan_pieces(int len, int L) { return len > 0 ? (len + L - 1) / L : 0; }
+
+// piece j of np equal cuts of [lo, lo + len)
+IRS_HD void plan_cut(int lo, int len, int np, int j, int& z0, int& z1) {
+    z0 = lo + (int)((long long)len * j / np);
+    z1 = lo + (int)((long long)len * (j + 1) / np);
+}
+
+// entry of run piece j of a column
+IRS_HD PlanEntry plan_entry(const ColPlan& c, int chain, int tile, int np, int j) {
+    int z0, z1;
+    plan_cut(c.lo, c.hi - c.lo, np, j, z0, z1);
+    return PlanEntry{chain, tile, z0, z1, 0, 0};
+}
+// the fill below (side 0: [f0, lo), for a column without a run range all of its fill) and above (side 1: [hi, f1)) a column's run range
+IRS_HD bool plan_has_fill(const ColPlan& c, int side) { return side == 0 ? c.f0 < c.lo : c.hi < c.f1 && c.hi > c.lo; }
+IRS_HD PlanEntry plan_fill_entry(const ColPlan& c, int chain, int tile, int side) {
+    return side == 0 ? PlanEntry{chain, tile, c.f0, c.lo, 1, 0} : PlanEntry{chain, tile, c.hi, c.f1, 1, 0};
+}
+
+// Piece length of a step: the smallest L in [lmin, lmax] whose run pieces (pieces[L], summed over the columns) fit one resident set
+// of G workgroups; lmax if none does.  The workgroups stride over the list: the fill entries behind the run pieces (a store per
+// plane) go to the first workgroups once they have marched their piece.
+IRS_HD int plan_pick_len(const int* pieces, int G, int lmin, int lmax) {
+    for (int L = lmin; L < lmax; ++L)
+        if (pieces[L] <= G) return L;
+    return lmax;
+}
+
+// entries a step's list can hold: a column gives at most ceil(D / kPlanMinForced) run pieces and two fills
+IRS_HD int plan_entries_cap(int columns, int D) { return columns * ((D + kPlanMinForced - 1) / kPlanMinForced + 2); }
+
+// workgroup id -> list position: runs of `run` consecutive entries (x-neighbouring tiles of one z band) stay on one XCD, as
+// common.h: xcd_swizzle_runs does for whole grids -- here for any count: the tail that fills no group of 8 runs keeps its order.
+IRS_HD int plan_swizzle(int id, int count, int run) {
+    if (run <= 1) return id;
+    const int group = 8 * run;
+    if (id >= count / group * group) return id;
+    const int g = id / group, w = id - g * group;
+    return g * group + (w & 7) * run + (w >> 3);
+}
+
+}  // namespace irs

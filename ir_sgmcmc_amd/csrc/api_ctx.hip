@@ -6,6 +6,7 @@
 
 #include <new>
 
+#include "adjoint_plan.h"
 #include "api_checks.h"
 #include "comm.h"
 
@@ -48,6 +49,7 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     memset((void*)c, 0, sizeof(*c));
     context_born();
     c->kn = global_knobs();
+    c->sparse_adjoint = true;  // (irs_sparse_adjoint_set)
     c->cfg = *cfg;
     c->C = C;
     c->vol = make_vol(D, H, W);
@@ -126,6 +128,8 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     const size_t o_sums = take(sizeof(double) * (kStatVals + 2 * IRS_MAX_CHAINS));
     const size_t o_dmax = take(sizeof(unsigned) * 4 * IRS_MAX_CHAINS * 32);
     const size_t o_cmm = take(coarse_minmax_bytes(c->vol, C));
+    const bool planned = !sl;  // (the slab engine marches full columns)
+    const size_t o_plan = take(planned ? adjoint_plan_bytes(c->vol, C, cfg->no_steps) : 0);
     const size_t o_state = take(sizeof(DevState));
     c->slab_bytes = off;
     // (a context is zeroed at birth and irs_destroy releases whatever exists by then: one teardown for every failure below)
@@ -155,6 +159,7 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     c->nll_sum = c->energy_sum + IRS_MAX_CHAINS;
     c->dmax = (unsigned*)(c->slab + o_dmax);
     c->cmm = (float*)(c->slab + o_cmm);
+    if (planned) c->plan = adjoint_plan_views(c->slab + o_plan, c->vol, C, cfg->no_steps);
     c->state = (DevState*)(c->slab + o_state);
 
     if (ensure_lin_tables(c->lin, D, H, W, nullptr)) {
@@ -490,6 +495,14 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
     if (!fuse_warp_bwd)
         launch_warp_bwd(io->moving_im, io->moving_chains == 1 ? 0 : vol.V, d_last, io->unif,
                         cfg.uniform_alpha > 0.0f ? cfg.uniform_alpha : 0.0f, c->gM, c->gA, C, vol, lin, cfg.seed, 0, it, st);
+    // the support of the gradient that enters the adjoint -> the piece lists of its steps (decided on the device: adjoint_plan.hip)
+    // Only where pieces can get shorter than the full-column launch's segments: at 128^3 with one chain those are already the
+    // shortest pieces (8 planes, one resident set), the lists could only match them, and the plan's four launches cost 3 % of that
+    // transition (profiles/sparse_adjoint_ab.txt).  A launch-shape rule on sizes, like the segment lengths themselves.
+    const bool sparse = c->sparse_adjoint && c->plan.entries != nullptr &&
+                        (global_knobs().march_seg > 0 || exp_bwd_dense_seg_len(vol, C) > kPlanMinLen);
+    c->plan_on = sparse;
+    if (sparse) launch_adjoint_plan(c->gM, c->dmax, c->plan, cfg.no_steps, C, vol, exp_bwd_plan_resident(), global_knobs().march_seg, st);
     LAUNCH_CHECK();
     if (timed) HIP_TRY(hipEventRecord(c->ev[3], st));
     const float* dense = c->ffd ? c->dense : vs;
@@ -514,7 +527,7 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
             // lds_from 2: the any-radius kernel, when launched, takes every step beyond the radius-1 gather (no radius-2 gather then)
             const int gr = global_knobs().lds_from <= 2 ? 1 : 2;
             launch_exp_step_bwd_march(G, dk, out, k == 0, cfg.no_steps, C, vol, lin, dm, (s2 || (gr == 1 && !sa)) ? 1 : 2, sa, gscale, lay,
-                                      timed ? c->ev_bwd[2 * k + 1] : nullptr, st);
+                                      timed ? c->ev_bwd[2 * k + 1] : nullptr, st, sparse ? &c->plan : nullptr, k);
             if (!sa) launch_exp_step_bwd_lds(G, dk, out, k == 0, cfg.no_steps, C, vol, lin, dm, 2, gr, gscale, lay, c->cmm, st);
             G = out;
             cur ^= 1;
@@ -626,6 +639,23 @@ int irs_flush(irs_ctx* c, void* stream) {
 int irs_recovered_transitions(const irs_ctx* c, uint64_t* out) {
     if (!c || !out) return fail("irs_recovered_transitions: null argument");
     *out = c->fails_total;
+    return 0;
+}
+
+int irs_sparse_adjoint_set(irs_ctx* c, int on) {
+    if (!c) return fail("irs_sparse_adjoint_set: null argument");
+    c->sparse_adjoint = on != 0;
+    return 0;
+}
+
+int irs_sparse_adjoint_get(irs_ctx* c, int32_t* out, void* stream) {
+    if (!c || !out) return fail("irs_sparse_adjoint_get: null argument");
+    const size_t n = (size_t)c->cfg.no_steps * c->C * kPlanStats;
+    memset(out, 0, n * sizeof(int32_t));
+    if (!c->plan.stats || !c->plan_on || c->n_enqueued == 0) return 0;  // full columns: nothing engaged
+    if (irs_flush(c, stream)) return 1;
+    HIP_TRY(hipMemcpyAsync(out, c->plan.stats, n * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return 0;
 }
 

@@ -14,6 +14,7 @@
 //             retire one lane per clock on gfx950, global ones cost 7.5 ms per step at 256^3), fixed summation order,
 //             plain coalesced stores, no zero-fill.  For max|d_k| >= 2 voxels the LDS-atomic scatter kernel takes over
 //             (correct for any displacement).  Which kernel does the work of a step is decided on the device.
+#include "adjoint_plan.h"
 #include "kernels.h"
 
 #include <type_traits>
@@ -890,12 +891,14 @@ extern "C" __attribute__((visibility("default"))) int irs_debug_bwd_trace(unsign
 #else
 #define IRS_BT(slot)
 #endif
-template <bool PRESCALE, int R>
+// PLAN: chain, tile and z-range come from a piece of the sparse adjoint plan (adjoint_plan.hip) instead of the launch's segments
+template <bool PRESCALE, int R, bool PLAN = false>
 __device__ __forceinline__ void exp_bwd_march_tile(const float* __restrict__ G, const float* __restrict__ dk,
                                                    float* __restrict__ gout, const Vol vol, const Lin lin, const Scale3L sc,
                                                    const unsigned* __restrict__ dmax, const int seg_len, const int nseg,
                                                    const int r_lo, const int own_rest, const int swz_run, const int tile_id,
-                                                   const dim3 tiles, const float* __restrict__ gscale, const int lay) {
+                                                   const dim3 tiles, const float* __restrict__ gscale, const int lay,
+                                                   const PlanEntry piece = PlanEntry{}) {
     using M = March<PRESCALE, R>;
     constexpr int NP = M::NP, PX = M::PX, PN = M::PN, NIT = M::NIT;
     // ring slot layout (9 floats per source, 8-byte fields so that the gather needs three ds_read_b64 per candidate):
@@ -910,15 +913,20 @@ __device__ __forceinline__ void exp_bwd_march_tile(const float* __restrict__ G, 
     __shared__ float2 q_xy[NPQ * PN], q_zg[NPQ * PN], q_g[NPQ * PN], q_d[NP * PN];
     __shared__ float q_dz[NP * PN];
     // XCD-aware tile assignment: consecutive tiles (x fastest, then y, then z-segment, then chain) stay on one L2
-    const int tile_ = xcd_swizzle_runs(tile_id, (int)(tiles.x * tiles.y * tiles.z), swz_run);
+    const int tile_ = PLAN ? piece.tile : xcd_swizzle_runs(tile_id, (int)(tiles.x * tiles.y * tiles.z), swz_run);
     const int tbx = tile_ % tiles.x, tby = (tile_ / tiles.x) % tiles.y, tbz = tile_ / (tiles.x * tiles.y);
-    const int chain = tbz / nseg, seg = tbz % nseg;
+    const int chain = PLAN ? piece.chain : tbz / nseg, seg = tbz % nseg;
     const int hs = max(max((int)floorf(__uint_as_float(dmax[chain * 4 + 0])), (int)floorf(__uint_as_float(dmax[chain * 4 + 1]))),
                        (int)floorf(__uint_as_float(dmax[chain * 4 + 2]))) + 1;
     if (hs <= r_lo || (hs > R && !(R == 2 && own_rest))) return;  // another variant of this step owns the chain
     const int ox = tbx * MTX, oy = tby * MTY;
     int z0, z1;
-    seg_range(vol, seg, seg_len, z0, z1);
+    if (PLAN) {
+        z0 = piece.z0;
+        z1 = piece.z1;
+    } else {
+        seg_range(vol, seg, seg_len, z0, z1);
+    }
     const int64_t V = vol.V;
     const int64_t cb = (int64_t)chain * 3 * V;
     // (The body stays inside a lambda, the shape it had when compile-time layouts were tried on it -- slower: DESIGN.md, "Round-5
@@ -1236,15 +1244,63 @@ __global__ __launch_bounds__(kMarchBlock, R == 1 ? IRS_MARCH_WAVES : IRS_MARCH_W
 }
 
 
-#ifndef IRS_BWD_MAX_SEG
-#define IRS_BWD_MAX_SEG 64  // longest z-segment the resident-set rule may give the adjoint step (common.h: pick_seg_len_fit)
-#endif
+// The same radius-1 kernel walking a piece list of the sparse adjoint plan (adjoint_plan.hip): the workgroups of ONE resident set
+// stride statically over the list, whose length they read from device memory.  An entry either runs the unchanged tile body on its
+// z-range or zero-fills it (plain coalesced stores in the output's layout).  Fills only exist for chains all of whose steps are this
+// kernel's, so they need no ownership test.
+constexpr int kPlanFillBlocks = 256;  // workgroups in front of the marching ones (a multiple of 8: the XCD of a marching workgroup stays id % 8)
+// (one thread per voxel column of the tile, as in the tile body's own stores)
+__device__ __forceinline__ void plan_zero_fill(float* __restrict__ o, const Lay3 LO, const Vol vol, const int ox, const int oy, int za, int zb) {
+    za = max(za, 0);
+    zb = min(zb, vol.D);
+    const int lx = threadIdx.x % MTX, ly = threadIdx.x / MTX;
+    const int x = ox + lx, y = oy + ly;
+    if (!(x < vol.W && y < vol.H)) return;
+    // (the tile body's own store addressing: uniform plane base + 32-bit lane offset -- nothing here that it does not form anyway)
+    const unsigned g = (unsigned)(y * vol.W + x) * 4u * (unsigned)LO.em;
+    for (int z = za; z < zb; ++z) {
+        const int64_t pl = (int64_t)z * vol.H * vol.W * LO.em;
+        if (LO.em == 3) {
+            st3_off(o + pl, g, 0.0f, 0.0f, 0.0f);
+        } else {
+            st_off(o + pl, g, 0.0f);
+            st_off(o + LO.cs + pl, g, 0.0f);
+            st_off(o + 2 * LO.cs + pl, g, 0.0f);
+        }
+    }
+}
+template <bool PRESCALE>
+__global__ __launch_bounds__(kMarchBlock, IRS_MARCH_WAVES) void exp_bwd_march_plan_kernel(
+    const float* __restrict__ G, const float* __restrict__ dk, float* __restrict__ gout, Vol vol, Lin lin, Scale3L sc,
+    const unsigned* __restrict__ dmax, const PlanEntry* __restrict__ entries, const int* __restrict__ count, int swz_run, dim3 tiles,
+    const float* __restrict__ gscale, int lay) {
+    const int n = count[0], n_run = count[1];  // the run pieces come first in the list
+    // The first kPlanFillBlocks workgroups store the zeros and leave; the others march.  One code path each: with the fill inside the
+    // entry loop of the marching workgroups the compiler kept values of it alive across the tile body, which sits exactly at 128
+    // VGPRs, and the kernel needed scratch memory -- 11 % slower per plane step on the same list (profiles/sparse_adjoint_ab.txt).
+    if (blockIdx.x < kPlanFillBlocks) {
+        for (int id = n_run + (int)blockIdx.x; id < n; id += kPlanFillBlocks) {
+            const PlanEntry e = entries[id];
+            plan_zero_fill(gout + (int64_t)e.chain * 3 * vol.V, lay3(lay & 4, vol.V), vol, (e.tile % (int)tiles.x) * MTX,
+                           (e.tile / (int)tiles.x) * MTY, e.z0, e.z1);
+        }
+        return;
+    }
+    const int first = (int)blockIdx.x - kPlanFillBlocks, stride = (int)gridDim.x - kPlanFillBlocks;
+    for (int id = first; id < n_run; id += stride)
+        exp_bwd_march_tile<PRESCALE, 1, true>(G, dk, gout, vol, lin, sc, dmax, 0, 1, 0, 0, 0, id, tiles, gscale, lay,
+                                              entries[plan_swizzle(id, n_run, swz_run)]);
+}
+int64_t exp_bwd_plan_resident() {
+    static int cache = 0;
+    return resident_blocks((const void*)exp_bwd_march_plan_kernel<false>, kMarchBlock, &cache);
+}
+
 constexpr int kRareGrid = 256 * IRS_MARCH_WAVES_R2;  // persistent grid of the rarely selected radius-2 variant (what the chip holds at once)
 
 
-void launch_exp_step_bwd_march(const float* G, const float* dk, float* gout, bool prescale_in, int no_steps, int C, Vol vol,
-                               Lin lin, const unsigned* dmax, int max_radius, bool r2_owns_rest, const float* gscale, int lay,
-                               hipEvent_t after_primary, hipStream_t st) {
+// z-segment length of the full-column radius-1 launch
+int exp_bwd_dense_seg_len(Vol vol, int C) {
     const int seg_env = global_knobs().march_seg;
     const int64_t per_layer = (int64_t)((vol.W + MTX - 1) / MTX) * ((vol.H + MTY - 1) / MTY) * C;
     int seg_len = pick_seg_len(vol.nz + vol.nzb, per_layer, 8, seg_env);
@@ -1253,6 +1309,15 @@ void launch_exp_step_bwd_march(const float* G, const float* dk, float* gout, boo
         const int64_t res = resident_blocks((const void*)exp_bwd_march_kernel<false, 1>, kMarchBlock, &cache);
         if (res > 0) seg_len = pick_seg_len_fit(vol.nz, vol.nzb, per_layer, 8, 2, res, 0, IRS_BWD_MAX_SEG);
     }
+    return seg_len;
+}
+
+void launch_exp_step_bwd_march(const float* G, const float* dk, float* gout, bool prescale_in, int no_steps, int C, Vol vol,
+                               Lin lin, const unsigned* dmax, int max_radius, bool r2_owns_rest, const float* gscale, int lay,
+                               hipEvent_t after_primary, hipStream_t st, const AdjointPlan* plan, int step) {
+    const int seg_env = global_knobs().march_seg;
+    const int64_t per_layer = (int64_t)((vol.W + MTX - 1) / MTX) * ((vol.H + MTY - 1) / MTY) * C;
+    const int seg_len = exp_bwd_dense_seg_len(vol, C);
     const int nseg = vol_nseg(vol, seg_len);  // segments of both windows
     const dim3 tiles((vol.W + MTX - 1) / MTX, (vol.H + MTY - 1) / MTY, (unsigned)(nseg * C));
     const int total = (int)(tiles.x * tiles.y * tiles.z);
@@ -1271,7 +1336,17 @@ void launch_exp_step_bwd_march(const float* G, const float* dk, float* gout, boo
     };
     // the radius-1 kernel first (the one the roofline is quoted on: `after_primary` brackets exactly its launch), then the
     // rarely selected radius-2 variant on the small persistent grid
-    with_bool(prescale_in, [&](auto P) { launch(P, Int<1>{}, 0, total, seg_len, nseg, tiles, total); });
+    if (plan && vol.nzb == 0 && vol.z0 == 0 && vol.nz == vol.D) {  // the step's piece list (full volume only), one resident set
+        const int64_t res = exp_bwd_plan_resident();
+        const dim3 tiles2d(tiles.x, tiles.y, 1);
+        with_bool(prescale_in, [&](auto P) {
+            hipLaunchKernelGGL((exp_bwd_march_plan_kernel<decltype(P)::value>), dim3((unsigned)((res > 0 ? res : kExpGridCap) + kPlanFillBlocks)), dim3(kMarchBlock), 0,
+                               st, G, dk, gout, vol, lin, sc, dmax, plan->entries + (int64_t)step * plan->cap, plan->count + 2 * step, swz_run, tiles2d,
+                               gscale, lay);
+        });
+    } else {
+        with_bool(prescale_in, [&](auto P) { launch(P, Int<1>{}, 0, total, seg_len, nseg, tiles, total); });
+    }
     if (after_primary) (void)hipEventRecord(after_primary, st);
     if (max_radius >= 2) {
         // its own segments: the variant walks its tiles on a persistent grid of what the chip holds of IT (three workgroups per CU,

@@ -53,9 +53,13 @@ void launch_exp_step_fwd_march(const float* din, float* dout, bool prescale, int
                                const unsigned* dmax_in, unsigned* dmax_out, bool only_r1, int lay, hipStream_t st);
 // the adjoint is launched as a set: gather radius 1, gather radius 2 and the scatter fallback; exactly one of them does
 // the work, chosen on the device from the bound max|d_k|
+// plan (adjoint_plan.hip), optional: the radius-1 kernel walks step `step`'s piece list instead of full columns
+struct AdjointPlan;
 void launch_exp_step_bwd_march(const float* G, const float* dk, float* gout, bool prescale, int no_steps, int C, Vol vol,
                                Lin lin, const unsigned* dmax, int max_radius, bool r2_owns_rest, const float* gscale, int lay,
-                               hipEvent_t after_primary, hipStream_t st);
+                               hipEvent_t after_primary, hipStream_t st, const AdjointPlan* plan = nullptr, int step = 0);
+int exp_bwd_dense_seg_len(Vol vol, int C);  // z-segment length of the full-column radius-1 launch
+int64_t exp_bwd_plan_resident();  // workgroups of the list-walking radius-1 kernel the chip holds at once (0: unknown)
 // cmm: scratch of coarse_minmax_bytes(vol, C) for the per-cell displacement extrema (nullptr: sources are bounded by the
 // global bound around the tile only -- correct, slow for large displacements)
 size_t coarse_minmax_bytes(Vol vol, int C);
@@ -63,6 +67,25 @@ void launch_exp_step_bwd_lds(const float* G, const float* dk, float* gout, bool 
                              Lin lin, const unsigned* dmax, int halo, int gather_radius, const float* gscale, int lay,
                              float* cmm, hipStream_t st);
 void launch_field_absmax(const float* d, bool prescale, int no_steps, unsigned* dmax, int C, Vol vol, hipStream_t st);
+
+// ---- adjoint_plan.hip (which planes the adjoint squaring steps march: the support of the incoming gradient, on the device)
+struct PlanEntry;
+struct ColPlan;
+struct AdjointPlan {   // views into one allocation of adjoint_plan_bytes()
+    int* ext = nullptr;            // [C][H W][2]: (D - lo, hi) of the planes where g_warped != 0, per voxel column
+    int* runs = nullptr;           // [no_steps][C tiles][2]: run range of every tile column
+    ColPlan* colplan = nullptr;    // [no_steps][C tiles]: run range + fills of every tile column (scratch of the list kernel)
+    PlanEntry* entries = nullptr;  // [no_steps][cap]
+    int* count = nullptr;          // [no_steps][2] entries of a step's list, and how many of them (the first) are run pieces
+    int* stats = nullptr;          // [no_steps][C][kPlanStats]
+    int cap = 0, ntx = 0, nty = 0;
+};
+size_t adjoint_plan_bytes(Vol vol, int C, int no_steps);
+AdjointPlan adjoint_plan_views(char* base, Vol vol, int C, int no_steps);
+// extents of g_warped ([C][V]) -> run ranges -> piece lists of all steps; dmax: [no_steps][C][4] bounds of d_k; G: resident set
+// the lists are cut for; forced_len > 0: that piece length
+void launch_adjoint_plan(const float* g_warped, const unsigned* dmax, const AdjointPlan& plan, int no_steps, int C, Vol vol,
+                         int64_t G, int forced_len, hipStream_t st);
 
 // ---- data_kernels.hip
 void launch_sobolev_march(const float* in, float* out, const Taps& taps, int planes, Vol vol, unsigned* dmax0, int no_steps,

@@ -162,6 +162,20 @@ class TransitionEngine:
         L.check(self.lib.irs_recovered_transitions(self._ctx, C.byref(n)))
         return int(n.value)
 
+    def set_sparse_adjoint(self, on):
+        """irs_sparse_adjoint_set: False -> the adjoint squaring steps march full columns (the same numbers; A/B and parity runs)"""
+        L.check(self.lib.irs_sparse_adjoint_set(self._ctx, int(bool(on))))
+
+    @_on_device
+    def sparse_adjoint(self):
+        """irs_sparse_adjoint_get: per adjoint step k and chain c of the last transition, [k][c] = dict(engaged, piece_len, pieces,
+        run_planes) -- whether the step marched only the planes the gradient reaches, and how they were cut"""
+        n, ch = self.cfg.no_steps, self.cfg.no_chains
+        buf = (C.c_int32 * (n * ch * 4))()
+        L.check(self.lib.irs_sparse_adjoint_get(self._ctx, buf, self._stream()))
+        keys = ('engaged', 'piece_len', 'pieces', 'run_planes')
+        return [[dict(zip(keys, buf[(k * ch + c) * 4:(k * ch + c) * 4 + 4])) for c in range(ch)] for k in range(n)]
+
     # ---------------------------------------------------------------- small state
     @property
     def workspace_bytes(self):
