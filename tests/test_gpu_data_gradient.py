@@ -1,0 +1,199 @@
+"""The image-gradient stage of a transition -- lcc_data_bwd_march_kernel<S, EXPLICIT_GZ, BATCH> in all its instantiations, both builds
+behind `k_le4`, and ssd_bwd_kernel -- against a float64 restatement of that stage ALONE (tests/_data_gradient.py), element by element.
+
+g_warped is no output.  It is read through grad_v of a transition at velocity zero (no Sobolev smoothing, no jitter, injected noise 0):
+the regulariser half of grad_v is exactly 0, every adjoint squaring step doubles its input and the 2^-N prescale undoes that exactly,
+and the adjoint of the identity warp multiplies g_warped by the one-sided difference of the moving image, +-1, +-2 or +-4 for the
+triangle-wave image used here.  Shapes are dyadic (2^k + 1): sampling positions are exact integers, nothing hangs on a rounding tie.
+Channel ch is exactly 0 on the two faces of its own axis; every voxel but the 8 corners shows in some channel.
+
+Shapes (tile 32 x 16, 4-plane segments): (9,17,33) x tiles 32 + 1, y tiles 16 + 1, segments 4 + 4 + 1; (5,9,129) five x tiles, the last
+1 wide, one ragged tile row, segments 4 + 1, the smallest depth lcc_s = 2 takes; (33,5,65) many segments, the smallest height for
+lcc_s = 2; (17,33,65) interior full tiles, seams on both axes.  The tolerance is derived on the reference side (1e-5 of the absolute
+addends of each output, plus the rounding of the read-out); tests/test_data_gradient_host.py proves on the CPU that a float32
+evaluation uses less than a tenth of it and that each mistake it is for exceeds it by more than 1e4."""
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+
+from ir_sgmcmc_amd import ops
+from ir_sgmcmc_amd.engine import EngineConfig, TransitionEngine
+from tests import _data_gradient as G
+from tests import _transition_scalars as R
+from tests._report import check
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+F64 = torch.float64
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def to_dev(d):
+    return {k: v.to(DEV).contiguous() for k, v in d.items()}
+
+
+def check_each(test, key, a, b, tol):
+    """|a - b| <= tol element by element; the parity report gets the worst deviation in units of its tolerance"""
+    a, b, tol = (torch.as_tensor(x, dtype=F64).cpu() for x in (a, b, tol))
+    exact = (a == b) | (a.isnan() & b.isnan())
+    return check(test, key + ' [deviation / tolerance]', torch.where(exact, torch.zeros_like(tol), (a - b).abs() / tol), torch.zeros_like(tol), 1.0)
+
+
+def run_engine(case, options=None, sparse_adjoint=None):
+    """one transition of the case at velocity zero -> what the GPU wrote and was given, on the CPU"""
+    dims, s, C, K, mask_kind, per_chain_fixed, kw = case
+    cfg = EngineConfig(dims=dims, no_chains=C, sobolev_s=0, uniform_noise=0.0, lcc_s=s, gmm_components=K, lr=0.05, **kw)
+    fixed, moving, mask = G.case_inputs(dims, C, mask_kind, per_chain_fixed)
+    eng = TransitionEngine(cfg, DEV)
+    eng.option('predict_variants', 0)   # every kernel variant is launched: nothing is assumed, no transition is re-run
+    for k, v in (options or {}).items():
+        eng.option(k, v)
+    if sparse_adjoint is not None:
+        eng.set_sparse_adjoint(sparse_adjoint)
+    fd, md = eng.prepare(to_dev({'im': fixed, 'mask': mask}), to_dev({'im': moving}))
+    state0 = None
+    if cfg.data_loss == 'GMM':          # the hand-set mixture, well away from its optimum, zeroed moments
+        eng.gmm_init(fd, md)
+        st = eng.state()
+        ls, lg = R.hand_set_mixture({'im': fixed, 'mask': mask}, {'im': moving}, K, s)
+        for k in range(K):
+            st.gmm_log_std[k], st.gmm_logits[k] = float(ls[k]), float(lg[k])
+            for i in range(2):
+                st.gmm_adam_m[i][k] = st.gmm_adam_v[i][k] = 0.0
+        st.gmm_adam_step[0] = st.gmm_adam_step[1] = 0
+        eng.set_state(st)
+        st = eng.state()
+        state0 = {'log_std': torch.tensor(list(st.gmm_log_std)[:K], dtype=F64), 'logits': torch.tensor(list(st.gmm_logits)[:K], dtype=F64),
+                  'm': torch.zeros(2, K, dtype=F64), 'v': torch.zeros(2, K, dtype=F64), 'step': [0, 0]}
+    z = lambda *shape: torch.full(shape, float('nan'), device=DEV, dtype=torch.float32)
+    out = {'curr_state': z(C, 3, *dims), 'residuals': z(C, 1, *dims), 'grad_v': z(C, 3, *dims), 'displacement': z(C, 3, *dims)}
+    v = torch.zeros(C, 3, *dims, device=DEV)
+    eng.transition(fd, md, v, None, torch.zeros(C, 3, *dims, device=DEV), None, out)
+    sc, st = eng.scalars(), eng.state()
+    res = {k: t.cpu() for k, t in out.items()}
+    res.update(alpha=list(sc['alpha']), state0=state0, v_new=v.cpu(),
+               params=(torch.tensor(list(st.gmm_log_std)[:K], dtype=F64), torch.tensor(list(st.gmm_logits)[:K], dtype=F64)))
+    return res
+
+
+def hold(case, r, tag=''):
+    """the outputs of run_engine against the restatement -> the restatement (for comparisons between runs)"""
+    dims, s, C, K, mask_kind, per_chain_fixed, kw = case
+    cfg = EngineConfig(dims=dims, no_chains=C, sobolev_s=0, uniform_noise=0.0, lcc_s=s, gmm_components=K, lr=0.05, **kw)
+    h = R.hyper_from_engine(cfg)
+    gmm = cfg.data_loss == 'GMM'
+    fixed, moving, mask = G.case_inputs(dims, C, mask_kind, per_chain_fixed)
+    T = 'stage/data_gradient/' + G.case_id(case) + tag
+    assert int(torch.count_nonzero(r['displacement'])) == 0 and int(torch.count_nonzero(r['curr_state'])) == 0
+    grad, z = r['grad_v'], r['residuals']
+    assert bool(torch.isfinite(grad).all()) and bool(torch.isfinite(z).all())
+    # the forward map first, so that an error there is not blamed on the adjoint
+    z_ref, tol_z = G.forward(fixed, moving, h, s)
+    check_each(T, 'residual z', z, z_ref.expand(C, -1, -1, -1, -1), tol_z.expand(C, -1, -1, -1, -1))
+    for a in r['alpha']:
+        if not cfg.virtual_decimation or mask_kind == 'checkerboard':
+            assert a == 1.0
+        else:
+            assert 0.0 < a < 0.9, r['alpha']
+    # one chain: the parameters its step left, read back; several: the float64 serial recursion's, with their spread in the tolerance
+    ref, _ = G.reference(z.to(F64), fixed, moving, mask, h, s, r['state0'], alpha=r['alpha'], params=[r['params']] if gmm and C == 1 else None)
+    for ch, ax in enumerate((-1, -2, -3)):
+        assert int(torch.count_nonzero(grad[:, ch].narrow(ax, 0, 1))) == 0 and int(torch.count_nonzero(grad[:, ch].narrow(ax, dims[ax] - 1, 1))) == 0
+        check_each(T, f'grad_v channel {ch}', grad[:, ch], ref['grad_v'][:, ch], ref['tol'][:, ch])
+    assert int(((ref['dm'] != 0).sum(1) == 0).sum()) == 8       # what no channel shows: the 8 corners
+    assert torch.equal(r['v_new'], -(torch.tensor(cfg.lr, dtype=torch.float32) * grad))
+    return ref
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the engine read-out
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('case', G.ENGINE_CASES, ids=[G.case_id(c) for c in G.ENGINE_CASES])
+def test_data_gradient_element_by_element(case):
+    C, gmm = case[2], case[6].get('data_loss', 'GMM') == 'GMM'
+    if not (gmm and C > 1):
+        hold(case, run_engine(case))
+        return
+    # several chains: one launch for all of them (chain c against the snapshot its step left) and one launch per chain, right behind
+    # its step -- each held to float64, and the same bits
+    batched, serial = run_engine(case, {'data_batch': 1}), run_engine(case, {'data_batch': 0})
+    hold(case, batched, '-data_batch=1')
+    hold(case, serial, '-data_batch=0')
+    for k in ('grad_v', 'residuals', 'v_new'):
+        assert torch.equal(batched[k], serial[k]), k
+    assert batched['alpha'] == serial['alpha']
+
+
+def test_sparse_adjoint_does_not_change_a_bit():
+    case = (G.M, 1, 1, 4, 'synthetic', False, {})
+    on, off = run_engine(case), run_engine(case, sparse_adjoint=False)
+    hold(case, off, '-dense_adjoint')
+    assert torch.equal(on['grad_v'], off['grad_v']) and torch.equal(on['residuals'], off['residuals'])
+
+
+SEG_CASE = (G.E, 1, 1, 4, 'synthetic', False, {})
+SEG_CHILD = r'''
+import sys
+import torch
+from tests import test_gpu_data_gradient as T
+torch.save(T.run_engine(T.SEG_CASE), sys.argv[1])
+print('ok')
+'''
+
+
+def test_another_segment_length_stays_inside_the_tolerance(tmp_path):
+    """`lcc_seg` sizes the partial-sum layout of every context of a process, so it is given to a fresh process: segments of 7 planes
+    put the seams of (33,5,65) at other planes than the 4-plane rule does"""
+    default = run_engine(SEG_CASE)
+    ref = hold(SEG_CASE, default)
+    path = str(tmp_path / 'seg7.pt')
+    env = {**os.environ, 'IRS_LCC_SEG': '7', 'PYTHONPATH': ROOT + os.pathsep + os.environ.get('PYTHONPATH', '')}
+    out = subprocess.run([sys.executable, '-c', SEG_CHILD, path], env=env, cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.strip().endswith('ok'), out.stderr
+    forced = torch.load(path)
+    hold(SEG_CASE, forced, '-lcc_seg=7')
+    check_each('stage/data_gradient/' + G.case_id(SEG_CASE) + '-lcc_seg=7', 'grad_v against the default segments', forced['grad_v'], default['grad_v'], ref['tol'])
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the stateless operators: irs_lcc_normalise, irs_lcc_map_fwd, irs_lcc_map_bwd (the EXPLICIT_GZ instantiation), no warp involved
+# ------------------------------------------------------------------------------------------------------------------------------
+OPS_SHAPES = [
+    ((12, 16, 64), 1), ((12, 16, 64), 2), ((8, 32, 32), 1), ((8, 32, 32), 2),   # exact tile multiples: the halo wholly outside the volume
+    ((3, 3, 3), 1), ((5, 5, 5), 2),                                             # the smallest legal shapes: both folded borders adjacent
+    ((9, 17, 33), 1), ((9, 17, 33), 2), ((6, 19, 35), 1), ((6, 19, 35), 2),     # one, two and three spare columns / rows
+]
+
+
+@pytest.mark.parametrize('per_chain_fhat', [False, True], ids=['shared', 'per_chain'])
+@pytest.mark.parametrize('dims,s', OPS_SHAPES, ids=['x'.join(map(str, d)) + f'-s{s}' for d, s in OPS_SHAPES])
+def test_lcc_operators_against_float64(dims, s, per_chain_fhat):
+    C = 2
+    gen = torch.Generator().manual_seed(7)
+    im_f = torch.rand(C if per_chain_fhat else 1, 1, *dims, generator=gen)
+    im_m = torch.rand(C, 1, *dims, generator=gen)
+    g_z = torch.randn(C, 1, *dims, generator=gen)
+    T = f'stage/lcc_operators/{"x".join(map(str, dims))}-s{s}-{"per_chain" if per_chain_fhat else "shared"}'
+    # irs_lcc_normalise
+    fhat, sig_f = ops.lcc_normalise(im_f.to(DEV), s, want_sigma=True)
+    wh_ref, sig_ref, _ = G.lcc_stats(im_f.to(F64), s)
+    tol_wh, tol_sig = G.tol_lcc(im_f, s)
+    check_each(T, 'lcc_normalise', fhat, wh_ref, tol_wh)
+    check_each(T, 'lcc_normalise sigma', sig_f, sig_ref, tol_sig)
+    # irs_lcc_map_fwd, at the fhat the GPU wrote
+    z, sig_m = ops.lcc_map_fwd(fhat, im_m.to(DEV), s)
+    wh_m, sig_m_ref, _ = G.lcc_stats(im_m.to(F64), s)
+    tol_wh, tol_sig = G.tol_lcc(im_m, s)
+    z_ref = fhat.cpu().to(F64) - wh_m
+    check_each(T, 'lcc_map_fwd', z, z_ref, tol_wh + G.U * z_ref.abs())
+    check_each(T, 'lcc_map_fwd sigma', sig_m, sig_m_ref, tol_sig)
+    # irs_lcc_map_bwd, at the fhat, z and sigma the GPU wrote: 1e-5 of the absolute addends of each output, as in the engine read-out
+    g = ops.lcc_map_bwd(fhat, z, sig_m, g_z.to(DEV), s)
+    wh = fhat.cpu().to(F64) - z.cpu().to(F64)
+    refs = [G.lcc_adjoint(g_z[c, 0].to(F64), wh[c, 0], sig_m[c, 0].cpu().to(F64), s) for c in range(C)]
+    g_ref, A = torch.stack([r[0] for r in refs]).unsqueeze(1), torch.stack([r[1] for r in refs]).unsqueeze(1)
+    assert float(g_ref.abs().max()) > 0.0
+    check_each(T, 'lcc_map_bwd', g, g_ref, 1e-5 * A)
