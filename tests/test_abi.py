@@ -45,6 +45,28 @@ def test_struct_layouts_match_the_header():
     assert C.sizeof(L.IrsState) == 2 * 4 * 8 + 2 * 2 * 8 * 8 + 16 + 3 * 16 + 16 + 8
 
 
+def _header_constants():
+    """every object-like `#define IRS_*` of the header whose body is an integer expression of literals and earlier names"""
+    src = open(os.path.join(ROOT, 'include', 'irsgmcmc.h')).read()
+    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S).replace('\\\n', ' ')
+    values = {}
+    for name, body in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(IRS_\w+)[ \t]+(\S.*)$', src, flags=re.M):
+        if re.fullmatch(r'[\w\s()+\-*<]+', body):  # names, decimal literals and + - * << only: what C and Python read alike
+            try:
+                values[name] = int(eval(body, {'__builtins__': {}}, dict(values)))
+            except NameError:  # built on a name that is no integer constant itself
+                pass
+    return values
+
+
+def test_constants_match_the_header():
+    """ops.py sizes its workspaces and summaries from the constants _lib.py copies by hand"""
+    header = _header_constants()
+    twins = {name: value for name, value in header.items() if hasattr(L, name)}
+    assert len(twins) >= 46 and 'IRS_SURFACE_WS_BYTES' in twins, sorted(header)
+    assert {name: getattr(L, name) for name in twins} == twins
+
+
 def test_cpu_tensors_are_refused():
     import torch
     from ir_sgmcmc_amd import ops
