@@ -496,6 +496,53 @@ int irs_local_similarity_update(const float* lncc, int C, int D, int H, int W, f
 int irs_local_similarity_finalize(const float* mean, const float* low, const int32_t* count, const uint8_t* mask, int D, int H,
                                   int W, long long* isummary, double* fsummary, void* ws, size_t ws_bytes, void* stream);
 
+/* Residual model check (the numbers behind the reference's log_hist_res figure, logger/visualization.py:64-86): the data term
+ * models the residual z as a zero-mean Gaussian mixture; these operators say whether that mixture fits the residuals it is
+ * applied to -- the histogram and the moments of z, to be set against the mixture on the host -- and where it does not: the
+ * per-voxel posterior mean of the negative log-likelihood.
+ *  - irs_residual_histogram.  residuals (C,1,D,H,W) float32, C in 1 .. IRS_MAX_CHAINS; mask (1,1,D,H,W) uint8 shared by the
+ *    chains, or NULL; every dim >= 1, fewer than 2^30 voxels; half_range h float32, finite and > 0; bins B in
+ *    IRS_RESIDUAL_MIN_BINS .. IRS_RESIDUAL_MAX_BINS.  A voxel takes part when the mask is set there (or is NULL) and z is
+ *    finite; masked voxels with a non-finite z are only counted (n_nonfinite).
+ *    Binning, in float32: inv_w = (float)B / (2 * h) on the host, t = (z + h) * inv_w (a sum, then a product), b = min(B - 1,
+ *    max(0, (int)floorf(t))).  |z| > h falls into the end bin and the voxel is counted in n_clipped; z == h is in bin B - 1
+ *    and not clipped.
+ *    hist (C,B) int64: hist[c][b] over the voxels of chain c taking part.  counts (C,3) int64: {n, n_nonfinite, n_clipped}.
+ *    sums (C,4) double over the voxels taking part: {sum z, sum z^2, sum z^4, max |z|}, each z converted to double first (a
+ *    maximum nothing entered is -inf).  The three arrays accumulate over calls: records_before == 0 overwrites them;
+ *    otherwise (records_before > 0, records_before + C <= INT32_MAX) the call's integers are added, each of its three sums is
+ *    added with one double add, and the maximum is merged.
+ *    ws: IRS_RESIDUAL_WS_BYTES of device memory.  One launch for all chains and one finish launch.  Deterministic: two identical
+ *    call sequences are bit-identical and chain c of a C-chain call is bit-identical to the single-chain call on that chain
+ *    (integer atomics only, fixed-order double sums, a grid per chain that depends on the volume only); no host sync.
+ *  - irs_residual_nll_update: residuals (C,1,D,H,W) float32, C in 1 .. IRS_MAX_CHAINS, every dim >= 1, fewer than 2^30 voxels.
+ *    The model is two host arrays of K doubles, K in 1 .. IRS_MAX_COMPONENTS: log_weight[k] = ln pi_k - ln sigma_k - 1/2 ln 2 pi
+ *    and inv_std[k] = 1 / sigma_k, every entry finite and inv_std > 0.  The per-voxel state mean (D,H,W) float32 and count
+ *    (D,H,W) int32 (8 bytes per voxel) is updated in place.  Per voxel the chains are folded in order and a non-finite z is
+ *    skipped; in float64 a_k = log_weight[k] - 1/2 (z inv_std[k])^2, m = max_k a_k, nll = -(m + log sum_k exp(a_k - m)),
+ *    rounded once to float32; then k = ++count, mean = mean + (nll - mean) / (float)k, every operation rounded once to
+ *    float32.  records_before >= 0, records_before + C <= INT32_MAX; records_before = 0 overwrites the state (count 0, mean
+ *    0 before the first sample), which is then never read.  The map is written at every voxel, masked or not.  Each thread
+ *    owns its voxels, no atomics; no host sync.
+ *  - irs_residual_nll_finalize: the summary of the state over the mask ((D,H,W) uint8, or NULL: the whole volume).
+ *    isummary: IRS_RESIDUAL_MAP_SUMMARY_INTS int64 {voxels, voxels with count == 0}; fsummary:
+ *    IRS_RESIDUAL_MAP_SUMMARY_FLOATS doubles over the voxels with count > 0 {sum of mean, max of mean}; a maximum nothing
+ *    entered is -inf.  ws: IRS_RESIDUAL_MAP_WS_BYTES of device memory.  Deterministic; no host sync. */
+#define IRS_RESIDUAL_MIN_BINS 2
+#define IRS_RESIDUAL_MAX_BINS 512
+#define IRS_RESIDUAL_MAX_BLOCKS 1024 /* rows of per-block partial sums per chain in the workspace */
+#define IRS_RESIDUAL_WS_BYTES (IRS_MAX_CHAINS * IRS_RESIDUAL_MAX_BLOCKS * (3 + 4) * 8)
+#define IRS_RESIDUAL_MAP_SUMMARY_INTS 2
+#define IRS_RESIDUAL_MAP_SUMMARY_FLOATS 2
+#define IRS_RESIDUAL_MAP_WS_BYTES (1024 * (IRS_RESIDUAL_MAP_SUMMARY_INTS + IRS_RESIDUAL_MAP_SUMMARY_FLOATS) * 8)
+int irs_residual_histogram(const float* residuals, int C, const uint8_t* mask, int D, int H, int W, float half_range, int bins,
+                           long long* hist, long long* counts, double* sums, int records_before, void* ws, size_t ws_bytes,
+                           void* stream);
+int irs_residual_nll_update(const float* residuals, int C, int D, int H, int W, const double* log_weight, const double* inv_std,
+                            int K, float* mean, int32_t* count, int records_before, void* stream);
+int irs_residual_nll_finalize(const float* mean, const int32_t* count, const uint8_t* mask, int D, int H, int W,
+                              long long* isummary, double* fsummary, void* ws, size_t ws_bytes, void* stream);
+
 /* Landmark propagation (absent in the reference, which has no point-set operator): a sampled displacement evaluated at K
  * positions that are no voxel centres, and the posterior of the mapped landmarks with their target registration error (TRE).
  * warped(x) = moving(x + d(x)): a point p of the fixed grid maps to p + d(p) in the moving image; points of the moving space

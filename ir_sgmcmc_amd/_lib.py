@@ -37,6 +37,10 @@ IRS_LOCAL_MAX_RADIUS, IRS_LOCAL_STATS, IRS_LOCAL_MAX_BLOCKS = 4, 7, 1024
 IRS_LOCAL_WS_BYTES = IRS_MAX_CHAINS * IRS_LOCAL_MAX_BLOCKS * IRS_LOCAL_STATS * 8
 IRS_LOCAL_MAP_SUMMARY_INTS, IRS_LOCAL_MAP_SUMMARY_FLOATS = 2, 3
 IRS_LOCAL_MAP_WS_BYTES = 1024 * (IRS_LOCAL_MAP_SUMMARY_INTS + IRS_LOCAL_MAP_SUMMARY_FLOATS) * 8
+IRS_RESIDUAL_MIN_BINS, IRS_RESIDUAL_MAX_BINS, IRS_RESIDUAL_MAX_BLOCKS = 2, 512, 1024
+IRS_RESIDUAL_WS_BYTES = IRS_MAX_CHAINS * IRS_RESIDUAL_MAX_BLOCKS * (3 + 4) * 8
+IRS_RESIDUAL_MAP_SUMMARY_INTS, IRS_RESIDUAL_MAP_SUMMARY_FLOATS = 2, 2
+IRS_RESIDUAL_MAP_WS_BYTES = 1024 * (IRS_RESIDUAL_MAP_SUMMARY_INTS + IRS_RESIDUAL_MAP_SUMMARY_FLOATS) * 8
 IRS_SURFACE_MAX_LEVELS, IRS_SURFACE_SUMMARY_INTS, IRS_SURFACE_SUMMARY_FLOATS, IRS_SURFACE_MAX_BLOCKS = 4, 7, 6, 512
 IRS_SURFACE_WS_BYTES = IRS_MAX_LABELS * IRS_SURFACE_MAX_BLOCKS * (IRS_SURFACE_SUMMARY_INTS + IRS_SURFACE_SUMMARY_FLOATS) * 8
 IRS_DATA_GMM_LCC, IRS_DATA_SSD = 0, 1
@@ -192,6 +196,9 @@ SIGNATURES = {
                              C.c_size_t, _P],
     'irs_local_similarity_update': [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P],
     'irs_local_similarity_finalize': [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, C.c_size_t, _P],
+    'irs_residual_histogram': [_P, _I, _P, _I, _I, _I, _F, _I, _P, _P, _P, _I, _P, C.c_size_t, _P],
+    'irs_residual_nll_update': [_P, _I, _I, _I, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), _I, _P, _P, _I, _P],
+    'irs_residual_nll_finalize': [_P, _P, _P, _I, _I, _I, _P, _P, _P, C.c_size_t, _P],
     'irs_create': [C.POINTER(IrsConfig), C.POINTER(_P)],
     'irs_destroy': [_P],
     'irs_workspace_bytes': [_P],

@@ -1125,4 +1125,62 @@ int irs_local_similarity_finalize(const float* mean, const float* low, const int
     return 0;
 }
 
+// ================================================================================================
+// residual model check (residual_kernels.hip)
+// ================================================================================================
+int irs_residual_histogram(const float* residuals, int C, const uint8_t* mask, int D, int H, int W, float half_range, int bins,
+                           long long* hist, long long* counts, double* sums, int records_before, void* ws, size_t ws_bytes,
+                           void* stream) {
+    if (!residuals || !hist || !counts || !sums || !ws) return fail("irs_residual_histogram: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (bins < IRS_RESIDUAL_MIN_BINS || bins > IRS_RESIDUAL_MAX_BINS)
+        return fail("irs_residual_histogram: bins = %d, %d..%d", bins, IRS_RESIDUAL_MIN_BINS, IRS_RESIDUAL_MAX_BINS);
+    if (!positive_finite(half_range))
+        return fail("irs_residual_histogram: half_range = %g, a finite value > 0 needed", (double)half_range);
+    ResBins bn;
+    bn.bins = bins;
+    bn.half_range = half_range;
+    bn.inv_w = (float)bins / (2.0f * half_range);  // fp32, as the definition states it
+    if (!positive_finite(bn.inv_w))
+        return fail("irs_residual_histogram: half_range = %g is too wide or too narrow for float32 bins", (double)half_range);
+    if (!local_dims_ok(__func__, D, H, W)) return 1;
+    if (!records_ok(__func__, records_before, C, INT32_MAX, "overflow the int32 record count")) return 1;
+    if (!workspace_ok(__func__, ws_bytes, (size_t)IRS_RESIDUAL_WS_BYTES, "IRS_RESIDUAL_WS_BYTES")) return 1;
+    launch_residual_histogram(residuals, mask, (int64_t)D * H * W, C, bn, hist, counts, sums, records_before, ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_residual_nll_update(const float* residuals, int C, int D, int H, int W, const double* log_weight, const double* inv_std,
+                            int K, float* mean, int32_t* count, int records_before, void* stream) {
+    if (!residuals || !log_weight || !inv_std || !mean || !count) return fail("irs_residual_nll_update: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (K < 1 || K > IRS_MAX_COMPONENTS) return fail("irs_residual_nll_update: K = %d components, 1..%d", K, IRS_MAX_COMPONENTS);
+    ResMixture mix;
+    memset(&mix, 0, sizeof(mix));
+    mix.K = K;
+    for (int k = 0; k < K; ++k) {
+        if (!isfinite(log_weight[k])) return fail("irs_residual_nll_update: log_weight[%d] = %g, a finite value needed", k, log_weight[k]);
+        if (!(inv_std[k] > 0.0) || !isfinite(inv_std[k]))
+            return fail("irs_residual_nll_update: inv_std[%d] = %g, a finite value > 0 needed", k, inv_std[k]);
+        mix.log_weight[k] = log_weight[k];
+        mix.inv_std[k] = inv_std[k];
+    }
+    if (!local_dims_ok(__func__, D, H, W)) return 1;
+    if (!records_ok(__func__, records_before, C, INT32_MAX, "overflow the int32 sample count")) return 1;
+    launch_residual_nll_update(residuals, C, (int64_t)D * H * W, mix, mean, count, records_before, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_residual_nll_finalize(const float* mean, const int32_t* count, const uint8_t* mask, int D, int H, int W,
+                              long long* isummary, double* fsummary, void* ws, size_t ws_bytes, void* stream) {
+    if (!mean || !count || !isummary || !fsummary || !ws) return fail("irs_residual_nll_finalize: bad arguments");
+    if (!local_dims_ok(__func__, D, H, W)) return 1;
+    if (!workspace_ok(__func__, ws_bytes, (size_t)IRS_RESIDUAL_MAP_WS_BYTES, "IRS_RESIDUAL_MAP_WS_BYTES")) return 1;
+    launch_residual_nll_finalize(mean, count, (int64_t)D * H * W, mask, isummary, fsummary, ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 }  // extern "C"

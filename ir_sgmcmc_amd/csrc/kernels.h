@@ -356,6 +356,29 @@ void launch_local_similarity_update(const float* lncc, int C, int64_t V, float* 
 void launch_local_similarity_finalize(const float* mean, const float* low, const int32_t* count, int64_t V, const uint8_t* mask,
                                       long long* isummary, double* fsummary, void* ws, hipStream_t st);
 
+// ---- residual_kernels.hip: the residuals against the mixture that models them -- histogram, moments and the per-voxel NLL
+struct ResBins {
+    int bins;
+    float half_range, inv_w;  // bins over [-half_range, half_range]; inv_w = bins / (2 half_range), formed in fp32
+};
+struct ResMixture {  // passed to the kernel by value
+    double log_weight[IRS_MAX_COMPONENTS];  // ln pi_k - ln sigma_k - 1/2 ln 2 pi
+    double inv_std[IRS_MAX_COMPONENTS];     // 1 / sigma_k
+    int K;
+};
+// residuals (C,V) float32; mask (V) uint8 or nullptr; hist (C,bins) / counts (C,3) int64 and sums (C,4) double, overwritten
+// when records_before == 0 and added to otherwise (hist is zeroed on the stream here); ws: C * min(blocks, IRS_RESIDUAL_MAX_BLOCKS)
+// rows of 3 int64 + 4 doubles (at most IRS_RESIDUAL_WS_BYTES)
+void launch_residual_histogram(const float* residuals, const uint8_t* mask, int64_t V, int C, const ResBins& bn, long long* hist,
+                               long long* counts, double* sums, int records_before, void* ws, hipStream_t st);
+// residuals (C,V) float32 -> mean (V) float32, count (V) int32: the NLL of every finite z under `mix`, folded in chain order
+// (records_before == 0 overwrites)
+void launch_residual_nll_update(const float* residuals, int C, int64_t V, const ResMixture& mix, float* mean, int32_t* count,
+                                int records_before, hipStream_t st);
+// isummary IRS_RESIDUAL_MAP_SUMMARY_INTS int64, fsummary IRS_RESIDUAL_MAP_SUMMARY_FLOATS doubles; ws: IRS_RESIDUAL_MAP_WS_BYTES
+void launch_residual_nll_finalize(const float* mean, const int32_t* count, int64_t V, const uint8_t* mask, long long* isummary,
+                                  double* fsummary, void* ws, hipStream_t st);
+
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h
 }  // namespace irs

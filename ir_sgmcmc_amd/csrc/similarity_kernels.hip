@@ -23,6 +23,7 @@
 // Two identical call sequences are bit-identical: integer histogram, fixed-order double sums, grids that depend on (V, C) only.
 #include <algorithm>
 
+#include "histogram_device.h"
 #include "kernels.h"
 #include "summary_device.h"
 
@@ -57,21 +58,6 @@ __device__ __forceinline__ void sim_block_reduce(SimAcc& a, double* smem) {
 }
 
 constexpr int kSimMaxBlocks = IRS_SIMILARITY_MAX_BLOCKS;  // all chains together: 256 CUs x 4 blocks of 4 wavefronts
-
-// h[cell] += 1 for every lane with take set.  Wave-uniform control flow: every lane of the wavefront calls it.
-__device__ __forceinline__ void hist_add(uint32_t* h, bool take, int cell, bool aggregate) {
-    if (aggregate) {
-        const unsigned long long todo = __ballot(take);
-        if (todo == 0) return;
-        const int leader = __ffsll(todo) - 1;
-        const int cl = __builtin_amdgcn_readlane(cell, leader);
-        if (__ballot(take && cell != cl) == 0) {  // one bin for the whole wavefront: one add of their number
-            if ((int)(threadIdx.x & (kWave - 1)) == leader) atomicAdd(&h[cl], (uint32_t)__popcll(todo));
-            return;
-        }
-    }
-    if (take) atomicAdd(&h[cell], 1u);
-}
 
 struct SimVoxel {
     bool take;

@@ -62,6 +62,11 @@ signed distance to the same structure's contour in the warped moving segmentatio
 distances of the Hausdorff call) into a Welford mean and M2, 12 * D * H * W bytes whatever the number of records or structures;
 at the end ops.surface_posterior_finalize gives the bias and spread maps and, per structure, the mean signed distance, the
 spread and how often the normal band of the samples holds the fixed boundary.
+
+The residual check (ResidualCheck, residual_check_options) is the one diagnostic of the likelihood: at a logged step the
+histogram of the masked residuals is set against the mixture that models them (residual_check.py), and at a recorded step the
+exact int64 histograms and moment sums are accumulated per chain and -log p(z) under the mixture of that step is folded into a
+per-voxel streaming mean (residual_check.residual_nll_update), 8 * D * H * W bytes whatever the number of records.
 """
 import math
 import numbers
@@ -71,6 +76,7 @@ import numpy as np
 import torch
 
 from . import ops
+from . import residual_check as _rc
 
 
 def diagnostics_period(cfg_trainer):
@@ -1307,6 +1313,148 @@ class LocalSimilarity(_Recorder):
         self.mean.copy_(sd['mean'])
         self.low.copy_(sd['low'])
         self.count.copy_(sd['count'])
+        self.records = int(sd['records'])
+
+
+RESIDUAL_OPTION_KEYS = ('bins', 'range', 'period', 'nll_map', 'save')
+RESIDUAL_DEFAULTS = {'bins': 128, 'range': None, 'nll_map': True, 'save': True}
+RESIDUAL_MAX_BINS = 512  # IRS_RESIDUAL_MAX_BINS
+# logged name -> how it follows from a row of residual_check.residual_fit; the ratios are empirical over model
+RESIDUAL_METRICS = (('KL', lambda r: r['kl']), ('TV', lambda r: r['tv']), ('KS', lambda r: r['ks']), ('chi2', lambda r: r['chi2']),
+                    ('tail', lambda r: r['tail']), ('std_ratio', lambda r: _nan_div(r['std'], r['std_model'])),
+                    ('kurtosis_ratio', lambda r: _nan_div(r['kurtosis'], r['kurtosis_model'])))
+RESIDUAL_MAP_METRICS = ('nll_mean', 'nll_max')
+
+
+def residual_check_options(cfg_trainer):
+    """`trainer.residual_check` -> None when off, else {'period': P, 'bins': B, 'range': h or None, 'nll_map': bool, 'save':
+    bool}.  Absent / false / null: off.  true: 128 bins over +- the largest finite |z| of the unregistered pair's masked
+    residual, the statistics at every logged step, the histogram and the NLL map recorded every log_period_MCMC-th step after
+    the burn-in, the files written.  {"bins": B, "range": h, "period": P, "nll_map": bool, "save": bool} sets any of them.
+    Refuses unknown keys, a non-integer B or a B outside 2 .. 512, an h that is no finite number > 0, a non-integer P or P < 1,
+    a non-bool nll_map or save, a config that records no step (no_samples_MCMC // P < 1) and one that would record more than
+    2^31 - 1 volumes."""
+    what = 'trainer.residual_check'
+
+    def own_keys(opt):
+        own = {**RESIDUAL_DEFAULTS, **{k: v for k, v in opt.items() if k != 'period'}}
+        b = own['bins']
+        if isinstance(b, bool) or not isinstance(b, numbers.Integral):
+            raise ValueError(f'{what}.bins must be an integer, got {b!r}')
+        if not 2 <= b <= RESIDUAL_MAX_BINS:
+            raise ValueError(f'{what}: bins must be in 2 .. {RESIDUAL_MAX_BINS}, got {b}')
+        h = own['range']
+        if h is not None and not (_number(h) and math.isfinite(h) and h > 0):
+            raise ValueError(f'{what}.range must be a finite number > 0, got {h!r}')
+        for key in ('nll_map', 'save'):
+            if not isinstance(own[key], bool):
+                raise ValueError(f'{what}.{key} must be true or false, got {own[key]!r}')
+        return {'bins': int(b), 'range': None if h is None else float(h), 'nll_map': own['nll_map'], 'save': own['save']}
+
+    return _record_options(cfg_trainer, 'residual_check', RESIDUAL_OPTION_KEYS,
+                           '{"bins": B, "range": h, "period": P, "nll_map": bool, "save": bool}', MAX_RECORDS,
+                           'the sample count holds at most {}', own_keys)
+
+
+def residual_check_metric_names(options, no_chains, vi=False):
+    """the metric names the option adds: the unregistered pair at step 0, the VI sample when VI runs, every chain's sample, the
+    histogram pooled over chains and records, and the two figures of the NLL map"""
+    prefixes = (['VI/train/residuals'] + (['VI/residuals'] if vi else []) + [f'MCMC/chain_{i}/residuals' for i in range(no_chains)] +
+                ['MCMC/residuals'])
+    return ([f'{p}/{k}' for p in prefixes for k, _ in RESIDUAL_METRICS] +
+            ([f'MCMC/residuals/{k}' for k in RESIDUAL_MAP_METRICS] if options['nll_map'] else []))
+
+
+def residual_metrics(row):
+    """a row of residual_check.residual_fit -> {logged name: value} in the order of RESIDUAL_METRICS"""
+    return {k: f(row) for k, f in RESIDUAL_METRICS}
+
+
+def residual_map_summary(isummary, fsummary, n):
+    """the summary of the NLL map from residual_check.residual_nll_finalize's columns (host ints / floats): isummary {voxels,
+    voxels without a finite residual}, fsummary {sum / max of the mean map} over the others, n records; NaN when no masked
+    voxel has a sample"""
+    voxels, empty = (int(x) for x in isummary)
+    m_sum, m_max = (float(x) for x in fsummary)
+    some = voxels - empty
+    return {'records': int(n), 'voxels': voxels, 'empty_voxels': empty, 'nll_mean': _nan_div(m_sum, some),
+            'nll_max': m_max if some else float('nan')}
+
+
+class ResidualCheck(_Recorder):
+    """Does the likelihood describe the residuals it is applied to?  Over the recorded steps: per chain the exact int64 histogram
+    of the residual z over `bins` equal bins of [-half_range, half_range] under the fixed mask, its counts and moment sums
+    (residual_check.residual_histogram: `hist` (C,bins), `counts` (C,3) int64, `sums` (C,4) float64), and -- with `nll_map` --
+    per voxel the streaming mean of -log p(z) under the mixture of that step and the number of finite residuals (`mean` (D,H,W)
+    float32, `count` (D,H,W) int32; residual_check.residual_nll_update), 8 D H W bytes whatever the number of records.
+    `set_mixture` gives the mixture the next record is scored under; `record(residuals)` takes the (C,1,D,H,W) float32
+    residuals of one step; `finalize(std, proportions, mask)` sets the pooled histogram against a mixture and summarises the
+    map."""
+    noun = 'residual check'
+
+    def __init__(self, dims, no_chains, device, half_range, bins=128, mask=None, nll_map=True):
+        self.dims, self.no_chains, self.bins = tuple(int(d) for d in dims), int(no_chains), int(bins)
+        if len(self.dims) != 3 or min(self.dims) < 1:
+            raise ValueError(f'residual check: three dims of at least 1, got {self.dims}')
+        self.device, self.nll_map = device, bool(nll_map)
+        self.half_range = float(torch.tensor(float(half_range), dtype=torch.float32))  # the value the kernel bins with
+        if not (math.isfinite(self.half_range) and self.half_range > 0):
+            raise ValueError(f'residual check: half_range = {half_range!r}, a finite value > 0 needed')
+        self.mask = None if mask is None else _bool_mask(mask, device).reshape(1, 1, *self.dims).contiguous()
+        self.hist = torch.zeros((self.no_chains, self.bins), device=device, dtype=torch.int64)
+        self.counts = torch.zeros((self.no_chains, 3), device=device, dtype=torch.int64)
+        self.sums = torch.zeros((self.no_chains, 4), device=device, dtype=torch.float64)
+        self.sums[:, 3] = -math.inf
+        self.mean = torch.zeros(self.dims if self.nll_map else (0, 0, 0), device=device, dtype=torch.float32)
+        self.count = torch.zeros(self.dims if self.nll_map else (0, 0, 0), device=device, dtype=torch.int32)
+        self.mixture = None
+
+    def set_mixture(self, log_weight, inv_std):
+        self.mixture = (list(log_weight), list(inv_std))
+
+    def _update(self, residuals):
+        if residuals.shape[0] != self.no_chains:
+            raise ValueError(f'residual check: {residuals.shape[0]} chains recorded, the state holds {self.no_chains}')
+        residuals = residuals.contiguous()
+        _rc.residual_histogram(residuals, self.mask, self.half_range, self.bins, self.hist, self.counts, self.sums, self.records)
+        if self.nll_map:
+            if self.mixture is None:
+                raise RuntimeError('ResidualCheck.record: set_mixture first')
+            _rc.residual_nll_update(residuals, *self.mixture, self.mean, self.count, self.records)
+
+    def pooled(self):
+        """-> (hist (bins,), counts (3,) int64, sums (4,) float64) on the host, over chains and records"""
+        hist, counts, sums = self.hist.cpu(), self.counts.cpu(), self.sums.cpu()
+        return hist.sum(0).numpy(), counts.sum(0).numpy(), np.concatenate([sums[:, :3].sum(0).numpy(), [float(sums[:, 3].max())]])
+
+    def finalize(self, std, proportions, mask=None):
+        """-> (the NLL map (D,H,W) float32 with NaN where no residual was ever finite -- None without nll_map --, summary):
+        {'records', 'half_range', 'bins', 'fit': residual_fit of the pooled histogram against (std, proportions), 'n_nonfinite',
+        'n_clipped'[, 'nll': residual_map_summary over the mask]}"""
+        self._need_records('finalize')
+        hist, counts, sums = self.pooled()
+        summary = {'records': self.records, 'half_range': self.half_range, 'bins': self.bins,
+                   'fit': _rc.residual_fit(hist, counts, sums, self.half_range, std, proportions),
+                   'n_nonfinite': int(counts[1]), 'n_clipped': int(counts[2])}
+        if not self.nll_map:
+            return None, summary
+        isum, fsum = _rc.residual_nll_finalize(self.mean, self.count, _bool_mask(mask, self.device))
+        summary['nll'] = residual_map_summary(*_host_summary(isum, fsum), self.records)
+        return self.mean.where(self.count > 0, self.mean.new_full((), math.nan)), summary
+
+    _STATE = ('hist', 'counts', 'sums', 'mean', 'count')
+
+    def state_dict(self):
+        return {'records': self.records, 'half_range': self.half_range, **{k: getattr(self, k).detach().cpu() for k in self._STATE}}
+
+    def load_state_dict(self, sd):
+        for name in self._STATE:
+            if tuple(sd[name].shape) != tuple(getattr(self, name).shape):
+                raise ValueError(f'residual check state of shape {tuple(sd[name].shape)} ({name}) does not match this run '
+                                 f'({tuple(getattr(self, name).shape)})')
+        for name in self._STATE:
+            getattr(self, name).copy_(sd[name])
+        self.half_range = float(sd['half_range'])
         self.records = int(sd['records'])
 
 

@@ -268,6 +268,39 @@ def save_local_similarity_of_mean(logger, save_dirs, spacing, lncc, ssim, model=
         save_im_to_disk(im, path.join(folder, f'{model}_{name}_of_mean.nii.gz'), spacing)
 
 
+def residual_histogram_rows(edges, hist, model_probability):
+    """the table of samples/{model}_residual_hist.csv: header, then one row per bin -- bin_lo, bin_hi, the count of every
+    chain, their sum, and the mixture's mass in the bin"""
+    hist = _np(hist)
+    header = ['bin_lo', 'bin_hi'] + [f'count_chain_{i}' for i in range(hist.shape[0])] + ['count', 'model_probability']
+    rows = [[repr(float(edges[b])), repr(float(edges[b + 1]))] + [str(int(c)) for c in hist[:, b]] +
+            [str(int(hist[:, b].sum())), repr(float(model_probability[b]))] for b in range(hist.shape[1])]
+    return header, rows
+
+
+def save_residual_histogram(logger, save_dirs, edges, hist, model_probability, model='MCMC'):
+    """the recorded residual histogram against the mixture (the numbers behind the reference's log_hist_res figure):
+    samples/{model}_residual_hist.csv, residual_histogram_rows"""
+    folder = _folder(save_dirs, 'samples')
+    header, rows = residual_histogram_rows(edges, hist, model_probability)
+    with open(path.join(folder, f'{model}_residual_hist.csv'), 'w', newline='\n') as f:
+        f.write(','.join(header) + '\n')
+        for row in rows:
+            f.write(','.join(row) + '\n')
+    logger.info(f'{model} residual histogram: {len(rows)} bins -> {model}_residual_hist.csv')
+
+
+def save_residual_nll(logger, save_dirs, spacing, mean, mask, model='MCMC'):
+    """the posterior mean of the per-voxel negative log-likelihood: samples/{model}_nll_mean[_masked].nii.gz (float32; NaN -- no
+    finite residual there -- written as 0, the masked one 0 outside the mask too)"""
+    folder = _folder(save_dirs, 'samples')
+    mask = mask.reshape(mean.shape).to(mean.device) != 0
+    im, undefined = _nan_to_zero(mean)
+    logger.info(f'{model}_nll_mean: {undefined} voxels without a finite residual written as 0')
+    save_im_to_disk(im, path.join(folder, f'{model}_nll_mean.nii.gz'), spacing)
+    save_im_to_disk(im.where(mask, im.new_zeros(())), path.join(folder, f'{model}_nll_mean_masked.nii.gz'), spacing)
+
+
 def save_surface_posterior(logger, save_dirs, spacing, bias, std, model='MCMC'):
     """the surface posterior (absent in the reference): samples/{model}_surface_bias.nii.gz and samples/{model}_surface_std.nii.gz
     (float32).  The maps live on the contours of the fixed structures: NaN everywhere else, and in the std map where a contour

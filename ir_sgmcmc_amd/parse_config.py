@@ -16,6 +16,7 @@ from .diagnostics import (COVARIANCE_METRICS, ICE_SPACES, JACOBIAN_METRICS, LABE
                           hausdorff_metric_names, hausdorff_options, image_similarity_metric_names, image_similarity_options,
                           inverse_consistency_options, jacobian_posterior_options, label_posterior_options,
                           landmark_metric_names, landmark_options, local_similarity_metric_names, local_similarity_options,
+                          residual_check_metric_names, residual_check_options,
                           native_resolution_options, surface_metric_names, surface_posterior_options)
 from .logger import setup_logging
 from .model import distributions as model_distr
@@ -135,6 +136,9 @@ class ConfigParser:
             m += landmark_metric_names(landmarks, C)
         if local_similarity_options(self['trainer']) is not None:
             m += local_similarity_metric_names(C)
+        residuals = residual_check_options(self['trainer'])
+        if residuals is not None:
+            m += residual_check_metric_names(residuals, C, bool(self['trainer'].get('VI', False)))
         return m
 
     def init_transformation_and_registration_modules(self):

@@ -11,6 +11,7 @@ Inside `_SGLD_transition` nothing runs in torch: one call into the C ABI launche
 HIP stream (ir_sgmcmc_amd/csrc/api_ctx.hip: transition_impl).  The hyper-parameters of the loss objects are mirrored into
 the device state once (`_engine_init`) and read back lazily (`sync_parameters`) when something logs them.
 """
+import math
 import time
 from collections import namedtuple
 
@@ -26,21 +27,24 @@ from ..diagnostics import (COVARIANCE_METRICS, ChainMoments, DisplacementCovaria
                            diagnostics_period, displacement_covariance_options, displacement_quantiles_options,
                            ess_options, hausdorff_options, image_similarity_options, inverse_consistency_options, is_recorded,
                            jacobian_posterior_options, label_posterior_options, landmark_options, local_similarity_options,
-                           native_resolution_options, SIMILARITY_METRICS, voxel_scale)
+                           native_resolution_options, ResidualCheck, residual_check_options, residual_metrics,
+                           SIMILARITY_METRICS, voxel_scale)
 from ..engine import EngineConfig, TransitionEngine
 from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_quantiles, save_ess,
                       save_field, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_landmarks,
-                      save_local_similarity_of_mean, save_local_similarity_posterior, save_native_mean, save_native_sample, save_rhat,
-                      save_sample, save_surface_posterior)
-from ..utils import (calc_DSC_GPU, calc_image_similarity, calc_norm, calc_no_non_diffeomorphic_voxels, init_identity_grid_3D,
-                     local_similarity_rows, sample_q_v, transform_coordinates)
+                      save_local_similarity_of_mean, save_local_similarity_posterior, save_native_mean, save_native_sample,
+                      save_residual_histogram, save_residual_nll, save_rhat, save_sample, save_surface_posterior)
+from .. import residual_check
+from ..utils import (calc_DSC_GPU, calc_image_similarity, calc_norm, calc_no_non_diffeomorphic_voxels, calc_residual_check,
+                     init_identity_grid_3D, local_similarity_rows, sample_q_v, transform_coordinates)
 from .vi import VIMixin
 
 
 # A posterior recorder of the MCMC stage (Trainer._recorders): its checkpoint key, its state object (diagnostics.py), its
 # period, the trainer.<option> that switches it on, the noun of the resume error, what it records of a transition (an
 # output: 'displacement', 'transformation'; 'seg_warped': the warped moving segmentation; 'velocity': the dense velocity the
-# exponential integrated; 'lncc': the LNCC maps of the warped moving image; or a tuple of these, recorded as a tuple), its
+# exponential integrated; 'lncc': the LNCC maps of the warped moving image; 'residuals': the dense residuals of the data term;
+# or a tuple of these, recorded as a tuple), its
 # _finish_* method and what that takes first ('fixed': the fixed image's dict, 'moving_mask': the mask of the displacement std
 # map, 'masks': {'fixed': ..., 'moving': ...})
 Recorder = namedtuple('Recorder', 'key state period option noun records finish takes')
@@ -134,6 +138,11 @@ class Trainer(VIMixin, BaseTrainer):
         self.local_options = local_similarity_options(cfg_trainer)
         self._local_similarity, self._local_ranges, self._local_warned = None, None, False
         self.local_lncc_mean, self.local_lncc_min, self.local_similarity_summary = None, None, None
+        # residual model check: the residuals against the mixture that models them, and the per-voxel NLL map
+        # (residual_check.py, diagnostics.ResidualCheck): None when trainer.residual_check is off
+        self.residual_options = residual_check_options(cfg_trainer)
+        self._residual_check, self._residual_range, self._residual_warned = None, None, False
+        self.residual_nll_mean, self.residual_summary = None, None
 
     # ---------------------------------------------------------------- engine plumbing
     def _engine_config(self):
@@ -219,7 +228,7 @@ class Trainer(VIMixin, BaseTrainer):
 
     def _recorders(self):
         """the active recorders, in the order they record and finish: moments, labels, surfaces, Jacobian, covariance,
-        quantiles, inverse consistency, landmarks, local similarity"""
+        quantiles, inverse consistency, landmarks, local similarity, residual check"""
         period = lambda options: options and options['period']
         rows = (('chain_moments', self._chain_moments, self.diagnostics_period, 'convergence_diagnostics', 'chain moments',
                  'displacement', self._finish_diagnostics, 'moving_mask'),
@@ -240,7 +249,9 @@ class Trainer(VIMixin, BaseTrainer):
                  ('displacement', 'velocity') if self.landmark_options and self.landmark_options['inverse'] else 'displacement',
                  self._finish_landmarks, 'masks'),
                 ('local_similarity', self._local_similarity, period(self.local_options), 'local_similarity', 'local similarity',
-                 'lncc', self._finish_local_similarity, 'fixed'))
+                 'lncc', self._finish_local_similarity, 'fixed'),
+                ('residual_check', self._residual_check, period(self.residual_options), 'residual_check', 'residual check',
+                 'residuals', self._finish_residual_check, 'fixed'))
         return [Recorder(*row) for row in rows if row[1] is not None]
 
     # ---------------------------------------------------------------- checkpoint / resume (absent in the reference)
@@ -424,6 +435,11 @@ class Trainer(VIMixin, BaseTrainer):
         if self.local_options is not None:
             self._local_init(fixed, moving)
             self._local_similarity = LocalSimilarity(self._outputs['displacement'].shape[2:], self.device)
+        if self.residual_options is not None:
+            self._residual_init(fixed, moving)
+            self._residual_check = ResidualCheck(self._outputs['residuals'].shape[2:], self.no_chains, self.device,
+                                                 self._residual_range, self.residual_options['bins'], fixed['mask'][:1],
+                                                 self.residual_options['nll_map'])
         if cfg_trainer.get('resume'):
             self.load_checkpoint(cfg_trainer['resume'])
             first = self._sample_no + 1
@@ -500,6 +516,10 @@ class Trainer(VIMixin, BaseTrainer):
                 local = self._local_maps(fixed, output['im_moving_warped'], ('lncc',))
                 lncc = local['lncc']
                 self._log_local([f'MCMC/chain_{idx}/local_similarity' for idx in range(self.no_chains)], local['rows'])
+            if self.residual_options is not None and logged:
+                self.sync_parameters()  # the mixture as it stands at this sample
+                self._log_residuals([f'MCMC/chain_{idx}/residuals' for idx in range(self.no_chains)],
+                                    self._residual_rows(aux['residuals'], fixed['mask'][:1]))
             due = [r for r in recorders if is_recorded(sample_no, self.no_iters_burn_in, r.period)]
             if due:
                 self.engine.flush()  # as above: the buffers hold sample `sample_no` once nothing is pending
@@ -508,7 +528,11 @@ class Trainer(VIMixin, BaseTrainer):
                     seg_warped = self.registration_module(moving['seg'], output['transformation'])
                 if r.records == 'lncc' and lncc is None:
                     lncc = self._local_maps(fixed, output['im_moving_warped'], ('lncc',))['lncc']
+                if r.records == 'residuals':  # scored under the mixture as it stands at this sample
+                    self.sync_parameters()
+                    r.state.set_mixture(*residual_check.mixture_terms(data_loss)[2:])
                 pick = lambda name: (seg_warped if name == 'seg_warped' else lncc if name == 'lncc' else
+                                     aux['residuals'] if name == 'residuals' else
                                      self._dense_velocity(output) if name == 'velocity' else output[name])
                 r.state.record(tuple(pick(n) for n in r.records) if isinstance(r.records, tuple) else pick(r.records))
             if self._inverse_consistency is not None:
@@ -847,6 +871,81 @@ class Trainer(VIMixin, BaseTrainer):
         if save_outputs and self.local_options['save']:
             save_local_similarity_posterior(self.logger, self.config.save_dirs, spacing, self.local_lncc_mean, self.local_lncc_min,
                                             mask, 'MCMC')
+
+    def _residual_init(self, fixed, moving):
+        """the half range of the residual histograms, taken once and kept: the option's, else the largest finite |z| of the
+        unregistered pair's residual under the fixed mask (one host read-back)"""
+        if self._residual_range is not None:
+            return
+        h = self.residual_options['range']
+        if h is None:
+            z = self.losses['data']['loss'].map(fixed['im'][:1], moving['im'][:1]).contiguous()
+            h = float(residual_check.residual_histogram(z, fixed['mask'][:1], 1.0, 2)['sums'][0, 3])
+            if not (math.isfinite(h) and h > 0):
+                self.logger.warning(f'residual check: the unregistered pair has no non-zero finite residual under the mask '
+                                    f'(max |z| = {h}); binning over [-1, 1]')
+                h = 1.0
+        self._residual_range = float(torch.tensor(h, dtype=torch.float32))
+        self.logger.info(f'residual check: {self.residual_options["bins"]} bins over [-{self._residual_range:g}, '
+                         f'{self._residual_range:g}]')
+
+    def _residual_rows(self, residuals, mask):
+        """utils.calc_residual_check of (C,1,D,H,W) residuals under `mask` against the data loss as it stands -> one dict per
+        chain; one warning per run when a residual was clipped or not finite"""
+        rows = calc_residual_check(residuals, mask, self.losses['data']['loss'], self._residual_range, self.residual_options['bins'])
+        if not self._residual_warned and any(r['n_clipped'] > 0 or r['n_nonfinite'] > 0 for r in rows):
+            self._residual_warned = True
+            self.logger.warning(f'residual check: {max(r["n_clipped"] for r in rows)} residuals beyond +-{self._residual_range:g} '
+                                f'(counted in the end bins) and {max(r["n_nonfinite"] for r in rows)} non-finite ones (left out); '
+                                f'not reported again in this run')
+        return rows
+
+    def _log_residuals(self, prefixes, rows):
+        for prefix, row in zip(prefixes, rows):
+            for key, value in residual_metrics(row).items():
+                self.metrics.update(f'{prefix}/{key}', value)
+
+    def _residual_summary(self, name, row, what):
+        """self.residual_summary[name] = one fit, and one log line"""
+        if self.residual_summary is None:
+            self.residual_summary = {}
+        self.residual_summary[name] = row
+        fit = row.get('fit', row)
+        self.logger.info(f'residuals of {what} against the mixture over {fit["n"]} values: KL {fit["kl"]:.4g}, TV {fit["tv"]:.4g}, '
+                         f'KS {fit["ks"]:.4g}; std {fit["std"]:.4g} (model {fit["std_model"]:.4g}), kurtosis {fit["kurtosis"]:.4g} '
+                         f'(model {fit["kurtosis_model"]:.4g}), beyond the range {fit["tail"]:.3g} (model {fit["tail_model"]:.3g})')
+
+    def _log_residuals_unregistered(self, fixed, moving):
+        """step 0: the unregistered pair's residual against the mixture as the GMM initialisation left it, under
+        VI/train/residuals/*"""
+        self._residual_init(fixed, moving)
+        self.writer.set_step(0)
+        z = self.losses['data']['loss'].map(fixed['im'][:1], moving['im'][:1])
+        row = self._residual_rows(z, fixed['mask'][:1])[0]
+        self._log_residuals(['VI/train/residuals'], [row])
+        self._residual_summary('unregistered', row, 'the unregistered pair')
+
+    def _finish_residual_check(self, fixed, spacing, save_outputs):
+        """the recorded histogram pooled over chains and records against the final mixture, and the NLL map over the FIXED mask
+        -> self.residual_nll_mean, residual_summary['posterior'], the MCMC/residuals/* metrics and, with save_outputs and the
+        option's save, samples/MCMC_residual_hist.csv and samples/MCMC_nll_mean[_masked].nii.gz"""
+        rc, mask = self._residual_check, fixed['mask'][0]
+        self.sync_parameters()
+        std, proportions, _, _ = residual_check.mixture_terms(self.losses['data']['loss'])
+        self.residual_nll_mean, s = rc.finalize(std, proportions, mask)
+        self._log_residuals(['MCMC/residuals'], [s['fit']])
+        if rc.nll_map:
+            self.metrics.update('MCMC/residuals/nll_mean', s['nll']['nll_mean'])
+            self.metrics.update('MCMC/residuals/nll_max', s['nll']['nll_max'])
+            self.logger.info(f'NLL map of {s["records"]} samples over {s["nll"]["voxels"]} masked voxels ({s["nll"]["empty_voxels"]} '
+                             f'without a finite residual): mean {s["nll"]["nll_mean"]:.6g}, max {s["nll"]["nll_max"]:.6g}')
+        self._residual_summary('posterior', s, f'{s["records"]} recorded volumes')
+        if save_outputs and self.residual_options['save']:
+            p, _ = residual_check.model_probabilities(rc.half_range, rc.bins, std, proportions)
+            save_residual_histogram(self.logger, self.config.save_dirs, residual_check.bin_edges(rc.half_range, rc.bins), rc.hist, p,
+                                    'MCMC')
+            if rc.nll_map:
+                save_residual_nll(self.logger, self.config.save_dirs, spacing, self.residual_nll_mean, mask, 'MCMC')
 
     def _landmarks_init(self, dims):
         """trainer.landmarks -> self._landmarks (diagnostics.LandmarkPair), once: the landmark files' voxel indices carried to

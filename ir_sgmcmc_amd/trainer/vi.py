@@ -206,6 +206,10 @@ class VIMixin:
                 if (iter_no % self.log_period_VI == 0 or iter_no == self.no_iters_VI) and 'seg' in moving and self.structures_dict:
                     seg_warped = self.registration_module(moving['seg'], output['transformation'].detach())
                     self._log_segmentation_metrics(('VI/train',), fixed['seg'], seg_warped, spacing)
+                if (iter_no % self.log_period_VI == 0 or iter_no == self.no_iters_VI) and self.residual_options is not None:
+                    # the masked residuals of the sample this iteration already has, as one row of voxels; nothing is accumulated
+                    z = aux['residuals'].detach().reshape(1, 1, 1, 1, -1)
+                    self._log_residuals(['VI/residuals'], self._residual_rows(z, None))
 
     @torch.no_grad()
     def _test_VI(self, fixed, moving, var_params_q_v):
@@ -253,13 +257,16 @@ class VIMixin:
     def _metrics_init(self, fixed, moving):
         """trainer.py:550-567, the metrics only: ASD and Dice of the unregistered pair at step 0 -- and, with
         trainer.image_similarity on, its intensity similarity, with trainer.landmarks its TRE and with
-        trainer.local_similarity its local similarity, which need no segmentation"""
+        trainer.local_similarity its local similarity, which need no segmentation, and with trainer.residual_check its residual
+        against the mixture"""
         if self.similarity_options is not None:
             self._log_similarity_unregistered(fixed, moving)
         if self.landmark_options is not None:
             self._log_landmarks_unregistered(fixed)
         if self.local_options is not None:
             self._log_local_unregistered(fixed, moving)
+        if self.residual_options is not None:
+            self._log_residuals_unregistered(fixed, moving)
         if 'seg' not in fixed or 'seg' not in moving or not self.structures_dict:
             return
         self.writer.set_step(0)

@@ -327,6 +327,21 @@ def calc_local_similarity(fixed, moving, mask=None, radius=2, fixed_range=None, 
     return local_similarity_rows(_ops.local_similarity(fixed, moving, mask, radius, fixed_range, moving_range, want=())['stats'])
 
 
+@torch.no_grad()
+def calc_residual_check(residuals, mask, data_loss, half_range, bins=128):
+    """Do the residuals look like the likelihood that models them (the numbers behind the reference's log_hist_res figure,
+    logger/visualization.py:64-86)?  residuals (C,1,D,H,W) float32 on the device -- the unscaled z of data_loss.map --, mask
+    (1,1,D,H,W) bool / uint8 or None, data_loss a GMM or an SSD, bins equal bins over [-half_range, half_range].  -> one dict
+    per chain: the entries of residual_check.residual_fit plus 'n_nonfinite' and 'n_clipped'; the three small state tensors are read back."""
+    from .. import residual_check as _rc
+    half_range = float(torch.tensor(float(half_range), dtype=torch.float32))  # the value the kernel bins with
+    out = _rc.residual_histogram(residuals.contiguous(), mask, half_range, bins)
+    std, proportions, _, _ = _rc.mixture_terms(data_loss)
+    counts = out['counts'].tolist()
+    rows = _rc.residual_fit(out['hist'], counts, out['sums'], half_range, std, proportions)
+    return [{**row, 'n_nonfinite': int(c[1]), 'n_clipped': int(c[2])} for row, c in zip(rows, counts)]
+
+
 def rescale_residuals(res, mask, data_loss):
     """VD-rescaled residual x = sum_k r_k (z / sigma_k)^2 (utils/util.py:330-347).  The reference obtains it as
     sum_k s_k * d(-log p)/d(s_k) with a nested backward; the closed form with the responsibilities r_k is the same number."""
