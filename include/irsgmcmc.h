@@ -306,6 +306,33 @@ int irs_displacement_covariance_finalize(const float* mean, const float* comomen
                                          const uint8_t* mask, float* std, float* direction, float* anisotropy, long long* isummary,
                                          double* fsummary, void* ws, size_t ws_bytes, void* stream);
 
+/* Posterior comparison (absent in the reference, which writes the VI and the MCMC displacement std and compares nothing): per
+ * voxel, the distances between the 3-D Gaussians fitted to two states A and B of irs_displacement_covariance_update.
+ *  - irs_posterior_compare: mean_x (3,D,H,W) and comoment_x (6,D,H,W: xx, yy, zz, xy, xz, yz) float32 after n_x >= 2 records,
+ *    every dim >= 2; scale: 3 host floats, finite and > 0, one per channel (s); std_floor: f, finite and > 0.  Per voxel, in
+ *    double: S_X = diag(s) comoment_X diag(s) / (n_X - 1), Delta = s o (mean_A - mean_B); S_A and S_B are diagonalised by the 5
+ *    cyclic Jacobi sweeps of irs_displacement_covariance_finalize, eigenvalues clamped at 0.  Four (D,H,W) float32 planes:
+ *    shift = |Delta|_2.  log_std_ratio = 1/2 ln(t_A / t_B), t_X = max(tr S_X, 3 f^2): negative where A is the narrower;
+ *    exactly 0 for t_A == t_B and exactly antisymmetric under A <-> B.  bures = sqrt(max(tr S_A + tr S_B - 2 sum_i
+ *    sqrt(max(lambda_i(R), 0)), 0)), R = S_B^1/2 S_A S_B^1/2, formed symmetric in B's eigenbasis and diagonalised by the same
+ *    sweeps; no floor (the 2-Wasserstein distance of the two Gaussians is sqrt(shift^2 + bures^2)).  jeffreys = 1/2 [tr(S~_B^-1
+ *    S~_A) + tr(S~_A^-1 S~_B) - 6 + Delta^T (S~_A^-1 + S~_B^-1) Delta] = KL(A|B) + KL(B|A), S~_X = S_X with every eigenvalue
+ *    raised to at least f^2.  A voxel with a non-finite value among its 18 state values gives NaN in all four planes.  mask
+ *    (D,H,W) uint8 or NULL (whole volume).  isummary: IRS_COMPARE_SUMMARY_INTS int64 over the mask {voxels, voxels with a
+ *    non-finite state, voxels where one of the six eigenvalues was raised to f^2, voxels with log_std_ratio < 0}.  fsummary:
+ *    IRS_COMPARE_SUMMARY_FLOATS doubles over the stored float32 planes of the finite masked voxels {sum shift, max shift, sum
+ *    log_std_ratio, min log_std_ratio, max log_std_ratio, sum bures, max bures, sum w2, max w2 (w2 = sqrt(shift^2 + bures^2)),
+ *    sum jeffreys, max jeffreys, sum tr S_A, sum tr S_B}; a maximum nothing entered is -inf, a minimum +inf.  ws:
+ *    IRS_COMPARE_WS_BYTES of device memory.  One launch and one finish launch.  Deterministic (exact integer sums, fixed-order
+ *    double sums and extrema); no host sync. */
+#define IRS_COMPARE_SUMMARY_INTS 4
+#define IRS_COMPARE_SUMMARY_FLOATS 13
+#define IRS_COMPARE_WS_BYTES (1024 * (IRS_COMPARE_SUMMARY_INTS + IRS_COMPARE_SUMMARY_FLOATS) * 8)
+int irs_posterior_compare(const float* mean_a, const float* comoment_a, int n_a, const float* mean_b, const float* comoment_b, int n_b,
+                          int D, int H, int W, const float* scale, double std_floor, const uint8_t* mask, float* shift,
+                          float* log_std_ratio, float* bures, float* jeffreys, long long* isummary, double* fsummary, void* ws,
+                          size_t ws_bytes, void* stream);
+
 /* Displacement credible intervals (absent in the reference, which keeps moments only): per voxel and channel a histogram of
  * the displacement over the records (one chain's displacement at one recorded step, pooled over chains), and from it the
  * quantiles of given probabilities and the width of the band between the first and the last of them.

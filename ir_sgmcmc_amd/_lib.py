@@ -22,6 +22,8 @@ IRS_JACOBIAN_SUMMARY_INTS, IRS_JACOBIAN_SUMMARY_FLOATS = 4, 5
 IRS_JACOBIAN_WS_BYTES = 1024 * (IRS_JACOBIAN_SUMMARY_INTS + IRS_JACOBIAN_SUMMARY_FLOATS) * 8
 IRS_COVARIANCE_SUMMARY_INTS, IRS_COVARIANCE_SUMMARY_FLOATS = 2, 8
 IRS_COVARIANCE_WS_BYTES = 1024 * (IRS_COVARIANCE_SUMMARY_INTS + IRS_COVARIANCE_SUMMARY_FLOATS) * 8
+IRS_COMPARE_SUMMARY_INTS, IRS_COMPARE_SUMMARY_FLOATS = 4, 13
+IRS_COMPARE_WS_BYTES = 1024 * (IRS_COMPARE_SUMMARY_INTS + IRS_COMPARE_SUMMARY_FLOATS) * 8
 IRS_QUANTILE_MIN_BINS, IRS_QUANTILE_MAX_BINS, IRS_QUANTILE_MAX_PROBS, IRS_QUANTILE_MAX_RECORDS = 4, 256, 8, 65535
 IRS_QUANTILE_SUMMARY_INTS, IRS_QUANTILE_SUMMARY_FLOATS = 3, 5
 IRS_QUANTILE_WS_BYTES = 1024 * (IRS_QUANTILE_SUMMARY_INTS + IRS_QUANTILE_SUMMARY_FLOATS) * 8
@@ -179,6 +181,8 @@ SIGNATURES = {
     'irs_jacobian_posterior_finalize': [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],
     'irs_displacement_covariance_update': [_P, _I, _I, _I, _I, _P, _P, _I, _P],
     'irs_displacement_covariance_finalize': [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],
+    'irs_posterior_compare': [_P, _P, _I, _P, _P, _I, _I, _I, _I, C.POINTER(C.c_float), C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t,
+                              _P],
     'irs_displacement_quantiles_update': [_P, _I, _I, _I, _I, _P, _P, _I, C.POINTER(C.c_float), _I, _P],
     'irs_displacement_quantiles_finalize': [_P, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                             C.POINTER(C.c_double), _I, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],

@@ -814,6 +814,27 @@ int irs_displacement_covariance_finalize(const float* mean, const float* comomen
 }
 
 // ================================================================================================
+// posterior comparison (compare_kernels.hip)
+// ================================================================================================
+int irs_posterior_compare(const float* mean_a, const float* comoment_a, int n_a, const float* mean_b, const float* comoment_b, int n_b,
+                          int D, int H, int W, const float* scale, double std_floor, const uint8_t* mask, float* shift,
+                          float* log_std_ratio, float* bures, float* jeffreys, long long* isummary, double* fsummary, void* ws,
+                          size_t ws_bytes, void* stream) {
+    if (!mean_a || !comoment_a || !mean_b || !comoment_b || !scale || !shift || !log_std_ratio || !bures || !jeffreys || !isummary ||
+        !fsummary || !ws || !dims_ok(1, D, H, W))
+        return fail("irs_posterior_compare: bad arguments");
+    if (n_a < 2 || n_b < 2) return fail("irs_posterior_compare: n_a = %d and n_b = %d records, at least 2 each needed", n_a, n_b);
+    if (!positive3(__func__, "scale", scale)) return 1;
+    if (!(std_floor > 0.0) || !isfinite(std_floor) || !(std_floor * std_floor > 0.0))
+        return fail("irs_posterior_compare: std_floor = %g, a finite value > 0 (whose square is > 0) needed", std_floor);
+    if (!workspace_ok(__func__, ws_bytes, (size_t)IRS_COMPARE_WS_BYTES, "IRS_COMPARE_WS_BYTES")) return 1;
+    launch_posterior_compare(mean_a, comoment_a, n_a, mean_b, comoment_b, n_b, (int64_t)D * H * W, scale, std_floor, mask, shift,
+                             log_std_ratio, bures, jeffreys, isummary, fsummary, ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // displacement credible intervals (quantile_kernels.hip)
 // ================================================================================================
 static bool quantile_bins_ok(int bins) { return bins >= IRS_QUANTILE_MIN_BINS && bins <= IRS_QUANTILE_MAX_BINS && bins % 2 == 0; }

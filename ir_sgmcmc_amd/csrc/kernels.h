@@ -262,6 +262,15 @@ void launch_covariance_finalize(const float* mean, const float* comoment, int64_
                                 float* stdev, float* direction, float* anisotropy, long long* isummary, double* fsummary, void* ws,
                                 hipStream_t st);
 
+// ---- compare_kernels.hip: posterior comparison (absent in the reference); arithmetic in compare_device.h
+// mean_x (3,V), comoment_x (6,V) float32 after n_x >= 2 records; scale: 3 host floats; shift, log_std_ratio, bures, jeffreys (V)
+// float32; isummary IRS_COMPARE_SUMMARY_INTS int64, fsummary IRS_COMPARE_SUMMARY_FLOATS doubles; ws: IRS_COMPARE_WS_BYTES (the
+// partials of at most 1024 blocks)
+void launch_posterior_compare(const float* mean_a, const float* comoment_a, int n_a, const float* mean_b, const float* comoment_b,
+                              int n_b, int64_t V, const float* scale, double std_floor, const uint8_t* mask, float* shift,
+                              float* log_std_ratio, float* bures, float* jeffreys, long long* isummary, double* fsummary, void* ws,
+                              hipStream_t st);
+
 // ---- quantile_kernels.hip: displacement credible intervals (absent in the reference); arithmetic in quantile_device.h
 // x (C,3,V) float32; centre (3,V) float32, hist (3,bins,V) uint16: the C chains counted after `records_before` records
 // (0: centre = chain 0 and hist overwritten); inv_width: 3 host floats

@@ -24,6 +24,11 @@ the displacement mean / std is: per voxel the Welford mean and the six co-moment
 36 * D * H * W bytes whatever the number of records, and at the end the principal spreads, the major direction and the
 fractional anisotropy of the 3 x 3 sample covariance and their summary over a mask (ops.displacement_covariance_finalize).
 
+The posterior comparison (PosteriorComparison, posterior_comparison_options) keeps two such states, one fed by the VI test
+samples and one by the recorded chain samples, 72 * D * H * W bytes, and at the end the distances between the Gaussians they
+describe per voxel -- mean shift, log ratio of the total spreads, Bures distance, Jeffreys divergence -- and their summary over
+a mask (posterior_comparison.posterior_compare).
+
 The displacement quantiles (DisplacementQuantiles) are what no moment gives: per voxel and channel a histogram of the
 displacement around the first record (ops.displacement_quantiles_update), 12 + 6 * bins bytes per voxel whatever the number of
 records, and at the end the quantiles of given probabilities, the width of the credible band between the first and the last
@@ -76,6 +81,7 @@ import numpy as np
 import torch
 
 from . import ops
+from . import posterior_comparison as _pc
 from . import residual_check as _rc
 
 
@@ -603,6 +609,94 @@ class DisplacementCovariance(_Recorder):
         self.mean.copy_(sd['mean'])
         self.comoment.copy_(sd['comoment'])
         self.records = int(sd['records'])
+
+
+COMPARISON_OPTION_KEYS = ('period', 'std_floor')
+COMPARISON_MIN_RECORDS = 4  # a 3 x 3 covariance of fewer than four samples is singular by construction
+COMPARISON_METRICS = ('shift_mean', 'shift_max', 'log_std_ratio_mean', 'log_std_ratio_min', 'log_std_ratio_max', 'std_ratio',
+                      'frac_vi_narrower', 'bures_mean', 'bures_max', 'w2_mean', 'w2_max', 'jeffreys_mean', 'jeffreys_max',
+                      'std_total_vi', 'std_total_mcmc')
+
+
+def posterior_comparison_options(cfg_trainer):
+    """`trainer.posterior_comparison` -> None when off, else {'period': P, 'std_floor': f}.
+    Absent / false / null: off.  true: P = log_period_MCMC, f = 1e-3.  A dict: either key may be left out.  The floor is in
+    the units of the comparison's scale (voxels).  Refuses what _record_options refuses, a floor that is not a finite number
+    > 0, `MCMC: false`, `VI: false` unless `resume` is set (the VI side then comes from the checkpoint), and fewer than 4
+    records on either side: no_samples_VI_test < 4, or (no_samples_MCMC // P) * no_chains < 4."""
+    what = 'trainer.posterior_comparison'
+
+    def own_keys(opt):
+        f = opt.get('std_floor', 1e-3)
+        if not _number(f) or not math.isfinite(f) or not f > 0:
+            raise ValueError(f'{what}.std_floor must be a finite number > 0, got {f!r}')
+        return {'std_floor': float(f)}
+
+    out = _record_options(cfg_trainer, 'posterior_comparison', COMPARISON_OPTION_KEYS, '{"period": P, "std_floor": f}', MAX_RECORDS,
+                          'the record count holds at most {}', own_keys)
+    if out is None:
+        return None
+    if not cfg_trainer.get('MCMC', True):
+        raise ValueError(f'{what} needs the MCMC stage: MCMC is false')
+    vi = bool(cfg_trainer.get('VI', False))
+    if not vi and not cfg_trainer.get('resume'):
+        raise ValueError(f'{what} needs the VI stage: VI is false and there is no resume checkpoint to take the VI side from')
+    need = COMPARISON_MIN_RECORDS
+    if vi and int(cfg_trainer['no_samples_VI_test']) < need:
+        raise ValueError(f'{what}: no_samples_VI_test = {int(cfg_trainer["no_samples_VI_test"])} records on the VI side, at least '
+                         f'{need} needed (a 3 x 3 covariance of fewer samples is singular)')
+    no_samples, chains = int(cfg_trainer['no_samples_MCMC']), int(cfg_trainer.get('no_chains', 1))
+    steps = no_samples // out['period']
+    if steps * chains < need:
+        raise ValueError(f'{what}: no_samples_MCMC = {no_samples} with period {out["period"]} gives {steps} steps of {chains} chains: '
+                         f'{steps * chains} records on the MCMC side, at least {need} needed (a 3 x 3 covariance of fewer samples '
+                         f'is singular)')
+    return out
+
+
+class PosteriorComparison(_Recorder):
+    """Two displacement covariance states, the VI side and the MCMC side, and the distances between the Gaussians they describe
+    (posterior_comparison.py).  `record_vi(displacement)` takes the (C,3,D,H,W) float32 displacements of VI test samples,
+    `record(displacement)` those of one recorded MCMC step, chains in order; `finalize` gives the four maps and the summary
+    over a mask.  `records` counts the MCMC side, as the recorder loop reads it."""
+    noun = 'posterior comparison'
+
+    def __init__(self, dims, device):
+        self.vi = DisplacementCovariance(dims, device)
+        self.mcmc = DisplacementCovariance(dims, device)
+        self.dims, self.device = self.mcmc.dims, device
+
+    @property
+    def records(self):
+        return self.mcmc.records
+
+    def record_vi(self, displacement):
+        self.vi.record(displacement)
+
+    def record(self, displacement):
+        self.mcmc.record(displacement)
+
+    def finalize(self, mask=None, scale=None, std_floor=1e-3):
+        """-> ({'shift', 'log_std_ratio', 'bures', 'jeffreys'}: (D,H,W) float32 maps on the device, summary dict of
+        posterior_comparison.comparison_summary).  scale: three positive floats, one per channel (default: voxel units);
+        log_std_ratio < 0 where the VI posterior is the narrower.  One device-to-host read (the summary)."""
+        for side, name in ((self.vi, 'VI'), (self.mcmc, 'MCMC')):
+            if side.records < 2:
+                raise RuntimeError(f'PosteriorComparison.finalize: {side.records} records on the {name} side, at least 2 needed')
+        scale = self.mcmc.default_scale() if scale is None else tuple(float(s) for s in scale)
+        *planes, isum, fsum = _pc.posterior_compare(self.vi.mean, self.vi.comoment, self.vi.records, self.mcmc.mean,
+                                                    self.mcmc.comoment, self.mcmc.records, scale, std_floor,
+                                                    _bool_mask(mask, self.device))
+        return (dict(zip(_pc.COMPARISON_PLANES, planes)),
+                _pc.comparison_summary(*_host_summary(isum, fsum), self.vi.records, self.mcmc.records))
+
+    def state_dict(self):
+        return {'vi': self.vi.state_dict(), 'mcmc': self.mcmc.state_dict()}
+
+    def load_state_dict(self, sd):
+        """both sides: the checkpoint's VI side replaces whatever this run's own VI stage recorded"""
+        self.vi.load_state_dict(sd['vi'])
+        self.mcmc.load_state_dict(sd['mcmc'])
 
 
 QUANTILE_OPTION_KEYS = ('period', 'probs', 'bins', 'bin_width')

@@ -301,6 +301,19 @@ def save_residual_nll(logger, save_dirs, spacing, mean, mask, model='MCMC'):
     save_im_to_disk(im.where(mask, im.new_zeros(())), path.join(folder, f'{model}_nll_mean_masked.nii.gz'), spacing)
 
 
+def save_posterior_comparison(logger, save_dirs, spacing, maps, mask, model='MCMC'):
+    """the VI posterior against the MCMC samples (absent in the reference): samples/{model}_vs_VI_{shift,log_std_ratio,bures,
+    jeffreys}[_masked].nii.gz (float32; NaN -- a non-finite state there -- written as 0, the masked ones 0 outside the mask too).
+    `maps`: the dict of diagnostics.PosteriorComparison.finalize"""
+    folder = _folder(save_dirs, 'samples')
+    for name in ('shift', 'log_std_ratio', 'bures', 'jeffreys'):
+        im, undefined = _nan_to_zero(maps[name])
+        m = mask.reshape(im.shape).to(im.device) != 0
+        logger.info(f'{model}_vs_VI_{name}: {undefined} voxels with a non-finite state written as 0')
+        save_im_to_disk(im, path.join(folder, f'{model}_vs_VI_{name}.nii.gz'), spacing)
+        save_im_to_disk(im.where(m, im.new_zeros(())), path.join(folder, f'{model}_vs_VI_{name}_masked.nii.gz'), spacing)
+
+
 def save_surface_posterior(logger, save_dirs, spacing, bias, std, model='MCMC'):
     """the surface posterior (absent in the reference): samples/{model}_surface_bias.nii.gz and samples/{model}_surface_std.nii.gz
     (float32).  The maps live on the contours of the fixed structures: NaN everywhere else, and in the std map where a contour

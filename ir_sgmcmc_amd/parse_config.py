@@ -11,12 +11,12 @@ from pathlib import Path
 import numpy as np
 
 from .data_loader import data_loaders as module_data
-from .diagnostics import (COVARIANCE_METRICS, ICE_SPACES, JACOBIAN_METRICS, LABEL_STRUCTURE_METRICS, QUANTILE_METRICS,
+from .diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ICE_SPACES, JACOBIAN_METRICS, LABEL_STRUCTURE_METRICS, QUANTILE_METRICS,
                           diagnostics_period, displacement_covariance_options, displacement_quantiles_options, ess_options,
                           hausdorff_metric_names, hausdorff_options, image_similarity_metric_names, image_similarity_options,
                           inverse_consistency_options, jacobian_posterior_options, label_posterior_options,
                           landmark_metric_names, landmark_options, local_similarity_metric_names, local_similarity_options,
-                          residual_check_metric_names, residual_check_options,
+                          posterior_comparison_options, residual_check_metric_names, residual_check_options,
                           native_resolution_options, surface_metric_names, surface_posterior_options)
 from .logger import setup_logging
 from .model import distributions as model_distr
@@ -139,6 +139,8 @@ class ConfigParser:
         residuals = residual_check_options(self['trainer'])
         if residuals is not None:
             m += residual_check_metric_names(residuals, C, bool(self['trainer'].get('VI', False)))
+        if posterior_comparison_options(self['trainer']) is not None:
+            m += [f'MCMC/vs_VI/{k}' for k in COMPARISON_METRICS]
         return m
 
     def init_transformation_and_registration_modules(self):

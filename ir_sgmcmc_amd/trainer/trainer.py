@@ -20,19 +20,21 @@ import torch
 
 from ..base import BaseTrainer
 from .. import ops
-from ..diagnostics import (COVARIANCE_METRICS, ChainMoments, DisplacementCovariance, DisplacementQuantiles, ICE_SPACES,
+from ..diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ChainMoments, DisplacementCovariance, DisplacementQuantiles, ICE_SPACES,
                            InverseConsistency, JACOBIAN_METRICS, JacobianPosterior, LABEL_STRUCTURE_METRICS, LANDMARK_METRICS,
                            LOCAL_METRICS, LabelPosterior, LandmarkPair, LandmarkPosterior, LocalSimilarity, QUANTILE_METRICS,
                            SURFACE_METRICS, SurfacePosterior, surface_coverage_key, surface_posterior_options,
                            diagnostics_period, displacement_covariance_options, displacement_quantiles_options,
                            ess_options, hausdorff_options, image_similarity_options, inverse_consistency_options, is_recorded,
                            jacobian_posterior_options, label_posterior_options, landmark_options, local_similarity_options,
-                           native_resolution_options, ResidualCheck, residual_check_options, residual_metrics,
+                           native_resolution_options, PosteriorComparison, posterior_comparison_options, ResidualCheck,
+                           residual_check_options, residual_metrics,
                            SIMILARITY_METRICS, voxel_scale)
 from ..engine import EngineConfig, TransitionEngine
 from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_quantiles, save_ess,
                       save_field, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_landmarks,
                       save_local_similarity_of_mean, save_local_similarity_posterior, save_native_mean, save_native_sample,
+                      save_posterior_comparison,
                       save_residual_histogram, save_residual_nll, save_rhat, save_sample, save_surface_posterior)
 from .. import residual_check
 from ..utils import (calc_DSC_GPU, calc_image_similarity, calc_norm, calc_no_non_diffeomorphic_voxels, calc_residual_check,
@@ -143,6 +145,12 @@ class Trainer(VIMixin, BaseTrainer):
         self.residual_options = residual_check_options(cfg_trainer)
         self._residual_check, self._residual_range, self._residual_warned = None, None, False
         self.residual_nll_mean, self.residual_summary = None, None
+        # VI against MCMC: the distances between the Gaussians fitted to the displacements of the two stages
+        # (posterior_comparison.py, diagnostics.PosteriorComparison): None when trainer.posterior_comparison is off
+        self.comparison_options = posterior_comparison_options(cfg_trainer)
+        self._posterior_comparison = None
+        self.comparison_shift, self.comparison_log_std_ratio, self.comparison_bures, self.comparison_jeffreys = None, None, None, None
+        self.comparison_summary = None
 
     # ---------------------------------------------------------------- engine plumbing
     def _engine_config(self):
@@ -228,7 +236,7 @@ class Trainer(VIMixin, BaseTrainer):
 
     def _recorders(self):
         """the active recorders, in the order they record and finish: moments, labels, surfaces, Jacobian, covariance,
-        quantiles, inverse consistency, landmarks, local similarity, residual check"""
+        quantiles, inverse consistency, landmarks, local similarity, residual check, posterior comparison"""
         period = lambda options: options and options['period']
         rows = (('chain_moments', self._chain_moments, self.diagnostics_period, 'convergence_diagnostics', 'chain moments',
                  'displacement', self._finish_diagnostics, 'moving_mask'),
@@ -251,7 +259,9 @@ class Trainer(VIMixin, BaseTrainer):
                 ('local_similarity', self._local_similarity, period(self.local_options), 'local_similarity', 'local similarity',
                  'lncc', self._finish_local_similarity, 'fixed'),
                 ('residual_check', self._residual_check, period(self.residual_options), 'residual_check', 'residual check',
-                 'residuals', self._finish_residual_check, 'fixed'))
+                 'residuals', self._finish_residual_check, 'fixed'),
+                ('posterior_comparison', self._posterior_comparison, period(self.comparison_options), 'posterior_comparison',
+                 'posterior comparison', 'displacement', self._finish_posterior_comparison, 'moving_mask'))
         return [Recorder(*row) for row in rows if row[1] is not None]
 
     # ---------------------------------------------------------------- checkpoint / resume (absent in the reference)
@@ -440,6 +450,8 @@ class Trainer(VIMixin, BaseTrainer):
             self._residual_check = ResidualCheck(self._outputs['residuals'].shape[2:], self.no_chains, self.device,
                                                  self._residual_range, self.residual_options['bins'], fixed['mask'][:1],
                                                  self.residual_options['nll_map'])
+        if self.comparison_options is not None:
+            self._comparison_init(self._outputs['displacement'].shape[2:])
         if cfg_trainer.get('resume'):
             self.load_checkpoint(cfg_trainer['resume'])
             first = self._sample_no + 1
@@ -946,6 +958,36 @@ class Trainer(VIMixin, BaseTrainer):
                                     'MCMC')
             if rc.nll_map:
                 save_residual_nll(self.logger, self.config.save_dirs, spacing, self.residual_nll_mean, mask, 'MCMC')
+
+    def _comparison_init(self, dims):
+        """trainer.posterior_comparison -> self._posterior_comparison, once: the VI test stage makes it, or -- on a resume
+        without a VI stage -- the MCMC stage, whose checkpoint then brings the VI side"""
+        if self._posterior_comparison is None:
+            self._posterior_comparison = PosteriorComparison(dims, self.device)
+        return self._posterior_comparison
+
+    def _finish_posterior_comparison(self, mask, spacing, save_outputs):
+        """the VI posterior (A) against the pooled MCMC samples (B): mean shift, log ratio of the total spreads, Bures distance
+        and Jeffreys divergence of the two per-voxel Gaussians, in voxels, and their summary -> self.comparison_shift /
+        comparison_log_std_ratio / comparison_bures / comparison_jeffreys / comparison_summary, the MCMC/vs_VI/* metrics and,
+        with save_outputs, samples/MCMC_vs_VI_{shift,log_std_ratio,bures,jeffreys}[_masked].nii.gz.  The summary is over the
+        mask the displacement std map uses."""
+        pc = self._posterior_comparison
+        maps, s = pc.finalize(mask, std_floor=self.comparison_options['std_floor'])
+        self.comparison_shift, self.comparison_log_std_ratio = maps['shift'], maps['log_std_ratio']
+        self.comparison_bures, self.comparison_jeffreys = maps['bures'], maps['jeffreys']
+        self.comparison_summary = s
+        for key in COMPARISON_METRICS:
+            self.metrics.update(f'MCMC/vs_VI/{key}', s[key])
+        self.logger.info(f'VI ({s["records_vi"]} samples) against MCMC ({s["records_mcmc"]} samples) over {s["voxels"]} masked voxels '
+                         f'({s["nonfinite_voxels"]} non-finite, {s["floored_voxels"]} with a floored eigenvalue): mean shift '
+                         f'{s["shift_mean"]:.4f}, max {s["shift_max"]:.4f} voxels; total std VI {s["std_total_vi"]:.4f}, MCMC '
+                         f'{s["std_total_mcmc"]:.4f}, ratio {s["std_ratio"]:.4f} (VI the narrower at '
+                         f'{100 * s["frac_vi_narrower"]:.2f} % of the voxels); Bures mean {s["bures_mean"]:.4f}, 2-Wasserstein mean '
+                         f'{s["w2_mean"]:.4f}, max {s["w2_max"]:.4f} voxels; Jeffreys mean {s["jeffreys_mean"]:.4g}, max '
+                         f'{s["jeffreys_max"]:.4g}')
+        if save_outputs:
+            save_posterior_comparison(self.logger, self.config.save_dirs, spacing, maps, mask, 'MCMC')
 
     def _landmarks_init(self, dims):
         """trainer.landmarks -> self._landmarks (diagnostics.LandmarkPair), once: the landmark files' voxel indices carried to

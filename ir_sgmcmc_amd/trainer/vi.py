@@ -223,6 +223,8 @@ class VIMixin:
             v = sample_q_v(var_params_q_v, no_samples=1)
             transformation, displacement = self.transformation_module(self._smooth(v))
             samples.append(displacement[0].clone())
+            if self.comparison_options is not None:  # the VI side of the posterior comparison: the sample this loop already has
+                self._comparison_init(displacement.shape[2:]).record_vi(displacement.contiguous())
             no_folds, log_det_J = calc_no_non_diffeomorphic_voxels(transformation, self.diff_op)
             self.metrics.update('VI/test/no_non_diffeomorphic_voxels', int(no_folds.sum()))
             warped = self.registration_module(moving['im'], transformation)

@@ -214,6 +214,28 @@ def calc_displacement_covariance(displacements, mask=None, scale=None):
 
 
 @torch.no_grad()
+def calc_posterior_comparison(displacements_a, displacements_b, mask=None, scale=None, std_floor=1e-3):
+    """The distances between the Gaussians fitted, per voxel, to two sets of displacement samples (absent in the reference):
+    displacements_a (n_a,3,D,H,W) and displacements_b (n_b,3,D,H,W) float32 on the device, in normalised coordinates, at least
+    2 records each; mask (D,H,W) or None; scale: three floats, one per channel (default: voxel units); std_floor: the floor of
+    the Jeffreys divergence's eigenvalues, in the units of the scale.  -> ({'shift', 'log_std_ratio', 'bures', 'jeffreys'}: maps,
+    summary dict), as diagnostics.PosteriorComparison.finalize with A in the role of the VI side."""
+    from .. import _lib as L
+    from ..diagnostics import PosteriorComparison
+    for name, d in (('displacements_a', displacements_a), ('displacements_b', displacements_b)):
+        if d.dim() != 5 or d.shape[1] != 3:
+            raise ValueError(f'{name} must have shape (n, 3, D, H, W), got {tuple(d.shape)}')
+    if tuple(displacements_a.shape[2:]) != tuple(displacements_b.shape[2:]):
+        raise ValueError(f'the two sets of displacements live on different grids: {tuple(displacements_a.shape[2:])} and '
+                         f'{tuple(displacements_b.shape[2:])}')
+    pc = PosteriorComparison(displacements_a.shape[2:], displacements_a.device)
+    for take, d in ((pc.record_vi, displacements_a), (pc.record, displacements_b)):
+        for i in range(0, d.shape[0], L.IRS_MAX_CHAINS):  # one launch folds up to IRS_MAX_CHAINS records, in order
+            take(d[i:i + L.IRS_MAX_CHAINS].float().contiguous())
+    return pc.finalize(mask, scale, std_floor)
+
+
+@torch.no_grad()
 def calc_displacement_quantiles(displacements, probs=(0.05, 0.5, 0.95), mask=None, bins=64, bin_width=0.125, scale=None):
     """Per-voxel quantiles of displacement samples and the width of the band between the first and the last (absent in the
     reference): displacements (n,3,D,H,W) float32 on the device, in normalised coordinates, n <= 65535 records, the first one
