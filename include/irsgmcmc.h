@@ -570,6 +570,29 @@ int irs_residual_nll_update(const float* residuals, int C, int D, int H, int W, 
 int irs_residual_nll_finalize(const float* mean, const int32_t* count, const uint8_t* mask, int D, int H, int W,
                               long long* isummary, double* fsummary, void* ws, size_t ws_bytes, void* stream);
 
+/* Coarse-to-fine start (absent in the reference, whose chains all start on the full grid): an image and a mask carried down to
+ * a coarser grid and a field carried up to a finer one.  The grids are align_corners, as every resize of the package: along one
+ * axis coarse index i of n sits at fine coordinate x_i = i (N - 1) / (n - 1) and fine index I of N at coarse coordinate
+ * I (n - 1) / (N - 1), each formed in double as the integer product divided once.  A velocity or displacement in normalised
+ * coordinates (2 spans n - 1 voxels) means the same on both grids and is not rescaled.  On every axis 2 <= n <= N; the fine
+ * volume has fewer than 2^30 voxels; volumes times the first extent of the written grid is at most 65535 (one launch row each).
+ * The sums are double, taken in the tap order z, then y, then x (acc = acc + ((w_z w_y) w_x) value, every operation rounded
+ * once), and the result is rounded to float32 once.  Each is one launch with one thread per output element; deterministic; no
+ * atomics; no host sync.
+ *  - irs_restrict_image: im (Cim,1,D,H,W) float32 -> out (Cim,1,d,h,w), Cim >= 1.  A separable tent filter of half-width
+ *    r = max(1, (N - 1) / (n - 1)) per axis: every integer k with |k - x_i| < r contributes the weight 1 - |k - x_i| / r to the
+ *    fine voxel clamp(k, 0, N - 1) (replicate padding, as the Sobolev and the LNCC windows), and the weights of an axis are
+ *    each divided by their sum (summed in the order of k).  n = N gives the identity bit for bit; N = 2 n - 1 gives the
+ *    full-weighting stencil 1/4, 1/2, 1/4 (3/4, 1/4 at the two ends): all weights dyadic.
+ *  - irs_restrict_mask: mask (Cm,1,D,H,W) uint8 -> out (Cm,1,d,h,w), Cm >= 1: the coarse voxel takes the fine voxel at
+ *    floor(x_i + 0.5) per axis.
+ *  - irs_prolong_field: x (C,ch,d,h,w) float32 -> out (C,ch,D,H,W), C >= 1, ch >= 1 (3 for a velocity, 1 for a scalar volume).
+ *    Trilinear at the coarse coordinate c of every fine voxel: i0 = floor(c), weights 1 - (c - i0) and c - i0 on the taps i0 and
+ *    i0 + 1.  Where i0 + 1 would be n its weight is 0 and the tap is not read.  n = N gives the identity bit for bit. */
+int irs_restrict_image(const float* im, int Cim, int D, int H, int W, float* out, int d, int h, int w, void* stream);
+int irs_restrict_mask(const uint8_t* mask, int Cm, int D, int H, int W, uint8_t* out, int d, int h, int w, void* stream);
+int irs_prolong_field(const float* x, int C, int ch, int d, int h, int w, float* out, int D, int H, int W, void* stream);
+
 /* Landmark propagation (absent in the reference, which has no point-set operator): a sampled displacement evaluated at K
  * positions that are no voxel centres, and the posterior of the mapped landmarks with their target registration error (TRE).
  * warped(x) = moving(x + d(x)): a point p of the fixed grid maps to p + d(p) in the moving image; points of the moving space

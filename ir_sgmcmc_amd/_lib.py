@@ -203,6 +203,9 @@ SIGNATURES = {
     'irs_residual_histogram': [_P, _I, _P, _I, _I, _I, _F, _I, _P, _P, _P, _I, _P, C.c_size_t, _P],
     'irs_residual_nll_update': [_P, _I, _I, _I, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), _I, _P, _P, _I, _P],
     'irs_residual_nll_finalize': [_P, _P, _P, _I, _I, _I, _P, _P, _P, C.c_size_t, _P],
+    'irs_restrict_image': [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P],
+    'irs_restrict_mask': [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P],
+    'irs_prolong_field': [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P],
     'irs_create': [C.POINTER(IrsConfig), C.POINTER(_P)],
     'irs_destroy': [_P],
     'irs_workspace_bytes': [_P],

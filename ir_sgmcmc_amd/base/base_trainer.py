@@ -27,7 +27,7 @@ class BaseTrainer:
         self.log_period_VI = cfg_trainer['log_period_VI']
 
         self.MCMC = cfg_trainer['MCMC']
-        self.MCMC_init = cfg_trainer['MCMC_init']  # one of 'VI', 'identity', 'noise'
+        self.MCMC_init = cfg_trainer['MCMC_init']  # one of 'VI', 'identity', 'noise', 'coarse' (with trainer.coarse_start)
         self.no_chains = int(cfg_trainer['no_chains'])
         self.no_samples_MCMC = int(cfg_trainer['no_samples_MCMC'])
         self.no_iters_burn_in = int(cfg_trainer['no_iters_burn_in'])

@@ -1204,4 +1204,53 @@ int irs_residual_nll_finalize(const float* mean, const int32_t* count, const uin
     return 0;
 }
 
+// ================================================================================================
+// coarse-to-fine start (multires_kernels.hip)
+// ================================================================================================
+// `volumes` volumes go between the fine and the coarse grid; `out_planes`: the first extent of the grid that is written (one
+// launch row per volume and plane of it)
+static bool multires_ok(const char* who, const void* in, const void* out, int64_t volumes, const int fine[3], const int coarse[3],
+                        int out_planes) {
+    if (!in || !out) return !fail("%s: null pointer", who);
+    const int* grids[2] = {fine, coarse};
+    const char* names[2] = {"fine", "coarse"};
+    for (int g = 0; g < 2; ++g)
+        if (grids[g][0] < 2 || grids[g][1] < 2 || grids[g][2] < 2)
+            return !fail("%s: %s dims (%d, %d, %d), every one >= 2 needed", who, names[g], grids[g][0], grids[g][1], grids[g][2]);
+    for (int a = 0; a < 3; ++a)
+        if (coarse[a] > fine[a])
+            return !fail("%s: coarse dims (%d, %d, %d) exceed the fine dims (%d, %d, %d) on axis %d", who, coarse[0], coarse[1],
+                         coarse[2], fine[0], fine[1], fine[2], a);
+    if ((int64_t)fine[0] * fine[1] * fine[2] >= ((int64_t)1 << 30)) return !fail("%s: the fine volume must have fewer than 2^30 voxels", who);
+    return volumes * out_planes <= 65535 ||
+           !fail("%s: %lld volumes of %d planes are more than the 65535 rows of one launch", who, (long long)volumes, out_planes);
+}
+
+int irs_restrict_image(const float* im, int Cim, int D, int H, int W, float* out, int d, int h, int w, void* stream) {
+    if (Cim < 1) return fail("irs_restrict_image: Cim = %d volumes, at least 1 needed", Cim);
+    const int fine[3] = {D, H, W}, coarse[3] = {d, h, w};
+    if (!multires_ok(__func__, im, out, Cim, fine, coarse, d)) return 1;
+    launch_restrict_image(im, out, Cim, make_vol(D, H, W), make_vol(d, h, w), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_restrict_mask(const uint8_t* mask, int Cm, int D, int H, int W, uint8_t* out, int d, int h, int w, void* stream) {
+    if (Cm < 1) return fail("irs_restrict_mask: Cm = %d volumes, at least 1 needed", Cm);
+    const int fine[3] = {D, H, W}, coarse[3] = {d, h, w};
+    if (!multires_ok(__func__, mask, out, Cm, fine, coarse, d)) return 1;
+    launch_restrict_mask(mask, out, Cm, make_vol(D, H, W), make_vol(d, h, w), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_prolong_field(const float* x, int C, int ch, int d, int h, int w, float* out, int D, int H, int W, void* stream) {
+    if (C < 1 || ch < 1) return fail("irs_prolong_field: C = %d chains of ch = %d channels, at least 1 each needed", C, ch);
+    const int fine[3] = {D, H, W}, coarse[3] = {d, h, w};
+    if (!multires_ok(__func__, x, out, (int64_t)C * ch, fine, coarse, D)) return 1;
+    launch_prolong_field(x, out, C * ch, make_vol(d, h, w), make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 }  // extern "C"

@@ -388,6 +388,12 @@ void launch_residual_nll_update(const float* residuals, int C, int64_t V, const 
 void launch_residual_nll_finalize(const float* mean, const int32_t* count, int64_t V, const uint8_t* mask, long long* isummary,
                                   double* fsummary, void* ws, hipStream_t st);
 
+// ---- multires_kernels.hip: the coarse-to-fine start -- `planes` volumes of the extents of `fine` <-> of `coarse` (align_corners
+// grids, coarse <= fine on every axis, both >= 2); one thread per output element, grid z = planes * (first extent of the output)
+void launch_restrict_image(const float* im, float* out, int planes, const Vol& fine, const Vol& coarse, hipStream_t st);
+void launch_restrict_mask(const uint8_t* mask, uint8_t* out, int planes, const Vol& fine, const Vol& coarse, hipStream_t st);
+void launch_prolong_field(const float* in, float* out, int planes, const Vol& coarse, const Vol& fine, hipStream_t st);
+
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h
 }  // namespace irs

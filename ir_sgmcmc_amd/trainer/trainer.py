@@ -11,6 +11,7 @@ Inside `_SGLD_transition` nothing runs in torch: one call into the C ABI launche
 HIP stream (ir_sgmcmc_amd/csrc/api_ctx.hip: transition_impl).  The hyper-parameters of the loss objects are mirrored into
 the device state once (`_engine_init`) and read back lazily (`sync_parameters`) when something logs them.
 """
+import dataclasses
 import math
 import time
 from collections import namedtuple
@@ -36,7 +37,8 @@ from ..logger import (save_displacement_covariance, save_displacement_mean_and_s
                       save_local_similarity_of_mean, save_local_similarity_posterior, save_native_mean, save_native_sample,
                       save_posterior_comparison,
                       save_residual_histogram, save_residual_nll, save_rhat, save_sample, save_surface_posterior)
-from .. import residual_check
+from .. import multires, residual_check
+from ..multires import coarse_start_options
 from ..utils import (calc_DSC_GPU, calc_image_similarity, calc_norm, calc_no_non_diffeomorphic_voxels, calc_residual_check,
                      init_identity_grid_3D, local_similarity_rows, sample_q_v, transform_coordinates)
 from .vi import VIMixin
@@ -151,6 +153,10 @@ class Trainer(VIMixin, BaseTrainer):
         self._posterior_comparison = None
         self.comparison_shift, self.comparison_log_std_ratio, self.comparison_bures, self.comparison_jeffreys = None, None, None, None
         self.comparison_summary = None
+        # coarse-to-fine start (multires.py, _coarse_start): None unless trainer.MCMC_init is "coarse"
+        self.coarse_options = coarse_start_options(cfg_trainer, config['data_loader']['args']['dims'],
+                                                   config['transformation_module']['type'])
+        self.coarse_summary = None
 
     # ---------------------------------------------------------------- engine plumbing
     def _engine_config(self):
@@ -201,17 +207,22 @@ class Trainer(VIMixin, BaseTrainer):
         self.engine = TransitionEngine(self._engine_config(), self.device)
         self._fixed, self._moving = self.engine.prepare(fixed, moving)
         self._mask_idx = None
-        # hyper-parameters of the loss objects -> device state
-        st = self.engine.state()
+        self._set_hyper_parameters(self.engine)
+
+    def _set_hyper_parameters(self, engine, lognormal=True):
+        """hyper-parameters of the loss objects -> the device state of `engine`.  lognormal False leaves RegLoss_LogNormal's
+        (loc, log_scale) as the engine initialised them for ITS grid (engine.lognormal_init): the loss object's loc was
+        computed for the degrees of freedom of the full grid."""
+        st = engine.state()
         data_loss, reg_loss = self.losses['data']['loss'], self.losses['reg']['loss']
         if type(data_loss).__name__ == 'GMM':
             for k in range(data_loss.no_components):
                 st.gmm_log_std[k], st.gmm_logits[k] = float(data_loss.log_std[k].detach()), float(data_loss.logits[k].detach())
         if type(reg_loss).__name__ == 'RegLoss_L2':
             st.reg_param[0] = float(reg_loss.log_w_reg.detach())
-        elif type(reg_loss).__name__ == 'RegLoss_LogNormal':
+        elif type(reg_loss).__name__ == 'RegLoss_LogNormal' and lognormal:
             st.reg_param[0], st.reg_param[1] = float(reg_loss.loc.detach()), float(reg_loss.log_scale.detach())
-        self.engine.set_state(st)
+        engine.set_state(st)
 
     def sync_parameters(self):
         """device state -> the nn.Parameters of the loss objects (what the reference's logging reads, trainer.py:391-402)"""
@@ -325,6 +336,13 @@ class Trainer(VIMixin, BaseTrainer):
             v, sigma = torch.zeros(shape, device=self.device), None
         elif self.MCMC_init == 'noise':
             v, sigma = torch.randn(shape, device=self.device), None
+        elif self.MCMC_init == 'coarse':
+            if self.config['trainer'].get('resume'):  # the checkpoint supplies v
+                self.logger.info('coarse start: skipped, the run resumes from a checkpoint')
+                self.coarse_summary = []
+                v, sigma = torch.zeros(shape, device=self.device), None
+            else:
+                v, sigma = self._coarse_start(), None
         else:
             raise ValueError(self.MCMC_init)
         tau = self.config['optimizer_SG_MCMC']['args']['lr']
@@ -335,6 +353,46 @@ class Trainer(VIMixin, BaseTrainer):
         new = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)
         self._outputs = {'curr_state': new(C, 3, *dv), 'im_moving_warped': new(C, 1, *d), 'residuals': new(C, 1, *d),
                          'displacement': new(C, 3, *d), 'transformation': new(C, 3, *d)}
+
+    def _coarse_start(self):
+        """The start of MCMC_init "coarse": short chains on the pair restricted to every level of trainer.coarse_start, coarse
+        to fine, each started from the prolonged result of the level below (zero at the first) -> v (no_chains,3,D,H,W) on the
+        full grid.  Every level restricts from the FULL volumes, runs all chains in one engine of its own (identity
+        pre-conditioner, in-kernel noise, seed + 1 + level) and is dropped before the next one allocates; the mixture of the
+        run's engine is then re-seeded from the residuals of the prolonged field (nothing to do for an SSD).  Fills
+        self.coarse_summary, one entry per level."""
+        dims = tuple(self.config['data_loader']['args']['dims'])
+        base = self._engine_config()
+        self.coarse_summary = []
+        v = None
+        for no, level in enumerate(self.coarse_options['levels']):
+            torch.cuda.synchronize(self.device)
+            start = time.perf_counter()
+            d, lr = level['dims'], base.lr if level['lr'] is None else level['lr']
+            engine = TransitionEngine(dataclasses.replace(base, dims=d, lr=lr, seed=base.seed + 1 + no), self.device)
+            fixed, moving = engine.prepare(*multires.restrict_pair(self._fixed, self._moving, d))
+            self._set_hyper_parameters(engine, lognormal=False)
+            v = torch.zeros((self.no_chains, 3, *d), device=self.device) if v is None else multires.prolong_field(v, d)
+            engine.gmm_init(fixed, moving, None if no == 0 else v[:1])
+            first = None
+            for it in range(level['no_iters']):
+                engine.transition(fixed, moving, v)
+                if it == 0:
+                    first = engine.scalars()['data_term']
+            engine.flush()
+            last = engine.scalars()['data_term']
+            del engine, fixed, moving
+            torch.cuda.synchronize(self.device)
+            entry = {'dims': d, 'no_iters': level['no_iters'], 'lr': lr, 'data_term_first': first, 'data_term_last': last,
+                     'seconds': time.perf_counter() - start}
+            self.coarse_summary.append(entry)
+            self.logger.info(f'coarse start, level {no}: dims {list(d)}, {entry["no_iters"]} transitions at lr {lr:g} in '
+                             f'{entry["seconds"]:.2f} s; data term per chain {[f"{x:.6g}" for x in first]} -> '
+                             f'{[f"{x:.6g}" for x in last]}')
+        v = multires.prolong_field(v, dims)
+        self.engine.gmm_init(self._fixed, self._moving, v[:1])
+        self.sync_parameters()
+        return v
 
     def _GMM_init(self, fixed, moving, var_params_q_v=None):
         """Trainer.__GMM_init (trainer.py:529-547): one velocity sample, std of the masked residual, 25 warm-up steps"""
