@@ -593,6 +593,44 @@ int irs_restrict_image(const float* im, int Cim, int D, int H, int W, float* out
 int irs_restrict_mask(const uint8_t* mask, int Cm, int D, int H, int W, uint8_t* out, int d, int h, int w, void* stream);
 int irs_prolong_field(const float* x, int C, int ch, int d, int h, int w, float* out, int D, int H, int W, void* stream);
 
+/* Affine pre-alignment (absent in the reference, whose volumes were registered affinely elsewhere): the Gauss-Newton normal
+ * equations of the sum of squared differences under a 3 x 4 map, the map as a transformation tensor, and the map composed with
+ * a sampled transformation.
+ * Voxel index coordinates in array order (D, H, W): index k = (k0, k1, k2), centre c = ((D - 1) / 2, (H - 1) / 2, (W - 1) / 2);
+ * fixed and moving volume have the same extents, every one >= 2, fewer than 2^30 voxels.  A map is lin[9] (3 x 3, row-major) and
+ * shift[3], host doubles, all finite.  Fixed voxel k reads the moving image at p = c + shift + lin (k - c), formed in double with
+ * every operation rounded once and none contracted: p_a = (((lin[a][0] d_0 + lin[a][1] d_1) + lin[a][2] d_2) + shift[a]) + c_a,
+ * d = k - c.  The identity gives p = k exactly.
+ *  - irs_affine_normal_equations: fixed, moving (D,H,W) float32; mask (D,H,W) uint8 or NULL.  A voxel takes part when the mask
+ *    is set (or absent), 0 <= p_a <= n_a - 1 on all three axes, and the fixed value and all eight moving taps are finite; the
+ *    tests are made in that order (a masked voxel mapped outside counts as outside, whatever its values).  Cell i0 =
+ *    min(floor(p), n - 2), w = p - i0 per axis.  The value M(p) and the gradient g = dM/dp (array order) are the trilinear
+ *    interpolant's, in double from the float32 taps t: M = sum over the taps in the order z, y, x of ((wz wy) wx) t; g_0 = sum over
+ *    (y, x) of (wy wx) (t[1][y][x] - t[0][y][x]), g_1 = sum over (z, x) of (wz wx) (t[z][1][x] - t[z][0][x]), g_2 = sum over (z, y)
+ *    of (wz wy) (t[z][y][1] - t[z][y][0]); r = M(p) - F(k).  Parameters theta = (lin row-major, shift), 12; with kt = (d_0, d_1,
+ *    d_2, 1): dr/dlin[a][b] = g_a kt_b, dr/dshift[a] = g_a.  H = sum J J^T with every term formed as (g_i g_j) (kt_a kt_b), b =
+ *    sum J r with every term formed as (g_a r) kt_b.  sums (device, IRS_AFFINE_SUMS doubles): [0, 78) the upper triangle of H
+ *    row-major, [78, 90) b, 90 sum r^2, 91 voxels taking part, 92 masked voxels mapped outside, 93 masked voxels inside dropped
+ *    for a non-finite value (counts as doubles, exact).  ws: IRS_AFFINE_WS_BYTES, 8-byte aligned (IRS_AFFINE_MAX_BLOCKS rows of
+ *    IRS_AFFINE_PARTIALS per-block sums, folded in a fixed order by a one-block kernel).  No floating-point atomics, a grid that
+ *    depends on the extents only: two identical calls are bit-identical.  No host sync.
+ *  - irs_affine_transformation: out (1,3,D,H,W) float32, the map as the [-1,1] transformation tensor the warps take
+ *    (align_corners, component 0 = x, the last axis): 2 p_a / (n_a - 1) - 1 in double, rounded to float32 once.  D <= 65535.
+ *  - irs_affine_compose: transformation (C,3,D,H,W) float32 in [-1,1], C in 1 .. IRS_MAX_CHAINS, C D <= 65535.  The moving image
+ *    a chain saw after resampling through the map A is M'(y) = M(A y), so the total map is x -> A(phi(x)): every vector of phi
+ *    goes to index coordinates ((g + 1) / 2) (n - 1) (in double, not clamped), through A as above with d = phi - c, and back.
+ *    total_transformation (C,3,D,H,W) in [-1,1] and total_displacement (C,3,D,H,W) = A(phi(x)) - x in voxels, component 0 = x;
+ *    either may be NULL, not both.  Element-wise, in double, rounded once. */
+#define IRS_AFFINE_SUMS 94
+#define IRS_AFFINE_PARTIALS 76        /* 60 distinct sums of H, 12 of b, sum r^2, three counts */
+#define IRS_AFFINE_MAX_BLOCKS 512     /* rows of per-block partial sums in the workspace */
+#define IRS_AFFINE_WS_BYTES (IRS_AFFINE_MAX_BLOCKS * IRS_AFFINE_PARTIALS * 8)
+int irs_affine_normal_equations(const float* fixed, const float* moving, const uint8_t* mask, int D, int H, int W, const double* lin,
+                                const double* shift, double* sums, void* ws, size_t ws_bytes, void* stream);
+int irs_affine_transformation(const double* lin, const double* shift, float* out, int D, int H, int W, void* stream);
+int irs_affine_compose(const float* transformation, const double* lin, const double* shift, float* total_transformation,
+                       float* total_displacement, int C, int D, int H, int W, void* stream);
+
 /* Landmark propagation (absent in the reference, which has no point-set operator): a sampled displacement evaluated at K
  * positions that are no voxel centres, and the posterior of the mapped landmarks with their target registration error (TRE).
  * warped(x) = moving(x + d(x)): a point p of the fixed grid maps to p + d(p) in the moving image; points of the moving space

@@ -45,6 +45,8 @@ IRS_RESIDUAL_MAP_SUMMARY_INTS, IRS_RESIDUAL_MAP_SUMMARY_FLOATS = 2, 2
 IRS_RESIDUAL_MAP_WS_BYTES = 1024 * (IRS_RESIDUAL_MAP_SUMMARY_INTS + IRS_RESIDUAL_MAP_SUMMARY_FLOATS) * 8
 IRS_SURFACE_MAX_LEVELS, IRS_SURFACE_SUMMARY_INTS, IRS_SURFACE_SUMMARY_FLOATS, IRS_SURFACE_MAX_BLOCKS = 4, 7, 6, 512
 IRS_SURFACE_WS_BYTES = IRS_MAX_LABELS * IRS_SURFACE_MAX_BLOCKS * (IRS_SURFACE_SUMMARY_INTS + IRS_SURFACE_SUMMARY_FLOATS) * 8
+IRS_AFFINE_SUMS, IRS_AFFINE_PARTIALS, IRS_AFFINE_MAX_BLOCKS = 94, 76, 512
+IRS_AFFINE_WS_BYTES = IRS_AFFINE_MAX_BLOCKS * IRS_AFFINE_PARTIALS * 8
 IRS_DATA_GMM_LCC, IRS_DATA_SSD = 0, 1
 IRS_REG_L2, IRS_REG_LOGNORMAL, IRS_REG_STUDENT, IRS_REG_LOGNORMAL_L2 = 0, 1, 2, 3
 
@@ -206,6 +208,9 @@ SIGNATURES = {
     'irs_restrict_image': [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P],
     'irs_restrict_mask': [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P],
     'irs_prolong_field': [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P],
+    'irs_affine_normal_equations': [_P, _P, _P, _I, _I, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, C.c_size_t, _P],
+    'irs_affine_transformation': [C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _I, _I, _I, _P],
+    'irs_affine_compose': [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, _I, _I, _I, _I, _P],
     'irs_create': [C.POINTER(IrsConfig), C.POINTER(_P)],
     'irs_destroy': [_P],
     'irs_workspace_bytes': [_P],

@@ -1253,4 +1253,58 @@ int irs_prolong_field(const float* x, int C, int ch, int d, int h, int w, float*
     return 0;
 }
 
+// ================================================================================================
+// affine pre-alignment (affine_kernels.hip)
+// ================================================================================================
+// the volume and the map of an affine call -> `map`; `rows`: launch rows (chains x planes) of the pointwise kernels, 0: none
+static bool affine_ok(const char* who, int D, int H, int W, const double* lin, const double* shift, int64_t rows, AffineMap& map) {
+    if (!lin || !shift) return !fail("%s: null pointer", who);
+    if (D < 2 || H < 2 || W < 2) return !fail("%s: dims (%d, %d, %d), every one >= 2 needed", who, D, H, W);
+    if ((int64_t)D * H * W >= ((int64_t)1 << 30)) return !fail("%s: the volume must have fewer than 2^30 voxels", who);
+    if (rows > 65535) return !fail("%s: %lld planes are more than the 65535 rows of one launch", who, (long long)rows);
+    for (int i = 0; i < 9; ++i) {
+        if (!isfinite(lin[i])) return !fail("%s: lin[%d] = %g is not finite", who, i, lin[i]);
+        map.lin[i] = lin[i];
+    }
+    for (int i = 0; i < 3; ++i) {
+        if (!isfinite(shift[i])) return !fail("%s: shift[%d] = %g is not finite", who, i, shift[i]);
+        map.shift[i] = shift[i];
+    }
+    return true;
+}
+
+int irs_affine_normal_equations(const float* fixed, const float* moving, const uint8_t* mask, int D, int H, int W, const double* lin,
+                                const double* shift, double* sums, void* ws, size_t ws_bytes, void* stream) {
+    if (!fixed || !moving || !sums || !ws) return fail("irs_affine_normal_equations: null pointer");
+    AffineMap map;
+    if (!affine_ok(__func__, D, H, W, lin, shift, 0, map)) return 1;
+    if (!workspace_ok(__func__, ws_bytes, (size_t)IRS_AFFINE_WS_BYTES, "IRS_AFFINE_WS_BYTES")) return 1;
+    if ((uintptr_t)ws & 7) return fail("irs_affine_normal_equations: the workspace must be 8-byte aligned");
+    launch_affine_normal_equations(fixed, moving, mask, make_vol(D, H, W), map, sums, (double*)ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_affine_transformation(const double* lin, const double* shift, float* out, int D, int H, int W, void* stream) {
+    if (!out) return fail("irs_affine_transformation: null pointer");
+    AffineMap map;
+    if (!affine_ok(__func__, D, H, W, lin, shift, D, map)) return 1;
+    launch_affine_transformation(map, out, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_affine_compose(const float* transformation, const double* lin, const double* shift, float* total_transformation,
+                       float* total_displacement, int C, int D, int H, int W, void* stream) {
+    if (!transformation) return fail("irs_affine_compose: null pointer");
+    if (!total_transformation && !total_displacement)
+        return fail("irs_affine_compose: total_transformation and total_displacement are both NULL, one is needed");
+    if (!chains_ok(__func__, C)) return 1;
+    AffineMap map;
+    if (!affine_ok(__func__, D, H, W, lin, shift, (int64_t)C * D, map)) return 1;
+    launch_affine_compose(transformation, map, total_transformation, total_displacement, C, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 }  // extern "C"

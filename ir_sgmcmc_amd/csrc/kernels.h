@@ -394,6 +394,22 @@ void launch_restrict_image(const float* im, float* out, int planes, const Vol& f
 void launch_restrict_mask(const uint8_t* mask, uint8_t* out, int planes, const Vol& fine, const Vol& coarse, hipStream_t st);
 void launch_prolong_field(const float* in, float* out, int planes, const Vol& coarse, const Vol& fine, hipStream_t st);
 
+// ---- affine_kernels.hip: the affine pre-alignment -- a map p = c + shift + lin (k - c) in voxel index coordinates, array order
+struct AffineMap {  // passed to the kernels by value
+    double lin[9];  // row-major
+    double shift[3];
+};
+// fixed / moving (V) float32; mask (V) uint8 or nullptr; sums: IRS_AFFINE_SUMS doubles; partials: IRS_AFFINE_MAX_BLOCKS rows of
+// IRS_AFFINE_PARTIALS doubles
+void launch_affine_normal_equations(const float* fixed, const float* moving, const uint8_t* mask, const Vol& vol, const AffineMap& map,
+                                    double* sums, double* partials, hipStream_t st);
+// out (1,3,D,H,W): the map as a [-1,1] transformation tensor, channel 0 the last axis
+void launch_affine_transformation(const AffineMap& map, float* out, const Vol& vol, hipStream_t st);
+// transformation (C,3,D,H,W) in [-1,1] -> the map applied after it, as a transformation and / or a displacement in voxels (nullptr:
+// not wanted)
+void launch_affine_compose(const float* transformation, const AffineMap& map, float* total_transformation, float* total_displacement,
+                           int C, const Vol& vol, hipStream_t st);
+
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h
 }  // namespace irs

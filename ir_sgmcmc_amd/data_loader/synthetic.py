@@ -28,8 +28,32 @@ def _blobs(dims, shift_a, shift_b):
     return torch.exp(-4.0 * r2) + 0.5 * torch.exp(-30.0 * q2)
 
 
-def synthetic_pair(dims, seed=0, noise=0.02):
-    """Two Gaussian blobs + white noise; the moving image has both blobs shifted.  Returns (fixed, moving)."""
+def misalign_triple(triple, rotation_deg, shift):
+    """{'im', 'mask', 'seg'} of (1,D,H,W) read at p = c + shift + R (k - c) on the host: R the rotation about the vector
+    `rotation_deg` (array order, its length the angle in degrees), `shift` in voxels, c the centre of the grid.  Trilinear for
+    the image, nearest for mask and segmentation, border padding.  The pair a pre-alignment (trainer.affine_init) has to undo."""
+    import torch.nn.functional as F
+    D, H, W = triple['im'].shape[1:]
+    w = torch.tensor([math.radians(float(a)) for a in rotation_deg], dtype=torch.float64)
+    angle = float(w.norm())
+    K = torch.zeros(3, 3, dtype=torch.float64)
+    if angle > 0:
+        a0, a1, a2 = (w / angle).tolist()
+        K = torch.tensor([[0.0, -a2, a1], [a2, 0.0, -a0], [-a1, a0, 0.0]], dtype=torch.float64)
+    R = torch.eye(3, dtype=torch.float64) + math.sin(angle) * K + (1.0 - math.cos(angle)) * (K @ K)
+    c = torch.tensor([(D - 1) / 2.0, (H - 1) / 2.0, (W - 1) / 2.0], dtype=torch.float64)
+    k = torch.stack(torch.meshgrid(*[torch.arange(n, dtype=torch.float64) for n in (D, H, W)], indexing='ij'), -1)
+    p = (k - c) @ R.T + c + torch.tensor([float(s) for s in shift], dtype=torch.float64)
+    grid = (p / c - 1.0).flip(-1).float().unsqueeze(0)  # [-1, 1], x first
+    sample = lambda vol, mode: F.grid_sample(vol.float().unsqueeze(0), grid, mode=mode, padding_mode='border', align_corners=True)[0]
+    return {'im': sample(triple['im'], 'bilinear').contiguous(), 'mask': sample(triple['mask'], 'nearest').bool().contiguous(),
+            'seg': sample(triple['seg'], 'nearest').to(torch.int16).contiguous()}
+
+
+def synthetic_pair(dims, seed=0, noise=0.02, misalign=None):
+    """Two Gaussian blobs + white noise; the moving image has both blobs shifted.  Returns (fixed, moving).
+    misalign: None (the pair as it always was), or {"rotation_deg": [a0, a1, a2], "shift": [s0, s1, s2]}: the moving triple
+    is then rotated and shifted on the host (misalign_triple)."""
     dims = tuple(int(d) for d in dims)
     g = torch.Generator().manual_seed(seed)
     im_f = _blobs(dims, (0.0, 0.0, 0.0), (0.0, 0.0, 0.0)) + noise * torch.randn(dims, generator=g)
@@ -45,7 +69,13 @@ def synthetic_pair(dims, seed=0, noise=0.02):
         return {'im': im.float().unsqueeze(0).contiguous(), 'mask': mask.unsqueeze(0).contiguous(),
                 'seg': seg.unsqueeze(0).contiguous()}
 
-    return pack(im_f), pack(im_m)
+    fixed, moving = pack(im_f), pack(im_m)
+    if misalign is not None:
+        unknown = set(misalign) - {'rotation_deg', 'shift'}
+        if unknown:
+            raise ValueError(f'misalign: unknown keys {sorted(unknown)}; known: ["rotation_deg", "shift"]')
+        moving = misalign_triple(moving, misalign.get('rotation_deg', (0.0, 0.0, 0.0)), misalign.get('shift', (0.0, 0.0, 0.0)))
+    return fixed, moving
 
 
 FIXED_BLOBS = ((0.0, 0.0, 0.0), (0.3, -0.2, 0.1))          # the centres _blobs is called with above, normalised (z, y, x)

@@ -37,7 +37,7 @@ from ..logger import (save_displacement_covariance, save_displacement_mean_and_s
                       save_local_similarity_of_mean, save_local_similarity_posterior, save_native_mean, save_native_sample,
                       save_posterior_comparison,
                       save_residual_histogram, save_residual_nll, save_rhat, save_sample, save_surface_posterior)
-from .. import multires, residual_check
+from .. import affine, multires, residual_check
 from ..multires import coarse_start_options
 from ..utils import (calc_DSC_GPU, calc_image_similarity, calc_norm, calc_no_non_diffeomorphic_voxels, calc_residual_check,
                      init_identity_grid_3D, local_similarity_rows, sample_q_v, transform_coordinates)
@@ -87,6 +87,10 @@ class Trainer(VIMixin, BaseTrainer):
         self.engine = None
         self.v_curr_state, self.SGLD_params = None, None
         self._scalars_cache, self._outputs = None, None
+        # affine pre-alignment of the pair before anything else sees it (affine.py, _affine_init): None when
+        # trainer.affine_init is absent.  Read first: it refuses trainer.native_resolution and trainer.landmarks beside it
+        self.affine_options = affine.affine_init_options(cfg_trainer, config['data_loader']['args']['dims'])
+        self.affine_summary = None
         # split-R-hat of the displacement (diagnostics.py): None when trainer.convergence_diagnostics is off
         self.diagnostics_period = diagnostics_period(cfg_trainer)
         self._chain_moments = None
@@ -157,6 +161,61 @@ class Trainer(VIMixin, BaseTrainer):
         self.coarse_options = coarse_start_options(cfg_trainer, config['data_loader']['args']['dims'],
                                                    config['transformation_module']['type'])
         self.coarse_summary = None
+
+    # ---------------------------------------------------------------- affine pre-alignment
+    def _affine_init(self, fixed, moving):
+        """trainer.affine_init: the rigid / affine map of the pair (affine.register on fixed['im'], moving['im'] over
+        fixed['mask']) -> the moving triple resampled through it; self.affine_summary, the affine/* metrics, one log line per
+        level and, with save_outputs, samples/affine.json.  Deterministic: a resumed run computes the same map again."""
+        opt = self.affine_options
+        dims = tuple(int(n) for n in fixed['im'].shape[2:])
+        sp = getattr(self.data_loader, 'im_spacing', None)
+        spacing = np.ones(3) if sp is None else np.asarray(torch.as_tensor(sp).cpu(), dtype=np.float64).reshape(3)
+        model = affine.AffineModel(opt['model'], spacing)
+        start = time.perf_counter()
+        lin, shift, history = affine.register(fixed['im'], moving['im'], fixed['mask'], model, opt['levels'], opt['max_iters'],
+                                              opt['tol'], opt['min_overlap'], log=self.logger.info)
+        aligned = affine.resample_pair(moving, lin, shift)
+        seconds = time.perf_counter() - start
+        summary = {'model': opt['model'], 'dims': list(dims), 'spacing': spacing.tolist(), 'lin': lin.tolist(), 'shift': shift.tolist(),
+                   'index_matrix': affine.index_matrix(lin, shift, dims).tolist(),
+                   'normalised_matrix': affine.normalised_matrix(lin, shift, dims).tolist(),
+                   'mm_matrix': affine.mm_matrix(lin, shift, dims, spacing).tolist(), 'history': history,
+                   'SSD_before': history[-1]['mean_ssd_first'] if len(history) == 1 else None, 'SSD_after': history[-1]['mean_ssd_last'],
+                   'overlap': history[-1]['overlap'], 'iterations': sum(h['iterations'] for h in history), 'seconds': seconds}
+        if summary['SSD_before'] is None:  # with coarser levels the full grid starts from their map: the identity is measured here
+            f, m = affine._standardise(fixed['im'], moving['im'], fixed['mask'].bool())
+            before = affine.normal_equations(f, m, fixed['mask'], np.eye(3), np.zeros(3))
+            summary['SSD_before'] = before['ssd'] / max(before['n'], 1)
+        if 'seg' in fixed and 'seg' in moving and self.structures_dict:
+            for name, seg in (('DSC_before', moving['seg']), ('DSC_after', aligned['seg'])):
+                DSC = calc_DSC_GPU(1, fixed['seg'], seg, self.structures_dict)
+                summary[name] = {structure: float(DSC[0][j]) for j, structure in enumerate(self.structures_dict)}
+        self.affine_summary = summary
+        self.writer.set_step(0)
+        for key in ('SSD_before', 'SSD_after', 'overlap', 'iterations'):
+            self.metrics.update(f'affine/{key}', float(summary[key]))
+        self.logger.info(f'affine pre-alignment ({opt["model"]}): mean SSD {summary["SSD_before"]:.6g} -> {summary["SSD_after"]:.6g} in '
+                         f'{summary["iterations"]} iterations, {seconds:.2f} seconds')
+        if self.config['trainer'].get('save_outputs', True):
+            import json
+            folder = self.config.save_dirs['samples']
+            folder.mkdir(parents=True, exist_ok=True)
+            with open(folder / 'affine.json', 'w') as f:
+                json.dump(summary, f, indent=2)
+        return aligned
+
+    def _save_total_mean(self, mean, spacing):
+        """samples/MCMC_sample_mean_total.vtk: the posterior-mean displacement composed with the pre-alignment, in mm as the
+        mean itself is saved.  A(x + u) - x is affine in u, so the mean composes exactly."""
+        from ..logger import save_field_to_disk
+        ident = init_identity_grid_3D(mean.shape[1:], self.device).permute(0, 4, 1, 2, 3)
+        s = self.affine_summary
+        _, total = affine.compose((ident + transform_coordinates(mean.unsqueeze(0))).contiguous(), s['lin'], s['shift'])
+        self.displacement_mean_total = total[0]
+        folder = self.config.save_dirs['samples']
+        folder.mkdir(parents=True, exist_ok=True)
+        save_field_to_disk(total[0] * spacing[0], str(folder / 'MCMC_sample_mean_total.vtk'), spacing)
 
     # ---------------------------------------------------------------- engine plumbing
     def _engine_config(self):
@@ -643,6 +702,8 @@ class Trainer(VIMixin, BaseTrainer):
         if n_rec > 0 and cfg_trainer.get('save_outputs', True):
             save_displacement_mean_and_std_dev(self.logger, self.config.save_dirs, spacing, self.displacement_mean,
                                                self.displacement_std, moving.get('mask', fixed['mask'])[0].to(mean.dtype), 'MCMC')  # trainer.py:461-462: the MOVING mask
+        if self.affine_summary is not None and n_rec > 0 and cfg_trainer.get('save_outputs', True):
+            self._save_total_mean(mean, spacing)
         if self._native is not None and n_rec > 0 and cfg_trainer.get('save_outputs', True):
             nat = self._native
             out = ops.native_warp(transform_coordinates(mean.unsqueeze(0)).contiguous(), nat['grid'], im=nat['moving_im'],
@@ -1137,6 +1198,8 @@ class Trainer(VIMixin, BaseTrainer):
         for fixed, moving, var_params_q_v in self.data_loader:
             fixed = {k: v.to(self.device) for k, v in fixed.items()}
             moving = {k: v.to(self.device) for k, v in moving.items()}
+            if self.affine_options is not None:
+                moving = self._affine_init(fixed, moving)
             self._engine_init(fixed, moving)
             self._GMM_init(fixed, moving, var_params_q_v)
             self._metrics_init(fixed, moving)
