@@ -631,6 +631,44 @@ int irs_affine_transformation(const double* lin, const double* shift, float* out
 int irs_affine_compose(const float* transformation, const double* lin, const double* shift, float* total_transformation,
                        float* total_displacement, int C, int D, int H, int W, void* stream);
 
+/* Cubic B-spline output resampling (absent in the reference, which resamples everything trilinearly): the interpolating cubic
+ * B-spline of a volume, for the images that are written -- never for what the chain reads, whose adjoint is the trilinear one's.
+ * A volume s of extents n = (D, H, W), every one >= 2 and fewer than 2^30 voxels, is extended by whole-sample mirroring
+ * (k < 0 -> -k, k > n - 1 -> 2 (n - 1) - k; scipy's mode='mirror').
+ *  - Coefficients (irs_bspline_prefilter): im (Cim,1,D,H,W) float32 -> coeff of the same shape, Cim in 1 .. IRS_MAX_CHAINS,
+ *    Cim D <= 65535; coeff may be im.  The lines are filtered separably, along x (the last axis), then y, then z.  Per line of
+ *    length n, with z1 = sqrt(3) - 2 and gain 6, in double, every operation rounded once and none contracted, T = 2 n - 2 and
+ *    mir() the mirror above:
+ *      1. c+[0] = (sum_{k=0}^{T-1} zk (6 s[mir(k)])) / (1 - z1^T) when T <= 32, otherwise the first 32 terms of the same series
+ *         with no divisor (|z1|^32 / (1 - |z1|) = 7e-19 is below double rounding); the sum starts at 0 and runs in the order of
+ *         k; zk starts at 1 and is multiplied by z1 after every term, and z1^T is zk after the last one;
+ *      2. c+[k] = 6 s[k] + z1 c+[k-1] for k = 1 .. n - 1;
+ *      3. c[n-1] = (z1 / (z1^2 - 1)) (c+[n-1] + z1 c+[n-2]), the constant formed on the host in double;
+ *      4. c[k] = z1 (c[k+1] - c+[k]) for k = n - 2 .. 0.
+ *    The running values -- c+[k-1] in 2, c[k+1] in 4 -- are carried in double.  The line rests in float32 between its two
+ *    sweeps: every c+[k] is stored rounded to float32 once and steps 3 and 4 read the stored values (coeff may be the input and
+ *    there is no workspace, so float32 is all there is); every c[k] is rounded to float32 once when it is stored, and the next
+ *    axis reads float32.  Three launches; no scratch; deterministic; no atomics; no host sync.
+ *  - Evaluation at a position q in index coordinates, in float32, every operation rounded once: per axis q is clamped to
+ *    [0, n - 1] (the border rule of every warp; a NaN goes to 0), i0 = min(floor(q), n - 2), t = q - i0, u = 1 - t; the taps are
+ *    i0 - 1 .. i0 + 2, mirrored once, with the weights w0 = u*u*u/6, w1 = (3*t*t*t - 6*t*t + 4)/6, w2 = (3*u*u*u - 6*u*u + 4)/6,
+ *    w3 = t*t*t/6, each formed left to right as written.  The sum is separable: for every (z, y) tap pair the row sum over the
+ *    four x taps, acc = acc + w c from 0 with the taps ascending; then the four row sums over y in the same way; then over z.
+ *  - irs_bspline_warp, the twin of irs_warp_transformation: coeff (Cim,1,D,H,W) float32 with Cim 1 (shared) or C;
+ *    transformation (C,3,D,H,W) float32 in [-1,1], component 0 = x; out (C,1,D,H,W): the spline at the index coordinate
+ *    ((g + 1) * 0.5) * (n - 1) of every voxel, as the trilinear sampler forms it.  C in 1 .. IRS_MAX_CHAINS, C D <= 65535.  One
+ *    launch, one thread per output voxel.
+ *  - irs_native_warp_cubic, the image output of irs_native_warp with the cubic rule (labels and masks stay with that call):
+ *    displacement, dims, native, padding, Cim, fill and im_out as there, every native extent >= 2; im (Cim,1,n0,n1,n2) the
+ *    unpadded native image and coeff its irs_bspline_prefilter.  The source position r of a voxel is irs_native_warp's (the
+ *    same expressions).  Where all eight trilinear taps of r lie inside the native box the value is the spline of the unpadded
+ *    volume at q = r - p, from coeff; elsewhere -- in the pad and on the ramp between the image edge and the fill -- it is the
+ *    trilinear blend with `fill` read from im, exactly what irs_native_warp writes.  One launch; deterministic; no host sync. */
+int irs_bspline_prefilter(const float* im, float* coeff, int Cim, int D, int H, int W, void* stream);
+int irs_bspline_warp(const float* coeff, int Cim, const float* transformation, float* out, int C, int D, int H, int W, void* stream);
+int irs_native_warp_cubic(const float* displacement, int C, const int32_t* dims, const int32_t* native, const int32_t* padding,
+                          const float* im, const float* coeff, int Cim, float fill, float* im_out, void* stream);
+
 /* Landmark propagation (absent in the reference, which has no point-set operator): a sampled displacement evaluated at K
  * positions that are no voxel centres, and the posterior of the mapped landmarks with their target registration error (TRE).
  * warped(x) = moving(x + d(x)): a point p of the fixed grid maps to p + d(p) in the moving image; points of the moving space

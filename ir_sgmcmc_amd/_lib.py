@@ -211,6 +211,9 @@ SIGNATURES = {
     'irs_affine_normal_equations': [_P, _P, _P, _I, _I, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, C.c_size_t, _P],
     'irs_affine_transformation': [C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _I, _I, _I, _P],
     'irs_affine_compose': [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, _I, _I, _I, _I, _P],
+    'irs_bspline_prefilter': [_P, _P, _I, _I, _I, _I, _P],
+    'irs_bspline_warp': [_P, _I, _P, _P, _I, _I, _I, _I, _P],
+    'irs_native_warp_cubic': [_P, _I, _I32P, _I32P, _I32P, _P, _P, _I, _F, _P, _P],
     'irs_create': [C.POINTER(IrsConfig), C.POINTER(_P)],
     'irs_destroy': [_P],
     'irs_workspace_bytes': [_P],

@@ -41,6 +41,43 @@ inline bool workspace_ok(const char* who, size_t have, size_t need, const char* 
     return have >= need || !fail("%s: workspace of %zu bytes, %zu needed (%s)", who, have, need, hint);
 }
 
+// the geometry of a native-resolution warp (irs_native_warp, irs_native_warp_cubic) -> gm (out_scale 0, fill unset) and the
+// voxels of the native volume; `min_native`: the smallest native extent the caller takes
+inline bool native_geometry_ok(const char* who, int C, const int32_t* dims, const int32_t* native, const int32_t* padding,
+                               int min_native, NativeGeom& gm, int64_t& voxels) {
+    voxels = 1;
+    for (int a = 0; a < 3; ++a) {
+        const int64_t P = (int64_t)native[a] + 2 * (int64_t)padding[a];
+        if (native[a] < min_native) return !fail("%s: native[%d] = %d < %d", who, a, native[a], min_native);
+        if (padding[a] < 0) return !fail("%s: padding[%d] = %d < 0", who, a, padding[a]);
+        if (P < 2) return !fail("%s: padded extent %lld of axis %d, >= 2 needed", who, (long long)P, a);
+        if (dims[a] < 2) return !fail("%s: dims[%d] = %d < 2", who, a, dims[a]);
+        if (P >= ((int64_t)1 << 24)) return !fail("%s: padded extent %lld of axis %d is not exact in float32", who, (long long)P, a);
+        voxels *= native[a];
+        gm.n[a] = native[a];
+        gm.p[a] = padding[a];
+        gm.P[a] = (int)P;
+        gm.m[a] = dims[a];
+        gm.grid_step[a] = (float)((double)(dims[a] - 1) / (double)(P - 1));
+        gm.half_extent[a] = 0.5f * (float)(P - 1);
+        gm.out_scale[a] = 0.0f;
+        if (voxels >= ((int64_t)1 << 30)) return !fail("%s: the native volume must have fewer than 2^30 voxels", who);
+    }
+    if (!dims_ok(C, dims[0], dims[1], dims[2])) return !fail("%s: bad dims", who);
+    // the launch is one block row per (chain, plane) and per four rows of a plane
+    return ((int64_t)native[0] * C <= 65535 && (native[1] + 3) / 4 <= 65535) ||
+           !fail("%s: native shape (%d, %d, %d) x %d chains exceeds the launch grid", who, native[0], native[1], native[2], C);
+}
+
+// the volume of a cubic B-spline call: every extent >= 2 (the mirror needs two samples), fewer than 2^30 voxels, and `volumes`
+// volumes of it within the launch grid (one block row per volume and plane, and per four rows of a plane)
+inline bool bspline_volume_ok(const char* who, int volumes, int D, int H, int W) {
+    if (D < 2 || H < 2 || W < 2) return !fail("%s: dims (%d, %d, %d), every one >= 2 needed", who, D, H, W);
+    if ((int64_t)D * H * W >= ((int64_t)1 << 30)) return !fail("%s: the volume must have fewer than 2^30 voxels", who);
+    return ((int64_t)D * volumes <= 65535 && (H + 3) / 4 <= 65535) ||
+           !fail("%s: dims (%d, %d, %d) x %d volumes exceed the launch grid", who, D, H, W, volumes);
+}
+
 inline SplineTaps make_spline(int cps) {
     // sampled cubic B-spline (utils/transformation.py:79-102); evaluated in double, stored as float like the reference
     SplineTaps t;

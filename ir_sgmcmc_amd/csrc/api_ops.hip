@@ -961,28 +961,8 @@ int irs_native_warp(const float* displacement, int C, const int32_t* dims, const
         return fail("irs_native_warp: an output is requested of a moving volume that is NULL");
     if (displacement_out && !scale) return fail("irs_native_warp: displacement_out needs scale");
     NativeGeom gm;
-    int64_t voxels = 1;
-    for (int a = 0; a < 3; ++a) {
-        const int64_t P = (int64_t)native[a] + 2 * (int64_t)padding[a];
-        if (native[a] < 1) return fail("irs_native_warp: native[%d] = %d < 1", a, native[a]);
-        if (padding[a] < 0) return fail("irs_native_warp: padding[%d] = %d < 0", a, padding[a]);
-        if (P < 2) return fail("irs_native_warp: padded extent %lld of axis %d, >= 2 needed", (long long)P, a);
-        if (dims[a] < 2) return fail("irs_native_warp: dims[%d] = %d < 2", a, dims[a]);
-        if (P >= ((int64_t)1 << 24)) return fail("irs_native_warp: padded extent %lld of axis %d is not exact in float32", (long long)P, a);
-        voxels *= native[a];
-        gm.n[a] = native[a];
-        gm.p[a] = padding[a];
-        gm.P[a] = (int)P;
-        gm.m[a] = dims[a];
-        gm.grid_step[a] = (float)((double)(dims[a] - 1) / (double)(P - 1));
-        gm.half_extent[a] = 0.5f * (float)(P - 1);
-        gm.out_scale[a] = 0.0f;
-        if (voxels >= ((int64_t)1 << 30)) return fail("irs_native_warp: the native volume must have fewer than 2^30 voxels");
-    }
-    if (!dims_ok(C, dims[0], dims[1], dims[2])) return fail("irs_native_warp: bad dims");
-    // the launch is one block row per (chain, plane) and per four rows of a plane
-    if ((int64_t)native[0] * C > 65535 || (native[1] + 3) / 4 > 65535)
-        return fail("irs_native_warp: native shape (%d, %d, %d) x %d chains exceeds the launch grid", native[0], native[1], native[2], C);
+    int64_t voxels;
+    if (!native_geometry_ok(__func__, C, dims, native, padding, 1, gm, voxels)) return 1;
     if (displacement_out)
         for (int c = 0; c < 3; ++c) {
             if (!isfinite(scale[c])) return fail("irs_native_warp: scale[%d] = %g, a finite value needed", c, (double)scale[c]);
@@ -992,6 +972,21 @@ int irs_native_warp(const float* displacement, int C, const int32_t* dims, const
     gm.fill = fill;
     launch_native_warp(displacement, im_out ? im : nullptr, seg_out ? seg : nullptr, mask_out ? mask : nullptr,
                        Cim == 1 ? 0 : voxels, im_out, seg_out, mask_out, displacement_out, gm, C, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_native_warp_cubic(const float* displacement, int C, const int32_t* dims, const int32_t* native, const int32_t* padding,
+                          const float* im, const float* coeff, int Cim, float fill, float* im_out, void* stream) {
+    if (!displacement || !dims || !native || !padding || !im || !coeff || !im_out) return fail("irs_native_warp_cubic: null pointer");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!broadcast_ok(Cim, C)) return fail("irs_native_warp_cubic: moving volumes of %d chains, 1 or %d needed", Cim, C);
+    NativeGeom gm;
+    int64_t voxels;
+    if (!native_geometry_ok(__func__, C, dims, native, padding, 2, gm, voxels)) return 1;
+    if (!isfinite(fill)) return fail("irs_native_warp_cubic: fill = %g, a finite value needed", (double)fill);
+    gm.fill = fill;
+    launch_native_warp_cubic(displacement, im, coeff, Cim == 1 ? 0 : voxels, im_out, gm, C, (hipStream_t)stream);
     LAUNCH_CHECK();
     return 0;
 }
@@ -1303,6 +1298,29 @@ int irs_affine_compose(const float* transformation, const double* lin, const dou
     AffineMap map;
     if (!affine_ok(__func__, D, H, W, lin, shift, (int64_t)C * D, map)) return 1;
     launch_affine_compose(transformation, map, total_transformation, total_displacement, C, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
+// cubic B-spline output resampling (bspline_kernels.hip)
+// ================================================================================================
+int irs_bspline_prefilter(const float* im, float* coeff, int Cim, int D, int H, int W, void* stream) {
+    if (!im || !coeff) return fail("irs_bspline_prefilter: null pointer");
+    if (!chain_count_ok(Cim)) return fail("irs_bspline_prefilter: Cim = %d volumes, 1..%d", Cim, IRS_MAX_CHAINS);
+    if (!bspline_volume_ok(__func__, Cim, D, H, W)) return 1;
+    launch_bspline_prefilter(im, coeff, Cim, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_bspline_warp(const float* coeff, int Cim, const float* transformation, float* out, int C, int D, int H, int W, void* stream) {
+    if (!coeff || !transformation || !out) return fail("irs_bspline_warp: null pointer");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!broadcast_ok(Cim, C)) return fail("irs_bspline_warp: coefficients of %d chains, 1 or %d needed", Cim, C);
+    if (!bspline_volume_ok(__func__, C, D, H, W)) return 1;
+    const Vol vol = make_vol(D, H, W);
+    launch_bspline_warp(coeff, Cim == 1 ? 0 : vol.V, transformation, out, C, vol, (hipStream_t)stream);
     LAUNCH_CHECK();
     return 0;
 }

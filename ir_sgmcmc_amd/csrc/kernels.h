@@ -410,6 +410,18 @@ void launch_affine_transformation(const AffineMap& map, float* out, const Vol& v
 void launch_affine_compose(const float* transformation, const AffineMap& map, float* total_transformation, float* total_displacement,
                            int C, const Vol& vol, hipStream_t st);
 
+// ---- bspline_kernels.hip: cubic B-spline resampling of the written images (absent in the reference) -- the prefilter and the
+// two gathers; include/irsgmcmc.h has the definition
+// im, coeff (volumes, D,H,W) float32, coeff may be im; three launches (x, y, z); volumes * D <= 65535
+void launch_bspline_prefilter(const float* im, float* coeff, int volumes, const Vol& vol, hipStream_t st);
+// coeff (1 or C, V) with coeff_stride 0 or V; transformation (C,3,V) in [-1,1]; out (C,V)
+void launch_bspline_warp(const float* coeff, int64_t coeff_stride, const float* transformation, float* out, int C, const Vol& vol,
+                         hipStream_t st);
+// the image output of launch_native_warp with the cubic rule: u (C,3,m); im, coeff (1 or C, n) with moving_stride 0 or n0 n1 n2;
+// im_out (C,n)
+void launch_native_warp_cubic(const float* u, const float* im, const float* coeff, int64_t moving_stride, float* im_out,
+                              const NativeGeom& gm, int C, hipStream_t st);
+
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h
 }  // namespace irs

@@ -19,37 +19,12 @@
 #include <array>
 #include <utility>
 
-#include "kernels.h"
+#include "native_device.h"
 
 namespace irs {
 namespace {
 
 enum : int { kNatIm = 1, kNatSeg = 2, kNatMask = 4, kNatDisp = 8 };
-
-// tap pair and weights of one axis at the position r, 0 <= r <= last
-struct NativeTap {
-    int i0, i1;
-    float w0, w1;
-};
-__device__ __forceinline__ NativeTap native_tap(float r, int last) {
-    NativeTap t;
-    const float f = floorf(r);
-    t.i0 = min((int)f, last);
-    t.i1 = min(t.i0 + 1, last);
-    t.w1 = __fsub_rn(r, f);
-    t.w0 = __fsub_rn(__fadd_rn(f, 1.0f), r);
-    return t;
-}
-
-// one axis of the moving volume: the padded index k (0 <= k < P) as an index clamped into the native box and whether it was in it
-struct BoxIndex {
-    int i;
-    bool in;
-};
-__device__ __forceinline__ BoxIndex box_index(int k, int p, int n) {
-    const int i = k - p;
-    return {min(max(i, 0), n - 1), i >= 0 && i < n};
-}
 
 template <int OUT>
 __global__ __launch_bounds__(kBlock) void native_warp_kernel(const float* __restrict__ u, const float* __restrict__ im,
@@ -61,34 +36,8 @@ __global__ __launch_bounds__(kBlock) void native_warp_kernel(const float* __rest
     const int idx[3] = {z, y, x};  // axis order (D, H, W); channel c of a field belongs to axis 2 - c
 
     // 1. the displacement at the grid coordinate of this voxel
-    NativeTap ft[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float g = fminf(__fmul_rn((float)(idx[a] + gm.p[a]), gm.grid_step[a]), (float)(gm.m[a] - 1));
-        ft[a] = native_tap(g, gm.m[a] - 1);
-    }
-    const unsigned mhw = (unsigned)(gm.m[1] * gm.m[2]), mw = (unsigned)gm.m[2];
-    const unsigned fz[2] = {(unsigned)ft[0].i0 * mhw, (unsigned)ft[0].i1 * mhw};
-    const unsigned fy[2] = {(unsigned)ft[1].i0 * mw, (unsigned)ft[1].i1 * mw};
-    const unsigned fx[2] = {(unsigned)ft[2].i0, (unsigned)ft[2].i1};
-    const int64_t Vm = (int64_t)gm.m[0] * gm.m[1] * gm.m[2];
     float uc[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float* f = u + ((int64_t)chain * 3 + c) * Vm;
-        float pz[2];
-#pragma unroll
-        for (int cz = 0; cz < 2; ++cz) {
-            float py[2];
-#pragma unroll
-            for (int cy = 0; cy < 2; ++cy) {
-                const unsigned row = fz[cz] + fy[cy];
-                py[cy] = __fadd_rn(__fmul_rn(ft[2].w0, f[row + fx[0]]), __fmul_rn(ft[2].w1, f[row + fx[1]]));
-            }
-            pz[cz] = __fadd_rn(__fmul_rn(ft[1].w0, py[0]), __fmul_rn(ft[1].w1, py[1]));
-        }
-        uc[c] = __fadd_rn(__fmul_rn(ft[0].w0, pz[0]), __fmul_rn(ft[0].w1, pz[1]));
-    }
+    native_displacement(u, chain, idx, gm, uc);
     if (OUT & kNatDisp) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) disp_out[((int64_t)chain * 3 + c) * vol.V + vox] = __fmul_rn(uc[c], gm.out_scale[c]);
@@ -97,46 +46,12 @@ __global__ __launch_bounds__(kBlock) void native_warp_kernel(const float* __rest
 
     // 2., 3. the source position in the padded frame, clamped to the padded box
     float r[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float last = (float)(gm.P[a] - 1);
-        const float raw = __fadd_rn((float)(idx[a] + gm.p[a]), __fmul_rn(uc[2 - a], gm.half_extent[a]));
-        r[a] = fminf(fmaxf(raw, 0.0f), last);  // a NaN displacement samples the first plane (fmaxf drops it)
-    }
+    native_source(uc, idx, gm, r);
     const unsigned nhw = (unsigned)(vol.H * vol.W), nw = (unsigned)vol.W;
     const int64_t mov = (int64_t)chain * moving_stride, outb = (int64_t)chain * vol.V + vox;
 
     // 4. the taps, read from the unpadded volume
-    if (OUT & kNatIm) {
-        unsigned off[3][2];
-        bool in[3][2];
-        float w[3][2];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const NativeTap t = native_tap(r[a], gm.P[a] - 1);
-            const unsigned stride = a == 0 ? nhw : (a == 1 ? nw : 1u);
-            const BoxIndex b0 = box_index(t.i0, gm.p[a], gm.n[a]), b1 = box_index(t.i1, gm.p[a], gm.n[a]);
-            off[a][0] = (unsigned)b0.i * stride;
-            off[a][1] = (unsigned)b1.i * stride;
-            in[a][0] = b0.in;
-            in[a][1] = b1.in;
-            w[a][0] = t.w0;
-            w[a][1] = t.w1;
-        }
-        const float* src = im + mov;
-        float acc = 0.0f;
-#pragma unroll
-        for (int cz = 0; cz < 2; ++cz)
-#pragma unroll
-            for (int cy = 0; cy < 2; ++cy)
-#pragma unroll
-                for (int cx = 0; cx < 2; ++cx) {
-                    const float v = src[off[0][cz] + off[1][cy] + off[2][cx]];
-                    const float val = (in[0][cz] && in[1][cy] && in[2][cx]) ? v : gm.fill;
-                    acc = __fadd_rn(acc, __fmul_rn(val, __fmul_rn(__fmul_rn(w[2][cx], w[1][cy]), w[0][cz])));
-                }
-        im_out[outb] = acc;
-    }
+    if (OUT & kNatIm) im_out[outb] = native_trilinear(im + mov, native_taps(r, gm), gm.fill);
     if (OUT & (kNatSeg | kNatMask)) {
         unsigned off = 0;
         bool in = true;

@@ -37,7 +37,7 @@ from ..logger import (save_displacement_covariance, save_displacement_mean_and_s
                       save_local_similarity_of_mean, save_local_similarity_posterior, save_native_mean, save_native_sample,
                       save_posterior_comparison,
                       save_residual_histogram, save_residual_nll, save_rhat, save_sample, save_surface_posterior)
-from .. import affine, multires, residual_check
+from .. import affine, bspline, multires, residual_check
 from ..multires import coarse_start_options
 from ..utils import (calc_DSC_GPU, calc_image_similarity, calc_norm, calc_no_non_diffeomorphic_voxels, calc_residual_check,
                      init_identity_grid_3D, local_similarity_rows, sample_q_v, transform_coordinates)
@@ -161,6 +161,11 @@ class Trainer(VIMixin, BaseTrainer):
         self.coarse_options = coarse_start_options(cfg_trainer, config['data_loader']['args']['dims'],
                                                    config['transformation_module']['type'])
         self.coarse_summary = None
+        # cubic B-spline resampling of the images that are saved (bspline.py): None unless trainer.output_interpolation is
+        # "cubic".  _spline_coeff: the coefficients of the moving image, formed when the engine is set up (a resumed run forms
+        # them again: nothing goes into a checkpoint)
+        self.interpolation_options = bspline.output_interpolation_options(cfg_trainer)
+        self._spline_coeff = None
 
     # ---------------------------------------------------------------- affine pre-alignment
     def _affine_init(self, fixed, moving):
@@ -267,6 +272,26 @@ class Trainer(VIMixin, BaseTrainer):
         self._fixed, self._moving = self.engine.prepare(fixed, moving)
         self._mask_idx = None
         self._set_hyper_parameters(self.engine)
+        if self.interpolation_options is not None:
+            self._spline_coeff = self._spline_prefilter(moving['im'], 'the moving image')
+
+    def _spline_prefilter(self, im, what):
+        """the cubic B-spline coefficients of `im` (.,1,D,H,W), with the one log line of trainer.output_interpolation"""
+        torch.cuda.synchronize()
+        start = time.perf_counter()
+        coeff = bspline.prefilter(im.contiguous())
+        peak = float(coeff.abs().max())  # the read-back waits for the three passes
+        self.logger.info(f'output interpolation: cubic B-spline of {what} {tuple(im.shape[2:])}, max|c| {peak:.6g}, prefilter '
+                         f'{time.perf_counter() - start:.4f} seconds')
+        return coeff
+
+    def _saved_image(self, im_moving_warped, transformation):
+        """the warped moving image that goes to disk: the transition's trilinear one, or -- trainer.output_interpolation
+        "cubic" -- the spline of the moving image at the same transformation.  The chain and every metric keep reading the
+        trilinear image."""
+        if self._spline_coeff is None:
+            return im_moving_warped
+        return bspline.warp(self._spline_coeff, transformation.contiguous())
 
     def _set_hyper_parameters(self, engine, lognormal=True):
         """hyper-parameters of the loss objects -> the device state of `engine`.  lognormal False leaves RegLoss_LogNormal's
@@ -619,8 +644,9 @@ class Trainer(VIMixin, BaseTrainer):
                                                    spacing)
                 no_voxels = int(np.prod(displacement.shape[2:]))
                 if save_samples:
+                    saved_im = self._saved_image(output['im_moving_warped'], transformation)
                     for idx in range(self.no_chains):
-                        save_sample(self.config.save_dirs, spacing, sample_no, output['im_moving_warped'][idx:idx + 1],
+                        save_sample(self.config.save_dirs, spacing, sample_no, saved_im[idx:idx + 1],
                                     displacement[idx:idx + 1], log_det_J[idx:idx + 1], 'MCMC', chain_no=idx)
                 for idx in range(self.no_chains):
                     n_rec += 1
@@ -706,8 +732,12 @@ class Trainer(VIMixin, BaseTrainer):
             self._save_total_mean(mean, spacing)
         if self._native is not None and n_rec > 0 and cfg_trainer.get('save_outputs', True):
             nat = self._native
-            out = ops.native_warp(transform_coordinates(mean.unsqueeze(0)).contiguous(), nat['grid'], im=nat['moving_im'],
-                                  fill=nat['fill'], want_displacement=nat['grid'].mm_scale())
+            u_mean = transform_coordinates(mean.unsqueeze(0)).contiguous()
+            cubic = nat['coeff'] is not None
+            out = ops.native_warp(u_mean, nat['grid'], im=None if cubic else nat['moving_im'], fill=nat['fill'],
+                                  want_displacement=nat['grid'].mm_scale())
+            if cubic:
+                out['im'] = bspline.native_warp_cubic(u_mean, nat['grid'], nat['moving_im'], nat['coeff'], nat['fill'])
             save_native_mean(self.logger, self.config.save_dirs, nat['grid'].zooms, out['displacement'][0], out['im'][0, 0], 'MCMC')
         if self.similarity_options is not None and n_rec > 0:
             # the moving image under the posterior-mean displacement: identity + the mean in [-1, 1] coordinates
@@ -876,10 +906,12 @@ class Trainer(VIMixin, BaseTrainer):
         pair = self.data_loader.native()
         to = lambda t: t.unsqueeze(0).contiguous().to(self.device)
         self._native = {'grid': pair['grid'], 'fill': pair['fill']['moving'], 'moving_im': to(pair['moving']['im']),
-                        'moving_seg': to(pair['moving']['seg']), 'fixed_seg': to(pair['fixed']['seg'])}
+                        'moving_seg': to(pair['moving']['seg']), 'fixed_seg': to(pair['fixed']['seg']), 'coeff': None}
         g = pair['grid']
         self.logger.info(f'native resolution: {g.shape} voxels of {g.zooms} mm, padded by {g.padding} to {g.padded}, '
                          f'registered at {g.dims}')
+        if self.interpolation_options is not None:
+            self._native['coeff'] = self._spline_prefilter(self._native['moving_im'], 'the native moving image')
 
     def _log_native(self, sample_no, displacement, save):
         """the sample carried to the image's own voxel grid in ONE launch: the warped native moving segmentation -> the metrics
@@ -889,9 +921,12 @@ class Trainer(VIMixin, BaseTrainer):
         nat, opt = self._native, self.native_options
         grid = nat['grid']
         want = set(opt['save']) if save else set()
-        out = ops.native_warp(transform_coordinates(displacement).contiguous(), grid, seg=nat['moving_seg'],
-                              im=nat['moving_im'] if 'im' in want else None, fill=nat['fill'],
-                              want_displacement=grid.mm_scale() if 'displacement' in want else None)
+        cubic = nat['coeff'] is not None and 'im' in want  # the saved image alone: the labels stay nearest-neighbour
+        u = transform_coordinates(displacement).contiguous()
+        out = ops.native_warp(u, grid, seg=nat['moving_seg'], im=nat['moving_im'] if 'im' in want and not cubic else None,
+                              fill=nat['fill'], want_displacement=grid.mm_scale() if 'displacement' in want else None)
+        if cubic:
+            out['im'] = bspline.native_warp_cubic(u, grid, nat['moving_im'], nat['coeff'], nat['fill'])
         if self.structures_dict:
             self._log_segmentation_metrics([f'MCMC/chain_{idx}/native' for idx in range(self.no_chains)], nat['fixed_seg'],
                                            out['seg'], grid.spacing_xyz())

@@ -231,11 +231,11 @@ class VIMixin:
             if 'seg' in moving and self.structures_dict:
                 self._log_segmentation_metrics(('VI/test',), fixed['seg'], self.registration_module(moving['seg'], transformation), spacing)
             if save:
-                save_sample(self.config.save_dirs, spacing, n, warped, displacement, log_det_J, 'VI')
+                save_sample(self.config.save_dirs, spacing, n, self._saved_image(warped, transformation), displacement, log_det_J, 'VI')
         transformation, displacement = self.transformation_module(self._smooth(var_params_q_v['mu']))
         warped = self.registration_module(moving['im'], transformation)
         if save:   # save_variational_posterior_mean (logger/logger.py:198-208)
-            save_im(self.config.save_dirs, spacing, warped[0, 0], 'im_moving_warped_mu')
+            save_im(self.config.save_dirs, spacing, self._saved_image(warped, transformation)[0, 0], 'im_moving_warped_mu')
             save_field(self.config.save_dirs, spacing, displacement[0] * spacing[0], 'displacement_mu')
         if samples:
             mean, std = calc_posterior_statistics(torch.stack(samples), device=self.device)
