@@ -847,6 +847,24 @@ int irs_sparse_adjoint_set(irs_ctx* ctx, int on);
  * switched off, on a slab context, before the first transition, and on a volume so small that the full-column launch already uses
  * the shortest pieces (128^3 with one chain: the lists could only match them).  Calls irs_flush; blocking. */
 int irs_sparse_adjoint_get(irs_ctx* ctx, int32_t* out, void* stream);
+/* The sparse data stage of a context on (the default) or off.  On: the z-extent of the fixed mask is found on the device in every
+ * transition, the warp computes only the 64 x 8 tile-planes within 3 lcc_s voxels of it (SSD: on it), and the LCC map and the data
+ * term march piece lists of their 32 x 16 tile columns at reach lcc_s and 2 lcc_s (the data term zero-fills the rest of g_warped;
+ * the statistics keep their dense launch).  What is skipped is only ever multiplied by an exact
+ * zero: v, grad_v, the state and every scalar equal the dense stage's as numbers, except data_term[c], an fp64 sum whose grouping
+ * follows the pieces (it differs by re-association, at most n_masked 2^-52 relative to the sum of |-log p|).  A transition whose
+ * irs_io asks for im_moving_warped or residuals runs the dense stage.  on: 0 off; 1 on, where the volume is large enough for lists
+ * to be shorter than the full-column segments (see irs_sparse_data_get); n >= 2: on whatever the volume's size, with pieces of at
+ * most n planes (at least 4) instead of the shortest that fit one resident set -- for tests and A/B runs on small volumes.  A call
+ * of its own, like irs_sparse_adjoint_set. */
+int irs_sparse_data_set(irs_ctx* ctx, int on);
+/* What the sparse data stage did in the LAST transition.  out: int32 [4][no_chains][4], rows warp, LCC map, statistics, data term;
+ * per row and chain: engaged, piece length (planes), entries of the chain in the kernel's list, planes marched -- for the map and
+ * the data term planes of 32 x 16 tile columns in run pieces; for the warp, which has no list, tile-planes of 64 x 8 inside the
+ * hull (piece length and entries 0); the statistics row is zero (dense launch).  All zero when switched off, on a slab context, before the first
+ * transition, when the dense stage ran, and on a volume whose full-column LCC launches already use the shortest pieces (128^3).
+ * Calls irs_flush; blocking. */
+int irs_sparse_data_get(irs_ctx* ctx, int32_t* out, void* stream);
 
 /* timing hook for bench.py: the same transition with hipEvents recorded on `stream` around the stages; blocking.
  * All times in milliseconds for THIS call. */

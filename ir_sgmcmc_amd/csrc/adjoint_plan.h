@@ -1,6 +1,6 @@
-// Splitting arithmetic of the sparse adjoint plan (adjoint_plan.hip): which planes of a tile column an adjoint squaring step
-// marches, which it only zero-fills, and how a column is cut into pieces.  Plain integer functions, host and device: the device
-// kernels and tests/csrc/adjoint_plan_check.cpp (a CPU program) run the same code.
+// Splitting arithmetic of the sparse plans (adjoint_plan.hip): which planes of a tile column an adjoint squaring step -- or a kernel
+// of the data stage -- marches, which it only zero-fills, and how a column is cut into pieces.  Plain integer functions, host and
+// device: the device kernels and tests/csrc/adjoint_plan_check.cpp / data_plan_check.cpp (CPU programs) run the same code.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -81,6 +81,35 @@ IRS_HD ColPlan plan_column_of(const int* runs, int k, int col, int C, int ntx, i
     return plan_column(r[0], r[1], nlo, nhi);
 }
 
+// ---- the same arithmetic for any tile and reach (the data stage: adjoint_plan.hip, "sparse data stage")
+constexpr int kLccTX = 32, kLccTY = 16;   // tile column of the LCC map and of the data term (stencil_kernels.hip: LMX x LMY)
+constexpr int kWarpTX = 64, kWarpTY = 8;  // tile-plane of the warp (field_kernels.hip)
+constexpr int kDataKernels = 4;           // read-back rows of the data stage: warp, LCC map, statistics (dense: zero), data term
+enum PlanFill { kFillNext = 0, kFillAll = 1, kFillNone = 2 };  // what a list zero-fills: what the next step reads / the rest of every column / nothing
+// How the run ranges and the lists of one launch are formed.  List k has reach reach0 - k * reach_dec; list 0 and the lists behind it
+// may differ in what they fill and in the resident set they are cut for (the data term and the LCC map share a launch).
+struct PlanShape {
+    int tx, ty;
+    int reach0, reach_dec;
+    int fill[2];
+    int G[2];
+    int lmin;
+};
+IRS_HD int plan_reach(const PlanShape& s, int k) { return s.reach0 - k * s.reach_dec; }
+IRS_HD int plan_fill_of(const PlanShape& s, int k) { return s.fill[k > 0 ? 1 : 0]; }
+IRS_HD int plan_resident_of(const PlanShape& s, int k) { return s.G[k > 0 ? 1 : 0]; }
+// the voxels [a, b) of an axis of n within m of tile t of `size`
+IRS_HD void plan_tile_window(int t, int size, int m, int n, int& a, int& b) {
+    a = plan_max(t * size - m, 0);
+    b = plan_min(t * size + size + m, n);
+}
+// the plan of column `col` of list k under fill rule `fill`
+IRS_HD ColPlan plan_column_by(const int* runs, int k, int col, int C, int ntx, int nty, int D, int fill) {
+    if (fill == kFillNext) return plan_column_of(runs, k, col, C, ntx, nty, D);
+    const int* r = runs + ((long long)k * C * ntx * nty + col) * 2;
+    return fill == kFillAll ? plan_column(r[0], r[1], 0, D) : plan_column(r[0], r[1], 0, 0);
+}
+
 IRS_HD int plan_pieces(int len, int L) { return len > 0 ? (len + L - 1) / L : 0; }
 
 // piece j of np equal cuts of [lo, lo + len)
@@ -108,6 +137,14 @@ IRS_HD int plan_pick_len(const int* pieces, int G, int lmin, int lmax) {
     for (int L = lmin; L < lmax; ++L)
         if (pieces[L] <= G) return L;
     return lmax;
+}
+
+// Most run pieces a list of `columns` columns can have: the length search stays within G unless even the longest piece does not
+// fit; a forced length cuts every column at that length.  (The grid of a kernel that gives every run piece a workgroup of its own.)
+IRS_HD int plan_run_bound(int columns, int D, int G, int forced_len) {
+    const int lmax = plan_max(plan_min(kPlanMaxLen, D), 1);
+    if (forced_len > 0) return columns * plan_pieces(D, plan_min(plan_max(forced_len, kPlanMinForced), lmax));
+    return plan_max(G, columns * plan_pieces(D, lmax));
 }
 
 // entries a step's list can hold: a column gives at most ceil(D / kPlanMinForced) run pieces and two fills

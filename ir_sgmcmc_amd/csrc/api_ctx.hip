@@ -50,6 +50,7 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     context_born();
     c->kn = global_knobs();
     c->sparse_adjoint = true;  // (irs_sparse_adjoint_set)
+    c->sparse_data = 1;        // (irs_sparse_data_set)
     c->cfg = *cfg;
     c->C = C;
     c->vol = make_vol(D, H, W);
@@ -130,6 +131,7 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     const size_t o_cmm = take(coarse_minmax_bytes(c->vol, C));
     const bool planned = !sl;  // (the slab engine marches full columns)
     const size_t o_plan = take(planned ? adjoint_plan_bytes(c->vol, C, cfg->no_steps) : 0);
+    const size_t o_dplan = take(planned ? data_plan_bytes(c->vol, C) : 0);
     const size_t o_state = take(sizeof(DevState));
     c->slab_bytes = off;
     // (a context is zeroed at birth and irs_destroy releases whatever exists by then: one teardown for every failure below)
@@ -137,7 +139,13 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
         irs_destroy(c);
         return fail("irs_create: hipMalloc of %zu workspace bytes failed", off);
     }
-    if (c->sl.on) (void)hipMemset(c->slab, 0, off);  // ghost planes nobody has written yet must hold finite values
+    // What nobody has written yet must hold finite values: the ghost planes of a slab, and whatever the sparse data stage leaves
+    // unwritten far from the mask, which later kernels read and multiply by an exact zero (sigma_M is divided by: 1 below)
+    if (hipMemset(c->slab, 0, off) != hipSuccess ||
+        hipMemsetD32((hipDeviceptr_t)(c->slab + o_sig), 0x3f800000, imageI / sizeof(float)) != hipSuccess) {
+        irs_destroy(c);
+        return fail("irs_create: clearing the workspace failed");
+    }
     c->steps = (float*)(c->slab + o_steps);
     c->tmpA = (float*)(c->slab + o_tmpA);
     c->tmpB = (float*)(c->slab + o_tmpB);
@@ -160,6 +168,7 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     c->dmax = (unsigned*)(c->slab + o_dmax);
     c->cmm = (float*)(c->slab + o_cmm);
     if (planned) c->plan = adjoint_plan_views(c->slab + o_plan, c->vol, C, cfg->no_steps);
+    if (planned) c->dplan = data_plan_views(c->slab + o_dplan, c->vol, C);
     c->state = (DevState*)(c->slab + o_state);
 
     if (ensure_lin_tables(c->lin, D, H, W, nullptr)) {
@@ -308,8 +317,9 @@ int irs_get_scalars(irs_ctx* c, irs_scalars* out, void* stream) {
 // the transition
 // ================================================================================================
 // velocity (v + noise, smoothed) -> vs; dense velocity -> d_1..d_n; warp -> warped; residual -> z (+ sigM)
+// data_on (ctx.h): > 0 the warp leaves the tile-planes outside the data plan's hull unwritten, > 1 the LCC map walks its list
 static int forward_pass(irs_ctx* c, const irs_io* io, const float* v, bool with_noise, bool with_jitter, float* vs,
-                        float* warped, float* z, float* gradm, int chains, hipStream_t st, int timed) {
+                        float* warped, float* z, float* gradm, int chains, hipStream_t st, int timed, int data_on = 0) {
     const irs_config& cfg = c->cfg;
     const int C = chains;
     const uint64_t* it = &c->state->st.iteration;
@@ -357,8 +367,10 @@ static int forward_pass(irs_ctx* c, const irs_io* io, const float* v, bool with_
     // 4. warp (+ jitter) and residual
     const float alpha = with_jitter ? cfg.uniform_alpha : 0.0f;
     launch_warp_fwd(io->moving_im, io->moving_chains == 1 ? 0 : c->vol.V, d_last, io->unif, alpha, warped, gradm, 1, C, c->vol, lin,
-                    cfg.seed, 0, it, st);
-    if (cfg.data_loss == IRS_DATA_GMM_LCC)
+                    cfg.seed, 0, it, st, data_on > 0 ? c->dplan.hull : nullptr);
+    if (cfg.data_loss == IRS_DATA_GMM_LCC && data_on > 1)
+        launch_lcc_fwd_plan(c->fhat, c->fhat_chains == 1 ? 0 : c->vol.V, warped, z, c->sigM, cfg.lcc_s, C, c->vol, c->dplan, st);
+    else if (cfg.data_loss == IRS_DATA_GMM_LCC)
         launch_lcc_fwd_march(c->fhat, c->fhat_chains == 1 ? 0 : c->vol.V, warped, z, c->sigM, cfg.lcc_s, C, c->vol, st);
     else
         launch_residual_ssd(io->fixed_im, io->fixed_chains == 1 ? 0 : c->vol.V, warped, z, C, c->vol, st);
@@ -437,7 +449,26 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
     // fused backward warp: the forward warp also writes d(warped)/d(d_last) into gA, and the first adjoint squaring step
     // multiplies it with g_warped while staging (kernels.h: gscale)
     const bool fuse_warp_bwd = c->kn.fuse_warp_bwd != 0;
-    if (forward_pass(c, io, io->v, true, cfg.uniform_alpha > 0.0f, vs, warped, z, fuse_warp_bwd ? c->gA : nullptr, C, st, timed)) return 1;
+    // Sparse data stage (adjoint_plan.hip): the z-extent of the mask, found now on the device, decides which tile-planes the warp
+    // computes and which pieces the LCC map and the data term march.  What stays unwritten holds
+    // the zeros (sigma_M: ones) of irs_create or an earlier transition's values, and is only ever multiplied by an exact zero -- in
+    // the context's own buffers: a caller who asks for the warped image or the residuals gets the dense stage.  The rule on sizes:
+    // only where the full-column LCC launches use segments above the shortest piece (256^3: 19 and 26 planes).  At 128^3 they are 4
+    // to 8 planes in less than one resident set: lists could only match them, and the plan's launches would be a net cost there, as
+    // for the adjoint below.
+    const bool lcc = cfg.data_loss == IRS_DATA_GMM_LCC;
+    const int forced_piece = c->sparse_data > 1 ? c->sparse_data : 0;  // (tests: short pieces on small volumes)
+    int data_on = 0;
+    c->dplan.forced_len = forced_piece;
+    if (c->sparse_data && c->dplan.entries && !io->im_moving_warped && !io->residuals &&
+        (forced_piece > 0 || plan_min(lcc_dense_seg_len(vol, C, false), lcc_dense_seg_len(vol, c->nll_seg_C, true)) > kPlanMinLen)) {
+        // the data term's list needs every chain in one launch (or a single chain); the per-chain launches keep their full columns
+        const bool one_launch = C == 1 || (c->kn.data_batch != 0 && !(c->side && c->kn.chain_overlap != 0));
+        data_on = !lcc ? 1 : one_launch ? 3 : 2;
+        launch_data_plan(io->mask, io->mask_chains, c->dplan, lcc ? cfg.lcc_s : 0, lcc, C, vol, st);
+    }
+    c->data_on = data_on;
+    if (forward_pass(c, io, io->v, true, cfg.uniform_alpha > 0.0f, vs, warped, z, fuse_warp_bwd ? c->gA : nullptr, C, st, timed, data_on)) return 1;
     const int64_t field = (int64_t)C * 3 * vol.V;
     const float* d_last = c->steps + (int64_t)(cfg.no_steps - 1) * field;
     if (io->transformation || io->displacement) launch_svf_outputs(d_last, io->transformation, io->displacement, C, vol, lin, st);
@@ -476,7 +507,7 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
         launch_stats(cfg.virtual_decimation, zc, mask, c->state, c->stat_partials, vol, st, c->dcfg.K);
         if (overlap && ch > 0) HIP_TRY(hipStreamWaitEvent(st, c->ev_side[2 * (ch - 1) + 1], 0));  // data term of chain ch - 1 has read the mixture
         launch_chain_scalar(c->state, c->stat_partials, sb, ch, (ch == 0 ? 7 : 3) | (batch ? 8 : 0), c->dcfg, st, vd);  // chain 0: + the verdict
-        if (batch) continue;
+        if (batch || data_on == 3) continue;
         const float* f = cfg.data_loss == IRS_DATA_GMM_LCC ? c->fhat + (c->fhat_chains == 1 ? 0 : (int64_t)ch * vol.V) : nullptr;
         hipStream_t ds = st;
         if (overlap && ch + 1 < C) {  // (the last chain's data term has nothing to overlap with: it stays on the caller's stream)
@@ -488,7 +519,10 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
                         c->gM + (int64_t)ch * vol.V, c->nll_partials + (int64_t)ch * c->nll_blocks, cfg.lcc_s, 1, vol, ds, c->nll_seg_C);
         if (ds != st) HIP_TRY(hipEventRecord(c->ev_side[2 * ch + 1], c->side));
     }
-    if (batch)
+    if (data_on == 3)  // (one chain, or all chains against their snapshots: scalar stage op bit 3 above)
+        launch_lcc_data_bwd_plan(c->fhat, c->fhat_chains == 1 ? 0 : vol.V, z, c->sigM, io->mask, io->mask_chains == 1 ? 0 : vol.V, c->state, c->gM,
+                                 cfg.lcc_s, C, vol, c->dplan, st);
+    else if (batch)
         launch_data_bwd(cfg.data_loss, c->fhat, c->fhat_chains == 1 ? 0 : vol.V, z, c->sigM, io->mask, io->mask_chains == 1 ? 0 : vol.V, nullptr,
                         c->state, 0, c->gM, c->nll_partials, cfg.lcc_s, C, vol, st, c->nll_seg_C);
     // back through the warp and the squaring steps
@@ -549,8 +583,9 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
                            energy_in_update ? c->energy_partials : nullptr, energy_in_update);
     }
     // bookkeeping (+ the regulariser scalar stage of the L2 family, whose energy the update has just produced: one launch)
-    launch_finalize(c->state, c->nll_partials, c->nll_blocks, c->dcfg, true, c->dmax, c->hint, 4 * C * (cfg.no_steps + 1), vd,
-                    kHintWords - 7, true, st, energy_in_update ? c->energy_partials : nullptr, upd_blocks);
+    launch_finalize(c->state, data_on == 3 ? c->dplan.nll : c->nll_partials, c->nll_blocks, c->dcfg, true, c->dmax, c->hint,
+                    4 * C * (cfg.no_steps + 1), vd, kHintWords - 7, true, st, energy_in_update ? c->energy_partials : nullptr, upd_blocks,
+                    data_on == 3 ? c->dplan.entries : nullptr, data_on == 3 ? c->dplan.count : nullptr);
     c->dmax_clean = true;
     LAUNCH_CHECK();
     if (timed) HIP_TRY(hipEventRecord(c->ev[5], st));
@@ -656,6 +691,44 @@ int irs_sparse_adjoint_get(irs_ctx* c, int32_t* out, void* stream) {
     if (irs_flush(c, stream)) return 1;
     HIP_TRY(hipMemcpyAsync(out, c->plan.stats, n * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+}
+
+int irs_sparse_data_set(irs_ctx* c, int on) {
+    if (!c) return fail("irs_sparse_data_set: null argument");
+    if (on < 0) return fail("irs_sparse_data_set: 0 (off), 1 (on) or a piece length");
+    c->sparse_data = on;
+    return 0;
+}
+
+int irs_sparse_data_get(irs_ctx* c, int32_t* out, void* stream) {
+    if (!c || !out) return fail("irs_sparse_data_get: null argument");
+    const int C = c->C;
+    memset(out, 0, (size_t)kDataKernels * C * kPlanStats * sizeof(int32_t));
+    if (!c->dplan.entries || c->data_on == 0 || c->n_enqueued == 0) return 0;  // the dense stage: nothing engaged
+    if (irs_flush(c, stream)) return 1;
+    // row 0 (warp: no list): the tile-planes of 64 x 8 inside the hull; rows 1 / 3 (map, data term): the lists' own figures; row 2
+    // (statistics): zero -- trimming its segments to the hull measured no faster, it keeps its dense launch
+    const size_t tiles = (size_t)c->dplan.wtx * c->dplan.wty;
+    int* hull = (int*)malloc(sizeof(int) * 2 * tiles * C);
+    int32_t lists[2 * IRS_MAX_CHAINS * kPlanStats];
+    if (!hull) return fail("irs_sparse_data_get: out of host memory");
+    hipError_t e = hipMemcpyAsync(hull, c->dplan.hull, sizeof(int) * 2 * tiles * C, hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(lists, c->dplan.stats, sizeof(int32_t) * 2 * C * kPlanStats, hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) {
+        free(hull);
+        return fail("irs_sparse_data_get: read-back failed: %s", hipGetErrorString(e));
+    }
+    for (int ch = 0; ch < C; ++ch) {
+        int32_t planes = 0;
+        for (size_t t = 0; t < tiles; ++t) planes += hull[(ch * tiles + t) * 2 + 1] - hull[(ch * tiles + t) * 2];
+        out[(size_t)ch * kPlanStats] = 1;
+        out[(size_t)ch * kPlanStats + 3] = planes;
+        if (c->data_on >= 2) memcpy(out + ((size_t)1 * C + ch) * kPlanStats, lists + ((size_t)C + ch) * kPlanStats, sizeof(int32_t) * kPlanStats);
+        if (c->data_on >= 3) memcpy(out + ((size_t)3 * C + ch) * kPlanStats, lists + (size_t)ch * kPlanStats, sizeof(int32_t) * kPlanStats);
+    }
+    free(hull);
     return 0;
 }
 

@@ -59,6 +59,10 @@ struct irs_ctx {
     irs::AdjointPlan plan;  // sparse adjoint plan (adjoint_plan.hip); no buffers on a slab context
     bool sparse_adjoint = true;  // irs_sparse_adjoint_set: the adjoint steps walk the plan's lists (false: full columns)
     bool plan_on = false;   // the last transition enqueued walked the plan's lists
+    irs::DataPlan dplan;    // sparse data stage (adjoint_plan.hip); no buffers on a slab context
+    int sparse_data = 1;    // irs_sparse_data_set: 0 the dense data stage; 1 warp, LCC map, statistics and data term only where the mask
+                            // reaches (where the rule on sizes lets them); n >= 2: on whatever the size, pieces of n planes
+    int data_on = 0;        // the last transition enqueued: 0 dense data stage, 1 the warp's hull, 2 + the map's list, 3 + the data term's
     float* cmm;      // coarse (8^3 cells) min / max of d_k for the source boxes of the any-radius adjoint (kernels.h)
     unsigned* hint = nullptr;  // pinned host copy of dmax as of the last finished transition (written by finalize_kernel, read
                      // by the host WITHOUT synchronisation: a hint that only decides which variants are launched)

@@ -4,6 +4,7 @@
 //   trilinear / nearest warps               (utils/registration.py:17-30, utils/util.py:44-53)
 //   cubic B-spline FFD up-sampling / adjoint (utils/transformation.py:105-153)
 // All of it is HBM/L2-bound gather/stencil work on planar fp32 fields (C,3,D,H,W); no MFMA by design.
+#include "adjoint_plan.h"
 #include "kernels.h"
 #include "warp_device.h"
 
@@ -156,10 +157,17 @@ __device__ __forceinline__ void grid_point(const float* __restrict__ d, const fl
 __global__ __launch_bounds__(kBlock) void warp_fwd_kernel(const float* __restrict__ im, int64_t im_stride,
                                                           const float* __restrict__ d, const float* __restrict__ unif,
                                                           Jitter jt, float* __restrict__ out, float* __restrict__ gradm,
-                                                          int gradm_aos, Vol vol, Lin lin) {
+                                                          int gradm_aos, Vol vol, Lin lin, const int* __restrict__ hull) {
     constexpr int NV = IRS_WARP_NV;
+    static_assert(4 * NV == kWarpTY, "the hull of the sparse data stage is formed for this kernel's 64 x 8 tile-planes");
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y0 = blockIdx.y * (4 * NV) + (threadIdx.x >> 6);
     const int chain = blockIdx.z / vol.nz, z = vol.z0 + blockIdx.z - chain * vol.nz;
+    // sparse data stage: nothing reads the warped image or its gradient further than the hull's reach from the mask (adjoint_plan.hip);
+    // a workgroup whose tile-plane lies outside leaves at once and stores nothing
+    if (hull) {
+        const int* r = hull + (((int64_t)chain * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 2;
+        if (z < r[0] || z >= r[1]) return;
+    }
     if (x >= vol.W || y0 >= vol.H) return;
     const int64_t cb3 = (int64_t)chain * 3 * vol.V;
     const float* src = im + (int64_t)chain * im_stride;
@@ -193,10 +201,10 @@ __global__ __launch_bounds__(kBlock) void warp_fwd_kernel(const float* __restric
 
 void launch_warp_fwd(const float* im, int64_t im_stride, const float* d, const float* unif, float alpha, float* out,
                      float* gradm, int gradm_aos, int C, Vol vol, Lin lin, uint64_t seed, uint64_t iteration,
-                     const uint64_t* dev_iteration, hipStream_t st) {
+                     const uint64_t* dev_iteration, hipStream_t st, const int* hull) {
     const dim3 grid((unsigned)((vol.W + 63) / 64), (unsigned)((vol.H + 4 * IRS_WARP_NV - 1) / (4 * IRS_WARP_NV)), (unsigned)(vol.nz * C));
     hipLaunchKernelGGL(warp_fwd_kernel, grid, dim3(kBlock), 0, st, im, im_stride, d, unif,
-                       make_jitter(alpha, vol, seed, iteration, dev_iteration), out, gradm, gradm_aos, vol, lin);
+                       make_jitter(alpha, vol, seed, iteration, dev_iteration), out, gradm, gradm_aos, vol, lin, hull);
 }
 
 __global__ __launch_bounds__(kBlock) void warp_bwd_kernel(const float* __restrict__ im, int64_t im_stride,

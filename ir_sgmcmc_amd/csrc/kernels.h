@@ -31,7 +31,8 @@ void launch_svf_outputs(const float* d, float* transformation, float* displaceme
                         hipStream_t st);
 void launch_warp_fwd(const float* im, int64_t im_stride, const float* d, const float* unif, float alpha, float* out,
                      float* gradm, int gradm_aos, int C, Vol vol, Lin lin, uint64_t seed, uint64_t iteration,
-                     const uint64_t* dev_iteration, hipStream_t st);
+                     const uint64_t* dev_iteration, hipStream_t st, const int* hull = nullptr);  // hull: DataPlan::hull -- tile-planes
+                                                                                                 // outside it are left unwritten
 void launch_warp_bwd(const float* im, int64_t im_stride, const float* d, const float* unif, float alpha,
                      const float* g_warped, float* g_d, int C, Vol vol, Lin lin, uint64_t seed, uint64_t iteration,
                      const uint64_t* dev_iteration, hipStream_t st);
@@ -86,6 +87,27 @@ AdjointPlan adjoint_plan_views(char* base, Vol vol, int C, int no_steps);
 // the lists are cut for; forced_len > 0: that piece length
 void launch_adjoint_plan(const float* g_warped, const unsigned* dmax, const AdjointPlan& plan, int no_steps, int C, Vol vol,
                          int64_t G, int forced_len, hipStream_t st);
+// Sparse data stage: the z-extent of the fixed mask per voxel column -> the warp's hull and the piece lists of the
+// data term (list 0) and the LCC map (list 1).  Views into one allocation of data_plan_bytes().
+struct DataPlan {
+    int* ext = nullptr;            // [mask chains][H W][2]: (D - lo, hi) of the planes where mask != 0
+    int* runs = nullptr;           // [2][C tiles][2]: run ranges of the 32 x 16 tile columns at reach 2 s (data term) and s (map)
+    int* hull = nullptr;           // [C][64 x 8 tiles][2]: planes of a tile column within 3 s (SSD: 0) of the mask
+    ColPlan* colplan = nullptr;    // [2][C tiles]
+    PlanEntry* entries = nullptr;  // [2][cap]
+    int* count = nullptr;          // [2][2] entries of a list, and how many of them (the first) are run pieces
+    int* stats = nullptr;          // [2][C][kPlanStats]
+    double* nll = nullptr;         // [cap]: -log p summed over run piece i of the data term's list
+    int cap = 0, ntx = 0, nty = 0, wtx = 0, wty = 0;
+    int forced_len = 0;            // > 0: the piece length of both lists (irs_sparse_data_set); 0: the shortest that fits a resident set
+};
+size_t data_plan_bytes(Vol vol, int C);
+DataPlan data_plan_views(char* base, Vol vol, int C);
+// mask: (mask_chains, V), mask_chains 1 or C; s: LCC half width (0: SSD); lists: false builds the hull alone.  The lists are cut for
+// the resident sets of the list-walking LCC kernels, or to plan.forced_len
+void launch_data_plan(const uint8_t* mask, int mask_chains, const DataPlan& plan, int s, bool lists, int C, Vol vol, hipStream_t st);
+// most run pieces the data term's (bwd) / the map's list can have: the marching grid of its kernel
+int data_plan_run_bound(const DataPlan& plan, int s, bool bwd, int C, Vol vol);
 
 // ---- data_kernels.hip
 void launch_sobolev_march(const float* in, float* out, const Taps& taps, int planes, Vol vol, unsigned* dmax0, int no_steps,
@@ -96,6 +118,11 @@ void launch_perturb_sobolev_march(const float* v, const float* sigma, const floa
                                   const uint64_t* dev_iteration, hipStream_t st);  // stencil_kernels.hip
 void launch_lcc_fwd_march(const float* fhat, int64_t fhat_stride, const float* im, float* z, float* sigma_out, int s, int C,
                     Vol vol, hipStream_t st);  // z-marching version (stencil_kernels.hip)
+// the same tile body walking the run pieces of the map's list (DataPlan, list 1): z, sigma_out outside the pieces stay as they were
+void launch_lcc_fwd_plan(const float* fhat, int64_t fhat_stride, const float* im, float* z, float* sigma_out, int s, int C, Vol vol,
+                         const DataPlan& plan, hipStream_t st);
+int64_t lcc_plan_resident(int s, bool bwd, bool batch);  // workgroups of a list-walking LCC kernel the chip holds at once (0: unknown)
+int lcc_dense_seg_len(Vol vol, int C, bool bwd);         // z-segment length of the full-column LCC launches
 struct GmmDev;  // device-side mixture parameters (scalar_kernels.hip)
 // data term + its gradient w.r.t. the warped image (LCC adjoint fused); mode: IRS_DATA_*.  C_launch > 1 (GMM / LCC only): that many
 // chains from `chain` on in one launch -- z, sigma_m, g_warped and the partial sums at their chain offsets, fhat / mask every
@@ -115,6 +142,11 @@ void launch_lcc_data_bwd_march(const float* fhat, const float* z, const float* s
                                const float* g_z_override, const void* dev_state, int chain, float* g_warped,
                                double* nll_partials, int s, Vol vol, hipStream_t st, int batch = 0, int64_t f_stride = 0,
                                int64_t m_stride = 0, int seg_C = 1);  // batch > 0: chains chain .. chain + batch - 1 in one launch, each against its snapshot
+// the same tile body walking the data term's list (DataPlan, list 0): run pieces marched, the rest of g_warped zero-filled, -log p
+// per run piece into plan.nll.  C == 1: the mixture in force; C > 1: every chain against its snapshot, as `batch` above
+void launch_lcc_data_bwd_plan(const float* fhat, int64_t f_stride, const float* z, const float* sigma_m, const uint8_t* mask,
+                              int64_t m_stride, const void* dev_state, float* g_warped, int s, int C, Vol vol, const DataPlan& plan,
+                              hipStream_t st);
 int data_bwd_blocks(int mode, Vol vol, int seg_C = 1);
 void launch_masked_moments(const float* z, const uint8_t* mask, double* partials, Vol vol, hipStream_t st);
 void launch_reg_energy(const float* v, double* partials, int C, Vol vol, hipStream_t st);

@@ -9,6 +9,7 @@
 namespace irs {
 
 constexpr int kStatVals = 5 + 2 * IRS_MAX_COMPONENTS;  // n, sum x^2, 3 lag-1 products, K dNLL/dlog_std, K resp. sums
+struct PlanEntry;  // adjoint_plan.h
 
 struct DevState {
     irs_state st;  // parameters + Adam moments (host-visible layout)
@@ -164,7 +165,8 @@ void launch_reg_scalar(DevState* s, const double* energy_partials, int nblocks, 
 // transition.  `reg_partials` (optional): the regulariser scalar stage runs first, in the same launch (energy from the update).
 void launch_finalize(DevState* s, const double* nll_partials, int nblocks_per_chain, DevCfg cfg, bool advance,
                      unsigned* bounds, unsigned* hint, int nbounds, Verdict vd, int flag_word, bool zero_bounds,
-                     hipStream_t st, const double* reg_partials = nullptr, int reg_blocks = 0);
+                     hipStream_t st, const double* reg_partials = nullptr, int reg_blocks = 0, const PlanEntry* pieces = nullptr,
+                     const int* piece_count = nullptr);  // pieces: nll_partials is one sum per run piece of the data term's list
 void launch_gmm_init_from_moments(DevState* s, const double* moment_partials, int nblocks, DevCfg cfg, hipStream_t st);
 
 }  // namespace irs

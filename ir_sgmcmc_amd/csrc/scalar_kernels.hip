@@ -5,6 +5,8 @@
 // model/loss.py:172-312; model/distributions.py.
 #include "scalar_kernels.h"
 
+#include "adjoint_plan.h"
+
 namespace irs {
 
 #ifndef IRS_REDUCE_U
@@ -351,7 +353,8 @@ __global__ __launch_bounds__(kBlock) void finalize_kernel(DevState* s, const dou
                                                           int nblocks_per_chain, DevCfg cfg, int advance,
                                                           unsigned* __restrict__ bounds, unsigned* __restrict__ hint,
                                                           int nbounds, Verdict vd, int flag_word, int zero_bounds,
-                                                          const double* __restrict__ reg_partials, int reg_blocks) {
+                                                          const double* __restrict__ reg_partials, int reg_blocks,
+                                                          const PlanEntry* __restrict__ pieces, const int* __restrict__ piece_count) {
     __shared__ double smem[kBlock / kWave];
     const bool bad = verdict_bad(vd) || comm_bad(s);
     if (reg_partials) {
@@ -368,7 +371,19 @@ __global__ __launch_bounds__(kBlock) void finalize_kernel(DevState* s, const dou
     }
     for (int c = 0; c < cfg.C; ++c) {
         double acc[1];
-        sum_rows(partials + (int64_t)c * nblocks_per_chain, nblocks_per_chain, acc, smem);
+        if (pieces && cfg.C == 1) {
+            // sparse data stage: `partials` holds one sum per run piece of the data term's list (the first piece_count[1] entries)
+            sum_rows(partials, piece_count[1], acc, smem);
+        } else if (pieces) {
+            // ... the chains interleaved: a thread's pieces in ascending order, then the fixed-order block sum
+            acc[0] = 0.0;
+            const int n_run = piece_count[1];
+            for (int i = threadIdx.x; i < n_run; i += kBlock)
+                if (pieces[i].chain == c) acc[0] += partials[i];
+            block_sum<1>(acc, smem);
+        } else {
+            sum_rows(partials + (int64_t)c * nblocks_per_chain, nblocks_per_chain, acc, smem);
+        }
         if (threadIdx.x == 0) s->sc.data_term[c] = s->sc.alpha[c] * acc[0];
         __syncthreads();
     }
@@ -381,9 +396,10 @@ __global__ __launch_bounds__(kBlock) void finalize_kernel(DevState* s, const dou
 
 void launch_finalize(DevState* s, const double* nll_partials, int nblocks_per_chain, DevCfg cfg, bool advance,
                      unsigned* bounds, unsigned* hint, int nbounds, Verdict vd, int flag_word, bool zero_bounds,
-                     hipStream_t st, const double* reg_partials, int reg_blocks) {
+                     hipStream_t st, const double* reg_partials, int reg_blocks, const PlanEntry* pieces, const int* piece_count) {
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(kBlock), 0, st, s, nll_partials, nblocks_per_chain, cfg,
-                       advance ? 1 : 0, bounds, hint, nbounds, vd, flag_word, zero_bounds ? 1 : 0, reg_partials, reg_blocks);
+                       advance ? 1 : 0, bounds, hint, nbounds, vd, flag_word, zero_bounds ? 1 : 0, reg_partials, reg_blocks, pieces,
+                       piece_count);
 }
 
 // GMM.init_parameters (model/loss.py:61-65) from the unbiased std of the masked residuals (trainer.py:537-541)

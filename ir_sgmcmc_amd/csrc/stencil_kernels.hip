@@ -11,6 +11,7 @@
 // SQ_INSTS_VALU); these need 50-250.
 #include <stdlib.h>
 
+#include "adjoint_plan.h"
 #include "common.h"
 #include "kernels.h"
 #include "scalar_kernels.h"
@@ -467,20 +468,19 @@ void launch_perturb_sobolev_march(const float* v, const float* sigma, const floa
 #endif
 constexpr int LMX = IRS_LMX, LMY = IRS_LMY;
 
+static_assert(LMX == kLccTX && LMY == kLccTY, "the lists of the sparse data stage are cut for this tile (adjoint_plan.h)");
+
+// the planes [z0, z1) of the tile column at (ox, oy) of `chain`
 template <int S, bool MAP>
-__global__ __launch_bounds__(kStBlock) void lcc_fwd_march_kernel(const float* __restrict__ fhat, int64_t fhat_stride,
-                                                                 const float* __restrict__ im, float* __restrict__ out,
-                                                                 float* __restrict__ sigma_out, Vol vol, int seg_len, int nseg) {
+__device__ __forceinline__ void lcc_fwd_march_tile(const float* __restrict__ fhat, int64_t fhat_stride, const float* __restrict__ im,
+                                                   float* __restrict__ out, float* __restrict__ sigma_out, const Vol vol,
+                                                   const int chain, const int ox, const int oy, const int z0, const int z1) {
     constexpr int NT = 2 * S + 1, NS = S + 2;
     constexpr int AX = LMX + 4 * S, AY = LMY + 4 * S, AN = AX * AY, NITA = (AN + kStBlock - 1) / kStBlock;
     constexpr int BX = LMX + 2 * S, BY = LMY + 2 * S, BN = BX * BY, NITB = (BN + kStBlock - 1) / kStBlock;
     __shared__ float LA[AN];
     __shared__ float LW[NS * BN];
 
-    const Blk3 blk = swizzled_block();
-    const int chain = blk.z / nseg, seg = blk.z % nseg;
-    const int ox = blk.x * LMX, oy = blk.y * LMY;
-    const int z0 = vol.z0 + seg * seg_len, z1 = min(z0 + seg_len, vol.z0 + vol.nz);
     const int64_t HW = (int64_t)vol.H * vol.W;
     const float* __restrict__ src = im + (int64_t)chain * vol.V;
     const float n = (float)(NT * NT * NT);
@@ -634,6 +634,41 @@ __global__ __launch_bounds__(kStBlock) void lcc_fwd_march_kernel(const float* __
     }
 }
 
+template <int S, bool MAP>
+__global__ __launch_bounds__(kStBlock) void lcc_fwd_march_kernel(const float* __restrict__ fhat, int64_t fhat_stride,
+                                                                 const float* __restrict__ im, float* __restrict__ out,
+                                                                 float* __restrict__ sigma_out, Vol vol, int seg_len, int nseg) {
+    const Blk3 blk = swizzled_block();
+    const int chain = blk.z / nseg, seg = blk.z % nseg;
+    const int z0 = vol.z0 + seg * seg_len, z1 = min(z0 + seg_len, vol.z0 + vol.nz);
+    lcc_fwd_march_tile<S, MAP>(fhat, fhat_stride, im, out, sigma_out, vol, chain, blk.x * LMX, blk.y * LMY, z0, z1);
+}
+
+// a list entry the whole workgroup works on: its fields into scalar registers (the entry's address is uniform, but that is not known
+// to the compiler once the list position comes out of the remap -- the tile body would keep its plane loop and LDS slots in VGPRs)
+__device__ __forceinline__ PlanEntry uniform_entry(const PlanEntry& e) {
+    return PlanEntry{__builtin_amdgcn_readfirstlane(e.chain), __builtin_amdgcn_readfirstlane(e.tile), __builtin_amdgcn_readfirstlane(e.z0),
+                     __builtin_amdgcn_readfirstlane(e.z1), __builtin_amdgcn_readfirstlane(e.fill), 0};
+}
+
+// Sparse data stage: the same tile body on the run pieces of the map's list (adjoint_plan.hip).  One workgroup per run piece: the
+// grid is the most pieces the list can have (adjoint_plan.h: plan_run_bound -- one resident set unless a piece length is forced), the
+// list's length is read from device memory and the workgroups behind it leave at once.  (With an entry LOOP around the tile body the
+// data term's kernel went from 92 to 118 VGPRs and lost its fifth workgroup per CU: everything the loop needs stays live across the
+// body.)  Nothing is filled -- what lies outside the pieces is further than s from the mask, where z and sigma_M are only ever
+// multiplied by an exact zero.
+template <int S, bool MAP>
+__global__ __launch_bounds__(kStBlock) void lcc_fwd_march_plan_kernel(const float* __restrict__ fhat, int64_t fhat_stride,
+                                                                      const float* __restrict__ im, float* __restrict__ out,
+                                                                      float* __restrict__ sigma_out, Vol vol,
+                                                                      const PlanEntry* __restrict__ entries, const int* __restrict__ count,
+                                                                      int ntx) {
+    const int n_run = count[1], id = (int)blockIdx.x;
+    if (id >= n_run) return;
+    const PlanEntry e = uniform_entry(entries[plan_swizzle(id, n_run, ntx)]);
+    lcc_fwd_march_tile<S, MAP>(fhat, fhat_stride, im, out, sigma_out, vol, e.chain, (e.tile % ntx) * LMX, (e.tile / ntx) * LMY, e.z0, e.z1);
+}
+
 // the LCC kernels re-read 4S planes per segment; measured at 128^3: 8-plane segments (1.5x staging, 4x the workgroups)
 // still beat 16 and 32
 template <int S, bool G, bool BATCH>
@@ -673,6 +708,20 @@ void launch_lcc_fwd_march(const float* fhat, int64_t fhat_stride, const float* i
                             sigma_out, vol, seg_len, nseg);
     if (s == 1) { IRS_LCC_FWD(1) } else { IRS_LCC_FWD(2) }
 #undef IRS_LCC_FWD
+}
+
+int lcc_dense_seg_len(Vol vol, int C, bool bwd) { return lcc_seg_len(vol, C, bwd); }
+
+void launch_lcc_fwd_plan(const float* fhat, int64_t fhat_stride, const float* im, float* z, float* sigma_out, int s, int C, Vol vol,
+                         const DataPlan& plan, hipStream_t st) {
+    const dim3 grid((unsigned)data_plan_run_bound(plan, s, false, C, vol));
+    const PlanEntry* list = plan.entries + plan.cap;  // list 1
+    if (s == 1)
+        hipLaunchKernelGGL((lcc_fwd_march_plan_kernel<1, true>), grid, dim3(kStBlock), 0, st, fhat, fhat_stride, im, z, sigma_out, vol, list,
+                           plan.count + 2, plan.ntx);
+    else
+        hipLaunchKernelGGL((lcc_fwd_march_plan_kernel<2, true>), grid, dim3(kStBlock), 0, st, fhat, fhat_stride, im, z, sigma_out, vol, list,
+                           plan.count + 2, plan.ntx);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -721,16 +770,14 @@ __device__ __forceinline__ float adjoint_ring_sum(const float (&ring)[2 * S + 1]
 // is one of two (DevState::A or a chain's snapshot) the compiler fetched them with vector loads inside the plane loop -- 132 global
 // loads instead of 24 in the kernel, 187 instead of 141 us at 256^3 with ONE chain; each instantiation reads its constants through
 // `state` directly and keeps the scalar loads
+// The planes [z0, z1) of the tile column at (ox, oy) of `chain`; the array arguments are that chain's.  -log p summed over the
+// column's planes goes to *nll_slot.
 template <int S, bool EXPLICIT_GZ, bool BATCH>
-__global__ __launch_bounds__(kStBlock) void lcc_data_bwd_march_kernel(const float* __restrict__ fhat,
-                                                                      const float* __restrict__ z,
-                                                                      const float* __restrict__ sigma_m,
-                                                                      const uint8_t* __restrict__ mask,
-                                                                      const float* __restrict__ gz_in,
-                                                                      const DevState* __restrict__ state, int chain,
-                                                                      float* __restrict__ g_m, double* __restrict__ nll_out,
-                                                                      Vol vol, int seg_len, int nseg, int batch,
-                                                                      int64_t f_stride, int64_t m_stride) {
+__device__ __forceinline__ void lcc_data_bwd_march_tile(const float* __restrict__ fhat, const float* __restrict__ z,
+                                                        const float* __restrict__ sigma_m, const uint8_t* __restrict__ mask,
+                                                        const float* __restrict__ gz_in, const DevState* __restrict__ state,
+                                                        const int chain, float* __restrict__ g_m, double* __restrict__ nll_slot,
+                                                        const Vol vol, const int ox, const int oy, const int z0, const int z1) {
     constexpr int NT = 2 * S + 1, NS1 = S + 1, NS2 = S + 2;
     constexpr int AX = LMX + 4 * S, AY = LMY + 4 * S, AN = AX * AY, NITA = (AN + kStBlock - 1) / kStBlock;
     constexpr int BX = LMX + 2 * S, BY = LMY + 2 * S, BN = BX * BY, NITB = (BN + kStBlock - 1) / kStBlock;
@@ -739,25 +786,8 @@ __global__ __launch_bounds__(kStBlock) void lcc_data_bwd_march_kernel(const floa
     __shared__ float LG[NS2 * BN];
     __shared__ double red[kStBlock / kWave];
 
-    const Blk3 blk = swizzled_block();
-    int seg = blk.z;
-    // `batch` chains in one launch (grid.z = nseg x batch, chain-major): chain `chain + cl` against the snapshot its GMM step left
-    // (scalar_kernels.h: DevState::snapA), planes and partial sums at its chain offset -- the same values, sums and slots as `batch`
-    // launches of one chain each, every one right behind its chain's step
-    if (BATCH) {
-        const int cl = __builtin_amdgcn_readfirstlane(blk.z / nseg);  // (uniform, but the quotient comes out of the vector ALU)
-        seg = blk.z - cl * nseg;
-        chain += cl;
-        fhat += cl * f_stride;
-        mask += cl * m_stride;
-        z += cl * vol.V;
-        sigma_m += cl * vol.V;
-        g_m += cl * vol.V;
-    }
     const float* __restrict__ mixA = BATCH ? state->snapA[chain] : state->A;
     const float* __restrict__ mix_iv = BATCH ? state->snap_inv_var[chain] : state->inv_var;
-    const int ox = blk.x * LMX, oy = blk.y * LMY;
-    const int z0 = vol.z0 + seg * seg_len, z1 = min(z0 + seg_len, vol.z0 + vol.nz);
     const int64_t HW = (int64_t)vol.H * vol.W;
     const float n = (float)(NT * NT * NT);
     const float alpha = EXPLICIT_GZ ? 1.0f : (float)state->sc.alpha[chain];
@@ -929,9 +959,81 @@ __global__ __launch_bounds__(kStBlock) void lcc_data_bwd_march_kernel(const floa
         if (threadIdx.x == 0) {
             double t = 0.0;
             for (int w = 0; w < kStBlock / kWave; ++w) t += red[w];
-            nll_out[(blk.z * gridDim.y + blk.y) * gridDim.x + blk.x] = t;  // slot of the logical tile: same partial layout as unswizzled
+            *nll_slot = t;
         }
     }
+}
+
+template <int S, bool EXPLICIT_GZ, bool BATCH>
+__global__ __launch_bounds__(kStBlock) void lcc_data_bwd_march_kernel(const float* __restrict__ fhat,
+                                                                      const float* __restrict__ z,
+                                                                      const float* __restrict__ sigma_m,
+                                                                      const uint8_t* __restrict__ mask,
+                                                                      const float* __restrict__ gz_in,
+                                                                      const DevState* __restrict__ state, int chain,
+                                                                      float* __restrict__ g_m, double* __restrict__ nll_out,
+                                                                      Vol vol, int seg_len, int nseg, int batch,
+                                                                      int64_t f_stride, int64_t m_stride) {
+    const Blk3 blk = swizzled_block();
+    int seg = blk.z;
+    // `batch` chains in one launch (grid.z = nseg x batch, chain-major): chain `chain + cl` against the snapshot its GMM step left
+    // (scalar_kernels.h: DevState::snapA), planes and partial sums at its chain offset -- the same values, sums and slots as `batch`
+    // launches of one chain each, every one right behind its chain's step
+    if (BATCH) {
+        const int cl = __builtin_amdgcn_readfirstlane(blk.z / nseg);  // (uniform, but the quotient comes out of the vector ALU)
+        seg = blk.z - cl * nseg;
+        chain += cl;
+        fhat += cl * f_stride;
+        mask += cl * m_stride;
+        z += cl * vol.V;
+        sigma_m += cl * vol.V;
+        g_m += cl * vol.V;
+    }
+    const int z0 = vol.z0 + seg * seg_len, z1 = min(z0 + seg_len, vol.z0 + vol.nz);
+    // slot of the logical tile: same partial layout as unswizzled
+    lcc_data_bwd_march_tile<S, EXPLICIT_GZ, BATCH>(fhat, z, sigma_m, mask, gz_in, state, chain, g_m,
+                                                   nll_out + (blk.z * gridDim.y + blk.y) * gridDim.x + blk.x, vol, blk.x * LMX, blk.y * LMY,
+                                                   z0, z1);
+}
+
+// Sparse data stage: the same tile body on the run pieces of the data term's list (adjoint_plan.hip), -log p of piece i into nll[i]
+// (finalize_kernel sums them per chain, in list order).  g_warped is read whole by the adjoint and keeps an earlier transition's
+// values where the mask has moved, so the rest of every column is zero-filled -- by workgroups of their own in FRONT of the marching
+// ones (one code path each: exp_kernels.hip, exp_bwd_march_plan_kernel, has the measurement).
+constexpr int kLccFillBlocks = 256;  // (a multiple of 8: the XCD of a marching workgroup stays id % 8)
+template <int S, bool BATCH>
+__global__ __launch_bounds__(kStBlock) void lcc_data_bwd_march_plan_kernel(const float* __restrict__ fhat, const float* __restrict__ z,
+                                                                           const float* __restrict__ sigma_m,
+                                                                           const uint8_t* __restrict__ mask,
+                                                                           const DevState* __restrict__ state, float* __restrict__ g_m,
+                                                                           double* __restrict__ nll, Vol vol,
+                                                                           const PlanEntry* __restrict__ entries,
+                                                                           const int* __restrict__ count, int ntx, int64_t f_stride,
+                                                                           int64_t m_stride) {
+    const int n = count[0], n_run = count[1];
+    if (blockIdx.x < kLccFillBlocks) {
+        const int lx = threadIdx.x % LMX, ly = threadIdx.x / LMX;
+        const int64_t HW = (int64_t)vol.H * vol.W;
+        for (int id = n_run + (int)blockIdx.x; id < n; id += kLccFillBlocks) {
+            const PlanEntry e = uniform_entry(entries[id]);
+            const int x = (e.tile % ntx) * LMX + lx, za = max(e.z0, 0), zb = min(e.z1, vol.D);
+            float* __restrict__ o = g_m + (int64_t)e.chain * vol.V;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int y = (e.tile / ntx) * LMY + ly + h * (LMY / 2);
+                if (x < vol.W && y < vol.H)
+                    for (int zz = za; zz < zb; ++zz) o[(int64_t)zz * HW + (unsigned)(y * vol.W + x)] = 0.0f;
+            }
+        }
+        return;
+    }
+    const int id = (int)blockIdx.x - kLccFillBlocks;  // one run piece per marching workgroup (see lcc_fwd_march_plan_kernel)
+    if (id >= n_run) return;
+    const int pos = plan_swizzle(id, n_run, ntx);
+    const PlanEntry e = uniform_entry(entries[pos]);
+    const int cl = BATCH ? e.chain : 0;
+    lcc_data_bwd_march_tile<S, false, BATCH>(fhat + cl * f_stride, z + cl * vol.V, sigma_m + cl * vol.V, mask + cl * m_stride, nullptr, state,
+                                             cl, g_m + cl * vol.V, nll + pos, vol, (e.tile % ntx) * LMX, (e.tile / ntx) * LMY, e.z0, e.z1);
 }
 
 int lcc_data_bwd_march_blocks(Vol vol, int seg_C) {
@@ -966,6 +1068,34 @@ void launch_lcc_data_bwd_march(const float* fhat, const float* z, const float* s
                             g_z_override, state, chain, g_warped, nll_partials, vol, seg_len, nseg, batch, f_stride, m_stride);
     if (s == 1) { IRS_LCC_BWD(1) } else { IRS_LCC_BWD(2) }
 #undef IRS_LCC_BWD
+}
+
+int64_t lcc_plan_resident(int s, bool bwd, bool batch) {
+    static int cache[2][2][2] = {};
+    const void* fn;
+    if (!bwd) fn = s == 1 ? (const void*)lcc_fwd_march_plan_kernel<1, true> : (const void*)lcc_fwd_march_plan_kernel<2, true>;
+    else if (batch) fn = s == 1 ? (const void*)lcc_data_bwd_march_plan_kernel<1, true> : (const void*)lcc_data_bwd_march_plan_kernel<2, true>;
+    else fn = s == 1 ? (const void*)lcc_data_bwd_march_plan_kernel<1, false> : (const void*)lcc_data_bwd_march_plan_kernel<2, false>;
+    return resident_blocks(fn, kStBlock, &cache[s == 1 ? 0 : 1][bwd ? 1 : 0][batch ? 1 : 0]);
+}
+
+void launch_lcc_data_bwd_plan(const float* fhat, int64_t f_stride, const float* z, const float* sigma_m, const uint8_t* mask,
+                              int64_t m_stride, const void* dev_state, float* g_warped, int s, int C, Vol vol, const DataPlan& plan,
+                              hipStream_t st) {
+    const bool batch = C > 1;
+    const dim3 grid((unsigned)(data_plan_run_bound(plan, s, true, C, vol) + kLccFillBlocks));
+    const DevState* state = (const DevState*)dev_state;
+#define IRS_LCC_BWD_PLAN(SS, BB)                                                                                                       \
+    hipLaunchKernelGGL((lcc_data_bwd_march_plan_kernel<SS, BB>), grid, dim3(kStBlock), 0, st, fhat, z, sigma_m, mask, state, g_warped, \
+                       plan.nll, vol, plan.entries, plan.count, plan.ntx, f_stride, m_stride)
+    if (s == 1) {
+        if (batch) IRS_LCC_BWD_PLAN(1, true);
+        else IRS_LCC_BWD_PLAN(1, false);
+    } else {
+        if (batch) IRS_LCC_BWD_PLAN(2, true);
+        else IRS_LCC_BWD_PLAN(2, false);
+    }
+#undef IRS_LCC_BWD_PLAN
 }
 
 // ------------------------------------------------------------------------------------------------

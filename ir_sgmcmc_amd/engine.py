@@ -176,6 +176,22 @@ class TransitionEngine:
         keys = ('engaged', 'piece_len', 'pieces', 'run_planes')
         return [[dict(zip(keys, buf[(k * ch + c) * 4:(k * ch + c) * 4 + 4])) for c in range(ch)] for k in range(n)]
 
+    def set_sparse_data(self, on):
+        """irs_sparse_data_set: False -> warp, LCC map, statistics and data term run over the whole volume (the same numbers); an
+        int n >= 2 -> on whatever the volume's size, with pieces of at most n planes (tests)"""
+        L.check(self.lib.irs_sparse_data_set(self._ctx, int(on)))
+
+    @_on_device
+    def sparse_data(self):
+        """irs_sparse_data_get: per kernel of the data stage and chain c of the last transition, [kernel][c] = dict(engaged,
+        piece_len, pieces, run_planes); kernel in ('warp', 'map', 'stats', 'data_term')"""
+        ch = self.cfg.no_chains
+        buf = (C.c_int32 * (4 * ch * 4))()
+        L.check(self.lib.irs_sparse_data_get(self._ctx, buf, self._stream()))
+        keys = ('engaged', 'piece_len', 'pieces', 'run_planes')
+        return {name: [dict(zip(keys, buf[(k * ch + c) * 4:(k * ch + c) * 4 + 4])) for c in range(ch)]
+                for k, name in enumerate(('warp', 'map', 'stats', 'data_term'))}
+
     # ---------------------------------------------------------------- small state
     @property
     def workspace_bytes(self):
