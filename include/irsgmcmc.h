@@ -669,6 +669,48 @@ int irs_bspline_warp(const float* coeff, int Cim, const float* transformation, f
 int irs_native_warp_cubic(const float* displacement, int C, const int32_t* dims, const int32_t* native, const int32_t* padding,
                           const float* im, const float* coeff, int Cim, float fill, float* im_out, void* stream);
 
+/* Foreground masks from the image (absent in the reference, which reads every mask from a file): histogram, connected components,
+ * selection of the largest components, hole filling and ball morphology.  Every call takes C >= 1 volumes (C,1,D,H,W), every
+ * extent >= 1, fewer than 2^30 voxels each and C D <= 65535, and treats the volumes independently; a mask is uint8, set where
+ * non-zero, and every mask written holds 0 / 1.  Nothing is a neighbour across the end of a row, a plane or a volume.  Every
+ * result is a function of the input alone (integer counts, canonical labels): atomics are used and two calls are still
+ * bit-identical.  No call synchronises with the host.
+ *  - irs_intensity_histogram: im (C,1,D,H,W) float32; mask (Cm,1,D,H,W) with Cm 1 (shared) or C, or NULL; lo < hi finite; bins in
+ *    IRS_MASK_MIN_BINS .. IRS_MASK_MAX_BINS; hist (C,bins) int64, overwritten.  A voxel counts when the mask is set (or absent) and
+ *    its value is finite; its bin is that of irs_image_similarity: in float32, inv_w = bins / (hi - lo), t = (x - lo) * inv_w,
+ *    b = min(bins - 1, max(0, floor(t))), so a value outside [lo, hi] lands in the first or the last bin.  One launch.
+ *  - irs_mask_threshold: out = im > threshold (a NaN is background).
+ *  - irs_connected_components: connectivity 6, 18 or 26 (neighbours that differ in at most 1, 2 or 3 coordinates, by one each);
+ *    labels (C,1,D,H,W) int32: 0 background, the components of each volume numbered 1 .. n in ascending order of their smallest
+ *    linear voxel index; counts (C) int32: n.  ws: irs_connected_components_workspace bytes (two int32 fields and one int32 per
+ *    1024 voxels), 16-byte aligned.  Six launches: union-find in LDS tiles, unions across tile faces, flatten, scan of the root
+ *    counts, root numbers, relabel; every loop has a trip bound that follows from the voxel count and no workgroup waits for another.
+ *  - irs_mask_keep_largest: out = the voxels of the `keep` (1 .. IRS_MASK_MAX_KEEP) largest components of each volume, ties going
+ *    to the smaller number; fewer components: all of them; an empty mask stays empty.  irs_mask_fill_holes: out = mask, plus the
+ *    background voxels with no 6-connected background path to the border of the volume (scipy's binary_fill_holes with its default
+ *    structure).  ws of both: irs_mask_select_workspace bytes, 16-byte aligned; out may be mask.
+ *  - irs_mask_dilate: out = the voxels whose squared distance, in voxels, to the nearest set voxel is <= r2, 0 <= r2 <=
+ *    IRS_MASK_MAX_RADIUS^2: the dilation by the Euclidean ball, compared in integers.  erode != 0: the same for the complement,
+ *    complemented -- the erosion; voxels outside the volume are not background, so a mask on the border is not eaten from there.
+ *    ws: irs_mask_morphology_workspace bytes (3 bytes per voxel), 16-byte aligned; out may be mask.  Three launches. */
+#define IRS_MASK_MIN_BINS 2
+#define IRS_MASK_MAX_BINS 4096
+#define IRS_MASK_MAX_KEEP 64
+#define IRS_MASK_MAX_RADIUS 16
+int irs_intensity_histogram(const float* im, int C, const uint8_t* mask, int Cm, int D, int H, int W, float lo, float hi, int bins,
+                            long long* hist, void* stream);
+int irs_mask_threshold(const float* im, int C, int D, int H, int W, float threshold, uint8_t* out, void* stream);
+int irs_connected_components_workspace(int C, int D, int H, int W, size_t* bytes);
+int irs_connected_components(const uint8_t* mask, int C, int D, int H, int W, int connectivity, int32_t* labels, int32_t* counts,
+                             void* ws, size_t ws_bytes, void* stream);
+int irs_mask_select_workspace(int C, int D, int H, int W, size_t* bytes);
+int irs_mask_keep_largest(const uint8_t* mask, int C, int D, int H, int W, int connectivity, int keep, uint8_t* out, void* ws,
+                          size_t ws_bytes, void* stream);
+int irs_mask_fill_holes(const uint8_t* mask, int C, int D, int H, int W, uint8_t* out, void* ws, size_t ws_bytes, void* stream);
+int irs_mask_morphology_workspace(int C, int D, int H, int W, size_t* bytes);
+int irs_mask_dilate(const uint8_t* mask, int C, int D, int H, int W, int r2, int erode, uint8_t* out, void* ws, size_t ws_bytes,
+                    void* stream);
+
 /* Landmark propagation (absent in the reference, which has no point-set operator): a sampled displacement evaluated at K
  * positions that are no voxel centres, and the posterior of the mapped landmarks with their target registration error (TRE).
  * warped(x) = moving(x + d(x)): a point p of the fixed grid maps to p + d(p) in the moving image; points of the moving space

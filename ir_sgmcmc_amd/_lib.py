@@ -47,6 +47,7 @@ IRS_SURFACE_MAX_LEVELS, IRS_SURFACE_SUMMARY_INTS, IRS_SURFACE_SUMMARY_FLOATS, IR
 IRS_SURFACE_WS_BYTES = IRS_MAX_LABELS * IRS_SURFACE_MAX_BLOCKS * (IRS_SURFACE_SUMMARY_INTS + IRS_SURFACE_SUMMARY_FLOATS) * 8
 IRS_AFFINE_SUMS, IRS_AFFINE_PARTIALS, IRS_AFFINE_MAX_BLOCKS = 94, 76, 512
 IRS_AFFINE_WS_BYTES = IRS_AFFINE_MAX_BLOCKS * IRS_AFFINE_PARTIALS * 8
+IRS_MASK_MIN_BINS, IRS_MASK_MAX_BINS, IRS_MASK_MAX_KEEP, IRS_MASK_MAX_RADIUS = 2, 4096, 64, 16
 IRS_DATA_GMM_LCC, IRS_DATA_SSD = 0, 1
 IRS_REG_L2, IRS_REG_LOGNORMAL, IRS_REG_STUDENT, IRS_REG_LOGNORMAL_L2 = 0, 1, 2, 3
 
@@ -214,6 +215,15 @@ SIGNATURES = {
     'irs_bspline_prefilter': [_P, _P, _I, _I, _I, _I, _P],
     'irs_bspline_warp': [_P, _I, _P, _P, _I, _I, _I, _I, _P],
     'irs_native_warp_cubic': [_P, _I, _I32P, _I32P, _I32P, _P, _P, _I, _F, _P, _P],
+    'irs_intensity_histogram': [_P, _I, _P, _I, _I, _I, _I, _F, _F, _I, _P, _P],
+    'irs_mask_threshold': [_P, _I, _I, _I, _I, _F, _P, _P],
+    'irs_connected_components_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
+    'irs_connected_components': [_P, _I, _I, _I, _I, _I, _P, _P, _P, C.c_size_t, _P],
+    'irs_mask_select_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
+    'irs_mask_keep_largest': [_P, _I, _I, _I, _I, _I, _I, _P, _P, C.c_size_t, _P],
+    'irs_mask_fill_holes': [_P, _I, _I, _I, _I, _P, _P, C.c_size_t, _P],
+    'irs_mask_morphology_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
+    'irs_mask_dilate': [_P, _I, _I, _I, _I, _I, _I, _P, _P, C.c_size_t, _P],
     'irs_create': [C.POINTER(IrsConfig), C.POINTER(_P)],
     'irs_destroy': [_P],
     'irs_workspace_bytes': [_P],

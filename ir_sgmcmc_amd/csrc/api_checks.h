@@ -78,6 +78,15 @@ inline bool bspline_volume_ok(const char* who, int volumes, int D, int H, int W)
            !fail("%s: dims (%d, %d, %d) x %d volumes exceed the launch grid", who, D, H, W, volumes);
 }
 
+// the volumes of a mask call (mask_kernels.hip): C >= 1 of them, every extent >= 1, fewer than 2^30 voxels each (labels and union-
+// find parents are int32 voxel indices) and one launch row per volume and plane
+inline bool mask_volumes_ok(const char* who, int C, int D, int H, int W) {
+    if (C < 1) return !fail("%s: C = %d volumes, at least 1 needed", who, C);
+    if (D < 1 || H < 1 || W < 1) return !fail("%s: dims (%d, %d, %d), every one >= 1 needed", who, D, H, W);
+    if ((int64_t)D * H * W >= ((int64_t)1 << 30)) return !fail("%s: the volume must have fewer than 2^30 voxels", who);
+    return (int64_t)C * D <= 65535 || !fail("%s: %d volumes of %d planes are more than the 65535 rows of one launch", who, C, D);
+}
+
 inline SplineTaps make_spline(int cps) {
     // sampled cubic B-spline (utils/transformation.py:79-102); evaluated in double, stored as float like the reference
     SplineTaps t;

@@ -1249,6 +1249,113 @@ int irs_prolong_field(const float* x, int C, int ch, int d, int h, int w, float*
 }
 
 // ================================================================================================
+// foreground masks (mask_kernels.hip)
+// ================================================================================================
+int irs_intensity_histogram(const float* im, int C, const uint8_t* mask, int Cm, int D, int H, int W, float lo, float hi, int bins,
+                            long long* hist, void* stream) {
+    if (!im || !hist) return fail("irs_intensity_histogram: null pointer");
+    if (!mask_volumes_ok(__func__, C, D, H, W)) return 1;
+    if (mask && !broadcast_ok(Cm, C)) return fail("irs_intensity_histogram: mask of %d volumes, 1 or %d needed", Cm, C);
+    if (bins < IRS_MASK_MIN_BINS || bins > IRS_MASK_MAX_BINS)
+        return fail("irs_intensity_histogram: bins = %d, %d..%d", bins, IRS_MASK_MIN_BINS, IRS_MASK_MAX_BINS);
+    if (!isfinite(lo) || !isfinite(hi) || !(hi > lo))
+        return fail("irs_intensity_histogram: range [%g, %g], finite bounds with hi > lo needed", (double)lo, (double)hi);
+    const float width = hi - lo;  // fp32, as the definition states it
+    const float inv_w = (float)bins / width;
+    if (!positive_finite(inv_w))
+        return fail("irs_intensity_histogram: range [%g, %g] is too wide or too narrow for float32 bins", (double)lo, (double)hi);
+    const int64_t V = (int64_t)D * H * W;
+    launch_intensity_histogram(im, mask, mask && Cm == C && C > 1 ? V : 0, V, C, lo, inv_w, bins, hist, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_mask_threshold(const float* im, int C, int D, int H, int W, float threshold, uint8_t* out, void* stream) {
+    if (!im || !out) return fail("irs_mask_threshold: null pointer");
+    if (!mask_volumes_ok(__func__, C, D, H, W)) return 1;
+    if (isnan(threshold)) return fail("irs_mask_threshold: the threshold is NaN");
+    launch_mask_threshold(im, threshold, out, C, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+static bool connectivity_ok(const char* who, int connectivity) {
+    return connectivity == 6 || connectivity == 18 || connectivity == 26 || !fail("%s: connectivity = %d, 6, 18 or 26", who, connectivity);
+}
+
+// the workspace of a mask call: given, 16-byte aligned and of `need` bytes (`hint`: the query that tells them)
+static bool mask_workspace_ok(const char* who, const void* ws, size_t have, size_t need, const char* hint) {
+    if (!ws) return !fail("%s: null workspace", who);
+    if ((uintptr_t)ws & 15) return !fail("%s: the workspace must be 16-byte aligned", who);
+    return workspace_ok(who, have, need, hint);
+}
+
+int irs_connected_components_workspace(int C, int D, int H, int W, size_t* bytes) {
+    if (!bytes) return fail("irs_connected_components_workspace: bad arguments");
+    if (!mask_volumes_ok(__func__, C, D, H, W)) return 1;
+    *bytes = connected_components_bytes(C, (int64_t)D * H * W);
+    return 0;
+}
+
+int irs_connected_components(const uint8_t* mask, int C, int D, int H, int W, int connectivity, int32_t* labels, int32_t* counts,
+                             void* ws, size_t ws_bytes, void* stream) {
+    if (!mask || !labels || !counts) return fail("irs_connected_components: null pointer");
+    if (!mask_volumes_ok(__func__, C, D, H, W) || !connectivity_ok(__func__, connectivity)) return 1;
+    if (!mask_workspace_ok(__func__, ws, ws_bytes, connected_components_bytes(C, (int64_t)D * H * W), "irs_connected_components_workspace"))
+        return 1;
+    launch_connected_components(mask, false, connectivity, labels, counts, C, make_vol(D, H, W), ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_mask_select_workspace(int C, int D, int H, int W, size_t* bytes) {
+    if (!bytes) return fail("irs_mask_select_workspace: bad arguments");
+    if (!mask_volumes_ok(__func__, C, D, H, W)) return 1;
+    *bytes = mask_select_bytes(C, (int64_t)D * H * W);
+    return 0;
+}
+
+int irs_mask_keep_largest(const uint8_t* mask, int C, int D, int H, int W, int connectivity, int keep, uint8_t* out, void* ws,
+                          size_t ws_bytes, void* stream) {
+    if (!mask || !out) return fail("irs_mask_keep_largest: null pointer");
+    if (!mask_volumes_ok(__func__, C, D, H, W) || !connectivity_ok(__func__, connectivity)) return 1;
+    if (keep < 1 || keep > IRS_MASK_MAX_KEEP) return fail("irs_mask_keep_largest: keep = %d, 1..%d", keep, IRS_MASK_MAX_KEEP);
+    if (!mask_workspace_ok(__func__, ws, ws_bytes, mask_select_bytes(C, (int64_t)D * H * W), "irs_mask_select_workspace")) return 1;
+    launch_mask_keep_largest(mask, connectivity, keep, out, C, make_vol(D, H, W), ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_mask_fill_holes(const uint8_t* mask, int C, int D, int H, int W, uint8_t* out, void* ws, size_t ws_bytes, void* stream) {
+    if (!mask || !out) return fail("irs_mask_fill_holes: null pointer");
+    if (!mask_volumes_ok(__func__, C, D, H, W)) return 1;
+    if (!mask_workspace_ok(__func__, ws, ws_bytes, mask_select_bytes(C, (int64_t)D * H * W), "irs_mask_select_workspace")) return 1;
+    launch_mask_fill_holes(mask, out, C, make_vol(D, H, W), ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_mask_morphology_workspace(int C, int D, int H, int W, size_t* bytes) {
+    if (!bytes) return fail("irs_mask_morphology_workspace: bad arguments");
+    if (!mask_volumes_ok(__func__, C, D, H, W)) return 1;
+    *bytes = mask_morphology_bytes(C, (int64_t)D * H * W);
+    return 0;
+}
+
+int irs_mask_dilate(const uint8_t* mask, int C, int D, int H, int W, int r2, int erode, uint8_t* out, void* ws, size_t ws_bytes,
+                    void* stream) {
+    if (!mask || !out) return fail("irs_mask_dilate: null pointer");
+    if (!mask_volumes_ok(__func__, C, D, H, W)) return 1;
+    if (r2 < 0 || r2 > IRS_MASK_MAX_RADIUS * IRS_MASK_MAX_RADIUS)
+        return fail("irs_mask_dilate: r2 = %d, 0..%d (a radius of at most %d voxels)", r2, IRS_MASK_MAX_RADIUS * IRS_MASK_MAX_RADIUS,
+                    IRS_MASK_MAX_RADIUS);
+    if (!mask_workspace_ok(__func__, ws, ws_bytes, mask_morphology_bytes(C, (int64_t)D * H * W), "irs_mask_morphology_workspace")) return 1;
+    launch_mask_dilate(mask, r2, erode != 0, out, C, make_vol(D, H, W), ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // affine pre-alignment (affine_kernels.hip)
 // ================================================================================================
 // the volume and the map of an affine call -> `map`; `rows`: launch rows (chains x planes) of the pointwise kernels, 0: none

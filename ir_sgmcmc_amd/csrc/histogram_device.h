@@ -1,8 +1,16 @@
-// The LDS histogram add the histogram kernels share (similarity_kernels.hip, residual_kernels.hip).
+// The bin rule and the LDS histogram add the histogram kernels share (similarity_kernels.hip, residual_kernels.hip,
+// mask_kernels.hip).
 #pragma once
 #include "common.h"
 
 namespace irs {
+
+// The bin rule, in fp32 with every operation rounded once: t = (x - lo) * inv_w -- a difference, then a product: nothing to
+// contract -- and b = min(last, max(0, floor(t))) with last = bins - 1 as a float.  Clamped as floats: floor(t) of a finite
+// value far outside the range need not fit an int.
+__device__ __forceinline__ int hist_bin(float x, float lo, float inv_w, float last) {
+    return (int)fminf(fmaxf(floorf(__fmul_rn(__fsub_rn(x, lo), inv_w)), 0.0f), last);
+}
 
 // h[cell] += 1 for every lane with take set.  Wave-uniform control flow: every lane of the wavefront calls it.  One LDS
 // address hit by all 64 lanes serialises (a constant region: background, saturation): with `aggregate`, when every voxel the

@@ -454,6 +454,25 @@ void launch_bspline_warp(const float* coeff, int64_t coeff_stride, const float* 
 void launch_native_warp_cubic(const float* u, const float* im, const float* coeff, int64_t moving_stride, float* im_out,
                               const NativeGeom& gm, int C, hipStream_t st);
 
+// ---- mask_kernels.hip: foreground masks from the image (absent in the reference) -- histogram, components, selection, hole
+// filling and ball morphology over C volumes of `vol`, each on its own; include/irsgmcmc.h has the definitions.  C * D <= 65535
+// im (C,V); mask (1 or C, V) with mask_stride 0 or V, or nullptr; hist (C,bins) int64, zeroed on the stream here; inv_w = bins /
+// (hi - lo), formed in fp32
+void launch_intensity_histogram(const float* im, const uint8_t* mask, int64_t mask_stride, int64_t V, int C, float lo, float inv_w,
+                                int bins, long long* hist, hipStream_t st);
+void launch_mask_threshold(const float* im, float threshold, uint8_t* out, int C, const Vol& vol, hipStream_t st);
+// labels (C,V) int32 and counts (C) int32 of the mask (invert: of its complement); conn 6 / 18 / 26; ws: connected_components_bytes
+size_t connected_components_bytes(int C, int64_t V);
+void launch_connected_components(const uint8_t* mask, bool invert, int conn, int32_t* labels, int32_t* counts, int C, const Vol& vol,
+                                 void* ws, hipStream_t st);
+// out may be mask; ws: mask_select_bytes
+size_t mask_select_bytes(int C, int64_t V);
+void launch_mask_keep_largest(const uint8_t* mask, int conn, int keep, uint8_t* out, int C, const Vol& vol, void* ws, hipStream_t st);
+void launch_mask_fill_holes(const uint8_t* mask, uint8_t* out, int C, const Vol& vol, void* ws, hipStream_t st);
+// the dilation by the ball of squared radius r2 (erode: of the complement, complemented); out may be mask; ws: mask_morphology_bytes
+size_t mask_morphology_bytes(int C, int64_t V);
+void launch_mask_dilate(const uint8_t* mask, int r2, bool erode, uint8_t* out, int C, const Vol& vol, void* ws, hipStream_t st);
+
 // ---- scalar_kernels.hip
 struct DevState;  // full definition in scalar_kernels.h
 }  // namespace irs

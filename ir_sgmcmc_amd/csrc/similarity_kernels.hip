@@ -70,9 +70,7 @@ __device__ __forceinline__ SimVoxel sim_voxel(float f, float m, bool masked, con
     const bool take = masked && finite;
     a.i[1] += masked && !finite;
     const float last = (float)(bn.bins - 1);
-    // clamped as floats: floor(t) of a finite intensity far outside the range need not fit an int
-    const int bf = (int)fminf(fmaxf(floorf(__fmul_rn(__fsub_rn(f, bn.f_lo), bn.f_inv)), 0.0f), last);
-    const int bm = (int)fminf(fmaxf(floorf(__fmul_rn(__fsub_rn(m, bn.m_lo), bn.m_inv)), 0.0f), last);
+    const int bf = hist_bin(f, bn.f_lo, bn.f_inv, last), bm = hist_bin(m, bn.m_lo, bn.m_inv, last);
     if (take) {
         const double df = (double)f, dm = (double)m, d = df - dm;
         a.i[0] += 1;

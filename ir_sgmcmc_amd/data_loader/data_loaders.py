@@ -17,6 +17,7 @@ class SyntheticDataLoader:
         self.im_spacing = None
 
     native = None  # no volumes at another resolution than `dims` (BiobankDataLoader.native)
+    has_masks, has_segs = True, True  # the synthetic pair has both (BiobankDataLoader: `optional`)
 
     @property
     def dims_v(self):
@@ -38,17 +39,19 @@ class BiobankDataLoader(SyntheticDataLoader):
     (numpy NIfTI reader instead of SimpleITK).  An unusable `data_dir` is an ERROR, as in the reference (its `listdir`
     raises): a typo must not turn into a registration of fake data written out under the requested names.  The synthetic
     pair of the same `dims` is only used when the config asks for it: `"allow_synthetic_fallback": true` (the reference
-    ships no image data, its configs point at the author's cluster), or the `SyntheticDataLoader` type."""
+    ships no image data, its configs point at the author's cluster), or the `SyntheticDataLoader` type.  `optional`: the
+    directories out of "masks" and "segs" that may be missing (BiobankDataset); has_masks / has_segs tell what was found."""
 
     def __init__(self, data_dir=None, dims=None, sigma_v_init=0.5, u_v_init=0.1, cps=None, save_dirs=None,
-                 allow_synthetic_fallback=False, **kw):
+                 allow_synthetic_fallback=False, optional=(), **kw):
         super().__init__(dims, sigma_v_init, u_v_init, cps, save_dirs, **kw)
         self.data_dir, self.dataset = data_dir, None
         from .datasets import BiobankDataset
         try:
             if not data_dir:  # a config without data_dir (None / ''): the same explanatory error or fallback as a missing directory
                 raise FileNotFoundError('no data_dir given')
-            self.dataset = BiobankDataset(dims, data_dir, save_dirs, sigma_v_init, u_v_init, cps=cps)
+            self.dataset = BiobankDataset(dims, data_dir, save_dirs, sigma_v_init, u_v_init, cps=cps, optional=tuple(optional))
+            self.has_masks, self.has_segs = self.dataset.has_masks, self.dataset.has_segs
         except (FileNotFoundError, NotADirectoryError) as e:
             if not allow_synthetic_fallback:
                 raise FileNotFoundError(f'BiobankDataLoader: no usable image pair under data_dir={data_dir!r} ({e}); set '

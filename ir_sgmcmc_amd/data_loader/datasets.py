@@ -5,6 +5,7 @@ name; image 0 is the fixed image, image idx + 1 the moving one (all-to-one, `__l
 its minimum to a cube of the largest extent, then resized to `dims`: trilinear / align_corners for images, nearest for
 masks and segmentations -- the same torch calls the reference makes (:70-105)."""
 import json
+import logging
 import os
 from os import listdir, path
 
@@ -18,7 +19,14 @@ from ..utils.imageio import read_nifti
 
 
 class BiobankDataset:
-    def __init__(self, dims, im_paths, save_paths=None, sigma_v_init=0.5, u_v_init=0.1, cps=None):
+    OPTIONAL = ('masks', 'segs')  # the directories `optional` may list
+
+    def __init__(self, dims, im_paths, save_paths=None, sigma_v_init=0.5, u_v_init=0.1, cps=None, optional=()):
+        """optional: the directories out of OPTIONAL that may be missing or empty (absent in the reference, which needs both).
+        Without masks every mask is all-true; without segs the pair has no 'seg' key.  One warning each.  `native_pair` keeps
+        requiring its files."""
+        if isinstance(optional, str) or any(name not in self.OPTIONAL for name in optional):
+            raise ValueError(f'optional must be a list out of {list(self.OPTIONAL)}, got {optional!r}')
         self.im_paths, self.save_paths = im_paths, save_paths
         self.sigma_v_init, self.u_v_init = sigma_v_init, u_v_init
         self.dims = tuple(dims)
@@ -30,8 +38,19 @@ class BiobankDataset:
         im_filenames = self._get_filenames(im_paths)
         mask_filenames = self._get_filenames(path.join(im_paths, 'masks'))
         seg_filenames = self._get_filenames(path.join(im_paths, 'segs'))
-        self.im_mask_seg_triples = [{'im': t[0], 'mask': t[1], 'seg': t[2]}
-                                    for t in zip(im_filenames, mask_filenames, seg_filenames)]
+        # an optional directory that is missing or empty is left out of the triples (a directory with files in it is read and
+        # checked as ever)
+        self.has_masks = not ('masks' in optional and not any(mask_filenames))
+        self.has_segs = not ('segs' in optional and not any(seg_filenames))
+        for present, name, instead in ((self.has_masks, 'masks', 'every mask is all-true'), (self.has_segs, 'segs', "the pair has no 'seg'")):
+            if not present:
+                logging.getLogger('default').warning(f'BiobankDataset: no files under {path.join(im_paths, name)}: {instead}')
+        columns = {'im': im_filenames}
+        if self.has_masks:
+            columns['mask'] = mask_filenames
+        if self.has_segs:
+            columns['seg'] = seg_filenames
+        self.im_mask_seg_triples = [dict(zip(columns, t)) for t in zip(*columns.values())]
         if len(self.im_mask_seg_triples) < 2 or any(not path.isfile(f) for t in self.im_mask_seg_triples[:2] for f in t.values()):
             raise FileNotFoundError(f'{im_paths}: need at least two image / mask / seg triples (fixed + moving)')
         if save_paths and save_paths.get('dir'):
@@ -70,7 +89,11 @@ class BiobankDataset:
         return F.interpolate(self._padded(seg_path), size=self.dims, mode='nearest').short().squeeze(0)
 
     def _load(self, triple):
-        return {'im': self._get_image(triple['im']), 'mask': self._get_mask(triple['mask']), 'seg': self._get_seg(triple['seg'])}
+        out = {'im': self._get_image(triple['im'])}
+        out['mask'] = self._get_mask(triple['mask']) if 'mask' in triple else torch.ones(out['im'].shape, dtype=torch.bool)
+        if 'seg' in triple:
+            out['seg'] = self._get_seg(triple['seg'])
+        return out
 
     def native_pair(self, idx=0):
         """The pair at its own resolution (absent in the reference, which keeps the resized volumes only): the files are read
@@ -79,6 +102,8 @@ class BiobankDataset:
         shape), 'fill' the minimum each image is padded with, and the grid carries the header zooms of the fixed image.  The data
         set applies ONE padding to every volume, so volumes of different shapes are refused."""
         triples = {'fixed': self.im_mask_seg_triples[0], 'moving': self.im_mask_seg_triples[idx + 1]}
+        if not (self.has_masks and self.has_segs):
+            raise FileNotFoundError(f'{self.im_paths}: the native-resolution pair needs the mask and the segmentation files')
         out, shape, zooms, fill = {}, None, None, {}
         for side, triple in triples.items():
             out[side] = {}

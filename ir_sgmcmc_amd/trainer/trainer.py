@@ -38,6 +38,7 @@ from ..logger import (save_displacement_covariance, save_displacement_mean_and_s
                       save_posterior_comparison,
                       save_residual_histogram, save_residual_nll, save_rhat, save_sample, save_surface_posterior)
 from .. import affine, bspline, multires, residual_check
+from .. import masks as mask_ops  # (`masks` names the pair of masks in several methods below)
 from ..multires import coarse_start_options
 from ..utils import (calc_DSC_GPU, calc_image_similarity, calc_norm, calc_no_non_diffeomorphic_voxels, calc_residual_check,
                      init_identity_grid_3D, local_similarity_rows, sample_q_v, transform_coordinates)
@@ -91,6 +92,17 @@ class Trainer(VIMixin, BaseTrainer):
         # trainer.affine_init is absent.  Read first: it refuses trainer.native_resolution and trainer.landmarks beside it
         self.affine_options = affine.affine_init_options(cfg_trainer, config['data_loader']['args']['dims'])
         self.affine_summary = None
+        # automatic foreground masks (masks.py, _auto_mask): None when trainer.auto_mask is absent, and then nothing changes.
+        # Computed from the pair on the registration grid before the pre-alignment; a resumed run computes them again
+        self.auto_mask_options = mask_ops.auto_mask_options(cfg_trainer)
+        self.auto_mask_summary = None
+        if self.auto_mask_options is not None and self.auto_mask_options['source'] == 'file' and not getattr(data_loader, 'has_masks', True):
+            raise ValueError('trainer.auto_mask: "source": "file" needs mask files, and the data loader found no "masks" directory')
+        if (self.auto_mask_options is not None and self.auto_mask_options['source'] == 'image' and cfg_trainer.get('native_resolution')
+                and not getattr(data_loader, 'has_masks', True)):
+            raise ValueError('trainer.auto_mask with "source": "image" and no mask files cannot be combined with '
+                             'trainer.native_resolution, which reads its masks on the native grid from files (masks on the native '
+                             'grid are not computed)')
         # split-R-hat of the displacement (diagnostics.py): None when trainer.convergence_diagnostics is off
         self.diagnostics_period = diagnostics_period(cfg_trainer)
         self._chain_moments = None
@@ -166,6 +178,55 @@ class Trainer(VIMixin, BaseTrainer):
         # them again: nothing goes into a checkpoint)
         self.interpolation_options = bspline.output_interpolation_options(cfg_trainer)
         self._spline_coeff = None
+        # a diagnostic that needs segmentations refuses here, not in the middle of a run, when the data loader has none
+        if not getattr(data_loader, 'has_segs', True):
+            for name, opt in (('label_posterior', self.label_options), ('surface_posterior', self.surface_options)):
+                if opt is not None:
+                    raise ValueError(f'trainer.{name} needs the fixed and the moving segmentation, and the data loader '
+                                     f'({type(data_loader).__name__}) found no "segs" directory')
+
+    # ---------------------------------------------------------------- automatic foreground masks
+    def _auto_mask(self, fixed, moving):
+        """trainer.auto_mask: the masks of the chosen sides replaced in place -- "source": "image": mask_ops.foreground_mask of the
+        image; "file": the file mask with holes filled, closed and dilated.  self.auto_mask_summary, the auto_mask/{side}/*
+        metrics, one log line per side and, with save_outputs and the option's save, samples/auto_mask_{side}.nii.gz.
+        Deterministic: a resumed run computes the same masks again."""
+        opt = self.auto_mask_options
+        have_files = getattr(self.data_loader, 'has_masks', True)
+        sp = getattr(self.data_loader, 'im_spacing', None)
+        spacing = torch.ones(3) if sp is None else sp
+        self.auto_mask_summary = {}
+        self.writer.set_step(0)
+        for side, triple in (('fixed', fixed), ('moving', moving)):
+            if side not in mask_ops.auto_mask_sides(opt):
+                continue
+            file_mask = triple['mask'].bool() if have_files else None
+            start = time.perf_counter()
+            mask, summary = mask_ops.auto_mask(triple['im'], file_mask, opt)
+            summary['seconds'] = time.perf_counter() - start
+            voxels = int(mask.sum())
+            summary.update(source=opt['source'], voxels_final=voxels, fraction=voxels / summary['total'])
+            for key in ('threshold', 'components'):
+                if key in summary:
+                    self.metrics.update(f'auto_mask/{side}/{key}', float(summary[key]))
+            self.metrics.update(f'auto_mask/{side}/voxels', float(voxels))
+            self.metrics.update(f'auto_mask/{side}/fraction', summary['fraction'])
+            if file_mask is not None:
+                both = int((mask & file_mask).sum())
+                summary['dice_vs_file'] = 2.0 * both / max(voxels + int(file_mask.sum()), 1)
+                self.metrics.update(f'auto_mask/{side}/dice_vs_file', summary['dice_vs_file'])
+            self.auto_mask_summary[side] = summary
+            self.logger.info(f'auto mask ({side}, from the {opt["source"]}): {voxels} voxels, {100 * summary["fraction"]:.2f} % of the '
+                             f'volume' + (f', threshold {summary["threshold"]:.6g}, {summary["components"]} components'
+                                          if 'threshold' in summary else '') +
+                             (f', Dice against the file mask {summary["dice_vs_file"]:.4f}' if 'dice_vs_file' in summary else '') +
+                             f', box {summary["bounding_box"]}, {summary["seconds"]:.3f} seconds')
+            triple['mask'] = mask
+            if self.config['trainer'].get('save_outputs', True) and opt['save']:
+                from ..logger import save_im_to_disk
+                folder = self.config.save_dirs['samples']
+                folder.mkdir(parents=True, exist_ok=True)
+                save_im_to_disk(mask[0, 0].to(torch.uint8), str(folder / f'auto_mask_{side}.nii.gz'), spacing)
 
     # ---------------------------------------------------------------- affine pre-alignment
     def _affine_init(self, fixed, moving):
@@ -1233,6 +1294,8 @@ class Trainer(VIMixin, BaseTrainer):
         for fixed, moving, var_params_q_v in self.data_loader:
             fixed = {k: v.to(self.device) for k, v in fixed.items()}
             moving = {k: v.to(self.device) for k, v in moving.items()}
+            if self.auto_mask_options is not None:
+                self._auto_mask(fixed, moving)
             if self.affine_options is not None:
                 moving = self._affine_init(fixed, moving)
             self._engine_init(fixed, moving)
