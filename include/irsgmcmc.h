@@ -276,6 +276,38 @@ int irs_jacobian_posterior_finalize(const int32_t* folds, const float* mean, con
                                     const uint8_t* mask, float* fold_prob, float* logJ_mean, float* logJ_std, long long* isummary,
                                     double* fsummary, void* ws, size_t ws_bytes, void* stream);
 
+/* Image posterior (absent in the reference): S volumes that live on the moving image's grid, carried through every recorded
+ * transformation; per voxel of the fixed grid and volume, over n records (one chain's transformation at one recorded step), the
+ * Welford mean / M2, the minimum and the maximum of the trilinear sample, whatever n is: 16 S bytes per voxel.
+ *  - irs_image_posterior_update: volumes (S,1,D,H,W) float32 shared by the chains, S in 1 .. IRS_IMAGE_POSTERIOR_MAX_VOLUMES;
+ *    transformation (C,3,D,H,W) float32 in [-1,1] coordinates, C in 1 .. IRS_MAX_CHAINS, every dim >= 2: what
+ *    irs_warp_transformation takes, and the sample x is bit for bit the value that call writes (same expressions, border clamp;
+ *    a tap read with weight 0 still carries a NaN, 0 * NaN, as it does there).  mean, m2, low, high (S,D,H,W) float32, updated
+ *    in place with the C records in chain order: k = records_before + c + 1, d = x - mean, mean += d / (float)k,
+ *    m2 += d * (x - mean), low = fminf(low, x), high = fmaxf(high, x).  records_before >= 0 records were folded in before,
+ *    records_before + C <= INT32_MAX; records_before = 0 overwrites the state (mean = low = high = x, m2 = 0), which is then
+ *    never read.  A non-finite sample leaves the voxel's mean non-finite for good.  One launch: a thread owns one voxel of a
+ *    group of volumes, forms the taps and weights of a chain once for all of them and keeps their state in registers; no atomics.
+ *  - irs_image_posterior_finalize: ONE volume's four state planes (D,H,W) after n >= 1 records.  std_out = sqrtf(m2 /
+ *    max(n - 1, 1)), range_out = high - low; with reference (D,H,W) float32, z_out = (reference - mean) / sqrtf(std^2 +
+ *    std_floor^2), std_floor finite and >= 0: the misfit of the posterior-mean image in units of the spread the registration
+ *    uncertainty explains.  reference and z_out are both NULL or both given.  A voxel with a non-finite mean gets NaN in every
+ *    map.  mask (D,H,W) uint8 or NULL (whole volume).  isummary: IRS_IMAGE_POSTERIOR_SUMMARY_INTS int64 over the mask {voxels,
+ *    voxels with a non-finite mean, voxels with |z| > 2, voxels with |z| > 3}.  fsummary: IRS_IMAGE_POSTERIOR_SUMMARY_FLOATS
+ *    doubles over the stored float32 maps of the other masked voxels {sum mean, sum std, max std, max range, sum z^2, max |z|};
+ *    a NaN z (0 / 0) enters no z column; a maximum nothing entered is -inf; without a reference the z counts are 0 and the two
+ *    z columns NaN.  ws: IRS_IMAGE_POSTERIOR_WS_BYTES of device memory.  Deterministic (exact integer sums, fixed-order double
+ *    sums and maxima); no host sync. */
+#define IRS_IMAGE_POSTERIOR_MAX_VOLUMES 8
+#define IRS_IMAGE_POSTERIOR_SUMMARY_INTS 4
+#define IRS_IMAGE_POSTERIOR_SUMMARY_FLOATS 6
+#define IRS_IMAGE_POSTERIOR_WS_BYTES (1024 * (IRS_IMAGE_POSTERIOR_SUMMARY_INTS + IRS_IMAGE_POSTERIOR_SUMMARY_FLOATS) * 8)
+int irs_image_posterior_update(const float* volumes, int S, const float* transformation, int C, int D, int H, int W, float* mean,
+                               float* m2, float* low, float* high, int records_before, void* stream);
+int irs_image_posterior_finalize(const float* mean, const float* m2, const float* low, const float* high, int D, int H, int W, int n,
+                                 const float* reference, float std_floor, const uint8_t* mask, float* std_out, float* range_out,
+                                 float* z_out, long long* isummary, double* fsummary, void* ws, size_t ws_bytes, void* stream);
+
 /* Displacement covariance posterior (absent in the reference, whose displacement std is three per-component numbers): per
  * voxel, over n records (one chain's displacement at one recorded step, pooled over chains), the Welford mean and the six
  * co-moments of the displacement, and from them the principal spreads and the major direction of its 3 x 3 sample covariance.

@@ -787,6 +787,42 @@ int irs_jacobian_posterior_finalize(const int32_t* folds, const float* mean, con
 }
 
 // ================================================================================================
+// image posterior (image_posterior_kernels.hip)
+// ================================================================================================
+int irs_image_posterior_update(const float* volumes, int S, const float* transformation, int C, int D, int H, int W, float* mean,
+                               float* m2, float* low, float* high, int records_before, void* stream) {
+    if (!volumes || !transformation || !mean || !m2 || !low || !high || !dims_ok(C, D, H, W))
+        return fail("irs_image_posterior_update: bad arguments");
+    if (S < 1 || S > IRS_IMAGE_POSTERIOR_MAX_VOLUMES)
+        return fail("irs_image_posterior_update: S = %d volumes, 1..%d", S, IRS_IMAGE_POSTERIOR_MAX_VOLUMES);
+    if (!chains_ok(__func__, C)) return 1;
+    if (!records_ok(__func__, records_before, C, INT32_MAX, "overflow the int32 record count")) return 1;
+    // the launch is one block row per (volume group, plane) and per four rows of a plane
+    if ((int64_t)D * ((S + kImagePosteriorGroup - 1) / kImagePosteriorGroup) > 65535 || (H + 3) / 4 > 65535)
+        return fail("irs_image_posterior_update: dims (%d, %d, %d) x %d volumes exceed the launch grid", D, H, W, S);
+    launch_image_posterior_update(volumes, S, transformation, C, mean, m2, low, high, records_before, make_vol(D, H, W),
+                                  (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_image_posterior_finalize(const float* mean, const float* m2, const float* low, const float* high, int D, int H, int W, int n,
+                                 const float* reference, float std_floor, const uint8_t* mask, float* std_out, float* range_out,
+                                 float* z_out, long long* isummary, double* fsummary, void* ws, size_t ws_bytes, void* stream) {
+    if (!mean || !m2 || !low || !high || !std_out || !range_out || !isummary || !fsummary || !ws || !dims_ok(1, D, H, W))
+        return fail("irs_image_posterior_finalize: bad arguments");
+    if (n < 1) return fail("irs_image_posterior_finalize: n = %d records, at least 1 needed", n);
+    if (!reference != !z_out) return fail("irs_image_posterior_finalize: reference and z_out go together, one of them is NULL");
+    if (!(std_floor >= 0.0f) || !isfinite(std_floor))
+        return fail("irs_image_posterior_finalize: std_floor = %g, a finite value >= 0 needed", (double)std_floor);
+    if (!workspace_ok(__func__, ws_bytes, (size_t)IRS_IMAGE_POSTERIOR_WS_BYTES, "IRS_IMAGE_POSTERIOR_WS_BYTES")) return 1;
+    launch_image_posterior_finalize(mean, m2, low, high, (int64_t)D * H * W, n, reference, std_floor, mask, std_out, range_out, z_out,
+                                    isummary, fsummary, ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // displacement covariance posterior (covariance_kernels.hip)
 // ================================================================================================
 int irs_displacement_covariance_update(const float* displacement, int C, int D, int H, int W, float* mean, float* comoment,

@@ -294,6 +294,20 @@ void launch_covariance_finalize(const float* mean, const float* comoment, int64_
                                 float* stdev, float* direction, float* anisotropy, long long* isummary, double* fsummary, void* ws,
                                 hipStream_t st);
 
+// ---- image_posterior_kernels.hip: volumes carried through every recorded transformation (absent in the reference)
+// volumes (S,V), t (C,3,V) float32; mean, m2, low, high (S,V) float32: the C samples of every volume folded in chain order after
+// `records_before` records (0 overwrites the state); the sample is launch_warp_transformation's, bit for bit.  The grid is
+// (ceil(W / 64), ceil(H / 4), D * ceil(S / kImagePosteriorGroup)): a thread owns one voxel of a group of volumes
+constexpr int kImagePosteriorGroup = 2;
+void launch_image_posterior_update(const float* volumes, int S, const float* t, int C, float* mean, float* m2, float* low,
+                                   float* high, int records_before, Vol vol, hipStream_t st);
+// one volume's state (V) after n records, reference (V) or nullptr -> std_out, range_out, z_out (V; nullptr with the reference);
+// isummary IRS_IMAGE_POSTERIOR_SUMMARY_INTS int64, fsummary IRS_IMAGE_POSTERIOR_SUMMARY_FLOATS doubles; ws:
+// IRS_IMAGE_POSTERIOR_WS_BYTES (the partials of at most 1024 blocks)
+void launch_image_posterior_finalize(const float* mean, const float* m2, const float* low, const float* high, int64_t V, int n,
+                                     const float* reference, float std_floor, const uint8_t* mask, float* std_out, float* range_out,
+                                     float* z_out, long long* isummary, double* fsummary, void* ws, hipStream_t st);
+
 // ---- compare_kernels.hip: posterior comparison (absent in the reference); arithmetic in compare_device.h
 // mean_x (3,V), comoment_x (6,V) float32 after n_x >= 2 records; scale: 3 host floats; shift, log_std_ratio, bures, jeffreys (V)
 // float32; isummary IRS_COMPARE_SUMMARY_INTS int64, fsummary IRS_COMPARE_SUMMARY_FLOATS doubles; ws: IRS_COMPARE_WS_BYTES (the

@@ -72,14 +72,23 @@ The residual check (ResidualCheck, residual_check_options) is the one diagnostic
 histogram of the masked residuals is set against the mixture that models them (residual_check.py), and at a recorded step the
 exact int64 histograms and moment sums are accumulated per chain and -log p(z) under the mixture of that step is folded into a
 per-voxel streaming mean (residual_check.residual_nll_update), 8 * D * H * W bytes whatever the number of records.
+
+The image posterior (ImagePosterior, image_posterior_options) carries what a registration exists to move: at a recorded step the
+moving image and up to seven more volumes on its grid (a dose or PET map, a second contrast) are sampled under every chain's
+transformation and folded into a per-voxel Welford mean / M2, minimum and maximum in one fused launch
+(image_posterior.image_posterior_update), 16 * S * D * H * W bytes whatever the number of records; at the end
+image_posterior.image_posterior_finalize gives the std and range maps and, for the moving image, the misfit of its posterior mean
+against the fixed image in units of the spread the registration uncertainty explains.
 """
 import math
 import numbers
+import re
 
 import numpy as np
 
 import torch
 
+from . import image_posterior as _ip
 from . import ops
 from . import posterior_comparison as _pc
 from . import residual_check as _rc
@@ -529,6 +538,149 @@ class JacobianPosterior(_Recorder):
         self.folds.copy_(sd['folds'])
         self.mean.copy_(sd['mean'])
         self.m2.copy_(sd['m2'])
+        self.records = int(sd['records'])
+
+
+IMAGE_OPTION_KEYS = ('period', 'volumes', 'reference', 'std_floor', 'save')
+IMAGE_DEFAULTS = {'volumes': (), 'reference': True, 'std_floor': None, 'save': True}
+IMAGE_MAX_EXTRAS = _ip.MAX_VOLUMES - 1  # the moving image is always carried
+IMAGE_METRICS = ('std_mean', 'std_max', 'range_max')  # logged per volume
+IMAGE_Z_METRICS = ('z_rms', 'z_gt2', 'z_gt3')  # logged for the moving image against the fixed one
+IMAGE_STD_FLOOR_FRACTION = 1e-3  # "std_floor": null -> this fraction of the moving image's intensity range
+
+
+def image_posterior_options(cfg_trainer):
+    """`trainer.image_posterior` -> None when off, else {'period': P, 'volumes': ({'name', 'path'}, ...), 'reference': bool,
+    'std_floor': float | None, 'save': bool}.
+    Absent / false / null: off.  true: the moving image alone, recorded every log_period_MCMC-th step after the burn-in, its z
+    map against the fixed image, the floor of z taken from the moving image's intensity range, the maps written.  A dict sets
+    any of "period", "volumes" (at most 7 extra volumes {"name": ..., "path": ...} on the moving image's grid, the names unique,
+    of [A-Za-z0-9_]+ and not "moving"), "reference", "std_floor" (a number >= 0, or null) and "save".  Refuses unknown keys, a
+    non-integer P or P < 1, a config that records no step (no_samples_MCMC // P < 1) and one that would record more than
+    2^31 - 1 samples."""
+    what = 'trainer.image_posterior'
+
+    def own_keys(opt):
+        own = {**IMAGE_DEFAULTS, **{k: v for k, v in opt.items() if k != 'period'}}
+        volumes = own['volumes']
+        if not isinstance(volumes, (list, tuple)):
+            raise ValueError(f'{what}.volumes must be a list of {{"name": ..., "path": ...}}, got {volumes!r}')
+        if len(volumes) > IMAGE_MAX_EXTRAS:
+            raise ValueError(f'{what}.volumes: {len(volumes)} entries, at most {IMAGE_MAX_EXTRAS} beside the moving image')
+        names = []
+        for i, entry in enumerate(volumes):
+            if not isinstance(entry, dict) or set(entry) != {'name', 'path'}:
+                raise ValueError(f'{what}.volumes[{i}] must be {{"name": ..., "path": ...}}, got {entry!r}')
+            name, file_path = entry['name'], entry['path']
+            if not isinstance(name, str) or not re.fullmatch(r'[A-Za-z0-9_]+', name):
+                raise ValueError(f'{what}.volumes[{i}].name must match [A-Za-z0-9_]+, got {name!r}')
+            if name == 'moving':
+                raise ValueError(f'{what}.volumes[{i}].name: "moving" names the moving image itself')
+            if name in names:
+                raise ValueError(f'{what}.volumes[{i}].name: {name!r} is listed twice')
+            if not isinstance(file_path, str) or not file_path:
+                raise ValueError(f'{what}.volumes[{i}].path must be a file name, got {file_path!r}')
+            names.append(name)
+        for key in ('reference', 'save'):
+            if not isinstance(own[key], bool):
+                raise ValueError(f'{what}.{key} must be true or false, got {own[key]!r}')
+        floor = own['std_floor']
+        if floor is not None and (not _number(floor) or not math.isfinite(floor) or floor < 0):
+            raise ValueError(f'{what}.std_floor must be a finite number >= 0 or null, got {floor!r}')
+        return {'volumes': tuple({'name': e['name'], 'path': e['path']} for e in volumes), 'reference': own['reference'],
+                'std_floor': None if floor is None else float(floor), 'save': own['save']}
+
+    return _record_options(cfg_trainer, 'image_posterior', IMAGE_OPTION_KEYS,
+                           '{"period": P, "volumes": [...], "reference": bool, "std_floor": x, "save": bool}', MAX_RECORDS,
+                           'the sample count holds at most {}', own_keys)
+
+
+def image_posterior_names(options):
+    """the volumes the option carries, in state order: the moving image, then the extras"""
+    return ['moving'] + [v['name'] for v in options['volumes']]
+
+
+def image_posterior_metric_names(options):
+    """the metric names the option adds: MCMC/image/{name}/{std_mean,std_max,range_max} per volume and, with "reference",
+    MCMC/image/moving/{z_rms,z_gt2,z_gt3}"""
+    m = [f'MCMC/image/{name}/{k}' for name in image_posterior_names(options) for k in IMAGE_METRICS]
+    return m + ([f'MCMC/image/moving/{k}' for k in IMAGE_Z_METRICS] if options['reference'] else [])
+
+
+def image_summary(isummary, fsummary, n, with_z):
+    """the summary of one volume from the finalize's reduced columns (host ints / floats): isummary {voxels, non-finite voxels,
+    |z| > 2, |z| > 3}, fsummary {sum mean, sum / max std, max range, sum z^2, max |z|} over the finite ones, n records.  The
+    z entries (`with_z`) are fractions of the finite voxels and the root mean square; an empty mask gives NaN."""
+    voxels, nonfinite, gt2, gt3 = (int(x) for x in isummary)
+    mean_sum, std_sum, std_max, range_max, z2_sum, z_max = (float(x) for x in fsummary)
+    some = voxels - nonfinite
+    nan = float('nan')
+    out = {'records': int(n), 'voxels': voxels, 'nonfinite_voxels': nonfinite, 'mean': _nan_div(mean_sum, some),
+           'std_mean': _nan_div(std_sum, some), 'std_max': std_max if some else nan, 'range_max': range_max if some else nan}
+    if with_z:
+        out.update(z_rms=math.sqrt(z2_sum / some) if some else nan, z_max=z_max if some else nan, z_gt2=_nan_div(gt2, some),
+                   z_gt3=_nan_div(gt3, some))
+    return out
+
+
+class ImagePosterior(_Recorder):
+    """Per voxel of the fixed grid and volume, the Welford mean / M2, the minimum and the maximum of the volume's trilinear sample
+    under every recorded transformation, on the device (16 S D H W bytes whatever the number of records).  `volumes`
+    (S,1,D,H,W) float32 live on the moving image's grid and are shared by the chains; `names`: one per volume.
+    `record(transformation)` takes the (C,3,D,H,W) float32 transformations of one step, chains in order, in ONE launch for all
+    volumes; `finalize` gives every volume's maps and summary."""
+    noun = 'image posterior'
+
+    def __init__(self, volumes, names, device):
+        names = tuple(str(n) for n in names)
+        if volumes.dim() != 5 or volumes.shape[1] != 1 or volumes.shape[0] != len(names) or len(set(names)) != len(names):
+            raise ValueError(f'image posterior: (S,1,D,H,W) volumes and S distinct names, got {tuple(volumes.shape)} and {names}')
+        self.names, self.device = names, device
+        self.dims = tuple(int(d) for d in volumes.shape[2:])
+        self.volumes = volumes.to(device=device, dtype=torch.float32).contiguous()
+        self.state = _ip.image_posterior_state(len(names), self.dims, device)
+
+    def _update(self, transformation):
+        _ip.image_posterior_update(self.volumes, transformation, self.state, self.records)
+
+    def finalize(self, mask=None, reference=None, std_floor=0.0):
+        """-> {name: {'mean', 'std', 'range' (D,H,W) float32 on the device[, 'z'], 'summary': image_summary}}.  reference:
+        {name: volume on the fixed grid} or None: those volumes get a z map, (reference - mean) / sqrt(std^2 + std_floor^2).
+        One device-to-host read per volume (the summary)."""
+        self._need_records('finalize')
+        reference = dict(reference or {})
+        unknown = set(reference) - set(self.names)
+        if unknown:
+            raise ValueError(f'image posterior: reference for {sorted(unknown)}, the volumes are {list(self.names)}')
+        mask = _bool_mask(mask, self.device)
+        out = {}
+        for index, name in enumerate(self.names):
+            ref = reference.get(name)
+            ref = None if ref is None else ref.to(device=self.device, dtype=torch.float32)
+            std, rng, z, isum, fsum = _ip.image_posterior_finalize(self.state, index, self.records, ref, std_floor, mask)
+            nan = std.new_full((), math.nan)
+            mean = self.state['mean'][index]
+            out[name] = {'mean': mean.where(mean.isfinite(), nan), 'std': std, 'range': rng,
+                         'summary': image_summary(*_host_summary(isum, fsum), self.records, ref is not None)}
+            if z is not None:
+                out[name]['z'] = z
+        return out
+
+    def state_dict(self):
+        return {'records': self.records, 'names': list(self.names), 'dims': list(self.dims),
+                **{key: t.detach().cpu() for key, t in self.state.items()}}
+
+    def load_state_dict(self, sd):
+        if tuple(sd['names']) != self.names:
+            raise ValueError(f'image posterior of the volumes {list(sd["names"])} does not match this run ({list(self.names)})')
+        if tuple(sd['dims']) != self.dims:
+            raise ValueError(f'image posterior of dims {tuple(sd["dims"])} does not match this run ({self.dims})')
+        for key, t in self.state.items():
+            if tuple(sd[key].shape) != tuple(t.shape):
+                raise ValueError(f'image posterior state of shape {tuple(sd[key].shape)} ({key}) does not match this run '
+                                 f'({tuple(t.shape)})')
+        for key, t in self.state.items():
+            t.copy_(sd[key])
         self.records = int(sd['records'])
 
 

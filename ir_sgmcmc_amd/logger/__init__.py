@@ -154,6 +154,22 @@ def save_jacobian_posterior(logger, save_dirs, spacing, fold_prob, logJ_mean, lo
         save_im_to_disk(im.where(mask, im.new_zeros(())), path.join(folder, f'{model}_{name}_masked.nii.gz'), spacing)
 
 
+def save_image_posterior(logger, save_dirs, spacing, maps, mask, model='MCMC'):
+    """the image posterior (absent in the reference): per volume `name` of `maps` (diagnostics.ImagePosterior.finalize)
+    samples/{model}_im_{name}_{mean,std,range}[_masked].nii.gz and, where it holds a z map, {model}_im_{name}_z[_masked].nii.gz
+    (float32; NaN -- a non-finite sample there -- written as 0, the masked ones 0 outside the FIXED mask too)"""
+    folder = _folder(save_dirs, 'samples')
+    for name, volume in maps.items():
+        for key in ('mean', 'std', 'range', 'z'):
+            if key not in volume:
+                continue
+            im, undefined = _nan_to_zero(volume[key])
+            m = mask.reshape(im.shape).to(im.device) != 0
+            logger.info(f'{model}_im_{name}_{key}: {undefined} voxels without a finite value written as 0')
+            save_im_to_disk(im, path.join(folder, f'{model}_im_{name}_{key}.nii.gz'), spacing)
+            save_im_to_disk(im.where(m, im.new_zeros(())), path.join(folder, f'{model}_im_{name}_{key}_masked.nii.gz'), spacing)
+
+
 def save_displacement_covariance(logger, save_dirs, spacing, std, direction, anisotropy, mask, model='MCMC'):
     """principal spread of the displacement posterior (absent in the reference): samples/{model}_disp_std_major[_masked].nii.gz,
     {model}_disp_std_minor[_masked].nii.gz and {model}_disp_anisotropy[_masked].nii.gz (float32, the std in the units of the

@@ -13,7 +13,8 @@ import numpy as np
 from .data_loader import data_loaders as module_data
 from .diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ICE_SPACES, JACOBIAN_METRICS, LABEL_STRUCTURE_METRICS, QUANTILE_METRICS,
                           diagnostics_period, displacement_covariance_options, displacement_quantiles_options, ess_options,
-                          hausdorff_metric_names, hausdorff_options, image_similarity_metric_names, image_similarity_options,
+                          hausdorff_metric_names, hausdorff_options, image_posterior_metric_names, image_posterior_options,
+                          image_similarity_metric_names, image_similarity_options,
                           inverse_consistency_options, jacobian_posterior_options, label_posterior_options,
                           landmark_metric_names, landmark_options, local_similarity_metric_names, local_similarity_options,
                           posterior_comparison_options, residual_check_metric_names, residual_check_options,
@@ -118,6 +119,9 @@ class ConfigParser:
             m += surface_metric_names(surface, self.structures_dict)
         if jacobian_posterior_options(self['trainer']) is not None:
             m += [f'MCMC/jacobian/{k}' for k in JACOBIAN_METRICS]
+        image = image_posterior_options(self['trainer'])
+        if image is not None:
+            m += image_posterior_metric_names(image)
         if displacement_covariance_options(self['trainer']) is not None:
             m += [f'MCMC/covariance/{k}' for k in COVARIANCE_METRICS]
         if displacement_quantiles_options(self['trainer']) is not None:

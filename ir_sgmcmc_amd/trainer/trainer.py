@@ -13,6 +13,7 @@ the device state once (`_engine_init`) and read back lazily (`sync_parameters`) 
 """
 import dataclasses
 import math
+import os
 import time
 from collections import namedtuple
 
@@ -22,7 +23,8 @@ import torch
 from ..base import BaseTrainer
 from .. import ops
 from ..diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ChainMoments, DisplacementCovariance, DisplacementQuantiles, ICE_SPACES,
-                           InverseConsistency, JACOBIAN_METRICS, JacobianPosterior, LABEL_STRUCTURE_METRICS, LANDMARK_METRICS,
+                           IMAGE_METRICS, IMAGE_STD_FLOOR_FRACTION, IMAGE_Z_METRICS, ImagePosterior, image_posterior_names,
+                           image_posterior_options, InverseConsistency, JACOBIAN_METRICS, JacobianPosterior, LABEL_STRUCTURE_METRICS, LANDMARK_METRICS,
                            LOCAL_METRICS, LabelPosterior, LandmarkPair, LandmarkPosterior, LocalSimilarity, QUANTILE_METRICS,
                            SURFACE_METRICS, SurfacePosterior, surface_coverage_key, surface_posterior_options,
                            diagnostics_period, displacement_covariance_options, displacement_quantiles_options,
@@ -33,11 +35,11 @@ from ..diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ChainMoments,
                            SIMILARITY_METRICS, voxel_scale)
 from ..engine import EngineConfig, TransitionEngine
 from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_quantiles, save_ess,
-                      save_field, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_landmarks,
+                      save_field, save_image_posterior, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_landmarks,
                       save_local_similarity_of_mean, save_local_similarity_posterior, save_native_mean, save_native_sample,
                       save_posterior_comparison,
                       save_residual_histogram, save_residual_nll, save_rhat, save_sample, save_surface_posterior)
-from .. import affine, bspline, multires, residual_check
+from .. import affine, bspline, image_posterior, multires, residual_check
 from .. import masks as mask_ops  # (`masks` names the pair of masks in several methods below)
 from ..multires import coarse_start_options
 from ..utils import (calc_DSC_GPU, calc_image_similarity, calc_norm, calc_no_non_diffeomorphic_voxels, calc_residual_check,
@@ -144,6 +146,20 @@ class Trainer(VIMixin, BaseTrainer):
         # native volumes go to the device in _run_MCMC
         self.native_options = native_resolution_options(cfg_trainer, data_loader)
         self._native = None
+        # image posterior: the moving image and the extra volumes on its grid carried through every recorded transformation
+        # (image_posterior.py, diagnostics.ImagePosterior): None when trainer.image_posterior is off.  _image_volumes: the
+        # volumes on the registration grid, formed in _run_model once the pair is masked and pre-aligned (a resumed run forms
+        # them again: only the state goes into a checkpoint)
+        self.image_options = image_posterior_options(cfg_trainer)
+        self._image_posterior, self._image_volumes, self._image_std_floor = None, None, None
+        self.image_maps, self.image_summary = None, None
+        if self.image_options is not None and self.image_options['volumes']:
+            if self.native_options is not None:
+                raise ValueError('trainer.image_posterior.volumes cannot be combined with trainer.native_resolution: the extra '
+                                 'volumes are read on the registration grid only')
+            for v in self.image_options['volumes']:
+                if not os.path.isfile(v['path']):
+                    raise FileNotFoundError(f'trainer.image_posterior.volumes: {v["name"]!r}: no file {v["path"]!r}')
         # label-free similarity of the fixed and the warped moving image (ops.image_similarity): None when
         # trainer.image_similarity is off.  No state but the two intensity ranges, taken from the pair
         self.similarity_options = image_similarity_options(cfg_trainer)
@@ -391,7 +407,7 @@ class Trainer(VIMixin, BaseTrainer):
         return self._scalars_cache
 
     def _recorders(self):
-        """the active recorders, in the order they record and finish: moments, labels, surfaces, Jacobian, covariance,
+        """the active recorders, in the order they record and finish: moments, labels, surfaces, Jacobian, images, covariance,
         quantiles, inverse consistency, landmarks, local similarity, residual check, posterior comparison"""
         period = lambda options: options and options['period']
         rows = (('chain_moments', self._chain_moments, self.diagnostics_period, 'convergence_diagnostics', 'chain moments',
@@ -402,6 +418,8 @@ class Trainer(VIMixin, BaseTrainer):
                  'surface posterior', 'seg_warped', self._finish_surface_posterior, 'fixed'),
                 ('jacobian_posterior', self._jacobian_posterior, period(self.jacobian_options), 'jacobian_posterior',
                  'Jacobian posterior', 'transformation', self._finish_jacobian_posterior, 'fixed'),
+                ('image_posterior', self._image_posterior, period(self.image_options), 'image_posterior', 'image posterior',
+                 'transformation', self._finish_image_posterior, 'fixed'),
                 ('displacement_covariance', self._displacement_covariance, period(self.covariance_options),
                  'displacement_covariance', 'displacement covariance', 'displacement', self._finish_displacement_covariance,
                  'moving_mask'),
@@ -624,6 +642,10 @@ class Trainer(VIMixin, BaseTrainer):
             self._surface_posterior = SurfacePosterior(fixed['seg'][:1], self.structures_dict, spacing, self.device)
         if self.jacobian_options is not None:
             self._jacobian_posterior = JacobianPosterior(self._outputs['transformation'].shape[2:], self.device)
+        if self.image_options is not None:
+            if self._image_volumes is None:
+                self._image_init(fixed, moving)
+            self._image_posterior = ImagePosterior(self._image_volumes, image_posterior_names(self.image_options), self.device)
         if self.covariance_options is not None:
             self._displacement_covariance = DisplacementCovariance(self._outputs['displacement'].shape[2:], self.device)
         if self.quantiles_options is not None:
@@ -915,6 +937,48 @@ class Trainer(VIMixin, BaseTrainer):
         if save_outputs:
             save_jacobian_posterior(self.logger, self.config.save_dirs, spacing, self.jacobian_fold_prob, self.jacobian_logJ_mean,
                                     self.jacobian_logJ_std, mask, 'MCMC')
+
+    def _image_init(self, fixed, moving):
+        """trainer.image_posterior -> self._image_volumes (S,1,D,H,W) on the device: the moving image as the chain warps it, then
+        the extra volumes, read onto the registration grid as the loader reads the moving image and -- with trainer.affine_init
+        -- resampled through the same map (affine.resample_pair, as its 'im'); and the floor of the z map, the option's or 1e-3
+        of the moving image's intensity range (one host read-back)"""
+        opt = self.image_options
+        volumes = [moving['im'][:1].to(self.device, torch.float32)]
+        for v in opt['volumes']:
+            extra = image_posterior.load_volume(v['path'], self.data_loader).to(self.device)
+            if self.affine_summary is not None:
+                extra = affine.resample_pair({'im': extra}, self.affine_summary['lin'], self.affine_summary['shift'])['im']
+            volumes.append(extra)
+        self._image_volumes = torch.cat(volumes).contiguous()
+        self._image_std_floor = opt['std_floor']
+        if self._image_std_floor is None:
+            _, (m_lo, m_hi) = ops.intensity_ranges(fixed['im'], moving['im'])
+            self._image_std_floor = IMAGE_STD_FLOOR_FRACTION * (m_hi - m_lo)
+        self.logger.info(f'image posterior: {len(volumes)} volumes ({", ".join(image_posterior_names(opt))}), '
+                         f'{16 * len(volumes)} bytes per voxel; floor of the z map {self._image_std_floor:.6g}')
+
+    def _finish_image_posterior(self, fixed, spacing, save_outputs):
+        """mean, std and range maps of every carried volume and, for the moving image with the option's "reference", the z map of
+        its posterior mean against the fixed image -> self.image_maps / self.image_summary (keyed by volume name), the
+        MCMC/image/{name}/* metrics and, with save_outputs and the option's save,
+        samples/MCMC_im_{name}_{mean,std,range}[_masked].nii.gz and samples/MCMC_im_moving_z[_masked].nii.gz.  The maps live on
+        the fixed grid, so the summaries are over the FIXED mask, as for the Jacobian posterior."""
+        mask = fixed['mask'][0]
+        opt = self.image_options
+        reference = {'moving': fixed['im'][0, 0]} if opt['reference'] else None
+        self.image_maps = self._image_posterior.finalize(mask, reference, self._image_std_floor)
+        self.image_summary = {name: volume['summary'] for name, volume in self.image_maps.items()}
+        for name, s in self.image_summary.items():
+            for key in IMAGE_METRICS + (IMAGE_Z_METRICS if 'z_rms' in s else ()):
+                self.metrics.update(f'MCMC/image/{name}/{key}', s[key])
+            self.logger.info(f'image posterior of {name!r}: {s["records"]} samples over {s["voxels"]} masked voxels '
+                             f'({s["nonfinite_voxels"]} non-finite): mean {s["mean"]:.6g}, std mean {s["std_mean"]:.6g}, max '
+                             f'{s["std_max"]:.6g}, widest range {s["range_max"]:.6g}' +
+                             (f'; against the fixed image z rms {s["z_rms"]:.4g}, max {s["z_max"]:.4g}, '
+                              f'{100 * s["z_gt2"]:.2f} % above 2, {100 * s["z_gt3"]:.2f} % above 3' if 'z_rms' in s else ''))
+        if save_outputs and opt['save']:
+            save_image_posterior(self.logger, self.config.save_dirs, spacing, self.image_maps, mask, 'MCMC')
 
     def _finish_displacement_covariance(self, mask, spacing, save_outputs):
         """principal standard deviations (voxels), major direction and fractional anisotropy of the displacement posterior and
@@ -1298,6 +1362,8 @@ class Trainer(VIMixin, BaseTrainer):
                 self._auto_mask(fixed, moving)
             if self.affine_options is not None:
                 moving = self._affine_init(fixed, moving)
+            if self.image_options is not None:
+                self._image_init(fixed, moving)
             self._engine_init(fixed, moving)
             self._GMM_init(fixed, moving, var_params_q_v)
             self._metrics_init(fixed, moving)

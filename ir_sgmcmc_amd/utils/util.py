@@ -199,6 +199,27 @@ def calc_jacobian_posterior(transformations, mask=None):
 
 
 @torch.no_grad()
+def calc_image_posterior(volumes, transformations, reference=None, mask=None, std_floor=0.0):
+    """Volumes carried through transformation samples (absent in the reference): volumes (S,1,D,H,W) float32 on the device, on
+    the grid the transformations sample, S in 1 .. 8; transformations (n,3,D,H,W) float32 in normalised coordinates, the n
+    records in order; reference: {index of a volume: (D,H,W) volume it is compared with} or None; mask (D,H,W) or None.
+    -> one dict per volume {'mean', 'std', 'range'[, 'z'], 'summary'}, as diagnostics.ImagePosterior.finalize."""
+    from .. import _lib as L
+    from ..diagnostics import ImagePosterior
+    if transformations.dim() != 5 or transformations.shape[1] != 3:
+        raise ValueError(f'transformations must have shape (n, 3, D, H, W), got {tuple(transformations.shape)}')
+    if volumes.dim() != 5 or volumes.shape[1] != 1 or volumes.shape[2:] != transformations.shape[2:]:
+        raise ValueError(f'volumes must have shape (S, 1, {", ".join(str(n) for n in transformations.shape[2:])}), got '
+                         f'{tuple(volumes.shape)}')
+    names = [str(i) for i in range(volumes.shape[0])]
+    ip = ImagePosterior(volumes, names, transformations.device)
+    for i in range(0, transformations.shape[0], L.IRS_MAX_CHAINS):  # one launch folds up to IRS_MAX_CHAINS records, in order
+        ip.record(transformations[i:i + L.IRS_MAX_CHAINS].float().contiguous())
+    out = ip.finalize(mask, {str(k): v for k, v in (reference or {}).items()}, std_floor)
+    return [out[name] for name in names]
+
+
+@torch.no_grad()
 def calc_displacement_covariance(displacements, mask=None, scale=None):
     """Principal spread and direction of displacement samples (absent in the reference): displacements (n,3,D,H,W) float32 on
     the device, in normalised coordinates, the n records in order; mask (D,H,W) or None; scale: three floats, one per channel
