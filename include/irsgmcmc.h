@@ -939,6 +939,24 @@ int irs_sparse_data_set(irs_ctx* ctx, int on);
  * transition, when the dense stage ran, and on a volume whose full-column LCC launches already use the shortest pieces (128^3).
  * Calls irs_flush; blocking. */
 int irs_sparse_data_get(irs_ctx* ctx, int32_t* out, void* stream);
+/* The sparse forward squaring steps of a context on (the default) or off.  On: step k computes d_{k+1} only on the run pieces of
+ * its list -- per 64 x 8 tile column the planes within 3 lcc_s + h_{k+1} + ... + h_{n-1} voxels of the fixed mask (SSD: lcc_s = 0),
+ * h_i the planned width of step i -- which is where the warp, the steps behind it and the adjoint read it.  The widths are planned on
+ * the host from the published bounds max|d_i| (1.25 m + 0.25, as a slab's ghost widths) and checked on the device after the forward
+ * pass (floor(max|d_i|) + 1 <= h_i): a transition whose plan does not hold is a no-op that is re-run with dense steps (irs_flush,
+ * irs_recovered_transitions).  v, grad_v, the state and every scalar equal the dense steps' as numbers wherever both select the
+ * same adjoint variants; the published bounds are maxima over the marched pieces.  Engaged only when the sparse data stage ran in
+ * the transition, every width could be planned (a published bound for every step, predict_variants = 1, not a re-run, not a
+ * captured stream), no step needs the any-radius adjoint, the context has no FFD and no slab, and the irs_io asks for neither
+ * transformation nor displacement (nor im_moving_warped / residuals).  on: 0 off; 1 on, where the dense launch uses segments longer
+ * than the shortest piece in its two-rows form (not at 128^3); n >= 2: on whatever the volume's size, with pieces of at most n planes
+ * (at least 4) -- for tests and A/B runs.  A call of its own, like irs_sparse_data_set.  Test hook: slab_force_h > 0 (irs_option_set)
+ * on a context without a slab forces every planned width to that value. */
+int irs_sparse_forward_set(irs_ctx* ctx, int on);
+/* What the sparse forward steps did in the LAST transition.  out: int32 [no_steps][no_chains][5] = engaged, piece length (planes),
+ * run pieces of the chain in the step's list, planes of 64 x 8 tile columns in its run ranges, planned width of the step.  All zero
+ * when the dense steps ran.  Calls irs_flush; blocking. */
+int irs_sparse_forward_get(irs_ctx* ctx, int32_t* out, void* stream);
 
 /* timing hook for bench.py: the same transition with hipEvents recorded on `stream` around the stages; blocking.
  * All times in milliseconds for THIS call. */

@@ -23,6 +23,7 @@ constexpr int kPlanMaxLen = IRS_BWD_MAX_SEG;
 constexpr int kPlanMinLen = 8;     // shortest piece the length search may choose (two run-in planes per piece: 25 % at 8)
 constexpr int kPlanMinForced = 4;  // shortest piece a forced length (march_seg) may ask for; sizes the entry lists
 constexpr int kPlanStats = 4;      // per (step, chain): engaged, piece length, pieces, planes in run ranges
+constexpr int kForwardStats = 5;   // read-back of the sparse forward steps: the four above and the step's planned width
 
 // One unit of work of a step, on the planes [z0, z1) of tile column `tile` of `chain`: march them (fill == 0) or store zeros to them.
 // Marching and filling are separate entries: a workgroup that did both kept the fill's addresses alive across the tile body, and
@@ -86,16 +87,29 @@ constexpr int kLccTX = 32, kLccTY = 16;   // tile column of the LCC map and of t
 constexpr int kWarpTX = 64, kWarpTY = 8;  // tile-plane of the warp (field_kernels.hip)
 constexpr int kDataKernels = 4;           // read-back rows of the data stage: warp, LCC map, statistics (dense: zero), data term
 enum PlanFill { kFillNext = 0, kFillAll = 1, kFillNone = 2 };  // what a list zero-fills: what the next step reads / the rest of every column / nothing
-// How the run ranges and the lists of one launch are formed.  List k has reach reach0 - k * reach_dec; list 0 and the lists behind it
-// may differ in what they fill and in the resident set they are cut for (the data term and the LCC map share a launch).
+constexpr int kPlanMaxLists = 32;         // most lists a shape with per-list reaches describes (the forward steps: one per step)
+// How the run ranges and the lists of one launch are formed.  List k has reach reach0 - k * reach_dec -- or, with n_reach > 0, its own
+// reach[k] (the forward steps: their reaches are sums of planned widths); list 0 and the lists behind it may differ in what they
+// fill and in the resident set they are cut for (the data term and the LCC map share a launch).
 struct PlanShape {
     int tx, ty;
     int reach0, reach_dec;
     int fill[2];
     int G[2];
     int lmin;
+    int n_reach;
+    int reach[kPlanMaxLists];
 };
-IRS_HD int plan_reach(const PlanShape& s, int k) { return s.reach0 - k * s.reach_dec; }
+IRS_HD int plan_reach(const PlanShape& s, int k) { return s.n_reach > 0 ? s.reach[k] : s.reach0 - k * s.reach_dec; }
+
+// ---- sparse forward squaring steps (adjoint_plan.hip, "sparse forward steps"): d_j must be exact on W_j = mask (+) reach_j,
+// reach_j = 3 S + h_j + ... + h_{n-1} (h_i: planned width of step i, floor(max|d_i|) + 1 <= h_i; S: LCC half width, SSD 0).  Forward
+// step k writes d_{k+1}: its list is the hull of W_{k+1} over the forward tile's columns.
+IRS_HD int plan_forward_reach(const int* h, int n, int S, int k) {
+    int m = 3 * S;
+    for (int i = k + 1; i < n; ++i) m += h[i];
+    return m;
+}
 IRS_HD int plan_fill_of(const PlanShape& s, int k) { return s.fill[k > 0 ? 1 : 0]; }
 IRS_HD int plan_resident_of(const PlanShape& s, int k) { return s.G[k > 0 ? 1 : 0]; }
 // the voxels [a, b) of an axis of n within m of tile t of `size`

@@ -223,15 +223,15 @@ struct PlanLayout {
     size_t ext, runs, colplan, entries, count, stats, total;
     int cap, ntx, nty;
 };
-static PlanLayout plan_layout(Vol vol, int C, int no_steps) {
+static PlanLayout plan_layout(Vol vol, int C, int no_steps, int tx = kPlanTX, int ty = kPlanTY, bool own_ext = true) {
     PlanLayout l;
-    l.ntx = (vol.W + kPlanTX - 1) / kPlanTX;
-    l.nty = (vol.H + kPlanTY - 1) / kPlanTY;
+    l.ntx = (vol.W + tx - 1) / tx;
+    l.nty = (vol.H + ty - 1) / ty;
     const size_t cols = (size_t)C * l.ntx * l.nty;
     l.cap = plan_entries_cap((int)cols, vol.D);
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += plan_align(bytes); return o; };
-    l.ext = take(sizeof(int) * 2 * (size_t)C * vol.H * vol.W);
+    l.ext = take(own_ext ? sizeof(int) * 2 * (size_t)C * vol.H * vol.W : 0);
     l.runs = take(sizeof(int) * 2 * cols * no_steps);
     l.colplan = take(sizeof(ColPlan) * cols * no_steps);
     l.entries = take(sizeof(PlanEntry) * (size_t)l.cap * no_steps);
@@ -243,10 +243,9 @@ static PlanLayout plan_layout(Vol vol, int C, int no_steps) {
 
 size_t adjoint_plan_bytes(Vol vol, int C, int no_steps) { return plan_layout(vol, C, no_steps).total; }
 
-AdjointPlan adjoint_plan_views(char* base, Vol vol, int C, int no_steps) {
-    const PlanLayout l = plan_layout(vol, C, no_steps);
+static AdjointPlan plan_views(char* base, const PlanLayout& l, bool own_ext) {
     AdjointPlan p;
-    p.ext = (int*)(base + l.ext);
+    p.ext = own_ext ? (int*)(base + l.ext) : nullptr;
     p.runs = (int*)(base + l.runs);
     p.colplan = (ColPlan*)(base + l.colplan);
     p.entries = (PlanEntry*)(base + l.entries);
@@ -257,6 +256,7 @@ AdjointPlan adjoint_plan_views(char* base, Vol vol, int C, int no_steps) {
     p.nty = l.nty;
     return p;
 }
+AdjointPlan adjoint_plan_views(char* base, Vol vol, int C, int no_steps) { return plan_views(base, plan_layout(vol, C, no_steps), true); }
 
 void launch_adjoint_plan(const float* g_warped, const unsigned* dmax, const AdjointPlan& plan, int no_steps, int C, Vol vol,
                          int64_t G, int forced_len, hipStream_t st) {
@@ -266,6 +266,29 @@ void launch_adjoint_plan(const float* g_warped, const unsigned* dmax, const Adjo
     hipLaunchKernelGGL(plan_runs_kernel, dim3((unsigned)(C * plan.ntx * plan.nty), (unsigned)no_steps), dim3(kWave), 0, st, plan.ext, C, dmax,
                        plan.runs, vol, C, no_steps, plan.ntx, plan.nty, shape);
     hipLaunchKernelGGL(plan_lists_kernel, dim3((unsigned)no_steps), dim3(kPlanBlock), 0, st, plan.runs, dmax, plan.colplan, plan.entries, plan.count,
+                       plan.stats, vol, C, no_steps, plan.ntx, plan.nty, plan.cap, shape, forced_len);
+}
+
+// ------------------------------------------------------------------------------------------------
+// sparse forward steps: the lists of all steps from the mask's extent table (the data plan's, formed in front of the forward pass)
+// and the reaches the host planned (adjoint_plan.h: plan_forward_reach).  Run pieces only: what a step leaves unwritten is stale
+// but finite, and only ever meets a zero weight or a zero gradient.  The views have no extent table of their own.
+// ------------------------------------------------------------------------------------------------
+size_t forward_plan_bytes(Vol vol, int C, int no_steps) { return plan_layout(vol, C, no_steps, kWarpTX, kWarpTY, false).total; }
+AdjointPlan forward_plan_views(char* base, Vol vol, int C, int no_steps) {
+    return plan_views(base, plan_layout(vol, C, no_steps, kWarpTX, kWarpTY, false), false);
+}
+int forward_plan_run_bound(const AdjointPlan& plan, int C, Vol vol, int64_t G, int forced_len) {
+    return plan_run_bound(C * plan.ntx * plan.nty, vol.D, (int)(G > 0 ? G : 1024), forced_len);
+}
+void launch_forward_plan(const int* ext, int ext_chains, const AdjointPlan& plan, const int* width, int S, int no_steps, int C, Vol vol,
+                         int64_t G, int forced_len, hipStream_t st) {
+    const int g = (int)(G > 0 ? G : 1024);
+    PlanShape shape{kWarpTX, kWarpTY, 0, 0, {kFillNone, kFillNone}, {g, g}, kPlanMinLen, no_steps, {}};
+    for (int k = 0; k < no_steps && k < kPlanMaxLists; ++k) shape.reach[k] = plan_forward_reach(width, no_steps, S, k);
+    hipLaunchKernelGGL(plan_runs_kernel, dim3((unsigned)(C * plan.ntx * plan.nty), (unsigned)no_steps), dim3(kWave), 0, st, ext, ext_chains, nullptr,
+                       plan.runs, vol, C, no_steps, plan.ntx, plan.nty, shape);
+    hipLaunchKernelGGL(plan_lists_kernel, dim3((unsigned)no_steps), dim3(kPlanBlock), 0, st, plan.runs, nullptr, plan.colplan, plan.entries, plan.count,
                        plan.stats, vol, C, no_steps, plan.ntx, plan.nty, plan.cap, shape, forced_len);
 }
 

@@ -51,6 +51,7 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     c->kn = global_knobs();
     c->sparse_adjoint = true;  // (irs_sparse_adjoint_set)
     c->sparse_data = 1;        // (irs_sparse_data_set)
+    c->sparse_forward = 1;     // (irs_sparse_forward_set)
     c->cfg = *cfg;
     c->C = C;
     c->vol = make_vol(D, H, W);
@@ -132,6 +133,7 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     const bool planned = !sl;  // (the slab engine marches full columns)
     const size_t o_plan = take(planned ? adjoint_plan_bytes(c->vol, C, cfg->no_steps) : 0);
     const size_t o_dplan = take(planned ? data_plan_bytes(c->vol, C) : 0);
+    const size_t o_fplan = take(planned && !c->ffd ? forward_plan_bytes(c->vol, C, cfg->no_steps) : 0);
     const size_t o_state = take(sizeof(DevState));
     c->slab_bytes = off;
     // (a context is zeroed at birth and irs_destroy releases whatever exists by then: one teardown for every failure below)
@@ -169,6 +171,7 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     c->cmm = (float*)(c->slab + o_cmm);
     if (planned) c->plan = adjoint_plan_views(c->slab + o_plan, c->vol, C, cfg->no_steps);
     if (planned) c->dplan = data_plan_views(c->slab + o_dplan, c->vol, C);
+    if (planned && !c->ffd) c->fplan = forward_plan_views(c->slab + o_fplan, c->vol, C, cfg->no_steps);
     c->state = (DevState*)(c->slab + o_state);
 
     if (ensure_lin_tables(c->lin, D, H, W, nullptr)) {
@@ -318,8 +321,9 @@ int irs_get_scalars(irs_ctx* c, irs_scalars* out, void* stream) {
 // ================================================================================================
 // velocity (v + noise, smoothed) -> vs; dense velocity -> d_1..d_n; warp -> warped; residual -> z (+ sigM)
 // data_on (ctx.h): > 0 the warp leaves the tile-planes outside the data plan's hull unwritten, > 1 the LCC map walks its list
+// fwd_lists: the squaring steps walk the lists of c->fplan (launch_forward_plan has run on this stream)
 static int forward_pass(irs_ctx* c, const irs_io* io, const float* v, bool with_noise, bool with_jitter, float* vs,
-                        float* warped, float* z, float* gradm, int chains, hipStream_t st, int timed, int data_on = 0) {
+                        float* warped, float* z, float* gradm, int chains, hipStream_t st, int timed, int data_on = 0, bool fwd_lists = false) {
     const irs_config& cfg = c->cfg;
     const int C = chains;
     const uint64_t* it = &c->state->st.iteration;
@@ -359,8 +363,12 @@ static int forward_pass(irs_ctx* c, const irs_io* io, const float* v, bool with_
     for (int k = 0; k < cfg.no_steps; ++k) {
         const float* in = k == 0 ? dense : c->steps + (int64_t)(k - 1) * field;
         float* out = c->steps + (int64_t)k * field;
-        launch_exp_step_fwd_march(in, out, k == 0, cfg.no_steps, C, c->vol, lin, c->dmax + (int64_t)k * c->C * 4,
-                                  c->dmax + (int64_t)(k + 1) * c->C * 4, predicted_small(c, k), fwd_lay(c, k), st);
+        if (fwd_lists)
+            launch_exp_step_fwd_plan(in, out, k == 0, cfg.no_steps, C, c->vol, lin, c->dmax + (int64_t)(k + 1) * c->C * 4, fwd_lay(c, k), c->fplan, k,
+                                     c->sparse_forward > 1 ? c->sparse_forward : 0, st);
+        else
+            launch_exp_step_fwd_march(in, out, k == 0, cfg.no_steps, C, c->vol, lin, c->dmax + (int64_t)k * c->C * 4,
+                                      c->dmax + (int64_t)(k + 1) * c->C * 4, predicted_small(c, k), fwd_lay(c, k), st);
     }
     if (timed) HIP_TRY(hipEventRecord(c->ev[2], st));
     const float* d_last = c->steps + (int64_t)(cfg.no_steps - 1) * field;
@@ -468,7 +476,33 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
         launch_data_plan(io->mask, io->mask_chains, c->dplan, lcc ? cfg.lcc_s : 0, lcc, C, vol, st);
     }
     c->data_on = data_on;
-    if (forward_pass(c, io, io->v, true, cfg.uniform_alpha > 0.0f, vs, warped, z, fuse_warp_bwd ? c->gA : nullptr, C, st, timed, data_on)) return 1;
+    // Sparse forward steps (adjoint_plan.hip): d_j is only read within 3 S + h_j + ... + h_{n-1} of the mask -- by the warp, by the
+    // forward steps behind it and by the adjoint, whose gradient is zero further out -- where h_i is how far step i reaches,
+    // floor(max|d_i|) + 1.  The widths are PLANNED here from the bounds the host last saw, with the safety factor of a slab's ghost
+    // widths, go into the verdict, and are checked on the device after the forward pass: a step that outgrew its width makes the
+    // transition a no-op that is re-run without assumptions, which means dense.  Only where every width can be planned (a valid
+    // hint for every step, production prediction, no re-run, no capture), the any-radius adjoint is left out for every step (it takes
+    // maxima over whole fields), the data plan has formed the extent table, nobody asked for the fields themselves, and -- the rule
+    // on sizes -- the dense launch uses segments above the shortest piece in its two-rows form (not at 128^3).
+    const int fwd_forced = c->sparse_forward > 1 ? c->sparse_forward : 0;
+    bool fwd_on = c->sparse_forward != 0 && data_on > 0 && c->fplan.entries != nullptr && !c->ffd && !io->transformation && !io->displacement &&
+                  c->kn.predict_variants == 1 && !no_assumptions && !is_capturing(st) && c->hint != nullptr && cfg.no_steps <= kPlanMaxLists &&
+                  (fwd_forced > 0 || exp_fwd_dense_allows_lists(vol, C));
+    for (int k = 0; k < cfg.no_steps && fwd_on; ++k) {
+        bool valid;
+        const float m = hint_row_max(c->hint + (size_t)k * C * 4, C * 4, &valid);
+        // (slab_force_h on a context without a slab: every planned width forced -- a deliberately wrong plan for the validation to catch)
+        const int h = !valid ? -1 : c->kn.slab_force_h > 0 ? c->kn.slab_force_h : ghost_width_from_bound(m, true);
+        fwd_on = skip_any[k] && h >= 1 && h <= 255;
+        c->fwd_width[k] = h;
+    }
+    c->fwd_on = fwd_on;
+    if (fwd_on) {
+        for (int k = 0; k < cfg.no_steps; ++k) vd.width[k] = (unsigned char)c->fwd_width[k];
+        launch_forward_plan(c->dplan.ext, io->mask_chains, c->fplan, c->fwd_width, lcc ? cfg.lcc_s : 0, cfg.no_steps, C, vol, exp_fwd_plan_resident(),
+                            fwd_forced, st);
+    }
+    if (forward_pass(c, io, io->v, true, cfg.uniform_alpha > 0.0f, vs, warped, z, fuse_warp_bwd ? c->gA : nullptr, C, st, timed, data_on, fwd_on)) return 1;
     const int64_t field = (int64_t)C * 3 * vol.V;
     const float* d_last = c->steps + (int64_t)(cfg.no_steps - 1) * field;
     if (io->transformation || io->displacement) launch_svf_outputs(d_last, io->transformation, io->displacement, C, vol, lin, st);
@@ -691,6 +725,31 @@ int irs_sparse_adjoint_get(irs_ctx* c, int32_t* out, void* stream) {
     if (irs_flush(c, stream)) return 1;
     HIP_TRY(hipMemcpyAsync(out, c->plan.stats, n * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+}
+
+int irs_sparse_forward_set(irs_ctx* c, int on) {
+    if (!c) return fail("irs_sparse_forward_set: null argument");
+    if (on < 0) return fail("irs_sparse_forward_set: 0 (off), 1 (on) or a piece length");
+    c->sparse_forward = on;
+    return 0;
+}
+
+int irs_sparse_forward_get(irs_ctx* c, int32_t* out, void* stream) {
+    if (!c || !out) return fail("irs_sparse_forward_get: null argument");
+    const int n = c->cfg.no_steps, C = c->C;
+    memset(out, 0, (size_t)n * C * kForwardStats * sizeof(int32_t));
+    if (!c->fplan.stats || !c->fwd_on || c->n_enqueued == 0) return 0;  // dense forward steps: nothing engaged
+    int width[32];  // (a re-run inside irs_flush is dense and clears fwd_on: the figures are those of the last transition CALLED)
+    memcpy(width, c->fwd_width, sizeof(width));
+    if (irs_flush(c, stream)) return 1;
+    int32_t stats[32 * IRS_MAX_CHAINS * kPlanStats];
+    HIP_TRY(hipMemcpyAsync(stats, c->fplan.stats, (size_t)n * C * kPlanStats * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    for (int i = 0; i < n * C; ++i) {
+        memcpy(out + (size_t)i * kForwardStats, stats + (size_t)i * kPlanStats, sizeof(int32_t) * kPlanStats);
+        out[(size_t)i * kForwardStats + kPlanStats] = width[i / C];
+    }
     return 0;
 }
 

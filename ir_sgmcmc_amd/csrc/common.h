@@ -101,7 +101,7 @@ struct Knobs {
     int slab_buffers = 3;      // IRS_SLAB_BUFFERS      gradient fields the adjoint of a multi-rank slab rotates through (2: rounds of at most two steps)
     int slab_split = 1;        // IRS_SLAB_SPLIT        interior / boundary split around an exchange
     int slab_exact = 0;        // IRS_SLAB_EXACT        every transition in measuring mode
-    int slab_force_h = 0;      // IRS_SLAB_FORCE_H      test hook: a deliberately wrong ghost-width plan
+    int slab_force_h = 0;      // IRS_SLAB_FORCE_H      test hook: a deliberately wrong ghost-width plan (without a slab: every planned width of the sparse forward steps)
     int data_batch = 1;        // IRS_DATA_BATCH        C > 1, GMM / LCC: the data terms of all chains in ONE launch behind the serial statistics -> step loop
     int chain_overlap = 0;     // IRS_CHAIN_OVERLAP     C > 1: data term of chain c on a side stream, overlapping the statistics of chain c + 1
                                //                       (round 5, asked for; measured SLOWER: 0.728 against 0.711 ms per chain-transition at 128^3

@@ -1,5 +1,6 @@
 // The context behind include/irsgmcmc.h (shared by api_ops.hip, api_ctx.hip, knobs.hip and slab.hip): workspace views, variant prediction, error plumbing.
 #pragma once
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -63,6 +64,11 @@ struct irs_ctx {
     int sparse_data = 1;    // irs_sparse_data_set: 0 the dense data stage; 1 warp, LCC map, statistics and data term only where the mask
                             // reaches (where the rule on sizes lets them); n >= 2: on whatever the size, pieces of n planes
     int data_on = 0;        // the last transition enqueued: 0 dense data stage, 1 the warp's hull, 2 + the map's list, 3 + the data term's
+    irs::AdjointPlan fplan; // sparse forward steps (adjoint_plan.hip): one list per step over 64 x 8 columns; no buffers on a slab context
+    int sparse_forward = 1; // irs_sparse_forward_set: 0 dense forward steps; 1 only where a later kernel reads them (where the rule on
+                            // sizes lets them); n >= 2: on whatever the size, pieces of n planes
+    bool fwd_on = false;    // the last transition enqueued walked the forward lists ...
+    int fwd_width[32] = {}; // ... with these planned widths h_k (in its verdict: floor(max|d_k|) + 1 <= h_k)
     float* cmm;      // coarse (8^3 cells) min / max of d_k for the source boxes of the any-radius adjoint (kernels.h)
     unsigned* hint = nullptr;  // pinned host copy of dmax as of the last finished transition (written by finalize_kernel, read
                      // by the host WITHOUT synchronisation: a hint that only decides which variants are launched)
@@ -141,6 +147,13 @@ inline float hint_row_max(const unsigned* row, int n, bool* valid) {
         m = f > m ? f : m;
     }
     return m;
+}
+
+// Planned width of a step whose published bound is m: what a ghost zone of a slab rank, or the reach of a sparse forward list,
+// allows the step's displacement (floor(max|d_k|) + 1 <= width).  safety: room for the bound to move until the plan is used.
+inline int ghost_width_from_bound(float m, bool safety) {
+    if (!(m >= 0.0f) || m > 1.0e6f) return -1;
+    return (int)floorf(safety ? 1.25f * m + 0.25f : m) + 1;
 }
 
 // Host-side guess of "max |d_k| stays well below `bound`" from the bounds of the last transition the host has seen

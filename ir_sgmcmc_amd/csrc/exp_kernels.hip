@@ -1431,12 +1431,14 @@ extern "C" __attribute__((visibility("default"))) int irs_debug_fwd_trace(unsign
 #endif
 // PF: how many planes ahead of the one being committed the global loads run (1: the next plane is in flight while this one is
 // sampled; 2: two planes -- short segments on small volumes, where a plane step is otherwise one load latency long)
-template <bool PRESCALE, int R, int FROWS, int PF>
+// PLAN: chain, tile and z-range come from a run piece of the sparse forward plan (adjoint_plan.hip) instead of the launch's segments;
+// no window test on the input's bound -- the radius-1 ring is correct for any displacement (far taps go to global memory)
+template <bool PRESCALE, int R, int FROWS, int PF, bool PLAN = false>
 __device__ __forceinline__ void exp_fwd_march_tile(const float* __restrict__ din, float* __restrict__ dout, const Vol vol,
                                                    const Lin lin, const Scale3L sc, const unsigned* __restrict__ dmax_in,
                                                    unsigned* __restrict__ dmax_out, const int seg_len, const int nseg,
                                                    const int h_lo, const int h_hi, const int swz_run, const int tile_id,
-                                                   const dim3 tiles, const int lay) {
+                                                   const dim3 tiles, const int lay, const PlanEntry piece = PlanEntry{}) {
     using M = MarchF<R, FROWS>;
     constexpr int PX = M::PX, PN = M::PN, NIT = M::NIT, PITCH = M::PITCH, PNP = M::PNP, kFwdBlock = M::kFwdBlock;
     // ring of 2R+2 slots: one more than a sample can reach, so that the commit of the next source plane never overwrites
@@ -1445,17 +1447,22 @@ __device__ __forceinline__ void exp_fwd_march_tile(const float* __restrict__ din
     __shared__ float2 r_xy[NS * PNP];  // (d0, d1): one ds_read_b64 per tap
     __shared__ float r_z[NS * PNP];    // d2
     __shared__ float red[3 * (kFwdBlock / kWave)];
-    const int tile_ = xcd_swizzle_runs(tile_id, (int)(tiles.x * tiles.y * tiles.z), swz_run);
+    const int tile_ = PLAN ? piece.tile : xcd_swizzle_runs(tile_id, (int)(tiles.x * tiles.y * tiles.z), swz_run);
     const int tbx = tile_ % tiles.x, tby = (tile_ / tiles.x) % tiles.y, tbz = tile_ / (tiles.x * tiles.y);
-    const int chain = tbz / nseg, seg = tbz % nseg;
-    if (dmax_in) {
+    const int chain = PLAN ? piece.chain : tbz / nseg, seg = tbz % nseg;
+    if (!PLAN && dmax_in) {
         const int need = max(max((int)ceilf(__uint_as_float(dmax_in[chain * 4 + 0])), (int)ceilf(__uint_as_float(dmax_in[chain * 4 + 1]))),
                              (int)ceilf(__uint_as_float(dmax_in[chain * 4 + 2])));
         if (need <= h_lo || need > h_hi) return;
     }
     const int ox = tbx * FTX, oy = tby * FTY;
     int z0, z1;
-    seg_range(vol, seg, seg_len, z0, z1);
+    if (PLAN) {
+        z0 = piece.z0;
+        z1 = piece.z1;
+    } else {
+        seg_range(vol, seg, seg_len, z0, z1);
+    }
     const int64_t V = vol.V;
     const int64_t cb = (int64_t)chain * 3 * V;
     // The layouts are COMPILE-TIME constants inside `run`: with a run-time layout both forms of a prefetch load (one 12-byte load /
@@ -1705,10 +1712,46 @@ __global__ __launch_bounds__(FTX * FTY / FROWS, R == 1 ? IRS_FWD_WAVES : 1) void
     }
 }
 
-// (A radius-1 kernel that marches TWO planes per step was built for small launches and measured flat: DESIGN.md, "Round-5
-// measurements and experiments".)
-void launch_exp_step_fwd_march(const float* din, float* dout, bool prescale_in, int no_steps, int C, Vol vol, Lin lin,
-                               const unsigned* dmax_in, unsigned* dmax_out, bool only_r1, int lay, hipStream_t st) {
+// The forward step on the run pieces of its list (sparse forward steps: adjoint_plan.hip): the unchanged radius-1 tile body, two
+// rows per thread, one plane of prefetch.  ONE workgroup per run piece on a grid of the most pieces the list can have
+// (plan_run_bound), the ones beyond the count leave at once.  A resident set of workgroups striding over the list was built too and
+// measured slower (profiles/sparse_forward_ab.txt): the entry loop costs the tile body 12 registers and 12 bytes of scratch (128
+// VGPRs against 116 and none), 74.0 against 72.5 us per launch on the bench's lists.
+static_assert(FTX == kWarpTX && FTY == kWarpTY, "the forward lists are cut over the forward tile's columns");
+template <bool PRESCALE>
+__global__ __launch_bounds__(FTX * FTY / FROWS_BIG, IRS_FWD_WAVES) void exp_fwd_march_plan_kernel(
+    const float* __restrict__ din, float* __restrict__ dout, Vol vol, Lin lin, Scale3L sc, unsigned* __restrict__ dmax_out,
+    const PlanEntry* __restrict__ entries, const int* __restrict__ count, int cap, int swz_run, dim3 tiles, int lay) {
+    // The piece is requested at both positions plan_swizzle can give -- the XCD-swizzled one and, for the tail that fills no group of
+    // 8 runs, the plain one -- BEFORE the count has arrived: one memory latency in front of the march instead of two in a row.
+    const int id = (int)blockIdx.x, group = 8 * swz_run;
+    const int g = swz_run > 1 ? id / group : 0, w = id - g * group;
+    const int swz = swz_run > 1 ? g * group + (w & 7) * swz_run + (w >> 3) : id;
+    const PlanEntry e_swz = entries[min(swz, cap - 1)], e_plain = entries[min(id, cap - 1)];
+    const int n_run = count[1];  // run pieces only: the forward lists have no fills
+    if (id >= n_run) return;
+    exp_fwd_march_tile<PRESCALE, 1, FROWS_BIG, 1, true>(din, dout, vol, lin, sc, nullptr, dmax_out, 0, 1, 0, 0, 0, id, tiles, lay,
+                                                        plan_swizzle(id, n_run, swz_run) == id ? e_plain : e_swz);
+}
+int64_t exp_fwd_plan_resident() {
+    static int cache = 0;
+    return resident_blocks((const void*)exp_fwd_march_plan_kernel<false>, FTX * FTY / FROWS_BIG, &cache);
+}
+void launch_exp_step_fwd_plan(const float* din, float* dout, bool prescale_in, int no_steps, int C, Vol vol, Lin lin, unsigned* dmax_out, int lay,
+                              const AdjointPlan& plan, int step, int forced_len, hipStream_t st) {
+    const dim3 tiles((vol.W + FTX - 1) / FTX, (vol.H + FTY - 1) / FTY, 1);
+    const Scale3L sc = make_scale_l(vol, no_steps);
+    const int swz_env = global_knobs().swz_run;
+    const int swz_run = swz_env >= 0 ? swz_env : (int)tiles.x;
+    const int grid = forward_plan_run_bound(plan, C, vol, exp_fwd_plan_resident(), forced_len);
+    with_bool(prescale_in, [&](auto P) {
+        hipLaunchKernelGGL((exp_fwd_march_plan_kernel<decltype(P)::value>), dim3((unsigned)(grid > 0 ? grid : 1)), dim3(FTX * FTY / FROWS_BIG), 0, st, din,
+                           dout, vol, lin, sc, dmax_out, plan.entries + (int64_t)step * plan.cap, plan.count + 2 * step, plan.cap, swz_run, tiles, lay);
+    });
+}
+
+// segment length of the dense radius-1 launch, and whether it takes the small one-row-per-thread form
+static int exp_fwd_dense_seg_len(Vol vol, int C, bool* small_out) {
     const int seg_env = global_knobs().march_seg_fwd;
     const int64_t per_layer = (int64_t)((vol.W + FTX - 1) / FTX) * ((vol.H + FTY - 1) / FTY) * C;
     int seg_len = pick_seg_len(vol.nz + vol.nzb, per_layer, 8, seg_env);
@@ -1726,6 +1769,23 @@ void launch_exp_step_fwd_march(const float* din, float* dout, bool prescale_in, 
                                   : resident_blocks((const void*)exp_fwd_march_kernel<false, 1, FROWS_BIG, 1>, FTX * FTY / FROWS_BIG, &cache_big);
         if (res > 0) seg_len = pick_seg_len_fit(vol.nz, vol.nzb, per_layer, 8, 2, res, 0);
     }
+    *small_out = small;
+    return seg_len;
+}
+bool exp_fwd_dense_allows_lists(Vol vol, int C) {
+    bool small;
+    const int seg_len = exp_fwd_dense_seg_len(vol, C, &small);
+    return !small && seg_len > kPlanMinLen;
+}
+
+// (A radius-1 kernel that marches TWO planes per step was built for small launches and measured flat: DESIGN.md, "Round-5
+// measurements and experiments".)
+void launch_exp_step_fwd_march(const float* din, float* dout, bool prescale_in, int no_steps, int C, Vol vol, Lin lin,
+                               const unsigned* dmax_in, unsigned* dmax_out, bool only_r1, int lay, hipStream_t st) {
+    const int seg_env = global_knobs().march_seg_fwd;
+    const int64_t per_layer = (int64_t)((vol.W + FTX - 1) / FTX) * ((vol.H + FTY - 1) / FTY) * C;
+    bool small;
+    const int seg_len = exp_fwd_dense_seg_len(vol, C, &small);
     const int nseg = vol_nseg(vol, seg_len);  // segments of both windows
     const dim3 tiles((vol.W + FTX - 1) / FTX, (vol.H + FTY - 1) / FTY, (unsigned)(nseg * C));
     const int total = (int)(tiles.x * tiles.y * tiles.z);

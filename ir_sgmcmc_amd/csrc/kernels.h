@@ -87,6 +87,20 @@ AdjointPlan adjoint_plan_views(char* base, Vol vol, int C, int no_steps);
 // the lists are cut for; forced_len > 0: that piece length
 void launch_adjoint_plan(const float* g_warped, const unsigned* dmax, const AdjointPlan& plan, int no_steps, int C, Vol vol,
                          int64_t G, int forced_len, hipStream_t st);
+// Sparse forward steps: one run-piece list per squaring step over the 64 x 8 columns of the forward tile, from the extent table of
+// the data plan (`ext`, formed in front of the forward pass) and the widths the host planned: list k (the step that writes d_{k+1})
+// is the hull of mask (+) (3 S + width[k+1] + ... + width[n-1]).  The views are an AdjointPlan without an extent table of its own.
+size_t forward_plan_bytes(Vol vol, int C, int no_steps);
+AdjointPlan forward_plan_views(char* base, Vol vol, int C, int no_steps);
+void launch_forward_plan(const int* ext, int ext_chains, const AdjointPlan& plan, const int* width, int S, int no_steps, int C, Vol vol,
+                         int64_t G, int forced_len, hipStream_t st);
+int forward_plan_run_bound(const AdjointPlan& plan, int C, Vol vol, int64_t G, int forced_len);  // most run pieces a step's list can have
+// the forward step on step `step`'s list (exp_kernels.hip): the radius-1 tile body, bound of the marched pieces into dmax_out
+void launch_exp_step_fwd_plan(const float* din, float* dout, bool prescale, int no_steps, int C, Vol vol, Lin lin, unsigned* dmax_out, int lay,
+                              const AdjointPlan& plan, int step, int forced_len, hipStream_t st);
+int64_t exp_fwd_plan_resident();  // workgroups of the list-walking forward kernel the chip holds at once (0: unknown)
+// the rule on sizes of the sparse forward steps: the dense launch uses segments longer than the shortest piece, and not its small form
+bool exp_fwd_dense_allows_lists(Vol vol, int C);
 // Sparse data stage: the z-extent of the fixed mask per voxel column -> the warp's hull and the piece lists of the
 // data term (list 0) and the LCC map (list 1).  Views into one allocation of data_plan_bytes().
 struct DataPlan {

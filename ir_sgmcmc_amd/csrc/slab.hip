@@ -742,11 +742,6 @@ struct Exec {
 };
 
 // validation of the planned ghost widths against the (all-reduced) bounds of this transition; sticky flag in pinned memory
-int ghost_width_from_bound(float m, bool safety) {
-    if (!(m >= 0.0f) || m > 1.0e6f) return -1;
-    return (int)floorf(safety ? 1.25f * m + 0.25f : m) + 1;
-}
-
 // global bound (all chains, all axes) of d_k in a slot of the plan hints
 float hint_bound(const irs_ctx* c, const unsigned* slot, int k) {
     bool valid;

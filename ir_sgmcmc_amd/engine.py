@@ -192,6 +192,21 @@ class TransitionEngine:
         return {name: [dict(zip(keys, buf[(k * ch + c) * 4:(k * ch + c) * 4 + 4])) for c in range(ch)]
                 for k, name in enumerate(('warp', 'map', 'stats', 'data_term'))}
 
+    def set_sparse_forward(self, on):
+        """irs_sparse_forward_set: False -> the forward squaring steps march the whole volume (the same numbers); an int n >= 2 -> on
+        whatever the volume's size, with pieces of at most n planes (tests)"""
+        L.check(self.lib.irs_sparse_forward_set(self._ctx, int(on)))
+
+    @_on_device
+    def sparse_forward(self):
+        """irs_sparse_forward_get: per forward step k and chain c of the last transition, [k][c] = dict(engaged, piece_len, pieces,
+        run_planes, width) -- whether the step computed only what a later kernel reads, how its columns were cut, its planned width"""
+        n, ch = self.cfg.no_steps, self.cfg.no_chains
+        buf = (C.c_int32 * (n * ch * 5))()
+        L.check(self.lib.irs_sparse_forward_get(self._ctx, buf, self._stream()))
+        keys = ('engaged', 'piece_len', 'pieces', 'run_planes', 'width')
+        return [[dict(zip(keys, buf[(k * ch + c) * 5:(k * ch + c) * 5 + 5])) for c in range(ch)] for k in range(n)]
+
     # ---------------------------------------------------------------- small state
     @property
     def workspace_bytes(self):
