@@ -1,5 +1,5 @@
-"""Exact ("dyadic") inputs for the warp family and the Jacobian operators, shared by the host and GPU tests (DESIGN.md,
-"Numerics": the exact-case method), and an integer restatement of the Philox jitter of the warp.
+"""Exact ("dyadic") inputs for the warp family, the Jacobian operators and the squaring steps with their adjoints, shared by the
+host and GPU tests ("Numerics": the exact-case method), and an integer restatement of the Philox jitter of the warp.
 
 When every dimension is 2^k + 1, the linspace(-1, 1, n) tables, 2 / (n - 1) and ((g + 1) * 0.5) * (n - 1) are exact in fp32.
 Displacements on a 1/4-voxel lattice (1/8 with the dyadic jitter draws) then give exactly representable interpolation weights,
@@ -101,7 +101,92 @@ def dyadic_transformation(dims, C=CHAINS, seed=0):
     return t.float().contiguous()
 
 
+# ---- squaring steps (csrc/exp_kernels.hip): d_out = d + sample(d, id + d) on a 3-channel field, and its adjoint
+STEP_CLASSES = ('3/4', 'exactly 1', '7/4', 'exactly 2', 'past every face')   # the chains of a step case, by max|d| in voxels
+STEP_REACH = (3, 4, 7, 8)            # quarter voxels: the amplitude of chains 0..3
+STEP_WIDTHS = (1, 2, 2, 3)           # floor(max|d|) + 1 of chains 0..3; chain 4 is beyond 3
+
+
+def extreme_voxels(dims):
+    """[(z, y, x), sign] where the exact-amplitude classes hold +a or -a in all three channels.  For dims 2^k + 1 the last 32- or
+    64-wide tile in x and the last 8-row tile in y hold one column / row: the far corner sits in the ragged last tile of both (the
+    -a there points inwards and lands exactly a voxels inside, or on the near face where the axis is shorter than a), the origin
+    on three faces (+a: inwards), the third on the face x = 0 (-a: outwards in x), the fourth in the ragged last tile row (+a:
+    outwards in y)."""
+    D, H, W = dims
+    return [((D - 1, H - 1, W - 1), -1), ((0, 0, 0), 1), ((D // 2, H // 2, 0), -1), ((D // 2, H - 1, W // 2), 1)]
+
+
+def dyadic_step_case(dims, seed=0):
+    """One squaring step's input on which fp32 arithmetic is exact: D (5,3,*dims) in normalised units, = q * 2 / (n - 1) per axis
+    with q on the quarter-voxel lattice, one chain per class of STEP_CLASSES: chains 0..3 white with |q| <= 3/4, 1, 7/4, 2 voxels
+    (the bound held at extreme_voxels with both signs, whatever the draw), chain 4 with id + q anywhere up to 3 voxels past every
+    face (_positions).  G (5,3,*dims): integers -8..8, the upstream gradient."""
+    assert all(((n - 1) & (n - 2)) == 0 for n in dims), 'every dim must be 2^k + 1'
+    g = torch.Generator().manual_seed(seed)
+    q = torch.empty(5, 3, *dims, dtype=torch.float64)
+    for chain, a in enumerate(STEP_REACH):
+        q[chain] = torch.randint(-a, a + 1, (3, *dims), generator=g).double() / 4.0
+        for (z, y, x), sign in extreme_voxels(dims):
+            q[chain, :, z, y, x] = sign * a / 4.0
+    for c, (n, idx) in enumerate(zip(axis_sizes(dims), _index_grids(dims))):
+        q[4, c] = _positions(n, dims, 4, 3, g) - idx
+    D = torch.stack([q[:, c] * (2.0 / (n - 1)) for c, n in enumerate(axis_sizes(dims))], 1)
+    G = torch.randint(-8, 9, (5, 3, *dims), generator=g).float()
+    assert torch.equal(D.float().double(), D)
+    return SimpleNamespace(dims=tuple(dims), C=5, D=D.float().contiguous(), G=G)
+
+
+def dyadic_velocity_case(dims, no_steps, reach, seed=0):
+    """A velocity field v (len(reach),3,*dims) in VOXELS whose scaling-and-squaring chain of `no_steps` (1 or 2) steps is exact in
+    fp32: v = q * 2^no_steps with q = d_0 on the quarter-voxel lattice for one step and on the half-voxel lattice for two
+    ("Numerics note (exact cases)": why not finer, why not three steps).  reach[c] is chain c's: a number r (voxels, a
+    multiple of the lattice step) draws q white in [-r, r], r held with both signs at extreme_voxels; ('checker', r), r <= 1/2,
+    draws component c from {0, r (-1)^(index along c)}, 0 where that would point out of the volume.  Where such a component is not
+    0 its sample sits between two neighbours along c that are 0 or of opposite sign, |sample| <= r (1 - r); where it is 0 the sample
+    is one of the field's values or a mean of them along the other axes, at most r: max|d_1| <= max(r (2 - r), r) = 3/4 voxel
+    for r = 1/2 -- on the half-voxel lattice, where white noise of the smallest amplitude reaches |d_1| = 1, the way to keep a
+    chain's d_1 inside the radius-1 ring."""
+    assert no_steps in (1, 2) and all(((n - 1) & (n - 2)) == 0 for n in dims), 'every dim must be 2^k + 1'
+    step = 4 if no_steps == 1 else 2
+    g = torch.Generator().manual_seed(seed)
+    q = torch.empty(len(reach), 3, *dims, dtype=torch.float64)
+    for chain, r in enumerate(reach):
+        checker = isinstance(r, tuple)
+        a = (r[1] if checker else r) * step
+        assert a == int(a) and a >= 1, 'a reach is a multiple of the lattice step'
+        a = int(a)
+        if checker:
+            sign = torch.stack([(1.0 - 2.0 * (idx % 2)) * (idx + 1 - 2 * (idx % 2) <= n - 1)
+                                for idx, n in zip(_index_grids(dims), axis_sizes(dims))]).double()
+            q[chain] = torch.randint(0, 2, (3, *dims), generator=g).double() * sign * (a / step)
+        else:
+            q[chain] = torch.randint(-a, a + 1, (3, *dims), generator=g).double() / step
+            for (z, y, x), s in extreme_voxels(dims):
+                q[chain, :, z, y, x] = s * a / step
+    v = q * float(2 ** no_steps)
+    assert torch.equal(v.float().double(), v)
+    return SimpleNamespace(dims=tuple(dims), C=len(reach), no_steps=no_steps, v=v.float().contiguous())
+
+
 # ---- the cases the GPU tests run; tests/test_exact_cases_host.py proves fp32 == fp64 on each of them
+VELOCITY_CASES = {   # name -> (no_steps, reach per chain in voxels of d_0)
+    'one step': (1, (0.25, 0.75, 1, 3)),                          # max|d_0| 1/4, 3/4, 1, 3
+    'two steps': (2, (('checker', 0.5), 0.5, 1, 3)),              # max|d_1| < 1, in [1, 2), >= 2, >= 2; max|d_2| towards 12
+    'two steps, far': (2, (0.5, 6)),                              # max|d_2| towards 24 voxels
+    'engine': (2, (('checker', 0.5), 0.5, 3)),                    # max|d_1| < 1, in [1, 2), >= 2
+}
+
+
+def step_case(dims):
+    return dyadic_step_case(dims, seed=4000 + EXACT_DIMS.index(tuple(dims)))
+
+
+def velocity_case(dims, name):
+    no_steps, reach = VELOCITY_CASES[name]
+    return dyadic_velocity_case(dims, no_steps, reach, seed=5000 + 10 * EXACT_DIMS.index(tuple(dims)) + list(VELOCITY_CASES).index(name))
+
+
 WARP_CASES = [(dims, per_chain) for dims in EXACT_DIMS for per_chain in (False, True)]
 
 
@@ -141,6 +226,44 @@ def warp_reference(case, dtype, jitter=False, explicit=False):
     out = O.warp_trilinear(im, grid)
     gd, = torch.autograd.grad(out, d, gw)
     return out.detach(), gd, grid.detach()
+
+
+def step_reference(d, G, dtype, explicit=False):
+    """One squaring step d_out = d + sample(d, id + d) and its adjoint on a field d (C,3,*dims) in normalised units, in `dtype`:
+    -> (d_out, d(sum(d_out * G)) / d(d)).  Through ATen's grid_sample and autograd, or (explicit) restated with the oracle's own
+    sampler and its two adjoints, which share no arithmetic with ATen or the kernels: G itself, the trilinear scatter of G (the
+    gradient w.r.t. the sampled field) and the coordinate gradient (w.r.t. the sampling grid), which _unnormalise_clip switches
+    off unless the coordinate is strictly inside the volume."""
+    dims = tuple(d.shape[2:])
+    d, G = d.to(dtype), G.to(dtype)
+    if explicit:
+        g5 = (identity(dims, dtype) + d).permute(0, 2, 3, 4, 1)
+        out = d + O.trilinear_sample_explicit(d, g5)
+        g_field, g_grid = O.trilinear_backward_explicit(d, g5, G)
+        return out, G + g_field + g_grid.permute(0, 4, 1, 2, 3)
+    d = d.clone().requires_grad_(True)
+    out = d + O.warp_trilinear(d, identity(dims, dtype) + d)
+    gd, = torch.autograd.grad(out, d, G)
+    return out.detach(), gd
+
+
+def chain_reference(v, no_steps, dtype, g_last=None):
+    """O.svf_exp of a velocity field in voxels, in `dtype`: -> (transformation, displacement, [d_0 .. d_n], grad_v or None), grad_v
+    = d(sum(d_n * g_last)) / d(v) by autograd"""
+    v = v.to(dtype).clone().requires_grad_(g_last is not None)
+    t, disp, steps = O.svf_exp(v, no_steps, keep_steps=True)
+    gv = None
+    if g_last is not None:
+        gv, = torch.autograd.grad(steps[-1], v, g_last.to(dtype))
+    return t.detach(), disp.detach(), [s.detach() for s in steps], gv
+
+
+def step_widths(d):
+    """floor(max|d|) + 1 per chain of a field (C,3,*dims) in normalised units, |d| in voxels and the maximum over the three axes:
+    what the device decides the kernel of a step by (1: radius-1 ring / gather, 2: radius-2, 3 and more: global-memory taps /
+    the any-radius adjoint)"""
+    vox = O.to_voxels(d.double()).abs().flatten(1).max(1).values
+    return [int(m) + 1 for m in vox.tolist()]
 
 
 def nearest_reference(seg, transformation, dtype):

@@ -103,6 +103,174 @@ def test_transformation_case_is_exact_and_folds_differently_per_chain(dims):
         assert int((det64 == 0).sum()) >= 10   # det J == 0: log gives -inf, which is no fold
 
 
+# ---------------------------------------------------------------- squaring steps
+def _step_grid(case):
+    return X.identity(case.dims, torch.float64) + case.D.double()
+
+
+@pytest.mark.parametrize('dims', X.EXACT_DIMS)
+def test_step_case_is_exact_in_fp32(dims):
+    """one step and its adjoint: fp32 == fp64 bit for bit through ATen and through the explicit restatement, which agree in fp64"""
+    case = X.step_case(dims)
+    assert case.D.shape == case.G.shape == (5, 3, *dims) and case.D.dtype == torch.float32
+    assert torch.equal(case.G, case.G.round()) and float(case.G.abs().max()) == 8.0
+    quarter = X.O.to_voxels(case.D.double()) * 4.0
+    assert torch.equal(quarter, quarter.round())
+    out64, gd64 = X.step_reference(case.D, case.G, torch.float64)
+    for explicit in (False, True):
+        out32, gd32 = X.step_reference(case.D, case.G, torch.float32, explicit)
+        assert same_bits(out32, out64), ('step', explicit)
+        assert same_bits(gd32, gd64), ('adjoint', explicit)
+    oute, gde = X.step_reference(case.D, case.G, torch.float64, explicit=True)
+    assert torch.equal(oute, out64) and torch.equal(gde, gd64)
+    # what the stateless adjoint returns for this case (tests/test_gpu_exp_exact.py, b and c): the adjoint over n_c - 1, a power of two
+    gv64 = X.chain_reference(2.0 * X.O.to_voxels(case.D), 1, torch.float64, case.G)[3]
+    gv32 = X.chain_reference(2.0 * X.O.to_voxels(case.D), 1, torch.float32, case.G)[3]
+    scale = torch.tensor([1.0 / (n - 1) for n in X.axis_sizes(dims)], dtype=torch.float64).view(1, 3, 1, 1, 1)
+    assert same_bits(gv32, gv64) and torch.equal(gv64, gd64 * scale)
+    for c in range(5):   # every chain's gradient differs from its upstream gradient and from the other chains'
+        assert not torch.equal(gd64[c], case.G[c].double())
+
+
+@pytest.mark.parametrize('dims', X.EXACT_DIMS)
+def test_step_case_holds_its_amplitude_classes_and_the_hard_positions(dims):
+    """floor(max|d|) + 1 = 1, 2, 2, 3 and more than 3: the radius-1 gather, the radius-2 gather twice (at exactly one voxel and
+    below two), the any-radius kernel twice (at exactly two voxels and far beyond).  The four class shares are asked of every
+    case, (2, 3, 5) included, pooled over the five chains and the three axes.  Asked per axis as well: the extremes, and the
+    share of interior voxel centres -- from which the z axis of (2, 3, 5) is exempt, n = 2 has no interior centre.  Asked per
+    chain as well: a coordinate on each border, below and above the volume -- from which (2, 3, 5) is exempt, 30 voxels a chain
+    do not hold all four on every axis whatever the draw; there the five chains are taken together."""
+    case = X.step_case(dims)
+    widths = X.step_widths(case.D)
+    assert tuple(widths[:4]) == X.STEP_WIDTHS and widths[4] > 3, widths
+    vox = X.O.to_voxels(case.D.double())
+    for chain, a in enumerate(X.STEP_REACH):
+        assert float(vox[chain].abs().max()) == a / 4.0
+        for (z, y, x), sign in X.extreme_voxels(dims):
+            assert vox[chain, :, z, y, x].tolist() == [sign * a / 4.0] * 3
+    D, H, W = dims
+    (far, _), (_, _), (face, _), (row, _) = X.extreme_voxels(dims)
+    assert far[2] // 32 == (W - 1) // 32 and (W % 32 == 1 or W < 32) and far[1] // 8 == (H - 1) // 8 and (H % 8 == 1 or H < 8)   # ragged last tile
+    assert face[2] == 0 and row[1] == H - 1
+    grid = _step_grid(case)
+    share = X.coordinate_classes(grid, dims)
+    for k in ('border', 'below', 'above', 'centre'):
+        assert share[k] >= MIN_SHARE, (k, share)
+    for c, (raw, n) in enumerate(zip(X.voxel_coordinates(grid, dims), X.axis_sizes(dims))):
+        assert float(raw.min()) == -3.0 and float(raw.max()) == n - 1 + 3.0
+        # every chain: coordinates exactly on both borders, below and above the volume ((2, 3, 5) has 30 voxels: the five together)
+        for r in (raw if raw[0].numel() > 1000 else [raw]):
+            assert int((r == 0).sum()) > 0 and int((r == n - 1).sum()) > 0 and int((r < 0).sum()) > 0 and int((r > n - 1).sum()) > 0, c
+        if n > 2:
+            inside = (raw > 0) & (raw < n - 1)
+            assert int((inside & (raw == raw.floor())).sum()) >= MIN_SHARE * raw.numel(), c
+    assert len({case.D[c].abs().sum().item() for c in range(5)}) == 5
+
+
+@pytest.mark.parametrize('dims', X.EXACT_DIMS)
+def test_the_adjoint_of_a_step_at_zero_doubles_its_input(dims):
+    """d = 0: the sample is the field itself and its coordinate gradient vanishes, so the adjoint is G + G (what makes step 0 of the
+    injected two-step call of tests/test_gpu_exp_exact.py an exact factor)"""
+    case = X.step_case(dims)
+    zero = torch.zeros_like(case.D)
+    for dtype in (torch.float32, torch.float64):
+        for explicit in (False, True):
+            out, gd = X.step_reference(zero, case.G, dtype, explicit)
+            assert torch.equal(gd, 2.0 * case.G.to(dtype)) and torch.equal(out, zero.to(dtype))
+
+
+@pytest.mark.parametrize('dims', X.EXACT_DIMS)
+def test_a_restatement_with_another_border_rule_is_noticed(dims, monkeypatch):
+    """the coordinate gradient left ON at i = 0 and i = n - 1 (`<=` for `<`): the cases hold enough coordinates exactly on a border,
+    next to values that differ, for the adjoint to come out different in every chain"""
+    case = X.step_case(dims)
+    _, right = X.step_reference(case.D, case.G, torch.float64, explicit=True)
+
+    def closed(g, size):
+        i = ((g + 1.0) / 2.0) * (size - 1)
+        return i.clamp(0, size - 1), ((i >= 0) & (i <= size - 1)).to(g.dtype) * ((size - 1) / 2.0)
+    monkeypatch.setattr(X.O, '_unnormalise_clip', closed)
+    out, wrong = X.step_reference(case.D, case.G, torch.float64, explicit=True)
+    assert torch.equal(out, X.step_reference(case.D, case.G, torch.float64)[0])   # the forward step does not see the rule
+    for chain in range(5):
+        assert not torch.equal(wrong[chain], right[chain]), chain
+    # ... and only where a coordinate is exactly on a border
+    raw = X.voxel_coordinates(_step_grid(case), dims)
+    on_border = torch.stack([(r == 0) | (r == n - 1) for r, n in zip(raw, X.axis_sizes(dims))], 1)
+    assert int(((wrong != right) & ~on_border).sum()) == 0 and int((wrong != right).sum()) > 0
+
+
+VELOCITY = [(dims, name) for dims in X.EXACT_DIMS for name in X.VELOCITY_CASES]
+
+
+@pytest.mark.parametrize('dims,name', VELOCITY)
+def test_velocity_case_is_exact_in_fp32(dims, name):
+    """every field of the chain, the transformation and the displacement: fp32 == fp64 bit for bit; one step: grad_v too (of two
+    steps it is not exact, DESIGN.md "Numerics note (exact cases)", and is not asked for)"""
+    case = X.velocity_case(dims, name)
+    n = case.no_steps
+    lattice = case.v.double() / 2 ** n * (4 if n == 1 else 2)
+    assert torch.equal(lattice, lattice.round()) and case.v.shape == (case.C, 3, *dims)
+    g_last = X.step_case(dims).G[:case.C] if n == 1 else None
+    t32, u32, s32, gv32 = X.chain_reference(case.v, n, torch.float32, g_last)
+    t64, u64, s64, gv64 = X.chain_reference(case.v, n, torch.float64, g_last)
+    assert len(s64) == n + 1 and same_bits(t32, t64) and same_bits(u32, u64)
+    for a, b in zip(s32, s64):
+        assert same_bits(a, b)
+    assert torch.equal(X.O.to_voxels(s64[0]), case.v.double() / 2 ** n)
+    if n == 1:
+        assert same_bits(gv32, gv64)
+    # the restated step gives the same chain
+    d = s64[0]
+    for k in range(n):
+        d, _ = X.step_reference(d, torch.zeros_like(d), torch.float64, explicit=True)
+        assert torch.equal(d, s64[k + 1]), k
+    for a in range(case.C):
+        for b in range(a + 1, case.C):
+            assert not torch.equal(case.v[a], case.v[b])
+
+
+def _below_one(w):
+    return w == 1
+
+
+def _one_to_two(w):
+    return w == 2
+
+
+def _two_or_more(w):
+    return w >= 3
+
+
+# floor(max|d_k|) + 1 per chain, for k = 0 .. no_steps - 1 (the fields a step READS): what each case was built to select
+VELOCITY_WIDTHS = {
+    'one step': [[_below_one, _below_one, _one_to_two, _two_or_more]],
+    'two steps': [[_below_one, _below_one, _one_to_two, _two_or_more], [_below_one, _one_to_two, _two_or_more, _two_or_more]],
+    'two steps, far': [[_below_one, _two_or_more], [_one_to_two, _two_or_more]],
+    'engine': [[_below_one, _below_one, _two_or_more], [_below_one, _one_to_two, _two_or_more]],
+}
+
+
+@pytest.mark.parametrize('dims,name', VELOCITY)
+def test_velocity_case_puts_its_chains_on_both_sides_of_one_and_two_voxels(dims, name):
+    case = X.velocity_case(dims, name)
+    _, _, steps, _ = X.chain_reference(case.v, case.no_steps, torch.float64)
+    for k, classes in enumerate(VELOCITY_WIDTHS[name]):
+        widths = X.step_widths(steps[k])
+        assert all(ok(w) for ok, w in zip(classes, widths)), (k, widths)
+    if name == 'two steps, far' and min(dims) > 5:
+        assert X.step_widths(steps[2])[1] > 12, X.step_widths(steps[2])   # the last field reaches far out of any ring
+
+
+@pytest.mark.parametrize('n', [2, 3, 5, 6, 128, 130, 132])
+def test_the_identity_table_is_one_rounding_from_linspace(n):
+    """fp32 linspace(-1, 1, n) as torch's CPU kernel evaluates it (csrc/field_kernels.hip: fill_linspace repeats it) against the
+    float64 one: a rounded step, a rounded product and a rounded sum, yet within 2^-24 -- the rounding of one fp32 operation on
+    values up to 2 -- at the sizes of test_outputs_kernel_rounds_once_per_operation, whose bound starts from that"""
+    err = (torch.linspace(-1, 1, n).double() - torch.linspace(-1, 1, n, dtype=torch.float64)).abs()
+    assert float(err.max()) <= 2.0 ** -24
+
+
 # ---------------------------------------------------------------- Philox restatement
 @pytest.mark.parametrize('ctr,key,expect', [((0, 0), 0, (0xff1dae59, 0x6cd10df2)),
                                             ((0xffffffff, 0xffffffff), 0xffffffff, (0x2c3f628b, 0xab4fd7ad)),
