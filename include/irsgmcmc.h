@@ -66,7 +66,11 @@ int irs_svf_exp_bwd(const float* v, const float* steps, const float* g_last, flo
                     int C, int D, int H, int W, void* stream);
 
 /* Cubic_B_spline_FFD_3D.forward (utils/transformation.py:126-153) and its adjoint.
- * v_cp: (C,3,G0,G1,G2), G = ceil((N-1)/cps)+3; dense: (C,3,D,H,W); tmp: 2 x (C,3,D,H,W) scratch. */
+ * v_cp: (C,3,G0,G1,G2), G = ceil((N-1)/cps)+3; dense: (C,3,D,H,W); c0, c1, c2: control-point spacing of D, H, W, 1..8.
+ * tmp: scratch of irs_ffd_scratch_floats(C, D, H, W, c0, c1, c2) floats, the same for both directions: the two intermediates
+ * (C,3,D,G1,G2) and (C,3,D,H,G2).  With cps = 1, or a volume of a few voxels, that is more than 2 x (C,3,D,H,W).
+ * irs_ffd_scratch_floats returns 0 for arguments that irs_ffd_up / irs_ffd_adjoint refuse. */
+size_t irs_ffd_scratch_floats(int C, int D, int H, int W, int c0, int c1, int c2);
 int irs_ffd_up(const float* v_cp, float* dense, float* tmp, int C, int D, int H, int W, int c0, int c1, int c2,
                void* stream);
 int irs_ffd_adjoint(const float* g_dense, float* g_cp, float* tmp, int C, int D, int H, int W, int c0, int c1, int c2,

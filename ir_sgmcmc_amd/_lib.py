@@ -148,6 +148,7 @@ SIGNATURES = {
     'irs_perturb_smooth': [_P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P, _P, _U64, _U64, _P],
     'irs_svf_exp_fwd': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     'irs_svf_exp_bwd': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    'irs_ffd_scratch_floats': [_I, _I, _I, _I, _I, _I, _I],
     'irs_ffd_up': [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     'irs_ffd_adjoint': [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     'irs_warp_fwd': [_P, _I, _P, _P, _F, _P, _I, _I, _I, _I, _U64, _U64, _P],
@@ -271,8 +272,8 @@ SIGNATURES = {
     'irs_last_error': [],
     'irs_version': [],
 }
-_RESTYPES = {'irs_reduce_scratch_doubles': C.c_size_t, 'irs_workspace_bytes': C.c_size_t, 'irs_destroy': None,
-             'irs_comm_destroy': None,
+_RESTYPES = {'irs_reduce_scratch_doubles': C.c_size_t, 'irs_ffd_scratch_floats': C.c_size_t, 'irs_workspace_bytes': C.c_size_t,
+             'irs_destroy': None, 'irs_comm_destroy': None,
              'irs_last_error': C.c_char_p, 'irs_version': C.c_char_p}
 
 _lib = None

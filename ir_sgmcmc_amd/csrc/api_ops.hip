@@ -191,9 +191,20 @@ int irs_svf_exp_bwd(const float* v, const float* steps, const float* g_last, flo
     return 0;
 }
 
+static bool ffd_args_ok(int C, int D, int H, int W, int c0, int c1, int c2) {
+    return dims_ok(C, D, H, W) && c0 >= 1 && c1 >= 1 && c2 >= 1 && c0 <= 8 && c1 <= 8 && c2 <= 8;
+}
+
+// the two intermediates of ffd_up / ffd_adjoint above: (C,3,D,G1,G2) and (C,3,D,H,G2), in either direction
+size_t irs_ffd_scratch_floats(int C, int D, int H, int W, int c0, int c1, int c2) {
+    if (!ffd_args_ok(C, D, H, W, c0, c1, c2)) return 0;
+    const size_t G1 = (size_t)control_points(H, c1), G2 = (size_t)control_points(W, c2);
+    return (size_t)C * 3 * (size_t)D * (G1 * G2 + (size_t)H * G2);
+}
+
 int irs_ffd_up(const float* v_cp, float* dense, float* tmp, int C, int D, int H, int W, int c0, int c1, int c2,
                void* stream) {
-    if (!v_cp || !dense || !tmp || !dims_ok(C, D, H, W) || c0 < 1 || c1 < 1 || c2 < 1 || c0 > 8 || c1 > 8 || c2 > 8)
+    if (!v_cp || !dense || !tmp || !ffd_args_ok(C, D, H, W, c0, c1, c2))
         return fail("irs_ffd_up: bad arguments");
     const Vol vol = make_vol(D, H, W);
     const int G[3] = {control_points(D, c0), control_points(H, c1), control_points(W, c2)};
@@ -205,7 +216,7 @@ int irs_ffd_up(const float* v_cp, float* dense, float* tmp, int C, int D, int H,
 
 int irs_ffd_adjoint(const float* g_dense, float* g_cp, float* tmp, int C, int D, int H, int W, int c0, int c1, int c2,
                     void* stream) {
-    if (!g_dense || !g_cp || !tmp || !dims_ok(C, D, H, W) || c0 < 1 || c1 < 1 || c2 < 1 || c0 > 8 || c1 > 8 || c2 > 8)
+    if (!g_dense || !g_cp || !tmp || !ffd_args_ok(C, D, H, W, c0, c1, c2))
         return fail("irs_ffd_adjoint: bad arguments");
     const Vol vol = make_vol(D, H, W);
     const int G[3] = {control_points(D, c0), control_points(H, c1), control_points(W, c2)};

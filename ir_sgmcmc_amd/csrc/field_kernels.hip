@@ -302,7 +302,7 @@ void launch_warp_nearest_i16(const int16_t* im, int64_t im_stride, const float* 
 
 // ------------------------------------------------------------------------------------------------
 // cubic B-spline FFD, one axis.  Arrays are viewed as [outer][n][inner].
-//   up      : out[o][x][i] = sum_j in[o][j][i] * k[x + 3c - 1 - j c],   j = floor(x/c) .. floor(x/c)+3
+//   up      : out[o][x][i] = sum_j in[o][j][i] * k[x + 3c - 1 - j c],   j = floor(x/c) .. floor(x/c)+3, taps 0 .. 4c-2 only
 //   adjoint : out[o][j][i] = sum_x in[o][x][i] * k[x + 3c - 1 - j c],   x = (j-3)c+1 .. (j+1)c-1
 // which is conv_transpose1d(stride c, padding 2c-1) followed by the crop [c : c+N] of
 // utils/transformation.py:146-153, and its transpose.
@@ -328,8 +328,8 @@ __global__ __launch_bounds__(kBlock) void ffd_axis_kernel(const float* __restric
         const int j0 = p / c;
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
-            const int j = j0 + jj;
-            if (j < n_in) acc = fmaf(src[(int64_t)j * inner], taps.k[p + 3 * c - 1 - j * c], acc);
+            const int j = j0 + jj, tap = p + 3 * c - 1 - j * c;  // tap = -1 at jj = 3 of a row with p % c == 0: past the support
+            if (j < n_in && tap >= 0) acc = fmaf(src[(int64_t)j * inner], taps.k[tap], acc);
         }
         out[(o * store_n + (p - store_lo)) * inner + i] = acc;
     } else {

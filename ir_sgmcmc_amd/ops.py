@@ -175,6 +175,14 @@ def svf_exp_bwd(v, steps, g_last):
     return g_v
 
 
+def _ffd_scratch(Cn, D, H, W, cps, device):
+    """the scratch of irs_ffd_up / irs_ffd_adjoint, sized by irs_ffd_scratch_floats (0: arguments the operators refuse)"""
+    floats = L.load().irs_ffd_scratch_floats(Cn, D, H, W, *cps)
+    if floats == 0:
+        raise L.IrsError(f'ffd: dims {(D, H, W)} x {Cn} chains / cps {tuple(cps)} are refused (every extent >= 2, spacings 1..8)')
+    return torch.empty(floats, device=device, dtype=torch.float32)
+
+
 def ffd_up(v_cp, dims, cps):
     """Cubic_B_spline_FFD_3D.forward (utils/transformation.py:146-153)."""
     Cn = v_cp.shape[0]
@@ -182,7 +190,7 @@ def ffd_up(v_cp, dims, cps):
     if tuple(v_cp.shape[2:]) != control_grid_size(dims, cps):
         raise L.IrsError(f'control grid {tuple(v_cp.shape[2:])} does not match dims {dims} / cps {cps}')
     dense = torch.empty((Cn, 3, D, H, W), device=v_cp.device, dtype=torch.float32)
-    tmp = torch.empty((2, Cn, 3, D, H, W), device=v_cp.device, dtype=torch.float32)
+    tmp = _ffd_scratch(Cn, D, H, W, cps, v_cp.device)
     _call('irs_ffd_up', L.dev_ptr(v_cp, torch.float32), L.dev_ptr(dense), L.dev_ptr(tmp), Cn, D, H, W, *cps)
     return dense
 
@@ -191,7 +199,7 @@ def ffd_adjoint(g_dense, cps):
     Cn, D, H, W = _dims5(g_dense, 3)
     G = control_grid_size((D, H, W), cps)
     g_cp = torch.empty((Cn, 3, *G), device=g_dense.device, dtype=torch.float32)
-    tmp = torch.empty((2, Cn, 3, D, H, W), device=g_dense.device, dtype=torch.float32)
+    tmp = _ffd_scratch(Cn, D, H, W, cps, g_dense.device)
     _call('irs_ffd_adjoint', L.dev_ptr(g_dense.contiguous(), torch.float32), L.dev_ptr(g_cp), L.dev_ptr(tmp), Cn, D, H, W, *cps)
     return g_cp
 

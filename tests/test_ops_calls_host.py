@@ -7,7 +7,8 @@ argument (ints and floats by value, ctypes arrays by their contents, pointer tok
 full message of what it raises.  The stand-in also holds every call to `_lib.SIGNATURES`: the number of arguments and, through
 each ctypes type's own from_param, what kind of value stands where.
 
-The expectations are data: tests/golden/ops_calls.json, recorded from the ops.py of the commit before its helpers were folded.
+The expectations are data: tests/golden/ops_calls.json, recorded from the ops.py of the commit before its helpers were folded
+(ffd_up/plain, ffd_adjoint/plain and ffd_adjoint/strided again since: their scratch is sized by irs_ffd_scratch_floats).
 `IRS_RECORD_OPS_CALLS=1 python -m pytest tests/test_ops_calls_host.py` writes the file anew; a change of ops.py that is meant
 to leave its behaviour alone does not need to.
 """
@@ -98,6 +99,8 @@ class Recorder:
             self.calls.append({'fn': name, 'args': [self.argument(name, i, args) for i in range(len(args))]})
             if name.endswith('_workspace'):
                 args[-1]._obj.value = WS_BYTES
+            if name == 'irs_ffd_scratch_floats':  # a size by value: the scratch the next call takes shows it
+                return WS_BYTES // 4
             if name == 'irs_label_boxes':  # the boxes a later call reads back through its host pointer
                 args[5].tensor.copy_(torch.arange(args[5].tensor.numel()).reshape(args[5].tensor.shape))
             return 0
