@@ -478,6 +478,31 @@ int irs_native_warp(const float* displacement, int C, const int32_t* dims, const
                     const float* im, const int16_t* seg, const uint8_t* mask, int Cim, float fill, const float* scale,
                     float* im_out, int16_t* seg_out, uint8_t* mask_out, float* displacement_out, void* stream);
 
+/* Native-grid posteriors (absent in the reference): the posterior label maps and the image posterior above, accumulated on the
+ * image's own voxel grid in one fused launch per recorded step -- up-sample, warp and fold, with no warped volume in between.
+ * The geometry (dims, native, padding), displacement, im, seg, Cim and fill are irs_native_warp's, with every n_a >= 2 in
+ * addition (the finalizers need it).  Per chain c = 0 .. C-1, in order, and per native voxel the source position is formed once;
+ *  - labels: the label is the value irs_native_warp writes to seg_out (nearest, half to even, 0 outside the native box);
+ *    structure j is label value labels[j] as in irs_label_posterior_update (HOST int32, K in 1 .. IRS_MAX_LABELS, distinct, in
+ *    the int16 range; every other value is "other").  counts (K,n0,n1,n2) int32, += 1 where the record carries the structure;
+ *    volume (K,2) double {mean, M2}: Welford state of the per-record volumes (native voxels carrying the structure), folded with
+ *    k = records_before + c + 1 (k = 1 overwrites it) -- the semantics of irs_label_posterior_update.
+ *  - image: the sample x is bit for bit the value irs_native_warp writes to im_out.  mean, m2, low, high (n0,n1,n2) float32,
+ *    updated in place with the recurrence of irs_image_posterior_update, k = records_before + c + 1: d = x - mean,
+ *    mean += d / (float)k, m2 += d * (x - mean), low = fminf(low, x), high = fmaxf(high, x), every operation rounded to nearest
+ *    on its own (no fused multiply-add); k = 1 overwrites the state (mean = low = high = x, m2 = 0), which is then never read.
+ *  seg, labels, counts and volume are all given or all NULL, and so are im, mean, m2, low and high; at least one group must be
+ *  given.  records_before >= 0, records_before + C <= INT32_MAX.  fill: finite.  ws: device workspace of
+ *  irs_native_posterior_workspace bytes (K = 0 without the labels; never 0 bytes).  A thread owns a voxel: plain read-modify-
+ *  writes, the state of the image in registers over the chains; exact integer sums in fixed order; two identical call sequences
+ *  give identical bits; no host sync.  Both states go to irs_label_posterior_finalize / irs_image_posterior_finalize as they
+ *  are, with (D,H,W) = native. */
+int irs_native_posterior_workspace(int C, int K, const int32_t* native, size_t* bytes);
+int irs_native_posterior_update(const float* displacement, int C, const int32_t* dims, const int32_t* native, const int32_t* padding,
+                                const float* im, const int16_t* seg, int Cim, float fill, const int32_t* labels, int K,
+                                int32_t* counts, double* volume, float* mean, float* m2, float* low, float* high,
+                                int records_before, void* ws, size_t ws_bytes, void* stream);
+
 /* Intensity similarity (absent in the reference, which reports only its loss terms and segmentation metrics): per chain the
  * joint intensity histogram of the fixed image and a (warped) moving image and, from ONE pass over the two volumes, MSE, the
  * global normalised cross-correlation, mutual information and normalised mutual information.

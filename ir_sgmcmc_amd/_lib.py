@@ -199,6 +199,9 @@ SIGNATURES = {
     'irs_inverse_consistency_update': [_P, _I, _I, _I, _I, _P, _P, _I, _P],
     'irs_inverse_consistency_finalize': [_P, _P, _I, _I, _I, _P, _F, _P, _P, _P, C.c_size_t, _P],
     'irs_native_warp': [_P, _I, _I32P, _I32P, _I32P, _P, _P, _P, _I, _F, C.POINTER(C.c_float), _P, _P, _P, _P, _P],
+    'irs_native_posterior_workspace': [_I, _I, _I32P, C.POINTER(C.c_size_t)],
+    'irs_native_posterior_update': [_P, _I, _I32P, _I32P, _I32P, _P, _P, _I, _F, _I32P, _I, _P, _P, _P, _P, _P, _P, _I, _P, C.c_size_t,
+                                    _P],
     'irs_image_similarity_workspace': [_I, _I, C.POINTER(C.c_size_t)],
     'irs_image_similarity': [_P, _I, _P, _I, _P, _I, _I, _I, _F, _F, _F, _F, _I, _P, _P, _P, C.c_size_t, _P],
     'irs_transform_points': [_P, _I, _P, _I, _I, _I, _I, C.POINTER(C.c_float), _P, _P, _P, _P],

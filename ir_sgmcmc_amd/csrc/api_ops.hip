@@ -1039,6 +1039,51 @@ int irs_native_warp_cubic(const float* displacement, int C, const int32_t* dims,
 }
 
 // ================================================================================================
+// native-grid posteriors (native_posterior_kernels.hip)
+// ================================================================================================
+static size_t native_posterior_ws(int C, int K, const NativeGeom& gm) {
+    return sizeof(int32_t) * (size_t)C * K * native_posterior_blocks(gm);
+}
+
+int irs_native_posterior_workspace(int C, int K, const int32_t* native, size_t* bytes) {
+    if (!bytes || !native || !chain_count_ok(C) || K < 0 || K > IRS_MAX_LABELS || native[0] < 2 || native[1] < 2 || native[2] < 2)
+        return fail("irs_native_posterior_workspace: bad arguments");
+    NativeGeom gm = {};
+    for (int a = 0; a < 3; ++a) gm.n[a] = native[a];
+    *bytes = std::max<size_t>(native_posterior_ws(C, K, gm), 16);  // never empty: a caller without labels still allocates it
+    return 0;
+}
+
+int irs_native_posterior_update(const float* displacement, int C, const int32_t* dims, const int32_t* native, const int32_t* padding,
+                                const float* im, const int16_t* seg, int Cim, float fill, const int32_t* labels, int K,
+                                int32_t* counts, double* volume, float* mean, float* m2, float* low, float* high,
+                                int records_before, void* ws, size_t ws_bytes, void* stream) {
+    if (!displacement || !dims || !native || !padding || !ws) return fail("irs_native_posterior_update: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!broadcast_ok(Cim, C)) return fail("irs_native_posterior_update: moving volumes of %d chains, 1 or %d needed", Cim, C);
+    const int lab_given = !!seg + !!labels + !!counts + !!volume, im_given = !!im + !!mean + !!m2 + !!low + !!high;
+    if (lab_given != 0 && lab_given != 4)
+        return fail("irs_native_posterior_update: seg, labels, counts and volume go together, %d of them given", lab_given);
+    if (im_given != 0 && im_given != 5)
+        return fail("irs_native_posterior_update: im, mean, m2, low and high go together, %d of them given", im_given);
+    if (!lab_given && !im_given) return fail("irs_native_posterior_update: neither the label nor the image part is given");
+    NativeGeom gm;
+    int64_t voxels;
+    if (!native_geometry_ok(__func__, C, dims, native, padding, 2, gm, voxels)) return 1;
+    if (!records_ok(__func__, records_before, C, INT32_MAX, "overflow the int32 record count")) return 1;
+    if (lab_given && !distinct_labels_ok(__func__, labels, K)) return 1;
+    if (!isfinite(fill)) return fail("irs_native_posterior_update: fill = %g, a finite value needed", (double)fill);
+    gm.fill = fill;
+    const size_t need = lab_given ? native_posterior_ws(C, K, gm) : 0;
+    if (!workspace_ok(__func__, ws_bytes, need, "irs_native_posterior_workspace")) return 1;
+    launch_native_posterior_update(displacement, im, seg, Cim == 1 ? 0 : voxels, lab_given ? surf_labels(labels, K) : SurfLabels{},
+                                   lab_given ? K : 0, counts, volume, (int32_t*)ws, mean, m2, low, high, records_before, gm, C,
+                                   (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // landmark propagation (landmark_kernels.hip)
 // ================================================================================================
 static bool landmark_count_ok(int K) { return K >= 1 && K <= IRS_LANDMARK_MAX_POINTS; }

@@ -280,6 +280,8 @@ void launch_split_ess(const float* mean, const float* m2, const float* vsum, int
 int label_update_partials_blocks(int64_t V);
 void launch_label_update(const int16_t* seg, int C, int64_t V, const SurfLabels& lab, int K, int32_t* counts, double* volume,
                          int records_before, int32_t* partials, hipStream_t st);
+// the second half of the update alone: nblocks rows of C * K int32 block partials summed in block order, then folded into volume
+void launch_label_volume_fold(const int32_t* partials, int nblocks, int C, int K, double* volume, int records_before, hipStream_t st);
 // entropy (V) float32, map_label (V) int16, summary (K, 6 + 3 * IRS_LABEL_BINS) int64, mask_summary 4 doubles;
 // partials: K * (6 + 3 * IRS_LABEL_BINS) int64 and dpartials: 4 doubles per block (label_finalize_blocks(V) blocks)
 int label_finalize_blocks(int64_t V);
@@ -373,6 +375,16 @@ struct NativeGeom {
 void launch_native_warp(const float* u, const float* im, const int16_t* seg, const uint8_t* mask, int64_t moving_stride,
                         float* im_out, int16_t* seg_out, uint8_t* mask_out, float* disp_out, const NativeGeom& gm, int C,
                         hipStream_t st);
+
+// ---- native_posterior_kernels.hip: the label and image posteriors on the image's own voxel grid (absent in the reference)
+// u (C,3,m) float32; im float32 / seg int16: (1 or C, n) with moving_stride 0 or n0 n1 n2.  seg, counts (K,n) int32, volume (K,2)
+// double and partials (C * K int32 per block, native_posterior_blocks(gm) blocks) go together or are all nullptr; so do im and
+// mean / m2 / low / high (n) float32; at least one of the two groups.  The C samples are folded in chain order after
+// `records_before` records (0 overwrites the image state); gm.fill is what the pad of the image holds
+int native_posterior_blocks(const NativeGeom& gm);
+void launch_native_posterior_update(const float* u, const float* im, const int16_t* seg, int64_t moving_stride, const SurfLabels& lab,
+                                    int K, int32_t* counts, double* volume, int32_t* partials, float* mean, float* m2, float* low,
+                                    float* high, int records_before, const NativeGeom& gm, int C, hipStream_t st);
 
 // ---- similarity_kernels.hip: joint intensity histogram, MI / NMI, MSE and NCC of two images (absent in the reference)
 struct SimBins {

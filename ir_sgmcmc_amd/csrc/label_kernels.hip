@@ -14,33 +14,13 @@
 //    sequences are bit-identical.
 #include <algorithm>
 
-#include "kernels.h"
+#include "label_device.h"
 
 namespace irs {
 namespace {
 
 constexpr int kLabelMaxBlocks = 1024;  // 256 CUs x 4 blocks of 4 wavefronts
 constexpr int kLabelCols = 6 + 3 * IRS_LABEL_BINS;  // S0 .. S5, then per bin: pairs, sum of c, sum of y
-
-__device__ __forceinline__ int structure_of(int x, const SurfLabels& lab, int K) {
-    int idx = -1;  // labels are distinct: at most one matches
-    for (int j = 0; j < K; ++j) idx = lab.v[j] == x ? j : idx;
-    return idx;
-}
-
-// cnt[j] += number of lanes holding j, for every j >= 0 held in the wavefront: one LDS add per distinct value (a single
-// address hit by all 64 lanes would serialise)
-__device__ __forceinline__ void wave_count(int j, int* cnt) {
-    unsigned long long todo = __ballot(j >= 0);
-    const int lane = threadIdx.x & (kWave - 1);
-    while (todo) {
-        const int leader = __ffsll((unsigned long long)todo) - 1;
-        const int jl = __shfl(j, leader, kWave);
-        const unsigned long long m = __ballot(j == jl);
-        if (lane == leader) atomicAdd(&cnt[jl], __popcll(m));
-        todo &= ~m;
-    }
-}
 
 __device__ __forceinline__ void count_one(int32_t* __restrict__ counts, int j, int64_t V, int64_t v) {
     if (j >= 0) counts[(int64_t)j * V + v] += 1;
@@ -294,7 +274,11 @@ void launch_label_update(const int16_t* seg, int C, int64_t V, const SurfLabels&
         hipLaunchKernelGGL(label_update_kernel<true>, dim3(blocks), dim3(kBlock), 0, st, seg, C, V, lab, K, counts, partials);
     else
         hipLaunchKernelGGL(label_update_kernel<false>, dim3(blocks), dim3(kBlock), 0, st, seg, C, V, lab, K, counts, partials);
-    hipLaunchKernelGGL(label_volume_fold_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, C, K, volume, records_before);
+    launch_label_volume_fold(partials, blocks, C, K, volume, records_before, st);
+}
+
+void launch_label_volume_fold(const int32_t* partials, int nblocks, int C, int K, double* volume, int records_before, hipStream_t st) {
+    hipLaunchKernelGGL(label_volume_fold_kernel, dim3(1), dim3(kBlock), 0, st, partials, nblocks, C, K, volume, records_before);
 }
 
 void launch_label_finalize(const int32_t* counts, int K, int64_t V, int n, const SurfLabels& lab, const int16_t* seg_fixed,

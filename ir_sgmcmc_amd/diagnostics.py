@@ -79,6 +79,12 @@ transformation and folded into a per-voxel Welford mean / M2, minimum and maximu
 (image_posterior.image_posterior_update), 16 * S * D * H * W bytes whatever the number of records; at the end
 image_posterior.image_posterior_finalize gives the std and range maps and, for the moving image, the misfit of its posterior mean
 against the fixed image in units of the spread the registration uncertainty explains.
+
+The native posterior (NativePosterior, native_posterior_options) puts the label and the image posterior where a user opens them,
+on the image's own voxel grid: at a recorded step every chain's displacement is carried to the native grid and the nearest label
+and the trilinear sample of the native moving volumes are folded in one fused launch that forms no warped volume
+(native_posterior.native_posterior_update), 4 K + 16 bytes per native voxel whatever the number of records; the finalizers of the
+label and the image posterior then run on the native extents, with the volumes in mm^3 under the header zooms.
 """
 import math
 import numbers
@@ -1839,4 +1845,173 @@ class SurfacePosterior(_Recorder):
         self.mean.copy_(sd['mean'])
         self.m2.copy_(sd['m2'])
         self.count.copy_(sd['count'])
+        self.records = int(sd['records'])
+
+
+NATIVE_POSTERIOR_OPTION_KEYS = ('period', 'labels', 'image', 'prob_maps', 'std_floor')
+NATIVE_POSTERIOR_DEFAULTS = {'labels': True, 'image': True, 'prob_maps': False, 'std_floor': None}
+NATIVE_POSTERIOR_IMAGE_METRICS = IMAGE_METRICS + IMAGE_Z_METRICS  # the native fixed image is always the reference
+
+
+def native_posterior_options(cfg_trainer, data_loader=None):
+    """`trainer.native_posterior` -> None when off, else {'period': P, 'labels': bool, 'image': bool, 'prob_maps': bool,
+    'std_floor': float | None}.
+    Absent / false / null: off.  true: both parts, recorded every log_period_MCMC-th step after the burn-in.  A dict sets any of
+    "period", "labels", "image" (the two parts; at least one stays on), "prob_maps" (write the label probabilities) and
+    "std_floor" (the floor of the z map: a number >= 0, or null for 1e-3 of the native moving image's intensity range).  Refuses
+    unknown keys, a non-integer P or P < 1, a value of another type, both parts off, a config that records no step
+    (no_samples_MCMC // P < 1) or more than 2^31 - 1 samples, the option without trainer.native_resolution (whose loader supplies
+    the native pair) and -- when `data_loader` is given -- "labels" with a loader that found no segmentations."""
+    what = 'trainer.native_posterior'
+
+    def own_keys(opt):
+        own = {**NATIVE_POSTERIOR_DEFAULTS, **{k: v for k, v in opt.items() if k != 'period'}}
+        for key in ('labels', 'image', 'prob_maps'):
+            if not isinstance(own[key], bool):
+                raise ValueError(f'{what}.{key} must be true or false, got {own[key]!r}')
+        if not own['labels'] and not own['image']:
+            raise ValueError(f'{what}: "labels" and "image" are both false, nothing would be recorded')
+        floor = own['std_floor']
+        if floor is not None and (not _number(floor) or not math.isfinite(floor) or floor < 0):
+            raise ValueError(f'{what}.std_floor must be a finite number >= 0 or null, got {floor!r}')
+        own['std_floor'] = None if floor is None else float(floor)
+        return own
+
+    out = _record_options(cfg_trainer, 'native_posterior', NATIVE_POSTERIOR_OPTION_KEYS,
+                          '{"period": P, "labels": bool, "image": bool, "prob_maps": bool, "std_floor": x}', MAX_RECORDS,
+                          'the counts hold at most {}', own_keys)
+    if out is None:
+        return None
+    if cfg_trainer.get('native_resolution', False) in (None, False):
+        raise ValueError(f'{what} needs trainer.native_resolution, whose data loader supplies the pair on its own voxel grid')
+    if out['labels'] and data_loader is not None and not getattr(data_loader, 'has_segs', True):
+        raise ValueError(f'{what}: "labels" needs the fixed and the moving segmentation, and the data loader '
+                         f'({type(data_loader).__name__}) found no "segs" directory')
+    return out
+
+
+def native_posterior_metric_names(options, structures):
+    """the metric names the option adds: MCMC/native/seg/{metric}/{structure}, MCMC/native/seg/{entropy_mean,entropy_max,ECE} and
+    MCMC/native/image/moving/{std_mean,std_max,range_max,z_rms,z_gt2,z_gt3}"""
+    m = []
+    if options['labels']:
+        m += [f'MCMC/native/seg/{key}/{name}' for name in structures for key in LABEL_STRUCTURE_METRICS]
+        m += [f'MCMC/native/seg/{key}' for key in ('entropy_mean', 'entropy_max', 'ECE')]
+    if options['image']:
+        m += [f'MCMC/native/image/moving/{key}' for key in NATIVE_POSTERIOR_IMAGE_METRICS]
+    return m
+
+
+class NativePosterior(_Recorder):
+    """The label posterior and the image posterior on the image's own voxel grid (native_posterior.py): per native voxel the
+    counts of every structure of `structures_dict` over the recorded nearest-neighbour warps of the native moving segmentation
+    and / or the Welford mean / M2, minimum and maximum of the trilinear sample of the native moving image, on the device
+    (4 K + 16 bytes per native voxel whatever the number of records).  `record(displacement)` takes the (C,3,*grid.dims)
+    displacements of one step, chains in order, in voxels of the registration grid as the transition returns them (`voxels`
+    False: in [-1,1] coordinates), in ONE launch; `finalize` gives the maps and the summaries.  moving_seg int16 / moving_im
+    float32: (1,1,*grid.shape), each None when its part is off."""
+    noun = 'native posterior'
+
+    def __init__(self, grid, device, structures_dict=None, moving_seg=None, moving_im=None, fill=None, voxels=True):
+        from . import native_posterior as _np_ops
+        self._ops = _np_ops
+        self.grid, self.device, self.voxels = grid, device, bool(voxels)
+        self.names = list(structures_dict) if moving_seg is not None else []
+        self.labels = [int(structures_dict[k]) for k in self.names]
+        if moving_seg is None and moving_im is None:
+            raise ValueError('native posterior: neither the moving segmentation nor the moving image is given')
+        if moving_seg is not None and not 1 <= len(self.labels) <= 64:
+            raise ValueError(f'native posterior: 1 to 64 structures, got {len(self.labels)}')
+        if len(set(self.labels)) != len(self.labels):
+            raise ValueError(f'native posterior: the label values {self.labels} are not distinct')
+        if moving_im is not None and (fill is None or not math.isfinite(float(fill))):
+            raise ValueError(f'native posterior: the moving image needs a finite fill, got {fill!r}')
+        put = lambda t, dtype: None if t is None else t.to(device=device, dtype=dtype).contiguous()
+        self.moving_seg, self.moving_im = put(moving_seg, torch.int16), put(moving_im, torch.float32)
+        self.fill = 0.0 if fill is None else float(fill)
+        self.state = _np_ops.native_posterior_state(grid, self.labels if moving_seg is not None else None, moving_im is not None,
+                                                    device)
+
+    @property
+    def with_labels(self):
+        return self.moving_seg is not None
+
+    @property
+    def with_image(self):
+        return self.moving_im is not None
+
+    def state_bytes(self):
+        return self._ops.state_bytes(self.grid, len(self.labels), self.with_image)
+
+    def _geometry(self):
+        g = self.grid
+        return [list(g.shape), list(g.padding), list(g.dims)]
+
+    def _update(self, displacement):
+        if self.voxels:
+            from .utils.util import transform_coordinates
+            displacement = transform_coordinates(displacement)
+        self._ops.native_posterior_update(displacement.contiguous(), self.grid, self.state, self.records, seg=self.moving_seg,
+                                          im=self.moving_im, fill=self.fill)
+
+    def finalize(self, seg_fixed=None, im_fixed=None, mask=None, std_floor=0.0):
+        """-> {'labels': {'entropy' float32, 'map' int16 (*grid.shape) on the device, 'summary': label_summary with the volumes
+        in mm^3 under the header zooms}, 'image': {'mean', 'std', 'range'[, 'z'], 'summary': image_summary}}, each part when it
+        is recorded.  seg_fixed: the NATIVE fixed segmentation (needed with the labels); im_fixed: the native fixed image, the
+        reference of the z map, or None; mask: the native fixed mask or None.  One device-to-host read per part."""
+        from . import _lib as L
+        self._need_records('finalize')
+        mask = _bool_mask(mask, self.device)
+        out = {}
+        if self.with_labels:
+            if seg_fixed is None:
+                raise ValueError('native posterior: finalize needs the native fixed segmentation')
+            entropy, map_label, raw, ms = self._ops.native_label_finalize(self.state, self.records,
+                                                                          seg_fixed.to(device=self.device, dtype=torch.int16), mask)
+            host = torch.cat([raw.reshape(-1).view(torch.float64), ms, self.state['volume'].reshape(-1)]).cpu()
+            KC = raw.numel()
+            raw_h = host[:KC].view(torch.int64).reshape(raw.shape).numpy()
+            ms_h, vol_h = host[KC:KC + 4].numpy(), host[KC + 4:].reshape(-1, 2).numpy()
+            if ms_h[3] != 0:
+                raise L.IrsError(f'native posterior: {int(ms_h[3])} voxels hold more than the {self.records} records counted: '
+                                 f'the counts and the record number disagree')
+            summary = label_summary(raw_h, vol_h, self.records, ms_h, self.names, self.grid.spacing_xyz())
+            summary['raw'] = raw_h
+            out['labels'] = {'entropy': entropy, 'map': map_label, 'summary': summary}
+        if self.with_image:
+            ref = None if im_fixed is None else im_fixed.to(device=self.device, dtype=torch.float32)
+            std, rng, z, isum, fsum = self._ops.native_image_finalize(self.state, self.records, ref, std_floor, mask)
+            mean = self.state['mean']
+            out['image'] = {'mean': mean.where(mean.isfinite(), std.new_full((), math.nan)), 'std': std, 'range': rng,
+                            'summary': image_summary(*_host_summary(isum, fsum), self.records, ref is not None)}
+            if z is not None:
+                out['image']['z'] = z
+        return out
+
+    def probabilities(self):
+        """-> (K,*grid.shape) float32 on the device: counts / n"""
+        self._need_records('probabilities')
+        if not self.with_labels:
+            raise RuntimeError('NativePosterior.probabilities: the labels are not recorded')
+        return self.state['counts'].float() / self.records
+
+    def state_dict(self):
+        return {'records': self.records, 'labels': list(self.labels), 'geometry': self._geometry(), 'image': self.with_image,
+                **{key: t.detach().cpu() for key, t in self.state.items() if key != 'labels'}}
+
+    def load_state_dict(self, sd):
+        if [int(x) for x in sd['labels']] != self.labels:
+            raise ValueError(f'native posterior of labels {list(sd["labels"])} does not match this run ({self.labels})')
+        if [list(int(x) for x in g) for g in sd['geometry']] != self._geometry():
+            raise ValueError(f'native posterior of geometry {sd["geometry"]} (shape, padding, dims) does not match this run '
+                             f'({self._geometry()})')
+        if bool(sd['image']) != self.with_image:
+            raise ValueError(f'native posterior {"with" if sd["image"] else "without"} the image part does not match this run')
+        tensors = {key: t for key, t in self.state.items() if key != 'labels'}
+        for key, t in tensors.items():
+            if key not in sd or tuple(sd[key].shape) != tuple(t.shape):
+                raise ValueError(f'native posterior state {key!r} of shape {tuple(sd[key].shape) if key in sd else None} does not '
+                                 f'match this run ({tuple(t.shape)})')
+        for key, t in tensors.items():
+            t.copy_(sd[key])
         self.records = int(sd['records'])

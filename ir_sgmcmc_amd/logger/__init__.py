@@ -239,6 +239,28 @@ def save_native_mean(logger, save_dirs, zooms, displacement_mm, im_warped, model
     save_im_to_disk(im_warped, path.join(folder, f'{model}_im_moving_warped_mean_native.nii.gz'), zooms)
 
 
+def save_native_posterior(logger, save_dirs, zooms, maps, prob=None, names=(), model='MCMC'):
+    """the posteriors on the image's own voxel grid (absent in the reference), `maps` as diagnostics.NativePosterior.finalize
+    returns them: samples/{model}_seg_{entropy,MAP}_native.nii.gz (float32 / int16), with `prob` (K, *native shape)
+    {model}_seg_prob_{name}_native.nii.gz per structure, and samples/{model}_im_moving_{mean,std,range,z}_native.nii.gz (float32;
+    NaN -- a non-finite sample there -- written as 0).  `zooms`: the header zooms in the axis order of the arrays, written as
+    the files' spacing"""
+    folder = _folder(save_dirs, 'samples')
+    if 'labels' in maps:
+        logger.info(f'{model} native segmentation entropy max.: {float(maps["labels"]["entropy"].max()):.4f} nats')
+        save_im_to_disk(maps['labels']['entropy'], path.join(folder, f'{model}_seg_entropy_native.nii.gz'), zooms)
+        save_im_to_disk(maps['labels']['map'], path.join(folder, f'{model}_seg_MAP_native.nii.gz'), zooms)
+        if prob is not None:
+            for name, p in zip(names, prob):
+                save_im_to_disk(p, path.join(folder, f'{model}_seg_prob_{name}_native.nii.gz'), zooms)
+    if 'image' in maps:
+        for key in ('mean', 'std', 'range', 'z'):
+            if key in maps['image']:
+                im, undefined = _nan_to_zero(maps['image'][key])
+                logger.info(f'{model}_im_moving_{key}_native: {undefined} voxels without a finite value written as 0')
+                save_im_to_disk(im, path.join(folder, f'{model}_im_moving_{key}_native.nii.gz'), zooms)
+
+
 def save_landmarks(logger, save_dirs, mean_points, table, columns, unit, model='MCMC', tag=''):
     """the landmark posterior (absent in the reference): samples/{model}_landmarks{tag}.csv, one row per landmark under a header
     line -- the posterior-mean mapped point (x, y, z) and the columns of ops.LANDMARK_COLUMNS, in `unit` -- and

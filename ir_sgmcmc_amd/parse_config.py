@@ -18,7 +18,7 @@ from .diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ICE_SPACES, JA
                           inverse_consistency_options, jacobian_posterior_options, label_posterior_options,
                           landmark_metric_names, landmark_options, local_similarity_metric_names, local_similarity_options,
                           posterior_comparison_options, residual_check_metric_names, residual_check_options,
-                          native_resolution_options, surface_metric_names, surface_posterior_options)
+                          native_posterior_metric_names, native_posterior_options, native_resolution_options, surface_metric_names, surface_posterior_options)
 from .logger import setup_logging
 from .model import distributions as model_distr
 from .model import loss as model_loss
@@ -145,6 +145,9 @@ class ConfigParser:
             m += residual_check_metric_names(residuals, C, bool(self['trainer'].get('VI', False)))
         if posterior_comparison_options(self['trainer']) is not None:
             m += [f'MCMC/vs_VI/{k}' for k in COMPARISON_METRICS]
+        native_posterior = native_posterior_options(self['trainer'])
+        if native_posterior is not None:
+            m += native_posterior_metric_names(native_posterior, self.structures_dict)
         return m
 
     def init_transformation_and_registration_modules(self):

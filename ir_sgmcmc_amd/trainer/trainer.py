@@ -30,13 +30,14 @@ from ..diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ChainMoments,
                            diagnostics_period, displacement_covariance_options, displacement_quantiles_options,
                            ess_options, hausdorff_options, image_similarity_options, inverse_consistency_options, is_recorded,
                            jacobian_posterior_options, label_posterior_options, landmark_options, local_similarity_options,
+                           NATIVE_POSTERIOR_IMAGE_METRICS, NativePosterior, native_posterior_options,
                            native_resolution_options, PosteriorComparison, posterior_comparison_options, ResidualCheck,
                            residual_check_options, residual_metrics,
                            SIMILARITY_METRICS, voxel_scale)
 from ..engine import EngineConfig, TransitionEngine
 from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_quantiles, save_ess,
                       save_field, save_image_posterior, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_landmarks,
-                      save_local_similarity_of_mean, save_local_similarity_posterior, save_native_mean, save_native_sample,
+                      save_local_similarity_of_mean, save_local_similarity_posterior, save_native_mean, save_native_posterior, save_native_sample,
                       save_posterior_comparison,
                       save_residual_histogram, save_residual_nll, save_rhat, save_sample, save_surface_posterior)
 from .. import affine, bspline, image_posterior, multires, residual_check
@@ -146,6 +147,11 @@ class Trainer(VIMixin, BaseTrainer):
         # native volumes go to the device in _run_MCMC
         self.native_options = native_resolution_options(cfg_trainer, data_loader)
         self._native = None
+        # the label and the image posterior on the image's own voxel grid (native_posterior.py, diagnostics.NativePosterior): None
+        # when trainer.native_posterior is off.  It needs trainer.native_resolution, whose loader supplies the native pair
+        self.native_posterior_options = native_posterior_options(cfg_trainer, data_loader)
+        self._native_posterior, self._native_std_floor = None, None
+        self.native_posterior_maps, self.native_posterior_summary = None, None
         # image posterior: the moving image and the extra volumes on its grid carried through every recorded transformation
         # (image_posterior.py, diagnostics.ImagePosterior): None when trainer.image_posterior is off.  _image_volumes: the
         # volumes on the registration grid, formed in _run_model once the pair is masked and pre-aligned (a resumed run forms
@@ -408,7 +414,7 @@ class Trainer(VIMixin, BaseTrainer):
 
     def _recorders(self):
         """the active recorders, in the order they record and finish: moments, labels, surfaces, Jacobian, images, covariance,
-        quantiles, inverse consistency, landmarks, local similarity, residual check, posterior comparison"""
+        quantiles, inverse consistency, landmarks, local similarity, residual check, posterior comparison, native posterior"""
         period = lambda options: options and options['period']
         rows = (('chain_moments', self._chain_moments, self.diagnostics_period, 'convergence_diagnostics', 'chain moments',
                  'displacement', self._finish_diagnostics, 'moving_mask'),
@@ -435,7 +441,9 @@ class Trainer(VIMixin, BaseTrainer):
                 ('residual_check', self._residual_check, period(self.residual_options), 'residual_check', 'residual check',
                  'residuals', self._finish_residual_check, 'fixed'),
                 ('posterior_comparison', self._posterior_comparison, period(self.comparison_options), 'posterior_comparison',
-                 'posterior comparison', 'displacement', self._finish_posterior_comparison, 'moving_mask'))
+                 'posterior comparison', 'displacement', self._finish_posterior_comparison, 'moving_mask'),
+                ('native_posterior', self._native_posterior, period(self.native_posterior_options), 'native_posterior',
+                 'native posterior', 'displacement', self._finish_native_posterior, 'fixed'))
         return [Recorder(*row) for row in rows if row[1] is not None]
 
     # ---------------------------------------------------------------- checkpoint / resume (absent in the reference)
@@ -663,6 +671,8 @@ class Trainer(VIMixin, BaseTrainer):
                     and bool(self.structures_dict))
         if self.native_options is not None:
             self._native_init()
+        if self.native_posterior_options is not None:
+            self._native_posterior_init()
         if self.similarity_options is not None:
             self._similarity_init(fixed, moving)
         if self.landmark_options is not None:
@@ -1037,6 +1047,59 @@ class Trainer(VIMixin, BaseTrainer):
                          f'registered at {g.dims}')
         if self.interpolation_options is not None:
             self._native['coeff'] = self._spline_prefilter(self._native['moving_im'], 'the native moving image')
+        if self.native_posterior_options is not None:  # what the native posterior is finalized against
+            self._native['fixed_im'], self._native['fixed_mask'] = to(pair['fixed']['im']), to(pair['fixed']['mask'])
+
+    def _native_posterior_init(self):
+        """trainer.native_posterior -> self._native_posterior over the native pair of _native_init, and the floor of the z map:
+        the option's, or 1e-3 of the native moving image's intensity range (one host read-back).  The samples are trilinear
+        whatever trainer.output_interpolation says: that option concerns the images that are saved"""
+        nat, opt = self._native, self.native_posterior_options
+        if opt['labels'] and not self.structures_dict:
+            raise ValueError('trainer.native_posterior: "labels" needs structures (the config lists none)')
+        np_ = NativePosterior(nat['grid'], self.device, self.structures_dict if opt['labels'] else None,
+                              nat['moving_seg'] if opt['labels'] else None, nat['moving_im'] if opt['image'] else None, nat['fill'])
+        self._native_posterior = np_
+        self._native_std_floor = opt['std_floor']
+        if opt['image'] and self._native_std_floor is None:
+            lo, hi = nat['moving_im'].aminmax()
+            self._native_std_floor = IMAGE_STD_FLOOR_FRACTION * float(hi - lo)
+        self.logger.info(f'native posterior: {"labels (" + str(len(np_.labels)) + " structures)" if opt["labels"] else ""}'
+                         f'{" and " if opt["labels"] and opt["image"] else ""}{"image" if opt["image"] else ""} on '
+                         f'{nat["grid"].shape} voxels, {4 * len(np_.labels) + (16 if opt["image"] else 0)} bytes per native voxel, '
+                         f'{np_.state_bytes() / 1e6:.1f} MB on the device')
+
+    def _finish_native_posterior(self, fixed, spacing, save_outputs):
+        """entropy and MAP maps of the propagated native segmentation, mean / std / range / z maps of the native moving image and
+        their summaries over the NATIVE fixed mask -> self.native_posterior_maps / native_posterior_summary, the MCMC/native/seg/*
+        and MCMC/native/image/moving/* metrics (the volumes in mm^3 under the header zooms) and, with save_outputs,
+        samples/MCMC_seg_{entropy,MAP}_native.nii.gz[, MCMC_seg_prob_{structure}_native.nii.gz] and
+        samples/MCMC_im_moving_{mean,std,range,z}_native.nii.gz with the header zooms.  `fixed` and `spacing` belong to the
+        registration grid and are not used"""
+        nat, opt, np_ = self._native, self.native_posterior_options, self._native_posterior
+        self.native_posterior_maps = np_.finalize(nat['fixed_seg'][0, 0] if opt['labels'] else None, nat['fixed_im'][0, 0],
+                                                  nat['fixed_mask'][0, 0], self._native_std_floor or 0.0)
+        self.native_posterior_summary = {part: maps['summary'] for part, maps in self.native_posterior_maps.items()}
+        if opt['labels']:
+            s = self.native_posterior_summary['labels']
+            for name, st in s['structures'].items():
+                for key in LABEL_STRUCTURE_METRICS:
+                    self.metrics.update(f'MCMC/native/seg/{key}/{name}', st[key])
+            for key in ('entropy_mean', 'entropy_max', 'ECE'):
+                self.metrics.update(f'MCMC/native/seg/{key}', s[key])
+            self.logger.info(f'native label posterior of {s["records"]} warped segmentations: entropy over {s["voxels"]} masked '
+                             f'voxels mean {s["entropy_mean"]:.4f}, max {s["entropy_max"]:.4f} nats; pooled ECE {s["ECE"]:.4f}')
+        if opt['image']:
+            s = self.native_posterior_summary['image']
+            for key in NATIVE_POSTERIOR_IMAGE_METRICS:
+                self.metrics.update(f'MCMC/native/image/moving/{key}', s[key])
+            self.logger.info(f'native image posterior: {s["records"]} samples over {s["voxels"]} masked voxels '
+                             f'({s["nonfinite_voxels"]} non-finite): std mean {s["std_mean"]:.6g}, max {s["std_max"]:.6g}; against '
+                             f'the fixed image z rms {s["z_rms"]:.4g}, {100 * s["z_gt2"]:.2f} % above 2')
+        if save_outputs:
+            prob = np_.probabilities() if opt['labels'] and opt['prob_maps'] else None
+            save_native_posterior(self.logger, self.config.save_dirs, nat['grid'].zooms, self.native_posterior_maps, prob, np_.names,
+                                  'MCMC')
 
     def _log_native(self, sample_no, displacement, save):
         """the sample carried to the image's own voxel grid in ONE launch: the warped native moving segmentation -> the metrics

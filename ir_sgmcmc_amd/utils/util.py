@@ -385,6 +385,24 @@ def calc_residual_check(residuals, mask, data_loss, half_range, bins=128):
     return [{**row, 'n_nonfinite': int(c[1]), 'n_clipped': int(c[2])} for row, c in zip(rows, counts)]
 
 
+def calc_native_posterior(displacements, grid, moving_seg=None, structures_dict=None, moving_im=None, fill=None, seg_fixed=None,
+                          im_fixed=None, mask=None, std_floor=0.0, voxels=False):
+    """The label and / or image posterior on the image's own voxel grid over a list of displacements (absent in the reference):
+    the functional form of diagnostics.NativePosterior.  displacements: (C,3,*grid.dims) float32 tensors on the device, one per
+    recorded step, in [-1,1] coordinates (`voxels`: in voxels of the registration grid); grid: a native.NativeGrid; moving_seg
+    int16 with structures_dict {name: label value} and / or moving_im float32 with its `fill`: the native moving volumes
+    (1,1,*grid.shape); seg_fixed / im_fixed / mask: the native fixed segmentation, image (the reference of the z map) and mask.
+    -> (what NativePosterior.finalize returns, the recorder itself)"""
+    from ..diagnostics import NativePosterior
+    displacements = list(displacements)
+    if not displacements:
+        raise ValueError('calc_native_posterior: no displacement given')
+    rec = NativePosterior(grid, displacements[0].device, structures_dict, moving_seg, moving_im, fill, voxels)
+    for u in displacements:
+        rec.record(u)
+    return rec.finalize(seg_fixed, im_fixed, mask, std_floor), rec
+
+
 def rescale_residuals(res, mask, data_loss):
     """VD-rescaled residual x = sum_k r_k (z / sigma_k)^2 (utils/util.py:330-347).  The reference obtains it as
     sum_k s_k * d(-log p)/d(s_k) with a nested backward; the closed form with the responsibilities r_k is the same number."""
