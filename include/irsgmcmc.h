@@ -654,6 +654,44 @@ int irs_restrict_image(const float* im, int Cim, int D, int H, int W, float* out
 int irs_restrict_mask(const uint8_t* mask, int Cm, int D, int H, int W, uint8_t* out, int d, int h, int w, void* stream);
 int irs_prolong_field(const float* x, int C, int ch, int d, int h, int w, float* out, int D, int H, int W, void* stream);
 
+/* Adaptive pSGLD preconditioner (absent in the reference, whose sigma field is the VI posterior's standard deviation): the diagonal
+ * RMSprop estimator of Li et al. 2016 -- a running second moment of the gradient, and the sigma field formed from it.  All fields
+ * live on the velocity grid (., 3, D, H, W) of the caller (the image grid for SVF_3D, the control grid for SVFFD_3D); every extent
+ * >= 1, n = D H W < 2^30, ceil(H / 8) and 3 ceil(D / 4) at most 65535.  C in 1 .. IRS_MAX_CHAINS.  Every float32 operation named
+ * below is one IEEE operation rounded to nearest (add, multiply, divide, square root); NO operation is fused: where a product is
+ * added to something, the product is rounded first.  Doubles are used for the sums named so and nowhere else.
+ *  - irs_precond_accumulate: grad_v (C,3,D,H,W) float32 as irs_io.grad_v hands it out (sigma^2 dL/dv_s), sigma (C,3,D,H,W) float32
+ *    or NULL (= 1), beta in [0, 1), V (1,3,D,H,W) float32 in/out: ONE second moment shared by the chains.  Per element, float32:
+ *    g_c = grad_v_c / (sigma_c sigma_c) (grad_v_c itself when sigma is NULL; sigma = 1 gives the same bits); q = g_0 g_0, then
+ *    q = q + g_c g_c for c = 1 .. C - 1; m = q / (float)C; V = (beta V) + ((1 - beta) m) with 1 - beta one float32 subtraction.
+ *    nonfinite: one int64 on the device, to which the number of non-finite g_c of the call is added (integer atomics, one per
+ *    block that saw any); a non-finite g_c enters V like any other value.  V must not overlap grad_v or sigma.  One launch for
+ *    all chains: 16-byte accesses when every array is 16-byte aligned and C = 1 or 3 n is a multiple of 4 (the rest of 3 n mod 4
+ *    elements one by one), one element per thread otherwise; every thread owns its elements; no host sync.
+ *  - irs_precond_sigma: V as above -> sigma (C,3,D,H,W) float32, the same field written to every chain, and summary,
+ *    IRS_PRECOND_SUMMARY doubles on the device.  bias: 1 / (1 - beta^t) after t updates, formed by the caller in double, finite and
+ *    >= 1; smooth r in 0 .. IRS_PRECOND_MAX_SMOOTH; damping > 0 and finite; 0 < sigma_min <= 1 <= sigma_max < inf.
+ *    1. vhat = V (float)bias.  2. r > 0: every channel's vhat is replaced by its (2r+1)^3 box mean with replicate padding -- the
+ *    window summed in double in the order dz, dy, dx ascending, divided by (2r+1)^3 in double, rounded to float32 once.
+ *    3. s = sqrtf(vhat); sbar = (double sum of s over all N = 3 n elements) / N; lambda = (float)(damping sbar).
+ *    4. G = 1 / (lambda + s); Gbar = (double sum of G) / N.  sbar == 0 (no gradient seen yet): G = 1 everywhere.
+ *    5. raw = sqrtf(G / (float)Gbar); sigma = min(max(raw, sigma_min), sigma_max).
+ *    The double sums are taken in a fixed order (per-thread strided sums, the lanes of a wavefront by a butterfly, the wavefronts
+ *    and then the blocks in order; the grids depend on N only): two identical call sequences are bit-identical.
+ *    summary: {sbar, Gbar, min sigma, max sigma, mean of sigma^2 (double products, double sum, / N), elements with raw <
+ *    sigma_min, elements with raw > sigma_max, *nonfinite (the counter of irs_precond_accumulate, copied; NULL: 0)}.
+ *    sigma must not overlap V.  ws: irs_precond_workspace bytes of device memory.  No atomics; no host sync.
+ *  - irs_precond_workspace: the bytes irs_precond_sigma needs for the grid and r (a smoothed copy of vhat when r > 0, and the
+ *    rows of per-block partial sums). */
+#define IRS_PRECOND_MAX_SMOOTH 2
+#define IRS_PRECOND_SUMMARY 8
+int irs_precond_workspace(int D, int H, int W, int smooth, size_t* bytes);
+int irs_precond_accumulate(const float* grad_v, const float* sigma, int C, int D, int H, int W, float beta, float* V,
+                           long long* nonfinite, void* stream);
+int irs_precond_sigma(const float* V, int C, int D, int H, int W, double bias, int smooth, double damping, float sigma_min,
+                      float sigma_max, const long long* nonfinite, float* sigma, double* summary, void* ws, size_t ws_bytes,
+                      void* stream);
+
 /* Affine pre-alignment (absent in the reference, whose volumes were registered affinely elsewhere): the Gauss-Newton normal
  * equations of the sum of squared differences under a 3 x 4 map, the map as a transformation tensor, and the map composed with
  * a sampled transformation.

@@ -1341,6 +1341,65 @@ int irs_prolong_field(const float* x, int C, int ch, int d, int h, int w, float*
 }
 
 // ================================================================================================
+// adaptive pSGLD preconditioner (precond_kernels.hip)
+// ================================================================================================
+static bool precond_grid_ok(const char* who, int D, int H, int W) {
+    if (D < 1 || H < 1 || W < 1) return !fail("%s: dims (%d, %d, %d), every one >= 1 needed", who, D, H, W);
+    if ((int64_t)D * H * W >= ((int64_t)1 << 30)) return !fail("%s: the volume must have fewer than 2^30 voxels", who);
+    return ((H + 7) / 8 <= 65535 && 3 * (((int64_t)D + 3) / 4) <= 65535) ||
+           !fail("%s: dims (%d, %d, %d) exceed the launch grid", who, D, H, W);
+}
+
+// [a, a + na) and [b, b + nb) floats share an element
+static bool floats_overlap(const float* a, int64_t na, const float* b, int64_t nb) {
+    return (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
+}
+
+int irs_precond_workspace(int D, int H, int W, int smooth, size_t* bytes) {
+    if (!bytes) return fail("irs_precond_workspace: null pointer");
+    if (!precond_grid_ok(__func__, D, H, W)) return 1;
+    if (smooth < 0 || smooth > IRS_PRECOND_MAX_SMOOTH)
+        return fail("irs_precond_workspace: smooth = %d, 0..%d", smooth, IRS_PRECOND_MAX_SMOOTH);
+    *bytes = precond_workspace_bytes(make_vol(D, H, W), smooth);
+    return 0;
+}
+
+int irs_precond_accumulate(const float* grad_v, const float* sigma, int C, int D, int H, int W, float beta, float* V,
+                           long long* nonfinite, void* stream) {
+    if (!grad_v || !V || !nonfinite) return fail("irs_precond_accumulate: null pointer");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!precond_grid_ok(__func__, D, H, W)) return 1;
+    if (!(beta >= 0.0f && beta < 1.0f)) return fail("irs_precond_accumulate: beta = %g, a value in [0, 1) needed", (double)beta);
+    const int64_t N = (int64_t)3 * D * H * W;
+    if (floats_overlap(V, N, grad_v, C * N)) return fail("irs_precond_accumulate: V overlaps grad_v");
+    if (sigma && floats_overlap(V, N, sigma, C * N)) return fail("irs_precond_accumulate: V overlaps sigma");
+    launch_precond_accumulate(grad_v, sigma, C, N, beta, V, nonfinite, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_precond_sigma(const float* V, int C, int D, int H, int W, double bias, int smooth, double damping, float sigma_min,
+                      float sigma_max, const long long* nonfinite, float* sigma, double* summary, void* ws, size_t ws_bytes,
+                      void* stream) {
+    if (!V || !sigma || !summary || !ws) return fail("irs_precond_sigma: null pointer");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!precond_grid_ok(__func__, D, H, W)) return 1;
+    if (!(bias >= 1.0) || !isfinite((float)bias))
+        return fail("irs_precond_sigma: bias = %g, a finite value >= 1 needed (1 / (1 - beta^t))", bias);
+    if (smooth < 0 || smooth > IRS_PRECOND_MAX_SMOOTH) return fail("irs_precond_sigma: smooth = %d, 0..%d", smooth, IRS_PRECOND_MAX_SMOOTH);
+    if (!(damping > 0.0) || !isfinite(damping)) return fail("irs_precond_sigma: damping = %g, a finite value > 0 needed", damping);
+    if (!(sigma_min > 0.0f && sigma_min <= 1.0f && sigma_max >= 1.0f && isfinite(sigma_max)))
+        return fail("irs_precond_sigma: sigma_min = %g, sigma_max = %g, 0 < sigma_min <= 1 <= sigma_max < inf needed", (double)sigma_min,
+                    (double)sigma_max);
+    const Vol vol = make_vol(D, H, W);
+    if (!workspace_ok(__func__, ws_bytes, precond_workspace_bytes(vol, smooth), "irs_precond_workspace")) return 1;
+    if (floats_overlap(sigma, (int64_t)C * 3 * vol.V, V, 3 * vol.V)) return fail("irs_precond_sigma: sigma overlaps V");
+    launch_precond_sigma(V, C, vol, (float)bias, smooth, damping, sigma_min, sigma_max, nonfinite, sigma, summary, ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // foreground masks (mask_kernels.hip)
 // ================================================================================================
 int irs_intensity_histogram(const float* im, int C, const uint8_t* mask, int Cm, int D, int H, int W, float lo, float hi, int bins,

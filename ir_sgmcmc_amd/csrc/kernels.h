@@ -466,6 +466,15 @@ void launch_restrict_image(const float* im, float* out, int planes, const Vol& f
 void launch_restrict_mask(const uint8_t* mask, uint8_t* out, int planes, const Vol& fine, const Vol& coarse, hipStream_t st);
 void launch_prolong_field(const float* in, float* out, int planes, const Vol& coarse, const Vol& fine, hipStream_t st);
 
+// ---- precond_kernels.hip: the adaptive pSGLD preconditioner (absent in the reference); include/irsgmcmc.h has the arithmetic
+// grad_v, sigma (C, N) float32 with N = 3 D H W (sigma may be nullptr); V (N) in/out; nonfinite: one int64 on the device
+void launch_precond_accumulate(const float* grad_v, const float* sigma, int C, int64_t N, float beta, float* V, long long* nonfinite,
+                               hipStream_t st);
+// V (3, vol) -> sigma (C, 3, vol), summary IRS_PRECOND_SUMMARY doubles; ws: precond_workspace_bytes(vol, smooth)
+size_t precond_workspace_bytes(const Vol& vol, int smooth);
+void launch_precond_sigma(const float* V, int C, const Vol& vol, float bias, int smooth, double damping, float sigma_min,
+                          float sigma_max, const long long* nonfinite, float* sigma, double* summary, void* ws, hipStream_t st);
+
 // ---- affine_kernels.hip: the affine pre-alignment -- a map p = c + shift + lin (k - c) in voxel index coordinates, array order
 struct AffineMap {  // passed to the kernels by value
     double lin[9];  // row-major

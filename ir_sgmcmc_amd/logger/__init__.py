@@ -105,6 +105,17 @@ def save_sample(save_dirs, spacing, sample_no, im_moving_warped_batch, displacem
     save_im(save_dirs, spacing, log_det_J_batch[0], f'{prefix}_log_det_J', model)
 
 
+def save_precond_sigma(logger, save_dirs, spacing, sigma_rms, mask, model='MCMC'):
+    """the frozen sigma field of the adaptive preconditioner (absent in the reference), per voxel the RMS of its three channels,
+    plain and masked as the std map is: samples/{model}_precond_sigma.nii.gz and samples/{model}_precond_sigma_masked.nii.gz"""
+    folder = _folder(save_dirs, 'samples')
+    mask = mask.reshape(sigma_rms.shape).to(sigma_rms.device) != 0
+    logger.info(f'{model} preconditioner sigma (RMS over the channels) min.: {float(sigma_rms.min()):.4f}, max.: '
+                f'{float(sigma_rms.max()):.4f}')
+    save_im_to_disk(sigma_rms, path.join(folder, f'{model}_precond_sigma.nii.gz'), spacing)
+    save_im_to_disk(sigma_rms.where(mask, sigma_rms.new_zeros(())), path.join(folder, f'{model}_precond_sigma_masked.nii.gz'), spacing)
+
+
 def save_rhat(logger, save_dirs, spacing, rhat, mask, model='MCMC'):
     """split-R-hat map of the displacement (absent in the reference), plain and masked as the std map is:
     samples/{model}_rhat.nii.gz and samples/{model}_rhat_masked.nii.gz (0 outside the mask)"""

@@ -38,9 +38,9 @@ from ..engine import EngineConfig, TransitionEngine
 from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_quantiles, save_ess,
                       save_field, save_image_posterior, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_landmarks,
                       save_local_similarity_of_mean, save_local_similarity_posterior, save_native_mean, save_native_posterior, save_native_sample,
-                      save_posterior_comparison,
+                      save_posterior_comparison, save_precond_sigma,
                       save_residual_histogram, save_residual_nll, save_rhat, save_sample, save_surface_posterior)
-from .. import affine, bspline, image_posterior, multires, residual_check
+from .. import affine, bspline, image_posterior, multires, preconditioner, residual_check
 from .. import masks as mask_ops  # (`masks` names the pair of masks in several methods below)
 from ..multires import coarse_start_options
 from ..utils import (calc_DSC_GPU, calc_image_similarity, calc_norm, calc_no_non_diffeomorphic_voxels, calc_residual_check,
@@ -195,6 +195,12 @@ class Trainer(VIMixin, BaseTrainer):
         self.coarse_options = coarse_start_options(cfg_trainer, config['data_loader']['args']['dims'],
                                                    config['transformation_module']['type'])
         self.coarse_summary = None
+        # adaptive pSGLD preconditioner (preconditioner.py, _adapt_preconditioner): None when trainer.adaptive_preconditioner is
+        # absent, and then nothing changes.  _precond: the estimator's state while sigma is still adapted; _precond_frozen_at:
+        # the transition after which sigma stays as it is
+        self.precond_options = preconditioner.adaptive_preconditioner_options(cfg_trainer, self.no_iters_burn_in)
+        self._precond, self._precond_grad, self._precond_frozen_at = None, None, None
+        self.preconditioner_summary = None
         # cubic B-spline resampling of the images that are saved (bspline.py): None unless trainer.output_interpolation is
         # "cubic".  _spline_coeff: the coefficients of the moving image, formed when the engine is set up (a resumed run forms
         # them again: nothing goes into a checkpoint)
@@ -459,6 +465,8 @@ class Trainer(VIMixin, BaseTrainer):
                 'sample_no': getattr(self, '_sample_no', 0),
                 'moments': {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in getattr(self, '_moments', {}).items()},
                 'config_name': self.config['name'],
+                **({'preconditioner': preconditioner.checkpoint_entry(self._precond, self._precond_frozen_at)}
+                   if self._precond is not None else {}),
                 **{r.key: r.state.state_dict() for r in self._recorders()}}
 
     def load_state_dict(self, sd):
@@ -477,6 +485,9 @@ class Trainer(VIMixin, BaseTrainer):
         self.SGLD_params = {'tau': sd['tau'], 'sigma': self._sigma if self._sigma is not None else torch.ones_like(self.v_curr_state)}
         self._sample_no = int(sd['sample_no'])
         self._moments = {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in sd.get('moments', {}).items()}
+        if self.precond_options is not None:
+            preconditioner.check_checkpoint(sd, self.precond_options, self._sample_no)
+            self._precond_restore(sd.get('preconditioner'))
         for r in self._recorders():
             if r.key in sd:
                 r.state.load_state_dict(sd[r.key])
@@ -565,6 +576,57 @@ class Trainer(VIMixin, BaseTrainer):
         self.sync_parameters()
         return v
 
+    # ---------------------------------------------------------------- adaptive pSGLD preconditioner (absent in the reference)
+    def _precond_init(self):
+        """the estimator of trainer.adaptive_preconditioner at the start of a run: a zero second moment on the velocity grid.
+        self._sigma stays as _SGLD_init left it (None) until the first refresh: up to then the chain is the sigma-free chain"""
+        self._precond = preconditioner.preconditioner_state(self.v_curr_state.shape, self.device)
+        self._precond_grad, self._precond_frozen_at = None, None
+        self.preconditioner_summary = {'options': dict(self.precond_options), 'refreshes': [], 'frozen_at': None}
+
+    def _precond_restore(self, entry):
+        """the estimator as a checkpoint holds it (entry None: a checkpoint past `until` written without the option -- its sigma
+        is the frozen field, and nothing more is adapted)"""
+        if entry is None:
+            self._precond, frozen = None, self.precond_options['until']
+        else:
+            self._precond = {'V': entry['V'].to(self.device).contiguous(), 'count': int(entry['count']),
+                             'nonfinite': torch.tensor([int(entry['nonfinite'])], device=self.device, dtype=torch.int64)}
+            frozen = None if int(entry['frozen']) < 0 else int(entry['frozen'])
+        self._precond_frozen_at = frozen
+        if self.preconditioner_summary is None:
+            self.preconditioner_summary = {'options': dict(self.precond_options), 'refreshes': [], 'frozen_at': None}
+        self.preconditioner_summary['frozen_at'] = frozen  # the refreshes of a resumed run are those it made itself
+
+    def _adapt_preconditioner(self, step, mask, spacing):
+        """After adapting transition `step` (<= until): its gradient into the second moment, and at a refresh the new sigma.
+        grad_v belongs to transition `step` only once nothing is pending, hence the flush -- one host synchronisation per
+        adapting transition, none afterwards."""
+        opt = self.precond_options
+        self.engine.flush()
+        preconditioner.preconditioner_accumulate(self._precond_grad, self._sigma, self._precond, opt['beta'])
+        if not preconditioner.is_refresh(step, opt):
+            return
+        sigma, summary = preconditioner.preconditioner_sigma(self._precond, self.no_chains, opt['beta'], opt['smooth'], opt['damping'],
+                                                             opt['sigma_min'], opt['sigma_max'])
+        if summary['nonfinite']:
+            raise RuntimeError(f'adaptive preconditioner: {summary["nonfinite"]} non-finite gradient values up to transition {step} '
+                               f'(a chain has diverged; lower the learning rate or sigma_max)')
+        self._sigma = sigma
+        self.SGLD_params['sigma'] = sigma
+        for key in preconditioner.METRICS:
+            self.metrics.update(f'MCMC/precond/{key}', summary[key])
+        self.preconditioner_summary['refreshes'].append({'step': step, **summary})
+        self.logger.info(f'adaptive preconditioner, transition {step}: sigma in [{summary["sigma_min"]:.4g}, {summary["sigma_max"]:.4g}], '
+                         f'mean sigma^2 {summary["sigma2_mean"]:.4g}, clamped {summary["clamped_low"]} low / {summary["clamped_high"]} high')
+        if step == opt['until']:
+            self._precond_frozen_at = self.preconditioner_summary['frozen_at'] = step
+            self._precond_grad = None
+            self.logger.info(f'adaptive preconditioner: sigma frozen after transition {step}')
+            if opt['save'] and self.config['trainer'].get('save_outputs', True) and self.config['transformation_module']['type'] == 'SVF_3D':
+                rms = sigma[0].square().mean(dim=0).sqrt()
+                save_precond_sigma(self.logger, self.config.save_dirs, spacing, rms, mask)
+
     def _GMM_init(self, fixed, moving, var_params_q_v=None):
         """Trainer.__GMM_init (trainer.py:529-547): one velocity sample, std of the masked residual, 25 warm-up steps"""
         # the reference draws sample_q_v(var_params_q_v) here whatever MCMC_init is (mu = 0, sigma_v_init, u_v_init at the
@@ -591,6 +653,8 @@ class Trainer(VIMixin, BaseTrainer):
         if self.engine is None:
             raise RuntimeError('call _engine_init / _run_MCMC first')
         out = self._outputs if with_outputs else {k: self._outputs[k] for k in ('curr_state', 'im_moving_warped', 'residuals')}
+        if self._precond_grad is not None:  # an adapting transition of the adaptive preconditioner: it reads the gradient
+            out = {**out, 'grad_v': self._precond_grad}
         self.engine.transition(self._fixed, self._moving, self.v_curr_state, self._sigma, eps, unif, out)
         self._scalars_cache = None
         C = self.no_chains
@@ -687,6 +751,8 @@ class Trainer(VIMixin, BaseTrainer):
                                                  self.residual_options['nll_map'])
         if self.comparison_options is not None:
             self._comparison_init(self._outputs['displacement'].shape[2:])
+        if self.precond_options is not None:
+            self._precond_init()
         if cfg_trainer.get('resume'):
             self.load_checkpoint(cfg_trainer['resume'])
             first = self._sample_no + 1
@@ -697,7 +763,12 @@ class Trainer(VIMixin, BaseTrainer):
         for sample_no in range(first, n_total + 1):
             if sample_no < self.no_iters_burn_in and sample_no % self.log_period_MCMC == 0:
                 log(f'burn-in sample no. {sample_no}/{self.no_iters_burn_in}')
+            adapting = self.precond_options is not None and sample_no <= self.precond_options['until']
+            if adapting and self._precond_grad is None:
+                self._precond_grad = torch.empty_like(self.v_curr_state)
             loss_terms, output, aux = self._SGLD_transition(fixed, moving, data_loss, reg_loss, like_reference=False)
+            if adapting:
+                self._adapt_preconditioner(sample_no, masks['moving'], spacing)
             if sample_no == self.no_iters_burn_in:
                 log('ENDED BURNING IN')
             seg_warped = None  # the warped segmentation of this step, when the Dice / ASD branch builds it
