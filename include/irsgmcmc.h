@@ -692,6 +692,39 @@ int irs_precond_sigma(const float* V, int C, int D, int H, int W, double bias, i
                       float sigma_max, const long long* nonfinite, float* sigma, double* summary, void* ws, size_t ws_bytes,
                       void* stream);
 
+/* Posterior principal modes (absent in the reference): the recorded displacements kept on the device and the Gram matrix the
+ * snapshot PCA of them needs.  store (cap,3,D,H,W) float32, cap in 1 .. IRS_MODES_MAX_RECORDS, record i in slot i; every extent
+ * >= 1, V = D H W < 2^30.  The host algebra (centring, the voxel scale, the eigen-decomposition) is the caller's.
+ *  - irs_modes_gram_rows: one call per recorded step.  The n_new in 1 .. IRS_MAX_CHAINS new records are already in slots
+ *    n_before .. n_before + n_new - 1, n_before >= 0, n_before + n_new <= cap; mask (D,H,W) uint8 (a voxel counts where != 0)
+ *    or NULL (every voxel); gram (3,cap,cap) float64 in/out.  For every new slot i, every slot j <= i and every channel c:
+ *    G[c][i][j] = sum over the voxels x the mask admits of (double)store[i][c][x] (double)store[j][c][x], and G[c][j][i] is
+ *    written from the same value (the two triangles are bit-equal); no other element is touched.  Every product is exact in
+ *    double (two 24-bit significands); the sums are double.  A voxel outside the mask is not read into any sum; a non-finite
+ *    value inside it propagates.  Order of a sum: the voxels are dealt to B = min(256, ceil(V / 256)) blocks of 256 threads,
+ *    thread t of block b adds its voxels b 256 + t, b 256 + t + 256 B, ... in order; the 64 lanes of a wavefront are added by
+ *    the shuffle butterfly (offsets 32, 16, ..., 1), the four wavefronts in order, then the B blocks in order.  The order
+ *    depends on V and these constants only -- not on n_before, n_new, cap or timing: the same records give the same bits, and
+ *    an element has the same bits whichever call wrote it.  No atomics; two launches; no host sync.
+ *    ws: irs_modes_gram_workspace bytes of device memory, 8-byte aligned (the rows of per-block partial sums).
+ *  - irs_modes_gram_workspace: the bytes irs_modes_gram_rows needs for the grid and n_new, whatever n_before and cap.
+ *  - irs_modes_project: the first n in 1 .. IRS_MODES_MAX_RECORDS slots of the store, coeff (M,n) float64 on the device, M in
+ *    1 .. IRS_MODES_MAX, scale: three host doubles, finite and > 0 -> mean (3,D,H,W), modes (M,3,D,H,W), explained (D,H,W)
+ *    float32.  Per voxel x and channel c, with x_i = (double)store[i][c][x], in record order i = 0 .. n - 1 from zero:
+ *    S = S + x_i; Q = Q + x_i x_i (the product exact); a_m = a_m + (coeff[m][i] x_i) with the product rounded to double first
+ *    and the sum rounded second -- never one fused operation.  mean[c][x] = (float)(S / n); modes[m][c][x] = (float)a_m.
+ *    var_c = (Q - (S S) / n) / (n - 1), every operation rounded once.  explained[x] = (float)(num / den) with num = sum over c of
+ *    scale_c^2 (sum over m of a_m a_m) on the unrounded a_m and den = sum over c of scale_c^2 var_c; 0 where den == 0 and for
+ *    n < 2; no clamp (arbitrary coefficients may exceed 1); the mask plays no part.  Non-finite inputs propagate.  One launch,
+ *    one voxel per thread, the channels one after the other; deterministic; no atomics; no host sync. */
+#define IRS_MODES_MAX 16
+#define IRS_MODES_MAX_RECORDS 1024
+int irs_modes_gram_workspace(int D, int H, int W, int n_new, size_t* bytes);
+int irs_modes_gram_rows(const float* store, int cap, int n_before, int n_new, int D, int H, int W, const uint8_t* mask, double* gram,
+                        void* ws, size_t ws_bytes, void* stream);
+int irs_modes_project(const float* store, int n, int D, int H, int W, const double* coeff, int M, const double* scale, float* mean,
+                      float* modes, float* explained, void* stream);
+
 /* Affine pre-alignment (absent in the reference, whose volumes were registered affinely elsewhere): the Gauss-Newton normal
  * equations of the sum of squared differences under a 3 x 4 map, the map as a transformation tensor, and the map composed with
  * a sampled transformation.

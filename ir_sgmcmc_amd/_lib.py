@@ -48,6 +48,7 @@ IRS_RESIDUAL_MAP_WS_BYTES = 1024 * (IRS_RESIDUAL_MAP_SUMMARY_INTS + IRS_RESIDUAL
 IRS_SURFACE_MAX_LEVELS, IRS_SURFACE_SUMMARY_INTS, IRS_SURFACE_SUMMARY_FLOATS, IRS_SURFACE_MAX_BLOCKS = 4, 7, 6, 512
 IRS_SURFACE_WS_BYTES = IRS_MAX_LABELS * IRS_SURFACE_MAX_BLOCKS * (IRS_SURFACE_SUMMARY_INTS + IRS_SURFACE_SUMMARY_FLOATS) * 8
 IRS_PRECOND_MAX_SMOOTH, IRS_PRECOND_SUMMARY = 2, 8
+IRS_MODES_MAX, IRS_MODES_MAX_RECORDS = 16, 1024
 IRS_AFFINE_SUMS, IRS_AFFINE_PARTIALS, IRS_AFFINE_MAX_BLOCKS = 94, 76, 512
 IRS_AFFINE_WS_BYTES = IRS_AFFINE_MAX_BLOCKS * IRS_AFFINE_PARTIALS * 8
 IRS_MASK_MIN_BINS, IRS_MASK_MAX_BINS, IRS_MASK_MAX_KEEP, IRS_MASK_MAX_RADIUS = 2, 4096, 64, 16
@@ -221,7 +222,10 @@ SIGNATURES = {
     'irs_precond_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
     'irs_precond_accumulate': [_P, _P, _I, _I, _I, _I, _F, _P, _P, _P],
     'irs_precond_sigma': [_P, _I, _I, _I, _I, C.c_double, _I, C.c_double, _F, _F, _P, _P, _P, _P, C.c_size_t, _P],
-    'irs_affine_normal_equations': [_P, _P, _P, _I, _I, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, C.c_size_t, _P],
+    'irs_modes_gram_workspace': [_I, _I, _I, _I, C.POINTER(C.c_size_t)],
+    'irs_modes_gram_rows': [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, C.c_size_t, _P],
+    'irs_modes_project': [_P, _I, _I, _I, _I, _P, _I, C.POINTER(C.c_double), _P, _P, _P, _P],
+    'irs_affine_normal_equations':[_P, _P, _P, _I, _I, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, C.c_size_t, _P],
     'irs_affine_transformation': [C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _I, _I, _I, _P],
     'irs_affine_compose': [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, _I, _I, _I, _I, _P],
     'irs_bspline_prefilter': [_P, _P, _I, _I, _I, _I, _P],

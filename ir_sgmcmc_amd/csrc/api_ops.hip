@@ -1400,6 +1400,50 @@ int irs_precond_sigma(const float* V, int C, int D, int H, int W, double bias, i
 }
 
 // ================================================================================================
+// posterior principal modes (modes_kernels.hip)
+// ================================================================================================
+static bool modes_grid_ok(const char* who, int D, int H, int W) {
+    if (D < 1 || H < 1 || W < 1) return !fail("%s: dims (%d, %d, %d), every one >= 1 needed", who, D, H, W);
+    return (int64_t)D * H * W < ((int64_t)1 << 30) || !fail("%s: the volume must have fewer than 2^30 voxels", who);
+}
+
+int irs_modes_gram_workspace(int D, int H, int W, int n_new, size_t* bytes) {
+    if (!bytes) return fail("irs_modes_gram_workspace: null pointer");
+    if (!modes_grid_ok(__func__, D, H, W)) return 1;
+    if (n_new < 1 || n_new > IRS_MAX_CHAINS) return fail("irs_modes_gram_workspace: n_new = %d records, 1..%d", n_new, IRS_MAX_CHAINS);
+    *bytes = modes_gram_workspace_bytes((int64_t)D * H * W, n_new);
+    return 0;
+}
+
+int irs_modes_gram_rows(const float* store, int cap, int n_before, int n_new, int D, int H, int W, const uint8_t* mask, double* gram,
+                        void* ws, size_t ws_bytes, void* stream) {
+    if (!store || !gram || !ws) return fail("irs_modes_gram_rows: null pointer");
+    if (cap < 1 || cap > IRS_MODES_MAX_RECORDS) return fail("irs_modes_gram_rows: cap = %d records, 1..%d", cap, IRS_MODES_MAX_RECORDS);
+    if (n_new < 1 || n_new > IRS_MAX_CHAINS) return fail("irs_modes_gram_rows: n_new = %d records, 1..%d", n_new, IRS_MAX_CHAINS);
+    if (!records_ok(__func__, n_before, n_new, cap, "exceed the store's cap")) return 1;
+    if (!modes_grid_ok(__func__, D, H, W)) return 1;
+    const int64_t V = (int64_t)D * H * W;
+    if (!workspace_ok(__func__, ws_bytes, modes_gram_workspace_bytes(V, n_new), "irs_modes_gram_workspace")) return 1;
+    launch_modes_gram_rows(store, cap, n_before, n_new, V, mask, gram, ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_modes_project(const float* store, int n, int D, int H, int W, const double* coeff, int M, const double* scale, float* mean,
+                      float* modes, float* explained, void* stream) {
+    if (!store || !coeff || !scale || !mean || !modes || !explained) return fail("irs_modes_project: null pointer");
+    if (n < 1 || n > IRS_MODES_MAX_RECORDS) return fail("irs_modes_project: n = %d records, 1..%d", n, IRS_MODES_MAX_RECORDS);
+    if (M < 1 || M > IRS_MODES_MAX) return fail("irs_modes_project: M = %d modes, 1..%d", M, IRS_MODES_MAX);
+    if (!modes_grid_ok(__func__, D, H, W)) return 1;
+    for (int a = 0; a < 3; ++a)
+        if (!(scale[a] > 0.0) || !isfinite(scale[a]))
+            return fail("irs_modes_project: scale[%d] = %g, a finite value > 0 needed", a, scale[a]);
+    launch_modes_project(store, n, (int64_t)D * H * W, coeff, M, scale, mean, modes, explained, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // foreground masks (mask_kernels.hip)
 // ================================================================================================
 int irs_intensity_histogram(const float* im, int C, const uint8_t* mask, int Cm, int D, int H, int W, float lo, float hi, int bins,

@@ -475,6 +475,16 @@ size_t precond_workspace_bytes(const Vol& vol, int smooth);
 void launch_precond_sigma(const float* V, int C, const Vol& vol, float bias, int smooth, double damping, float sigma_min,
                           float sigma_max, const long long* nonfinite, float* sigma, double* summary, void* ws, hipStream_t st);
 
+// ---- modes_kernels.hip: the posterior principal modes (absent in the reference); include/irsgmcmc.h has the arithmetic
+// store (cap, 3, V) float32 with the new records already in slots n_before .. n_before + n_new - 1; mask (V) uint8 or nullptr;
+// gram (3, cap, cap) double; ws: modes_gram_workspace_bytes(V, n_new)
+size_t modes_gram_workspace_bytes(int64_t V, int n_new);
+void launch_modes_gram_rows(const float* store, int cap, int n_before, int n_new, int64_t V, const uint8_t* mask, double* gram, void* ws,
+                            hipStream_t st);
+// coeff (M, n) double on the device, scale: three host doubles -> mean (3, V), modes (M, 3, V), explained (V) float32
+void launch_modes_project(const float* store, int n, int64_t V, const double* coeff, int M, const double* scale, float* mean, float* modes,
+                          float* explained, hipStream_t st);
+
 // ---- affine_kernels.hip: the affine pre-alignment -- a map p = c + shift + lin (k - c) in voxel index coordinates, array order
 struct AffineMap {  // passed to the kernels by value
     double lin[9];  // row-major

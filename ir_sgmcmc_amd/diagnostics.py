@@ -24,6 +24,12 @@ the displacement mean / std is: per voxel the Welford mean and the six co-moment
 36 * D * H * W bytes whatever the number of records, and at the end the principal spreads, the major direction and the
 fractional anisotropy of the 3 x 3 sample covariance and their summary over a mask (ops.displacement_covariance_finalize).
 
+The displacement modes (DisplacementModes, displacement_modes_options) are the one summary across voxels, and the one recorder
+that keeps the samples: the recorded displacements stay on the device (12 * D * H * W bytes per record, at most max_records of
+them) with their per-channel Gram matrix (modes.modes_append), and at the end the host diagonalises the centred, scaled n x n
+matrix and one pass over the store forms the mean, the leading 1-sigma mode fields and an explained-variance map
+(modes.modes_decompose, modes.modes_project).
+
 The posterior comparison (PosteriorComparison, posterior_comparison_options) keeps two such states, one fed by the VI test
 samples and one by the recorded chain samples, 72 * D * H * W bytes, and at the end the distances between the Gaussians they
 describe per voxel -- mean shift, log ratio of the total spreads, Bures distance, Jeffreys divergence -- and their summary over
@@ -94,7 +100,9 @@ import numpy as np
 
 import torch
 
+from . import _lib as _L
 from . import image_posterior as _ip
+from . import modes as _modes
 from . import ops
 from . import posterior_comparison as _pc
 from . import residual_check as _rc
@@ -767,6 +775,146 @@ class DisplacementCovariance(_Recorder):
         self.mean.copy_(sd['mean'])
         self.comoment.copy_(sd['comoment'])
         self.records = int(sd['records'])
+
+
+MODES_OPTION_KEYS = ('period', 'modes', 'max_records', 'save')
+MODES_DEFAULTS = {'modes': 8, 'max_records': 256, 'save': True}
+MODES_METRICS = ('var_total', 'explained_1', 'explained_M', 'n90', 'participation', 'std_1', 'rhat_max')
+
+
+def displacement_modes_options(cfg_trainer):
+    """`trainer.displacement_modes` -> None when off, else {'period': P, 'modes': M, 'max_records': cap, 'save': bool}.
+    Absent / false / null: off.  true: the defaults (P = log_period_MCMC, 8 modes, a store of 256 records, save).  A dict: any of
+    "period", "modes" (1 .. 16), "max_records" (2 .. 1024: the records the device store holds, 12 D H W bytes each) and "save"
+    (write the mode fields and the explained map with save_outputs).  Refuses unknown keys, wrong types (booleans as numbers
+    too), values out of range, a config that records no step or fewer than 2 records in all, and one that would record more
+    than max_records (nothing is thinned or dropped: raise max_records or the period)."""
+    what = 'trainer.displacement_modes'
+
+    def own_keys(opt):
+        out = dict(MODES_DEFAULTS)
+        for key, lo, hi in (('modes', 1, _L.IRS_MODES_MAX), ('max_records', 2, _L.IRS_MODES_MAX_RECORDS)):
+            if key in opt:
+                v = opt[key]
+                if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+                    raise ValueError(f'{what}.{key} must be an integer, got {v!r}')
+                if not lo <= v <= hi:
+                    raise ValueError(f'{what}.{key} must be in {lo} .. {hi}, got {v}')
+                out[key] = int(v)
+        if 'save' in opt and not isinstance(opt['save'], bool):
+            raise ValueError(f'{what}.save must be true or false, got {opt["save"]!r}')
+        out['save'] = opt.get('save', True)
+        return out
+
+    opt = cfg_trainer.get('displacement_modes', False)
+    if opt is None or opt is False:
+        return None
+    # the ceiling is the option's own max_records: read it first (own_keys runs again inside, after the key checks)
+    ceiling = MODES_DEFAULTS['max_records']
+    if isinstance(opt, dict) and not (set(opt) - set(MODES_OPTION_KEYS)):
+        ceiling = own_keys(opt)['max_records']
+    out = _record_options(cfg_trainer, 'displacement_modes', MODES_OPTION_KEYS,
+                          '{"period": P, "modes": M, "max_records": N, "save": true}', ceiling,
+                          'the store holds at most {} (trainer.displacement_modes.max_records; nothing is thinned)', own_keys)
+    records = int(cfg_trainer['no_samples_MCMC']) // out['period'] * int(cfg_trainer.get('no_chains', 1))
+    if records < 2:
+        raise ValueError(f'{what}: the run records {records} displacement; modes need at least 2')
+    return out
+
+
+def modes_summary(dec, M):
+    """the summary of DESIGN.md section 6 from modes.modes_decompose's dict: records, modes kept, var_total (voxels^2 summed over
+    the mask), explained_1 and explained_M (the share of the first mode and of the first M together), n90, the participation
+    ratio, std_1 (RMS voxel displacement of the first mode) and rhat_max (the largest split-R-hat of the M score series; NaN
+    with one chain or fewer than 4 records per chain)"""
+    K = min(int(M), len(dec['eigenvalues']))
+    rhat = dec['rhat'][:K]
+    finite = rhat[~np.isnan(rhat)]
+    return {'records': int(dec['n']), 'modes': K, 'var_total': float(dec['var_total']),
+            'explained_1': float(dec['explained'][0]) if K else float('nan'),
+            'explained_M': float(np.sum(dec['explained'][:K])) if K else float('nan'), 'n90': int(dec['n90']),
+            'participation': float(dec['participation']), 'std_1': float(dec['std'][0]) if K else float('nan'),
+            'rhat_max': float(finite.max()) if finite.size else float('nan')}
+
+
+class DisplacementModes(_Recorder):
+    """The recorded displacements themselves, on the device, and their Gram matrix (modes.py): `record(displacement)` takes the
+    (C,3,D,H,W) float32 displacements of one step, chains in order, into the next C slots of a store of `cap` records (12 D H W
+    cap bytes) and fills their rows of the per-channel Gram matrices; `finalize(M)` diagonalises the centred, scaled Gram matrix
+    on the host and forms the mean, the M leading 1-sigma mode fields and the explained-variance map in one pass over the
+    store.  The mask is fixed at creation: it enters the Gram matrix (the inner product of the modes) only."""
+    noun = 'displacement modes'
+    exceed = 'exceed the store of {} (trainer.displacement_modes.max_records)'
+
+    def __init__(self, dims, device, cap, mask=None, logger=None):
+        self.dims = tuple(int(d) for d in dims)
+        if len(self.dims) != 3 or min(self.dims) < 2:
+            raise ValueError(f'displacement modes: three dims of at least 2, got {self.dims}')
+        self.device, self.cap, self.max_records, self.logger = device, int(cap), int(cap), logger
+        self.dev = _modes.modes_state(self.dims, self.cap, device, _bool_mask(mask, device))
+        self.steps, self.chains = [], []
+        self._logged_checkpoint = False
+        if logger is not None:
+            logger.info(f'displacement modes: a store of {self.cap} records, {self.store_bytes() / 1e6:.1f} MB on the device '
+                        f'(12 x {int(np.prod(self.dims))} voxels x {self.cap}), {self.dev["mask_voxels"]} voxels in the mask')
+
+    def store_bytes(self):
+        return 12 * int(np.prod(self.dims)) * self.cap
+
+    def default_scale(self):
+        return voxel_scale(self.dims)
+
+    def record(self, sample, step=None):
+        C = sample.shape[0]
+        super().record(sample)
+        step = (self.steps[-1] + 1 if self.steps else 1) if step is None else int(step)
+        self.steps += [step] * C
+        self.chains += list(range(C))
+
+    def _update(self, displacement):
+        _modes.modes_append(self.dev, displacement)
+
+    def gram(self):
+        return _modes.modes_gram(self.dev)
+
+    def finalize(self, M=MODES_DEFAULTS['modes'], scale=None):
+        """-> {'eigenvalues', 'explained', 'scores', 'rhat' (numpy, of modes_decompose), 'mean' (3,D,H,W), 'modes' (K,3,D,H,W):
+        the 1-sigma mode fields in normalised coordinates, 'explained_map' (D,H,W), float32 on the device, 'steps', 'chains',
+        'summary': modes_summary}, K = min(M, n - 1).  Needs at least 2 records.  One device-to-host read (the Gram matrix)."""
+        self._need_records('finalize')
+        if self.records < 2:
+            raise RuntimeError(f'DisplacementModes.finalize: {self.records} record; modes need at least 2')
+        if isinstance(M, bool) or not isinstance(M, numbers.Integral) or not 1 <= M <= _L.IRS_MODES_MAX:
+            raise ValueError(f'displacement modes: M must be an integer in 1 .. {_L.IRS_MODES_MAX}, got {M!r}')
+        scale = self.default_scale() if scale is None else tuple(float(s) for s in scale)
+        dec = _modes.modes_decompose(self.gram(), scale, self.dev['mask_voxels'], self.chains, M)
+        mean, fields, explained_map = _modes.modes_project(self.dev, dec['coeff'], scale)
+        return {'eigenvalues': dec['eigenvalues'], 'explained': dec['explained'], 'scores': dec['scores'], 'rhat': dec['rhat'],
+                'mean': mean, 'modes': fields, 'explained_map': explained_map, 'steps': list(self.steps), 'chains': list(self.chains),
+                'summary': modes_summary(dec, M)}
+
+    def state_dict(self):
+        n = self.records
+        sd = {'store': self.dev['store'][:n].detach().cpu(), 'gram': self.dev['gram'].detach().cpu(), 'records': n, 'cap': self.cap,
+              'steps': list(self.steps), 'chains': list(self.chains)}
+        if self.logger is not None and not self._logged_checkpoint:
+            self._logged_checkpoint = True
+            self.logger.info(f'displacement modes: a checkpoint holds the {n} records so far, {12 * int(np.prod(self.dims)) * n / 1e6:.1f} '
+                             f'MB now and up to {self.store_bytes() / 1e6:.1f} MB')
+        return sd
+
+    def load_state_dict(self, sd):
+        n = int(sd['records'])
+        if tuple(sd['store'].shape) != (n, 3) + self.dims:
+            raise ValueError(f'displacement modes of shape {tuple(sd["store"].shape)} (store) do not match this run '
+                             f'({(n, 3) + self.dims})')
+        if int(sd['cap']) != self.cap or tuple(sd['gram'].shape) != (3, self.cap, self.cap):
+            raise ValueError(f'displacement modes with a store of {int(sd["cap"])} records do not match this run '
+                             f'(trainer.displacement_modes.max_records = {self.cap})')
+        self.dev['store'][:n].copy_(sd['store'])
+        self.dev['gram'].copy_(sd['gram'])
+        self.dev['n'] = self.records = n
+        self.steps, self.chains = [int(s) for s in sd['steps']], [int(c) for c in sd['chains']]
 
 
 COMPARISON_OPTION_KEYS = ('period', 'std_floor')

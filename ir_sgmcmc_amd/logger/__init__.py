@@ -195,6 +195,32 @@ def save_displacement_covariance(logger, save_dirs, spacing, std, direction, ani
     save_field_to_disk(direction * std[0], path.join(folder, f'{model}_disp_direction.vtk'), spacing)
 
 
+def save_displacement_modes(logger, save_dirs, spacing, out, mask, model='MCMC'):
+    """principal modes of the displacement posterior (absent in the reference), `out` as diagnostics.DisplacementModes.finalize
+    returns it: samples/{model}_mode_{k}.vtk, k = 1 .. K, the 1-sigma mode field written the way the mean displacement is;
+    {model}_modes_explained[_masked].nii.gz (float32, the masked one 0 outside the mask); {model}_modes.csv (m, eigenvalue,
+    share, cumulative share, split R-hat of the scores) and {model}_mode_scores.csv (record, step, chain, one score per mode)"""
+    folder = _folder(save_dirs, 'samples')
+    explained = out['explained_map']
+    mask = mask.reshape(explained.shape).to(explained.device) != 0
+    logger.info(f'{model} explained-variance map of {out["modes"].shape[0]} modes min.: {float(explained.min()):.4f}, max.: '
+                f'{float(explained.max()):.4f}')
+    for k, field in enumerate(out['modes'], start=1):
+        save_field_to_disk(field * spacing[0], path.join(folder, f'{model}_mode_{k}.vtk'), spacing)
+    save_im_to_disk(explained, path.join(folder, f'{model}_modes_explained.nii.gz'), spacing)
+    save_im_to_disk(explained.where(mask, explained.new_zeros(())), path.join(folder, f'{model}_modes_explained_masked.nii.gz'), spacing)
+    K = out['scores'].shape[1]
+    cumulative = np.cumsum(out['explained'])
+    with open(path.join(folder, f'{model}_modes.csv'), 'w') as f:
+        f.write('m,eigenvalue,share,cumulative_share,rhat\n')
+        for m in range(K):
+            f.write(f'{m + 1},{out["eigenvalues"][m]:.17g},{out["explained"][m]:.17g},{cumulative[m]:.17g},{out["rhat"][m]:.6g}\n')
+    with open(path.join(folder, f'{model}_mode_scores.csv'), 'w') as f:
+        f.write('record,step,chain,' + ','.join(f'score_{m + 1}' for m in range(K)) + '\n')
+        for i, (step, chain) in enumerate(zip(out['steps'], out['chains'])):
+            f.write(f'{i},{step},{chain},' + ','.join(f'{v:.17g}' for v in out['scores'][i]) + '\n')
+
+
 def save_displacement_quantiles(logger, save_dirs, spacing, probs, quantiles, ci_width, mask, model='MCMC'):
     """credible intervals of the displacement posterior (absent in the reference): samples/{model}_disp_q{PP}.vtk, one field
     per probability (PP the probability in percent, `g` formatting, the dot replaced by `p`: q5, q50, q95, q2p5; NaN where out

@@ -11,7 +11,8 @@ from pathlib import Path
 import numpy as np
 
 from .data_loader import data_loaders as module_data
-from .diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ICE_SPACES, JACOBIAN_METRICS, LABEL_STRUCTURE_METRICS, QUANTILE_METRICS,
+from .diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ICE_SPACES, JACOBIAN_METRICS, LABEL_STRUCTURE_METRICS, MODES_METRICS,
+                          QUANTILE_METRICS, displacement_modes_options,
                           diagnostics_period, displacement_covariance_options, displacement_quantiles_options, ess_options,
                           hausdorff_metric_names, hausdorff_options, image_posterior_metric_names, image_posterior_options,
                           image_similarity_metric_names, image_similarity_options,
@@ -124,6 +125,8 @@ class ConfigParser:
             m += image_posterior_metric_names(image)
         if displacement_covariance_options(self['trainer']) is not None:
             m += [f'MCMC/covariance/{k}' for k in COVARIANCE_METRICS]
+        if displacement_modes_options(self['trainer']) is not None:
+            m += [f'MCMC/modes/{k}' for k in MODES_METRICS]
         if displacement_quantiles_options(self['trainer']) is not None:
             m += [f'MCMC/quantiles/{k}' for k in QUANTILE_METRICS]
         ice = inverse_consistency_options(self['trainer'])

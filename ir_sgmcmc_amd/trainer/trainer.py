@@ -22,7 +22,8 @@ import torch
 
 from ..base import BaseTrainer
 from .. import ops
-from ..diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ChainMoments, DisplacementCovariance, DisplacementQuantiles, ICE_SPACES,
+from ..diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ChainMoments, DisplacementCovariance, DisplacementModes,
+                           DisplacementQuantiles, ICE_SPACES, MODES_METRICS, displacement_modes_options,
                            IMAGE_METRICS, IMAGE_STD_FLOOR_FRACTION, IMAGE_Z_METRICS, ImagePosterior, image_posterior_names,
                            image_posterior_options, InverseConsistency, JACOBIAN_METRICS, JacobianPosterior, LABEL_STRUCTURE_METRICS, LANDMARK_METRICS,
                            LOCAL_METRICS, LabelPosterior, LandmarkPair, LandmarkPosterior, LocalSimilarity, QUANTILE_METRICS,
@@ -35,7 +36,7 @@ from ..diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ChainMoments,
                            residual_check_options, residual_metrics,
                            SIMILARITY_METRICS, voxel_scale)
 from ..engine import EngineConfig, TransitionEngine
-from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_quantiles, save_ess,
+from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_modes, save_displacement_quantiles, save_ess,
                       save_field, save_image_posterior, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_landmarks,
                       save_local_similarity_of_mean, save_local_similarity_posterior, save_native_mean, save_native_posterior, save_native_sample,
                       save_posterior_comparison, save_precond_sigma,
@@ -132,6 +133,10 @@ class Trainer(VIMixin, BaseTrainer):
         self._displacement_covariance = None
         self.displacement_cov_std, self.displacement_cov_direction = None, None
         self.displacement_cov_anisotropy, self.displacement_cov_summary = None, None
+        # posterior principal modes (diagnostics.DisplacementModes): None when trainer.displacement_modes is off
+        self.modes_options = displacement_modes_options(cfg_trainer)
+        self._displacement_modes = None
+        self.displacement_modes_summary, self.displacement_mode_fields, self.displacement_mode_scores = None, None, None
         # displacement credible intervals (diagnostics.DisplacementQuantiles): None when trainer.displacement_quantiles is off
         self.quantiles_options = displacement_quantiles_options(cfg_trainer)
         self._displacement_quantiles = None
@@ -420,7 +425,7 @@ class Trainer(VIMixin, BaseTrainer):
 
     def _recorders(self):
         """the active recorders, in the order they record and finish: moments, labels, surfaces, Jacobian, images, covariance,
-        quantiles, inverse consistency, landmarks, local similarity, residual check, posterior comparison, native posterior"""
+        modes, quantiles, inverse consistency, landmarks, local similarity, residual check, posterior comparison, native posterior"""
         period = lambda options: options and options['period']
         rows = (('chain_moments', self._chain_moments, self.diagnostics_period, 'convergence_diagnostics', 'chain moments',
                  'displacement', self._finish_diagnostics, 'moving_mask'),
@@ -435,6 +440,8 @@ class Trainer(VIMixin, BaseTrainer):
                 ('displacement_covariance', self._displacement_covariance, period(self.covariance_options),
                  'displacement_covariance', 'displacement covariance', 'displacement', self._finish_displacement_covariance,
                  'moving_mask'),
+                ('displacement_modes', self._displacement_modes, period(self.modes_options), 'displacement_modes',
+                 'displacement modes', 'displacement', self._finish_displacement_modes, 'moving_mask'),
                 ('displacement_quantiles', self._displacement_quantiles, period(self.quantiles_options), 'displacement_quantiles',
                  'displacement quantiles', 'displacement', self._finish_displacement_quantiles, 'moving_mask'),
                 ('inverse_consistency', self._inverse_consistency, period(self.ice_options), 'inverse_consistency',
@@ -728,6 +735,9 @@ class Trainer(VIMixin, BaseTrainer):
                              f'{self._displacement_quantiles.bytes_per_voxel(q["bins"])} bytes per voxel, '
                              f'{self._displacement_quantiles.state_bytes() / 1e6:.1f} MB on the device')
         masks = {'fixed': fixed['mask'][0], 'moving': moving.get('mask', fixed['mask'])[0]}
+        if self.modes_options is not None:  # its mask, the std map's, is fixed here: it enters the Gram matrix
+            self._displacement_modes = DisplacementModes(self._outputs['displacement'].shape[2:], self.device,
+                                                         self.modes_options['max_records'], masks['moving'], self.logger)
         if self.ice_options is not None:
             self._inverse_consistency = InverseConsistency(self._outputs['displacement'].shape[2:], self.device,
                                                            getattr(self.transformation_module, 'no_steps', 12), masks)
@@ -853,7 +863,8 @@ class Trainer(VIMixin, BaseTrainer):
                 pick = lambda name: (seg_warped if name == 'seg_warped' else lncc if name == 'lncc' else
                                      aux['residuals'] if name == 'residuals' else
                                      self._dense_velocity(output) if name == 'velocity' else output[name])
-                r.state.record(tuple(pick(n) for n in r.records) if isinstance(r.records, tuple) else pick(r.records))
+                r.state.record(tuple(pick(n) for n in r.records) if isinstance(r.records, tuple) else pick(r.records),
+                               **({'step': sample_no} if r.state is self._displacement_modes else {}))
             if self._inverse_consistency is not None:
                 ice = self._inverse_consistency
                 recorded = any(r.state is ice for r in due)
@@ -1081,6 +1092,24 @@ class Trainer(VIMixin, BaseTrainer):
         if save_outputs:
             save_displacement_covariance(self.logger, self.config.save_dirs, spacing, self.displacement_cov_std,
                                          self.displacement_cov_direction, self.displacement_cov_anisotropy, mask, 'MCMC')
+
+    def _finish_displacement_modes(self, mask, spacing, save_outputs):
+        """principal modes of the displacement posterior: eigenvalues, shares, scores and the 1-sigma mode fields ->
+        self.displacement_modes_summary / displacement_mode_fields (K,3,D,H,W, normalised coordinates) /
+        displacement_mode_scores (n,K), the MCMC/modes/* metrics and, with save_outputs and the option's save,
+        samples/MCMC_mode_{k}.vtk, MCMC_modes_explained[_masked].nii.gz, MCMC_modes.csv and MCMC_mode_scores.csv.  The inner
+        product of the modes is over the mask the displacement std map uses, fixed when the recorder was created."""
+        out = self._displacement_modes.finalize(self.modes_options['modes'])
+        s = self.displacement_modes_summary = out['summary']
+        self.displacement_mode_fields, self.displacement_mode_scores = out['modes'], out['scores']
+        for key in MODES_METRICS:
+            self.metrics.update(f'MCMC/modes/{key}', s[key])
+        self.logger.info(f'displacement modes of {s["records"]} samples: total variance {s["var_total"]:.6g} voxels^2 over the mask, '
+                         f'mode 1 explains {100 * s["explained_1"]:.2f} % (RMS {s["std_1"]:.4f} voxels), the first {s["modes"]} '
+                         f'{100 * s["explained_M"]:.2f} %; {s["n90"]} modes reach 90 %, participation ratio '
+                         f'{s["participation"]:.2f}; largest split R-hat of the scores {s["rhat_max"]:.4f}')
+        if save_outputs and self.modes_options['save']:
+            save_displacement_modes(self.logger, self.config.save_dirs, spacing, out, mask, 'MCMC')
 
     def _finish_displacement_quantiles(self, mask, spacing, save_outputs):
         """quantiles of the displacement posterior (voxels) at the option's probabilities, the width of the band between the

@@ -235,6 +235,21 @@ def calc_displacement_covariance(displacements, mask=None, scale=None):
 
 
 @torch.no_grad()
+def calc_displacement_modes(displacements, mask=None, modes=8, scale=None, chains=1):
+    """Principal modes of displacement samples by the snapshot method (absent in the reference): displacements (n,3,D,H,W)
+    float32 on the device, in normalised coordinates, 2 <= n <= 1024 records ordered by step, then by chain (`chains` per step);
+    mask (D,H,W) or None: the voxels of the inner product; modes: 1 .. 16; scale: three floats, one per channel (default: voxel
+    units).  -> the dict of diagnostics.DisplacementModes.finalize."""
+    from ..diagnostics import DisplacementModes
+    if displacements.dim() != 5 or displacements.shape[1] != 3:
+        raise ValueError(f'displacements must have shape (n, 3, D, H, W), got {tuple(displacements.shape)}')
+    dm = DisplacementModes(displacements.shape[2:], displacements.device, displacements.shape[0], mask)
+    for i in range(0, displacements.shape[0], chains):  # one launch folds the records of one step, in order
+        dm.record(displacements[i:i + chains].float().contiguous())
+    return dm.finalize(modes, scale)
+
+
+@torch.no_grad()
 def calc_posterior_comparison(displacements_a, displacements_b, mask=None, scale=None, std_floor=1e-3):
     """The distances between the Gaussians fitted, per voxel, to two sets of displacement samples (absent in the reference):
     displacements_a (n_a,3,D,H,W) and displacements_b (n_b,3,D,H,W) float32 on the device, in normalised coordinates, at least
