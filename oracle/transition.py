@@ -342,5 +342,6 @@ class OracleVI:
         if ch.adam_reg is not None:
             ch.adam_reg.step(list(grads[n_q:]))
         self.adam.step(list(grads[:n_q]))
+        # 'grads': the raw gradients of this iteration (mu, log_var, u, then the learnable regulariser parameters), before Adam
         return {'data': float(data), 'reg': float(reg), 'entropy': float(entropy), 'loss': float(loss), 'alpha': out['alpha'],
-                'displacement': out['displacement']}
+                'displacement': out['displacement'], 'grads': [g.detach().clone() for g in grads]}
