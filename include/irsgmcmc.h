@@ -1057,6 +1057,19 @@ int irs_sparse_forward_set(irs_ctx* ctx, int on);
  * run pieces of the chain in the step's list, planes of 64 x 8 tile columns in its run ranges, planned width of the step.  All zero
  * when the dense steps ran.  Calls irs_flush; blocking. */
 int irs_sparse_forward_get(irs_ctx* ctx, int32_t* out, void* stream);
+/* How the piece lists of the three sparse stages are kept from transition to transition.  A list is a pure function of its extent
+ * table (the fixed mask's, or g_warped's), of the launch shape it is cut for (tile, reach, fill rule, resident set, piece length,
+ * chains, dims) and -- the adjoint -- of which chains left the radius-1 kernel; each list keeps a record of those on the device, the
+ * extent pass notes whether its table changed, and the launches that would rebuild a list whose record still holds leave at once.
+ * Decided on the device, in stream order, from data: a mask that changes under the same pointer is seen in the transition in which
+ * it changes, nothing is read back, and the sequence captures into a graph.  reuse: bit 0 (default 1) reuse on, 0 every list is
+ * rebuilt in every transition; bit 1 (default 0) the adjoint's lists are always cut from the extents of g_warped -- by default they are
+ * cut from the mask's table, at the reach of g_warped's support around the mask more, whenever the sparse data stage formed that
+ * table in the transition.  The same numbers either way.  A call of its own, like irs_sparse_data_set. */
+int irs_sparse_plan_set(irs_ctx* ctx, int reuse);
+/* out: int32 [3][2] = per family (data stage with the warp's hull counted as a list, forward steps, adjoint steps) the lists rebuilt
+ * and the lists reused since irs_create, counted on the device.  Calls irs_flush; blocking. */
+int irs_sparse_plan_get(irs_ctx* ctx, int32_t* out, void* stream);
 
 /* timing hook for bench.py: the same transition with hipEvents recorded on `stream` around the stages; blocking.
  * All times in milliseconds for THIS call. */

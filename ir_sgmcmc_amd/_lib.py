@@ -258,6 +258,8 @@ SIGNATURES = {
     'irs_sparse_data_get': [_P, _I32P, _P],
     'irs_sparse_forward_set': [_P, _I],
     'irs_sparse_forward_get': [_P, _I32P, _P],
+    'irs_sparse_plan_set': [_P, _I],
+    'irs_sparse_plan_get': [_P, _I32P, _P],
     'irs_transition_timed': [_P, C.POINTER(IrsIO), _P, C.POINTER(IrsTimings)],
     'irs_comm_unique_id': [C.POINTER(C.c_uint8 * IRS_COMM_ID_BYTES)],
     'irs_comm_create_rccl': [C.POINTER(C.c_uint8 * IRS_COMM_ID_BYTES), _I, _I, C.POINTER(_P)],

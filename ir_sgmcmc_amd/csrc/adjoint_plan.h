@@ -164,6 +164,53 @@ IRS_HD int plan_run_bound(int columns, int D, int G, int forced_len) {
 // entries a step's list can hold: a column gives at most ceil(D / kPlanMinForced) run pieces and two fills
 IRS_HD int plan_entries_cap(int columns, int D) { return columns * ((D + kPlanMinForced - 1) / kPlanMinForced + 2); }
 
+// ---- plan reuse (adjoint_plan.hip, "plan reuse"): a list in the workspace is a pure function of its extent table, of what the host
+// passes to the launch that cuts it, and -- the adjoint -- of which chains left the radius-1 kernel.  Every list keeps a record of
+// those, and the launches that would rebuild it leave at once while the record still holds.
+// One entry of an extent table from a column's first and last non-zero plane (hi < 0: none): (D - lo, hi + 1), empty (0, 0).
+IRS_HD void plan_extent_entry(int lo, int hi, int D, int& a, int& b) {
+    a = hi < 0 ? 0 : D - lo;
+    b = hi < 0 ? 0 : hi + 1;
+}
+enum PlanSource { kSourceGradient = 0, kSourceMask = 1 };  // the table a list was cut from: g_warped's extents or the mask's
+constexpr int kPlanKeyLen = 20;
+// everything the host passes in that decides list k of a launch
+struct PlanKey {
+    int v[kPlanKeyLen];
+};
+// generation of an extent table: the extent pass adds to it whenever an entry changed, so a list cut from generation g is clean
+// for exactly as long as the table still says g (a consumer that was not launched for a while compares like any other)
+typedef unsigned long long PlanGen;
+struct PlanRecord {
+    int valid;       // zeroed memory is no record
+    unsigned dense;  // bit c: chain c was given full columns (chain_is_dense)
+    PlanGen gen;
+    PlanKey key;
+};
+// `lists`: how many lists the launch cuts (the adjoint's fills look at list k - 1, the dense flags at every step); `source`: PlanSource
+IRS_HD PlanKey plan_key(const PlanShape& s, int k, int lists, int forced_len, int C, int ext_chains, int D, int H, int W, int source,
+                        bool with_dense) {
+    PlanKey key;
+    const int before = k > 0 && plan_fill_of(s, k) == kFillNext ? plan_reach(s, k - 1) : -1;  // (plan_column_of reads the runs of list k - 1)
+    const int v[kPlanKeyLen] = {s.tx, s.ty, plan_reach(s, k), before, plan_fill_of(s, k), plan_resident_of(s, k), s.lmin,
+                                forced_len, C, ext_chains, D, H, W, source, with_dense ? 1 : 0, lists, k, 0, 0, 0};
+    for (int i = 0; i < kPlanKeyLen; ++i) key.v[i] = v[i];
+    return key;
+}
+IRS_HD bool plan_key_equal(const PlanKey& a, const PlanKey& b) {
+    bool eq = true;
+    for (int i = 0; i < kPlanKeyLen; ++i) eq = eq && a.v[i] == b.v[i];
+    return eq;
+}
+// the list a record describes is, byte for byte, what a rebuild with (key, dense, gen) would write
+IRS_HD bool plan_reusable(const PlanRecord& r, const PlanKey& key, unsigned dense, PlanGen gen) {
+    return r.valid == 1 && r.dense == dense && r.gen == gen && plan_key_equal(r.key, key);
+}
+IRS_HD PlanRecord plan_record(const PlanKey& key, unsigned dense, PlanGen gen) { return PlanRecord{1, dense, gen, key}; }
+// reach of the adjoint's list k of n: the gradient step k produces is zero further than n - k from the support of g_warped, which
+// itself lies within 2 S of the mask (S: LCC half width, SSD 0)
+IRS_HD int plan_adjoint_reach0(int n, int S, int source) { return source == kSourceMask ? 2 * S + n : n; }
+
 // workgroup id -> list position: runs of `run` consecutive entries (x-neighbouring tiles of one z band) stay on one XCD, as
 // common.h: xcd_swizzle_runs does for whole grids -- here for any count: the tail that fills no group of 8 runs keeps its order.
 IRS_HD int plan_swizzle(int id, int count, int run) {

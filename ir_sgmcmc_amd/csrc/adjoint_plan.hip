@@ -2,15 +2,17 @@
 //
 // The gradient that enters the adjoint is g_warped times d(warped)/d(d_n), and the data terms write g_warped = 0 off the mask.  A
 // radius-1 adjoint step (max|d_k| < 1 voxel) moves a gradient by less than one voxel, so the gradient that step k produces is
-// exactly zero further than m = no_steps - k voxels (Chebyshev) from the support of g_warped.  Three small launches in front of
+// exactly zero further than m = no_steps - k voxels (Chebyshev) from the support of g_warped.  Small launches in front of
 // the adjoint turn that into work lists, all on the device and in stream order:
-//   grad_extent_kernel   per voxel column (y, x) the z-extent of g_warped != 0 (integer atomic maxima into a zeroed table)
+//   grad_extent_kernel   per voxel column (y, x) the z-extent of g_warped != 0 -- only where the data plan has not formed the MASK's
+//                        table in this transition: g_warped lies within 2 S of the mask, and the lists are cut from that table
 //   plan_runs_kernel     per step and 32 x 8 tile column the run range: the hull of the extents, widened by m, of every voxel
 //                        column within m of the tile.  A chain one of whose steps leaves the radius-1 kernel gets full columns.
 //   plan_lists_kernel    per step the piece list: every run range cut into equal pieces of at most L planes, L the smallest length
 //                        whose list fits one resident set of workgroups; the planes the NEXT step's pieces read around their own
 //                        range but this step does not march become zero-fill entries behind the run pieces (the gradient buffers
 //                        ping-pong, so those planes hold an earlier transition's values).
+// A list whose inputs did not change since it was cut is left as it is ("plan reuse" below).
 // The splitting arithmetic is adjoint_plan.h (also run on the CPU by tests/csrc/adjoint_plan_check.cpp).
 //
 // Sparse data stage: the same three kernels, with the tile and the reach passed in (adjoint_plan.h: PlanShape), on the extents of
@@ -25,41 +27,90 @@
 
 namespace irs {
 
-constexpr int kExtChunk = 32;  // planes one thread of the extent kernel scans
+// ------------------------------------------------------------------------------------------------
+// extent pass: one workgroup owns its voxel columns over all of z -- kExtXL lanes along x (the mask: 4 columns each, read as one
+// 32-bit word where the rows allow it) times kExtZP parts of z, combined through LDS.  The owning thread compares the column's final
+// entry with the one in the table, stores only a changed one, and a workgroup that changed anything advances the table's generation
+// (adjoint_plan.h: PlanGen).  No clear and no atomics on entries: the zeroed workspace is a table of empty columns.
+// ------------------------------------------------------------------------------------------------
+constexpr int kExtXL = 32, kExtZP = kBlock / kExtXL;
+static_assert(kBlock == 256 && kExtZP == 8, "extent pass: 32 lanes x 8 parts of z");
 
-// T = float: g_warped (NaN counts as a gradient); T = uint8_t: the mask
-template <typename T>
-__device__ __forceinline__ void extent_body(const T* __restrict__ g, int* __restrict__ ext, const Vol& vol) {
-    const int x = (int)blockIdx.x * 64 + ((int)threadIdx.x & 63), y = (int)blockIdx.y * 4 + ((int)threadIdx.x >> 6);
-    const int nch = (vol.D + kExtChunk - 1) / kExtChunk;
-    const int chain = (int)blockIdx.z / nch, za = ((int)blockIdx.z - chain * nch) * kExtChunk, zb = min(za + kExtChunk, vol.D);
-    if (x >= vol.W || y >= vol.H) return;
+// T = float: g_warped, one column per lane (NaN counts as a gradient); T = uint8_t: the mask, CPL = 4 columns per lane
+template <typename T, int CPL, bool WORD>
+__device__ __forceinline__ void extent_body(const T* __restrict__ g, int* __restrict__ ext, PlanGen* __restrict__ gen, const Vol& vol) {
+    __shared__ int s_lo[kExtZP][kExtXL * CPL], s_hi[kExtZP][kExtXL * CPL];
+    const int lane = (int)threadIdx.x % kExtXL, part = (int)threadIdx.x / kExtXL;
+    const int x0 = ((int)blockIdx.x * kExtXL + lane) * CPL, y = (int)blockIdx.y, chain = (int)blockIdx.z;
+    const int per = (vol.D + kExtZP - 1) / kExtZP, za = min(part * per, vol.D), zb = min(za + per, vol.D);
     const int64_t plane = (int64_t)vol.H * vol.W;
-    const T* __restrict__ p = g + (int64_t)chain * vol.V + (int64_t)y * vol.W + x;
-    int lo = vol.D, hi = -1;
-#pragma unroll 8
-    for (int z = za; z < zb; ++z) {
-        const bool nz = p[z * plane] != (T)0;
-        lo = nz ? min(lo, z) : lo;
-        hi = nz ? z : hi;
+    const T* __restrict__ p = g + (int64_t)chain * vol.V + (int64_t)y * vol.W + x0;
+    int lo[CPL], hi[CPL];
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+        lo[j] = vol.D;
+        hi[j] = -1;
     }
-    if (hi < 0) return;
-    int* e = ext + ((int64_t)chain * plane + (int64_t)y * vol.W + x) * 2;
-    atomicMax(e, vol.D - lo);
-    atomicMax(e + 1, hi + 1);
+    if (x0 < vol.W) {
+#pragma unroll 8
+        for (int z = za; z < zb; ++z) {
+            if constexpr (WORD) {  // (W % 4 == 0: the four columns are inside the row together)
+                const unsigned w = *reinterpret_cast<const unsigned*>(p + z * plane);
+#pragma unroll
+                for (int j = 0; j < CPL; ++j) {
+                    const bool nz = ((w >> (8 * j)) & 0xffu) != 0u;
+                    lo[j] = nz ? min(lo[j], z) : lo[j];
+                    hi[j] = nz ? z : hi[j];
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < CPL; ++j) {
+                    const bool nz = x0 + j < vol.W && p[z * plane + j] != (T)0;
+                    lo[j] = nz ? min(lo[j], z) : lo[j];
+                    hi[j] = nz ? z : hi[j];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+        s_lo[part][lane * CPL + j] = lo[j];
+        s_hi[part][lane * CPL + j] = hi[j];
+    }
+    __syncthreads();
+    int changed = 0;
+    const int c = (int)threadIdx.x, x = (int)blockIdx.x * kExtXL * CPL + c;
+    if (c < kExtXL * CPL && x < vol.W) {
+        int l = vol.D, h = -1;
+#pragma unroll
+        for (int q = 0; q < kExtZP; ++q) {
+            l = min(l, s_lo[q][c]);
+            h = max(h, s_hi[q][c]);
+        }
+        int a, b;
+        plan_extent_entry(l, h, vol.D, a, b);
+        int2* e = reinterpret_cast<int2*>(ext + ((int64_t)chain * plane + (int64_t)y * vol.W + x) * 2);
+        const int2 old = *e;
+        if (old.x != a || old.y != b) {
+            *e = make_int2(a, b);
+            changed = 1;
+        }
+    }
+    if (__syncthreads_or(changed) && threadIdx.x == 0) atomicAdd(gen, (PlanGen)1);
 }
-__global__ __launch_bounds__(kBlock) void grad_extent_kernel(const float* __restrict__ g, int* __restrict__ ext, Vol vol) {
-    extent_body<float>(g, ext, vol);
+__global__ __launch_bounds__(kBlock) void grad_extent_kernel(const float* __restrict__ g, int* __restrict__ ext, PlanGen* __restrict__ gen, Vol vol) {
+    extent_body<float, 1, false>(g, ext, gen, vol);
 }
-__global__ __launch_bounds__(kBlock) void mask_extent_kernel(const uint8_t* __restrict__ mask, int* __restrict__ ext, Vol vol) {
-    extent_body<uint8_t>(mask, ext, vol);
+template <bool WORD>
+__global__ __launch_bounds__(kBlock) void mask_extent_kernel(const uint8_t* __restrict__ mask, int* __restrict__ ext, PlanGen* __restrict__ gen, Vol vol) {
+    extent_body<uint8_t, 4, WORD>(mask, ext, gen, vol);
 }
-static void launch_extent(const float* g, const uint8_t* mask, int* ext, int chains, Vol vol, hipStream_t st) {
-    (void)hipMemsetAsync(ext, 0, sizeof(int) * 2 * (size_t)chains * vol.H * vol.W, st);
-    const int nch = (vol.D + kExtChunk - 1) / kExtChunk;
-    const dim3 grid((unsigned)((vol.W + 63) / 64), (unsigned)((vol.H + 3) / 4), (unsigned)(nch * chains));
-    if (g) hipLaunchKernelGGL(grad_extent_kernel, grid, dim3(kBlock), 0, st, g, ext, vol);
-    else hipLaunchKernelGGL(mask_extent_kernel, grid, dim3(kBlock), 0, st, mask, ext, vol);
+static void launch_extent(const float* g, const uint8_t* mask, int* ext, PlanGen* gen, int chains, Vol vol, hipStream_t st) {
+    const int cols = kExtXL * (g ? 1 : 4);
+    const dim3 grid((unsigned)((vol.W + cols - 1) / cols), (unsigned)vol.H, (unsigned)chains);
+    if (g) hipLaunchKernelGGL(grad_extent_kernel, grid, dim3(kBlock), 0, st, g, ext, gen, vol);
+    else if (vol.W % 4 == 0 && (uintptr_t)mask % 4 == 0) hipLaunchKernelGGL(mask_extent_kernel<true>, grid, dim3(kBlock), 0, st, mask, ext, gen, vol);
+    else hipLaunchKernelGGL(mask_extent_kernel<false>, grid, dim3(kBlock), 0, st, mask, ext, gen, vol);
 }
 
 // rule 5 of the plan: a chain is marched sparsely only if EVERY step of it belongs to the radius-1 kernel (the same test as
@@ -75,26 +126,78 @@ __device__ __forceinline__ bool chain_is_dense(const unsigned* __restrict__ dmax
     return dense;
 }
 
+// ------------------------------------------------------------------------------------------------
+// plan reuse.  A family is the lists one marching kernel (or the warp: its hull, run ranges only) takes from one extent table; a
+// batch is the families one pair of launches cuts.  Every workgroup of the runs stage and the single workgroup per list of the
+// lists stage evaluate the same predicate (adjoint_plan.h: plan_reusable) on the same data -- the list's record, which only the
+// lists stage writes, behind the runs stage in stream order -- and leave at once when it holds.
+// ------------------------------------------------------------------------------------------------
+struct PlanFamily {
+    const int* ext;
+    const PlanGen* gen;
+    const unsigned* dmax;  // the adjoint: bounds of d_k, [no_steps][C][4]; else nullptr
+    int* runs;             // [lists][C tiles][2] (the hull: the warp's table itself)
+    ColPlan* colplan;
+    PlanEntry* entries;
+    int* count;
+    int* stats;
+    PlanRecord* rec;       // [lists]
+    int* counters;         // the family's {rebuilds, reuses}
+    int lists, ntx, nty, cap, forced_len, ext_chains, source, no_steps, runs_only;
+    PlanShape shape;
+};
+constexpr int kBatchFamilies = 3;
+struct PlanBatch {
+    PlanFamily f[kBatchFamilies];
+    int nf, reuse;
+};
+
+__device__ __forceinline__ unsigned dense_mask(const unsigned* __restrict__ dmax, int C, int no_steps) {
+    unsigned m = 0;
+    for (int c = 0; c < C; ++c) m |= chain_is_dense(dmax, c, C, no_steps) ? 1u << c : 0u;
+    return m;
+}
+// blockIdx -> family and list; false: beyond the batch
+__device__ __forceinline__ bool batch_list(const PlanBatch& b, int id, int& fi, int& k) {
+    fi = 0;
+    k = id;
+    while (fi < b.nf && k >= b.f[fi].lists) k -= b.f[fi++].lists;
+    return fi < b.nf;
+}
+__device__ __forceinline__ bool list_reusable(const PlanFamily& f, int k, int C, const Vol& vol, int reuse, PlanKey& key, unsigned& dense,
+                                              PlanGen& gen) {
+    key = plan_key(f.shape, k, f.lists, f.forced_len, C, f.ext_chains, vol.D, vol.H, vol.W, f.source, f.dmax != nullptr);
+    dense = dense_mask(f.dmax, C, f.no_steps);
+    gen = *f.gen;
+    return reuse != 0 && plan_reusable(f.rec[k], key, dense, gen);
+}
+
 // one wavefront per (tile column of a chain, list); ext_chains == 1: one extent table for every chain
-__global__ __launch_bounds__(kWave) void plan_runs_kernel(const int* __restrict__ ext, int ext_chains, const unsigned* __restrict__ dmax,
-                                                          int* __restrict__ runs, Vol vol, int C, int no_steps, int ntx, int nty,
-                                                          PlanShape shape) {
-    const int col = (int)blockIdx.x, k = (int)blockIdx.y, tiles = ntx * nty;
+__global__ __launch_bounds__(kWave) void plan_runs_kernel(PlanBatch batch, Vol vol, int C) {
+    int fi, k;
+    if (!batch_list(batch, (int)blockIdx.y, fi, k)) return;
+    const PlanFamily& f = batch.f[fi];
+    const int col = (int)blockIdx.x, ntx = f.ntx, tiles = ntx * f.nty;
+    if (col >= C * tiles) return;
+    PlanKey key;
+    unsigned dense;
+    PlanGen gen;
+    if (list_reusable(f, k, C, vol, batch.reuse, key, dense, gen)) return;
     const int chain = col / tiles, tile = col - chain * tiles, tx = tile % ntx, ty = tile / ntx;
-    int* out = runs + ((int64_t)k * C * tiles + col) * 2;
-    if (chain_is_dense(dmax, chain, C, no_steps)) {
+    int* out = f.runs + ((int64_t)k * C * tiles + col) * 2;
+    if (dense >> chain & 1u) {
         if (threadIdx.x == 0) {
             out[0] = 0;
             out[1] = vol.D;
         }
         return;
     }
-    const int m = plan_reach(shape, k);
+    const int m = plan_reach(f.shape, k);
     int x0, x1, y0, y1;
-    plan_tile_window(tx, shape.tx, m, vol.W, x0, x1);
-    plan_tile_window(ty, shape.ty, m, vol.H, y0, y1);
+    plan_tile_window(tx, f.shape.tx, m, vol.W, x0, x1);
+    plan_tile_window(ty, f.shape.ty, m, vol.H, y0, y1);
     const int nx = x1 - x0, n = nx * (y1 - y0);
-    const int* __restrict__ e = ext + (int64_t)(ext_chains == 1 ? 0 : chain) * vol.H * vol.W * 2;
+    const int* __restrict__ e = f.ext + (int64_t)(f.ext_chains == 1 ? 0 : chain) * vol.H * vol.W * 2;
     int lo = vol.D, hi = 0;
     for (int i = (int)threadIdx.x; i < n; i += kWave) {
         const int yy = i / nx, xx = i - yy * nx;
@@ -138,16 +241,35 @@ __device__ __forceinline__ int block_rank(bool flag, int* wave_tot, int& total) 
 // one workgroup per list (the adjoint: per step).  List order: piece index (z band) outermost, then chain, tile row, tile --
 // x-neighbouring tiles of one z band are consecutive; the fills behind the run pieces.  The column plans are formed once (the
 // adjoint: nine neighbour look-ups each) and kept in `colplan` for the passes that follow.
-__global__ __launch_bounds__(kPlanBlock) void plan_lists_kernel(const int* __restrict__ runs, const unsigned* __restrict__ dmax,
-                                                                ColPlan* __restrict__ colplan, PlanEntry* __restrict__ entries,
-                                                                int* __restrict__ count, int* __restrict__ stats, Vol vol, int C,
-                                                                int no_steps, int ntx, int nty, int cap, PlanShape shape, int forced_len) {
+// A list whose record still holds is left as it is (its `count` and `stats` rows with it); a rebuilt one gets its record here, by
+// the only workgroup that writes it.  The hull (runs_only) has no list: its workgroup only keeps the record.
+__global__ __launch_bounds__(kPlanBlock) void plan_lists_kernel(PlanBatch batch, Vol vol, int C) {
     __shared__ int pieces[kPlanMaxLen + 1], s_maxlen, s_L, s_nrun, wave_tot[kPlanBlock / kWave];
     __shared__ int s_pieces[IRS_MAX_CHAINS], s_planes[IRS_MAX_CHAINS];
-    const int k = (int)blockIdx.x, tiles = ntx * nty, cols = C * tiles, tid = (int)threadIdx.x;
+    int fi, k;
+    if (!batch_list(batch, (int)blockIdx.x, fi, k)) return;
+    const PlanFamily& f = batch.f[fi];
+    const int tid = (int)threadIdx.x;
+    PlanKey key;
+    unsigned dense;
+    PlanGen gen;
+    const bool keep = list_reusable(f, k, C, vol, batch.reuse, key, dense, gen);
+    if (tid == 0) atomicAdd(f.counters + (keep ? 1 : 0), 1);
+    if (keep) return;
+    if (f.runs_only) {
+        if (tid == 0) f.rec[k] = plan_record(key, dense, gen);
+        return;
+    }
+    const int* __restrict__ runs = f.runs;
+    PlanEntry* __restrict__ entries = f.entries;
+    int* __restrict__ count = f.count;
+    int* __restrict__ stats = f.stats;
+    const PlanShape& shape = f.shape;
+    const int ntx = f.ntx, nty = f.nty, cap = f.cap, forced_len = f.forced_len;
+    const int tiles = ntx * nty, cols = C * tiles;
     const int lmax = max(min(kPlanMaxLen, vol.D), 1), lmin = min(shape.lmin, lmax);
     const int fill = plan_fill_of(shape, k);
-    ColPlan* __restrict__ cps = colplan + (int64_t)k * cols;
+    ColPlan* __restrict__ cps = f.colplan + (int64_t)k * cols;
     for (int i = tid; i <= kPlanMaxLen; i += kPlanBlock) pieces[i] = 0;
     if (tid < IRS_MAX_CHAINS) s_pieces[tid] = s_planes[tid] = 0;
     if (tid == 0) s_maxlen = s_nrun = 0;
@@ -207,10 +329,11 @@ __global__ __launch_bounds__(kPlanBlock) void plan_lists_kernel(const int* __res
     if (tid == 0) {
         count[2 * k] = min(base, cap);
         count[2 * k + 1] = min(s_nrun, cap);
+        f.rec[k] = plan_record(key, dense, gen);
     }
     if (tid < C) {
         int* s = stats + ((int64_t)k * C + tid) * kPlanStats;
-        s[0] = chain_is_dense(dmax, tid, C, no_steps) ? 0 : 1;
+        s[0] = dense >> tid & 1u ? 0 : 1;
         s[1] = L;
         s[2] = s_pieces[tid];
         s[3] = s_planes[tid];
@@ -220,9 +343,10 @@ __global__ __launch_bounds__(kPlanBlock) void plan_lists_kernel(const int* __res
 static size_t plan_align(size_t b) { return (b + 255) / 256 * 256; }
 
 struct PlanLayout {
-    size_t ext, runs, colplan, entries, count, stats, total;
+    size_t ext, runs, colplan, entries, count, stats, rec, gen, counters, total;
     int cap, ntx, nty;
 };
+constexpr size_t kCounterBytes = sizeof(int) * 2;  // {rebuilds, reuses} of a family
 static PlanLayout plan_layout(Vol vol, int C, int no_steps, int tx = kPlanTX, int ty = kPlanTY, bool own_ext = true) {
     PlanLayout l;
     l.ntx = (vol.W + tx - 1) / tx;
@@ -237,6 +361,9 @@ static PlanLayout plan_layout(Vol vol, int C, int no_steps, int tx = kPlanTX, in
     l.entries = take(sizeof(PlanEntry) * (size_t)l.cap * no_steps);
     l.count = take(sizeof(int) * 2 * no_steps);
     l.stats = take(sizeof(int) * kPlanStats * (size_t)C * no_steps);
+    l.rec = take(sizeof(PlanRecord) * (size_t)no_steps);
+    l.gen = take(own_ext ? sizeof(PlanGen) : 0);
+    l.counters = take(kCounterBytes);
     l.total = off;
     return l;
 }
@@ -251,6 +378,9 @@ static AdjointPlan plan_views(char* base, const PlanLayout& l, bool own_ext) {
     p.entries = (PlanEntry*)(base + l.entries);
     p.count = (int*)(base + l.count);
     p.stats = (int*)(base + l.stats);
+    p.rec = (PlanRecord*)(base + l.rec);
+    p.gen = own_ext ? (PlanGen*)(base + l.gen) : nullptr;
+    p.counters = (int*)(base + l.counters);
     p.cap = l.cap;
     p.ntx = l.ntx;
     p.nty = l.nty;
@@ -258,15 +388,54 @@ static AdjointPlan plan_views(char* base, const PlanLayout& l, bool own_ext) {
 }
 AdjointPlan adjoint_plan_views(char* base, Vol vol, int C, int no_steps) { return plan_views(base, plan_layout(vol, C, no_steps), true); }
 
-void launch_adjoint_plan(const float* g_warped, const unsigned* dmax, const AdjointPlan& plan, int no_steps, int C, Vol vol,
-                         int64_t G, int forced_len, hipStream_t st) {
+// the lists of `plan`, cut from the table (ext, gen) of ext_chains chains
+static PlanFamily list_family(const AdjointPlan& plan, const int* ext, const PlanGen* gen, int ext_chains, int source, const unsigned* dmax,
+                              int lists, int forced_len, const PlanShape& shape) {
+    PlanFamily f{};
+    f.ext = ext;
+    f.gen = gen;
+    f.dmax = dmax;
+    f.runs = plan.runs;
+    f.colplan = plan.colplan;
+    f.entries = plan.entries;
+    f.count = plan.count;
+    f.stats = plan.stats;
+    f.rec = plan.rec;
+    f.counters = plan.counters;
+    f.lists = lists;
+    f.ntx = plan.ntx;
+    f.nty = plan.nty;
+    f.cap = plan.cap;
+    f.forced_len = forced_len;
+    f.ext_chains = ext_chains;
+    f.source = source;
+    f.no_steps = lists;
+    f.shape = shape;
+    return f;
+}
+// the runs launch and the lists launch of a batch
+static void launch_batch(PlanBatch& b, int C, Vol vol, int reuse, hipStream_t st) {
+    int cols = 0, lists = 0;
+    for (int i = 0; i < b.nf; ++i) {
+        cols = plan_max(cols, C * b.f[i].ntx * b.f[i].nty);
+        lists += b.f[i].lists;
+    }
+    b.reuse = reuse & 1;
+    hipLaunchKernelGGL(plan_runs_kernel, dim3((unsigned)cols, (unsigned)lists), dim3(kWave), 0, st, b, vol, C);
+    hipLaunchKernelGGL(plan_lists_kernel, dim3((unsigned)lists), dim3(kPlanBlock), 0, st, b, vol, C);
+}
+
+void launch_adjoint_plan(const float* g_warped, const DataPlan* mask_table, int mask_chains, int S, const unsigned* dmax, const AdjointPlan& plan,
+                         int no_steps, int C, Vol vol, int64_t G, int forced_len, int reuse, hipStream_t st) {
     const int g = (int)(G > 0 ? G : 1024);
-    const PlanShape shape{kPlanTX, kPlanTY, no_steps, 1, {kFillNext, kFillNext}, {g, g}, kPlanMinLen};
-    launch_extent(g_warped, nullptr, plan.ext, C, vol, st);
-    hipLaunchKernelGGL(plan_runs_kernel, dim3((unsigned)(C * plan.ntx * plan.nty), (unsigned)no_steps), dim3(kWave), 0, st, plan.ext, C, dmax,
-                       plan.runs, vol, C, no_steps, plan.ntx, plan.nty, shape);
-    hipLaunchKernelGGL(plan_lists_kernel, dim3((unsigned)no_steps), dim3(kPlanBlock), 0, st, plan.runs, dmax, plan.colplan, plan.entries, plan.count,
-                       plan.stats, vol, C, no_steps, plan.ntx, plan.nty, plan.cap, shape, forced_len);
+    const int source = mask_table ? kSourceMask : kSourceGradient;
+    const PlanShape shape{kPlanTX, kPlanTY, plan_adjoint_reach0(no_steps, S, source), 1, {kFillNext, kFillNext}, {g, g}, kPlanMinLen};
+    if (!mask_table) launch_extent(g_warped, nullptr, plan.ext, plan.gen, C, vol, st);
+    PlanBatch b{};
+    b.nf = 1;
+    b.f[0] = mask_table ? list_family(plan, mask_table->ext, mask_table->gen, mask_chains, source, dmax, no_steps, forced_len, shape)
+                        : list_family(plan, plan.ext, plan.gen, C, source, dmax, no_steps, forced_len, shape);
+    launch_batch(b, C, vol, reuse, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -281,22 +450,11 @@ AdjointPlan forward_plan_views(char* base, Vol vol, int C, int no_steps) {
 int forward_plan_run_bound(const AdjointPlan& plan, int C, Vol vol, int64_t G, int forced_len) {
     return plan_run_bound(C * plan.ntx * plan.nty, vol.D, (int)(G > 0 ? G : 1024), forced_len);
 }
-void launch_forward_plan(const int* ext, int ext_chains, const AdjointPlan& plan, const int* width, int S, int no_steps, int C, Vol vol,
-                         int64_t G, int forced_len, hipStream_t st) {
-    const int g = (int)(G > 0 ? G : 1024);
-    PlanShape shape{kWarpTX, kWarpTY, 0, 0, {kFillNone, kFillNone}, {g, g}, kPlanMinLen, no_steps, {}};
-    for (int k = 0; k < no_steps && k < kPlanMaxLists; ++k) shape.reach[k] = plan_forward_reach(width, no_steps, S, k);
-    hipLaunchKernelGGL(plan_runs_kernel, dim3((unsigned)(C * plan.ntx * plan.nty), (unsigned)no_steps), dim3(kWave), 0, st, ext, ext_chains, nullptr,
-                       plan.runs, vol, C, no_steps, plan.ntx, plan.nty, shape);
-    hipLaunchKernelGGL(plan_lists_kernel, dim3((unsigned)no_steps), dim3(kPlanBlock), 0, st, plan.runs, nullptr, plan.colplan, plan.entries, plan.count,
-                       plan.stats, vol, C, no_steps, plan.ntx, plan.nty, plan.cap, shape, forced_len);
-}
-
 // ------------------------------------------------------------------------------------------------
 // sparse data stage
 // ------------------------------------------------------------------------------------------------
 struct DataLayout {
-    size_t ext, runs, hull, colplan, entries, count, stats, nll, total;
+    size_t ext, runs, hull, colplan, entries, count, stats, nll, rec, gen, counters, total;
     int cap, ntx, nty, wtx, wty;
 };
 static DataLayout data_layout(Vol vol, int C) {
@@ -317,6 +475,9 @@ static DataLayout data_layout(Vol vol, int C) {
     l.count = take(sizeof(int) * 2 * 2);
     l.stats = take(sizeof(int) * kPlanStats * (size_t)C * 2);
     l.nll = take(sizeof(double) * (size_t)l.cap);
+    l.rec = take(sizeof(PlanRecord) * 3);
+    l.gen = take(sizeof(PlanGen));
+    l.counters = take(kCounterBytes);
     l.total = off;
     return l;
 }
@@ -334,6 +495,9 @@ DataPlan data_plan_views(char* base, Vol vol, int C) {
     p.count = (int*)(base + l.count);
     p.stats = (int*)(base + l.stats);
     p.nll = (double*)(base + l.nll);
+    p.rec = (PlanRecord*)(base + l.rec);
+    p.gen = (PlanGen*)(base + l.gen);
+    p.counters = (int*)(base + l.counters);
     p.cap = l.cap;
     p.ntx = l.ntx;
     p.nty = l.nty;
@@ -351,19 +515,51 @@ int data_plan_run_bound(const DataPlan& plan, int s, bool bwd, int C, Vol vol) {
     return plan_run_bound(C * plan.ntx * plan.nty, vol.D, data_list_resident(s, bwd, C), plan.forced_len);
 }
 
-void launch_data_plan(const uint8_t* mask, int mask_chains, const DataPlan& plan, int s, bool lists, int C, Vol vol, hipStream_t st) {
-    launch_extent(nullptr, mask, plan.ext, mask_chains, vol, st);
+// Everything in front of the forward pass, three launches: the mask's extent pass, then one runs and one lists launch over the warp's
+// hull (its record alone in the lists stage), the two lists of the LCC kernels (`lists`) and the forward steps' lists (`fplan`, with
+// the widths the host planned; nullptr: dense forward steps).  Records: DataPlan::rec[0 .. 1] the lists, [2] the hull.
+void launch_front_plans(const uint8_t* mask, int mask_chains, const DataPlan& plan, int s, bool lists, const AdjointPlan* fplan, const int* width,
+                        int no_steps, int64_t fwd_G, int fwd_forced, int C, Vol vol, int reuse, hipStream_t st) {
+    launch_extent(nullptr, mask, plan.ext, plan.gen, mask_chains, vol, st);
+    PlanBatch b{};
     // the warp's hull: reach 3 s with the LCC map behind it, the mask itself (s == 0) with the SSD residual
-    const PlanShape warp{kWarpTX, kWarpTY, 3 * s, 0, {kFillNone, kFillNone}, {1, 1}, kPlanMinLen};
-    hipLaunchKernelGGL(plan_runs_kernel, dim3((unsigned)(C * plan.wtx * plan.wty), 1u), dim3(kWave), 0, st, plan.ext, mask_chains, nullptr,
-                       plan.hull, vol, C, 1, plan.wtx, plan.wty, warp);
-    if (!lists) return;
-    const PlanShape lcc{kLccTX, kLccTY, 2 * s, s, {kFillAll, kFillNone}, {data_list_resident(s, true, C), data_list_resident(s, false, C)},
-                        kPlanMinLen};
-    hipLaunchKernelGGL(plan_runs_kernel, dim3((unsigned)(C * plan.ntx * plan.nty), 2u), dim3(kWave), 0, st, plan.ext, mask_chains, nullptr,
-                       plan.runs, vol, C, 2, plan.ntx, plan.nty, lcc);
-    hipLaunchKernelGGL(plan_lists_kernel, dim3(2u), dim3(kPlanBlock), 0, st, plan.runs, nullptr, plan.colplan, plan.entries, plan.count, plan.stats,
-                       vol, C, 2, plan.ntx, plan.nty, plan.cap, lcc, plan.forced_len);
+    PlanFamily& hull = b.f[b.nf++];
+    hull.ext = plan.ext;
+    hull.gen = plan.gen;
+    hull.runs = plan.hull;
+    hull.rec = plan.rec + 2;
+    hull.counters = plan.counters;
+    hull.lists = hull.no_steps = hull.runs_only = 1;
+    hull.ntx = plan.wtx;
+    hull.nty = plan.wty;
+    hull.ext_chains = mask_chains;
+    hull.source = kSourceMask;
+    hull.shape = PlanShape{kWarpTX, kWarpTY, 3 * s, 0, {kFillNone, kFillNone}, {1, 1}, kPlanMinLen};
+    if (lists) {
+        PlanFamily& f = b.f[b.nf++];
+        f = hull;
+        f.runs = plan.runs;
+        f.colplan = plan.colplan;
+        f.entries = plan.entries;
+        f.count = plan.count;
+        f.stats = plan.stats;
+        f.rec = plan.rec;
+        f.lists = f.no_steps = 2;
+        f.runs_only = 0;
+        f.ntx = plan.ntx;
+        f.nty = plan.nty;
+        f.cap = plan.cap;
+        f.forced_len = plan.forced_len;
+        f.shape = PlanShape{kLccTX, kLccTY, 2 * s, s, {kFillAll, kFillNone}, {data_list_resident(s, true, C), data_list_resident(s, false, C)},
+                            kPlanMinLen};
+    }
+    if (fplan) {
+        const int g = (int)(fwd_G > 0 ? fwd_G : 1024);
+        PlanShape shape{kWarpTX, kWarpTY, 0, 0, {kFillNone, kFillNone}, {g, g}, kPlanMinLen, no_steps, {}};
+        for (int k = 0; k < no_steps && k < kPlanMaxLists; ++k) shape.reach[k] = plan_forward_reach(width, no_steps, s, k);
+        b.f[b.nf++] = list_family(*fplan, plan.ext, plan.gen, mask_chains, kSourceMask, nullptr, no_steps, fwd_forced, shape);
+    }
+    launch_batch(b, C, vol, reuse, st);
 }
 
 }  // namespace irs

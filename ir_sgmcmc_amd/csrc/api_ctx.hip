@@ -52,6 +52,7 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     c->sparse_adjoint = true;  // (irs_sparse_adjoint_set)
     c->sparse_data = 1;        // (irs_sparse_data_set)
     c->sparse_forward = 1;     // (irs_sparse_forward_set)
+    c->sparse_plan = 1;        // (irs_sparse_plan_set)
     c->cfg = *cfg;
     c->C = C;
     c->vol = make_vol(D, H, W);
@@ -473,7 +474,6 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
         // the data term's list needs every chain in one launch (or a single chain); the per-chain launches keep their full columns
         const bool one_launch = C == 1 || (c->kn.data_batch != 0 && !(c->side && c->kn.chain_overlap != 0));
         data_on = !lcc ? 1 : one_launch ? 3 : 2;
-        launch_data_plan(io->mask, io->mask_chains, c->dplan, lcc ? cfg.lcc_s : 0, lcc, C, vol, st);
     }
     c->data_on = data_on;
     // Sparse forward steps (adjoint_plan.hip): d_j is only read within 3 S + h_j + ... + h_{n-1} of the mask -- by the warp, by the
@@ -497,11 +497,13 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
         c->fwd_width[k] = h;
     }
     c->fwd_on = fwd_on;
-    if (fwd_on) {
+    if (fwd_on)
         for (int k = 0; k < cfg.no_steps; ++k) vd.width[k] = (unsigned char)c->fwd_width[k];
-        launch_forward_plan(c->dplan.ext, io->mask_chains, c->fplan, c->fwd_width, lcc ? cfg.lcc_s : 0, cfg.no_steps, C, vol, exp_fwd_plan_resident(),
-                            fwd_forced, st);
-    }
+    // the mask's extent pass and the lists of the data stage and of the forward steps: three launches, which leave at once where the
+    // lists in the workspace are still what they would write (adjoint_plan.hip: plan reuse)
+    if (data_on > 0)
+        launch_front_plans(io->mask, io->mask_chains, c->dplan, lcc ? cfg.lcc_s : 0, lcc, fwd_on ? &c->fplan : nullptr, c->fwd_width, cfg.no_steps,
+                           exp_fwd_plan_resident(), fwd_forced, C, vol, c->sparse_plan, st);
     if (forward_pass(c, io, io->v, true, cfg.uniform_alpha > 0.0f, vs, warped, z, fuse_warp_bwd ? c->gA : nullptr, C, st, timed, data_on, fwd_on)) return 1;
     const int64_t field = (int64_t)C * 3 * vol.V;
     const float* d_last = c->steps + (int64_t)(cfg.no_steps - 1) * field;
@@ -570,7 +572,12 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
     const bool sparse = c->sparse_adjoint && c->plan.entries != nullptr &&
                         (global_knobs().march_seg > 0 || exp_bwd_dense_seg_len(vol, C) > kPlanMinLen);
     c->plan_on = sparse;
-    if (sparse) launch_adjoint_plan(c->gM, c->dmax, c->plan, cfg.no_steps, C, vol, exp_bwd_plan_resident(), global_knobs().march_seg, st);
+    // (with the mask's extent table formed above the lists are cut from it, at the reach of g_warped's support around the mask more:
+    // the same lists from transition to transition, and no pass over g_warped)
+    const bool from_mask = data_on > 0 && !(c->sparse_plan & 2);
+    if (sparse)
+        launch_adjoint_plan(c->gM, from_mask ? &c->dplan : nullptr, io->mask_chains, lcc ? cfg.lcc_s : 0, c->dmax, c->plan, cfg.no_steps, C, vol,
+                            exp_bwd_plan_resident(), global_knobs().march_seg, c->sparse_plan, st);
     LAUNCH_CHECK();
     if (timed) HIP_TRY(hipEventRecord(c->ev[3], st));
     const float* dense = c->ffd ? c->dense : vs;
@@ -724,6 +731,25 @@ int irs_sparse_adjoint_get(irs_ctx* c, int32_t* out, void* stream) {
     if (!c->plan.stats || !c->plan_on || c->n_enqueued == 0) return 0;  // full columns: nothing engaged
     if (irs_flush(c, stream)) return 1;
     HIP_TRY(hipMemcpyAsync(out, c->plan.stats, n * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+}
+
+int irs_sparse_plan_set(irs_ctx* c, int reuse) {
+    if (!c) return fail("irs_sparse_plan_set: null argument");
+    if (reuse < 0 || reuse > 3) return fail("irs_sparse_plan_set: bit 0 reuse, bit 1 the adjoint's lists from the gradient");
+    c->sparse_plan = reuse;
+    return 0;
+}
+
+int irs_sparse_plan_get(irs_ctx* c, int32_t* out, void* stream) {
+    if (!c || !out) return fail("irs_sparse_plan_get: null argument");
+    memset(out, 0, 6 * sizeof(int32_t));
+    if (!c->plan.counters || c->n_enqueued == 0) return 0;
+    if (irs_flush(c, stream)) return 1;
+    const int* src[3] = {c->dplan.counters, c->fplan.counters, c->plan.counters};
+    for (int i = 0; i < 3; ++i)
+        if (src[i]) HIP_TRY(hipMemcpyAsync(out + 2 * i, src[i], 2 * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return 0;
 }

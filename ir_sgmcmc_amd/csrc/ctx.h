@@ -68,6 +68,7 @@ struct irs_ctx {
     int sparse_forward = 1; // irs_sparse_forward_set: 0 dense forward steps; 1 only where a later kernel reads them (where the rule on
                             // sizes lets them); n >= 2: on whatever the size, pieces of n planes
     bool fwd_on = false;    // the last transition enqueued walked the forward lists ...
+    int sparse_plan = 1;    // irs_sparse_plan_set: bit 0 lists whose record holds are reused, bit 1 the adjoint's lists from g_warped always
     int fwd_width[32] = {}; // ... with these planned widths h_k (in its verdict: floor(max|d_k|) + 1 <= h_k)
     float* cmm;      // coarse (8^3 cells) min / max of d_k for the source boxes of the any-radius adjoint (kernels.h)
     unsigned* hint = nullptr;  // pinned host copy of dmax as of the last finished transition (written by finalize_kernel, read

@@ -72,6 +72,8 @@ void launch_field_absmax(const float* d, bool prescale, int no_steps, unsigned* 
 // ---- adjoint_plan.hip (which planes the adjoint squaring steps march: the support of the incoming gradient, on the device)
 struct PlanEntry;
 struct ColPlan;
+struct PlanRecord;
+struct DataPlan;
 struct AdjointPlan {   // views into one allocation of adjoint_plan_bytes()
     int* ext = nullptr;            // [C][H W][2]: (D - lo, hi) of the planes where g_warped != 0, per voxel column
     int* runs = nullptr;           // [no_steps][C tiles][2]: run range of every tile column
@@ -79,21 +81,24 @@ struct AdjointPlan {   // views into one allocation of adjoint_plan_bytes()
     PlanEntry* entries = nullptr;  // [no_steps][cap]
     int* count = nullptr;          // [no_steps][2] entries of a step's list, and how many of them (the first) are run pieces
     int* stats = nullptr;          // [no_steps][C][kPlanStats]
+    PlanRecord* rec = nullptr;     // [no_steps]: what every list was cut from (adjoint_plan.h: plan reuse)
+    unsigned long long* gen = nullptr;  // generation of `ext`
+    int* counters = nullptr;       // {lists rebuilt, lists reused} since irs_create
     int cap = 0, ntx = 0, nty = 0;
 };
 size_t adjoint_plan_bytes(Vol vol, int C, int no_steps);
 AdjointPlan adjoint_plan_views(char* base, Vol vol, int C, int no_steps);
 // extents of g_warped ([C][V]) -> run ranges -> piece lists of all steps; dmax: [no_steps][C][4] bounds of d_k; G: resident set
-// the lists are cut for; forced_len > 0: that piece length
-void launch_adjoint_plan(const float* g_warped, const unsigned* dmax, const AdjointPlan& plan, int no_steps, int C, Vol vol,
-                         int64_t G, int forced_len, hipStream_t st);
+// the lists are cut for; forced_len > 0: that piece length.  mask_table: the data plan whose extent table of the MASK this transition
+// has formed (mask_chains chains; S: LCC half width, SSD 0) -- the lists are cut from it at reach 2 S + (n - k), a superset of the
+// gradient's support, and g_warped is not scanned; nullptr: from g_warped's own extents.  reuse bit 0: lists whose record holds stay
+void launch_adjoint_plan(const float* g_warped, const DataPlan* mask_table, int mask_chains, int S, const unsigned* dmax, const AdjointPlan& plan,
+                         int no_steps, int C, Vol vol, int64_t G, int forced_len, int reuse, hipStream_t st);
 // Sparse forward steps: one run-piece list per squaring step over the 64 x 8 columns of the forward tile, from the extent table of
 // the data plan (`ext`, formed in front of the forward pass) and the widths the host planned: list k (the step that writes d_{k+1})
 // is the hull of mask (+) (3 S + width[k+1] + ... + width[n-1]).  The views are an AdjointPlan without an extent table of its own.
 size_t forward_plan_bytes(Vol vol, int C, int no_steps);
 AdjointPlan forward_plan_views(char* base, Vol vol, int C, int no_steps);
-void launch_forward_plan(const int* ext, int ext_chains, const AdjointPlan& plan, const int* width, int S, int no_steps, int C, Vol vol,
-                         int64_t G, int forced_len, hipStream_t st);
 int forward_plan_run_bound(const AdjointPlan& plan, int C, Vol vol, int64_t G, int forced_len);  // most run pieces a step's list can have
 // the forward step on step `step`'s list (exp_kernels.hip): the radius-1 tile body, bound of the marched pieces into dmax_out
 void launch_exp_step_fwd_plan(const float* din, float* dout, bool prescale, int no_steps, int C, Vol vol, Lin lin, unsigned* dmax_out, int lay,
@@ -112,14 +117,19 @@ struct DataPlan {
     int* count = nullptr;          // [2][2] entries of a list, and how many of them (the first) are run pieces
     int* stats = nullptr;          // [2][C][kPlanStats]
     double* nll = nullptr;         // [cap]: -log p summed over run piece i of the data term's list
+    PlanRecord* rec = nullptr;     // [3]: the two lists and the hull (adjoint_plan.h: plan reuse)
+    unsigned long long* gen = nullptr;  // generation of `ext`
+    int* counters = nullptr;       // {lists rebuilt, lists reused} since irs_create (the hull counts as a list)
     int cap = 0, ntx = 0, nty = 0, wtx = 0, wty = 0;
     int forced_len = 0;            // > 0: the piece length of both lists (irs_sparse_data_set); 0: the shortest that fits a resident set
 };
 size_t data_plan_bytes(Vol vol, int C);
 DataPlan data_plan_views(char* base, Vol vol, int C);
 // mask: (mask_chains, V), mask_chains 1 or C; s: LCC half width (0: SSD); lists: false builds the hull alone.  The lists are cut for
-// the resident sets of the list-walking LCC kernels, or to plan.forced_len
-void launch_data_plan(const uint8_t* mask, int mask_chains, const DataPlan& plan, int s, bool lists, int C, Vol vol, hipStream_t st);
+// the resident sets of the list-walking LCC kernels, or to plan.forced_len.  fplan (optional): the forward steps' lists in the same
+// launches, from the planned widths `width` (list k: the hull of mask (+) (3 S + width[k+1] + ... + width[n-1])).  reuse as above
+void launch_front_plans(const uint8_t* mask, int mask_chains, const DataPlan& plan, int s, bool lists, const AdjointPlan* fplan, const int* width,
+                        int no_steps, int64_t fwd_G, int fwd_forced, int C, Vol vol, int reuse, hipStream_t st);
 // most run pieces the data term's (bwd) / the map's list can have: the marching grid of its kernel
 int data_plan_run_bound(const DataPlan& plan, int s, bool bwd, int C, Vol vol);
 

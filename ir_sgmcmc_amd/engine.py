@@ -207,6 +207,18 @@ class TransitionEngine:
         keys = ('engaged', 'piece_len', 'pieces', 'run_planes', 'width')
         return [[dict(zip(keys, buf[(k * ch + c) * 5:(k * ch + c) * 5 + 5])) for c in range(ch)] for k in range(n)]
 
+    def set_sparse_plan(self, reuse):
+        """irs_sparse_plan_set: bit 0 -> piece lists whose inputs did not change are kept (default); 0 -> every list is rebuilt in every
+        transition; bit 1 -> the adjoint's lists always from the extents of g_warped (A/B and parity runs)"""
+        L.check(self.lib.irs_sparse_plan_set(self._ctx, int(reuse)))
+
+    @_on_device
+    def sparse_plan(self):
+        """irs_sparse_plan_get: per family in ('data', 'forward', 'adjoint') dict(rebuilds, reuses): lists since the context was made"""
+        buf = (C.c_int32 * 6)()
+        L.check(self.lib.irs_sparse_plan_get(self._ctx, buf, self._stream()))
+        return {name: dict(rebuilds=int(buf[2 * i]), reuses=int(buf[2 * i + 1])) for i, name in enumerate(('data', 'forward', 'adjoint'))}
+
     # ---------------------------------------------------------------- small state
     @property
     def workspace_bytes(self):
