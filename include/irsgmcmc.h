@@ -889,6 +889,42 @@ int irs_landmark_finalize(const double* mean, const double* comoment, const doub
                           const double* tre_max, const int32_t* count, const float* target, int K, double* out, long long* isummary,
                           double* fsummary, void* ws, size_t ws_bytes, void* stream);
 
+/* Structure report (absent in the reference, whose every summary is one number over the mask): per structure of the fixed
+ * segmentation, the sums behind the posterior of its mean displacement and of its volume change, reduced from ONE recorded
+ * sample per row, and the same labelled reduction over finished per-voxel maps.  seg_fixed (D,H,W) int16 is shared by the rows;
+ * structure j is label value labels[j] (HOST int32, n_labels = K in 1 .. IRS_MAX_LABELS, distinct, in the int16 range).  Voxel p
+ * belongs to structure j when seg_fixed[p] == labels[j] and, with mask (D,H,W) uint8 given (NULL: none), mask[p] != 0; every
+ * other value of the map -- 0, negative values and unlisted labels included -- belongs to no structure.
+ *  - irs_structure_motion: displacement (C,3,D,H,W) float32 in voxels as the transition writes it, transformation (C,3,D,H,W)
+ *    float32 in [-1,1] coordinates (required), C in 1 .. IRS_MAX_CHAINS, every dim >= 2 (det J reads a neighbour); scale: 3
+ *    host floats, finite and > 0, one per channel.  Per (chain, structure), over the structure's voxels: ints (C,K,
+ *    IRS_STRUCTURE_MOTION_INTS) int64 {voxels, folded}; floats (C,K,IRS_STRUCTURE_MOTION_FLOATS) doubles {sum w_x, sum w_y,
+ *    sum w_z, sum |w|, sum |w|^2, max |w|, sum det J, min det J, max det J}.  w_c = (double)u_c * (double)scale_c (exact);
+ *    |w|^2 = (w_x^2 + w_y^2) + w_z^2 and |w| = sqrt(|w|^2) in double, every operation rounded once.  det J is the float32 value
+ *    irs_log_det_jacobian and irs_jacobian_posterior_update form (the same device function), converted to double; a voxel is
+ *    folded when !(det > 0), NaN included, and a NaN det is left out of the three det columns (the columns do not tell how
+ *    many were).  A non-finite displacement propagates into its structure's sums; the maximum drops a NaN, as fmax does.
+ *  - irs_structure_map_stats: maps (M,D,H,W) float32, any M >= 1, every dim >= 1.  Per (map, structure): ints (M,K,
+ *    IRS_STRUCTURE_MAP_INTS) int64 {finite, non_finite} values; floats (M,K,IRS_STRUCTURE_MAP_FLOATS) doubles {sum x, sum x^2,
+ *    min, max} over the finite values, x^2 formed in double (exact).
+ *  An empty structure gives integers 0 and sums 0.0; a maximum nothing entered stays -inf, a minimum +inf.  The output
+ *  pointers are device arrays and may point into a larger series buffer.  ws: device workspace of irs_structure_workspace bytes,
+ *  rows = C or M.  Two stages: per block of the stream, per wavefront and distinct structure a shuffle reduction into the
+ *  wavefront's own table, the tables merged in order; then the blocks' partials folded in block order.  Sums in double in an
+ *  order fixed by the shapes and the label map, no floating-point atomics, exact counts: two identical calls are bit-identical.
+ *  A refused call writes nothing.  No host sync. */
+#define IRS_STRUCTURE_MOTION_INTS 2
+#define IRS_STRUCTURE_MOTION_FLOATS 9
+#define IRS_STRUCTURE_MAP_INTS 2
+#define IRS_STRUCTURE_MAP_FLOATS 4
+int irs_structure_workspace(int D, int H, int W, int n_labels, int rows, size_t* bytes);
+int irs_structure_motion(const float* displacement, const float* transformation, int C, int D, int H, int W, const int16_t* seg_fixed,
+                         const int32_t* labels, int n_labels, const uint8_t* mask, const float* scale, long long* ints,
+                         double* floats, void* ws, size_t ws_bytes, void* stream);
+int irs_structure_map_stats(const float* maps, int M, int D, int H, int W, const int16_t* seg_fixed, const int32_t* labels,
+                            int n_labels, const uint8_t* mask, long long* ints, double* floats, void* ws, size_t ws_bytes,
+                            void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * fused transition (Trainer._SGLD_transition, trainer/trainer.py:291-356)
  * ---------------------------------------------------------------------------------------------- */

@@ -20,6 +20,7 @@ IRS_HAUSDORFF_MAX_PERCENTILES = 4
 IRS_LABEL_BINS = 10
 IRS_JACOBIAN_SUMMARY_INTS, IRS_JACOBIAN_SUMMARY_FLOATS = 4, 5
 IRS_JACOBIAN_WS_BYTES = 1024 * (IRS_JACOBIAN_SUMMARY_INTS + IRS_JACOBIAN_SUMMARY_FLOATS) * 8
+IRS_STRUCTURE_MOTION_INTS, IRS_STRUCTURE_MOTION_FLOATS, IRS_STRUCTURE_MAP_INTS, IRS_STRUCTURE_MAP_FLOATS = 2, 9, 2, 4
 IRS_IMAGE_POSTERIOR_MAX_VOLUMES, IRS_IMAGE_POSTERIOR_SUMMARY_INTS, IRS_IMAGE_POSTERIOR_SUMMARY_FLOATS = 8, 4, 6
 IRS_IMAGE_POSTERIOR_WS_BYTES = 1024 * (IRS_IMAGE_POSTERIOR_SUMMARY_INTS + IRS_IMAGE_POSTERIOR_SUMMARY_FLOATS) * 8
 IRS_COVARIANCE_SUMMARY_INTS, IRS_COVARIANCE_SUMMARY_FLOATS = 2, 8
@@ -187,6 +188,9 @@ SIGNATURES = {
     'irs_label_posterior_finalize': [_P, _I, _I, _I, _I, _I, _I32P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],
     'irs_jacobian_posterior_update': [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P],
     'irs_jacobian_posterior_finalize': [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],
+    'irs_structure_workspace': [_I, _I, _I, _I, _I, C.POINTER(C.c_size_t)],
+    'irs_structure_motion': [_P, _P, _I, _I, _I, _I, _P, _I32P, _I, _P, C.POINTER(C.c_float), _P, _P, _P, C.c_size_t, _P],
+    'irs_structure_map_stats': [_P, _I, _I, _I, _I, _P, _I32P, _I, _P, _P, _P, _P, C.c_size_t, _P],
     'irs_image_posterior_update': [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P],
     'irs_image_posterior_finalize': [_P, _P, _P, _P, _I, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],
     'irs_displacement_covariance_update': [_P, _I, _I, _I, _I, _P, _P, _I, _P],

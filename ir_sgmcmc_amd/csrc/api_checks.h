@@ -87,6 +87,15 @@ inline bool mask_volumes_ok(const char* who, int C, int D, int H, int W) {
     return (int64_t)C * D <= 65535 || !fail("%s: %d volumes of %d planes are more than the 65535 rows of one launch", who, C, D);
 }
 
+// the volume and the structure count of a structure-report call (structure_kernels.hip): every extent >= min_dim (2 where det J
+// reads a neighbour, else 1), fewer than 2^30 voxels, K structures in 1 .. IRS_MAX_LABELS
+inline bool structure_shape_ok(const char* who, int D, int H, int W, int min_dim, int K) {
+    if (D < min_dim || H < min_dim || W < min_dim)
+        return !fail("%s: dims (%d, %d, %d), every one >= %d needed", who, D, H, W, min_dim);
+    if ((int64_t)D * H * W >= ((int64_t)1 << 30)) return !fail("%s: the volume must have fewer than 2^30 voxels", who);
+    return (K >= 1 && K <= IRS_MAX_LABELS) || !fail("%s: K = %d structures, 1..%d", who, K, IRS_MAX_LABELS);
+}
+
 inline SplineTaps make_spline(int cps) {
     // sampled cubic B-spline (utils/transformation.py:79-102); evaluated in double, stored as float like the reference
     SplineTaps t;

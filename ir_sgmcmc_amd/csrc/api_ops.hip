@@ -798,6 +798,49 @@ int irs_jacobian_posterior_finalize(const int32_t* folds, const float* mean, con
 }
 
 // ================================================================================================
+// structure report (structure_kernels.hip)
+// ================================================================================================
+int irs_structure_workspace(int D, int H, int W, int n_labels, int rows, size_t* bytes) {
+    if (!bytes) return fail("irs_structure_workspace: bad arguments");
+    if (!structure_shape_ok(__func__, D, H, W, 1, n_labels)) return 1;
+    if (rows < 1) return fail("irs_structure_workspace: rows = %d, at least 1 needed", rows);
+    *bytes = structure_workspace_bytes((int64_t)D * H * W, n_labels, rows);
+    return 0;
+}
+
+int irs_structure_motion(const float* displacement, const float* transformation, int C, int D, int H, int W, const int16_t* seg_fixed,
+                         const int32_t* labels, int n_labels, const uint8_t* mask, const float* scale, long long* ints,
+                         double* floats, void* ws, size_t ws_bytes, void* stream) {
+    if (!displacement || !transformation || !seg_fixed || !labels || !scale || !ints || !floats || !ws)
+        return fail("irs_structure_motion: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!structure_shape_ok(__func__, D, H, W, 2, n_labels)) return 1;
+    if (!distinct_labels_ok(__func__, labels, n_labels)) return 1;
+    if (!positive3(__func__, "scale", scale)) return 1;
+    const Vol vol = make_vol(D, H, W);
+    if (!workspace_ok(__func__, ws_bytes, structure_workspace_bytes(vol.V, n_labels, C), "irs_structure_workspace")) return 1;
+    launch_structure_motion(displacement, transformation, seg_fixed, surf_labels(labels, n_labels), n_labels, mask, scale, ints, floats,
+                            ws, C, vol, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_structure_map_stats(const float* maps, int M, int D, int H, int W, const int16_t* seg_fixed, const int32_t* labels,
+                            int n_labels, const uint8_t* mask, long long* ints, double* floats, void* ws, size_t ws_bytes,
+                            void* stream) {
+    if (!maps || !seg_fixed || !labels || !ints || !floats || !ws) return fail("irs_structure_map_stats: bad arguments");
+    if (M < 1) return fail("irs_structure_map_stats: M = %d maps, at least 1 needed", M);
+    if (!structure_shape_ok(__func__, D, H, W, 1, n_labels)) return 1;
+    if (!distinct_labels_ok(__func__, labels, n_labels)) return 1;
+    const int64_t V = (int64_t)D * H * W;
+    if (!workspace_ok(__func__, ws_bytes, structure_workspace_bytes(V, n_labels, M), "irs_structure_workspace")) return 1;
+    launch_structure_map_stats(maps, M, V, seg_fixed, surf_labels(labels, n_labels), n_labels, mask, ints, floats, ws,
+                               (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // image posterior (image_posterior_kernels.hip)
 // ================================================================================================
 int irs_image_posterior_update(const float* volumes, int S, const float* transformation, int C, int D, int H, int W, float* mean,

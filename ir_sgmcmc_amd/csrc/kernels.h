@@ -310,6 +310,19 @@ void launch_jacobian_finalize(const int32_t* folds, const float* mean, const flo
                               float* fold_prob, float* logj_mean, float* logj_std, long long* isummary, double* fsummary,
                               void* ws, hipStream_t st);
 
+// ---- structure_kernels.hip: structure report (absent in the reference); arithmetic in structure_device.h
+// blocks per row of both first stages, and the bytes of partials `rows` rows (chains, or maps) of K structures need
+int structure_blocks(int64_t V);
+size_t structure_workspace_bytes(int64_t V, int K, int64_t rows);
+// displacement, transformation (C,3,V) float32; seg_fixed (V) int16 shared by the chains; mask (V) uint8 or nullptr; scale: 3 host
+// floats; ints (C,K,IRS_STRUCTURE_MOTION_INTS) int64, floats (C,K,IRS_STRUCTURE_MOTION_FLOATS) doubles; ws: structure_workspace_bytes
+void launch_structure_motion(const float* displacement, const float* transformation, const int16_t* seg_fixed, const SurfLabels& lab,
+                             int K, const uint8_t* mask, const float* scale, long long* ints, double* floats, void* ws, int C, Vol vol,
+                             hipStream_t st);
+// maps (M,V) float32, any M >= 1; ints (M,K,IRS_STRUCTURE_MAP_INTS) int64, floats (M,K,IRS_STRUCTURE_MAP_FLOATS) doubles
+void launch_structure_map_stats(const float* maps, int64_t M, int64_t V, const int16_t* seg_fixed, const SurfLabels& lab, int K,
+                                const uint8_t* mask, long long* ints, double* floats, void* ws, hipStream_t st);
+
 // ---- covariance_kernels.hip: displacement covariance posterior (absent in the reference); arithmetic in covariance_device.h
 // x (C,3,V) float32; mean (3,V), comoment (6,V: xx, yy, zz, xy, xz, yz) float32: Welford moments, the C chains folded in order
 // after `records_before` records

@@ -91,6 +91,13 @@ on the image's own voxel grid: at a recorded step every chain's displacement is 
 and the trilinear sample of the native moving volumes are folded in one fused launch that forms no warped volume
 (native_posterior.native_posterior_update), 4 K + 16 bytes per native voxel whatever the number of records; the finalizers of the
 label and the image posterior then run on the native extents, with the volumes in mm^3 under the header zooms.
+
+The structure report (StructureReport, structure_report.structure_report_options) is the one recorder that answers per anatomical
+structure and the second that keeps a series: at a recorded step one labelled reduction of every chain's displacement and
+transformation over the structures of the fixed segmentation (structure_report.structure_motion) writes 11 numbers per chain and
+structure into a device series allocated once, 88 * K bytes per record; at the end the host turns the series into the posterior
+of every structure's mean displacement and volume change, and the same reduction over the finished maps of the other options
+(structure_report.structure_map_stats) gives their per-structure rows.
 """
 import math
 import numbers
@@ -106,6 +113,7 @@ from . import modes as _modes
 from . import ops
 from . import posterior_comparison as _pc
 from . import residual_check as _rc
+from . import structure_report as _sr
 
 
 def diagnostics_period(cfg_trainer):
@@ -915,6 +923,81 @@ class DisplacementModes(_Recorder):
         self.dev['gram'].copy_(sd['gram'])
         self.dev['n'] = self.records = n
         self.steps, self.chains = [int(s) for s in sd['steps']], [int(c) for c in sd['chains']]
+
+
+class StructureReport(_Recorder):
+    """Per structure of the fixed segmentation, the series of the per-record sums behind the posterior of its mean displacement
+    and of its volume change (structure_report.py): two device arrays, (steps * C, K, 2) int64 and (steps * C, K, 9) float64,
+    allocated once -- the number of records is known from the config -- and written row by row.  `record((displacement,
+    transformation))` takes the (C,3,D,H,W) float32 outputs of one step, chains in order, and one launch writes rows records ..
+    records + C of both; `finalize` copies the series to the host once and gives the per-structure table."""
+    noun = 'structure report'
+    exceed = 'exceed the {} rows the series was allocated for'
+
+    def __init__(self, seg_fixed, structures_dict, capacity, device, scale=(1.0, 1.0, 1.0), mask=None):
+        if seg_fixed.dim() < 3 or seg_fixed.numel() != int(np.prod(seg_fixed.shape[-3:])):
+            raise ValueError(f'structure report: seg_fixed must be one (D,H,W) volume, got {tuple(seg_fixed.shape)}')
+        self.dims = tuple(int(d) for d in seg_fixed.shape[-3:])
+        if min(self.dims) < 2:
+            raise ValueError(f'structure report: three dims of at least 2, got {self.dims}')
+        if not structures_dict:
+            raise ValueError('structure report: structures_dict is empty')
+        self.names, self.labels = list(structures_dict), [int(v) for v in structures_dict.values()]
+        if len(self.labels) > _L.IRS_MAX_LABELS:
+            raise ValueError(f'structure report: {len(self.labels)} structures, at most {_L.IRS_MAX_LABELS}')
+        self.device, self.max_records = device, int(capacity)
+        if self.max_records < 1:
+            raise ValueError(f'structure report: room for {capacity} records, at least 1 needed')
+        self.scale = tuple(float(s) for s in scale)
+        self.seg_fixed = seg_fixed.reshape(self.dims).to(device=device, dtype=torch.int16).contiguous()
+        self.mask = _bool_mask(mask, device)
+        K = len(self.labels)
+        self.ints = torch.zeros((self.max_records, K, _L.IRS_STRUCTURE_MOTION_INTS), device=device, dtype=torch.int64)
+        self.floats = torch.zeros((self.max_records, K, _L.IRS_STRUCTURE_MOTION_FLOATS), device=device, dtype=torch.float64)
+
+    def record(self, sample):
+        displacement, transformation = sample
+        if tuple(displacement.shape) != tuple(transformation.shape):
+            raise ValueError(f'structure report: displacement {tuple(displacement.shape)} and transformation '
+                             f'{tuple(transformation.shape)} differ in shape')
+        C = displacement.shape[0]
+        if self.records + C > self.max_records:
+            raise ValueError(f'{self.noun}: {self.records} + {C} records {self.exceed.format(self.max_records)}')
+        self._update(displacement, transformation)
+        self.records += C
+
+    def _update(self, displacement, transformation):
+        rows = slice(self.records, self.records + displacement.shape[0])
+        _sr.structure_motion(displacement, transformation, self.seg_fixed, self.labels, self.scale, self.mask,
+                             out=(self.ints[rows], self.floats[rows]))
+
+    def series(self):
+        """-> (ints (records,K,2) int64, floats (records,K,9) float64) as numpy: ONE device-to-host copy"""
+        self._need_records('series')
+        both = torch.cat([self.ints[:self.records].view(torch.float64), self.floats[:self.records]], dim=2).cpu()
+        ni = _L.IRS_STRUCTURE_MOTION_INTS
+        return both[..., :ni].contiguous().view(torch.int64).numpy(), both[..., ni:].contiguous().numpy()
+
+    def map_stats(self, maps):
+        """structure_report.structure_map_stats of (M,D,H,W) float32 maps over this report's structures, on the device"""
+        return _sr.structure_map_stats(maps, self.seg_fixed, self.labels, self.mask)
+
+    def finalize(self, spacing=(1.0, 1.0, 1.0), chains=1, cov_trace=None):
+        """-> (summary dict of structure_report.structure_summary, (ints, floats) of series())"""
+        ints, floats = self.series()
+        return _sr.structure_summary(ints, floats, self.names, spacing, chains, cov_trace), (ints, floats)
+
+    def state_dict(self):
+        return {'ints': self.ints.detach().cpu(), 'floats': self.floats.detach().cpu(), 'records': self.records}
+
+    def load_state_dict(self, sd):
+        for key, t in (('ints', self.ints), ('floats', self.floats)):
+            if tuple(sd[key].shape) != tuple(t.shape):
+                raise ValueError(f'structure report series of shape {tuple(sd[key].shape)} ({key}) does not match this run '
+                                 f'({tuple(t.shape)})')
+        self.ints.copy_(sd['ints'])
+        self.floats.copy_(sd['floats'])
+        self.records = int(sd['records'])
 
 
 COMPARISON_OPTION_KEYS = ('period', 'std_floor')

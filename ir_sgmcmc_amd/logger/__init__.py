@@ -315,6 +315,18 @@ def save_landmarks(logger, save_dirs, mean_points, table, columns, unit, model='
     logger.info(f'{model} landmarks{tag}: {len(table)} rows in {unit} -> {model}_landmarks{tag}.csv, {model}_landmarks{tag}_mean.vtk')
 
 
+def save_structure_report(logger, save_dirs, table, series, model='MCMC'):
+    """the structure report (absent in the reference): samples/{model}_structures.csv, one row per structure -- the motion
+    columns, then the map columns -- and samples/{model}_structure_series.csv, one row per record and structure; `table` and
+    `series` are the (header, rows) of structure_report.structures_csv / series_csv (floats by repr: they read back exactly)"""
+    from ..structure_report import write_csv
+    folder = _folder(save_dirs, 'samples')
+    write_csv(path.join(folder, f'{model}_structures.csv'), *table)
+    write_csv(path.join(folder, f'{model}_structure_series.csv'), *series)
+    logger.info(f'{model} structure report: {len(table[1])} structures, {len(series[1])} series rows -> {model}_structures.csv, '
+                f'{model}_structure_series.csv')
+
+
 def _nan_to_zero(im):
     """-> (the map with 0 where it is NaN, how many voxels that was)"""
     nan = im.isnan()

@@ -72,7 +72,7 @@ def modes_gram(state):
     return state['gram'][:, :n, :n].cpu().numpy()
 
 
-def _split_rhat(series):
+def split_rhat_series(series):
     """scalar split-R-hat (Gelman et al., BDA3 section 11.4) of `series` (C, N): every chain's N values in order, halves of
     N // 2 (the middle one of an odd count goes to neither) -- ops.split_rhat's formula: sqrt(var+ / W), 1 where W = B = 0, inf
     where W = 0 < B"""
@@ -136,7 +136,7 @@ def modes_decompose(G3, scale, mask_voxels, chain=None, M=8):
         if len(ids) >= 2 and min(counts) >= 4:
             N = min(counts)
             for m in range(K):
-                rhat[m] = _split_rhat(np.stack([scores[chain == c, m][:N] for c in ids]))
+                rhat[m] = split_rhat_series(np.stack([scores[chain == c, m][:N] for c in ids]))
     return {'n': n, 'eigenvalues': lam, 'var_total': var_total, 'explained': explained, 'n90': n90, 'participation': participation,
             'std': std, 'scores': scores, 'coeff': np.ascontiguousarray(coeff), 'eigenvectors': U[:, :K], 'rhat': rhat}
 

@@ -21,6 +21,7 @@ from .diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ICE_SPACES, JA
                           posterior_comparison_options, residual_check_metric_names, residual_check_options,
                           native_posterior_metric_names, native_posterior_options, native_resolution_options, surface_metric_names, surface_posterior_options)
 from .logger import setup_logging
+from .structure_report import structure_metric_names, structure_report_options
 from .model import distributions as model_distr
 from .model import loss as model_loss
 from .optimizers import Adam
@@ -151,6 +152,8 @@ class ConfigParser:
         native_posterior = native_posterior_options(self['trainer'])
         if native_posterior is not None:
             m += native_posterior_metric_names(native_posterior, self.structures_dict)
+        if structure_report_options(self['trainer']) is not None:
+            m += structure_metric_names(self['trainer'], self.structures_dict)
         return m
 
     def init_transformation_and_registration_modules(self):

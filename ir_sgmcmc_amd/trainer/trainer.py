@@ -34,14 +34,14 @@ from ..diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ChainMoments,
                            NATIVE_POSTERIOR_IMAGE_METRICS, NativePosterior, native_posterior_options,
                            native_resolution_options, PosteriorComparison, posterior_comparison_options, ResidualCheck,
                            residual_check_options, residual_metrics,
-                           SIMILARITY_METRICS, voxel_scale)
+                           SIMILARITY_METRICS, StructureReport, recorded_steps, voxel_scale)
 from ..engine import EngineConfig, TransitionEngine
 from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_modes, save_displacement_quantiles, save_ess,
                       save_field, save_image_posterior, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_landmarks,
                       save_local_similarity_of_mean, save_local_similarity_posterior, save_native_mean, save_native_posterior, save_native_sample,
                       save_posterior_comparison, save_precond_sigma,
-                      save_residual_histogram, save_residual_nll, save_rhat, save_sample, save_surface_posterior)
-from .. import affine, bspline, image_posterior, multires, preconditioner, residual_check
+                      save_residual_histogram, save_residual_nll, save_rhat, save_sample, save_structure_report, save_surface_posterior)
+from .. import affine, bspline, image_posterior, multires, preconditioner, residual_check, structure_report
 from .. import masks as mask_ops  # (`masks` names the pair of masks in several methods below)
 from ..multires import coarse_start_options
 from ..utils import (calc_DSC_GPU, calc_image_similarity, calc_norm, calc_no_non_diffeomorphic_voxels, calc_residual_check,
@@ -196,6 +196,12 @@ class Trainer(VIMixin, BaseTrainer):
         self._posterior_comparison = None
         self.comparison_shift, self.comparison_log_std_ratio, self.comparison_bures, self.comparison_jeffreys = None, None, None, None
         self.comparison_summary = None
+        # structure report: per structure of the fixed segmentation, the posterior of its mean displacement and volume change and
+        # the per-structure rows of the maps above (structure_report.py, diagnostics.StructureReport): None when
+        # trainer.structure_report is off
+        self.structure_options = structure_report.structure_report_options(cfg_trainer, data_loader, self.structures_dict)
+        self._structure_report = None
+        self.structure_summary = None
         # coarse-to-fine start (multires.py, _coarse_start): None unless trainer.MCMC_init is "coarse"
         self.coarse_options = coarse_start_options(cfg_trainer, config['data_loader']['args']['dims'],
                                                    config['transformation_module']['type'])
@@ -425,7 +431,8 @@ class Trainer(VIMixin, BaseTrainer):
 
     def _recorders(self):
         """the active recorders, in the order they record and finish: moments, labels, surfaces, Jacobian, images, covariance,
-        modes, quantiles, inverse consistency, landmarks, local similarity, residual check, posterior comparison, native posterior"""
+        modes, quantiles, inverse consistency, landmarks, local similarity, residual check, posterior comparison, native posterior,
+        and last the structure report, which reads the maps the others have finished"""
         period = lambda options: options and options['period']
         rows = (('chain_moments', self._chain_moments, self.diagnostics_period, 'convergence_diagnostics', 'chain moments',
                  'displacement', self._finish_diagnostics, 'moving_mask'),
@@ -456,7 +463,9 @@ class Trainer(VIMixin, BaseTrainer):
                 ('posterior_comparison', self._posterior_comparison, period(self.comparison_options), 'posterior_comparison',
                  'posterior comparison', 'displacement', self._finish_posterior_comparison, 'moving_mask'),
                 ('native_posterior', self._native_posterior, period(self.native_posterior_options), 'native_posterior',
-                 'native posterior', 'displacement', self._finish_native_posterior, 'fixed'))
+                 'native posterior', 'displacement', self._finish_native_posterior, 'fixed'),
+                ('structure_report', self._structure_report, period(self.structure_options), 'structure_report',
+                 'structure report', ('displacement', 'transformation'), self._finish_structure_report, 'fixed'))
         return [Recorder(*row) for row in rows if row[1] is not None]
 
     # ---------------------------------------------------------------- checkpoint / resume (absent in the reference)
@@ -763,6 +772,13 @@ class Trainer(VIMixin, BaseTrainer):
             self._comparison_init(self._outputs['displacement'].shape[2:])
         if self.precond_options is not None:
             self._precond_init()
+        if self.structure_options is not None:
+            if 'seg' not in fixed:
+                raise ValueError(f'trainer.structure_report needs the fixed segmentation ("seg"); fixed has {sorted(fixed)}')
+            # scale (1, 1, 1): voxels of the registration grid, the unit of the displacement covariance; no mask: the structures
+            # are the regions
+            steps = self.no_samples_MCMC // self.structure_options['period']
+            self._structure_report = StructureReport(fixed['seg'][0], self.structures_dict, steps * self.no_chains, self.device)
         if cfg_trainer.get('resume'):
             self.load_checkpoint(cfg_trainer['resume'])
             first = self._sample_no + 1
@@ -1029,6 +1045,65 @@ class Trainer(VIMixin, BaseTrainer):
         if save_outputs:
             save_jacobian_posterior(self.logger, self.config.save_dirs, spacing, self.jacobian_fold_prob, self.jacobian_logJ_mean,
                                     self.jacobian_logJ_std, mask, 'MCMC')
+
+    def _structure_maps(self):
+        """the finished per-voxel posterior maps the structure report tabulates: whichever exist -> (names, (M,D,H,W) float32 on
+        the device), or ([], None).  The names are the attributes' but for the split R-hat map, 'split_rhat': its maximum would
+        collide with the motion key rhat_max"""
+        std = self.displacement_std
+        cov_std = self.displacement_cov_std
+        maps = [('displacement_std_x', None if std is None else std[0]), ('displacement_std_y', None if std is None else std[1]),
+                ('displacement_std_z', None if std is None else std[2]),
+                ('displacement_std_norm', None if std is None else calc_norm(std.unsqueeze(0))[0, 0]),
+                ('split_rhat', self.rhat), ('ess', self.ess), ('mcse', self.mcse), ('label_entropy', self.label_entropy),
+                ('jacobian_fold_prob', self.jacobian_fold_prob), ('jacobian_logJ_mean', self.jacobian_logJ_mean),
+                ('jacobian_logJ_std', self.jacobian_logJ_std),
+                ('displacement_cov_std_major', None if cov_std is None else cov_std[0]),
+                ('displacement_cov_anisotropy', self.displacement_cov_anisotropy), ('displacement_ci_width', self.displacement_ci_width),
+                ('local_lncc_mean', self.local_lncc_mean), ('residual_nll_mean', self.residual_nll_mean),
+                ('comparison_shift', self.comparison_shift), ('comparison_log_std_ratio', self.comparison_log_std_ratio),
+                ('comparison_bures', self.comparison_bures), ('comparison_jeffreys', self.comparison_jeffreys)]
+        maps = [(name, m) for name, m in maps if m is not None]
+        if not maps:
+            return [], None
+        dims = self._structure_report.dims
+        return [name for name, _ in maps], torch.stack([m.to(self.device, torch.float32).reshape(dims) for _, m in maps]).contiguous()
+
+    def _finish_structure_report(self, fixed, spacing, save_outputs):
+        """the per-structure table -> self.structure_summary {'records', 'structures': {name: {...}}, 'maps': [names]}: the motion
+        keys of structure_report.structure_summary (with coherence / n_eff when trainer.displacement_covariance recorded the same
+        steps), then, with the option's "maps", the rows of every finished posterior map; the MCMC/structure/{key}/{structure}
+        metrics of the motion keys, one log line per structure and, with save_outputs and the option's save,
+        samples/MCMC_structures.csv and samples/MCMC_structure_series.csv.  Runs last: the other recorders have finished"""
+        report, opt = self._structure_report, self.structure_options
+        cov_trace = None
+        if structure_report.with_coherence(self.config['trainer']):
+            dc = self._displacement_covariance
+            if dc.records != report.records:
+                raise RuntimeError(f'structure report: {report.records} records against {dc.records} of the displacement covariance')
+            cov_trace = structure_report.covariance_trace(*report.map_stats(dc.comoment[:3].contiguous()), dc.records, report.scale)
+        summary, (ints, floats) = report.finalize([float(s) for s in spacing], self.no_chains, cov_trace)
+        summary['maps'] = []
+        if opt['maps']:
+            names, stacked = self._structure_maps()
+            if names:
+                structure_report.add_map_rows(summary, structure_report.structure_map_rows(*report.map_stats(stacked), names, report.names),
+                                              names)
+        self.structure_summary = summary
+        keys = structure_report.structure_metric_keys(self.config['trainer'])
+        for name, row in summary['structures'].items():
+            for key in keys:
+                self.metrics.update(f'MCMC/structure/{key}/{name}', row[key])
+            self.logger.info(f'structure {name}: {row["voxels"]} voxels over {summary["records"]} records; mean shift '
+                             f'({row["shift_mean_x"]:.4f}, {row["shift_mean_y"]:.4f}, {row["shift_mean_z"]:.4f}) voxels, its spread '
+                             f'major {row["shift_std_major"]:.4f}, total {row["shift_std_total"]:.4f}; |w| mean {row["disp_mean"]:.4f}, '
+                             f'max {row["disp_max"]:.4f}; volume ratio {row["vol_ratio_mean"]:.5f} +- {row["vol_ratio_std"]:.5f}, '
+                             f'folded {100 * row["fold_frac"]:.3f} %, split R-hat max {row["rhat_max"]:.4f}' +
+                             (f'; coherence {row["coherence"]:.4g} (n_eff {row["n_eff"]:.4g})' if 'coherence' in row else ''))
+        if save_outputs and opt['save']:
+            steps = recorded_steps(self.no_iters_burn_in, self.no_samples_MCMC, opt['period'])
+            save_structure_report(self.logger, self.config.save_dirs, structure_report.structures_csv(summary),
+                                  structure_report.series_csv(ints, floats, report.names, steps, self.no_chains), 'MCMC')
 
     def _image_init(self, fixed, moving):
         """trainer.image_posterior -> self._image_volumes (S,1,D,H,W) on the device: the moving image as the chain warps it, then

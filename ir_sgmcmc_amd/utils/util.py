@@ -199,6 +199,32 @@ def calc_jacobian_posterior(transformations, mask=None):
 
 
 @torch.no_grad()
+def calc_structure_report(displacements, transformations, seg_fixed, structures_dict, spacing, mask=None, maps=None, chains=1):
+    """Per-structure motion posterior of samples (absent in the reference): displacements (n,3,D,H,W) float32 in voxels and
+    transformations (n,3,D,H,W) float32 in normalised coordinates on the device, the n records ordered by step, then by chain
+    (`chains` per step); seg_fixed (D,H,W) int16; structures_dict {name: label}; spacing (sx, sy, sz); mask (D,H,W) or None;
+    maps: {name: (D,H,W) float32 map} or None, whose per-structure rows are added.  -> the dict of
+    structure_report.structure_summary with 'maps': the names of the maps, as Trainer.structure_summary; 'series': the (ints,
+    floats) arrays behind it."""
+    from .. import structure_report as sr
+    from ..diagnostics import StructureReport
+    for name, t in (('displacements', displacements), ('transformations', transformations)):
+        if t.dim() != 5 or t.shape[1] != 3:
+            raise ValueError(f'{name} must have shape (n, 3, D, H, W), got {tuple(t.shape)}')
+    n = displacements.shape[0]
+    report = StructureReport(seg_fixed, structures_dict, max(n, 1), displacements.device, mask=mask)
+    for i in range(0, n, chains):  # one launch reduces the records of one step, in order
+        report.record((displacements[i:i + chains].float().contiguous(), transformations[i:i + chains].float().contiguous()))
+    summary, series = report.finalize([float(s) for s in spacing], chains)
+    summary['maps'] = list(maps or {})
+    if maps:
+        stacked = torch.stack([m.to(displacements.device, torch.float32).reshape(report.dims) for m in maps.values()])
+        sr.add_map_rows(summary, sr.structure_map_rows(*report.map_stats(stacked), summary['maps'], report.names), summary['maps'])
+    summary['series'] = series
+    return summary
+
+
+@torch.no_grad()
 def calc_image_posterior(volumes, transformations, reference=None, mask=None, std_floor=0.0):
     """Volumes carried through transformation samples (absent in the reference): volumes (S,1,D,H,W) float32 on the device, on
     the grid the transformations sample, S in 1 .. 8; transformations (n,3,D,H,W) float32 in normalised coordinates, the n
