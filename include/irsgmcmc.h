@@ -925,6 +925,64 @@ int irs_structure_map_stats(const float* maps, int M, int D, int H, int W, const
                             int n_labels, const uint8_t* mask, long long* ints, double* floats, void* ws, size_t ws_bytes,
                             void* stream);
 
+/* Known-transformation validation (absent in the reference): the recorded displacement against a dense truth t (3,D,H,W) float32
+ * on the fixed grid, in the unit of the displacement.  scale: 3 HOST floats s, finite and > 0, one per channel; mask (D,H,W)
+ * uint8 or NULL (whole volume).  All arithmetic below is in double, every operation rounded once, nothing contracted.
+ *  - irs_truth_update: displacement (C,3,D,H,W) float32, C in 1 .. IRS_MAX_CHAINS, every dim >= 2; below (3,D,H,W) uint16,
+ *    updated in place: below[c,x] += #{chains k: u_k,c(x) < t_c(x)}, the comparison strict and on the raw float32 values (false
+ *    when either side is NaN), whatever the mask says.  records_before >= 0 records were counted before, records_before + C <=
+ *    IRS_TRUTH_MAX_RECORDS; records_before = 0 overwrites below, which is then never read.  Per chain, over the masked voxels:
+ *    e_c = s_c * ((double)u_c - (double)t_c), q = (e_x^2 + e_y^2) + e_z^2, r = sqrt(q); ints (C, IRS_TRUTH_UPDATE_INTS) int64
+ *    {voxels, voxels with a non-finite q}; floats (C, IRS_TRUTH_UPDATE_FLOATS) doubles over the other masked voxels {sum r,
+ *    sum q, max r}; a maximum nothing entered is -inf.  ints / floats are device pointers and may point into a larger series.
+ *    ws: IRS_TRUTH_UPDATE_WS_BYTES of device memory.  One launch and one finish launch.
+ *  - irs_truth_calibrate: mean (3,D,H,W), comoment (6,D,H,W: xx, yy, zz, xy, xz, yz) float32: a state of
+ *    irs_displacement_covariance_update after n records, 2 <= n <= IRS_TRUTH_MAX_RECORDS; below: as above after the same n
+ *    records; std_floor f, finite, > 0 and f^2 > 0.  Per voxel: Delta_c = s_c * ((double)mean_c - (double)t_c); A_ab = ((s_a *
+ *    s_b) * (double)comoment_ab) / (double)(n - 1), and A_cc += f^2.  LDL^T without pivoting: d0 = A_xx; l10 = A_xy / d0, l20 =
+ *    A_xz / d0; d1 = A_yy - l10 * A_xy; w = A_yz - l20 * A_xy, l21 = w / d1; d2 = (A_zz - l20 * A_xz) - l21 * w; every pivot is
+ *    raised to f^2 the moment it is formed if it is below (or NaN) -- in exact arithmetic none is -- and a voxel with a raised
+ *    pivot counts as `raised`.  y0 = Delta_x, y1 = Delta_y - l10 * y0, y2 = (Delta_z - l20 * y0) - l21 * y1; dist2 = (y0 * y0 /
+ *    d0 + y1 * y1 / d1) + y2 * y2 / d2; err2 = (Delta_x^2 + Delta_y^2) + Delta_z^2; v = (A_xx + A_yy) + A_zz; z_c = Delta_c^2 /
+ *    max(A_cc, f^2).  Maps (D,H,W) float32, whatever the mask says: error = (float)sqrt(err2), mahalanobis = (float)sqrt(dist2);
+ *    a voxel with a non-finite value among its 12 state and truth values, or a non-finite dist2, is `non-finite`: NaN in both.
+ *    Over the masked voxels that are not non-finite, exact int64 counts (IRS_TRUTH_COUNTS(B, L, Br) of them, in this order):
+ *    pit_hist[B]: bin = number of d2_edges <= dist2 (B - 1 HOST doubles, finite and strictly increasing, B in 1 ..
+ *    IRS_TRUTH_MAX_BINS); coverage[L]: dist2 <= levels[l] (L HOST doubles, finite, L in 1 .. IRS_TRUTH_MAX_LEVELS);
+ *    rank_hist[3][Br]: bin = min(below_c * Br / (n + 1), Br - 1) in integers, Br in 1 .. IRS_TRUTH_MAX_BINS.  The reliability
+ *    table over R in 1 .. IRS_TRUTH_MAX_RELIABILITY_BINS bins of v, bin = number of var_edges <= v (R - 1 HOST doubles, finite
+ *    and strictly increasing): rel_ints (R) int64 {voxels}, rel_floats (R,2) doubles {sum v, sum err2}, by the labelled
+ *    reduction of irs_structure_motion with the bin as the label.  isummary: IRS_TRUTH_SUMMARY_INTS int64 over the mask {voxels,
+ *    non-finite voxels, raised voxels}; fsummary: IRS_TRUTH_SUMMARY_FLOATS doubles over the other masked voxels {sum
+ *    sqrt(err2), sum err2, max sqrt(err2), sum dist2, max dist2, sum v, sum z_x, sum z_y, sum z_z}.  No transcendental is
+ *    evaluated on the device: whatever needs a distribution function is decided against the thresholds the host passes.  ws:
+ *    IRS_TRUTH_CALIBRATE_WS_BYTES of device memory.
+ *  Both: the grids depend on the volume alone; the double sums are reduced in two stages with a fixed merge order and no
+ *  floating-point atomics; the counts are integer sums.  Two identical calls are bit-identical.  A refused call writes nothing.
+ *  No host sync. */
+#define IRS_TRUTH_MAX_RECORDS 65535
+#define IRS_TRUTH_UPDATE_INTS 2
+#define IRS_TRUTH_UPDATE_FLOATS 3
+#define IRS_TRUTH_UPDATE_WS_BYTES (IRS_MAX_CHAINS * 1024 * (IRS_TRUTH_UPDATE_INTS + IRS_TRUTH_UPDATE_FLOATS) * 8)
+#define IRS_TRUTH_MAX_BINS 64
+#define IRS_TRUTH_MAX_LEVELS 8
+#define IRS_TRUTH_MAX_RELIABILITY_BINS 32
+#define IRS_TRUTH_RELIABILITY_INTS 1
+#define IRS_TRUTH_RELIABILITY_FLOATS 2
+#define IRS_TRUTH_SUMMARY_INTS 3
+#define IRS_TRUTH_SUMMARY_FLOATS 9
+#define IRS_TRUTH_CALIBRATE_WS_BYTES \
+    (1024 * (IRS_TRUTH_SUMMARY_INTS + IRS_TRUTH_SUMMARY_FLOATS + IRS_TRUTH_MAX_RELIABILITY_BINS * (IRS_TRUTH_RELIABILITY_INTS + IRS_TRUTH_RELIABILITY_FLOATS)) * 8)
+#define IRS_TRUTH_COUNTS(B, L, Br) ((B) + (L) + 3 * (Br))
+int irs_truth_update(const float* displacement, int C, int D, int H, int W, const float* truth, uint16_t* below, const uint8_t* mask,
+                     const float* scale, int records_before, long long* ints, double* floats, void* ws, size_t ws_bytes,
+                     void* stream);
+int irs_truth_calibrate(const float* mean, const float* comoment, const uint16_t* below, const float* truth, int D, int H, int W, int n,
+                        const float* scale, double std_floor, const uint8_t* mask, const double* d2_edges, int pit_bins,
+                        const double* levels, int n_levels, int rank_bins, const double* var_edges, int reliability_bins,
+                        float* error, float* mahalanobis, long long* counts, long long* rel_ints, double* rel_floats,
+                        long long* isummary, double* fsummary, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * fused transition (Trainer._SGLD_transition, trainer/trainer.py:291-356)
  * ---------------------------------------------------------------------------------------------- */

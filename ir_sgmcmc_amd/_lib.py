@@ -21,6 +21,12 @@ IRS_LABEL_BINS = 10
 IRS_JACOBIAN_SUMMARY_INTS, IRS_JACOBIAN_SUMMARY_FLOATS = 4, 5
 IRS_JACOBIAN_WS_BYTES = 1024 * (IRS_JACOBIAN_SUMMARY_INTS + IRS_JACOBIAN_SUMMARY_FLOATS) * 8
 IRS_STRUCTURE_MOTION_INTS, IRS_STRUCTURE_MOTION_FLOATS, IRS_STRUCTURE_MAP_INTS, IRS_STRUCTURE_MAP_FLOATS = 2, 9, 2, 4
+IRS_TRUTH_MAX_RECORDS, IRS_TRUTH_UPDATE_INTS, IRS_TRUTH_UPDATE_FLOATS = 65535, 2, 3
+IRS_TRUTH_UPDATE_WS_BYTES = IRS_MAX_CHAINS * 1024 * (IRS_TRUTH_UPDATE_INTS + IRS_TRUTH_UPDATE_FLOATS) * 8
+IRS_TRUTH_MAX_BINS, IRS_TRUTH_MAX_LEVELS, IRS_TRUTH_MAX_RELIABILITY_BINS = 64, 8, 32
+IRS_TRUTH_RELIABILITY_INTS, IRS_TRUTH_RELIABILITY_FLOATS, IRS_TRUTH_SUMMARY_INTS, IRS_TRUTH_SUMMARY_FLOATS = 1, 2, 3, 9
+IRS_TRUTH_CALIBRATE_WS_BYTES = 1024 * (IRS_TRUTH_SUMMARY_INTS + IRS_TRUTH_SUMMARY_FLOATS + IRS_TRUTH_MAX_RELIABILITY_BINS *
+                                       (IRS_TRUTH_RELIABILITY_INTS + IRS_TRUTH_RELIABILITY_FLOATS)) * 8
 IRS_IMAGE_POSTERIOR_MAX_VOLUMES, IRS_IMAGE_POSTERIOR_SUMMARY_INTS, IRS_IMAGE_POSTERIOR_SUMMARY_FLOATS = 8, 4, 6
 IRS_IMAGE_POSTERIOR_WS_BYTES = 1024 * (IRS_IMAGE_POSTERIOR_SUMMARY_INTS + IRS_IMAGE_POSTERIOR_SUMMARY_FLOATS) * 8
 IRS_COVARIANCE_SUMMARY_INTS, IRS_COVARIANCE_SUMMARY_FLOATS = 2, 8
@@ -191,6 +197,9 @@ SIGNATURES = {
     'irs_structure_workspace': [_I, _I, _I, _I, _I, C.POINTER(C.c_size_t)],
     'irs_structure_motion': [_P, _P, _I, _I, _I, _I, _P, _I32P, _I, _P, C.POINTER(C.c_float), _P, _P, _P, C.c_size_t, _P],
     'irs_structure_map_stats': [_P, _I, _I, _I, _I, _P, _I32P, _I, _P, _P, _P, _P, C.c_size_t, _P],
+    'irs_truth_update': [_P, _I, _I, _I, _I, _P, _P, _P, C.POINTER(C.c_float), _I, _P, _P, _P, C.c_size_t, _P],
+    'irs_truth_calibrate': [_P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(C.c_float), C.c_double, _P, C.POINTER(C.c_double), _I,
+                            C.POINTER(C.c_double), _I, _I, C.POINTER(C.c_double), _I, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],
     'irs_image_posterior_update': [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P],
     'irs_image_posterior_finalize': [_P, _P, _P, _P, _I, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],
     'irs_displacement_covariance_update': [_P, _I, _I, _I, _I, _P, _P, _I, _P],

@@ -96,6 +96,21 @@ inline bool structure_shape_ok(const char* who, int D, int H, int W, int min_dim
     return (K >= 1 && K <= IRS_MAX_LABELS) || !fail("%s: K = %d structures, 1..%d", who, K, IRS_MAX_LABELS);
 }
 
+// `count` host doubles, every one finite and, with `increasing`, each above the one before (truth_kernels.hip: bin edges, levels)
+inline bool thresholds_ok(const char* who, const char* name, const double* values, int count, bool increasing) {
+    for (int e = 0; e < count; ++e) {
+        if (!isfinite(values[e])) return !fail("%s: %s[%d] = %g is not finite", who, name, e, values[e]);
+        if (increasing && e > 0 && !(values[e] > values[e - 1]))
+            return !fail("%s: %s[%d] = %g is not above %s[%d] = %g", who, name, e, values[e], name, e - 1, values[e - 1]);
+    }
+    return true;
+}
+
+// a bin or level count within its cap
+inline bool count_ok(const char* who, const char* name, int value, int cap) {
+    return (value >= 1 && value <= cap) || !fail("%s: %s = %d, 1..%d", who, name, value, cap);
+}
+
 inline SplineTaps make_spline(int cps) {
     // sampled cubic B-spline (utils/transformation.py:79-102); evaluated in double, stored as float like the reference
     SplineTaps t;

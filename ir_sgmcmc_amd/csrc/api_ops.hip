@@ -841,6 +841,54 @@ int irs_structure_map_stats(const float* maps, int M, int D, int H, int W, const
 }
 
 // ================================================================================================
+// known-transformation validation (truth_kernels.hip)
+// ================================================================================================
+int irs_truth_update(const float* displacement, int C, int D, int H, int W, const float* truth, uint16_t* below, const uint8_t* mask,
+                     const float* scale, int records_before, long long* ints, double* floats, void* ws, size_t ws_bytes,
+                     void* stream) {
+    if (!displacement || !truth || !below || !scale || !ints || !floats || !ws || !dims_ok(C, D, H, W))
+        return fail("irs_truth_update: bad arguments");
+    if (!chains_ok(__func__, C)) return 1;
+    if (!positive3(__func__, "scale", scale)) return 1;
+    if (!records_ok(__func__, records_before, C, IRS_TRUTH_MAX_RECORDS, "exceed the 65535 a uint16 count holds")) return 1;
+    if (!workspace_ok(__func__, ws_bytes, (size_t)IRS_TRUTH_UPDATE_WS_BYTES, "IRS_TRUTH_UPDATE_WS_BYTES")) return 1;
+    launch_truth_update(displacement, C, truth, below, mask, scale, records_before, (int64_t)D * H * W, ints, floats, ws,
+                        (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_truth_calibrate(const float* mean, const float* comoment, const uint16_t* below, const float* truth, int D, int H, int W, int n,
+                        const float* scale, double std_floor, const uint8_t* mask, const double* d2_edges, int pit_bins,
+                        const double* levels, int n_levels, int rank_bins, const double* var_edges, int reliability_bins,
+                        float* error, float* mahalanobis, long long* counts, long long* rel_ints, double* rel_floats,
+                        long long* isummary, double* fsummary, void* ws, size_t ws_bytes, void* stream) {
+    if (!mean || !comoment || !below || !truth || !scale || !levels || !error || !mahalanobis || !counts || !rel_ints || !rel_floats ||
+        !isummary || !fsummary || !ws || !dims_ok(1, D, H, W))
+        return fail("irs_truth_calibrate: bad arguments");
+    if (n < 2) return fail("irs_truth_calibrate: n = %d records, at least 2 needed", n);
+    if (n > IRS_TRUTH_MAX_RECORDS)
+        return fail("irs_truth_calibrate: n = %d records, but the uint16 counts of `below` hold at most %d", n, IRS_TRUTH_MAX_RECORDS);
+    if (!positive3(__func__, "scale", scale)) return 1;
+    if (!(std_floor > 0.0) || !isfinite(std_floor) || !(std_floor * std_floor > 0.0))
+        return fail("irs_truth_calibrate: std_floor = %g, a finite value > 0 (whose square is > 0) needed", std_floor);
+    if (!count_ok(__func__, "pit_bins", pit_bins, IRS_TRUTH_MAX_BINS) || !count_ok(__func__, "n_levels", n_levels, IRS_TRUTH_MAX_LEVELS) ||
+        !count_ok(__func__, "rank_bins", rank_bins, IRS_TRUTH_MAX_BINS) ||
+        !count_ok(__func__, "reliability_bins", reliability_bins, IRS_TRUTH_MAX_RELIABILITY_BINS))
+        return 1;
+    if ((pit_bins > 1 && !d2_edges) || (reliability_bins > 1 && !var_edges)) return fail("irs_truth_calibrate: bad arguments");
+    if (!thresholds_ok(__func__, "d2_edges", d2_edges, pit_bins - 1, true) || !thresholds_ok(__func__, "levels", levels, n_levels, false) ||
+        !thresholds_ok(__func__, "var_edges", var_edges, reliability_bins - 1, true))
+        return 1;
+    if (!workspace_ok(__func__, ws_bytes, (size_t)IRS_TRUTH_CALIBRATE_WS_BYTES, "IRS_TRUTH_CALIBRATE_WS_BYTES")) return 1;
+    launch_truth_calibrate(mean, comoment, below, truth, (int64_t)D * H * W, n, scale, std_floor, mask, d2_edges, pit_bins, levels,
+                           n_levels, rank_bins, var_edges, reliability_bins, error, mahalanobis, counts, rel_ints, rel_floats, isummary,
+                           fsummary, ws, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ================================================================================================
 // image posterior (image_posterior_kernels.hip)
 // ================================================================================================
 int irs_image_posterior_update(const float* volumes, int S, const float* transformation, int C, int D, int H, int W, float* mean,

@@ -323,6 +323,19 @@ void launch_structure_motion(const float* displacement, const float* transformat
 void launch_structure_map_stats(const float* maps, int64_t M, int64_t V, const int16_t* seg_fixed, const SurfLabels& lab, int K,
                                 const uint8_t* mask, long long* ints, double* floats, void* ws, hipStream_t st);
 
+// ---- truth_kernels.hip: known-transformation validation (absent in the reference); arithmetic in truth_device.h
+// displacement (C,3,V), truth (3,V) float32; below (3,V) uint16; mask (V) uint8 or nullptr; scale: 3 host floats; ints (C,
+// IRS_TRUTH_UPDATE_INTS) int64, floats (C,IRS_TRUTH_UPDATE_FLOATS) doubles; ws: IRS_TRUTH_UPDATE_WS_BYTES
+void launch_truth_update(const float* displacement, int C, const float* truth, uint16_t* below, const uint8_t* mask, const float* scale,
+                         int records_before, int64_t V, long long* ints, double* floats, void* ws, hipStream_t st);
+// mean (3,V), comoment (6,V) after n records; d2_edges (B - 1), levels (L), var_edges (R - 1): host doubles; counts
+// (IRS_TRUTH_COUNTS(B, L, Br)) int64; rel_ints (R), rel_floats (R,2); ws: IRS_TRUTH_CALIBRATE_WS_BYTES
+void launch_truth_calibrate(const float* mean, const float* comoment, const uint16_t* below, const float* truth, int64_t V, int n,
+                            const float* scale, double std_floor, const uint8_t* mask, const double* d2_edges, int B,
+                            const double* levels, int L, int Br, const double* var_edges, int R, float* error, float* mahalanobis,
+                            long long* counts, long long* rel_ints, double* rel_floats, long long* isummary, double* fsummary,
+                            void* ws, hipStream_t st);
+
 // ---- covariance_kernels.hip: displacement covariance posterior (absent in the reference); arithmetic in covariance_device.h
 // x (C,3,V) float32; mean (3,V), comoment (6,V: xx, yy, zz, xy, xz, yz) float32: Welford moments, the C chains folded in order
 // after `records_before` records

@@ -98,6 +98,12 @@ transformation over the structures of the fixed segmentation (structure_report.s
 structure into a device series allocated once, 88 * K bytes per record; at the end the host turns the series into the posterior
 of every structure's mean displacement and volume change, and the same reduction over the finished maps of the other options
 (structure_report.structure_map_stats) gives their per-structure rows.
+
+The truth calibration (TruthCalibration, truth.truth_options) is the one recorder that holds the posterior against an independent
+dense truth -- a simulated transformation (truth.known_pair) or a field from elsewhere: at a recorded step one launch counts, per
+voxel and channel, the chains below the truth (6 bytes per voxel) and writes every chain's masked error row into a device series,
+and a covariance state of its own takes the step; at the end one launch turns state and truth into the error and Mahalanobis
+maps, the PIT and rank histograms, the coverage counts and the reliability table.
 """
 import math
 import numbers
@@ -114,6 +120,7 @@ from . import ops
 from . import posterior_comparison as _pc
 from . import residual_check as _rc
 from . import structure_report as _sr
+from . import truth as _truth
 
 
 def diagnostics_period(cfg_trainer):
@@ -998,6 +1005,111 @@ class StructureReport(_Recorder):
         self.ints.copy_(sd['ints'])
         self.floats.copy_(sd['floats'])
         self.records = int(sd['records'])
+
+
+class TruthCalibration(_Recorder):
+    """The recorded displacement against a dense truth (truth.py): `below` (3,D,H,W) uint16, per voxel and channel the number of
+    records strictly below the truth; a displacement covariance state of its own; and a device series of the per-record error
+    rows, (steps * C, 2) int64 and (steps * C, 3) float64, allocated once.  truth: (3,D,H,W) float32 in the unit of the recorded
+    displacement (voxels of the registration grid for the trainer's); scale: three positive floats, one per channel, the unit
+    of the errors (default 1: that of the displacement); mask: the voxels the series and, by default, the summary are taken
+    over.  `record(displacement)` takes the (C,3,D,H,W) float32 displacements of one step, chains in order: one launch of
+    truth.truth_update and one of the covariance update; `finalize` gives the maps, the tables and the summary with one
+    device-to-host read."""
+    noun, max_records, exceed = 'truth calibration', _L.IRS_TRUTH_MAX_RECORDS, 'exceed the {} a uint16 rank count holds'
+
+    def __init__(self, truth, capacity, device, scale=(1.0, 1.0, 1.0), mask=None):
+        if truth.dim() != 4 or truth.shape[0] != 3:
+            raise ValueError(f'truth calibration: the truth must have shape (3,D,H,W), got {tuple(truth.shape)}')
+        self.dims = tuple(int(d) for d in truth.shape[1:])
+        if min(self.dims) < 2:
+            raise ValueError(f'truth calibration: three dims of at least 2, got {self.dims}')
+        self.capacity = int(capacity)
+        if not 1 <= self.capacity <= self.max_records:
+            raise ValueError(f'truth calibration: room for {capacity} records, 1..{self.max_records} needed')
+        self.device = device
+        self.scale = tuple(float(s) for s in scale)
+        if len(self.scale) != 3 or not all(math.isfinite(s) and s > 0 for s in self.scale):
+            raise ValueError(f'truth calibration: scale must hold three finite floats > 0, got {scale}')
+        self.truth = truth.to(device=device, dtype=torch.float32).contiguous()
+        self.fingerprint = _truth.fingerprint(self.truth)
+        self.mask = _bool_mask(mask, device)
+        self.below = _truth.new_below(self.dims, device)
+        self.covariance = DisplacementCovariance(self.dims, device)
+        self.ints = torch.zeros((self.capacity, _L.IRS_TRUTH_UPDATE_INTS), device=device, dtype=torch.int64)
+        self.floats = torch.zeros((self.capacity, _L.IRS_TRUTH_UPDATE_FLOATS), device=device, dtype=torch.float64)
+        self.workspace = _truth.TruthWorkspace(device)
+
+    def record(self, displacement):
+        C = displacement.shape[0]
+        if self.records + C > self.capacity:
+            raise ValueError(f'{self.noun}: {self.records} + {C} records exceed the {self.capacity} rows the series was allocated for')
+        super().record(displacement)
+
+    def _update(self, displacement):
+        rows = slice(self.records, self.records + displacement.shape[0])
+        _truth.truth_update(displacement, self.truth, self.below, self.records, self.scale, self.mask,
+                            out=(self.ints[rows], self.floats[rows]), workspace=self.workspace)
+        self.covariance.record(displacement)
+
+    def initial_error(self):
+        """{'mean', 'rmse', 'max'} of the error of the identity -- a zero displacement -- over the mask: the update kernel into
+        scratch state.  One device-to-host read."""
+        zero = torch.zeros((1, 3) + self.dims, device=self.device, dtype=torch.float32)
+        ints, floats = _truth.truth_update(zero, self.truth, _truth.new_below(self.dims, self.device), 0, self.scale, self.mask,
+                                           workspace=self.workspace)
+        return _truth.error_stats(*_host_summary(ints.reshape(-1), floats.reshape(-1)))
+
+    def finalize(self, mask=None, levels=(0.5, 0.9, 0.95), pit_bins=20, rank_bins=16, reliability_bins=16, std_floor=1e-3,
+                 reference='hotelling', initial=None, floor=None):
+        """mask: the voxels of the summary and the tables (None: the recorder's own).  -> ({'error', 'mahalanobis'}: (D,H,W)
+        float32 maps on the device, summary dict of truth.calibration_summary, (ints, floats): the series as numpy arrays).
+        One device-to-host read: tables, summary and series travel together."""
+        self._need_records('finalize')
+        n = self.records
+        if n < _truth.MIN_RECORDS[reference]:
+            raise RuntimeError(f'TruthCalibration.finalize: {n} records, at least {_truth.MIN_RECORDS[reference]} needed with the '
+                               f'{reference!r} reference')
+        d2_edges, level_d2 = _truth.calibration_thresholds(n, levels, pit_bins, reference)
+        var_edges = _truth.default_var_edges(reliability_bins)
+        mask = self.mask if mask is None else _bool_mask(mask, self.device)
+        res = _truth.truth_calibrate(self.covariance.mean, self.covariance.comoment, self.below, self.truth, n, self.scale, d2_edges,
+                                     level_d2, rank_bins, var_edges, std_floor, mask, workspace=self.workspace)
+        parts_i = [res['isummary'], res['counts'], res['rel_ints'].reshape(-1), self.ints[:n].reshape(-1)]
+        parts_f = [res['fsummary'], res['rel_floats'].reshape(-1), self.floats[:n].reshape(-1)]
+        host = torch.cat([torch.cat(parts_i).view(torch.float64), torch.cat(parts_f)]).cpu()
+        ni = sum(p.numel() for p in parts_i)
+        hi, hf = host[:ni].contiguous().view(torch.int64).numpy(), host[ni:].numpy()
+        cut = lambda arr, parts: np.split(arr, np.cumsum([p.numel() for p in parts])[:-1])
+        isummary, counts, rel_ints, ints = cut(hi, parts_i)
+        fsummary, rel_floats, floats = cut(hf, parts_f)
+        B, Lv = int(pit_bins), len(level_d2)
+        summary = _truth.calibration_summary(isummary, fsummary, counts[:B], counts[B:B + Lv], counts[B + Lv:].reshape(3, -1), rel_ints,
+                                             rel_floats.reshape(-1, 2), n, levels, reference, var_edges, initial, floor)
+        return ({'error': res['error'], 'mahalanobis': res['mahalanobis']}, summary,
+                (ints.reshape(n, -1).copy(), floats.reshape(n, -1).copy()))
+
+    def state_dict(self):
+        return {'below': self.below.detach().cpu(), 'covariance': self.covariance.state_dict(), 'ints': self.ints.detach().cpu(),
+                'floats': self.floats.detach().cpu(), 'records': self.records, 'fingerprint': self.fingerprint}
+
+    def load_state_dict(self, sd):
+        if sd['fingerprint'] != self.fingerprint:
+            raise ValueError(f'truth calibration: the checkpoint was recorded against another truth (fingerprint '
+                             f'{str(sd["fingerprint"])[:12]}..., this run {self.fingerprint[:12]}...)')
+        for key, t in (('below', self.below), ('ints', self.ints), ('floats', self.floats)):
+            if tuple(sd[key].shape) != tuple(t.shape) or sd[key].dtype != t.dtype:
+                raise ValueError(f'truth calibration state of shape {tuple(sd[key].shape)} {sd[key].dtype} ({key}) does not match '
+                                 f'this run ({tuple(t.shape)} {t.dtype})')
+        records = int(sd['records'])
+        if not 0 <= records <= self.capacity or int(sd['covariance']['records']) != records:
+            raise ValueError(f'truth calibration: {records} records ({sd["covariance"]["records"]} in the covariance state), 0..'
+                             f'{self.capacity} expected')
+        self.below.view(torch.int16).copy_(sd['below'].view(torch.int16))
+        self.ints.copy_(sd['ints'])
+        self.floats.copy_(sd['floats'])
+        self.covariance.load_state_dict(sd['covariance'])
+        self.records = records
 
 
 COMPARISON_OPTION_KEYS = ('period', 'std_floor')

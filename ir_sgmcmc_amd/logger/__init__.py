@@ -327,6 +327,25 @@ def save_structure_report(logger, save_dirs, table, series, model='MCMC'):
                 f'{model}_structure_series.csv')
 
 
+def save_truth_calibration(logger, save_dirs, spacing, maps, mask, calibration, series, model='MCMC'):
+    """the known-transformation validation (absent in the reference): samples/{model}_truth_{error,mahalanobis}[_masked].nii.gz
+    (float32; NaN -- a non-finite state or truth there -- written as 0, the masked ones 0 outside the mask too),
+    samples/{model}_truth_calibration.csv and samples/{model}_truth_series.csv; `calibration` and `series` are the (header, rows)
+    of truth.calibration_csv / series_csv (floats by repr: they read back exactly)"""
+    from ..structure_report import write_csv
+    folder = _folder(save_dirs, 'samples')
+    for name in ('error', 'mahalanobis'):
+        im, undefined = _nan_to_zero(maps[name])
+        m = mask.reshape(im.shape).to(im.device) != 0
+        logger.info(f'{model}_truth_{name}: {undefined} voxels with a non-finite state written as 0')
+        save_im_to_disk(im, path.join(folder, f'{model}_truth_{name}.nii.gz'), spacing)
+        save_im_to_disk(im.where(m, im.new_zeros(())), path.join(folder, f'{model}_truth_{name}_masked.nii.gz'), spacing)
+    write_csv(path.join(folder, f'{model}_truth_calibration.csv'), *calibration)
+    write_csv(path.join(folder, f'{model}_truth_series.csv'), *series)
+    logger.info(f'{model} truth calibration: {len(calibration[1])} table rows, {len(series[1])} series rows -> '
+                f'{model}_truth_calibration.csv, {model}_truth_series.csv')
+
+
 def _nan_to_zero(im):
     """-> (the map with 0 where it is NaN, how many voxels that was)"""
     nan = im.isnan()

@@ -22,6 +22,7 @@ from .diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ICE_SPACES, JA
                           native_posterior_metric_names, native_posterior_options, native_resolution_options, surface_metric_names, surface_posterior_options)
 from .logger import setup_logging
 from .structure_report import structure_metric_names, structure_report_options
+from .truth import truth_metric_names, truth_options
 from .model import distributions as model_distr
 from .model import loss as model_loss
 from .optimizers import Adam
@@ -154,6 +155,9 @@ class ConfigParser:
             m += native_posterior_metric_names(native_posterior, self.structures_dict)
         if structure_report_options(self['trainer']) is not None:
             m += structure_metric_names(self['trainer'], self.structures_dict)
+        truth = truth_options(self['trainer'])
+        if truth is not None:
+            m += truth_metric_names(truth)
         return m
 
     def init_transformation_and_registration_modules(self):

@@ -34,14 +34,16 @@ from ..diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ChainMoments,
                            NATIVE_POSTERIOR_IMAGE_METRICS, NativePosterior, native_posterior_options,
                            native_resolution_options, PosteriorComparison, posterior_comparison_options, ResidualCheck,
                            residual_check_options, residual_metrics,
-                           SIMILARITY_METRICS, StructureReport, recorded_steps, voxel_scale)
+                           SIMILARITY_METRICS, StructureReport, TruthCalibration, recorded_steps, voxel_scale)
 from ..engine import EngineConfig, TransitionEngine
 from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_modes, save_displacement_quantiles, save_ess,
                       save_field, save_image_posterior, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_landmarks,
                       save_local_similarity_of_mean, save_local_similarity_posterior, save_native_mean, save_native_posterior, save_native_sample,
                       save_posterior_comparison, save_precond_sigma,
-                      save_residual_histogram, save_residual_nll, save_rhat, save_sample, save_structure_report, save_surface_posterior)
+                      save_residual_histogram, save_residual_nll, save_rhat, save_sample, save_structure_report, save_surface_posterior,
+                      save_truth_calibration)
 from .. import affine, bspline, image_posterior, multires, preconditioner, residual_check, structure_report
+from .. import truth as truth_ops
 from .. import masks as mask_ops  # (`masks` names the pair of masks in several methods below)
 from ..multires import coarse_start_options
 from ..utils import (calc_DSC_GPU, calc_image_similarity, calc_norm, calc_no_non_diffeomorphic_voxels, calc_residual_check,
@@ -202,6 +204,12 @@ class Trainer(VIMixin, BaseTrainer):
         self.structure_options = structure_report.structure_report_options(cfg_trainer, data_loader, self.structures_dict)
         self._structure_report = None
         self.structure_summary = None
+        # known-transformation validation (truth.py, diagnostics.TruthCalibration): None when trainer.truth is absent, and then
+        # nothing changes.  _truth: the dense truth on the device, in voxels as the transition writes the displacement, made (and,
+        # with "simulate", the moving triple replaced) in _run_model; a resumed run makes it again and checks its fingerprint
+        self.truth_options = truth_ops.truth_options(cfg_trainer)
+        self._truth, self._truth_floor, self._truth_initial, self._truth_calibration = None, None, None, None
+        self.truth_error, self.truth_mahalanobis, self.truth_summary = None, None, None
         # coarse-to-fine start (multires.py, _coarse_start): None unless trainer.MCMC_init is "coarse"
         self.coarse_options = coarse_start_options(cfg_trainer, config['data_loader']['args']['dims'],
                                                    config['transformation_module']['type'])
@@ -431,8 +439,8 @@ class Trainer(VIMixin, BaseTrainer):
 
     def _recorders(self):
         """the active recorders, in the order they record and finish: moments, labels, surfaces, Jacobian, images, covariance,
-        modes, quantiles, inverse consistency, landmarks, local similarity, residual check, posterior comparison, native posterior,
-        and last the structure report, which reads the maps the others have finished"""
+        modes, quantiles, inverse consistency, landmarks, local similarity, residual check, posterior comparison, truth
+        calibration, native posterior, and last the structure report, which reads the maps the others have finished"""
         period = lambda options: options and options['period']
         rows = (('chain_moments', self._chain_moments, self.diagnostics_period, 'convergence_diagnostics', 'chain moments',
                  'displacement', self._finish_diagnostics, 'moving_mask'),
@@ -462,6 +470,8 @@ class Trainer(VIMixin, BaseTrainer):
                  'residuals', self._finish_residual_check, 'fixed'),
                 ('posterior_comparison', self._posterior_comparison, period(self.comparison_options), 'posterior_comparison',
                  'posterior comparison', 'displacement', self._finish_posterior_comparison, 'moving_mask'),
+                ('truth_calibration', self._truth_calibration, period(self.truth_options), 'truth', 'truth calibration',
+                 'displacement', self._finish_truth_calibration, 'fixed'),
                 ('native_posterior', self._native_posterior, period(self.native_posterior_options), 'native_posterior',
                  'native posterior', 'displacement', self._finish_native_posterior, 'fixed'),
                 ('structure_report', self._structure_report, period(self.structure_options), 'structure_report',
@@ -772,6 +782,8 @@ class Trainer(VIMixin, BaseTrainer):
             self._comparison_init(self._outputs['displacement'].shape[2:])
         if self.precond_options is not None:
             self._precond_init()
+        if self.truth_options is not None:
+            self._truth_calibration_init(masks['fixed'])
         if self.structure_options is not None:
             if 'seg' not in fixed:
                 raise ValueError(f'trainer.structure_report needs the fixed segmentation ("seg"); fixed has {sorted(fixed)}')
@@ -1104,6 +1116,78 @@ class Trainer(VIMixin, BaseTrainer):
             steps = recorded_steps(self.no_iters_burn_in, self.no_samples_MCMC, opt['period'])
             save_structure_report(self.logger, self.config.save_dirs, structure_report.structures_csv(summary),
                                   structure_report.series_csv(ints, floats, report.names, steps, self.no_chains), 'MCMC')
+
+    # ---------------------------------------------------------------- known-transformation validation
+    def _truth_init(self, fixed, moving):
+        """trainer.truth -> self._truth, the dense truth (3,D,H,W) on the device in voxels of the registration grid, the unit the
+        recorders receive output['displacement'] in.  "simulate": truth.simulate_velocity + truth.known_pair -- the moving triple is
+        REPLACED by the fixed one pulled through the inverse of the known transformation; one log line gives the amplitude and the
+        truth's own error floor.  "file": truth.read_truth; the moving triple is left alone.  Deterministic: a resumed run makes the
+        same truth again.  -> the moving dict the run goes on with"""
+        opt = self.truth_options
+        dims = tuple(int(n) for n in fixed['im'].shape[2:])
+        sp = getattr(self.data_loader, 'im_spacing', None)
+        spacing = [1.0, 1.0, 1.0] if sp is None else [float(s) for s in torch.as_tensor(sp).reshape(-1)][:3]
+        if opt['source'] == 'simulate':
+            v = truth_ops.simulate_velocity(dims, opt['seed'], opt['amplitude'], opt['modes'], opt['max_wavenumber'])
+            known, self._truth, info = truth_ops.known_pair(fixed, v, getattr(self.transformation_module, 'no_steps', 12), opt['noise'],
+                                                            opt['seed'])
+            moving = {**moving, **known}
+            self._truth_floor = info
+            self.logger.info(f'truth (simulated, seed {opt["seed"]}): velocity amplitude {info["amplitude"]:.4g} voxels, largest '
+                             f'displacement component {info["truth_max"]:.4g} voxels; error floor |phi*^-1 o phi* - id| over '
+                             f'{info["floor_voxels"]} masked voxels: mean {info["floor_mean"]:.3g}, max {info["floor_max"]:.3g} voxels '
+                             f'(an error below it means nothing); the moving image, mask and segmentation are replaced')
+        else:
+            # the package saves its fields in mm as displacement * spacing[0]: channel c of a file in mm is divided by spacing[c]
+            self._truth = torch.as_tensor(truth_ops.read_truth(opt['path'], dims, opt['unit'], spacing)).to(self.device)
+            self.logger.info(f'truth (file {opt["path"]}, {opt["unit"]}): largest displacement component '
+                             f'{float(self._truth.abs().max()):.4g} voxels')
+        if self.config['trainer'].get('save_outputs', True) and opt['save'] and opt['source'] == 'simulate':
+            from ..logger import save_field_to_disk
+            folder = self.config.save_dirs['samples']
+            folder.mkdir(parents=True, exist_ok=True)
+            save_field_to_disk(self._truth * spacing[0], str(folder / 'truth_displacement.vtk'), spacing)
+        return moving
+
+    def _truth_calibration_init(self, mask):
+        """self._truth_calibration over the FIXED mask (the truth lives on the fixed grid), its series sized from the config, and
+        the step-0 metrics truth/initial/{rmse,mean,max}: the error of the identity, the update kernel on a zero displacement
+        into scratch state.  scale (1, 1, 1): the transition writes the displacement in voxels, and so are the errors"""
+        steps = self.no_samples_MCMC // self.truth_options['period']
+        self._truth_calibration = TruthCalibration(self._truth, steps * self.no_chains, self.device, mask=mask)
+        self._truth_initial = self._truth_calibration.initial_error()
+        self.writer.set_step(0)
+        for key in truth_ops.INITIAL_METRICS:
+            self.metrics.update(f'truth/initial/{key}', self._truth_initial[key])
+        self.logger.info('truth: error of the unregistered pair (identity) over the fixed mask: mean '
+                         f'{self._truth_initial["mean"]:.4g}, RMS {self._truth_initial["rmse"]:.4g}, max {self._truth_initial["max"]:.4g} voxels')
+
+    def _finish_truth_calibration(self, fixed, spacing, save_outputs):
+        """the posterior against the truth over the fixed mask -> self.truth_error / truth_mahalanobis (maps), self.truth_summary
+        (truth.calibration_summary), the MCMC/truth/* metrics and, with save_outputs and the option's save,
+        samples/MCMC_truth_{error,mahalanobis}[_masked].nii.gz, MCMC_truth_calibration.csv and MCMC_truth_series.csv"""
+        tc, opt = self._truth_calibration, self.truth_options
+        mask = fixed['mask'][0]
+        maps, s, (ints, floats) = tc.finalize(mask, opt['levels'], opt['pit_bins'], opt['rank_bins'], opt['reliability_bins'],
+                                              opt['std_floor'], opt['reference'], self._truth_initial, self._truth_floor)
+        self.truth_error, self.truth_mahalanobis, self.truth_summary = maps['error'], maps['mahalanobis'], s
+        for key in truth_ops.METRIC_KEYS:
+            self.metrics.update(f'MCMC/truth/{key}', s[key])
+        for key, row in s['coverage'].items():
+            self.metrics.update(f'MCMC/truth/coverage_{key}', row['observed'])
+        self.logger.info(f'truth calibration of {s["records"]} samples over {s["voxels"]} masked voxels ({s["nonfinite_voxels"]} '
+                         f'non-finite, {s["raised_voxels"]} with a raised pivot), reference {s["reference"]}: error of the posterior mean '
+                         f'RMS {s["rmse"]:.4g}, mean {s["mean"]:.4g}, max {s["max"]:.4g} voxels (identity: RMS {s["initial_rmse"]:.4g}; '
+                         f'error floor of the truth: mean {s["floor_mean"]:.3g}' + (', ABOVE this mean error' if s['below_floor'] else '') +
+                         '); coverage ' + ', '.join(f'{row["observed"]:.3f} at {row["nominal"]:g}' for row in s['coverage'].values()) +
+                         f'; scale factor {s["scale_factor"]:.4g} (an autocorrelated chain has n_eff < n: part of a factor above 1 is '
+                         f'the Monte-Carlo error of the mean); ENCE {s["ence"]:.4g}; PIT chi2 {s["pit_chi2"]:.4g}, KS {s["pit_ks"]:.4g}; '
+                         f'z RMS x {s["z_rms_x"]:.3f}, y {s["z_rms_y"]:.3f}, z {s["z_rms_z"]:.3f}')
+        if save_outputs and opt['save']:
+            steps = recorded_steps(self.no_iters_burn_in, self.no_samples_MCMC, opt['period'])
+            save_truth_calibration(self.logger, self.config.save_dirs, spacing, maps, mask, truth_ops.calibration_csv(s),
+                                   truth_ops.series_csv(ints, floats, steps, self.no_chains), 'MCMC')
 
     def _image_init(self, fixed, moving):
         """trainer.image_posterior -> self._image_volumes (S,1,D,H,W) on the device: the moving image as the chain warps it, then
@@ -1596,6 +1680,8 @@ class Trainer(VIMixin, BaseTrainer):
         for fixed, moving, var_params_q_v in self.data_loader:
             fixed = {k: v.to(self.device) for k, v in fixed.items()}
             moving = {k: v.to(self.device) for k, v in moving.items()}
+            if self.truth_options is not None:
+                moving = self._truth_init(fixed, moving)
             if self.auto_mask_options is not None:
                 self._auto_mask(fixed, moving)
             if self.affine_options is not None:

@@ -225,6 +225,24 @@ def calc_structure_report(displacements, transformations, seg_fixed, structures_
 
 
 @torch.no_grad()
+def calc_truth_calibration(displacements, truth, mask=None, chains=1, scale=(1.0, 1.0, 1.0), levels=(0.5, 0.9, 0.95), pit_bins=20,
+                           rank_bins=16, reliability_bins=16, std_floor=1e-3, reference='hotelling'):
+    """Samples against a known displacement (absent in the reference): displacements (n,3,D,H,W) float32 on the device, n <= 65535
+    records ordered by step, then by chain (`chains` per step); truth (3,D,H,W) float32 in the same unit; mask (D,H,W) or None;
+    scale: three floats, one per channel, the unit of the errors.  -> (maps {'error', 'mahalanobis'}: (D,H,W) float32 on the
+    device, summary dict of truth.calibration_summary with 'initial_*' the error of a zero displacement, series (ints (n,2),
+    floats (n,3)) of the per-record error rows), as Trainer.truth_summary."""
+    from ..diagnostics import TruthCalibration
+    if displacements.dim() != 5 or displacements.shape[1] != 3:
+        raise ValueError(f'displacements must have shape (n, 3, D, H, W), got {tuple(displacements.shape)}')
+    n = displacements.shape[0]
+    tc = TruthCalibration(truth, max(n, 1), displacements.device, scale, mask)
+    for i in range(0, n, chains):  # one launch takes the records of one step, in order
+        tc.record(displacements[i:i + chains].float().contiguous())
+    return tc.finalize(None, levels, pit_bins, rank_bins, reliability_bins, std_floor, reference, initial=tc.initial_error())
+
+
+@torch.no_grad()
 def calc_image_posterior(volumes, transformations, reference=None, mask=None, std_floor=0.0):
     """Volumes carried through transformation samples (absent in the reference): volumes (S,1,D,H,W) float32 on the device, on
     the grid the transformations sample, S in 1 .. 8; transformations (n,3,D,H,W) float32 in normalised coordinates, the n
