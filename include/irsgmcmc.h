@@ -36,6 +36,10 @@ extern "C" {
 
 enum { IRS_DATA_GMM_LCC = 0, IRS_DATA_SSD = 1 };
 enum { IRS_REG_L2 = 0, IRS_REG_LOGNORMAL = 1, IRS_REG_STUDENT = 2, IRS_REG_LOGNORMAL_L2 = 3 };
+/* differential operator of the regulariser energy y (irs_config.diff_op): the reference's GradientOperator, or the same
+ * operator applied twice (HessianOperator, the bending energy) */
+#define IRS_DIFF_GRADIENT 0
+#define IRS_DIFF_HESSIAN 1
 
 /* ------------------------------------------------------------------------------------------------
  * stateless operators (unit-parity surface; the Python modules SVF_3D, RegistrationModule, GMM.map,
@@ -108,6 +112,17 @@ int irs_lcc_map_bwd(const float* fhat, int Cf, const float* z, const float* sigm
  * y_out: C doubles on the device.  partials: scratch of irs_reduce_scratch_doubles() doubles. */
 int irs_reg_energy(const float* v, double* y_out, double* partials, int C, int D, int H, int W, void* stream);
 size_t irs_reduce_scratch_doubles(void);
+/* Bending energy: GradientOperator applied twice (forward differences, the difference array replicate-padded, both times),
+ * y[c] = sum over component, axis pair (a, b), voxel of (d_a d_b v_comp)^2.  Per component f, w(q) = 2 for q = n - 2, else 1:
+ *   pure terms   (f[i+2] - 2 f[i+1] + f[i])^2 for i <= n_a - 3 along every axis a, weight 1;
+ *   mixed terms  2 w_a(i) w_b(j) (f[i+1,j+1] - f[i,j+1] - f[i+1,j] + f[i,j])^2 for i <= n_a - 2, j <= n_b - 2, every a < b.
+ * v: (C,3,D,H,W); y_out: C doubles on the device; partials: scratch of irs_reduce_scratch_doubles() doubles.  Sums in a fixed
+ * order (no atomics): two calls give the same bits. */
+int irs_bending_energy(const float* v, double* y_out, double* partials, int C, int D, int H, int W, void* stream);
+/* out[c] = scale[c] * d y[c] / d v[c] = scale[c] * 2 H^T W H v[c], the exact adjoint of the above (in the interior the 25-tap
+ * stencil {centre 84, axis neighbours -24, axis distance two +2, in-plane diagonals +4} per component).
+ * scale: C floats on the device, or NULL for 1; out: (C,3,D,H,W), not v. */
+int irs_bending_energy_grad(const float* v, const float* scale, float* out, int C, int D, int H, int W, void* stream);
 /* GradientOperator.forward: nabla (C,3,D,H,W,3) as in utils/diff_op.py:92-96; transformation != 0 divides by the
  * pixel spacing 2/(N-1). */
 int irs_gradient_operator(const float* v, float* nabla, int transformation, int C, int D, int H, int W, void* stream);
@@ -1014,6 +1029,8 @@ typedef struct irs_config {
     float reg_lr0, reg_lr1, reg_lr_decay; /* (lr_loc, lr_log_scale) or (lr_log_w_reg, -) */
     float loc_prior_nu, loc_prior_w_reg;  /* LogEnergyExpGammaPrior */
     float reg_scale_prior_loc, reg_scale_prior_scale; /* LogScaleNormalPrior on log_scale */
+    int32_t diff_op;        /* IRS_DIFF_*; 0 (a zeroed struct) is the GradientOperator.  Sits where the padding in front of
+                               the doubles was: no other offset moved */
     double w_reg_prior_shape, w_reg_prior_rate;       /* LogPrecisionExpGammaPrior (learnable RegLoss_L2);
                                                          RegLoss_Student (model/loss.py:201-241): {a0, 2 b0} */
     uint64_t seed;          /* Philox key for in-kernel noise */

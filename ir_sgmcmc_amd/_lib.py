@@ -61,6 +61,7 @@ IRS_AFFINE_WS_BYTES = IRS_AFFINE_MAX_BLOCKS * IRS_AFFINE_PARTIALS * 8
 IRS_MASK_MIN_BINS, IRS_MASK_MAX_BINS, IRS_MASK_MAX_KEEP, IRS_MASK_MAX_RADIUS = 2, 4096, 64, 16
 IRS_DATA_GMM_LCC, IRS_DATA_SSD = 0, 1
 IRS_REG_L2, IRS_REG_LOGNORMAL, IRS_REG_STUDENT, IRS_REG_LOGNORMAL_L2 = 0, 1, 2, 3
+IRS_DIFF_GRADIENT, IRS_DIFF_HESSIAN = 0, 1
 
 
 class IrsConfig(C.Structure):
@@ -76,7 +77,7 @@ class IrsConfig(C.Structure):
         ('reg_loss', C.c_int32), ('reg_learnable', C.c_int32), ('w_reg', C.c_float), ('dof', C.c_double),
         ('reg_lr0', C.c_float), ('reg_lr1', C.c_float), ('reg_lr_decay', C.c_float),
         ('loc_prior_nu', C.c_float), ('loc_prior_w_reg', C.c_float),
-        ('reg_scale_prior_loc', C.c_float), ('reg_scale_prior_scale', C.c_float),
+        ('reg_scale_prior_loc', C.c_float), ('reg_scale_prior_scale', C.c_float), ('diff_op', C.c_int32),
         ('w_reg_prior_shape', C.c_double), ('w_reg_prior_rate', C.c_double),
         ('seed', C.c_uint64),
     ]
@@ -170,6 +171,8 @@ SIGNATURES = {
     'irs_lcc_map_bwd': [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     'irs_reg_energy': [_P, _P, _P, _I, _I, _I, _I, _P],
     'irs_reduce_scratch_doubles': [],
+    'irs_bending_energy': [_P, _P, _P, _I, _I, _I, _I, _P],
+    'irs_bending_energy_grad': [_P, _P, _P, _I, _I, _I, _I, _P],
     'irs_gradient_operator': [_P, _P, _I, _I, _I, _I, _I, _P],
     'irs_log_det_jacobian': [_P, _P, _P, _I, _I, _I, _I, _P],
     'irs_label_boxes': [_P, _I, _P, _I32P, _I, _P, _I, _I, _I, _I, _P],

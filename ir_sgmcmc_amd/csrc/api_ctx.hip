@@ -36,6 +36,8 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
         if (cfg->gmm_components < 1 || cfg->gmm_components > IRS_MAX_COMPONENTS) return fail("irs_create: 1..%d mixture components", IRS_MAX_COMPONENTS);
     } else if (!(cfg->ssd_sigma > 0.0f)) return fail("irs_create: ssd_sigma must be positive");
     if (cfg->reg_loss < IRS_REG_L2 || cfg->reg_loss > IRS_REG_LOGNORMAL_L2) return fail("irs_create: unknown regulariser");
+    if (cfg->diff_op != IRS_DIFF_GRADIENT && cfg->diff_op != IRS_DIFF_HESSIAN)
+        return fail("irs_create: unknown diff_op %d (IRS_DIFF_GRADIENT or IRS_DIFF_HESSIAN; zero the irs_config before filling it)", cfg->diff_op);
     if ((cfg->reg_loss == IRS_REG_STUDENT || cfg->reg_loss == IRS_REG_LOGNORMAL_L2) && cfg->reg_learnable)
         return fail("irs_create: RegLoss_Student / RegLoss_LogNormal_L2 have no learnable parameters");
     if (cfg->reg_loss == IRS_REG_STUDENT && !(cfg->w_reg_prior_rate > 0.0 && cfg->w_reg_prior_shape > 0.0))
@@ -514,11 +516,14 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
     // after it, inside the finalize launch (same values in, same order of the hyper-parameter step: the update still sees the
     // w of this transition)
     const int upd_blocks = sgld_update_blocks_per_chain(volv, C);
-    const bool energy_in_update = (cfg.reg_loss == IRS_REG_L2 || cfg.reg_loss == IRS_REG_LOGNORMAL_L2) &&
+    // the bending prior (bending_kernels.hip): its energy always comes first, whatever the knob says
+    const bool bending = cfg.diff_op == IRS_DIFF_HESSIAN;
+    const bool energy_in_update = !bending && (cfg.reg_loss == IRS_REG_L2 || cfg.reg_loss == IRS_REG_LOGNORMAL_L2) &&
                                   (int64_t)upd_blocks * C <= (int64_t)kMaxPartialBlocks * IRS_MAX_CHAINS &&
                                   c->kn.energy_in_update != 0;
     if (!energy_in_update) {
-        launch_reg_energy(vs, c->energy_partials, C, volv, st);
+        if (bending) launch_bending_energy(vs, c->energy_partials, energy_blocks(volv), C, volv, st);
+        else launch_reg_energy(vs, c->energy_partials, C, volv, st);
         launch_reg_scalar(c->state, c->energy_partials, energy_blocks(volv), c->dcfg, st, vd);
     }
 
@@ -617,8 +622,11 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
         launch_scale_channels(g0, scaled, s[0], s[1], s[2], C, vol, st);
         const int G[3] = {volv.D, volv.H, volv.W};
         ffd_adjoint(scaled, c->tmpB, c->tmpA, C, vol, G, c->spl, st);
-        launch_sgld_update(io->v, io->sigma, c->tmpB, vs, c->state, cfg.lr, 1.0f, 1.0f, 1.0f, io->grad_v, C, volv, st,
-                           energy_in_update ? c->energy_partials : nullptr, energy_in_update);
+        if (bending) launch_sgld_update_bending(io->v, io->sigma, c->tmpB, vs, c->state, cfg.lr, 1.0f, 1.0f, 1.0f, io->grad_v, C, volv, st);
+        else launch_sgld_update(io->v, io->sigma, c->tmpB, vs, c->state, cfg.lr, 1.0f, 1.0f, 1.0f, io->grad_v, C, volv, st,
+                                energy_in_update ? c->energy_partials : nullptr, energy_in_update);
+    } else if (bending) {
+        launch_sgld_update_bending(io->v, io->sigma, g0, vs, c->state, cfg.lr, s[0], s[1], s[2], io->grad_v, C, volv, st);
     } else {
         launch_sgld_update(io->v, io->sigma, g0, vs, c->state, cfg.lr, s[0], s[1], s[2], io->grad_v, C, volv, st,
                            energy_in_update ? c->energy_partials : nullptr, energy_in_update);

@@ -323,6 +323,22 @@ int irs_reg_energy(const float* v, double* y_out, double* partials, int C, int D
     return 0;
 }
 
+int irs_bending_energy(const float* v, double* y_out, double* partials, int C, int D, int H, int W, void* stream) {
+    if (!v || !y_out || !partials || !dims_ok(C, D, H, W) || !chain_count_ok(C)) return fail("irs_bending_energy: bad arguments");
+    const Vol vol = make_vol(D, H, W);
+    launch_bending_energy(v, partials, energy_blocks(vol), C, vol, (hipStream_t)stream);
+    launch_reduce_partials(partials, energy_blocks(vol), C, y_out, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_bending_energy_grad(const float* v, const float* scale, float* out, int C, int D, int H, int W, void* stream) {
+    if (!v || !out || v == out || !dims_ok(C, D, H, W) || !chain_count_ok(C)) return fail("irs_bending_energy_grad: bad arguments");
+    launch_bending_grad(v, scale, out, C, make_vol(D, H, W), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 int irs_gradient_operator(const float* v, float* nabla, int transformation, int C, int D, int H, int W, void* stream) {
     if (!v || !nabla || !dims_ok(C, D, H, W)) return fail("irs_gradient_operator: bad arguments");
     launch_gradient_operator(v, nabla, transformation, C, make_vol(D, H, W), (hipStream_t)stream);

@@ -194,6 +194,15 @@ void launch_sgld_update_march(float* v, const float* sigma, const float* g_d0, c
 int stats_blocks(Vol vol);
 int energy_blocks(Vol vol);
 
+// ---- bending_kernels.hip: the second-order operator (HessianOperator) -- energy, gradient and the fused update
+// partials: [C][blocks] doubles (blocks = energy_blocks(vol), as for launch_reg_energy)
+void launch_bending_energy(const float* v, double* partials, int blocks, int C, Vol vol, hipStream_t st);
+// out = scale_c * 2 H^T W H v; scale: C floats on the device or nullptr (= 1)
+void launch_bending_grad(const float* v, const float* scale, float* out, int C, Vol vol, hipStream_t st);
+// launch_sgld_update with the bending stencil; the coefficient is always the one the scalar stage left in the state
+void launch_sgld_update_bending(float* v, const float* sigma, const float* g_d0, const float* v_s, const void* dev_state, float lr,
+                                float s0, float s1, float s2, float* grad_out, int C, Vol vol, hipStream_t st);
+
 // ---- metric_kernels.hip: average surface distance of label contours (utils/util.py:152-206)
 struct SurfLabels {
     int32_t v[IRS_MAX_LABELS];

@@ -47,6 +47,7 @@ class EngineConfig:
     loc_prior_w_reg: Optional[float] = None
     reg_scale_prior: Tuple[float, float] = (2.8, 5.0)
     seed: int = 0
+    diff_op: str = 'GradientOperator'                     # reg_loss diff_op: 'GradientOperator' | 'HessianOperator' (bending energy)
 
     @property
     def dims_v(self):
@@ -63,9 +64,20 @@ def lognormal_init(w_reg, dof, nu=1.0):
     return loc, math.log(4.0) + math.log(loc)
 
 
+DIFF_OPS = {'GradientOperator': L.IRS_DIFF_GRADIENT, 'HessianOperator': L.IRS_DIFF_HESSIAN}
+
+
+def diff_op_code(name):
+    """IRS_DIFF_* of a differential operator's class name"""
+    if name not in DIFF_OPS:
+        raise ValueError(f'diff_op {name!r} is not wired into the fused transition: one of {sorted(DIFF_OPS)}')
+    return DIFF_OPS[name]
+
+
 def irs_config(cfg: EngineConfig):
     """EngineConfig -> the C struct of include/irsgmcmc.h"""
     c = L.IrsConfig()
+    c.diff_op = diff_op_code(cfg.diff_op)
     c.dims[:] = list(cfg.dims)
     c.cps[:] = list(cfg.cps) if cfg.cps else [0, 0, 0]
     c.no_chains, c.no_steps = cfg.no_chains, cfg.no_steps

@@ -14,8 +14,9 @@ from torch import nn
 from torch.nn.functional import log_softmax
 
 from . import distributions as model_distr
+from .. import bending as _bending
 from .. import ops as _ops
-from ..utils.diff_op import DifferentialOperator, GradientOperator
+from ..utils.diff_op import DifferentialOperator, GradientOperator, HessianOperator
 
 
 class DataLoss(nn.Module, ABC):
@@ -136,6 +137,20 @@ class _Energy(torch.autograd.Function):
         return g
 
 
+class _BendingEnergy(torch.autograd.Function):
+    """y_c = sum (GradientOperator applied twice)^2, the bending energy; forward and backward (2 H^T W H v) both in HIP"""
+
+    @staticmethod
+    def forward(ctx, v):
+        ctx.save_for_backward(v)
+        return _bending.bending_energy(v).to(v.dtype)
+
+    @staticmethod
+    def backward(ctx, g_y):
+        v, = ctx.saved_tensors
+        return _bending.bending_energy_grad(v, g_y)
+
+
 class RegLoss(nn.Module, ABC):
     """all regularisers are functions of the energy y = |D v|^2 (model/loss.py:122-169)"""
 
@@ -156,6 +171,8 @@ class RegLoss(nn.Module, ABC):
     def forward(self, input, *args, **kwargs):
         if isinstance(self.diff_op, GradientOperator):
             y = _Energy.apply(input)
+        elif isinstance(self.diff_op, HessianOperator):
+            y = _BendingEnergy.apply(input)
         else:
             y = torch.sum(self.diff_op(input) ** 2, dim=tuple(range(1, input.dim())))
         return self._loss(y, *args, **kwargs)

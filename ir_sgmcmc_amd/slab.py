@@ -22,7 +22,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
-from .engine import EngineConfig, TransitionEngine, _on_device, irs_config
+from .engine import EngineConfig, TransitionEngine, _on_device, diff_op_code, irs_config
 
 
 class _RawDevice:
@@ -208,6 +208,9 @@ class SlabEngine(TransitionEngine):
 
     def __init__(self, cfg: EngineConfig, device='cuda:0', comm: SlabComm = None, ghost_max=0, margin=0):
         self.comm = comm
+        if diff_op_code(cfg.diff_op) != L.IRS_DIFF_GRADIENT:  # (the library's refusal, before anything is allocated)
+            raise L.IrsError(f'irs_slab_create: diff_op {diff_op_code(cfg.diff_op)} is not supported on z-slabs (the bending prior needs a '
+                             'two-plane halo of v_s): diff_op must be IRS_DIFF_GRADIENT')
         self._scfg = L.IrsSlabConfig(ghost_max, margin)
         super().__init__(cfg, device)
         lay = L.IrsSlabLayout()

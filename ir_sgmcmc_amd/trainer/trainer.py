@@ -35,7 +35,7 @@ from ..diagnostics import (COMPARISON_METRICS, COVARIANCE_METRICS, ChainMoments,
                            native_resolution_options, PosteriorComparison, posterior_comparison_options, ResidualCheck,
                            residual_check_options, residual_metrics,
                            SIMILARITY_METRICS, StructureReport, TruthCalibration, recorded_steps, voxel_scale)
-from ..engine import EngineConfig, TransitionEngine
+from ..engine import EngineConfig, TransitionEngine, diff_op_code
 from ..logger import (save_displacement_covariance, save_displacement_mean_and_std_dev, save_displacement_modes, save_displacement_quantiles, save_ess,
                       save_field, save_image_posterior, save_inverse_consistency, save_jacobian_posterior, save_label_posterior, save_landmarks,
                       save_local_similarity_of_mean, save_local_similarity_posterior, save_native_mean, save_native_posterior, save_native_sample,
@@ -356,7 +356,8 @@ class Trainer(VIMixin, BaseTrainer):
         rname = type(reg_loss).__name__
         if rname not in ('RegLoss_L2', 'RegLoss_LogNormal', 'RegLoss_Student', 'RegLoss_LogNormal_L2'):
             raise NotImplementedError(rname + ' is not wired into the fused transition')
-        ec.update(reg_loss=rname, reg_learnable=bool(reg_loss.learnable))
+        ec.update(reg_loss=rname, reg_learnable=bool(reg_loss.learnable), diff_op=type(reg_loss.diff_op).__name__)
+        diff_op_code(ec['diff_op'])  # (raises for an operator the fused transition does not have)
         if rname == 'RegLoss_L2':
             ec.update(w_reg=float(reg_loss.log_w_reg.exp()))
             if reg_loss.learnable:

@@ -11,7 +11,7 @@ class DifferentialOperator(nn.Module):
 
     @staticmethod
     def from_string(s, *args, **kwargs):
-        for cls in (GradientOperator,):
+        for cls in (GradientOperator, HessianOperator):
             if cls.__name__ in s:
                 return cls(*args, **kwargs)
         raise ValueError('Unknown differential operator: {}'.format(s))
@@ -64,3 +64,22 @@ class GradientOperator(DifferentialOperator):
         if transformation and self.pixel_spacing is None:
             self._set_spacing(v)
         return _EnergyGrad.apply(v, bool(transformation))
+
+
+class HessianOperator(DifferentialOperator):
+    """GradientOperator applied twice: the second application acts on the three first-difference fields of each component, by the
+    same rule (forward differences, the difference array replicate-padded).  Output (C, 9[3 a + b], D, H, W, 3[component]) with
+    out[:, 3 a + b, ..., comp] = d_a d_b v_comp (a, b over d/dx, d/dy, d/dz), so that sum(out ** 2) per chain is the bending energy
+    y of `ir_sgmcmc_amd.bending.bending_energy`.  No counterpart in the reference, which has the first-order operator only."""
+
+    def __init__(self):
+        super().__init__()
+        self.gradient = GradientOperator()
+
+    def forward(self, v):
+        n1 = self.gradient(v)  # (C, 3[b], D, H, W, 3[comp])
+        # G of the three first-difference fields of one component at a time: (C, 3[a], D, H, W, 3[b]) per component
+        per_comp = [self.gradient(n1[..., comp].contiguous()) for comp in range(3)]
+        h = torch.stack(per_comp, dim=-1)  # (C, 3[a], D, H, W, 3[b], 3[comp])
+        C, _, D, H, W = v.shape
+        return h.permute(0, 1, 5, 2, 3, 4, 6).reshape(C, 9, D, H, W, 3)
