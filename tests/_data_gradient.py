@@ -198,11 +198,23 @@ def forward(fixed, moving, h, s, dtype=F64):
     return z, tol_lcc(fixed, s)[0] + tol_lcc(moving, s)[0] + U * z.abs().to(F64)
 
 
-def data_gradient(z, moving, fixed, mask, alpha, params, h, s, dtype=F64, tol_params=None, n=None, drop=(), seam=None, w_from_z=False):
+def plane_distance(mask3):
+    """(D,H,W) bool -> (D,1,1): how many planes each plane lies outside the mask's extent along z (0 inside it)"""
+    on = mask3.flatten(1).any(1).nonzero().flatten()
+    zz = torch.arange(mask3.shape[0])
+    return torch.clamp(torch.maximum(int(on.min()) - zz, zz - int(on.max())), min=0).view(-1, 1, 1)
+
+
+def data_gradient(z, moving, fixed, mask, alpha, params, h, s, dtype=F64, tol_params=None, n=None, drop=(), seam=None, w_from_z=False,
+                  stale_map=None, no_fill=False):
     """z (C,1,D,H,W): the residual the mixture is evaluated at (the GPU's own); moving (1,1,D,H,W); fixed, mask (1 or C,1,D,H,W);
     alpha: C numbers; params: per chain (log_std, logits) in force for that chain's data term (SSD: ignored); tol_params: per chain
     the (2,K) spread of those parameters, or None.  n, drop, seam: the mistakes of box_t / lcc_adjoint.  w_from_z: w / sigma taken
     as fhat - z like the kernel does (the float32 evaluation), not from the moving image.
+    The mistakes of a list-walking data stage (GMM), for a mask that leaves planes out of reach: stale_map = r: the LCC map marched
+    only the planes within r of the mask's extent along z (the right reach is S) -- beyond them w / sigma and sigma are an earlier
+    transition's, here those of the moving image moved by one voxel along W; no_fill: the data term did not zero-fill g_M beyond
+    its reach of 2 S planes -- there g_M is an earlier transition's, here that of the mask of ones.
     -> dict g_m, A (C,1,D,H,W), grad_v, tol (C,3,D,H,W)"""
     C = z.shape[0]
     mv = moving.to(dtype)
@@ -220,7 +232,15 @@ def data_gradient(z, moving, fixed, mask, alpha, params, h, s, dtype=F64, tol_pa
             Es.append(torch.zeros_like(g_z))
             continue
         wh = fhat[c if len(fhat) > 1 else 0] - z[c, 0].to(dtype) if w_from_z else wh_m
-        g_m, A = lcc_adjoint(g_z, wh, sigma_m, s, n, drop, seam)
+        sigma = sigma_m
+        if stale_map is not None:
+            far = plane_distance(chain_of(mask, c)[0]) > stale_map
+            wh_old, sigma_old, _ = lcc_stats(mv[0, 0].roll(1, -1), s)
+            wh, sigma = torch.where(far, wh_old, wh), torch.where(far, sigma_old, sigma_m)
+        g_m, A = lcc_adjoint(g_z, wh, sigma, s, n, drop, seam)
+        if no_fill:
+            g_old = lcc_adjoint(float(alpha[c]) * dnll_dz(z[c, 0], ls, lg, h, dtype), wh, sigma, s)[0]
+            g_m = torch.where(plane_distance(chain_of(mask, c)[0]) > 2 * s, g_old, g_m)
         E = torch.zeros_like(A)
         if tol_params is not None:      # the parameters are only known to their spread: that much of g_z, through the absolute map
             dg = abs(float(alpha[c])) * mk * dnll_dz_spread(z[c, 0], ls, lg, tol_params[c], h).to(dtype)
@@ -247,6 +267,8 @@ def make_mask(kind, base, C):
         m = (xx + yy + zz) % 2 == 0
     elif kind == 'seam_planes':         # the two planes on either side of the seam between the first two 4-plane segments
         m = (zz == 3) | (zz == 4)
+    elif kind == 'band':                # the synthetic mask on the four planes around D / 2: planes no list of the data stage reaches
+        m = base[0, 0] & (zz >= D // 2 - 2) & (zz < D // 2 + 2)
     elif kind == 'faces':               # every face of the volume on the mask
         m = base[0, 0] | (xx == 0) | (xx == W - 1) | (yy == 0) | (yy == H - 1) | (zz == 0) | (zz == D - 1)
     elif kind == 'per_chain':           # chain c's mask rolled by 3 c voxels along W
@@ -301,6 +323,18 @@ ENGINE_CASES = [
 # (K = 2: the hand-set mixture's narrow component makes the rescaled residual so heavy-tailed that every lag correlation sits below
 # exp(-pi/2) and alpha is capped at exactly 1 -- those cases run without virtual decimation or on the checkerboard, where alpha = 1 is
 # the configuration's and not an accident that would hide a missing alpha)
+
+
+# The list-walking kernels of the sparse data stage (lcc_fwd_march_plan_kernel, lcc_data_bwd_march_plan_kernel) against the same
+# restatement: masks confined to a few planes, so that the lists leave planes unmarched on shapes this small, with pieces of
+# SPARSE_PIECE planes, so that D = 17 and D = 33 get seams inside a run range.
+SPARSE_PIECE = 4
+SPARSE_CASES = [
+    (E, 1, 1, 4, 'band', False, {}), (E, 2, 1, 5, 'band', False, {}), (M, 1, 1, 8, 'band', False, {}), (M, 2, 1, 4, 'band', False, {}),
+    (E, 2, 1, 8, 'seam_planes', False, {}), (M, 1, 1, 5, 'seam_planes', False, {}),
+    (E, 2, 1, 4, 'band', False, {'virtual_decimation': False}), (M, 1, 1, 5, 'band', False, {'virtual_decimation': False}),
+    (E, 1, 3, 4, 'band', True, {}), (M, 2, 3, 5, 'seam_planes', True, {}), (M, 2, 3, 8, 'band', True, {'virtual_decimation': False}),
+]
 
 
 def case_id(c):

@@ -2,7 +2,8 @@
 CPU oracle run in float64 at velocity zero (which pins the constant of the read-out and the face zeros), the same formulas in float32
 against the tolerance (a quarter of it at the most), the proof that the tolerance sees the mistakes it is for (each beaten 10x at its
 worst element by a deliberate mistake in a copy of the restatement; the measured ratios are in DESIGN.md), and the conditions every
-case of the GPU test has to meet for that to mean something."""
+case of the GPU test has to meet for that to mean something -- the cases of the list-walking kernels (G.SPARSE_CASES) included: their
+masks leave planes out of every list's reach, and a reach one short or a missing fill there is beyond the tolerance."""
 import pytest
 import torch
 
@@ -98,7 +99,10 @@ def wrong(c, **kw):
 
 
 # b. float32 on the CPU stays inside a quarter of the tolerance; d. the inputs keep the reference inside the conditions
-@pytest.mark.parametrize('case', G.ENGINE_CASES, ids=[G.case_id(c) for c in G.ENGINE_CASES])
+ALL_CASES = G.ENGINE_CASES + G.SPARSE_CASES
+
+
+@pytest.mark.parametrize('case', ALL_CASES, ids=[G.case_id(c) for c in ALL_CASES])
 def test_every_gpu_case_float32_fits_and_conditions_hold(case):
     dims, s, C, K, mask_kind, per_chain_fixed, kw = case
     c = host_case(case)
@@ -137,6 +141,10 @@ def test_every_gpu_case_float32_fits_and_conditions_hold(case):
         elif mask_kind == 'seam_planes':
             lo, hi = max(3 - 2 * s, 1), min(4 + 2 * s, D - 2)
             assert float(inner[:, lo - 1:hi].double().mean()) >= 0.8 and not bool(inner[:, hi:].any()) and not bool(inner[:, :lo - 1].any())
+        elif mask_kind == 'band':
+            # four planes of the synthetic mask reach 4 + 4 S planes: every one of them shows, nothing beyond them does
+            lo, hi = max(D // 2 - 2 - 2 * s, 1), min(D // 2 + 1 + 2 * s, D - 2)
+            assert bool(inner[:, lo - 1:hi].flatten(2).any(2).all()) and not bool(inner[:, hi:].any()) and not bool(inner[:, :lo - 1].any())
         else:
             assert float(inner.double().mean()) >= 0.8, float(inner.double().mean())
     # the voxels no channel shows are the 8 corners, as a count
@@ -194,6 +202,55 @@ def test_tolerance_sees_a_neighbours_parameters_mask_and_fixed_image():
 def test_tolerance_sees_ignored_components_beyond_four(case):
     c = host_case(case)
     seen(f'K = {c["K"]}: components beyond the fourth ignored', worst(wrong(c, params=[(ls[:4], lg[:4]) for ls, lg in c['params']]), c['ref']))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# e. the cases of test_list_kernels_element_by_element: the lists leave planes unmarched, and the tolerance sees what a list-walking
+# data stage can get wrong there
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('case', G.SPARSE_CASES, ids=[G.case_id(c) for c in G.SPARSE_CASES])
+def test_sparse_cases_leave_planes_unmarched(case):
+    """at reach S (LCC map), 2 S (data term: tile 32 x 16) and 3 S (warp: tile 64 x 8) the run ranges the mask's geometry gives stay
+    below D x tile columns, and some run range is longer than two pieces: there are seams inside it"""
+    from tests.test_gpu_sparse_data import columns, planes_of, run_lengths
+    dims, s, C, K, mask_kind, per_chain_fixed, kw = case
+    _, _, mask = G.case_inputs(dims, C, mask_kind, per_chain_fixed)
+    assert mask.shape[0] == 1 and mask_kind in ('band', 'seam_planes') and dims in (E, M) and kw.get('data_loss', 'GMM') == 'GMM'
+    m3 = mask[0, 0]
+    for tile, reach in (((32, 16), s), ((32, 16), 2 * s), ((64, 8), 3 * s)):
+        runs = run_lengths(m3, tile, reach)
+        assert 0 < planes_of(runs) < dims[0] * columns(dims, tile), (tile, reach, planes_of(runs))
+        assert max(b - a for a, b in runs) < dims[0]
+    assert max(b - a for a, b in run_lengths(m3, (32, 16), 2 * s)) > G.SPARSE_PIECE
+    assert int(G.plane_distance(m3).max()) > 3 * s      # whole planes beyond every reach
+
+
+def test_sparse_cases_cover_what_they_are_for():
+    cases = G.SPARSE_CASES
+    assert {(c[1], c[3]) for c in cases} >= {(s, K) for s in (1, 2) for K in (4, 5, 8)}
+    assert {c[0] for c in cases} == {E, M} and {c[4] for c in cases} == {'band', 'seam_planes'}
+    assert any(c[2] == 3 and c[5] for c in cases) and any(c[2] == 1 for c in cases)
+    assert any(c[6].get('virtual_decimation') is False for c in cases) and any('virtual_decimation' not in c[6] for c in cases)
+    assert not {G.case_id(c) for c in cases} & {G.case_id(c) for c in G.ENGINE_CASES}
+
+
+@pytest.mark.parametrize('case', G.SPARSE_CASES, ids=[G.case_id(c) for c in G.SPARSE_CASES])
+def test_tolerance_sees_a_short_reach_and_a_missing_fill(case):
+    c = host_case(case)
+    seen(f'LCC map marched to reach S - 1, S = {c["s"]}', worst(wrong(c, stale_map=c['s'] - 1), c['ref']))
+    # (a missing fill leaves values where the reference and its tolerance are exactly 0: any of them is beyond the tolerance)
+    g = wrong(c, no_fill=True)
+    far = (G.plane_distance(c['mask'][0, 0]) > 2 * c['s']).expand(c['mask'].shape[-3:])
+    assert float(c['ref']['grad_v'][..., far].abs().max()) == 0.0 and float(c['ref']['tol'][..., far].max()) == 0.0
+    assert float(g[..., far].abs().max()) > 0.0
+    seen(f'data term without its zero fill, S = {c["s"]}', worst(g, c['ref']))
+    # ... and the mistakes of the dense kernels, where these masks can show them: a seam inside the run range (between two pieces of
+    # G.SPARSE_PIECE planes), the wrong 1 / n, alpha left out
+    seam = 4 if case[4] == 'seam_planes' else case[0][0] // 2
+    seen(f'ring not primed at the seam at plane {seam}, S = {c["s"]}', worst(wrong(c, seam=seam), c['ref']))
+    seen(f'1 / n with n = (2S+1)^2, S = {c["s"]}', worst(wrong(c, n=(2 * c['s'] + 1) ** 2), c['ref']))
+    if c['h'].virtual_decimation:
+        seen(f'alpha left out, S = {c["s"]}', worst(wrong(c, alpha=[1.0] * c['C']), c['ref']))
 
 
 def test_tolerance_sees_sigma_for_sigma_squared_ssd():

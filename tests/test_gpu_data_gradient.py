@@ -11,7 +11,11 @@ Shapes (tile 32 x 16, 4-plane segments): (9,17,33) x tiles 32 + 1, y tiles 16 + 
 1 wide, one ragged tile row, segments 4 + 1, the smallest depth lcc_s = 2 takes; (33,5,65) many segments, the smallest height for
 lcc_s = 2; (17,33,65) interior full tiles, seams on both axes.  The tolerance is derived on the reference side (1e-5 of the absolute
 addends of each output, plus the rounding of the read-out); tests/test_data_gradient_host.py proves on the CPU that a float32
-evaluation uses less than a tenth of it and that each mistake it is for exceeds it by more than 1e4."""
+evaluation uses less than a tenth of it and that each mistake it is for exceeds it by more than 1e4.
+
+The engine read-out asks for the residuals, which gives it the dense stage whatever the context would choose.  The list-walking kernels
+of the sparse data stage -- lcc_fwd_march_plan_kernel<S>, lcc_data_bwd_march_plan_kernel<S, BATCH> -- are held to the same restatement
+by test_list_kernels_element_by_element: G.SPARSE_CASES, masks confined to a few planes, pieces of 4 planes, grad_v the only output."""
 import os
 import subprocess
 import sys
@@ -42,8 +46,11 @@ def check_each(test, key, a, b, tol):
     return check(test, key + ' [deviation / tolerance]', torch.where(exact, torch.zeros_like(tol), (a - b).abs() / tol), torch.zeros_like(tol), 1.0)
 
 
-def run_engine(case, options=None, sparse_adjoint=None):
-    """one transition of the case at velocity zero -> what the GPU wrote and was given, on the CPU"""
+def run_engine(case, options=None, sparse_adjoint=None, sparse_data=None):
+    """one transition of the case at velocity zero -> what the GPU wrote and was given, on the CPU.  sparse_data: a piece length -- the
+    sparse data stage forced on with it (the list-walking kernels), after a transition with a mask of ones at another velocity under
+    the same pointers has left every buffer of the context full of values that are wrong for this one; only grad_v is asked for, as
+    a caller who wants the residuals or the warped image gets the dense stage"""
     dims, s, C, K, mask_kind, per_chain_fixed, kw = case
     cfg = EngineConfig(dims=dims, no_chains=C, sobolev_s=0, uniform_noise=0.0, lcc_s=s, gmm_components=K, lr=0.05, **kw)
     fixed, moving, mask = G.case_inputs(dims, C, mask_kind, per_chain_fixed)
@@ -53,6 +60,8 @@ def run_engine(case, options=None, sparse_adjoint=None):
         eng.option(k, v)
     if sparse_adjoint is not None:
         eng.set_sparse_adjoint(sparse_adjoint)
+    if sparse_data is not None:
+        eng.set_sparse_data(sparse_data)
     fd, md = eng.prepare(to_dev({'im': fixed, 'mask': mask}), to_dev({'im': moving}))
     state0 = None
     if cfg.data_loss == 'GMM':          # the hand-set mixture, well away from its optimum, zeroed moments
@@ -71,9 +80,21 @@ def run_engine(case, options=None, sparse_adjoint=None):
     z = lambda *shape: torch.full(shape, float('nan'), device=DEV, dtype=torch.float32)
     out = {'curr_state': z(C, 3, *dims), 'residuals': z(C, 1, *dims), 'grad_v': z(C, 3, *dims), 'displacement': z(C, 3, *dims)}
     v = torch.zeros(C, 3, *dims, device=DEV)
+    if sparse_data is not None:
+        out = {'grad_v': out['grad_v']}
+        # z, sigma_M, the warped image and g_warped of a quarter-voxel translation under a mask of ones: what a reach one short or a
+        # missing fill would leave in place.  Then the mixture, its moments and the iteration count as they were.
+        keep = fd['mask'].clone()
+        fd['mask'].fill_(True)
+        eng.transition(fd, md, v.fill_(0.25), None, torch.zeros(C, 3, *dims, device=DEV), None, out)
+        eng.set_state(st)
+        fd['mask'].copy_(keep)
+        v.zero_()
     eng.transition(fd, md, v, None, torch.zeros(C, 3, *dims, device=DEV), None, out)
     sc, st = eng.scalars(), eng.state()
     res = {k: t.cpu() for k, t in out.items()}
+    if sparse_data is not None:
+        res['plan'] = eng.sparse_data()
     res.update(alpha=list(sc['alpha']), state0=state0, v_new=v.cpu(),
                params=(torch.tensor(list(st.gmm_log_std)[:K], dtype=F64), torch.tensor(list(st.gmm_logits)[:K], dtype=F64)))
     return res
@@ -132,6 +153,31 @@ def test_sparse_adjoint_does_not_change_a_bit():
     on, off = run_engine(case), run_engine(case, sparse_adjoint=False)
     hold(case, off, '-dense_adjoint')
     assert torch.equal(on['grad_v'], off['grad_v']) and torch.equal(on['residuals'], off['residuals'])
+
+
+@pytest.mark.parametrize('case', G.SPARSE_CASES, ids=[G.case_id(c) for c in G.SPARSE_CASES])
+def test_list_kernels_element_by_element(case):
+    """lcc_fwd_march_plan_kernel and lcc_data_bwd_march_plan_kernel (the batch form for several chains) against the float64
+    restatement: the dense stage is held as above, then the sparse stage's grad_v to the SAME restatement -- fed the dense run's z and
+    the parameters read back -- at the same tolerance, and to the dense stage's grad_v as numbers"""
+    dims, s, C = case[0], case[1], case[2]
+    dense = run_engine(case)
+    ref = hold(case, dense)
+    sparse = run_engine(case, sparse_data=G.SPARSE_PIECE)
+    T = 'stage/data_gradient/' + G.case_id(case) + '-sparse'
+    grad = sparse['grad_v']
+    assert bool(torch.isfinite(grad).all())
+    for ch in range(3):
+        check_each(T, f'grad_v channel {ch}', grad[:, ch], ref['grad_v'][:, ch], ref['tol'][:, ch])
+    assert bool((grad == dense['grad_v']).all())          # as numbers: -0 == +0
+    assert sparse['alpha'] == dense['alpha'] and all(torch.equal(a, b) for a, b in zip(sparse['params'], dense['params']))
+    assert torch.equal(sparse['v_new'], -(torch.tensor(0.05, dtype=torch.float32) * grad))
+    all_planes = dims[0] * ((dims[1] + 15) // 16) * ((dims[2] + 31) // 32)
+    for ch in range(C):
+        for k in ('map', 'data_term'):
+            e = sparse['plan'][k][ch]
+            assert e['engaged'] == 1 and e['piece_len'] == G.SPARSE_PIECE and 0 < e['run_planes'] < all_planes, (k, ch, sparse['plan'])
+        assert sparse['plan']['warp'][ch]['engaged'] == 1 and 0 < sparse['plan']['warp'][ch]['run_planes'] < dims[0] * ((dims[1] + 7) // 8) * ((dims[2] + 63) // 64)
 
 
 SEG_CASE = (G.E, 1, 1, 4, 'synthetic', False, {})
