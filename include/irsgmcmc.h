@@ -34,7 +34,8 @@ extern "C" {
 #define IRS_MAX_LABELS 64    /* labels of one surface-distance call */
 #define IRS_HAUSDORFF_MAX_PERCENTILES 4 /* percentiles of one irs_label_hausdorff_distance call */
 
-enum { IRS_DATA_GMM_LCC = 0, IRS_DATA_SSD = 1 };
+/* data term (irs_config.data_loss).  The value 2 is reserved: irs_create refuses it. */
+enum { IRS_DATA_GMM_LCC = 0, IRS_DATA_SSD = 1, IRS_DATA_LNCC = 3 };
 enum { IRS_REG_L2 = 0, IRS_REG_LOGNORMAL = 1, IRS_REG_STUDENT = 2, IRS_REG_LOGNORMAL_L2 = 3 };
 /* differential operator of the regulariser energy y (irs_config.diff_op): the reference's GradientOperator, or the same
  * operator applied twice (HessianOperator, the bending energy) */
@@ -107,6 +108,24 @@ int irs_lcc_map_fwd(const float* fhat, int Cf, const float* warped, float* z, fl
 /* adjoint of GMM.map w.r.t. the warped image given g_z. */
 int irs_lcc_map_bwd(const float* fhat, int Cf, const float* z, const float* sigma_m, const float* g_z, float* g_warped,
                     int s, int C, int D, int H, int W, void* stream);
+
+/* The LNCC data term (absent in the reference): VoxelMorph's squared local normalised cross-correlation over the (2 radius + 1)^3
+ * box window with clamped indices (replicate padding), all of it float32.  With n = (2 radius + 1)^3 and the window sums S_f, S_m,
+ * S_ff, S_mm, S_fm of the fixed image F and the moving image M at a voxel,
+ *   A = S_fm - S_f S_m / n,  Bf = S_ff - S_f^2 / n,  Bm = S_mm - S_m^2 / n,  den = Bf Bm + eps,  d = 1 - A^2 / den
+ * (no special case: a flat window gives d = 1 and gradient 0), and the coefficient maps of the gradient of sum u d,
+ *   p = 2 u A / den,  q = 2 u A^2 Bf / den^2,  t = (q S_m - p S_f) / n.
+ * fixed: (Cf,1,D,H,W), Cf in {1, C}; moving: (C,1,D,H,W); upstream u: (Cu,1,D,H,W), Cu in {1, C}, or NULL for 1 (Cu ignored);
+ * radius 1 .. IRS_MAX_HALF_WIDTH with every dim >= 2 radius + 1; eps finite and > 0.  Outputs, each may be NULL: d (C,1,D,H,W);
+ * coef (C,3,D,H,W) = p, q, t; sums: C doubles on the device, sums[c] = sum u d of chain c, which needs partials: scratch of
+ * irs_reduce_scratch_doubles() doubles.  No atomics: two calls give the same bits, and chain c of a batch is the single-chain call. */
+int irs_lncc_fwd(const float* fixed, int Cf, const float* moving, const float* upstream, int Cu, int radius, float eps,
+                 float* d, float* coef, double* sums, double* partials, int C, int D, int H, int W, void* stream);
+/* g_moving = d(sum u d)/d(moving) = M box^T(q) - F box^T(p) - box^T(t) from the coefficient maps of irs_lncc_fwd, box^T the adjoint
+ * of the clamped box: the padding that was replicated from a face voxel counts there with its multiplicity, on all six faces.
+ * g_moving: (C,1,D,H,W), none of the inputs. */
+int irs_lncc_bwd(const float* fixed, int Cf, const float* moving, const float* coef, int radius, float* g_moving, int C, int D,
+                 int H, int W, void* stream);
 
 /* GradientOperator + energy (utils/diff_op.py:78-96, model/loss.py:158-159): y[c] = sum (fwd diff)^2.
  * y_out: C doubles on the device.  partials: scratch of irs_reduce_scratch_doubles() doubles. */
@@ -1013,7 +1032,7 @@ typedef struct irs_config {
     float uniform_alpha;    /* <= 0 -> disabled */
     int32_t virtual_decimation;
     int32_t data_loss;      /* IRS_DATA_* */
-    int32_t lcc_s;
+    int32_t lcc_s;          /* IRS_DATA_LNCC: the window radius, 1 .. IRS_MAX_HALF_WIDTH (weight and eps: irs_lncc_set) */
     int32_t gmm_components;
     float ssd_sigma;
     /* optimizer_GMM (optimizers/adam_rate_decay.py) + hyper-priors (trainer.py:68-77) */
@@ -1087,6 +1106,11 @@ int irs_velocity_dims(const irs_ctx* ctx, int32_t out[3]);
 
 /* pre-normalise the fixed image for the LCC map (iteration-invariant half of model/loss.py:103-105). */
 int irs_set_fixed(irs_ctx* ctx, const float* fixed_im, int fixed_chains, void* stream);
+/* IRS_DATA_LNCC: the data term of a chain is weight * sum mask * d (irs_lncc_fwd, radius = irs_config.lcc_s), alpha[c] = 1, and
+ * irs_io.residuals receives d at every voxel.  weight > 0, eps > 0, both finite; a context starts with 1 and 1e-5.  They travel
+ * here because irs_config has no room left, and may be set only before the first transition.  Such a context takes no virtual
+ * decimation and no z-slab, and its sparse data and sparse forward stages stay off (the sparse adjoint works as ever). */
+int irs_lncc_set(irs_ctx* ctx, float weight, float eps);
 /* blocking copies of the small state / scalars.  (A slab context whose transport has failed -- a peer gone, irs_slab_transition /
  * irs_flush return that error -- still answers these two: the device holds the state after the last good transition.) */
 int irs_get_state(irs_ctx* ctx, irs_state* out, void* stream);

@@ -30,10 +30,17 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     if (!dims_ok(C, D, H, W) || !chain_count_ok(C)) return fail("irs_create: bad dims / chains (C <= %d)", IRS_MAX_CHAINS);
     if (cfg->no_steps < 1 || cfg->no_steps > 30) return fail("irs_create: no_steps out of range");
     if (cfg->sobolev_s < 0 || cfg->sobolev_s > IRS_MAX_HALF_WIDTH) return fail("irs_create: sobolev_s out of range");
-    if (cfg->data_loss != IRS_DATA_GMM_LCC && cfg->data_loss != IRS_DATA_SSD) return fail("irs_create: unknown data loss");
+    if (cfg->data_loss != IRS_DATA_GMM_LCC && cfg->data_loss != IRS_DATA_SSD && cfg->data_loss != IRS_DATA_LNCC)
+        return fail("irs_create: unknown data loss");
     if (cfg->data_loss == IRS_DATA_GMM_LCC) {
         if (!lcc_ok(cfg->lcc_s, D, H, W)) return fail("irs_create: LCC half width must be 1 or 2");
         if (cfg->gmm_components < 1 || cfg->gmm_components > IRS_MAX_COMPONENTS) return fail("irs_create: 1..%d mixture components", IRS_MAX_COMPONENTS);
+    } else if (cfg->data_loss == IRS_DATA_LNCC) {
+        // (the window radius travels in lcc_s; weight and eps through irs_lncc_set)
+        if (cfg->lcc_s < 1 || cfg->lcc_s > IRS_MAX_HALF_WIDTH) return fail("irs_create: LNCC radius = %d, 1..%d", cfg->lcc_s, IRS_MAX_HALF_WIDTH);
+        if (D < 2 * cfg->lcc_s + 1 || H < 2 * cfg->lcc_s + 1 || W < 2 * cfg->lcc_s + 1)
+            return fail("irs_create: LNCC radius %d needs every dim >= %d", cfg->lcc_s, 2 * cfg->lcc_s + 1);
+        if (cfg->virtual_decimation != 0) return fail("irs_create: the LNCC data term takes no virtual decimation");
     } else if (!(cfg->ssd_sigma > 0.0f)) return fail("irs_create: ssd_sigma must be positive");
     if (cfg->reg_loss < IRS_REG_L2 || cfg->reg_loss > IRS_REG_LOGNORMAL_L2) return fail("irs_create: unknown regulariser");
     if (cfg->diff_op != IRS_DIFF_GRADIENT && cfg->diff_op != IRS_DIFF_HESSIAN)
@@ -55,6 +62,8 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     c->sparse_data = 1;        // (irs_sparse_data_set)
     c->sparse_forward = 1;     // (irs_sparse_forward_set)
     c->sparse_plan = 1;        // (irs_sparse_plan_set)
+    c->lncc_weight = 1.0f;     // (irs_lncc_set)
+    c->lncc_eps = 1e-5f;
     c->cfg = *cfg;
     c->C = C;
     c->vol = make_vol(D, H, W);
@@ -74,7 +83,8 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
 
     DevCfg& d = c->dcfg;
     d.K = cfg->data_loss == IRS_DATA_GMM_LCC ? cfg->gmm_components : 1;
-    d.mode = cfg->data_loss;
+    // (the statistics and scalar stages of an LNCC context only count the mask: to them it is an SSD context with 1 / sigma = 0)
+    d.mode = cfg->data_loss == IRS_DATA_LNCC ? IRS_DATA_SSD : cfg->data_loss;
     d.vd = cfg->virtual_decimation;
     d.C = C;
     d.gmm_lr_log_std = cfg->gmm_lr_log_std;
@@ -113,7 +123,8 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     // is the one that fits ALL chains into a resident set -- at 128^3, C = 2: 7-plane segments, 1216 workgroups of 11 plane steps in
     // one round instead of two launches of 1024 with 8 each
     c->nll_seg_C = (C > 1 && !sl && cfg->data_loss == IRS_DATA_GMM_LCC && c->kn.data_batch != 0) ? C : 1;
-    c->nll_blocks = data_bwd_blocks(cfg->data_loss, c->vol, c->nll_seg_C);
+    const bool lncc = cfg->data_loss == IRS_DATA_LNCC;
+    c->nll_blocks = lncc ? lncc_geometry(D, H, W, cfg->lcc_s).blocks : data_bwd_blocks(cfg->data_loss, c->vol, c->nll_seg_C);
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
     const size_t o_steps = take(fieldI * cfg->no_steps);
@@ -127,6 +138,7 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     const size_t o_gC = third ? take(fieldI) : 0;
     const size_t o_warped = take(imageI), o_z = take(imageI), o_sig = take(imageI), o_fhat = take(imageI), o_gM = take(imageI);
     const size_t o_dense = take(c->ffd ? fieldI : 0);
+    const size_t o_lncc = take(lncc ? 3 * imageI : 0);  // the coefficient maps p, q, t of the LNCC data term
     const size_t o_stat = take(sizeof(double) * kMaxPartialBlocks * kStatVals);
     const size_t o_energy = take(sizeof(double) * kMaxPartialBlocks * IRS_MAX_CHAINS);
     const size_t o_nll = take(sizeof(double) * (size_t)c->nll_blocks * C);
@@ -164,6 +176,7 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     c->fhat = (float*)(c->slab + o_fhat);
     c->gM = (float*)(c->slab + o_gM);
     c->dense = c->ffd ? (float*)(c->slab + o_dense) : nullptr;
+    c->lncc_coef = lncc ? (float*)(c->slab + o_lncc) : nullptr;
     c->stat_partials = (double*)(c->slab + o_stat);
     c->energy_partials = (double*)(c->slab + o_energy);
     c->nll_partials = (double*)(c->slab + o_nll);
@@ -383,6 +396,10 @@ static int forward_pass(irs_ctx* c, const irs_io* io, const float* v, bool with_
         launch_lcc_fwd_plan(c->fhat, c->fhat_chains == 1 ? 0 : c->vol.V, warped, z, c->sigM, cfg.lcc_s, C, c->vol, c->dplan, st);
     else if (cfg.data_loss == IRS_DATA_GMM_LCC)
         launch_lcc_fwd_march(c->fhat, c->fhat_chains == 1 ? 0 : c->vol.V, warped, z, c->sigM, cfg.lcc_s, C, c->vol, st);
+    else if (cfg.data_loss == IRS_DATA_LNCC)  // d into z, the coefficient maps for the adjoint, weight * sum mask * d per workgroup
+        launch_lncc_fwd(io->fixed_im, io->fixed_chains == 1 ? 0 : c->vol.V, warped, nullptr, 0, io->mask, io->mask_chains == 1 ? 0 : c->vol.V,
+                        cfg.lcc_s, c->lncc_eps, (double)c->lncc_weight, z, c->lncc_coef, c->nll_partials, C,
+                        lncc_geometry(c->vol.D, c->vol.H, c->vol.W, cfg.lcc_s), st);
     else
         launch_residual_ssd(io->fixed_im, io->fixed_chains == 1 ? 0 : c->vol.V, warped, z, C, c->vol, st);
     LAUNCH_CHECK();
@@ -468,10 +485,11 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
     // to 8 planes in less than one resident set: lists could only match them, and the plan's launches would be a net cost there, as
     // for the adjoint below.
     const bool lcc = cfg.data_loss == IRS_DATA_GMM_LCC;
+    const bool lncc = cfg.data_loss == IRS_DATA_LNCC;  // its window reads beyond the mask: no sparse data / forward stage
     const int forced_piece = c->sparse_data > 1 ? c->sparse_data : 0;  // (tests: short pieces on small volumes)
     int data_on = 0;
     c->dplan.forced_len = forced_piece;
-    if (c->sparse_data && c->dplan.entries && !io->im_moving_warped && !io->residuals &&
+    if (!lncc && c->sparse_data && c->dplan.entries && !io->im_moving_warped && !io->residuals &&
         (forced_piece > 0 || plan_min(lcc_dense_seg_len(vol, C, false), lcc_dense_seg_len(vol, c->nll_seg_C, true)) > kPlanMinLen)) {
         // the data term's list needs every chain in one launch (or a single chain); the per-chain launches keep their full columns
         const bool one_launch = C == 1 || (c->kn.data_batch != 0 && !(c->side && c->kn.chain_overlap != 0));
@@ -548,7 +566,7 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
         launch_stats(cfg.virtual_decimation, zc, mask, c->state, c->stat_partials, vol, st, c->dcfg.K);
         if (overlap && ch > 0) HIP_TRY(hipStreamWaitEvent(st, c->ev_side[2 * (ch - 1) + 1], 0));  // data term of chain ch - 1 has read the mixture
         launch_chain_scalar(c->state, c->stat_partials, sb, ch, (ch == 0 ? 7 : 3) | (batch ? 8 : 0), c->dcfg, st, vd);  // chain 0: + the verdict
-        if (batch || data_on == 3) continue;
+        if (batch || data_on == 3 || lncc) continue;
         const float* f = cfg.data_loss == IRS_DATA_GMM_LCC ? c->fhat + (c->fhat_chains == 1 ? 0 : (int64_t)ch * vol.V) : nullptr;
         hipStream_t ds = st;
         if (overlap && ch + 1 < C) {  // (the last chain's data term has nothing to overlap with: it stays on the caller's stream)
@@ -563,6 +581,9 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
     if (data_on == 3)  // (one chain, or all chains against their snapshots: scalar stage op bit 3 above)
         launch_lcc_data_bwd_plan(c->fhat, c->fhat_chains == 1 ? 0 : vol.V, z, c->sigM, io->mask, io->mask_chains == 1 ? 0 : vol.V, c->state, c->gM,
                                  cfg.lcc_s, C, vol, c->dplan, st);
+    else if (lncc)  // every chain in one launch: the coefficient maps of the forward pass -> g_warped
+        launch_lncc_bwd(io->fixed_im, io->fixed_chains == 1 ? 0 : vol.V, warped, c->lncc_coef, cfg.lcc_s, c->lncc_weight, c->gM, C,
+                        lncc_geometry(vol.D, vol.H, vol.W, cfg.lcc_s), st);
     else if (batch)
         launch_data_bwd(cfg.data_loss, c->fhat, c->fhat_chains == 1 ? 0 : vol.V, z, c->sigM, io->mask, io->mask_chains == 1 ? 0 : vol.V, nullptr,
                         c->state, 0, c->gM, c->nll_partials, cfg.lcc_s, C, vol, st, c->nll_seg_C);
@@ -747,6 +768,17 @@ int irs_sparse_plan_set(irs_ctx* c, int reuse) {
     if (!c) return fail("irs_sparse_plan_set: null argument");
     if (reuse < 0 || reuse > 3) return fail("irs_sparse_plan_set: bit 0 reuse, bit 1 the adjoint's lists from the gradient");
     c->sparse_plan = reuse;
+    return 0;
+}
+
+int irs_lncc_set(irs_ctx* c, float weight, float eps) {
+    if (!c) return fail("irs_lncc_set: null argument");
+    if (c->cfg.data_loss != IRS_DATA_LNCC) return fail("irs_lncc_set: the context's data loss is not IRS_DATA_LNCC");
+    if (!positive_finite(weight) || !positive_finite(eps))
+        return fail("irs_lncc_set: weight = %g, eps = %g, finite values > 0 needed", (double)weight, (double)eps);
+    if (c->n_enqueued > 0 || c->have_last_io) return fail("irs_lncc_set: weight and eps may be set only before the first transition");
+    c->lncc_weight = weight;
+    c->lncc_eps = eps;
     return 0;
 }
 

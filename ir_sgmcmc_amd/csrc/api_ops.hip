@@ -314,6 +314,42 @@ int irs_lcc_map_bwd(const float* fhat, int Cf, const float* z, const float* sigm
     return 0;
 }
 
+// the window of the LNCC data term (lncc_kernels.hip): radius 1 .. IRS_MAX_HALF_WIDTH, every dim at least the window
+static bool lncc_window_ok(const char* who, int radius, int D, int H, int W) {
+    if (radius < 1 || radius > IRS_MAX_HALF_WIDTH) return !fail("%s: LNCC radius = %d, 1..%d", who, radius, IRS_MAX_HALF_WIDTH);
+    const int n = 2 * radius + 1;
+    return (D >= n && H >= n && W >= n) || !fail("%s: dims (%d, %d, %d), every one >= 2 radius + 1 = %d needed", who, D, H, W, n);
+}
+
+int irs_lncc_fwd(const float* fixed, int Cf, const float* moving, const float* upstream, int Cu, int radius, float eps, float* d,
+                 float* coef, double* sums, double* partials, int C, int D, int H, int W, void* stream) {
+    if (!fixed || !moving || !dims_ok(C, D, H, W) || (sums && !partials)) return fail("irs_lncc_fwd: bad arguments");
+    if (!chains_ok("irs_lncc_fwd", C) || !lncc_window_ok("irs_lncc_fwd", radius, D, H, W)) return 1;
+    if (!broadcast_ok(Cf, C)) return fail("irs_lncc_fwd: fixed image of %d chains, 1 or %d needed", Cf, C);
+    if (upstream && !broadcast_ok(Cu, C)) return fail("irs_lncc_fwd: upstream of %d chains, 1 or %d needed", Cu, C);
+    if (!positive_finite(eps)) return fail("irs_lncc_fwd: eps = %g, a finite value > 0 needed", (double)eps);
+    const int64_t V = (int64_t)D * H * W;
+    const LnccGeom g = lncc_geometry(D, H, W, radius);
+    launch_lncc_fwd(fixed, Cf == 1 ? 0 : V, moving, upstream, Cu == 1 ? 0 : V, nullptr, 0, radius, eps, 1.0, d, coef,
+                    sums ? partials : nullptr, C, g, (hipStream_t)stream);
+    if (sums) launch_reduce_partials(partials, g.blocks, C, sums, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_lncc_bwd(const float* fixed, int Cf, const float* moving, const float* coef, int radius, float* g_moving, int C, int D,
+                 int H, int W, void* stream) {
+    if (!fixed || !moving || !coef || !g_moving || g_moving == fixed || g_moving == moving || g_moving == coef || !dims_ok(C, D, H, W))
+        return fail("irs_lncc_bwd: bad arguments");
+    if (!chains_ok("irs_lncc_bwd", C) || !lncc_window_ok("irs_lncc_bwd", radius, D, H, W)) return 1;
+    if (!broadcast_ok(Cf, C)) return fail("irs_lncc_bwd: fixed image of %d chains, 1 or %d needed", Cf, C);
+    const int64_t V = (int64_t)D * H * W;
+    launch_lncc_bwd(fixed, Cf == 1 ? 0 : V, moving, coef, radius, 1.0f, g_moving, C, lncc_geometry(D, H, W, radius),
+                    (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 int irs_reg_energy(const float* v, double* y_out, double* partials, int C, int D, int H, int W, void* stream) {
     if (!v || !y_out || !partials || !dims_ok(C, D, H, W) || !chain_count_ok(C)) return fail("irs_reg_energy: bad arguments");
     const Vol vol = make_vol(D, H, W);

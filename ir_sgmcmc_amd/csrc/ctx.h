@@ -56,6 +56,8 @@ struct irs_ctx {
     float *steps, *tmpA, *tmpB, *vs, *gA, *gB, *gC, *warped, *z, *sigM, *fhat, *gM, *dense;
     double *stat_partials, *energy_partials, *nll_partials;
     double *stat_sum, *energy_sum, *nll_sum;  // reduced partial sums (staged / slab path)
+    float* lncc_coef = nullptr;  // IRS_DATA_LNCC: (C,3,V) coefficient maps p, q, t, forward kernel -> adjoint kernel (lncc_kernels.hip)
+    float lncc_weight = 1.0f, lncc_eps = 1e-5f;  // irs_lncc_set
     unsigned* dmax;  // [no_steps + 1][C][4] max |d_k| in voxels per axis (float bits), by-product of the forward steps
     irs::AdjointPlan plan;  // sparse adjoint plan (adjoint_plan.hip); no buffers on a slab context
     bool sparse_adjoint = true;  // irs_sparse_adjoint_set: the adjoint steps walk the plan's lists (false: full columns)

@@ -482,6 +482,24 @@ void launch_local_similarity_update(const float* lncc, int C, int64_t V, float* 
 void launch_local_similarity_finalize(const float* mean, const float* low, const int32_t* count, int64_t V, const uint8_t* mask,
                                       long long* isummary, double* fsummary, void* ws, hipStream_t st);
 
+// ---- lncc_kernels.hip: the LNCC data term (squared local normalised cross-correlation over a box window) and its adjoint
+struct LnccGeom {
+    int D, H, W;
+    int tiles_x, tiles;  // 32 x 8 tiles along x, and per plane
+    int seg_len, nwork;  // planes per z-segment; work items = tiles x segments
+    int blocks;          // blocks per chain = partial sums per chain: min(nwork, kMaxPartialBlocks)
+};
+// the launch shape of a volume: depends on (D, H, W, radius) and the `lcc_seg` switch only
+LnccGeom lncc_geometry(int D, int H, int W, int radius);
+// fixed (1 or C,V) with fixed_stride 0 or V; moving (C,V); u = upstream (float, stride 0 or V) if given, else mask (uint8, stride 0
+// or V) if given, else 1.  d (C,V), coef (C,3,V: p, q, t) and partials ([C][g.blocks] doubles of scale * sum u d) may each be nullptr.
+void launch_lncc_fwd(const float* fixed, int64_t fixed_stride, const float* moving, const float* upstream, int64_t upstream_stride,
+                     const uint8_t* mask, int64_t mask_stride, int radius, float eps, double scale, float* d, float* coef,
+                     double* partials, int C, const LnccGeom& g, hipStream_t st);
+// g_moving (C,V) = scale * (M box^T(q) - F box^T(p) - box^T(t)) from the coefficient maps of the forward launch
+void launch_lncc_bwd(const float* fixed, int64_t fixed_stride, const float* moving, const float* coef, int radius, float scale,
+                     float* g_moving, int C, const LnccGeom& g, hipStream_t st);
+
 // ---- residual_kernels.hip: the residuals against the mixture that models them -- histogram, moments and the per-voxel NLL
 struct ResBins {
     int bins;

@@ -28,10 +28,12 @@ class EngineConfig:
     lr: float = 0.4                                       # optimizer_SG_MCMC.args.lr
     uniform_noise: float = 0.1                            # trainer.uniform_noise.magnitude (0 = disabled)
     virtual_decimation: bool = True
-    data_loss: str = 'GMM'                                # 'GMM' (reference) | 'SSD' (builder-defined)
+    data_loss: str = 'GMM'                                # 'GMM' (reference) | 'SSD' (builder-defined) | 'LNCC' (lcc_s = window radius)
     gmm_components: int = 4
     lcc_s: int = 1
     ssd_sigma: float = 0.1
+    lncc_weight: float = 1.0                              # 'LNCC': data term = lncc_weight * sum mask * (1 - cc), cc with + lncc_eps
+    lncc_eps: float = 1e-5
     gmm_lr_log_std: float = 0.2
     gmm_lr_logits: float = 0.2
     gmm_lr_decay: float = 0.001
@@ -64,6 +66,7 @@ def lognormal_init(w_reg, dof, nu=1.0):
     return loc, math.log(4.0) + math.log(loc)
 
 
+DATA_LOSSES = {'GMM': L.IRS_DATA_GMM_LCC, 'SSD': L.IRS_DATA_SSD, 'LNCC': L.IRS_DATA_LNCC}
 DIFF_OPS = {'GradientOperator': L.IRS_DIFF_GRADIENT, 'HessianOperator': L.IRS_DIFF_HESSIAN}
 
 
@@ -89,7 +92,9 @@ def irs_config(cfg: EngineConfig):
     c.lr = cfg.lr
     c.uniform_alpha = cfg.uniform_noise or 0.0
     c.virtual_decimation = int(cfg.virtual_decimation)
-    c.data_loss = L.IRS_DATA_GMM_LCC if cfg.data_loss == 'GMM' else L.IRS_DATA_SSD
+    if cfg.data_loss not in DATA_LOSSES:
+        raise ValueError(f'data_loss {cfg.data_loss!r} is not wired into the fused transition: one of {sorted(DATA_LOSSES)}')
+    c.data_loss = DATA_LOSSES[cfg.data_loss]
     c.lcc_s, c.gmm_components, c.ssd_sigma = cfg.lcc_s, cfg.gmm_components, cfg.ssd_sigma
     c.gmm_lr_log_std, c.gmm_lr_logits, c.gmm_lr_decay = cfg.gmm_lr_log_std, cfg.gmm_lr_logits, cfg.gmm_lr_decay
     c.adam_beta1, c.adam_beta2, c.adam_eps = 0.9, 0.999, 1e-8
@@ -135,6 +140,8 @@ class TransitionEngine:
         with torch.cuda.device(self.device):
             self._ctx = self._create(c)
         self._keep = {}
+        if cfg.data_loss == 'LNCC':  # (irs_config has no room for the two: they travel in a call of their own)
+            self.lncc_set(cfg.lncc_weight, cfg.lncc_eps)
         if cfg.reg_loss == 'RegLoss_LogNormal':
             st = self.state()
             st.reg_param[0], st.reg_param[1] = lognormal_init(cfg.w_reg, cfg.dof)
@@ -148,6 +155,10 @@ class TransitionEngine:
         ctx = C.c_void_p()
         L.check(self.lib.irs_create(C.byref(c), C.byref(ctx)))
         return ctx
+
+    def lncc_set(self, weight, eps):
+        """irs_lncc_set: weight and eps of the LNCC data term; only before the first transition"""
+        L.check(self.lib.irs_lncc_set(self._ctx, float(weight), float(eps)))
 
     def __del__(self):
         ctx, self._ctx = getattr(self, '_ctx', None), None

@@ -15,6 +15,7 @@ from torch.nn.functional import log_softmax
 
 from . import distributions as model_distr
 from .. import bending as _bending
+from .. import lncc as _lncc
 from .. import ops as _ops
 from ..utils.diff_op import DifferentialOperator, GradientOperator, HessianOperator
 
@@ -117,6 +118,41 @@ class SSD(DataLoss):
 
     def forward(self, z):
         return 0.5 * torch.sum((z / self.sigma) ** 2)
+
+
+class _LNCCMap(torch.autograd.Function):
+    """d = 1 - cc of the two images; backward runs both HIP operators with the incoming gradient as the upstream weight"""
+
+    @staticmethod
+    def forward(ctx, im_fixed, im_moving, radius, eps):
+        ctx.radius, ctx.eps = radius, eps
+        ctx.save_for_backward(im_fixed, im_moving)
+        return _lncc.lncc_forward(im_fixed, im_moving, radius, eps, want_coef=False, want_sums=False)['d']
+
+    @staticmethod
+    def backward(ctx, g_d):
+        im_fixed, im_moving = ctx.saved_tensors
+        coef = _lncc.lncc_forward(im_fixed, im_moving, ctx.radius, ctx.eps, upstream=g_d.contiguous(), want_map=False,
+                                  want_sums=False)['coef']
+        return None, _lncc.lncc_backward(im_fixed, im_moving, coef, ctx.radius), None, None
+
+
+class LNCC(DataLoss):
+    """local normalised cross-correlation over a (2 radius + 1)^3 box window, VoxelMorph's squared form: map = 1 - cc,
+    loss = weight * sum map.  Insensitive to a local gain and offset of either image.  No counterpart in the reference."""
+
+    def __init__(self, radius=2, weight=1.0, eps=1e-5):
+        super().__init__()
+        self.radius, self.weight, self.eps = int(radius), float(weight), float(eps)
+        self.no_components = 1
+
+    def map(self, im_fixed, im_moving):
+        if im_fixed.dim() == 5 and im_fixed.shape[0] > 1 and im_fixed.stride(0) == 0:
+            im_fixed = im_fixed[:1]
+        return _LNCCMap.apply(im_fixed.contiguous(), im_moving.contiguous(), self.radius, self.eps)
+
+    def forward(self, z):
+        return self.weight * z.sum()
 
 
 class _Energy(torch.autograd.Function):

@@ -211,6 +211,9 @@ class SlabEngine(TransitionEngine):
         if diff_op_code(cfg.diff_op) != L.IRS_DIFF_GRADIENT:  # (the library's refusal, before anything is allocated)
             raise L.IrsError(f'irs_slab_create: diff_op {diff_op_code(cfg.diff_op)} is not supported on z-slabs (the bending prior needs a '
                              'two-plane halo of v_s): diff_op must be IRS_DIFF_GRADIENT')
+        if cfg.data_loss == 'LNCC':
+            raise L.IrsError('irs_slab_create: the LNCC data term is not supported on z-slabs (its window and its adjoint need a halo of '
+                             '2 radius planes): data_loss must be GMM or SSD')
         self._scfg = L.IrsSlabConfig(ghost_max, margin)
         super().__init__(cfg, device)
         lay = L.IrsSlabLayout()

@@ -341,7 +341,7 @@ class Trainer(VIMixin, BaseTrainer):
                   no_steps=getattr(self.transformation_module, 'no_steps', 12), sobolev_s=self.Sobolev_s,
                   sobolev_lambda=self.Sobolev_lambda, lr=float(cfg['optimizer_SG_MCMC']['args']['lr']),
                   uniform_noise=float(self.alpha), virtual_decimation=bool(self.virutal_decimation),
-                  data_loss='GMM' if kind == 'GMM' else 'SSD', seed=int(cfg['trainer'].get('seed', 0)))
+                  data_loss=kind if kind in ('GMM', 'LNCC') else 'SSD', seed=int(cfg['trainer'].get('seed', 0)))
         if cfg['optimizer_SG_MCMC']['type'] != 'SGD':
             raise NotImplementedError('the SG-MCMC field update is plain SGD (reference configs), got ' + cfg['optimizer_SG_MCMC']['type'])
         if kind == 'GMM':
@@ -351,6 +351,14 @@ class Trainer(VIMixin, BaseTrainer):
                       gmm_lr_logits=o['lr_logits'], gmm_lr_decay=o['lr_decay'],
                       scale_prior=(float(sp.loc), float(sp.log_scale.exp())),
                       dirichlet_alpha=[float(x) for x in self.losses['data']['proportion_prior'].concentration])
+        elif kind == 'LNCC':
+            if self.virutal_decimation:
+                raise ValueError('the LNCC data loss takes no virtual decimation (its map is no residual whose correlation could be '
+                                 'estimated): set "virtual_decimation" to false')
+            if self.residual_options is not None:
+                raise ValueError('trainer.residual_check compares the residuals with the Gaussian mixture: it needs the GMM data loss, '
+                                 'not LNCC')
+            ec.update(lcc_s=data_loss.radius, lncc_weight=data_loss.weight, lncc_eps=data_loss.eps)
         else:
             ec.update(ssd_sigma=data_loss.sigma)
         rname = type(reg_loss).__name__
