@@ -35,7 +35,7 @@ extern "C" {
 #define IRS_HAUSDORFF_MAX_PERCENTILES 4 /* percentiles of one irs_label_hausdorff_distance call */
 
 /* data term (irs_config.data_loss).  The value 2 is reserved: irs_create refuses it. */
-enum { IRS_DATA_GMM_LCC = 0, IRS_DATA_SSD = 1, IRS_DATA_LNCC = 3 };
+enum { IRS_DATA_GMM_LCC = 0, IRS_DATA_SSD = 1, IRS_DATA_LNCC = 3, IRS_DATA_MI = 4 };
 enum { IRS_REG_L2 = 0, IRS_REG_LOGNORMAL = 1, IRS_REG_STUDENT = 2, IRS_REG_LOGNORMAL_L2 = 3 };
 /* differential operator of the regulariser energy y (irs_config.diff_op): the reference's GradientOperator, or the same
  * operator applied twice (HessianOperator, the bending energy) */
@@ -126,6 +126,42 @@ int irs_lncc_fwd(const float* fixed, int Cf, const float* moving, const float* u
  * g_moving: (C,1,D,H,W), none of the inputs. */
 int irs_lncc_bwd(const float* fixed, int Cf, const float* moving, const float* coef, int radius, float* g_moving, int C, int D,
                  int H, int W, void* stream);
+
+/* The mutual-information data term (absent in the reference): a Mattes-style estimator -- zero-order window on the fixed image, cubic
+ * B-spline window on the (warped) moving image -- per chain over the n voxels where the mask is set (or absent) and both
+ * intensities are finite.  With B = bins in IRS_MI_MIN_BINS .. IRS_MI_MAX_BINS and finite ranges with hi > lo:
+ *   fixed bin   a = min(B - 1, max(0, floor((f - f_lo) * (B / (f_hi - f_lo)))))   in float32, the rule of irs_image_similarity
+ *   moving      t_raw = (m - m_lo) * ((B - 3) / (m_hi - m_lo)) + 1,  t = clamp(t_raw, 1, B - 2),  k0 = min(floor(t), B - 3),
+ *               u = t - k0   in double, every operation rounded once; the taps k0 - 1 .. k0 + 2 always lie in [0, B - 1]
+ *   weights     w  = ((1-u)^3, 3u^3 - 6u^2 + 4, -3u^3 + 3u^2 + 3u + 1, u^3) / 6
+ *               w' = (-(1-u)^2 / 2, 1.5u^2 - 2u, -1.5u^2 + u + 0.5, u^2 / 2)
+ *   fixed point q_j = round(w_j 2^30) for j = 0, 2, 3 and q_1 = 2^30 - q_0 - q_2 - q_3: every voxel adds exactly 2^30 to the
+ *               uint64 histogram H, so sum H = n 2^30 as integers
+ *   p_ab = H_ab / (n 2^30), p_a and p_b from the integer row and column sums, T_ab = ln(p_ab / (p_a p_b)) (0 where H_ab = 0),
+ *   MI = sum p_ab T_ab, a fixed-order double sum; the data term of a chain is weight * n * (ln B - MI) >= 0, and 0 when n = 0.
+ *  - irs_mi_fwd.  fixed (Cf,1,D,H,W) float32, Cf in {1, C}; moving (C,1,D,H,W) float32; mask (Cm,1,D,H,W) uint8, Cm in {1, C}, or
+ *    NULL (Cm ignored).  Outputs on the device: hist (C,B,B) uint64, may be NULL; table (C,B,B) float32 = T; stats (C,
+ *    IRS_MI_STATS) double: n, n_nonfinite (masked voxels with a non-finite intensity), n_clipped (voxels that take part with f
+ *    outside [f_lo, f_hi] or t_raw outside [1, B - 2]), MI, H_f, H_m (the entropies of the marginals), the data term at weight 1.
+ *    scratch: IRS_MI_WS_BYTES bytes of device memory, 16-byte aligned.  The histogram is zeroed by a memset on the stream in front
+ *    of the accumulate kernel and left in place.
+ *  - irs_mi_bwd.  table from irs_mi_fwd with the same images, mask, bins and ranges.  g_moving (C,1,D,H,W) float32 =
+ *      -scale[c] * mask * inside * (B - 3) / (m_hi - m_lo) * sum_j w'_j(u) T[a][k0 - 1 + j],  inside: 1 <= t_raw <= B - 2,
+ *    the gradient of scale[c] * n * (ln B - MI) (n cancels, and so do the marginal terms: sum_j w'_j = 0); exactly 0 where the voxel
+ *    does not take part.  scale: C floats on the device, or NULL for 1.  pmi (C,1,D,H,W) float32, may be NULL: sum_j w_j T[a][k0 -
+ *    1 + j] at the voxels that take part, 0 elsewhere; in real arithmetic sum pmi = n MI.  Neither output may be an input.
+ * Integer histogram, fixed-order sums: two calls give the same bits, and chain c of a batch is the single-chain call. */
+#define IRS_MI_STATS 7
+#define IRS_MI_MIN_BINS 8
+#define IRS_MI_MAX_BINS 64
+#define IRS_MI_MAX_BLOCKS 1024 /* rows of per-block counts in the scratch: the accumulate grid has IRS_MI_MAX_BLOCKS / C blocks per chain at most */
+#define IRS_MI_WS_BYTES (IRS_MAX_CHAINS * IRS_MI_MAX_BINS * IRS_MI_MAX_BINS * 8 + IRS_MI_MAX_BLOCKS * 3 * 8)
+int irs_mi_fwd(const float* fixed, int Cf, const float* moving, const uint8_t* mask, int Cm, int bins, float f_lo, float f_hi,
+               float m_lo, float m_hi, uint64_t* hist, float* table, double* stats, void* scratch, int C, int D, int H, int W,
+               void* stream);
+int irs_mi_bwd(const float* fixed, int Cf, const float* moving, const uint8_t* mask, int Cm, const float* table, int bins, float f_lo,
+               float f_hi, float m_lo, float m_hi, const float* scale, float* g_moving, float* pmi, int C, int D, int H, int W,
+               void* stream);
 
 /* GradientOperator + energy (utils/diff_op.py:78-96, model/loss.py:158-159): y[c] = sum (fwd diff)^2.
  * y_out: C doubles on the device.  partials: scratch of irs_reduce_scratch_doubles() doubles. */
@@ -1032,7 +1068,8 @@ typedef struct irs_config {
     float uniform_alpha;    /* <= 0 -> disabled */
     int32_t virtual_decimation;
     int32_t data_loss;      /* IRS_DATA_* */
-    int32_t lcc_s;          /* IRS_DATA_LNCC: the window radius, 1 .. IRS_MAX_HALF_WIDTH (weight and eps: irs_lncc_set) */
+    int32_t lcc_s;          /* IRS_DATA_LNCC: the window radius, 1 .. IRS_MAX_HALF_WIDTH (weight and eps: irs_lncc_set);
+                             * IRS_DATA_MI: the bins, IRS_MI_MIN_BINS .. IRS_MI_MAX_BINS (weight and ranges: irs_mi_set) */
     int32_t gmm_components;
     float ssd_sigma;
     /* optimizer_GMM (optimizers/adam_rate_decay.py) + hyper-priors (trainer.py:68-77) */
@@ -1111,6 +1148,13 @@ int irs_set_fixed(irs_ctx* ctx, const float* fixed_im, int fixed_chains, void* s
  * here because irs_config has no room left, and may be set only before the first transition.  Such a context takes no virtual
  * decimation and no z-slab, and its sparse data and sparse forward stages stay off (the sparse adjoint works as ever). */
 int irs_lncc_set(irs_ctx* ctx, float weight, float eps);
+/* IRS_DATA_MI: the data term of a chain is weight * n * (ln B - MI) (irs_mi_fwd, B = irs_config.lcc_s), alpha[c] = 1, and
+ * irs_io.residuals receives mask * (ln B - pmi) (irs_mi_bwd), whose masked sum times weight is the data term.  weight > 0 and the
+ * two ranges, finite with hi > lo, travel here because irs_config has no room left; the call is required -- the library does not
+ * guess intensity ranges, and a transition of a context that never had it is refused -- and allowed only before the first
+ * transition.  Such a context takes no virtual decimation and no z-slab, and its sparse data and sparse forward stages stay off
+ * (the sparse adjoint works as ever: the gradient vanishes off the mask). */
+int irs_mi_set(irs_ctx* ctx, float weight, float f_lo, float f_hi, float m_lo, float m_hi);
 /* blocking copies of the small state / scalars.  (A slab context whose transport has failed -- a peer gone, irs_slab_transition /
  * irs_flush return that error -- still answers these two: the device holds the state after the last good transition.) */
 int irs_get_state(irs_ctx* ctx, irs_state* out, void* stream);

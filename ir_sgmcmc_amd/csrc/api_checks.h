@@ -111,6 +111,26 @@ inline bool count_ok(const char* who, const char* name, int value, int cap) {
     return (value >= 1 && value <= cap) || !fail("%s: %s = %d, 1..%d", who, name, value, cap);
 }
 
+// the bins and the two intensity ranges of the MI data term (mi_kernels.hip) -> bn: the fixed bin width in fp32 as hist_bin takes
+// it, the moving scale (bins - 3) / (m_hi - m_lo) in double
+inline bool mi_bins_ok(const char* who, int bins, float f_lo, float f_hi, float m_lo, float m_hi, MiBins& bn) {
+    if (bins < IRS_MI_MIN_BINS || bins > IRS_MI_MAX_BINS) return !fail("%s: bins = %d, %d..%d", who, bins, IRS_MI_MIN_BINS, IRS_MI_MAX_BINS);
+    const float lo[2] = {f_lo, m_lo}, hi[2] = {f_hi, m_hi};
+    for (int k = 0; k < 2; ++k) {
+        const char* name = k == 0 ? "fixed" : "moving";
+        if (!isfinite(lo[k]) || !isfinite(hi[k]) || !(hi[k] > lo[k]))
+            return !fail("%s: %s range [%g, %g], finite bounds with hi > lo needed", who, name, (double)lo[k], (double)hi[k]);
+        const float inv = (float)bins / (hi[k] - lo[k]);  // fp32, as the bin rule states it
+        if (!isfinite(inv) || !(inv > 0.0f))
+            return !fail("%s: %s range [%g, %g] is too wide or too narrow for float32 bins", who, name, (double)lo[k], (double)hi[k]);
+    }
+    bn.bins = bins;
+    bn.f_lo = f_lo, bn.f_hi = f_hi, bn.f_inv = (float)bins / (f_hi - f_lo);
+    bn.m_lo = (double)m_lo;
+    bn.m_scale = (double)(bins - 3) / ((double)m_hi - (double)m_lo);
+    return true;
+}
+
 inline SplineTaps make_spline(int cps) {
     // sampled cubic B-spline (utils/transformation.py:79-102); evaluated in double, stored as float like the reference
     SplineTaps t;

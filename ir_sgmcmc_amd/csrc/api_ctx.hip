@@ -30,7 +30,8 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     if (!dims_ok(C, D, H, W) || !chain_count_ok(C)) return fail("irs_create: bad dims / chains (C <= %d)", IRS_MAX_CHAINS);
     if (cfg->no_steps < 1 || cfg->no_steps > 30) return fail("irs_create: no_steps out of range");
     if (cfg->sobolev_s < 0 || cfg->sobolev_s > IRS_MAX_HALF_WIDTH) return fail("irs_create: sobolev_s out of range");
-    if (cfg->data_loss != IRS_DATA_GMM_LCC && cfg->data_loss != IRS_DATA_SSD && cfg->data_loss != IRS_DATA_LNCC)
+    if (cfg->data_loss != IRS_DATA_GMM_LCC && cfg->data_loss != IRS_DATA_SSD && cfg->data_loss != IRS_DATA_LNCC &&
+        cfg->data_loss != IRS_DATA_MI)
         return fail("irs_create: unknown data loss");
     if (cfg->data_loss == IRS_DATA_GMM_LCC) {
         if (!lcc_ok(cfg->lcc_s, D, H, W)) return fail("irs_create: LCC half width must be 1 or 2");
@@ -41,6 +42,11 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
         if (D < 2 * cfg->lcc_s + 1 || H < 2 * cfg->lcc_s + 1 || W < 2 * cfg->lcc_s + 1)
             return fail("irs_create: LNCC radius %d needs every dim >= %d", cfg->lcc_s, 2 * cfg->lcc_s + 1);
         if (cfg->virtual_decimation != 0) return fail("irs_create: the LNCC data term takes no virtual decimation");
+    } else if (cfg->data_loss == IRS_DATA_MI) {
+        // (the bins travel in lcc_s; weight and the two intensity ranges through irs_mi_set)
+        if (cfg->lcc_s < IRS_MI_MIN_BINS || cfg->lcc_s > IRS_MI_MAX_BINS)
+            return fail("irs_create: MI bins = %d, %d..%d", cfg->lcc_s, IRS_MI_MIN_BINS, IRS_MI_MAX_BINS);
+        if (cfg->virtual_decimation != 0) return fail("irs_create: the MI data term takes no virtual decimation");
     } else if (!(cfg->ssd_sigma > 0.0f)) return fail("irs_create: ssd_sigma must be positive");
     if (cfg->reg_loss < IRS_REG_L2 || cfg->reg_loss > IRS_REG_LOGNORMAL_L2) return fail("irs_create: unknown regulariser");
     if (cfg->diff_op != IRS_DIFF_GRADIENT && cfg->diff_op != IRS_DIFF_HESSIAN)
@@ -64,6 +70,7 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     c->sparse_plan = 1;        // (irs_sparse_plan_set)
     c->lncc_weight = 1.0f;     // (irs_lncc_set)
     c->lncc_eps = 1e-5f;
+    c->mi_weight = 1.0f;       // (irs_mi_set)
     c->cfg = *cfg;
     c->C = C;
     c->vol = make_vol(D, H, W);
@@ -83,8 +90,8 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
 
     DevCfg& d = c->dcfg;
     d.K = cfg->data_loss == IRS_DATA_GMM_LCC ? cfg->gmm_components : 1;
-    // (the statistics and scalar stages of an LNCC context only count the mask: to them it is an SSD context with 1 / sigma = 0)
-    d.mode = cfg->data_loss == IRS_DATA_LNCC ? IRS_DATA_SSD : cfg->data_loss;
+    // (the statistics and scalar stages of an LNCC or MI context only count the mask: to them it is an SSD context with 1 / sigma = 0)
+    d.mode = cfg->data_loss == IRS_DATA_LNCC || cfg->data_loss == IRS_DATA_MI ? IRS_DATA_SSD : cfg->data_loss;
     d.vd = cfg->virtual_decimation;
     d.C = C;
     d.gmm_lr_log_std = cfg->gmm_lr_log_std;
@@ -124,7 +131,8 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     // one round instead of two launches of 1024 with 8 each
     c->nll_seg_C = (C > 1 && !sl && cfg->data_loss == IRS_DATA_GMM_LCC && c->kn.data_batch != 0) ? C : 1;
     const bool lncc = cfg->data_loss == IRS_DATA_LNCC;
-    c->nll_blocks = lncc ? lncc_geometry(D, H, W, cfg->lcc_s).blocks : data_bwd_blocks(cfg->data_loss, c->vol, c->nll_seg_C);
+    const bool mi = cfg->data_loss == IRS_DATA_MI;  // (its finish kernel writes the data term of a chain: one "partial" per chain)
+    c->nll_blocks = lncc ? lncc_geometry(D, H, W, cfg->lcc_s).blocks : mi ? 1 : data_bwd_blocks(cfg->data_loss, c->vol, c->nll_seg_C);
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
     const size_t o_steps = take(fieldI * cfg->no_steps);
@@ -139,6 +147,10 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     const size_t o_warped = take(imageI), o_z = take(imageI), o_sig = take(imageI), o_fhat = take(imageI), o_gM = take(imageI);
     const size_t o_dense = take(c->ffd ? fieldI : 0);
     const size_t o_lncc = take(lncc ? 3 * imageI : 0);  // the coefficient maps p, q, t of the LNCC data term
+    const size_t mi_cells = mi ? (size_t)C * cfg->lcc_s * cfg->lcc_s : 0;  // the MI data term: histograms, tables, statistics, counts
+    const size_t o_mi_hist = take(mi_cells * sizeof(unsigned long long)), o_mi_table = take(mi_cells * sizeof(float));
+    const size_t o_mi_stats = take(mi ? sizeof(double) * C * IRS_MI_STATS : 0);
+    const size_t o_mi_ipart = take(mi ? sizeof(long long) * IRS_MI_MAX_BLOCKS * 3 : 0);
     const size_t o_stat = take(sizeof(double) * kMaxPartialBlocks * kStatVals);
     const size_t o_energy = take(sizeof(double) * kMaxPartialBlocks * IRS_MAX_CHAINS);
     const size_t o_nll = take(sizeof(double) * (size_t)c->nll_blocks * C);
@@ -177,6 +189,10 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     c->gM = (float*)(c->slab + o_gM);
     c->dense = c->ffd ? (float*)(c->slab + o_dense) : nullptr;
     c->lncc_coef = lncc ? (float*)(c->slab + o_lncc) : nullptr;
+    c->mi_hist = mi ? (unsigned long long*)(c->slab + o_mi_hist) : nullptr;
+    c->mi_table = mi ? (float*)(c->slab + o_mi_table) : nullptr;
+    c->mi_stats = mi ? (double*)(c->slab + o_mi_stats) : nullptr;
+    c->mi_ipart = mi ? (long long*)(c->slab + o_mi_ipart) : nullptr;
     c->stat_partials = (double*)(c->slab + o_stat);
     c->energy_partials = (double*)(c->slab + o_energy);
     c->nll_partials = (double*)(c->slab + o_nll);
@@ -232,6 +248,8 @@ int irs::check_io(const irs_ctx* c, const irs_io* io, const char* who) {
     if (!broadcast_ok(io->fixed_chains, c->C) || !broadcast_ok(io->moving_chains, c->C) || !broadcast_ok(io->mask_chains, c->C))
         return fail("%s: *_chains must be 1 or no_chains", who);
     if (c->cfg.data_loss == IRS_DATA_GMM_LCC && !c->fixed_set) return fail("%s: call irs_set_fixed first", who);
+    if (c->cfg.data_loss == IRS_DATA_MI && !c->mi_set)
+        return fail("%s: the MI data term needs irs_mi_set(ctx, weight, f_lo, f_hi, m_lo, m_hi) first: the library does not guess intensity ranges", who);
     return 0;
 }
 
@@ -400,7 +418,12 @@ static int forward_pass(irs_ctx* c, const irs_io* io, const float* v, bool with_
         launch_lncc_fwd(io->fixed_im, io->fixed_chains == 1 ? 0 : c->vol.V, warped, nullptr, 0, io->mask, io->mask_chains == 1 ? 0 : c->vol.V,
                         cfg.lcc_s, c->lncc_eps, (double)c->lncc_weight, z, c->lncc_coef, c->nll_partials, C,
                         lncc_geometry(c->vol.D, c->vol.H, c->vol.W, cfg.lcc_s), st);
-    else
+    else if (cfg.data_loss == IRS_DATA_MI) {  // histogram -> table T and the data term of every chain (nll_blocks = 1)
+        // (z is only written behind the statistics stage, by the gradient kernel: what that stage multiplies by 0 must be finite)
+        if (io->residuals) HIP_TRY(hipMemsetAsync(z, 0, (size_t)C * c->vol.V * sizeof(float), st));
+        HIP_TRY(launch_mi_fwd(io->fixed_im, io->fixed_chains == 1 ? 0 : c->vol.V, warped, io->mask, io->mask_chains == 1 ? 0 : c->vol.V, c->vol.V,
+                              C, c->mi_bins, c->mi_hist, c->mi_table, c->mi_stats, c->mi_ipart, (double)c->mi_weight, c->nll_partials, 1, st));
+    } else
         launch_residual_ssd(io->fixed_im, io->fixed_chains == 1 ? 0 : c->vol.V, warped, z, C, c->vol, st);
     LAUNCH_CHECK();
     return 0;
@@ -485,7 +508,10 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
     // to 8 planes in less than one resident set: lists could only match them, and the plan's launches would be a net cost there, as
     // for the adjoint below.
     const bool lcc = cfg.data_loss == IRS_DATA_GMM_LCC;
-    const bool lncc = cfg.data_loss == IRS_DATA_LNCC;  // its window reads beyond the mask: no sparse data / forward stage
+    // LNCC: its window reads beyond the mask; MI: its histogram wants every masked voxel of the warped image -- no sparse data /
+    // forward stage for either
+    const bool mi = cfg.data_loss == IRS_DATA_MI;
+    const bool lncc = cfg.data_loss == IRS_DATA_LNCC || mi;
     const int forced_piece = c->sparse_data > 1 ? c->sparse_data : 0;  // (tests: short pieces on small volumes)
     int data_on = 0;
     c->dplan.forced_len = forced_piece;
@@ -581,6 +607,9 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
     if (data_on == 3)  // (one chain, or all chains against their snapshots: scalar stage op bit 3 above)
         launch_lcc_data_bwd_plan(c->fhat, c->fhat_chains == 1 ? 0 : vol.V, z, c->sigM, io->mask, io->mask_chains == 1 ? 0 : vol.V, c->state, c->gM,
                                  cfg.lcc_s, C, vol, c->dplan, st);
+    else if (mi)  // every chain in one launch: the tables of the forward pass -> g_warped (and mask * (ln B - pmi) for the caller)
+        launch_mi_bwd(io->fixed_im, io->fixed_chains == 1 ? 0 : vol.V, warped, io->mask, io->mask_chains == 1 ? 0 : vol.V, c->mi_table, vol.V, C,
+                      c->mi_bins, c->mi_weight, nullptr, true, c->gM, io->residuals, st);
     else if (lncc)  // every chain in one launch: the coefficient maps of the forward pass -> g_warped
         launch_lncc_bwd(io->fixed_im, io->fixed_chains == 1 ? 0 : vol.V, warped, c->lncc_coef, cfg.lcc_s, c->lncc_weight, c->gM, C,
                         lncc_geometry(vol.D, vol.H, vol.W, cfg.lcc_s), st);
@@ -779,6 +808,19 @@ int irs_lncc_set(irs_ctx* c, float weight, float eps) {
     if (c->n_enqueued > 0 || c->have_last_io) return fail("irs_lncc_set: weight and eps may be set only before the first transition");
     c->lncc_weight = weight;
     c->lncc_eps = eps;
+    return 0;
+}
+
+int irs_mi_set(irs_ctx* c, float weight, float f_lo, float f_hi, float m_lo, float m_hi) {
+    if (!c) return fail("irs_mi_set: null argument");
+    if (c->cfg.data_loss != IRS_DATA_MI) return fail("irs_mi_set: the context's data loss is not IRS_DATA_MI");
+    if (!positive_finite(weight)) return fail("irs_mi_set: weight = %g, a finite value > 0 needed", (double)weight);
+    if (c->n_enqueued > 0 || c->have_last_io) return fail("irs_mi_set: weight and ranges may be set only before the first transition");
+    MiBins bn;
+    if (!mi_bins_ok("irs_mi_set", c->cfg.lcc_s, f_lo, f_hi, m_lo, m_hi, bn)) return 1;
+    c->mi_bins = bn;
+    c->mi_weight = weight;
+    c->mi_set = true;
     return 0;
 }
 

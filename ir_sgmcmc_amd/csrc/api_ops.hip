@@ -350,6 +350,47 @@ int irs_lncc_bwd(const float* fixed, int Cf, const float* moving, const float* c
     return 0;
 }
 
+// the mutual-information data term (mi_kernels.hip)
+static bool mi_chains_ok(const char* who, int Cf, const uint8_t* mask, int Cm, int C) {
+    if (!chains_ok(who, C)) return false;
+    if (!broadcast_ok(Cf, C)) return !fail("%s: fixed image of %d chains, 1 or %d needed", who, Cf, C);
+    return !mask || broadcast_ok(Cm, C) || !fail("%s: mask of %d chains, 1 or %d needed", who, Cm, C);
+}
+
+int irs_mi_fwd(const float* fixed, int Cf, const float* moving, const uint8_t* mask, int Cm, int bins, float f_lo, float f_hi,
+               float m_lo, float m_hi, uint64_t* hist, float* table, double* stats, void* scratch, int C, int D, int H, int W,
+               void* stream) {
+    if (!fixed || !moving || !table || !stats || !scratch || !dims_ok(C, D, H, W)) return fail("irs_mi_fwd: bad arguments");
+    if (!mi_chains_ok("irs_mi_fwd", Cf, mask, Cm, C)) return 1;
+    MiBins bn;
+    if (!mi_bins_ok("irs_mi_fwd", bins, f_lo, f_hi, m_lo, m_hi, bn)) return 1;
+    if ((uintptr_t)scratch & 15) return fail("irs_mi_fwd: the scratch must be 16-byte aligned");
+    const int64_t V = (int64_t)D * H * W;
+    const size_t hist_bytes = (size_t)C * bins * bins * sizeof(uint64_t);  // (a multiple of 16)
+    unsigned long long* h = hist ? (unsigned long long*)hist : (unsigned long long*)scratch;
+    long long* ipart = (long long*)((char*)scratch + (hist ? 0 : hist_bytes));
+    HIP_TRY(launch_mi_fwd(fixed, Cf == 1 ? 0 : V, moving, mask, mask && Cm != 1 ? V : 0, V, C, bn, h, table, stats, ipart, 1.0, nullptr, 0,
+                          (hipStream_t)stream));
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_mi_bwd(const float* fixed, int Cf, const float* moving, const uint8_t* mask, int Cm, const float* table, int bins, float f_lo,
+               float f_hi, float m_lo, float m_hi, const float* scale, float* g_moving, float* pmi, int C, int D, int H, int W,
+               void* stream) {
+    if (!fixed || !moving || !table || !g_moving || g_moving == fixed || g_moving == moving || g_moving == table || g_moving == pmi ||
+        (pmi && (pmi == fixed || pmi == moving || pmi == table)) || !dims_ok(C, D, H, W))
+        return fail("irs_mi_bwd: bad arguments");
+    if (!mi_chains_ok("irs_mi_bwd", Cf, mask, Cm, C)) return 1;
+    MiBins bn;
+    if (!mi_bins_ok("irs_mi_bwd", bins, f_lo, f_hi, m_lo, m_hi, bn)) return 1;
+    const int64_t V = (int64_t)D * H * W;
+    launch_mi_bwd(fixed, Cf == 1 ? 0 : V, moving, mask, mask && Cm != 1 ? V : 0, table, V, C, bn, 1.0f, scale, false, g_moving, pmi,
+                  (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 int irs_reg_energy(const float* v, double* y_out, double* partials, int C, int D, int H, int W, void* stream) {
     if (!v || !y_out || !partials || !dims_ok(C, D, H, W) || !chain_count_ok(C)) return fail("irs_reg_energy: bad arguments");
     const Vol vol = make_vol(D, H, W);

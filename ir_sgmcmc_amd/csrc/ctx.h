@@ -58,6 +58,15 @@ struct irs_ctx {
     double *stat_sum, *energy_sum, *nll_sum;  // reduced partial sums (staged / slab path)
     float* lncc_coef = nullptr;  // IRS_DATA_LNCC: (C,3,V) coefficient maps p, q, t, forward kernel -> adjoint kernel (lncc_kernels.hip)
     float lncc_weight = 1.0f, lncc_eps = 1e-5f;  // irs_lncc_set
+    // IRS_DATA_MI (mi_kernels.hip): the chains' joint histograms (C,B,B) uint64, tables T (C,B,B), statistics (C, IRS_MI_STATS) and
+    // the rows of per-block counts; weight and ranges from irs_mi_set, without which no transition runs
+    unsigned long long* mi_hist = nullptr;
+    float* mi_table = nullptr;
+    double* mi_stats = nullptr;
+    long long* mi_ipart = nullptr;
+    irs::MiBins mi_bins = {};
+    float mi_weight = 1.0f;
+    bool mi_set = false;
     unsigned* dmax;  // [no_steps + 1][C][4] max |d_k| in voxels per axis (float bits), by-product of the forward steps
     irs::AdjointPlan plan;  // sparse adjoint plan (adjoint_plan.hip); no buffers on a slab context
     bool sparse_adjoint = true;  // irs_sparse_adjoint_set: the adjoint steps walk the plan's lists (false: full columns)

@@ -500,6 +500,28 @@ void launch_lncc_fwd(const float* fixed, int64_t fixed_stride, const float* movi
 void launch_lncc_bwd(const float* fixed, int64_t fixed_stride, const float* moving, const float* coef, int radius, float scale,
                      float* g_moving, int C, const LnccGeom& g, hipStream_t st);
 
+// ---- mi_kernels.hip: the mutual-information data term (Parzen joint histogram in Q30 fixed point, the table T, the gradient)
+struct MiBins {
+    int bins;
+    float f_lo, f_hi, f_inv;  // range of the fixed image and bins / (hi - lo), formed in fp32 (the rule of hist_bin)
+    double m_lo, m_scale;     // of the moving image: m_lo and (bins - 3) / (m_hi - m_lo), formed in double
+};
+// blocks per chain of the accumulate and the gradient launch: min(ceil(units / 256), IRS_MI_MAX_BLOCKS / C), units of four voxels in
+// the vector form
+int mi_blocks(int64_t V, int C, bool vec);
+// fixed (1 or C,V) with fixed_stride 0 or V; moving (C,V); mask (1 or C,V) uint8 with mask_stride 0 or V, or nullptr; hist (C,B,B)
+// uint64 (zeroed on the stream here, left holding the histogram); table (C,B,B) float32; stats (C, IRS_MI_STATS); ipart:
+// IRS_MI_MAX_BLOCKS rows of 3 int64; data_out (or nullptr): data_out[c * data_stride] = weight * n_c * (ln B - MI_c).  -> the status
+// of the memset (nothing is launched behind one that failed)
+hipError_t launch_mi_fwd(const float* fixed, int64_t fixed_stride, const float* moving, const uint8_t* mask, int64_t mask_stride, int64_t V,
+                   int C, const MiBins& bn, unsigned long long* hist, float* table, double* stats, long long* ipart, double weight,
+                   double* data_out, int64_t data_stride, hipStream_t st);
+// g (C,V) = -weight * scale[c] * mask * inside * m_scale * sum_j w'_j T[a][k0 - 1 + j]; scale: C floats on the device or nullptr
+// (1); pmi (C,V) or nullptr: sum_j w_j T[a][k0 - 1 + j] at the voxels that take part (residual_form: ln B minus that), 0 elsewhere
+void launch_mi_bwd(const float* fixed, int64_t fixed_stride, const float* moving, const uint8_t* mask, int64_t mask_stride,
+                   const float* table, int64_t V, int C, const MiBins& bn, float weight, const float* scale, bool residual_form,
+                   float* g, float* pmi, hipStream_t st);
+
 // ---- residual_kernels.hip: the residuals against the mixture that models them -- histogram, moments and the per-voxel NLL
 struct ResBins {
     int bins;

@@ -8,9 +8,11 @@ from .synthetic import init_var_params, synthetic_pair
 class SyntheticDataLoader:
     """deterministic Gaussian-blob pair; the reference ships no image data"""
 
-    def __init__(self, dims, sigma_v_init=0.5, u_v_init=0.1, cps=None, save_dirs=None, seed=0, misalign=None, **_unused):
+    def __init__(self, dims, sigma_v_init=0.5, u_v_init=0.1, cps=None, save_dirs=None, seed=0, misalign=None, moving_contrast=None,
+                 **_unused):
         self.dims = tuple(dims)
         self.misalign = misalign  # synthetic_pair: the moving triple rotated and shifted on the host (None: as generated)
+        self.moving_contrast = moving_contrast  # synthetic_pair: None | "invert" | "fold", the moving image in another contrast
         self.cps = tuple(cps) if cps else None
         self.save_dirs = save_dirs
         self.sigma_v_init, self.u_v_init, self.seed = sigma_v_init, u_v_init, seed
@@ -27,7 +29,7 @@ class SyntheticDataLoader:
         return 1
 
     def __iter__(self):
-        fixed, moving = synthetic_pair(self.dims, seed=self.seed, misalign=self.misalign)
+        fixed, moving = synthetic_pair(self.dims, seed=self.seed, misalign=self.misalign, moving_contrast=self.moving_contrast)
         fixed = {k: v.unsqueeze(0) for k, v in fixed.items()}
         moving = {k: v.unsqueeze(0) for k, v in moving.items()}
         vp = {k: v.unsqueeze(0) for k, v in init_var_params(self.dims_v, self.sigma_v_init, self.u_v_init).items()}

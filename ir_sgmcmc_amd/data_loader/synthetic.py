@@ -50,14 +50,34 @@ def misalign_triple(triple, rotation_deg, shift):
             'seg': sample(triple['seg'], 'nearest').to(torch.int16).contiguous()}
 
 
-def synthetic_pair(dims, seed=0, noise=0.02, misalign=None):
+MOVING_CONTRASTS = ('invert', 'fold')
+
+
+def moving_contrast_map(im, kind):
+    """another contrast for the moving image, the anatomy unchanged: "invert" m <- max + min - m (a monotone decreasing map: T1 / T2
+    like), "fold" m <- 4 s (1 - s) of the image rescaled to s in [0, 1] (non-monotone: two intensities of the fixed image share one
+    of the moving image)"""
+    if kind not in MOVING_CONTRASTS:
+        raise ValueError(f'moving_contrast {kind!r}: null or one of {list(MOVING_CONTRASTS)}')
+    lo, hi = im.min(), im.max()
+    if kind == 'invert':
+        return hi + lo - im
+    s = (im - lo) / (hi - lo)
+    return 4.0 * s * (1.0 - s)
+
+
+def synthetic_pair(dims, seed=0, noise=0.02, misalign=None, moving_contrast=None):
     """Two Gaussian blobs + white noise; the moving image has both blobs shifted.  Returns (fixed, moving).
     misalign: None (the pair as it always was), or {"rotation_deg": [a0, a1, a2], "shift": [s0, s1, s2]}: the moving triple
-    is then rotated and shifted on the host (misalign_triple)."""
+    is then rotated and shifted on the host (misalign_triple).
+    moving_contrast: None (the pair as it always was), "invert" or "fold" (moving_contrast_map): the moving image in another
+    contrast, which only a mutual-information data term registers."""
     dims = tuple(int(d) for d in dims)
     g = torch.Generator().manual_seed(seed)
     im_f = _blobs(dims, (0.0, 0.0, 0.0), (0.0, 0.0, 0.0)) + noise * torch.randn(dims, generator=g)
     im_m = _blobs(dims, (0.08, -0.04, 0.05), (0.06, 0.05, 0.02)) + noise * torch.randn(dims, generator=g)
+    if moving_contrast is not None:
+        im_m = moving_contrast_map(im_m, moving_contrast)
     z, y, x = _coords(dims)
     r2 = z ** 2 + y ** 2 + x ** 2
     mask = (r2 < 0.9).expand(dims)

@@ -28,12 +28,16 @@ class EngineConfig:
     lr: float = 0.4                                       # optimizer_SG_MCMC.args.lr
     uniform_noise: float = 0.1                            # trainer.uniform_noise.magnitude (0 = disabled)
     virtual_decimation: bool = True
-    data_loss: str = 'GMM'                                # 'GMM' (reference) | 'SSD' (builder-defined) | 'LNCC' (lcc_s = window radius)
+    data_loss: str = 'GMM'                                # 'GMM' (reference) | 'SSD' (builder-defined) | 'LNCC' (lcc_s = window radius) | 'MI'
     gmm_components: int = 4
     lcc_s: int = 1
     ssd_sigma: float = 0.1
     lncc_weight: float = 1.0                              # 'LNCC': data term = lncc_weight * sum mask * (1 - cc), cc with + lncc_eps
     lncc_eps: float = 1e-5
+    mi_bins: int = 32                                     # 'MI': data term = mi_weight * n * (ln mi_bins - MI); the bins travel in lcc_s
+    mi_weight: float = 1.0
+    mi_fixed_range: Optional[Tuple[float, float]] = None  # (lo, hi) of the two images; while either is None the engine waits for
+    mi_moving_range: Optional[Tuple[float, float]] = None  # mi_set, and refuses a transition before it: no range is guessed
     gmm_lr_log_std: float = 0.2
     gmm_lr_logits: float = 0.2
     gmm_lr_decay: float = 0.001
@@ -66,7 +70,7 @@ def lognormal_init(w_reg, dof, nu=1.0):
     return loc, math.log(4.0) + math.log(loc)
 
 
-DATA_LOSSES = {'GMM': L.IRS_DATA_GMM_LCC, 'SSD': L.IRS_DATA_SSD, 'LNCC': L.IRS_DATA_LNCC}
+DATA_LOSSES = {'GMM': L.IRS_DATA_GMM_LCC, 'SSD': L.IRS_DATA_SSD, 'LNCC': L.IRS_DATA_LNCC, 'MI': L.IRS_DATA_MI}
 DIFF_OPS = {'GradientOperator': L.IRS_DIFF_GRADIENT, 'HessianOperator': L.IRS_DIFF_HESSIAN}
 
 
@@ -95,7 +99,7 @@ def irs_config(cfg: EngineConfig):
     if cfg.data_loss not in DATA_LOSSES:
         raise ValueError(f'data_loss {cfg.data_loss!r} is not wired into the fused transition: one of {sorted(DATA_LOSSES)}')
     c.data_loss = DATA_LOSSES[cfg.data_loss]
-    c.lcc_s, c.gmm_components, c.ssd_sigma = cfg.lcc_s, cfg.gmm_components, cfg.ssd_sigma
+    c.lcc_s, c.gmm_components, c.ssd_sigma = cfg.mi_bins if cfg.data_loss == 'MI' else cfg.lcc_s, cfg.gmm_components, cfg.ssd_sigma
     c.gmm_lr_log_std, c.gmm_lr_logits, c.gmm_lr_decay = cfg.gmm_lr_log_std, cfg.gmm_lr_logits, cfg.gmm_lr_decay
     c.adam_beta1, c.adam_beta2, c.adam_eps = 0.9, 0.999, 1e-8
     c.scale_prior_loc, c.scale_prior_scale = cfg.scale_prior
@@ -142,6 +146,8 @@ class TransitionEngine:
         self._keep = {}
         if cfg.data_loss == 'LNCC':  # (irs_config has no room for the two: they travel in a call of their own)
             self.lncc_set(cfg.lncc_weight, cfg.lncc_eps)
+        if cfg.data_loss == 'MI' and cfg.mi_fixed_range is not None and cfg.mi_moving_range is not None:
+            self.mi_set(cfg.mi_weight, cfg.mi_fixed_range, cfg.mi_moving_range)
         if cfg.reg_loss == 'RegLoss_LogNormal':
             st = self.state()
             st.reg_param[0], st.reg_param[1] = lognormal_init(cfg.w_reg, cfg.dof)
@@ -159,6 +165,12 @@ class TransitionEngine:
     def lncc_set(self, weight, eps):
         """irs_lncc_set: weight and eps of the LNCC data term; only before the first transition"""
         L.check(self.lib.irs_lncc_set(self._ctx, float(weight), float(eps)))
+
+    def mi_set(self, weight, fixed_range, moving_range):
+        """irs_mi_set: weight and the two intensity ranges (lo, hi) of the MI data term; required, and only before the first
+        transition"""
+        (f_lo, f_hi), (m_lo, m_hi) = fixed_range, moving_range
+        L.check(self.lib.irs_mi_set(self._ctx, float(weight), float(f_lo), float(f_hi), float(m_lo), float(m_hi)))
 
     def __del__(self):
         ctx, self._ctx = getattr(self, '_ctx', None), None

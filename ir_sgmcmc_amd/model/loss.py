@@ -16,6 +16,7 @@ from torch.nn.functional import log_softmax
 from . import distributions as model_distr
 from .. import bending as _bending
 from .. import lncc as _lncc
+from .. import mi as _mi
 from .. import ops as _ops
 from ..utils.diff_op import DifferentialOperator, GradientOperator, HessianOperator
 
@@ -153,6 +154,57 @@ class LNCC(DataLoss):
 
     def forward(self, z):
         return self.weight * z.sum()
+
+
+class _MILoss(torch.autograd.Function):
+    """n * (ln B - MI) per chain (C,) float64; backward runs the gradient kernel with the incoming gradient as the per-chain scale"""
+
+    @staticmethod
+    def forward(ctx, im_fixed, im_moving, mask, bins, fixed_range, moving_range):
+        out = _mi.mi_forward(im_fixed, im_moving, mask, bins, fixed_range, moving_range)
+        ctx.bins, ctx.ranges, ctx.mask = bins, out['ranges'], mask
+        ctx.save_for_backward(im_fixed, im_moving, out['table'])
+        return out['stats'][:, 6].clone()
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        im_fixed, im_moving, table = ctx.saved_tensors
+        g = _mi.mi_backward(im_fixed, im_moving, table, ctx.mask, ctx.bins, ctx.ranges[:2], ctx.ranges[2:],
+                            scale=g_loss.to(torch.float32).contiguous())
+        return None, g, None, None, None, None
+
+
+class MI(DataLoss):
+    """mutual information of the two images, a Mattes-style estimator (zero-order window on the fixed image, cubic B-spline window
+    on the moving one, `bins` bins each): loss = weight * sum over the chains of n * (ln bins - MI) >= 0, n the voxels under the
+    mask with both intensities finite.  Needs no common contrast of the two images.  fixed_range / moving_range: (lo, hi), or None
+    for the min / max of the finite values (the fixed image under its mask, the moving image over the whole volume) at every call.
+    No counterpart in the reference.  MI is NOT a per-voxel map followed by a masked sum -- the table ln(p_ab / (p_a p_b)) couples
+    all voxels of a chain -- so `forward` takes the images and the mask, the base-class signature of the reference's DataLoss, and
+    `map` / `reduce` raise."""
+
+    def __init__(self, bins=32, weight=1.0, fixed_range=None, moving_range=None):
+        super().__init__()
+        self.bins, self.weight = int(bins), float(weight)
+        self.fixed_range = None if fixed_range is None else tuple(float(x) for x in fixed_range)
+        self.moving_range = None if moving_range is None else tuple(float(x) for x in moving_range)
+        self.no_components = 1
+
+    def forward(self, im_fixed, im_moving, mask=None):
+        if im_fixed.dim() == 5 and im_fixed.shape[0] > 1 and im_fixed.stride(0) == 0:
+            im_fixed = im_fixed[:1]
+        if mask is not None and mask.dim() == 5 and mask.shape[0] > 1 and mask.stride(0) == 0:
+            mask = mask[:1]
+        terms = _MILoss.apply(im_fixed.contiguous(), im_moving.contiguous(), None if mask is None else mask.contiguous(), self.bins,
+                              self.fixed_range, self.moving_range)
+        return self.weight * terms.sum()
+
+    def map(self, im_fixed, im_moving):
+        raise NotImplementedError('MI is no per-voxel map followed by a masked sum: its table ln(p_ab / (p_a p_b)) is formed from the '
+                                  'joint histogram of all masked voxels.  Call the loss itself: MI()(im_fixed, im_moving, mask)')
+
+    def reduce(self, z):
+        raise NotImplementedError('MI has no residual map to reduce (see MI.map): call the loss itself with the images and the mask')
 
 
 class _Energy(torch.autograd.Function):

@@ -214,6 +214,9 @@ class SlabEngine(TransitionEngine):
         if cfg.data_loss == 'LNCC':
             raise L.IrsError('irs_slab_create: the LNCC data term is not supported on z-slabs (its window and its adjoint need a halo of '
                              '2 radius planes): data_loss must be GMM or SSD')
+        if cfg.data_loss == 'MI':
+            raise L.IrsError('irs_slab_create: the MI data term is not supported on z-slabs (the joint histogram of a chain would need '
+                             'an all-reduce between its accumulate and finish kernels): data_loss must be GMM or SSD')
         self._scfg = L.IrsSlabConfig(ghost_max, margin)
         super().__init__(cfg, device)
         lay = L.IrsSlabLayout()

@@ -42,7 +42,7 @@ from ..logger import (save_displacement_covariance, save_displacement_mean_and_s
                       save_posterior_comparison, save_precond_sigma,
                       save_residual_histogram, save_residual_nll, save_rhat, save_sample, save_structure_report, save_surface_posterior,
                       save_truth_calibration)
-from .. import affine, bspline, image_posterior, multires, preconditioner, residual_check, structure_report
+from .. import affine, bspline, image_posterior, mi, multires, preconditioner, residual_check, structure_report
 from .. import truth as truth_ops
 from .. import masks as mask_ops  # (`masks` names the pair of masks in several methods below)
 from ..multires import coarse_start_options
@@ -59,6 +59,18 @@ from .vi import VIMixin
 # _finish_* method and what that takes first ('fixed': the fixed image's dict, 'moving_mask': the mask of the displacement std
 # map, 'masks': {'fixed': ..., 'moving': ...})
 Recorder = namedtuple('Recorder', 'key state period option noun records finish takes')
+
+
+def mi_refusals(virtual_decimation, residual_options, vi):
+    """what a run with the MI data loss cannot be combined with, each refused with its reason"""
+    if virtual_decimation:
+        raise ValueError('the MI data loss takes no virtual decimation (it has no residual whose correlation could be estimated): set '
+                         '"virtual_decimation" to false')
+    if residual_options is not None:
+        raise ValueError('trainer.residual_check compares the residuals with the Gaussian mixture: it needs the GMM data loss, not MI')
+    if vi:
+        raise ValueError('the VI stage composes data_loss.map and data_loss.reduce, and MI is no per-voxel map followed by a masked sum: '
+                         'set trainer."VI" to false with the MI data loss')
 
 
 class LazyScalar:
@@ -341,7 +353,7 @@ class Trainer(VIMixin, BaseTrainer):
                   no_steps=getattr(self.transformation_module, 'no_steps', 12), sobolev_s=self.Sobolev_s,
                   sobolev_lambda=self.Sobolev_lambda, lr=float(cfg['optimizer_SG_MCMC']['args']['lr']),
                   uniform_noise=float(self.alpha), virtual_decimation=bool(self.virutal_decimation),
-                  data_loss=kind if kind in ('GMM', 'LNCC') else 'SSD', seed=int(cfg['trainer'].get('seed', 0)))
+                  data_loss=kind if kind in ('GMM', 'LNCC', 'MI') else 'SSD', seed=int(cfg['trainer'].get('seed', 0)))
         if cfg['optimizer_SG_MCMC']['type'] != 'SGD':
             raise NotImplementedError('the SG-MCMC field update is plain SGD (reference configs), got ' + cfg['optimizer_SG_MCMC']['type'])
         if kind == 'GMM':
@@ -359,6 +371,13 @@ class Trainer(VIMixin, BaseTrainer):
                 raise ValueError('trainer.residual_check compares the residuals with the Gaussian mixture: it needs the GMM data loss, '
                                  'not LNCC')
             ec.update(lcc_s=data_loss.radius, lncc_weight=data_loss.weight, lncc_eps=data_loss.eps)
+        elif kind == 'MI':
+            mi_refusals(self.virutal_decimation, self.residual_options, self.VI)
+            # (the ranges: the loss object's, else what _engine_init found on the pair it hands the chains; until then None, and an
+            # engine built from this config waits for mi_set)
+            found = getattr(self, '_mi_ranges', None) or (None, None)
+            ec.update(mi_bins=data_loss.bins, mi_weight=data_loss.weight, mi_fixed_range=data_loss.fixed_range or found[0],
+                      mi_moving_range=data_loss.moving_range or found[1])
         else:
             ec.update(ssd_sigma=data_loss.sigma)
         rname = type(reg_loss).__name__
@@ -385,7 +404,15 @@ class Trainer(VIMixin, BaseTrainer):
         return EngineConfig(**ec)
 
     def _engine_init(self, fixed, moving):
+        if type(self.losses['data']['loss']).__name__ == 'MI':
+            # once, from the pair the chains get (after auto_mask, affine_init and truth): the fixed image under its mask, the moving
+            # image over the whole volume
+            self._mi_ranges = mi.mi_ranges(fixed['im'], moving['im'], fixed['mask'])
         self.engine = TransitionEngine(self._engine_config(), self.device)
+        if self.engine.cfg.data_loss == 'MI':
+            ec = self.engine.cfg
+            self.logger.info(f'MI data term: {ec.mi_bins} bins, weight {ec.mi_weight:g}, fixed range [{ec.mi_fixed_range[0]:.6g}, '
+                             f'{ec.mi_fixed_range[1]:.6g}], moving range [{ec.mi_moving_range[0]:.6g}, {ec.mi_moving_range[1]:.6g}]')
         self._fixed, self._moving = self.engine.prepare(fixed, moving)
         self._mask_idx = None
         self._set_hyper_parameters(self.engine)
