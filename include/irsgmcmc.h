@@ -57,6 +57,19 @@ int irs_perturb_smooth(const float* v, const float* sigma, const float* eps, flo
                        int C, int D, int H, int W, float* tmp, float* out, uint64_t seed, uint64_t iteration,
                        void* stream);
 
+/* One SGHMC step (Chen, Fox & Guestrin 2014, eq. 15 with beta_hat = 0) on (v, momentum) in place, outside a transition.  Per
+ * element, float32, every operation rounded once and nothing contracted into an FMA:
+ *   t  = fsub(fmul(oma, m), fmul(lr, grad))                    oma = (float)(1 - (double)friction)
+ *   m' = T > 0 ? fadd(t, fmul(fmul(amp, sigma), n)) : t        amp = (float)sqrt(2 friction lr T), in double
+ *   v' = fadd(v, m')
+ * v, momentum, grad: (C,3,D,H,W); grad is what irs_io.grad_v holds (sigma^2 already applied).  sigma: NULL (= 1) or (C,3,D,H,W).
+ * n: eps where it is given, else the in-kernel Philox4x32-10 draw of irs_perturb_smooth -- one call per voxel pair (z even, z + 1),
+ * the same index and the same assignment of the six normals -- with the stream word 0x484D in place of 0x5347: never a draw the
+ * forward perturbation has used.  friction in (0, 1] (1: Langevin dynamics whose noise stays in v), temperature >= 0 (0: no noise
+ * is drawn, eps is not read).  Extents >= 1, C in 1..IRS_MAX_CHAINS. */
+int irs_sghmc_update(float* v, float* momentum, const float* grad, const float* sigma, const float* eps, int C, int D, int H, int W,
+                     float lr, float friction, float temperature, uint64_t seed, uint64_t iteration, void* stream);
+
 /* SVF_3D.forward (utils/transformation.py:63-76): scaling and squaring.
  * v: (C,3,D,H,W) voxel units.  steps: (no_steps, C,3,D,H,W) workspace receiving d_1..d_no_steps in
  * normalised units (kept for the backward).  transformation / displacement: outputs, either may be NULL. */
@@ -1155,6 +1168,16 @@ int irs_lncc_set(irs_ctx* ctx, float weight, float eps);
  * transition.  Such a context takes no virtual decimation and no z-slab, and its sparse data and sparse forward stages stay off
  * (the sparse adjoint works as ever: the gradient vanishes off the mask). */
 int irs_mi_set(irs_ctx* ctx, float weight, float f_lo, float f_hi, float m_lo, float m_hi);
+/* Switches the context's sampler to SGHMC: the update of a transition becomes the step of irs_sghmc_update on (irs_io.v, momentum)
+ * with lr = irs_config.lr, sigma = irs_io.sigma, the context's seed and Philox counter, and grad = grad_v, which irs_io.grad_v
+ * still receives; the forward pass adds NO noise -- curr_state is the smoothed v itself -- and irs_io.eps, where given, is the
+ * momentum's noise instead.  momentum: the caller's device array (C,3,Dv,Hv,Wv), which must outlive the transitions; a transition
+ * that ends as a no-op writes neither v nor momentum, and its re-run draws the same noise.  Jitter, counter, timings, stream
+ * capture and every other stage are as without the call.  friction in (0, 1], temperature >= 0 and finite; only before the first
+ * transition; not on a z-slab context.  With irs_config.sobolev_s > 0 grad_v is not the gradient of a potential in v (the
+ * smoothing's backward is the identity, as in the reference): the chain is then the momentum counterpart of the reference's
+ * scheme, textbook SGHMC only with sobolev_s = 0. */
+int irs_sghmc_set(irs_ctx* ctx, float friction, float temperature, float* momentum);
 /* blocking copies of the small state / scalars.  (A slab context whose transport has failed -- a peer gone, irs_slab_transition /
  * irs_flush return that error -- still answers these two: the device holds the state after the last good transition.) */
 int irs_get_state(irs_ctx* ctx, irs_state* out, void* stream);

@@ -269,6 +269,8 @@ SIGNATURES = {
     'irs_set_fixed': [_P, _P, _I, _P],
     'irs_lncc_set': [_P, _F, _F],
     'irs_mi_set': [_P, _F, _F, _F, _F, _F],
+    'irs_sghmc_set': [_P, _F, _F, _P],
+    'irs_sghmc_update': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _U64, _U64, _P],
     'irs_get_state': [_P, C.POINTER(IrsState), _P],
     'irs_set_state': [_P, C.POINTER(IrsState), _P],
     'irs_get_scalars': [_P, C.POINTER(IrsScalars), _P],

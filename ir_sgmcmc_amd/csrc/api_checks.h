@@ -20,6 +20,12 @@ inline bool chain_count_ok(int C) { return C >= 1 && C <= IRS_MAX_CHAINS; }
 inline bool broadcast_ok(int Cf, int C) { return Cf == 1 || Cf == C; }  // an array of one chain serves all, or there is one per chain
 inline bool positive_finite(float v) { return v > 0.0f && isfinite(v); }
 
+// the two numbers of the SGHMC sampler (sghmc_device.h): friction in (0, 1], temperature >= 0 and finite
+inline bool sghmc_numbers_ok(const char* who, float friction, float temperature) {
+    if (!(friction > 0.0f && friction <= 1.0f)) return !fail("%s: friction = %g, a value in (0, 1] needed", who, (double)friction);
+    return (temperature >= 0.0f && isfinite(temperature)) || !fail("%s: temperature = %g, a finite value >= 0 needed", who, (double)temperature);
+}
+
 // (fail() returns 1: `!fail(...)` is "refused")
 inline bool chains_ok(const char* who, int C) { return chain_count_ok(C) || !fail("%s: C = %d chains, 1..%d", who, C, IRS_MAX_CHAINS); }
 

@@ -373,6 +373,10 @@ static int forward_pass(irs_ctx* c, const irs_io* io, const float* v, bool with_
     if (with_noise && cfg.sobolev_s > 0 && !c->ffd && c->kn.fuse_noise && !(io->sigma && io->eps)) {
         have_dmax0 = true;
         launch_perturb_sobolev_march(v, io->sigma, io->eps, amp, vs, c->sob, C, c->volv, c->dmax, cfg.no_steps, cfg.seed, 0, it, st);
+    } else if (!with_noise && c->sghmc && v == io->v && cfg.sobolev_s > 0) {
+        // a transition under SGHMC (irs_sghmc_set): the noise enters with the momentum, in the update; the smoothing reads v where it lies
+        have_dmax0 = !c->ffd;
+        launch_sobolev_march(v, vs, c->sob, C * 3, c->volv, have_dmax0 ? c->dmax : nullptr, cfg.no_steps, st);
     } else {
         float* first = cfg.sobolev_s > 0 ? c->tmpA : vs;
         if (with_noise) launch_perturb(v, io->sigma, io->eps, amp, first, C, c->volv, cfg.seed, 0, it, st);
@@ -550,7 +554,7 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
     if (data_on > 0)
         launch_front_plans(io->mask, io->mask_chains, c->dplan, lcc ? cfg.lcc_s : 0, lcc, fwd_on ? &c->fplan : nullptr, c->fwd_width, cfg.no_steps,
                            exp_fwd_plan_resident(), fwd_forced, C, vol, c->sparse_plan, st);
-    if (forward_pass(c, io, io->v, true, cfg.uniform_alpha > 0.0f, vs, warped, z, fuse_warp_bwd ? c->gA : nullptr, C, st, timed, data_on, fwd_on)) return 1;
+    if (forward_pass(c, io, io->v, !c->sghmc, cfg.uniform_alpha > 0.0f, vs, warped, z, fuse_warp_bwd ? c->gA : nullptr, C, st, timed, data_on, fwd_on)) return 1;
     const int64_t field = (int64_t)C * 3 * vol.V;
     const float* d_last = c->steps + (int64_t)(cfg.no_steps - 1) * field;
     if (io->transformation || io->displacement) launch_svf_outputs(d_last, io->transformation, io->displacement, C, vol, lin, st);
@@ -667,19 +671,22 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
     if (timed) HIP_TRY(hipEventRecord(c->ev[4], st));
     float s[3];
     prescale_factors(vol, cfg.no_steps, s);
+    // SGHMC (irs_sghmc_set): the same launches, the step of sghmc_device.h in place of v <- v - lr grad_v
+    const SghmcArgs hm_args = sghmc_args(c->sghmc_m, io->eps, cfg.lr, c->sghmc_friction, c->sghmc_temperature, cfg.seed);
+    const SghmcArgs* hm = c->sghmc ? &hm_args : nullptr;
     if (c->ffd) {
         float* scaled = g0 == c->gA ? c->gB : c->gA;
         launch_scale_channels(g0, scaled, s[0], s[1], s[2], C, vol, st);
         const int G[3] = {volv.D, volv.H, volv.W};
         ffd_adjoint(scaled, c->tmpB, c->tmpA, C, vol, G, c->spl, st);
-        if (bending) launch_sgld_update_bending(io->v, io->sigma, c->tmpB, vs, c->state, cfg.lr, 1.0f, 1.0f, 1.0f, io->grad_v, C, volv, st);
+        if (bending) launch_sgld_update_bending(io->v, io->sigma, c->tmpB, vs, c->state, cfg.lr, 1.0f, 1.0f, 1.0f, io->grad_v, C, volv, st, hm);
         else launch_sgld_update(io->v, io->sigma, c->tmpB, vs, c->state, cfg.lr, 1.0f, 1.0f, 1.0f, io->grad_v, C, volv, st,
-                                energy_in_update ? c->energy_partials : nullptr, energy_in_update);
+                                energy_in_update ? c->energy_partials : nullptr, energy_in_update, hm);
     } else if (bending) {
-        launch_sgld_update_bending(io->v, io->sigma, g0, vs, c->state, cfg.lr, s[0], s[1], s[2], io->grad_v, C, volv, st);
+        launch_sgld_update_bending(io->v, io->sigma, g0, vs, c->state, cfg.lr, s[0], s[1], s[2], io->grad_v, C, volv, st, hm);
     } else {
         launch_sgld_update(io->v, io->sigma, g0, vs, c->state, cfg.lr, s[0], s[1], s[2], io->grad_v, C, volv, st,
-                           energy_in_update ? c->energy_partials : nullptr, energy_in_update);
+                           energy_in_update ? c->energy_partials : nullptr, energy_in_update, hm);
     }
     // bookkeeping (+ the regulariser scalar stage of the L2 family, whose energy the update has just produced: one launch)
     launch_finalize(c->state, data_on == 3 ? c->dplan.nll : c->nll_partials, c->nll_blocks, c->dcfg, true, c->dmax, c->hint,
@@ -808,6 +815,18 @@ int irs_lncc_set(irs_ctx* c, float weight, float eps) {
     if (c->n_enqueued > 0 || c->have_last_io) return fail("irs_lncc_set: weight and eps may be set only before the first transition");
     c->lncc_weight = weight;
     c->lncc_eps = eps;
+    return 0;
+}
+
+int irs_sghmc_set(irs_ctx* c, float friction, float temperature, float* momentum) {
+    if (!c || !momentum) return fail("irs_sghmc_set: null argument");
+    if (c->sl.on) return fail("irs_sghmc_set: a z-slab context keeps the reference's update");
+    if (!sghmc_numbers_ok("irs_sghmc_set", friction, temperature)) return 1;
+    if (c->n_enqueued > 0 || c->have_last_io) return fail("irs_sghmc_set: the sampler may be set only before the first transition");
+    c->sghmc = true;
+    c->sghmc_friction = friction;
+    c->sghmc_temperature = temperature;
+    c->sghmc_m = momentum;
     return 0;
 }
 

@@ -103,6 +103,23 @@ int irs_perturb_smooth(const float* v, const float* sigma, const float* eps, flo
     return 0;
 }
 
+int irs_sghmc_update(float* v, float* momentum, const float* grad, const float* sigma, const float* eps, int C, int D, int H, int W,
+                     float lr, float friction, float temperature, uint64_t seed, uint64_t iteration, void* stream) {
+    if (!v || !momentum || !grad) return fail("irs_sghmc_update: null argument");
+    if (D < 1 || H < 1 || W < 1) return fail("irs_sghmc_update: dims (%d, %d, %d), every one >= 1 needed", D, H, W);
+    if (!chains_ok("irs_sghmc_update", C)) return 1;
+    if (!sghmc_numbers_ok("irs_sghmc_update", friction, temperature)) return 1;
+    if (!isfinite(lr) || lr < 0.0f) return fail("irs_sghmc_update: lr = %g, a finite value >= 0 needed", (double)lr);
+    if ((int64_t)D * H * W >= ((int64_t)1 << 30)) return fail("irs_sghmc_update: the volume must have fewer than 2^30 voxels");
+    // one block row per (chain, plane pair) and per four rows of a plane
+    if ((int64_t)((D + 1) / 2) * C > 65535 || (H + 3) / 4 > 65535)
+        return fail("irs_sghmc_update: dims (%d, %d, %d) x %d chains exceed the launch grid", D, H, W, C);
+    launch_sghmc_update(v, grad, sigma, lr, sghmc_args(momentum, eps, lr, friction, temperature, seed), iteration, C, make_vol(D, H, W),
+                        (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 int irs_svf_exp_fwd(const float* v, float* steps, float* transformation, float* displacement, int no_steps, int C,
                     int D, int H, int W, void* stream) {
     if (!v || !steps || !dims_ok(C, D, H, W) || no_steps < 1 || no_steps > 30) return fail("irs_svf_exp_fwd: bad arguments");

@@ -244,12 +244,16 @@ __global__ __launch_bounds__(kBdBlock) void bending_grad_march_kernel(const floa
 //   grad_v = sigma^2 (g * s_c + 2 coef H^T W H v_s),   v <- v - lr grad_v     (v stays when the transition is frozen)
 // coef from state->coef[chain]: the energy and the scalar stage always run in front of this kernel.
 // ------------------------------------------------------------------------------------------------
-template <bool SIGMA>
-__global__ __launch_bounds__(kBdBlock) void sgld_update_bending_march_kernel(float* __restrict__ v, const float* __restrict__ sigma,
-                                                                             const float* __restrict__ g, const float* __restrict__ v_s,
-                                                                             const DevState* __restrict__ state, float lr, float s0,
-                                                                             float s1, float s2, float* __restrict__ grad_out, Vol vol,
-                                                                             int seg_len, int nseg, int ntx, int nty) {
+// HMC (compile-time, sghmc_device.h): 0 the update above; 1 / 2 the SGHMC step in its place, noise from Philox / from hm.eps, as in
+// sgld_update_march_kernel.  A workgroup marches ONE component: of the six normals of a voxel pair a thread keeps the two of its
+// component (the three components of a voxel make the same call -- thrice the generator's work of the first-order kernel, which
+// this kernel's 125-point stencil hides).  With HMC = 0 nothing of `hm` is touched.
+template <bool SIGMA, int HMC>
+__device__ __forceinline__ void sgld_update_bending_march_body(float* __restrict__ v, const float* __restrict__ sigma,
+                                                               const float* __restrict__ g, const float* __restrict__ v_s,
+                                                               const DevState* __restrict__ state, float lr, float s0,
+                                                               float s1, float s2, float* __restrict__ grad_out, Vol vol,
+                                                               int seg_len, int nseg, int ntx, int nty, const SghmcArgs& hm) {
     __shared__ float F[BNS * BPN];
     const BendTile b = bend_tile((int)blockIdx.x, (int)gridDim.x, vol, seg_len, nseg, ntx, nty);
     const int chain = blockIdx.y;
@@ -263,6 +267,7 @@ __global__ __launch_bounds__(kBdBlock) void sgld_update_bending_march_kernel(flo
     const unsigned own = col_in ? (unsigned)(oy_ * vol.W + ox_) * 4u : 0u;
     struct OwnIn {
         float g, v, s;
+        float m, e;  // SGHMC: momentum, injected noise
     };
     OwnIn qa = {}, qb = {};  // used alternately (no copies: a copy would have to wait for the loads it copies)
     auto load_own = [&](int z, OwnIn& q) {
@@ -270,7 +275,11 @@ __global__ __launch_bounds__(kBdBlock) void sgld_update_bending_march_kernel(flo
         q.g = ldg_off(g + base, own);
         q.v = ldg_off(v + base, own);
         if (SIGMA) q.s = ldg_off(sigma + base, own);
+        if (HMC) q.m = ldg_off(hm.m + base, own);
+        if (HMC == 2) q.e = ldg_off(hm.eps + base, own);
     };
+    float n_even = 0.0f, n_odd = 0.0f;  // SGHMC, Philox: this component's normals of the pair the plane in hand belongs to
+    const uint64_t iter = HMC == 1 ? state->st.iteration : 0ull;
     bending_march_tile<true, false>(
         F, v_s + cb, vol, b.ox, b.oy, b.z0, b.z1, [&](int z, auto par) { load_own(z, decltype(par)::value ? qb : qa); },
         [&](int z, int, int, float h, float, auto par) {
@@ -280,8 +289,40 @@ __global__ __launch_bounds__(kBdBlock) void sgld_update_bending_march_kernel(flo
             const float sg = SIGMA ? cur.s : 1.0f;
             const float gs = sg * sg * gr;  // SGLD.backward: sigma^2 * grad == v.grad in the reference
             if (grad_out) *reinterpret_cast<float*>(reinterpret_cast<char*>(grad_out + base) + own) = gs;
-            if (!frozen) *reinterpret_cast<float*>(reinterpret_cast<char*>(v + base) + own) = cur.v - lr * gs;
+            if (HMC) {
+                // (uniform branch; a segment that starts on an odd plane draws its pair too)
+                if (HMC == 1 && hm.noisy && ((z & 1) == 0 || z == b.z0)) {
+                    float n[2][3];
+                    sghmc_pair_draw(chain, vol.Vg, (int64_t)(z & ~1) * HW + (own >> 2), iter, hm.seed, n);
+                    n_even = b.comp == 0 ? n[0][0] : (b.comp == 1 ? n[0][1] : n[0][2]);
+                    n_odd = b.comp == 0 ? n[1][0] : (b.comp == 1 ? n[1][1] : n[1][2]);
+                }
+                float v1, m1;
+                sghmc_step(cur.v, cur.m, gs, sg, HMC == 2 ? cur.e : ((z & 1) ? n_odd : n_even), lr, hm.oma, hm.amp, hm.noisy != 0, v1, m1);
+                if (!frozen) {
+                    *reinterpret_cast<float*>(reinterpret_cast<char*>(v + base) + own) = v1;
+                    *reinterpret_cast<float*>(reinterpret_cast<char*>(hm.m + base) + own) = m1;
+                }
+            } else if (!frozen) *reinterpret_cast<float*>(reinterpret_cast<char*>(v + base) + own) = cur.v - lr * gs;
         });
+}
+
+template <bool SIGMA>
+__global__ __launch_bounds__(kBdBlock) void sgld_update_bending_march_kernel(float* __restrict__ v, const float* __restrict__ sigma,
+                                                                             const float* __restrict__ g, const float* __restrict__ v_s,
+                                                                             const DevState* __restrict__ state, float lr, float s0,
+                                                                             float s1, float s2, float* __restrict__ grad_out, Vol vol,
+                                                                             int seg_len, int nseg, int ntx, int nty) {
+    sgld_update_bending_march_body<SIGMA, 0>(v, sigma, g, v_s, state, lr, s0, s1, s2, grad_out, vol, seg_len, nseg, ntx, nty, SghmcArgs{});
+}
+
+template <bool SIGMA, int HMC>
+__global__ __launch_bounds__(kBdBlock) void sghmc_update_bending_march_kernel(float* __restrict__ v, const float* __restrict__ sigma,
+                                                                              const float* __restrict__ g, const float* __restrict__ v_s,
+                                                                              const DevState* __restrict__ state, float lr, float s0,
+                                                                              float s1, float s2, float* __restrict__ grad_out, Vol vol,
+                                                                              int seg_len, int nseg, int ntx, int nty, SghmcArgs hm) {
+    sgld_update_bending_march_body<SIGMA, HMC>(v, sigma, g, v_s, state, lr, s0, s1, s2, grad_out, vol, seg_len, nseg, ntx, nty, hm);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -319,7 +360,7 @@ void launch_bending_grad(const float* v, const float* scale, float* out, int C, 
 }
 
 void launch_sgld_update_bending(float* v, const float* sigma, const float* g_d0, const float* v_s, const void* dev_state, float lr,
-                                float s0, float s1, float s2, float* grad_out, int C, Vol vol, hipStream_t st) {
+                                float s0, float s1, float s2, float* grad_out, int C, Vol vol, hipStream_t st, const SghmcArgs* hm) {
     const int ntx = bend_ntx(vol), nty = bend_nty(vol);
     const int seg_len = bending_seg_len(vol, C);
     const int nseg = (vol.nz + seg_len - 1) / seg_len;
@@ -329,7 +370,17 @@ void launch_sgld_update_bending(float* v, const float* sigma, const float* g_d0,
         log_launch("sgld_update_bending_march_kernel", BTX, BTY, (int64_t)grid.x * C, kBdBlock, seg_len, 4, vol.nz, C,
                    resident_blocks((const void*)sgld_update_bending_march_kernel<false>, kBdBlock, &cache_l));
     }
-    if (sigma)
+    if (hm) {  // SGHMC; injected noise only counts where noise is added at all
+#define IRS_SGHMC_LAUNCH(SG, MODE)                                                                                                     \
+    hipLaunchKernelGGL((sghmc_update_bending_march_kernel<SG, MODE>), grid, dim3(kBdBlock), 0, st, v, sigma, g_d0, v_s,                       \
+                       (const DevState*)dev_state, lr, s0, s1, s2, grad_out, vol, seg_len, nseg, ntx, nty, *hm)
+        const bool inj = hm->eps && hm->noisy;
+        if (sigma && inj) IRS_SGHMC_LAUNCH(true, 2);
+        else if (sigma) IRS_SGHMC_LAUNCH(true, 1);
+        else if (inj) IRS_SGHMC_LAUNCH(false, 2);
+        else IRS_SGHMC_LAUNCH(false, 1);
+#undef IRS_SGHMC_LAUNCH
+    } else if (sigma)
         hipLaunchKernelGGL(sgld_update_bending_march_kernel<true>, grid, dim3(kBdBlock), 0, st, v, sigma, g_d0, v_s,
                            (const DevState*)dev_state, lr, s0, s1, s2, grad_out, vol, seg_len, nseg, ntx, nty);
     else

@@ -67,6 +67,10 @@ struct irs_ctx {
     irs::MiBins mi_bins = {};
     float mi_weight = 1.0f;
     bool mi_set = false;
+    // irs_sghmc_set: the update of a transition is the SGHMC step on (v, sghmc_m) and the forward pass adds no noise (sghmc_device.h)
+    bool sghmc = false;
+    float sghmc_friction = 1.0f, sghmc_temperature = 1.0f;
+    float* sghmc_m = nullptr;  // (C,3,Dv,Hv,Wv), the caller's
     unsigned* dmax;  // [no_steps + 1][C][4] max |d_k| in voxels per axis (float bits), by-product of the forward steps
     irs::AdjointPlan plan;  // sparse adjoint plan (adjoint_plan.hip); no buffers on a slab context
     bool sparse_adjoint = true;  // irs_sparse_adjoint_set: the adjoint steps walk the plan's lists (false: full columns)

@@ -61,6 +61,62 @@ void launch_perturb(const float* v, const float* sigma, const float* eps, float 
                        npair);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The SGHMC step (sghmc_device.h) outside a transition: (v, m) <- step(v, m, grad) in place.  perturb_kernel's launch shape -- one
+// thread per (x, y, z pair) and chain, the pair's six normals from one Philox call -- streaming: no LDS, no atomics; 16 to 24 bytes
+// read and 8 written per element.
+// ------------------------------------------------------------------------------------------------
+template <bool SIGMA, bool EPS>
+__global__ __launch_bounds__(kBlock) void sghmc_update_kernel(float* __restrict__ v, const float* __restrict__ grad,
+                                                              const float* __restrict__ sigma, float lr, SghmcArgs hm, Vol vol,
+                                                              uint64_t iteration, int npair) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int chain = blockIdx.z / npair;
+    const int za = 2 * ((int)blockIdx.z - chain * npair);
+    if (x >= vol.W || y >= vol.H) return;
+    const int64_t V = vol.V, HW = (int64_t)vol.H * vol.W;
+    const int64_t voxa = ((int64_t)za * vol.H + y) * vol.W + x;
+    const bool odd_in = za + 1 < vol.D;  // (an odd D: the last pair's odd plane is not there)
+    float n[2][3] = {};
+    if (!EPS && hm.noisy) sghmc_pair_draw(chain, vol.Vg, voxa, iteration, hm.seed, n);
+    // every load of the pair first, then the arithmetic and the stores
+    float fv[2][3], fm[2][3], fg[2][3], fs[2][3];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int64_t i = ((int64_t)chain * 3 + c) * V + voxa + (h && odd_in ? HW : 0);
+            fv[h][c] = v[i];
+            fm[h][c] = hm.m[i];
+            fg[h][c] = grad[i];
+            fs[h][c] = SIGMA ? sigma[i] : 1.0f;
+            if (EPS) n[h][c] = hm.eps[i];
+        }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (h && !odd_in) continue;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int64_t i = ((int64_t)chain * 3 + c) * V + voxa + h * HW;
+            float v1, m1;
+            sghmc_step(fv[h][c], fm[h][c], fg[h][c], fs[h][c], n[h][c], lr, hm.oma, hm.amp, hm.noisy != 0, v1, m1);
+            v[i] = v1;
+            hm.m[i] = m1;
+        }
+    }
+}
+
+void launch_sghmc_update(float* v, const float* grad, const float* sigma, float lr, const SghmcArgs& hm, uint64_t iteration, int C, Vol vol,
+                         hipStream_t st) {
+    const int npair = (vol.D + 1) / 2;
+    const dim3 grid((unsigned)((vol.W + 63) / 64), (unsigned)((vol.H + 3) / 4), (unsigned)(npair * C));
+    const bool inj = hm.eps && hm.noisy;  // injected noise only counts where noise is added at all
+    if (sigma && inj) hipLaunchKernelGGL((sghmc_update_kernel<true, true>), grid, dim3(kBlock), 0, st, v, grad, sigma, lr, hm, vol, iteration, npair);
+    else if (sigma) hipLaunchKernelGGL((sghmc_update_kernel<true, false>), grid, dim3(kBlock), 0, st, v, grad, sigma, lr, hm, vol, iteration, npair);
+    else if (inj) hipLaunchKernelGGL((sghmc_update_kernel<false, true>), grid, dim3(kBlock), 0, st, v, grad, sigma, lr, hm, vol, iteration, npair);
+    else hipLaunchKernelGGL((sghmc_update_kernel<false, false>), grid, dim3(kBlock), 0, st, v, grad, sigma, lr, hm, vol, iteration, npair);
+}
+
 // per-channel constants of the coordinate transforms: x <-> W, y <-> H, z <-> D (the reference pairs channel c with shape[2 + c],
 // which is the same thing for the cubic volumes it supports)
 struct Scale3 {

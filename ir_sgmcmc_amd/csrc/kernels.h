@@ -1,6 +1,7 @@
 // Host-side launchers of the gfx950 kernels (internal; the public surface is include/irsgmcmc.h).
 #pragma once
 #include "common.h"
+#include "sghmc_device.h"
 
 namespace irs {
 
@@ -27,6 +28,9 @@ int cached_lin(int D, int H, int W, hipStream_t st, Lin* out);
 // ---- field_kernels.hip
 void launch_perturb(const float* v, const float* sigma, const float* eps, float amp, float* out, int C, Vol vol,
                     uint64_t seed, uint64_t iteration, const uint64_t* dev_iteration, hipStream_t st);
+// the SGHMC step (sghmc_device.h) on (v, hm.m) in place, outside a transition: grad is grad_v, every chain in one launch
+void launch_sghmc_update(float* v, const float* grad, const float* sigma, float lr, const SghmcArgs& hm, uint64_t iteration, int C, Vol vol,
+                         hipStream_t st);
 void launch_svf_outputs(const float* d, float* transformation, float* displacement, int C, Vol vol, Lin lin,
                         hipStream_t st);
 void launch_warp_fwd(const float* im, int64_t im_stride, const float* d, const float* unif, float alpha, float* out,
@@ -179,9 +183,10 @@ void launch_reduce_partials(const double* partials, int nblocks, int nvals, doub
 void launch_reduce_cols(const double* partials, int nblocks, int ncols, double* out, hipStream_t st);
 // energy_partials (optional, [C][sgld_update_blocks_per_chain]): regulariser energy of v_s as a by-product; coef_from_w: the
 // regulariser coefficient is w / 2 from the state (L2 family) instead of the one reg_scalar_kernel left in the state
+// hm (optional): the SGHMC step on (v, hm->m) in place of v <- v - lr grad_v (sghmc_device.h)
 void launch_sgld_update(float* v, const float* sigma, const float* g_d0, const float* v_s, const void* dev_state,
                         float lr, float s0, float s1, float s2, float* grad_out, int C, Vol vol, hipStream_t st,
-                        double* energy_partials = nullptr, bool coef_from_w = false);
+                        double* energy_partials = nullptr, bool coef_from_w = false, const SghmcArgs* hm = nullptr);
 int sgld_update_blocks_per_chain(Vol vol, int C);
 void launch_gradient_operator(const float* v, float* nabla, int transformation, int C, Vol vol, hipStream_t st);
 void launch_log_det_jacobian(const float* t, float* log_det, long long* nan_count, int C, Vol vol, hipStream_t st);
@@ -190,7 +195,7 @@ void launch_stats_march(int want_vd, const float* z, const uint8_t* mask, const 
 void launch_reg_energy_march(const float* v, double* partials, int blocks, int C, Vol vol, hipStream_t st);
 void launch_sgld_update_march(float* v, const float* sigma, const float* g_d0, const float* v_s, const void* dev_state,
                               float lr, float s0, float s1, float s2, float* grad_out, int C, Vol vol, hipStream_t st,
-                              double* energy_partials = nullptr, bool coef_from_w = false);
+                              double* energy_partials = nullptr, bool coef_from_w = false, const SghmcArgs* hm = nullptr);
 int stats_blocks(Vol vol);
 int energy_blocks(Vol vol);
 
@@ -201,7 +206,8 @@ void launch_bending_energy(const float* v, double* partials, int blocks, int C, 
 void launch_bending_grad(const float* v, const float* scale, float* out, int C, Vol vol, hipStream_t st);
 // launch_sgld_update with the bending stencil; the coefficient is always the one the scalar stage left in the state
 void launch_sgld_update_bending(float* v, const float* sigma, const float* g_d0, const float* v_s, const void* dev_state, float lr,
-                                float s0, float s1, float s2, float* grad_out, int C, Vol vol, hipStream_t st);
+                                float s0, float s1, float s2, float* grad_out, int C, Vol vol, hipStream_t st,
+                                const SghmcArgs* hm = nullptr);
 
 // ---- metric_kernels.hip: average surface distance of label contours (utils/util.py:152-206)
 struct SurfLabels {

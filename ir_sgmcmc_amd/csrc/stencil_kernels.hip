@@ -1350,13 +1350,18 @@ constexpr int UPX = QTX + 2, UPY = QTY + 2, UPN = UPX * UPY, UNS = 4;
 // stencil above is built from exactly those differences and weights.  Used for the regularisers whose coefficient does not depend
 // on the energy (RegLoss_L2, RegLoss_LogNormal_L2: coef = w / 2, `coef_from_w`), where the energy is only needed AFTER the update
 // (loss term, Adam step on log w): one kernel and one pass over v_s less per transition.
-template <bool SIGMA>  // sigma field present (compile-time: a run-time branch around its loads leaves waits in the own-voxel prefetch)
-__global__ __launch_bounds__(kStBlock) void sgld_update_march_kernel(float* __restrict__ v, const float* __restrict__ sigma,
-                                                                     const float* __restrict__ g, const float* __restrict__ v_s,
-                                                                     const DevState* __restrict__ state, float lr, float s0,
-                                                                     float s1, float s2, float* __restrict__ grad_out, Vol vol,
-                                                                     int seg_len, int nseg, int ntx, int nty,
-                                                                     double* __restrict__ energy_partials, int coef_from_w) {
+//
+// HMC (compile-time, sghmc_device.h): 0 the update above; 1 / 2 the SGHMC step in its place, noise from Philox / from hm.eps -- the
+// momentum (and the injected noise) join the own-voxel streams, a thread keeps the six normals of its voxel pair across the two
+// planes, and a frozen transition leaves the momentum alone as it leaves v.  With HMC = 0 nothing of `hm` is touched: the two
+// kernels of the reference's update compile from these lines to what they were.
+template <bool SIGMA, int HMC>  // sigma field present (compile-time: a run-time branch around its loads leaves waits in the own-voxel prefetch)
+__device__ __forceinline__ void sgld_update_march_body(float* __restrict__ v, const float* __restrict__ sigma,
+                                                       const float* __restrict__ g, const float* __restrict__ v_s,
+                                                       const DevState* __restrict__ state, float lr, float s0,
+                                                       float s1, float s2, float* __restrict__ grad_out, Vol vol,
+                                                       int seg_len, int nseg, int ntx, int nty,
+                                                       double* __restrict__ energy_partials, int coef_from_w, const SghmcArgs& hm) {
     constexpr int NIT = (UPN + kStBlock - 1) / kStBlock;
     __shared__ float F[UNS * 3 * UPN];
     __shared__ double esm[kStBlock / kWave];
@@ -1423,6 +1428,7 @@ __global__ __launch_bounds__(kStBlock) void sgld_update_march_kernel(float* __re
     // to v orders the next channel's load behind it).  That made this kernel latency-bound at 2.5x its HBM time.
     struct OwnIn {
         float g[3], v[3], s[3];
+        float m[3], e[3];  // SGHMC: momentum, injected noise
     };
     auto load_own = [&](int z, OwnIn& q) {
         const int64_t pl = (int64_t)z * HW;
@@ -1432,8 +1438,12 @@ __global__ __launch_bounds__(kStBlock) void sgld_update_march_kernel(float* __re
             q.g[c] = ldg_off(g + base, own);
             q.v[c] = ldg_off(v + base, own);
             if (SIGMA) q.s[c] = ldg_off(sigma + base, own);
+            if (HMC) q.m[c] = ldg_off(hm.m + base, own);
+            if (HMC == 2) q.e[c] = ldg_off(hm.eps + base, own);
         }
     };
+    float nz[2][3] = {};  // SGHMC, Philox: the normals of the pair the plane in hand belongs to, [plane parity][channel]
+    const uint64_t iter = HMC == 1 ? state->st.iteration : 0ull;
     // one plane: `cur` holds the plane's own-voxel streams (requested a step ago), `nxt` receives the next plane's
     auto step = [&](int zc, const OwnIn& cur, OwnIn& nxt) {
         // commit needs the newest loads anyway; said unconditionally (the commit's own waits sit behind per-lane guards) it also
@@ -1451,6 +1461,8 @@ __global__ __launch_bounds__(kStBlock) void sgld_update_march_kernel(float* __re
             const float wzm = wm(zc, vol.D), wzp = wp(zc, vol.D);
             const int ci = (ly + 1) * UPX + lx + 1;
             const int64_t pl = (int64_t)zc * HW;
+            // (uniform branch; a segment that starts on an odd plane draws its pair too)
+            if (HMC == 1 && hm.noisy && ((zc & 1) == 0 || zc == z0)) sghmc_pair_draw(chain, vol.Vg, (int64_t)(zc & ~1) * HW + (own >> 2), iter, hm.seed, nz);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float* __restrict__ P = F + (s0_ * 3 + c) * UPN;
@@ -1470,7 +1482,15 @@ __global__ __launch_bounds__(kStBlock) void sgld_update_march_kernel(float* __re
                 const float gs = sg * sg * gr;  // SGLD.backward: sigma^2 * grad == v.grad in the reference
                 float* __restrict__ vp = reinterpret_cast<float*>(reinterpret_cast<char*>(v + base) + own);
                 if (grad_out) *reinterpret_cast<float*>(reinterpret_cast<char*>(grad_out + base) + own) = gs;
-                if (!frozen) *vp = cur.v[c] - lr * gs;
+                if (HMC) {
+                    float v1, m1;
+                    sghmc_step(cur.v[c], cur.m[c], gs, sg, HMC == 2 ? cur.e[c] : ((zc & 1) ? nz[1][c] : nz[0][c]), lr, hm.oma, hm.amp, hm.noisy != 0,
+                               v1, m1);
+                    if (!frozen) {
+                        *vp = v1;
+                        *reinterpret_cast<float*>(reinterpret_cast<char*>(hm.m + base) + own) = m1;
+                    }
+                } else if (!frozen) *vp = cur.v[c] - lr * gs;
             }
         }
     };
@@ -1485,6 +1505,28 @@ __global__ __launch_bounds__(kStBlock) void sgld_update_march_kernel(float* __re
         block_sum<1>(eacc, esm);
         if (threadIdx.x == 0) energy_partials[tile] = eacc[0];  // tile = chain * tiles_per_chain + tile in chain: [C][tiles]
     }
+}
+
+template <bool SIGMA>
+__global__ __launch_bounds__(kStBlock) void sgld_update_march_kernel(float* __restrict__ v, const float* __restrict__ sigma,
+                                                                     const float* __restrict__ g, const float* __restrict__ v_s,
+                                                                     const DevState* __restrict__ state, float lr, float s0,
+                                                                     float s1, float s2, float* __restrict__ grad_out, Vol vol,
+                                                                     int seg_len, int nseg, int ntx, int nty,
+                                                                     double* __restrict__ energy_partials, int coef_from_w) {
+    sgld_update_march_body<SIGMA, 0>(v, sigma, g, v_s, state, lr, s0, s1, s2, grad_out, vol, seg_len, nseg, ntx, nty, energy_partials,
+                                     coef_from_w, SghmcArgs{});
+}
+
+template <bool SIGMA, int HMC>
+__global__ __launch_bounds__(kStBlock) void sghmc_update_march_kernel(float* __restrict__ v, const float* __restrict__ sigma,
+                                                                      const float* __restrict__ g, const float* __restrict__ v_s,
+                                                                      const DevState* __restrict__ state, float lr, float s0,
+                                                                      float s1, float s2, float* __restrict__ grad_out, Vol vol,
+                                                                      int seg_len, int nseg, int ntx, int nty,
+                                                                      double* __restrict__ energy_partials, int coef_from_w, SghmcArgs hm) {
+    sgld_update_march_body<SIGMA, HMC>(v, sigma, g, v_s, state, lr, s0, s1, s2, grad_out, vol, seg_len, nseg, ntx, nty, energy_partials,
+                                       coef_from_w, hm);
 }
 
 static int update_seg_len(Vol vol, int C) {
@@ -1506,7 +1548,7 @@ int sgld_update_blocks_per_chain(Vol vol, int C) {
 
 void launch_sgld_update_march(float* v, const float* sigma, const float* g_d0, const float* v_s, const void* dev_state,
                               float lr, float s0, float s1, float s2, float* grad_out, int C, Vol vol, hipStream_t st,
-                              double* energy_partials, bool coef_from_w) {
+                              double* energy_partials, bool coef_from_w, const SghmcArgs* hm) {
     const int seg_len = update_seg_len(vol, C);
     const int nseg = (vol.nz + seg_len - 1) / seg_len;
     const int ntx = (vol.W + QTX - 1) / QTX, nty = (vol.H + QTY - 1) / QTY;
@@ -1515,7 +1557,18 @@ void launch_sgld_update_march(float* v, const float* sigma, const float* g_d0, c
         log_launch("sgld_update_march_kernel", QTX, QTY, (int64_t)ntx * nty * nseg * C, kStBlock, seg_len, 2, vol.nz, C,
                    resident_blocks((const void*)sgld_update_march_kernel<false>, kStBlock, &cache_l));
     }
-    if (sigma)
+    if (hm) {  // SGHMC; injected noise only counts where noise is added at all
+        const dim3 grid((unsigned)(ntx * nty * nseg * C));
+#define IRS_SGHMC_LAUNCH(SG, MODE)                                                                                                       \
+    hipLaunchKernelGGL((sghmc_update_march_kernel<SG, MODE>), grid, dim3(kStBlock), 0, st, v, sigma, g_d0, v_s, (const DevState*)dev_state, lr, \
+                       s0, s1, s2, grad_out, vol, seg_len, nseg, ntx, nty, energy_partials, coef_from_w ? 1 : 0, *hm)
+        const bool inj = hm->eps && hm->noisy;
+        if (sigma && inj) IRS_SGHMC_LAUNCH(true, 2);
+        else if (sigma) IRS_SGHMC_LAUNCH(true, 1);
+        else if (inj) IRS_SGHMC_LAUNCH(false, 2);
+        else IRS_SGHMC_LAUNCH(false, 1);
+#undef IRS_SGHMC_LAUNCH
+    } else if (sigma)
         hipLaunchKernelGGL(sgld_update_march_kernel<true>, dim3((unsigned)(ntx * nty * nseg * C)), dim3(kStBlock), 0, st, v, sigma, g_d0,
                            v_s, (const DevState*)dev_state, lr, s0, s1, s2, grad_out, vol, seg_len, nseg, ntx, nty, energy_partials,
                            coef_from_w ? 1 : 0);

@@ -54,6 +54,9 @@ class EngineConfig:
     reg_scale_prior: Tuple[float, float] = (2.8, 5.0)
     seed: int = 0
     diff_op: str = 'GradientOperator'                     # reg_loss diff_op: 'GradientOperator' | 'HessianOperator' (bending energy)
+    sampler: str = 'SGLD'                                 # 'SGLD' (the reference's scheme) | 'SGHMC' (sghmc.py: momentum, noise kept in v)
+    sghmc_friction: float = 0.1                           # 'SGHMC': in (0, 1]; 1 = Langevin dynamics with persisted noise
+    sghmc_temperature: float = 1.0                        # 'SGHMC': >= 0; 0 = no noise, a heavy-ball optimiser
 
     @property
     def dims_v(self):
@@ -148,6 +151,12 @@ class TransitionEngine:
             self.lncc_set(cfg.lncc_weight, cfg.lncc_eps)
         if cfg.data_loss == 'MI' and cfg.mi_fixed_range is not None and cfg.mi_moving_range is not None:
             self.mi_set(cfg.mi_weight, cfg.mi_fixed_range, cfg.mi_moving_range)
+        # SGHMC: the momentum lives here, bound to the context before its first transition (irs_config has no room for the sampler)
+        if cfg.sampler not in ('SGLD', 'SGHMC'):
+            raise ValueError(f'sampler {cfg.sampler!r}: one of SGLD, SGHMC')
+        self.momentum = None
+        if cfg.sampler == 'SGHMC':
+            self._bind_momentum()
         if cfg.reg_loss == 'RegLoss_LogNormal':
             st = self.state()
             st.reg_param[0], st.reg_param[1] = lognormal_init(cfg.w_reg, cfg.dof)
@@ -171,6 +180,13 @@ class TransitionEngine:
         transition"""
         (f_lo, f_hi), (m_lo, m_hi) = fixed_range, moving_range
         L.check(self.lib.irs_mi_set(self._ctx, float(weight), float(f_lo), float(f_hi), float(m_lo), float(m_hi)))
+
+    def _bind_momentum(self):
+        """irs_sghmc_set: a zeroed momentum (C, 3, *dims_v) that the transitions update next to v; only before the first one"""
+        cfg = self.cfg
+        momentum = torch.zeros((cfg.no_chains, 3, *cfg.dims_v), device=self.device, dtype=torch.float32)
+        L.check(self.lib.irs_sghmc_set(self._ctx, float(cfg.sghmc_friction), float(cfg.sghmc_temperature), L.dev_ptr(momentum, torch.float32)))
+        self.momentum = momentum
 
     def __del__(self):
         ctx, self._ctx = getattr(self, '_ctx', None), None

@@ -217,6 +217,8 @@ class SlabEngine(TransitionEngine):
         if cfg.data_loss == 'MI':
             raise L.IrsError('irs_slab_create: the MI data term is not supported on z-slabs (the joint histogram of a chain would need '
                              'an all-reduce between its accumulate and finish kernels): data_loss must be GMM or SSD')
+        if cfg.sampler != 'SGLD':
+            raise L.IrsError(f'irs_sghmc_set: a z-slab context keeps the reference\'s update: sampler must be SGLD, got {cfg.sampler!r}')
         self._scfg = L.IrsSlabConfig(ghost_max, margin)
         super().__init__(cfg, device)
         lay = L.IrsSlabLayout()

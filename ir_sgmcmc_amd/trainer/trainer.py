@@ -42,7 +42,7 @@ from ..logger import (save_displacement_covariance, save_displacement_mean_and_s
                       save_posterior_comparison, save_precond_sigma,
                       save_residual_histogram, save_residual_nll, save_rhat, save_sample, save_structure_report, save_surface_posterior,
                       save_truth_calibration)
-from .. import affine, bspline, image_posterior, mi, multires, preconditioner, residual_check, structure_report
+from .. import affine, bspline, image_posterior, mi, multires, preconditioner, residual_check, sghmc, structure_report
 from .. import truth as truth_ops
 from .. import masks as mask_ops  # (`masks` names the pair of masks in several methods below)
 from ..multires import coarse_start_options
@@ -232,6 +232,13 @@ class Trainer(VIMixin, BaseTrainer):
         self.precond_options = preconditioner.adaptive_preconditioner_options(cfg_trainer, self.no_iters_burn_in)
         self._precond, self._precond_grad, self._precond_frozen_at = None, None, None
         self.preconditioner_summary = None
+        # the sampler (sghmc.py): None when trainer.sampler is absent or {"type": "SGLD"}, and then nothing changes.  With "SGHMC"
+        # the engine owns the momentum (engine.momentum); sampler_summary: the options and the last kinetic temperature logged
+        self.sampler_options = sghmc.sampler_options(cfg_trainer)
+        self.sampler_summary = None
+        extra = sghmc.extra_optimizer_keys(config['optimizer_SG_MCMC'])
+        if extra:  # (once: they have never been read, and still are not)
+            self.logger.warning(f'optimizer_SG_MCMC.args: {extra} are ignored -- the field update reads "lr" and nothing else')
         # cubic B-spline resampling of the images that are saved (bspline.py): None unless trainer.output_interpolation is
         # "cubic".  _spline_coeff: the coefficients of the moving image, formed when the engine is set up (a resumed run forms
         # them again: nothing goes into a checkpoint)
@@ -401,6 +408,9 @@ class Trainer(VIMixin, BaseTrainer):
                 lp, sp = self.losses['reg']['loc_prior'], self.losses['reg']['scale_prior'].normal
                 ec.update(reg_lr=(o['lr_loc'], o['lr_log_scale']), reg_lr_decay=o['lr_decay'], loc_prior_nu=float(lp.nu),
                           loc_prior_w_reg=float(lp.w_reg), reg_scale_prior=(float(sp.loc), float(sp.log_scale.exp())))
+        if self.sampler_options is not None:
+            ec.update(sampler=self.sampler_options['type'], sghmc_friction=self.sampler_options['friction'],
+                      sghmc_temperature=self.sampler_options['temperature'])
         return EngineConfig(**ec)
 
     def _engine_init(self, fixed, moving):
@@ -413,6 +423,11 @@ class Trainer(VIMixin, BaseTrainer):
             ec = self.engine.cfg
             self.logger.info(f'MI data term: {ec.mi_bins} bins, weight {ec.mi_weight:g}, fixed range [{ec.mi_fixed_range[0]:.6g}, '
                              f'{ec.mi_fixed_range[1]:.6g}], moving range [{ec.mi_moving_range[0]:.6g}, {ec.mi_moving_range[1]:.6g}]')
+        if self.sampler_options is not None:
+            opt = self.sampler_options
+            self.sampler_summary = {'options': dict(opt), 'kinetic_temperature': None}
+            self.logger.info(f'sampler: SGHMC, friction {opt["friction"]:g}, temperature {opt["temperature"]:g} (momentum on the '
+                             f'velocity grid, noise persisted in v; the forward pass adds none)')
         self._fixed, self._moving = self.engine.prepare(fixed, moving)
         self._mask_idx = None
         self._set_hyper_parameters(self.engine)
@@ -529,6 +544,7 @@ class Trainer(VIMixin, BaseTrainer):
                 'config_name': self.config['name'],
                 **({'preconditioner': preconditioner.checkpoint_entry(self._precond, self._precond_frozen_at)}
                    if self._precond is not None else {}),
+                **({'momentum': self.engine.momentum.detach().cpu()} if self.engine.momentum is not None else {}),
                 **{r.key: r.state.state_dict() for r in self._recorders()}}
 
     def load_state_dict(self, sd):
@@ -550,6 +566,14 @@ class Trainer(VIMixin, BaseTrainer):
         if self.precond_options is not None:
             preconditioner.check_checkpoint(sd, self.precond_options, self._sample_no)
             self._precond_restore(sd.get('preconditioner'))
+        if self.engine.momentum is not None:
+            if 'momentum' in sd:
+                self.engine.momentum.copy_(sd['momentum'].to(self.device))
+            elif self._sample_no > 0:
+                raise ValueError(f'the checkpoint at sample {self._sample_no} holds no momentum (written with trainer.sampler off or '
+                                 f'"SGLD") but this run samples with SGHMC')
+            else:
+                self.engine.momentum.zero_()
         for r in self._recorders():
             if r.key in sd:
                 r.state.load_state_dict(sd[r.key])
@@ -613,7 +637,8 @@ class Trainer(VIMixin, BaseTrainer):
             torch.cuda.synchronize(self.device)
             start = time.perf_counter()
             d, lr = level['dims'], base.lr if level['lr'] is None else level['lr']
-            engine = TransitionEngine(dataclasses.replace(base, dims=d, lr=lr, seed=base.seed + 1 + no), self.device)
+            # (the levels keep the reference's update whatever trainer.sampler says: their job is a start, not samples)
+            engine = TransitionEngine(dataclasses.replace(base, dims=d, lr=lr, seed=base.seed + 1 + no, sampler='SGLD'), self.device)
             fixed, moving = engine.prepare(*multires.restrict_pair(self._fixed, self._moving, d))
             self._set_hyper_parameters(engine, lognormal=False)
             v = torch.zeros((self.no_chains, 3, *d), device=self.device) if v is None else multires.prolong_field(v, d)
@@ -886,6 +911,12 @@ class Trainer(VIMixin, BaseTrainer):
                     for idx in range(self.no_chains):
                         save_sample(self.config.save_dirs, spacing, sample_no, saved_im[idx:idx + 1],
                                     displacement[idx:idx + 1], log_det_J[idx:idx + 1], 'MCMC', chain_no=idx)
+                if self.sampler_options is not None:
+                    kt = sghmc.kinetic_temperature(self.engine.momentum, self._sigma, self.engine.cfg.lr,
+                                                   self.sampler_options['friction']).tolist()
+                    self.sampler_summary['kinetic_temperature'] = kt
+                    for idx in range(self.no_chains):
+                        self.metrics.update(f'MCMC/chain_{idx}/sampler/kinetic_temperature', kt[idx])
                 for idx in range(self.no_chains):
                     n_rec += 1
                     delta = displacement[idx] - mean
