@@ -35,7 +35,7 @@ extern "C" {
 #define IRS_HAUSDORFF_MAX_PERCENTILES 4 /* percentiles of one irs_label_hausdorff_distance call */
 
 /* data term (irs_config.data_loss).  The value 2 is reserved: irs_create refuses it. */
-enum { IRS_DATA_GMM_LCC = 0, IRS_DATA_SSD = 1, IRS_DATA_LNCC = 3, IRS_DATA_MI = 4 };
+enum { IRS_DATA_GMM_LCC = 0, IRS_DATA_SSD = 1, IRS_DATA_LNCC = 3, IRS_DATA_MI = 4, IRS_DATA_NGF = 5 };
 enum { IRS_REG_L2 = 0, IRS_REG_LOGNORMAL = 1, IRS_REG_STUDENT = 2, IRS_REG_LOGNORMAL_L2 = 3 };
 /* differential operator of the regulariser energy y (irs_config.diff_op): the reference's GradientOperator, or the same
  * operator applied twice (HessianOperator, the bending energy) */
@@ -175,6 +175,32 @@ int irs_mi_fwd(const float* fixed, int Cf, const float* moving, const uint8_t* m
 int irs_mi_bwd(const float* fixed, int Cf, const float* moving, const uint8_t* mask, int Cm, const float* table, int bins, float f_lo,
                float f_hi, float m_lo, float m_hi, const float* scale, float* g_moving, float* pmi, int C, int D, int H, int W,
                void* stream);
+
+/* The NGF data term (absent in the reference): the normalised gradient field distance of Haber & Modersitzki (2006), which compares
+ * only the direction of the two image gradients, up to their sign -- local like LNCC, free of a common contrast like MI.  All of
+ * it float32.  grad is the central difference with clamped indices, in voxel units, on each of the three axes,
+ *   (grad I)_a(x) = 0.5 * (I[min(x_a + 1, n_a - 1)] - I[max(x_a - 1, 0)])        (the replicate padding of the LCC and LNCC windows).
+ * With a = grad F (fixed image), b = grad M (moving image) and the edge parameters eps_f, eps_m > 0, at every voxel
+ *   P = a.b        Nf = |a|^2 + eps_f^2        Nm = |b|^2 + eps_m^2
+ *   r = P / (Nf Nm)        d = 1 - P r                    ( = 1 - (a.b)^2 / (Nf Nm), in [0, 1] )
+ *   s = P / Nm             k = -2 u r
+ *   c = k (a - s b)                                       ( = u dd/db, three components in the order z, y, x )
+ *   g_M = grad^T c                                        ( = d/dM of sum u d )
+ * grad^T is the transpose of the clamped difference; on an axis of length n: interior y: 0.5 (c[y-1] - c[y+1]); low face y = 0:
+ * 0.5 (-c[0] - c[1]); high face y = n - 1: 0.5 (c[n-2] + c[n-1]); n = 2: the two face rules and nothing else.  The three axes are
+ * added in the order z, y, x.  No special case: a flat neighbourhood has P = 0, d = 1 and c = 0, and every denominator is positive.
+ * Every operation is rounded once, in the order written (a.b and |a|^2 added left to right over z, y, x; eps^2 a float32 product;
+ * the two divisions correctly rounded; nothing contracts into an FMA): a float32 restatement reproduces d, c and g bit for bit
+ * (csrc/ngf_device.h spells the operations out).
+ *  - irs_ngf_fwd.  fixed: (Cf,1,D,H,W), Cf in {1, C}; moving: (C,1,D,H,W); upstream u: (Cu,1,D,H,W), Cu in {1, C}, or NULL for 1 (Cu
+ *    ignored); eps_f, eps_m finite and > 0.  Outputs, each may be NULL: d (C,1,D,H,W); coef (C,3,D,H,W) = c_z, c_y, c_x; sums: C
+ *    doubles on the device, sums[c] = sum u d of chain c in a fixed order, which needs partials: scratch of
+ *    irs_reduce_scratch_doubles() doubles.
+ *  - irs_ngf_bwd.  g_moving (C,1,D,H,W) = grad^T coef, from the coefficient maps alone; g_moving must not be coef.
+ * No atomics and no state: two calls give the same bits, and chain c of a batch is the single-chain call. */
+int irs_ngf_fwd(const float* fixed, int Cf, const float* moving, const float* upstream, int Cu, float eps_f, float eps_m, float* d,
+                float* coef, double* sums, double* partials, int C, int D, int H, int W, void* stream);
+int irs_ngf_bwd(const float* coef, float* g_moving, int C, int D, int H, int W, void* stream);
 
 /* GradientOperator + energy (utils/diff_op.py:78-96, model/loss.py:158-159): y[c] = sum (fwd diff)^2.
  * y_out: C doubles on the device.  partials: scratch of irs_reduce_scratch_doubles() doubles. */
@@ -1082,7 +1108,7 @@ typedef struct irs_config {
     int32_t virtual_decimation;
     int32_t data_loss;      /* IRS_DATA_* */
     int32_t lcc_s;          /* IRS_DATA_LNCC: the window radius, 1 .. IRS_MAX_HALF_WIDTH (weight and eps: irs_lncc_set);
-                             * IRS_DATA_MI: the bins, IRS_MI_MIN_BINS .. IRS_MI_MAX_BINS (weight and ranges: irs_mi_set) */
+                             * IRS_DATA_MI: the bins, IRS_MI_MIN_BINS .. IRS_MI_MAX_BINS (weight and ranges: irs_mi_set); IRS_DATA_NGF: not read */
     int32_t gmm_components;
     float ssd_sigma;
     /* optimizer_GMM (optimizers/adam_rate_decay.py) + hyper-priors (trainer.py:68-77) */
@@ -1168,6 +1194,12 @@ int irs_lncc_set(irs_ctx* ctx, float weight, float eps);
  * transition.  Such a context takes no virtual decimation and no z-slab, and its sparse data and sparse forward stages stay off
  * (the sparse adjoint works as ever: the gradient vanishes off the mask). */
 int irs_mi_set(irs_ctx* ctx, float weight, float f_lo, float f_hi, float m_lo, float m_hi);
+/* IRS_DATA_NGF: the data term of a chain is weight * sum mask * d (irs_ngf_fwd with the mask as u), alpha[c] = 1, and
+ * irs_io.residuals receives mask * d.  weight, eps_f and eps_m, finite and > 0, travel here because irs_config has no room left;
+ * the call is required -- the library does not guess an edge parameter, and a transition of a context that never had it is
+ * refused -- and allowed only before the first transition.  Such a context takes no virtual decimation and no z-slab, and its
+ * sparse data and sparse forward stages stay off: the stencil reads beyond the mask (the sparse adjoint works as ever). */
+int irs_ngf_set(irs_ctx* ctx, float weight, float eps_f, float eps_m);
 /* Switches the context's sampler to SGHMC: the update of a transition becomes the step of irs_sghmc_update on (irs_io.v, momentum)
  * with lr = irs_config.lr, sigma = irs_io.sigma, the context's seed and Philox counter, and grad = grad_v, which irs_io.grad_v
  * still receives; the forward pass adds NO noise -- curr_state is the smoothed v itself -- and irs_io.eps, where given, is the

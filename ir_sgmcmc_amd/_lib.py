@@ -59,7 +59,7 @@ IRS_MODES_MAX, IRS_MODES_MAX_RECORDS = 16, 1024
 IRS_AFFINE_SUMS, IRS_AFFINE_PARTIALS, IRS_AFFINE_MAX_BLOCKS = 94, 76, 512
 IRS_AFFINE_WS_BYTES = IRS_AFFINE_MAX_BLOCKS * IRS_AFFINE_PARTIALS * 8
 IRS_MASK_MIN_BINS, IRS_MASK_MAX_BINS, IRS_MASK_MAX_KEEP, IRS_MASK_MAX_RADIUS = 2, 4096, 64, 16
-IRS_DATA_GMM_LCC, IRS_DATA_SSD, IRS_DATA_LNCC, IRS_DATA_MI = 0, 1, 3, 4  # (2 is reserved)
+IRS_DATA_GMM_LCC, IRS_DATA_SSD, IRS_DATA_LNCC, IRS_DATA_MI, IRS_DATA_NGF = 0, 1, 3, 4, 5  # (2 is reserved)
 IRS_MI_STATS, IRS_MI_MIN_BINS, IRS_MI_MAX_BINS, IRS_MI_MAX_BLOCKS = 7, 8, 64, 1024
 IRS_MI_WS_BYTES = IRS_MAX_CHAINS * IRS_MI_MAX_BINS * IRS_MI_MAX_BINS * 8 + IRS_MI_MAX_BLOCKS * 3 * 8
 IRS_REG_L2, IRS_REG_LOGNORMAL, IRS_REG_STUDENT, IRS_REG_LOGNORMAL_L2 = 0, 1, 2, 3
@@ -175,6 +175,8 @@ SIGNATURES = {
     'irs_lncc_bwd': [_P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P],
     'irs_mi_fwd': [_P, _I, _P, _P, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     'irs_mi_bwd': [_P, _I, _P, _P, _I, _P, _I, _F, _F, _F, _F, _P, _P, _P, _I, _I, _I, _I, _P],
+    'irs_ngf_fwd': [_P, _I, _P, _P, _I, _F, _F, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    'irs_ngf_bwd': [_P, _P, _I, _I, _I, _I, _P],
     'irs_reg_energy': [_P, _P, _P, _I, _I, _I, _I, _P],
     'irs_reduce_scratch_doubles': [],
     'irs_bending_energy': [_P, _P, _P, _I, _I, _I, _I, _P],
@@ -269,6 +271,7 @@ SIGNATURES = {
     'irs_set_fixed': [_P, _P, _I, _P],
     'irs_lncc_set': [_P, _F, _F],
     'irs_mi_set': [_P, _F, _F, _F, _F, _F],
+    'irs_ngf_set': [_P, _F, _F, _F],
     'irs_sghmc_set': [_P, _F, _F, _P],
     'irs_sghmc_update': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _U64, _U64, _P],
     'irs_get_state': [_P, C.POINTER(IrsState), _P],

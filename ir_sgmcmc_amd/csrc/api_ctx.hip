@@ -31,7 +31,7 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     if (cfg->no_steps < 1 || cfg->no_steps > 30) return fail("irs_create: no_steps out of range");
     if (cfg->sobolev_s < 0 || cfg->sobolev_s > IRS_MAX_HALF_WIDTH) return fail("irs_create: sobolev_s out of range");
     if (cfg->data_loss != IRS_DATA_GMM_LCC && cfg->data_loss != IRS_DATA_SSD && cfg->data_loss != IRS_DATA_LNCC &&
-        cfg->data_loss != IRS_DATA_MI)
+        cfg->data_loss != IRS_DATA_MI && cfg->data_loss != IRS_DATA_NGF)
         return fail("irs_create: unknown data loss");
     if (cfg->data_loss == IRS_DATA_GMM_LCC) {
         if (!lcc_ok(cfg->lcc_s, D, H, W)) return fail("irs_create: LCC half width must be 1 or 2");
@@ -47,6 +47,9 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
         if (cfg->lcc_s < IRS_MI_MIN_BINS || cfg->lcc_s > IRS_MI_MAX_BINS)
             return fail("irs_create: MI bins = %d, %d..%d", cfg->lcc_s, IRS_MI_MIN_BINS, IRS_MI_MAX_BINS);
         if (cfg->virtual_decimation != 0) return fail("irs_create: the MI data term takes no virtual decimation");
+    } else if (cfg->data_loss == IRS_DATA_NGF) {
+        // (lcc_s is not read; weight and the two edge parameters travel through irs_ngf_set)
+        if (cfg->virtual_decimation != 0) return fail("irs_create: the NGF data term takes no virtual decimation");
     } else if (!(cfg->ssd_sigma > 0.0f)) return fail("irs_create: ssd_sigma must be positive");
     if (cfg->reg_loss < IRS_REG_L2 || cfg->reg_loss > IRS_REG_LOGNORMAL_L2) return fail("irs_create: unknown regulariser");
     if (cfg->diff_op != IRS_DIFF_GRADIENT && cfg->diff_op != IRS_DIFF_HESSIAN)
@@ -90,8 +93,10 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
 
     DevCfg& d = c->dcfg;
     d.K = cfg->data_loss == IRS_DATA_GMM_LCC ? cfg->gmm_components : 1;
-    // (the statistics and scalar stages of an LNCC or MI context only count the mask: to them it is an SSD context with 1 / sigma = 0)
-    d.mode = cfg->data_loss == IRS_DATA_LNCC || cfg->data_loss == IRS_DATA_MI ? IRS_DATA_SSD : cfg->data_loss;
+    // (the statistics and scalar stages of an LNCC, MI or NGF context only count the mask: to them it is an SSD context with
+    // 1 / sigma = 0)
+    d.mode = cfg->data_loss == IRS_DATA_LNCC || cfg->data_loss == IRS_DATA_MI || cfg->data_loss == IRS_DATA_NGF ? IRS_DATA_SSD
+                                                                                                                : cfg->data_loss;
     d.vd = cfg->virtual_decimation;
     d.C = C;
     d.gmm_lr_log_std = cfg->gmm_lr_log_std;
@@ -132,7 +137,11 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     c->nll_seg_C = (C > 1 && !sl && cfg->data_loss == IRS_DATA_GMM_LCC && c->kn.data_batch != 0) ? C : 1;
     const bool lncc = cfg->data_loss == IRS_DATA_LNCC;
     const bool mi = cfg->data_loss == IRS_DATA_MI;  // (its finish kernel writes the data term of a chain: one "partial" per chain)
-    c->nll_blocks = lncc ? lncc_geometry(D, H, W, cfg->lcc_s).blocks : mi ? 1 : data_bwd_blocks(cfg->data_loss, c->vol, c->nll_seg_C);
+    const bool ngf = cfg->data_loss == IRS_DATA_NGF;  // (the launch shape of the LNCC kernels at radius 1)
+    c->nll_blocks = lncc  ? lncc_geometry(D, H, W, cfg->lcc_s).blocks
+                    : ngf ? lncc_geometry(D, H, W, 1).blocks
+                    : mi  ? 1
+                          : data_bwd_blocks(cfg->data_loss, c->vol, c->nll_seg_C);
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
     const size_t o_steps = take(fieldI * cfg->no_steps);
@@ -147,6 +156,7 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     const size_t o_warped = take(imageI), o_z = take(imageI), o_sig = take(imageI), o_fhat = take(imageI), o_gM = take(imageI);
     const size_t o_dense = take(c->ffd ? fieldI : 0);
     const size_t o_lncc = take(lncc ? 3 * imageI : 0);  // the coefficient maps p, q, t of the LNCC data term
+    const size_t o_ngf = take(ngf ? 3 * imageI : 0);    // the coefficient maps c_z, c_y, c_x of the NGF data term
     const size_t mi_cells = mi ? (size_t)C * cfg->lcc_s * cfg->lcc_s : 0;  // the MI data term: histograms, tables, statistics, counts
     const size_t o_mi_hist = take(mi_cells * sizeof(unsigned long long)), o_mi_table = take(mi_cells * sizeof(float));
     const size_t o_mi_stats = take(mi ? sizeof(double) * C * IRS_MI_STATS : 0);
@@ -189,6 +199,7 @@ int irs::create_ctx(const irs_config* cfg, const SlabInfo* sl, irs_ctx** out) {
     c->gM = (float*)(c->slab + o_gM);
     c->dense = c->ffd ? (float*)(c->slab + o_dense) : nullptr;
     c->lncc_coef = lncc ? (float*)(c->slab + o_lncc) : nullptr;
+    c->ngf_coef = ngf ? (float*)(c->slab + o_ngf) : nullptr;
     c->mi_hist = mi ? (unsigned long long*)(c->slab + o_mi_hist) : nullptr;
     c->mi_table = mi ? (float*)(c->slab + o_mi_table) : nullptr;
     c->mi_stats = mi ? (double*)(c->slab + o_mi_stats) : nullptr;
@@ -250,6 +261,8 @@ int irs::check_io(const irs_ctx* c, const irs_io* io, const char* who) {
     if (c->cfg.data_loss == IRS_DATA_GMM_LCC && !c->fixed_set) return fail("%s: call irs_set_fixed first", who);
     if (c->cfg.data_loss == IRS_DATA_MI && !c->mi_set)
         return fail("%s: the MI data term needs irs_mi_set(ctx, weight, f_lo, f_hi, m_lo, m_hi) first: the library does not guess intensity ranges", who);
+    if (c->cfg.data_loss == IRS_DATA_NGF && !c->ngf_set)
+        return fail("%s: the NGF data term needs irs_ngf_set(ctx, weight, eps_f, eps_m) first: the library does not guess an edge parameter", who);
     return 0;
 }
 
@@ -422,6 +435,10 @@ static int forward_pass(irs_ctx* c, const irs_io* io, const float* v, bool with_
         launch_lncc_fwd(io->fixed_im, io->fixed_chains == 1 ? 0 : c->vol.V, warped, nullptr, 0, io->mask, io->mask_chains == 1 ? 0 : c->vol.V,
                         cfg.lcc_s, c->lncc_eps, (double)c->lncc_weight, z, c->lncc_coef, c->nll_partials, C,
                         lncc_geometry(c->vol.D, c->vol.H, c->vol.W, cfg.lcc_s), st);
+    else if (cfg.data_loss == IRS_DATA_NGF)  // mask * d into z, the coefficient maps for the adjoint, weight * sum mask * d per workgroup
+        launch_ngf_fwd(io->fixed_im, io->fixed_chains == 1 ? 0 : c->vol.V, warped, nullptr, 0, io->mask, io->mask_chains == 1 ? 0 : c->vol.V,
+                       c->ngf_eps_f, c->ngf_eps_m, (double)c->ngf_weight, true, z, c->ngf_coef, c->nll_partials, C,
+                       lncc_geometry(c->vol.D, c->vol.H, c->vol.W, 1), st);
     else if (cfg.data_loss == IRS_DATA_MI) {  // histogram -> table T and the data term of every chain (nll_blocks = 1)
         // (z is only written behind the statistics stage, by the gradient kernel: what that stage multiplies by 0 must be finite)
         if (io->residuals) HIP_TRY(hipMemsetAsync(z, 0, (size_t)C * c->vol.V * sizeof(float), st));
@@ -512,10 +529,11 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
     // to 8 planes in less than one resident set: lists could only match them, and the plan's launches would be a net cost there, as
     // for the adjoint below.
     const bool lcc = cfg.data_loss == IRS_DATA_GMM_LCC;
-    // LNCC: its window reads beyond the mask; MI: its histogram wants every masked voxel of the warped image -- no sparse data /
-    // forward stage for either
+    // LNCC: its window reads beyond the mask, and so does the stencil of NGF; MI: its histogram wants every masked voxel of the warped
+    // image -- no sparse data / forward stage for any of them
     const bool mi = cfg.data_loss == IRS_DATA_MI;
-    const bool lncc = cfg.data_loss == IRS_DATA_LNCC || mi;
+    const bool ngf = cfg.data_loss == IRS_DATA_NGF;
+    const bool lncc = cfg.data_loss == IRS_DATA_LNCC || mi || ngf;
     const int forced_piece = c->sparse_data > 1 ? c->sparse_data : 0;  // (tests: short pieces on small volumes)
     int data_on = 0;
     c->dplan.forced_len = forced_piece;
@@ -614,6 +632,8 @@ static int enqueue_transition(irs_ctx* c, const irs_io* io, hipStream_t st, int 
     else if (mi)  // every chain in one launch: the tables of the forward pass -> g_warped (and mask * (ln B - pmi) for the caller)
         launch_mi_bwd(io->fixed_im, io->fixed_chains == 1 ? 0 : vol.V, warped, io->mask, io->mask_chains == 1 ? 0 : vol.V, c->mi_table, vol.V, C,
                       c->mi_bins, c->mi_weight, nullptr, true, c->gM, io->residuals, st);
+    else if (ngf)  // every chain in one launch: weight * grad^T of the coefficient maps of the forward pass -> g_warped
+        launch_ngf_bwd(c->ngf_coef, c->ngf_weight, c->gM, C, lncc_geometry(vol.D, vol.H, vol.W, 1), st);
     else if (lncc)  // every chain in one launch: the coefficient maps of the forward pass -> g_warped
         launch_lncc_bwd(io->fixed_im, io->fixed_chains == 1 ? 0 : vol.V, warped, c->lncc_coef, cfg.lcc_s, c->lncc_weight, c->gM, C,
                         lncc_geometry(vol.D, vol.H, vol.W, cfg.lcc_s), st);
@@ -840,6 +860,19 @@ int irs_mi_set(irs_ctx* c, float weight, float f_lo, float f_hi, float m_lo, flo
     c->mi_bins = bn;
     c->mi_weight = weight;
     c->mi_set = true;
+    return 0;
+}
+
+int irs_ngf_set(irs_ctx* c, float weight, float eps_f, float eps_m) {
+    if (!c) return fail("irs_ngf_set: null argument");
+    if (c->cfg.data_loss != IRS_DATA_NGF) return fail("irs_ngf_set: the context's data loss is not IRS_DATA_NGF");
+    if (!positive_finite(weight) || !positive_finite(eps_f) || !positive_finite(eps_m))
+        return fail("irs_ngf_set: weight = %g, eps_f = %g, eps_m = %g, finite values > 0 needed", (double)weight, (double)eps_f, (double)eps_m);
+    if (c->n_enqueued > 0 || c->have_last_io) return fail("irs_ngf_set: weight and edge parameters may be set only before the first transition");
+    c->ngf_weight = weight;
+    c->ngf_eps_f = eps_f;
+    c->ngf_eps_m = eps_m;
+    c->ngf_set = true;
     return 0;
 }
 

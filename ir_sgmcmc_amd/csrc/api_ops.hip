@@ -367,6 +367,34 @@ int irs_lncc_bwd(const float* fixed, int Cf, const float* moving, const float* c
     return 0;
 }
 
+// the NGF data term (ngf_kernels.hip)
+int irs_ngf_fwd(const float* fixed, int Cf, const float* moving, const float* upstream, int Cu, float eps_f, float eps_m, float* d,
+                float* coef, double* sums, double* partials, int C, int D, int H, int W, void* stream) {
+    if (!fixed || !moving || !dims_ok(C, D, H, W) || (sums && !partials)) return fail("irs_ngf_fwd: bad arguments");
+    if (!chains_ok("irs_ngf_fwd", C)) return 1;
+    if (!broadcast_ok(Cf, C)) return fail("irs_ngf_fwd: fixed image of %d chains, 1 or %d needed", Cf, C);
+    if (upstream && !broadcast_ok(Cu, C)) return fail("irs_ngf_fwd: upstream of %d chains, 1 or %d needed", Cu, C);
+    if (!positive_finite(eps_f) || !positive_finite(eps_m))
+        return fail("irs_ngf_fwd: eps_f = %g, eps_m = %g, finite values > 0 needed", (double)eps_f, (double)eps_m);
+    if ((d && (d == fixed || d == moving || d == upstream)) || (coef && (coef == fixed || coef == moving || coef == upstream || coef == d)))
+        return fail("irs_ngf_fwd: an output must not be an input or the other output");
+    const int64_t V = (int64_t)D * H * W;
+    const LnccGeom g = lncc_geometry(D, H, W, 1);
+    launch_ngf_fwd(fixed, Cf == 1 ? 0 : V, moving, upstream, Cu == 1 ? 0 : V, nullptr, 0, eps_f, eps_m, 1.0, false, d, coef,
+                   sums ? partials : nullptr, C, g, (hipStream_t)stream);
+    if (sums) launch_reduce_partials(partials, g.blocks, C, sums, (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int irs_ngf_bwd(const float* coef, float* g_moving, int C, int D, int H, int W, void* stream) {
+    if (!coef || !g_moving || g_moving == coef || !dims_ok(C, D, H, W)) return fail("irs_ngf_bwd: bad arguments");
+    if (!chains_ok("irs_ngf_bwd", C)) return 1;
+    launch_ngf_bwd(coef, 1.0f, g_moving, C, lncc_geometry(D, H, W, 1), (hipStream_t)stream);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 // the mutual-information data term (mi_kernels.hip)
 static bool mi_chains_ok(const char* who, int Cf, const uint8_t* mask, int Cm, int C) {
     if (!chains_ok(who, C)) return false;

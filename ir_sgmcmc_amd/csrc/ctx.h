@@ -71,6 +71,11 @@ struct irs_ctx {
     bool sghmc = false;
     float sghmc_friction = 1.0f, sghmc_temperature = 1.0f;
     float* sghmc_m = nullptr;  // (C,3,Dv,Hv,Wv), the caller's
+    // IRS_DATA_NGF (ngf_kernels.hip): (C,3,V) coefficient maps c_z, c_y, c_x, forward kernel -> adjoint kernel; weight and the two
+    // edge parameters from irs_ngf_set, without which no transition runs
+    float* ngf_coef = nullptr;
+    float ngf_weight = 1.0f, ngf_eps_f = 0.0f, ngf_eps_m = 0.0f;
+    bool ngf_set = false;
     unsigned* dmax;  // [no_steps + 1][C][4] max |d_k| in voxels per axis (float bits), by-product of the forward steps
     irs::AdjointPlan plan;  // sparse adjoint plan (adjoint_plan.hip); no buffers on a slab context
     bool sparse_adjoint = true;  // irs_sparse_adjoint_set: the adjoint steps walk the plan's lists (false: full columns)

@@ -528,6 +528,17 @@ void launch_mi_bwd(const float* fixed, int64_t fixed_stride, const float* moving
                    const float* table, int64_t V, int C, const MiBins& bn, float weight, const float* scale, bool residual_form,
                    float* g, float* pmi, hipStream_t st);
 
+// ---- ngf_kernels.hip: the NGF data term (normalised gradient field distance) and its adjoint; arithmetic in ngf_device.h.  The
+// launch shape is lncc_geometry(D, H, W, 1).
+// fixed (1 or C,V) with fixed_stride 0 or V; moving (C,V); u = upstream (float, stride 0 or V) if given, else mask (uint8, stride 0
+// or V) if given, else 1.  d (C,V; u d with weighted_map), coef (C,3,V: c_z, c_y, c_x) and partials ([C][g.blocks] doubles of
+// scale * sum u d) may each be nullptr.
+void launch_ngf_fwd(const float* fixed, int64_t fixed_stride, const float* moving, const float* upstream, int64_t upstream_stride,
+                    const uint8_t* mask, int64_t mask_stride, float eps_f, float eps_m, double scale, bool weighted_map, float* d,
+                    float* coef, double* partials, int C, const LnccGeom& g, hipStream_t st);
+// g_moving (C,V) = scale * grad^T c from the coefficient maps of the forward launch
+void launch_ngf_bwd(const float* coef, float scale, float* g_moving, int C, const LnccGeom& g, hipStream_t st);
+
 // ---- residual_kernels.hip: the residuals against the mixture that models them -- histogram, moments and the per-voxel NLL
 struct ResBins {
     int bins;

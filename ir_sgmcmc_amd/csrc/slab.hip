@@ -862,6 +862,8 @@ int irs_slab_create(const irs_config* cfg, const irs_slab_config* scfg, irs_comm
         return fail("irs_slab_create: the LNCC data term is not supported on z-slabs (its window and its adjoint need a halo of 2 radius planes): data_loss must be GMM or SSD");
     if (cfg->data_loss == IRS_DATA_MI)
         return fail("irs_slab_create: the MI data term is not supported on z-slabs (the joint histogram of a chain would need an all-reduce between its accumulate and finish kernels): data_loss must be GMM or SSD");
+    if (cfg->data_loss == IRS_DATA_NGF)
+        return fail("irs_slab_create: the NGF data term is not supported on z-slabs (its stencil and its adjoint need a halo of two planes of the warped image): data_loss must be GMM or SSD");
     SlabInfo s;
     if (plan_layout(cfg, scfg, rank, world, &s)) return 1;
     const int ls = cfg->data_loss == IRS_DATA_GMM_LCC ? cfg->lcc_s : 0;

@@ -9,9 +9,10 @@ class SyntheticDataLoader:
     """deterministic Gaussian-blob pair; the reference ships no image data"""
 
     def __init__(self, dims, sigma_v_init=0.5, u_v_init=0.1, cps=None, save_dirs=None, seed=0, misalign=None, moving_contrast=None,
-                 **_unused):
+                 moving_bias=None, **_unused):
         self.dims = tuple(dims)
         self.misalign = misalign  # synthetic_pair: the moving triple rotated and shifted on the host (None: as generated)
+        self.moving_bias = moving_bias  # synthetic_pair: None | a, the moving image times exp(a z_n)
         self.moving_contrast = moving_contrast  # synthetic_pair: None | "invert" | "fold", the moving image in another contrast
         self.cps = tuple(cps) if cps else None
         self.save_dirs = save_dirs
@@ -29,7 +30,8 @@ class SyntheticDataLoader:
         return 1
 
     def __iter__(self):
-        fixed, moving = synthetic_pair(self.dims, seed=self.seed, misalign=self.misalign, moving_contrast=self.moving_contrast)
+        fixed, moving = synthetic_pair(self.dims, seed=self.seed, misalign=self.misalign, moving_contrast=self.moving_contrast,
+                                       moving_bias=self.moving_bias)
         fixed = {k: v.unsqueeze(0) for k, v in fixed.items()}
         moving = {k: v.unsqueeze(0) for k, v in moving.items()}
         vp = {k: v.unsqueeze(0) for k, v in init_var_params(self.dims_v, self.sigma_v_init, self.u_v_init).items()}

@@ -66,18 +66,31 @@ def moving_contrast_map(im, kind):
     return 4.0 * s * (1.0 - s)
 
 
-def synthetic_pair(dims, seed=0, noise=0.02, misalign=None, moving_contrast=None):
+def moving_bias_field(im, a):
+    """a smooth intensity inhomogeneity for the moving image (bias field, coil shading): m <- m exp(a z_n), z_n the normalised
+    first coordinate in [-1, 1]"""
+    if isinstance(a, bool) or not isinstance(a, (int, float)) or not math.isfinite(a):
+        raise ValueError(f'moving_bias {a!r}: null or a finite number')
+    z, _, _ = _coords(tuple(im.shape))
+    return im * torch.exp(float(a) * z)
+
+
+def synthetic_pair(dims, seed=0, noise=0.02, misalign=None, moving_contrast=None, moving_bias=None):
     """Two Gaussian blobs + white noise; the moving image has both blobs shifted.  Returns (fixed, moving).
     misalign: None (the pair as it always was), or {"rotation_deg": [a0, a1, a2], "shift": [s0, s1, s2]}: the moving triple
     is then rotated and shifted on the host (misalign_triple).
     moving_contrast: None (the pair as it always was), "invert" or "fold" (moving_contrast_map): the moving image in another
-    contrast, which only a mutual-information data term registers."""
+    contrast, which only a mutual-information data term registers.
+    moving_bias: None (the pair as it always was), or a number a: the moving image is then multiplied by exp(a z_n) after
+    moving_contrast (moving_bias_field), an inhomogeneity that spreads one tissue over many bins of a global histogram."""
     dims = tuple(int(d) for d in dims)
     g = torch.Generator().manual_seed(seed)
     im_f = _blobs(dims, (0.0, 0.0, 0.0), (0.0, 0.0, 0.0)) + noise * torch.randn(dims, generator=g)
     im_m = _blobs(dims, (0.08, -0.04, 0.05), (0.06, 0.05, 0.02)) + noise * torch.randn(dims, generator=g)
     if moving_contrast is not None:
         im_m = moving_contrast_map(im_m, moving_contrast)
+    if moving_bias is not None:
+        im_m = moving_bias_field(im_m, moving_bias)
     z, y, x = _coords(dims)
     r2 = z ** 2 + y ** 2 + x ** 2
     mask = (r2 < 0.9).expand(dims)

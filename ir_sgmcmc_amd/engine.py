@@ -28,7 +28,7 @@ class EngineConfig:
     lr: float = 0.4                                       # optimizer_SG_MCMC.args.lr
     uniform_noise: float = 0.1                            # trainer.uniform_noise.magnitude (0 = disabled)
     virtual_decimation: bool = True
-    data_loss: str = 'GMM'                                # 'GMM' (reference) | 'SSD' (builder-defined) | 'LNCC' (lcc_s = window radius) | 'MI'
+    data_loss: str = 'GMM'                                # 'GMM' (reference) | 'SSD' (builder-defined) | 'LNCC' (lcc_s = window radius) | 'MI' | 'NGF'
     gmm_components: int = 4
     lcc_s: int = 1
     ssd_sigma: float = 0.1
@@ -38,6 +38,9 @@ class EngineConfig:
     mi_weight: float = 1.0
     mi_fixed_range: Optional[Tuple[float, float]] = None  # (lo, hi) of the two images; while either is None the engine waits for
     mi_moving_range: Optional[Tuple[float, float]] = None  # mi_set, and refuses a transition before it: no range is guessed
+    ngf_weight: float = 1.0                               # 'NGF': data term = ngf_weight * sum mask * d (ngf.py); lcc_s is not read
+    ngf_fixed_eps: Optional[float] = None                 # the two edge parameters; while either is None the engine waits for
+    ngf_moving_eps: Optional[float] = None                # ngf_set, and refuses a transition before it: no eps is guessed
     gmm_lr_log_std: float = 0.2
     gmm_lr_logits: float = 0.2
     gmm_lr_decay: float = 0.001
@@ -73,7 +76,7 @@ def lognormal_init(w_reg, dof, nu=1.0):
     return loc, math.log(4.0) + math.log(loc)
 
 
-DATA_LOSSES = {'GMM': L.IRS_DATA_GMM_LCC, 'SSD': L.IRS_DATA_SSD, 'LNCC': L.IRS_DATA_LNCC, 'MI': L.IRS_DATA_MI}
+DATA_LOSSES = {'GMM': L.IRS_DATA_GMM_LCC, 'SSD': L.IRS_DATA_SSD, 'LNCC': L.IRS_DATA_LNCC, 'MI': L.IRS_DATA_MI, 'NGF': L.IRS_DATA_NGF}
 DIFF_OPS = {'GradientOperator': L.IRS_DIFF_GRADIENT, 'HessianOperator': L.IRS_DIFF_HESSIAN}
 
 
@@ -151,6 +154,8 @@ class TransitionEngine:
             self.lncc_set(cfg.lncc_weight, cfg.lncc_eps)
         if cfg.data_loss == 'MI' and cfg.mi_fixed_range is not None and cfg.mi_moving_range is not None:
             self.mi_set(cfg.mi_weight, cfg.mi_fixed_range, cfg.mi_moving_range)
+        if cfg.data_loss == 'NGF' and cfg.ngf_fixed_eps is not None and cfg.ngf_moving_eps is not None:
+            self.ngf_set(cfg.ngf_weight, cfg.ngf_fixed_eps, cfg.ngf_moving_eps)
         # SGHMC: the momentum lives here, bound to the context before its first transition (irs_config has no room for the sampler)
         if cfg.sampler not in ('SGLD', 'SGHMC'):
             raise ValueError(f'sampler {cfg.sampler!r}: one of SGLD, SGHMC')
@@ -174,6 +179,10 @@ class TransitionEngine:
     def lncc_set(self, weight, eps):
         """irs_lncc_set: weight and eps of the LNCC data term; only before the first transition"""
         L.check(self.lib.irs_lncc_set(self._ctx, float(weight), float(eps)))
+
+    def ngf_set(self, weight, fixed_eps, moving_eps):
+        """irs_ngf_set: weight and the two edge parameters of the NGF data term; required, and only before the first transition"""
+        L.check(self.lib.irs_ngf_set(self._ctx, float(weight), float(fixed_eps), float(moving_eps)))
 
     def mi_set(self, weight, fixed_range, moving_range):
         """irs_mi_set: weight and the two intensity ranges (lo, hi) of the MI data term; required, and only before the first

@@ -17,6 +17,7 @@ from . import distributions as model_distr
 from .. import bending as _bending
 from .. import lncc as _lncc
 from .. import mi as _mi
+from .. import ngf as _ngf
 from .. import ops as _ops
 from ..utils.diff_op import DifferentialOperator, GradientOperator, HessianOperator
 
@@ -151,6 +152,54 @@ class LNCC(DataLoss):
         if im_fixed.dim() == 5 and im_fixed.shape[0] > 1 and im_fixed.stride(0) == 0:
             im_fixed = im_fixed[:1]
         return _LNCCMap.apply(im_fixed.contiguous(), im_moving.contiguous(), self.radius, self.eps)
+
+    def forward(self, z):
+        return self.weight * z.sum()
+
+
+class _NGFMap(torch.autograd.Function):
+    """the NGF distance map d of the two images; backward runs both HIP operators with the incoming gradient as the upstream weight"""
+
+    @staticmethod
+    def forward(ctx, im_fixed, im_moving, eps_f, eps_m):
+        if im_fixed.requires_grad:
+            raise NotImplementedError('NGF.map differentiates with respect to the moving image only: the fixed image must not require a '
+                                      'gradient (it would silently receive none)')
+        ctx.eps = eps_f, eps_m
+        ctx.save_for_backward(im_fixed, im_moving)
+        return _ngf.ngf_forward(im_fixed, im_moving, eps_f, eps_m, want_coef=False, want_sums=False)['d']
+
+    @staticmethod
+    def backward(ctx, g_d):
+        im_fixed, im_moving = ctx.saved_tensors
+        coef = _ngf.ngf_forward(im_fixed, im_moving, *ctx.eps, upstream=g_d.contiguous(), want_map=False, want_sums=False)['coef']
+        return None, _ngf.ngf_backward(coef), None, None
+
+
+class NGF(DataLoss):
+    """normalised gradient field distance (Haber & Modersitzki 2006): map = 1 - (grad F . grad M)^2 / ((|grad F|^2 + fixed_eps^2)
+    (|grad M|^2 + moving_eps^2)), loss = weight * sum map.  It compares the direction of the image gradients only, and not their
+    sign: local, and free of a common contrast.  fixed_eps / moving_eps: the edge parameters, or None for `found_eps` -- the pair a
+    caller computed once for the images at hand, as the trainer does -- and, without that, the mean of |grad I| over the whole
+    volume of the images of the call (`ngf.ngf_edge_parameters`; a constant, not differentiated).  The gradient is with respect to
+    the moving image only; a fixed image that requires one is refused.  No counterpart in the reference."""
+
+    def __init__(self, weight=1.0, fixed_eps=None, moving_eps=None):
+        super().__init__()
+        self.weight = float(weight)
+        self.fixed_eps = None if fixed_eps is None else float(fixed_eps)
+        self.moving_eps = None if moving_eps is None else float(moving_eps)
+        self.found_eps = None   # (eps_f, eps_m) computed for the pair at hand, used where the two above are None
+        self.no_components = 1
+
+    def map(self, im_fixed, im_moving):
+        if im_fixed.dim() == 5 and im_fixed.shape[0] > 1 and im_fixed.stride(0) == 0:
+            im_fixed = im_fixed[:1]
+        eps_f, eps_m = self.fixed_eps, self.moving_eps
+        if eps_f is None or eps_m is None:
+            found = self.found_eps or _ngf.ngf_edge_parameters(im_fixed.detach(), im_moving.detach())
+            eps_f, eps_m = found[0] if eps_f is None else eps_f, found[1] if eps_m is None else eps_m
+        return _NGFMap.apply(im_fixed.contiguous(), im_moving.contiguous(), eps_f, eps_m)
 
     def forward(self, z):
         return self.weight * z.sum()

@@ -219,6 +219,9 @@ class SlabEngine(TransitionEngine):
                              'an all-reduce between its accumulate and finish kernels): data_loss must be GMM or SSD')
         if cfg.sampler != 'SGLD':
             raise L.IrsError(f'irs_sghmc_set: a z-slab context keeps the reference\'s update: sampler must be SGLD, got {cfg.sampler!r}')
+        if cfg.data_loss == 'NGF':
+            raise L.IrsError('irs_slab_create: the NGF data term is not supported on z-slabs (its stencil and its adjoint need a halo of '
+                             'two planes of the warped image): data_loss must be GMM or SSD')
         self._scfg = L.IrsSlabConfig(ghost_max, margin)
         super().__init__(cfg, device)
         lay = L.IrsSlabLayout()

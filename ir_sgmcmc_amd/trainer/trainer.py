@@ -42,7 +42,7 @@ from ..logger import (save_displacement_covariance, save_displacement_mean_and_s
                       save_posterior_comparison, save_precond_sigma,
                       save_residual_histogram, save_residual_nll, save_rhat, save_sample, save_structure_report, save_surface_posterior,
                       save_truth_calibration)
-from .. import affine, bspline, image_posterior, mi, multires, preconditioner, residual_check, sghmc, structure_report
+from .. import affine, bspline, image_posterior, mi, multires, ngf, preconditioner, residual_check, sghmc, structure_report
 from .. import truth as truth_ops
 from .. import masks as mask_ops  # (`masks` names the pair of masks in several methods below)
 from ..multires import coarse_start_options
@@ -71,6 +71,26 @@ def mi_refusals(virtual_decimation, residual_options, vi):
     if vi:
         raise ValueError('the VI stage composes data_loss.map and data_loss.reduce, and MI is no per-voxel map followed by a masked sum: '
                          'set trainer."VI" to false with the MI data loss')
+
+
+def ngf_refusals(virtual_decimation, residual_options):
+    """what a run with the NGF data loss cannot be combined with, each refused with its reason"""
+    if virtual_decimation:
+        raise ValueError('the NGF data loss takes no virtual decimation (its map is no residual whose correlation could be estimated): '
+                         'set "virtual_decimation" to false')
+    if residual_options is not None:
+        raise ValueError('trainer.residual_check compares the residuals with the Gaussian mixture: it needs the GMM data loss, not NGF')
+
+
+ENGINE_DATA_LOSSES = ('GMM', 'SSD', 'LNCC', 'MI', 'NGF')
+
+
+def engine_data_loss(kind):
+    """the EngineConfig.data_loss of a data-loss class name; a class the fused transition does not know is refused (it used to run
+    as SSD, silently)"""
+    if kind not in ENGINE_DATA_LOSSES:
+        raise ValueError(f'data_loss.type {kind!r} is not wired into the fused transition: one of {list(ENGINE_DATA_LOSSES)}')
+    return kind
 
 
 class LazyScalar:
@@ -360,7 +380,7 @@ class Trainer(VIMixin, BaseTrainer):
                   no_steps=getattr(self.transformation_module, 'no_steps', 12), sobolev_s=self.Sobolev_s,
                   sobolev_lambda=self.Sobolev_lambda, lr=float(cfg['optimizer_SG_MCMC']['args']['lr']),
                   uniform_noise=float(self.alpha), virtual_decimation=bool(self.virutal_decimation),
-                  data_loss=kind if kind in ('GMM', 'LNCC', 'MI') else 'SSD', seed=int(cfg['trainer'].get('seed', 0)))
+                  data_loss=engine_data_loss(kind), seed=int(cfg['trainer'].get('seed', 0)))
         if cfg['optimizer_SG_MCMC']['type'] != 'SGD':
             raise NotImplementedError('the SG-MCMC field update is plain SGD (reference configs), got ' + cfg['optimizer_SG_MCMC']['type'])
         if kind == 'GMM':
@@ -385,6 +405,13 @@ class Trainer(VIMixin, BaseTrainer):
             found = getattr(self, '_mi_ranges', None) or (None, None)
             ec.update(mi_bins=data_loss.bins, mi_weight=data_loss.weight, mi_fixed_range=data_loss.fixed_range or found[0],
                       mi_moving_range=data_loss.moving_range or found[1])
+        elif kind == 'NGF':
+            ngf_refusals(self.virutal_decimation, self.residual_options)
+            # (the edge parameters: the loss object's, else what _engine_init found on the pair it hands the chains; until then None,
+            # and an engine built from this config waits for ngf_set)
+            found = getattr(self, '_ngf_eps', None) or (None, None)
+            ec.update(ngf_weight=data_loss.weight, ngf_fixed_eps=data_loss.fixed_eps or found[0],
+                      ngf_moving_eps=data_loss.moving_eps or found[1])
         else:
             ec.update(ssd_sigma=data_loss.sigma)
         rname = type(reg_loss).__name__
@@ -418,7 +445,18 @@ class Trainer(VIMixin, BaseTrainer):
             # once, from the pair the chains get (after auto_mask, affine_init and truth): the fixed image under its mask, the moving
             # image over the whole volume
             self._mi_ranges = mi.mi_ranges(fixed['im'], moving['im'], fixed['mask'])
+        data_loss = self.losses['data']['loss']
+        if type(data_loss).__name__ == 'NGF':
+            # once, from the pair the chains get (after auto_mask, affine_init and truth): the mean of |grad I| of the fixed image under
+            # its mask and of the moving image under its own mask, where the pair has one.  The config's nulls stay null: the values
+            # found are this pair's (`found_eps` of the loss object, so that the VI stage runs with the same two), formed again for
+            # the next pair
+            self._ngf_eps = ngf.ngf_edge_parameters(fixed['im'], moving['im'], fixed.get('mask'), moving.get('mask'))
+            data_loss.found_eps = self._ngf_eps
         self.engine = TransitionEngine(self._engine_config(), self.device)
+        if self.engine.cfg.data_loss == 'NGF':
+            ec = self.engine.cfg
+            self.logger.info(f'NGF data term: weight {ec.ngf_weight:g}, fixed eps {ec.ngf_fixed_eps:.6g}, moving eps {ec.ngf_moving_eps:.6g}')
         if self.engine.cfg.data_loss == 'MI':
             ec = self.engine.cfg
             self.logger.info(f'MI data term: {ec.mi_bins} bins, weight {ec.mi_weight:g}, fixed range [{ec.mi_fixed_range[0]:.6g}, '
